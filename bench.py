@@ -97,6 +97,38 @@ def _pytorch_cpu_row(batch, nBottleneck, threads):
                 sample="%d iterations of the same nets and losses at batchSize=%d, %.1f s" % (n, batch, dt))
 
 
+DUMP_MAX_ELEMS = 4 << 20         # per array (16 MB of float32): three tensors + the losses stay below 64 MB
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(tr, losses, out_dir, meta):
+    """--dump-outputs: what the caller of one training step holds after the LAST timed step — the losses, netG's output
+    (logical NCHW) and the updated parametersG / parametersD in Torch7's getParameters() order (nn.Sequential.reference_flat,
+    independent of this build's padded layout).  A tensor of more than DUMP_MAX_ELEMS elements is replaced by a fixed sample of
+    its flattened elements: numpy default_rng(DUMP_SAMPLE_SEED).integers(0, numel, DUMP_MAX_ELEMS), sorted (the same indices
+    for the same shape on every run and build).  dump_manifest.json lists every array with its full shape and whether it was sampled."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    manifest = dict(meta, arrays={})
+    arrays = [(k, np.array([v], np.float64)) for k, v in losses.items() if v is not None]
+    for name, t in (("netG_output", tr.netG.output), ("parametersG", tr.netG.reference_flat()),
+                    ("parametersD", tr.netD.reference_flat())):
+        t = t.detach().float().contiguous()
+        entry = dict(shape=list(t.shape), sampled=False)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            entry.update(sampled=True, sample_elems=DUMP_MAX_ELEMS, sample_seed=DUMP_SAMPLE_SEED)
+        arrays.append((name, t.cpu().numpy()))
+        manifest["arrays"][name] = entry
+    for name, a in arrays:
+        manifest["arrays"].setdefault(name, dict(shape=list(a.shape), sampled=False))["dtype"] = str(a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    with open(os.path.join(out_dir, "dump_manifest.json"), "w") as fh:
+        json.dump(manifest, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -161,7 +193,12 @@ def main():
     ap.add_argument("--overlap", action="store_true", help="3 streams (dW beside dX, netG forward beside netD's real pass): measured "
                     "+0.7 %% on one GPU with the current kernels (noise level), so the default is one stream")
     ap.add_argument("--no-overlap", action="store_true", help="(default now; kept so that older command lines still parse)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last of them computed "
+                    "(losses as float64; netG's output and the updated parametersG / parametersD as float32, a fixed seeded sample of "
+                    "4 M elements where larger) to DIR/<name>.npy, with DIR/dump_manifest.json describing them (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.batch is None:
         args.batch = {"center": 64, "vid16": 16, "vid4": 16, "wholeim": 4}[args.workload]
     if args.nBottleneck is None:
@@ -306,10 +343,17 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         B.all_reduce(t, op="max")           # vf_comm_allreduce_inline (or torch.distributed in the gloo rehearsal)
         dt = float(t.item())
+    if args.dump_outputs:
+        # before any further step runs.  losses() on every rank: it flushes a deferred update, which may be a collective
+        # (and after which a graph that begins with that update must not be replayed: the step-stats pass is skipped then)
+        last = tr.losses()
+        if rank == 0:
+            dump_outputs(tr, last, args.dump_outputs, dict(workload=wl, mfma=args.mfma, host=args.host, n_gpus=world,
+                                                           steps=args.steps, warmup=args.warmup))
     # per-step distribution (median and p10/p90 over >= 100 iterations): a separate pass after the timed
     # region, one event pair per step on the launch stream, nothing synchronises inside it
     step_stats = None
-    if rank == 0 and world == 1 and args.step_stats > 0:
+    if rank == 0 and world == 1 and args.step_stats > 0 and not tr._graph_stale:
         nd = args.step_stats
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(nd + 1)]
         evs[0].record()
