@@ -353,6 +353,36 @@ int vf_tiles_gather(vf_ctx* ctx, const float* full, float* tiles, int groups, in
 int vf_tiles_scatter(vf_ctx* ctx, const float* tiles, float* out, int groups, int nc, int H, int W, int fs,
                      const unsigned char* vflip);
 
+/* ---- Torch7 image.scale (bilinear) and the loaders built on it (vf_image.hip) --------------------
+ * Bit-identical to the float32 restatement of image.c's scaleBilinear: rows first (W -> width), then columns
+ * (H -> height), one rounding per operation.  src_layout 0: float planar N x C x H x W; src_layout 1: decoded uint8
+ * N x H x W x C (interleaved, as decoders return it), read as b / 255 in float (image.load(path, nc, 'float')).
+ * Sides must lie in [1, 65535].
+ * vf_image_scale: image.scale of N frames of one size into float planar N x C x height x width. */
+int vf_image_scale(vf_ctx* ctx, const void* src, int src_layout, float* dst, int N, int C, int H, int W, int height,
+                   int width);
+/* The Byte path (masks): uint8 planar N x C x H x W -> uint8 planar N x C x height x width; the intermediate row pass
+ * and the result are rounded through image.c's FromIntermediate (+0.5, clamp to [0, 255], truncate). */
+int vf_image_scale_u8(vf_ctx* ctx, const unsigned char* src, unsigned char* dst, int N, int C, int H, int W, int height,
+                      int width);
+/* data/donkey_folder.lua:40-88 (trainHook of train.lua's loader) for ONE image: image.scale to height x width, crop
+ * fs x fs at the 0-based corner (w1, h1) of the scaled image, mirror horizontally if flip, map [0,1] -> [-1,1]
+ * (mul(2):add(-1)); out: C x fs x fs planar (one row of the B x C x fs x fs loader batch).  Only the crop's pixels
+ * are evaluated; the scaled image is never stored. */
+int vf_image_hook2d(vf_ctx* ctx, const void* src, int src_layout, float* out, int C, int H, int W, int height, int width,
+                    int fs, int w1, int h1, int flip);
+/* test_vid_wholeim.lua:109-141 (loadImages): image.scale of N frames to height x width, pixels where fill_mask (DEVICE
+ * uint8 C x height x width, shared by the frames, non-zero = masked; or NULL) is set replaced by fill_value
+ * (maskedFill), zero-padded bottom-right to outh x outw, then mul(2):add(-1) over the whole padded frame (padding
+ * becomes -1).  out: float planar N x C x outh x outw. */
+int vf_image_whole_frames(vf_ctx* ctx, const void* src, int src_layout, float* out, int N, int C, int H, int W, int height,
+                          int width, int outh, int outw, const unsigned char* fill_mask, float fill_value);
+/* datavid/donkey_folder.lua:148,165 on the device clip (C x iH x iW planar float) and the Byte mask (iH x iW uint8, or
+ * NULL): out (DEVICE double[2]) = {sum of the fs x fs crop at 0-based (w1, h1) over all C channels, accumulated in
+ * double; max of the same crop of the mask}.  One block, fixed order: deterministic. */
+int vf_crop_stats(vf_ctx* ctx, const float* clip, const unsigned char* mask, int C, int iH, int iW, int fs, int w1, int h1,
+                  double* out);
+
 /* ---- option branches of train.lua: noiseGen (:109-124, 319-327) and conditionAdv (:158-180) -----------------------
  * nn.JoinTable(2) over NHWC tensors: dst[p][c_dst + c] = src[p][c_src + c] for c < Ccopy, p < npix (forward: one call
  * per table element into the joined tensor; updateGradInput: one call per element out of the joined gradient).

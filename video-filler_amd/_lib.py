@@ -79,6 +79,11 @@ SIGNATURES = {
     "vf_clip_prepare": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp]),
     "vf_tiles_gather": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "vf_tiles_scatter": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "vf_image_scale": (i32, [vp, vp, i32, vp] + [i32] * 6),
+    "vf_image_scale_u8": (i32, [vp, vp, vp] + [i32] * 6),
+    "vf_image_hook2d": (i32, [vp, vp, i32, vp] + [i32] * 9),
+    "vf_image_whole_frames": (i32, [vp, vp, i32, vp] + [i32] * 8 + [vp, f32]),
+    "vf_crop_stats": (i32, [vp, vp, vp] + [i32] * 6 + [vp]),
     "vf_channel_copy": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, i64]),
     "vf_noise_fill": (i32, [vp, vp, i64, u64, vp, u64, i32]),
     "vf_bce_fwd": (i32, [vp, vp, f32, i32, vp]),

@@ -733,6 +733,50 @@ class HipBackend:
         self._c("vf_tiles_scatter", _ptr(tiles), _ptr(out), groups, Ct // groups, H, W, fs,
                 _ptr(vflip) if vflip is not None else None)
 
+    # ---- Torch7 image.scale and the loaders on it (vf_image.hip).  Frames: hwc -> uint8 N x H x W x C, else float N x C x H x W
+    def image_scale(self, src, hwc, dst):
+        """image.scale of N frames into dst (float N x C x h x w, contiguous)."""
+        N, Cc, h, w = dst.shape
+        H, W = (src.shape[1], src.shape[2]) if hwc else (src.shape[2], src.shape[3])
+        assert src.is_contiguous() and dst.is_contiguous() and src.dtype == (torch.uint8 if hwc else torch.float32)
+        assert src.shape[0] == N and (src.shape[3] if hwc else src.shape[1]) == Cc
+        self._c("vf_image_scale", _ptr(src), 1 if hwc else 0, _ptr(dst), N, Cc, H, W, h, w)
+
+    def image_scale_u8(self, src, dst):
+        """the Byte path: uint8 N x C x H x W -> uint8 N x C x h x w."""
+        assert src.is_contiguous() and dst.is_contiguous() and src.dtype == dst.dtype == torch.uint8
+        N, Cc, H, W = src.shape
+        assert tuple(dst.shape[:2]) == (N, Cc)
+        self._c("vf_image_scale_u8", _ptr(src), _ptr(dst), N, Cc, H, W, dst.shape[2], dst.shape[3])
+
+    def image_hook2d(self, src, hwc, out, height, width, w1, h1, flip):
+        """data/donkey_folder.lua:40-88 for one frame (src: 1 frame) into out (C x fs x fs planar, contiguous)."""
+        Cc, fs, _ = out.shape
+        H, W = (src.shape[1], src.shape[2]) if hwc else (src.shape[2], src.shape[3])
+        assert src.is_contiguous() and out.is_contiguous() and src.shape[0] == 1
+        assert src.dtype == (torch.uint8 if hwc else torch.float32) and (src.shape[3] if hwc else src.shape[1]) == Cc
+        self._c("vf_image_hook2d", _ptr(src), 1 if hwc else 0, _ptr(out), Cc, H, W, height, width, fs, w1, h1,
+                int(bool(flip)))
+
+    def image_whole_frames(self, src, hwc, out, height, width, fill_mask, fill_value):
+        """test_vid_wholeim.lua:109-141: out float N x C x outh x outw; fill_mask uint8 C x height x width or None."""
+        N, Cc, outh, outw = out.shape
+        H, W = (src.shape[1], src.shape[2]) if hwc else (src.shape[2], src.shape[3])
+        assert src.is_contiguous() and out.is_contiguous() and src.shape[0] == N
+        assert src.dtype == (torch.uint8 if hwc else torch.float32) and (src.shape[3] if hwc else src.shape[1]) == Cc
+        if fill_mask is not None:
+            assert fill_mask.is_contiguous() and fill_mask.dtype == torch.uint8 and tuple(fill_mask.shape) == (Cc, height, width)
+        self._c("vf_image_whole_frames", _ptr(src), 1 if hwc else 0, _ptr(out), N, Cc, H, W, height, width, outh, outw,
+                _ptr(fill_mask), fill_value)
+
+    def crop_stats(self, clip, mask, fs, w1, h1, out):
+        """out (float64[2], device) = (sum of clip[:, h1:h1+fs, w1:w1+fs], max of mask[h1:h1+fs, w1:w1+fs])."""
+        Cc, iH, iW = clip.shape
+        assert clip.is_contiguous() and clip.dtype == torch.float32 and out.dtype == torch.float64
+        if mask is not None:
+            assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (iH, iW)
+        self._c("vf_crop_stats", _ptr(clip), _ptr(mask), Cc, iH, iW, fs, w1, h1, _ptr(out))
+
     def channel_copy(self, src, c_src, dst, c_dst, ncopy):
         """dst[:, c_dst:c_dst+ncopy] = src[:, c_src:c_src+ncopy] on NHWC tensors of equal B, H, W (nn.JoinTable(2))."""
         Bn, Cs, H, W = src.shape

@@ -4,6 +4,9 @@ The reference prepares every sample on the host, inside the loader threads (data
 the top of the closure (train.lua:284-298), and then copies the batch to the GPU.  Here the host only decodes and
 draws the random numbers; cropping, masking, flipping, the [0,1] -> [-1,1] map and the NCHW -> NHWC conversion are one
 kernel per sample, writing straight into the batch buffers the closures read (`vf_clip_prepare`, `vf_center_prepare`).
+The resize before them — Torch7's image.scale in the loaders' loadImage / loadContImages — is on the device too
+(vf_image.hip): `image_scale`, `ImageBatcher` (train.lua's loader, one fused launch per image) and
+`ClipBatcher.add_frames` take decoded frames, so JPEG decode is the only host step left.
 """
 import math
 
@@ -13,6 +16,127 @@ import torch
 from .backend import get_backend, nhwc_empty
 
 CENTER_FILL = (117.0, 104.0, 123.0)      # train.lua:287-289
+
+
+# ---------------------------------------------------------------------------------------------- image.scale
+def load_size(H, W, loadSize, scalef=None):
+    """(height, width) that loadImage / loadContImages (data/donkey_folder.lua:40-62, datavid/donkey_folder.lua:84-102)
+    scale an H x W image to.  loadSize > 0: the shorter side becomes loadSize, the other keeps the aspect ratio
+    (Lua arithmetic in double, truncated by the tensor constructor).  loadSize < 0: `image.scale(input, iH, iW)` with
+    iH = scalef*H, iW = scalef*W — the reference passes the scaled HEIGHT as the width, so the aspect is transposed;
+    kept.  loadSize == 0: unchanged."""
+    if loadSize > 0:
+        if W < H:
+            return int(loadSize * H / W), int(loadSize)   # image.scale(input, loadSize, loadSize * iH / iW)
+        return int(loadSize), int(loadSize * W / H)       # image.scale(input, loadSize * iW / iH, loadSize)
+    if loadSize < 0:
+        assert scalef is not None, "loadSize < 0 needs the random scale factor (draw_scalef)"
+        return int(scalef * W), int(scalef * H)
+    return int(H), int(W)
+
+
+def draw_scalef(loadSize, rng):
+    """The random scale of loadSize < 0: uniform in [0.5, 1.5] for -1, in [1, 3] for any other negative value."""
+    return float(rng.uniform(0.5, 1.5)) if loadSize == -1 else float(rng.uniform(1, 3))
+
+
+def byte_mask(decoded):
+    """`image.load(maskName):byte()` of a decoded uint8 mask image: the [0,1] float image truncated to Byte, so only
+    255 becomes 1.  Host or device tensor / array in, uint8 tensor (same place) out."""
+    m = torch.as_tensor(decoded)
+    return (m == 255).to(torch.uint8)
+
+
+def _frames(x, hwc):
+    """(device tensor, N, C, H, W) of one frame or a stack: hwc -> uint8 [N x] H x W x C (a decoder's interleaved
+    output; H x W for one channel), else [N x] C x H x W planar."""
+    B = get_backend()
+    t = torch.as_tensor(x)
+    if hwc:
+        assert t.dtype == torch.uint8, "decoded frames are uint8 H x W x C"
+        if t.dim() == 2:
+            t = t.unsqueeze(-1)
+        t = t if t.dim() == 4 else t.unsqueeze(0)
+        N, H, W, C = t.shape
+    else:
+        t = t.float() if t.is_floating_point() else t
+        t = t if t.dim() == 4 else t.unsqueeze(0)
+        N, C, H, W = t.shape
+    return B.from_host(t).contiguous(), N, C, H, W
+
+
+def image_scale(x, width, height, layout="chw"):
+    """Torch7 `image.scale(x, width, height)` (bilinear; Torch7 argument order, fractional sizes truncated) on the
+    device, bit-identical to image.c's float32 arithmetic.  A leading frame axis resizes N frames in one launch.
+      float [N x] C x H x W                 -> float planar [N x] C x height x width (the Float path);
+      uint8 [N x] C x H x W                 -> uint8 (the Byte path: masks; intermediate rounded as a ByteTensor);
+      uint8 [N x] H x W x C, layout="hwc"   -> decoded frames read as b / 255 (image.load(path, nc, 'float')),
+                                               float planar [N x] C x height x width.
+    Host or device tensors in; device tensors out."""
+    B = get_backend()
+    width, height = int(width), int(height)
+    t = torch.as_tensor(x)
+    single = t.dim() in (2, 3) if layout == "hwc" else t.dim() == 3
+    if layout == "hwc":
+        src, N, C, H, W = _frames(t, True)
+        out = B.empty(N, C, height, width)
+        B.image_scale(src, True, out)
+    elif t.dtype == torch.uint8:
+        src, N, C, H, W = _frames(t, False)
+        out = B.empty(N, C, height, width, dtype=torch.uint8)
+        B.image_scale_u8(src, out)
+    else:
+        src, N, C, H, W = _frames(t, False)
+        out = B.empty(N, C, height, width)
+        B.image_scale(src, False, out)
+    return out[0] if single else out
+
+
+class ImageBatcher:
+    """train.lua's loader (data/donkey_folder.lua:40-88: loadImage + trainHook) feeding CenterTrainer.set_batch.
+
+    add(image) takes ONE decoded image (uint8 H x W x nc, or float nc x H x W in [0,1]; host or device), draws the
+    loader's random numbers from `rng` in its order (scalef when loadSize < 0, then h1, w1, flip) — they depend only
+    on the scaled SIZES — and launches one kernel that resizes, crops, flips and maps to [-1,1] straight into row `n`
+    of the B x nc x fineSize x fineSize batch, evaluating only the crop's pixels.  batch() returns that planar batch."""
+
+    def __init__(self, batchSize, nc=3, fineSize=128, loadSize=350, rng=None):
+        B = get_backend()
+        self.B, self.nc, self.fs, self.loadSize = batchSize, nc, fineSize, loadSize
+        self.rng = rng or np.random.default_rng()
+        self.out = B.empty(batchSize, nc, fineSize, fineSize)
+        self.n = 0
+
+    def draw(self, H, W):
+        """The loader's decisions for an H x W image: {height, width, h1, w1, flip} (0-based corner, clamped as in
+        ClipBatcher.draw)."""
+        fs, rng = self.fs, self.rng
+        scalef = draw_scalef(self.loadSize, rng) if self.loadSize < 0 else None
+        height, width = load_size(H, W, self.loadSize, scalef)
+        assert height >= fs and width >= fs, "the %dx%d scaled image is smaller than fineSize=%d" % (height, width, fs)
+        h1 = int(math.ceil(rng.uniform(1e-2, height - fs)))      # :76-77
+        w1 = int(math.ceil(rng.uniform(1e-2, width - fs)))
+        flip = bool(rng.uniform() > 0.5)                          # :82
+        return dict(height=height, width=width, h1=min(h1, height - fs), w1=min(w1, width - fs), flip=flip)
+
+    def add(self, image, decisions=None):
+        """Returns the decisions used."""
+        B = get_backend()
+        assert self.n < self.B, "batch is full"
+        t = torch.as_tensor(image)
+        hwc = t.dtype == torch.uint8
+        src, N, C, H, W = _frames(t, hwc)
+        assert N == 1 and C == self.nc, "one %d-channel image, got %d x %d channels" % (self.nc, N, C)
+        d = decisions if decisions is not None else self.draw(H, W)
+        B.image_hook2d(src, hwc, self.out[self.n], d["height"], d["width"], d["w1"], d["h1"], d["flip"])
+        self.n += 1
+        return d
+
+    def batch(self):
+        """B x nc x fineSize x fineSize planar in [-1,1] on the device (the loader's batch of train.lua:282)."""
+        assert self.n == self.B, "batch holds %d of %d samples" % (self.n, self.B)
+        self.n = 0
+        return self.out
 
 
 def center_prepare(batch, overlapPred, fill=CENTER_FILL, out=None):
@@ -54,20 +178,87 @@ class ClipBatcher:
 
     def draw(self, clip, mask):
         """The hook's decisions for one sample (host side, no pixels touched beyond two reductions)."""
-        fs, rng = self.fs, self.rng
+        fs = self.fs
         _, iH, iW = clip.shape
+        return self._decide(iH, iW, lambda h1, w1: (float(clip[:, h1:h1 + fs, w1:w1 + fs].mean()),
+                                                    mask[:, h1:h1 + fs, w1:w1 + fs].max()))
+
+    def _decide(self, iH, iW, crop_stats):
+        """The hook's draws in its order; crop_stats(h1, w1) -> (mean of the clip's crop, max of the mask's crop)."""
+        fs, rng = self.fs, self.rng
         h1 = int(math.ceil(rng.uniform(1e-2, iH - fs)))          # :145-146 (1-based corner; image.crop takes it 0-based)
         w1 = int(math.ceil(rng.uniform(1e-2, iW - fs)))
         h1, w1 = min(h1, iH - fs), min(w1, iW - fs)
-        crop = clip[:, h1:h1 + fs, w1:w1 + fs]
-        if float(crop.mean()) < 0.1 and rng.uniform() > 0.05:     # :148-153: dark crops are mostly rejected
+        crop_mean, mask_max = crop_stats(h1, w1)
+        if crop_mean < 0.1 and rng.uniform() > 0.05:              # :148-153: dark crops are mostly rejected
             return None
         blocks, bs = None, fs // 6
-        if not (mask[:, h1:h1 + fs, w1:w1 + fs].max() > 0.5):     # :165-169
+        if not (mask_max > 0.5):                                  # :165-169
             nBlocks = int(rng.integers(2, 11))                   # torch.random(2, maxBlocks)
             blocks = [(int(rng.integers(3, fs - bs - 1)), int(rng.integers(3, fs - bs - 1))) for _ in range(nBlocks)]
         flip = bool(rng.uniform() > 0.5)                          # :178
         return dict(w1=w1, h1=h1, flip=flip, blocks=blocks, blockSize=bs)
+
+    def set_mask(self, mask):
+        """The loader's module-global Byte mask (datavid/donkey_folder.lua:33-35; `byte_mask` makes it from a decoded
+        image): 0/1 uint8 [1 x] H x W.  add_frames rescales it in place of the old one on every call."""
+        m = torch.as_tensor(mask)
+        assert m.dtype == torch.uint8, "the mask is a ByteTensor (byte_mask)"
+        self.mask_state = get_backend().from_host(m.reshape(1, m.shape[-2], m.shape[-1])).contiguous()
+
+    mask_state = last = None
+
+    def add_frames(self, frames, loadSize=0, decisions=None):
+        """loadContImages + trainHook (datavid/donkey_folder.lua:71-189) on the device for ONE clip of decoded frames
+        (uint8 predLen x H x W x nc, or float predLen x nc x H x W in [0,1]; host or device).
+
+        Draws scalef (loadSize < 0), scales the channel-stacked clip (image.scale), and — as the reference does on
+        every call, rejected samples included — replaces the mask state by `image.scale(mask, W, H)` of the PREVIOUS
+        state on the Byte path (with loadSize < 0 it degrades from call to call, as in the reference).  Then the hook's
+        draws in its order, the dark-crop mean and the mask test read as one device pair (vf_crop_stats, summed in
+        double as TH's mean), and the clip_prepare launch of `add`.  Returns True unless the sample is rejected;
+        `last` holds the sizes and decisions (None if rejected)."""
+        B = get_backend()
+        assert self.n < self.B, "batch is full"
+        assert self.mask_state is not None, "set_mask() first: the video loader's mask is part of its state"
+        t = torch.as_tensor(frames)
+        hwc = t.dtype == torch.uint8
+        src, N, C, H, W = _frames(t, hwc)
+        assert N * C == self.C, "%d frames x %d channels do not make the batcher's %d channels" % (N, C, self.C)
+        scalef = None
+        if decisions is None and loadSize < 0:
+            scalef = draw_scalef(loadSize, self.rng)
+        if decisions is not None:
+            height, width = decisions["height"], decisions["width"]
+        else:
+            height, width = load_size(H, W, loadSize, scalef)
+        clip = B.empty(N * C, height, width)
+        B.image_scale(src, hwc, clip.view(N, C, height, width))
+        mask = B.empty(1, height, width, dtype=torch.uint8)
+        B.image_scale_u8(self.mask_state.unsqueeze(0), mask.unsqueeze(0))
+        self.mask_state = mask
+        fs = self.fs
+        if decisions is None:
+            assert height >= fs and width >= fs, "the %dx%d scaled clip is smaller than fineSize=%d" % (height, width, fs)
+
+            def crop_stats(h1, w1):
+                st = B.empty(2, dtype=torch.float64)
+                B.crop_stats(clip, mask[0], fs, w1, h1, st)
+                s, m = st.tolist()
+                return s / (C * N * fs * fs), m
+
+            d = self._decide(height, width, crop_stats)
+        else:
+            d = decisions
+        self.last = None if d is None else dict(d, height=height, width=width)
+        if d is None:
+            return False
+        mask_f = mask[0].float() if d["blocks"] is None else None
+        n = self.n
+        B.clip_prepare(clip, mask_f, self.full[n:n + 1], self.masked[n:n + 1], self.mask[n:n + 1], d["w1"], d["h1"],
+                       d["flip"], self.maskValue, d["blocks"], d["blockSize"])
+        self.n += 1
+        return True
 
     def add(self, clip, mask, decisions=None):
         B = get_backend()

@@ -5,6 +5,8 @@ whole-image loop — one net:forward per 128x128 tile in the reference (test_vid
 forward over all tiles: `vf_tiles_gather` builds the NHWC batch (incl. the script's vertical-flip rule for the first
 three tiles of the top row), `vf_tiles_scatter` writes the output tiles back into the planar frames.
 """
+import math
+
 import torch
 
 from .backend import get_backend, nhwc_empty
@@ -23,6 +25,44 @@ def predict_clip(net, input_image):
     B.scale_shift(out_in, 0.5, 0.5)
     B.scale_shift(out_pred, 0.5, 0.5)
     return out_in, out_pred
+
+
+def whole_frame_sizes(loadSize, fineSize=128):
+    """test_vid_wholeim.lua:109-111: (inh, inw, outh, outw) for frames of the script's 360 x 480 geometry.  inw =
+    loadSize * 480 / 360 is truncated by the tensor constructor; outw is computed from the UNtruncated value."""
+    inw = loadSize * 480 / 360
+    return int(loadSize), int(inw), math.ceil(loadSize / fineSize) * fineSize, math.ceil(inw / fineSize) * fineSize
+
+
+def load_whole_frames(frames, mask, loadSize=360, fineSize=128, maskValue=110.0 / 255.0):
+    """test_vid_wholeim.lua:109-141, 208-212 (loadImages and padmask) on the device: the (fullImages, padmask) that
+    WholeImageInpainter takes.
+
+    frames: predLen decoded frames, uint8 predLen x H x W x nc (or float predLen x nc x H x W in [0,1]); host or device.
+    mask: the Byte mask (`data.byte_mask` of the decoded mask image), 1 or nc x Hm x Wm (or Hm x Wm); expanded to nc
+    channels as the script does.  Every frame is scaled to inh x inw, maskedFill'ed with maskValue where the scaled
+    Byte mask is > 0.3 (`scMask`), zero-padded bottom-right to outh x outw and mapped by mul(2):add(-1) (padding
+    becomes -1): one launch for the whole clip.  The script's second image.scale to the same size is a copy and is
+    not repeated.  padmask is the scaled Byte mask, zero-padded the same way.  mid_mask stays the caller's (the
+    script's construction indexes the height axis with inw, :154-158).
+    Returns (fullImages (predLen*nc) x outh x outw float, padmask nc x outh x outw uint8), on the device."""
+    from .data import _frames
+    B = get_backend()
+    t = torch.as_tensor(frames)
+    hwc = t.dtype == torch.uint8
+    src, N, nc, H, W = _frames(t, hwc)
+    inh, inw, outh, outw = whole_frame_sizes(loadSize, fineSize)
+    m = torch.as_tensor(mask)
+    assert m.dtype == torch.uint8, "the mask is a ByteTensor (data.byte_mask)"
+    m = m.reshape(-1, m.shape[-2], m.shape[-1])
+    m = B.from_host(m.expand(nc, m.shape[1], m.shape[2])).contiguous()       # torch.expand(mask, 3, h, w):byte()
+    smask = B.empty(1, nc, inh, inw, dtype=torch.uint8)
+    B.image_scale_u8(m.unsqueeze(0), smask)
+    full = B.empty(N, nc, outh, outw)
+    B.image_whole_frames(src, hwc, full, inh, inw, smask[0], float(maskValue))
+    padmask = B.zeros(nc, outh, outw, dtype=torch.uint8)
+    padmask[:, :inh, :inw] = smask[0]
+    return full.view(N * nc, outh, outw), padmask
 
 
 class WholeImageInpainter:

@@ -136,6 +136,11 @@ int vf_center_prepare(vf_ctx*, const float* batch_nchw, float* ctx_nhwc, float* 
 int vf_clip_prepare(vf_ctx*, const float* clip, const float* mask, float* full, float* masked, float* maskout, int C, int iH, int iW, int fs, int w1, int h1, int flip, float mask_value, int nblocks, int block_size, const int* tlx, const int* tly);
 int vf_tiles_gather(vf_ctx*, const float* full, float* tiles, int groups, int nc, int H, int W, int fs, const unsigned char* vflip);
 int vf_tiles_scatter(vf_ctx*, const float* tiles, float* out, int groups, int nc, int H, int W, int fs, const unsigned char* vflip);
+int vf_image_scale(vf_ctx*, const void* src, int src_layout, float* dst, int N, int C, int H, int W, int height, int width);
+int vf_image_scale_u8(vf_ctx*, const unsigned char* src, unsigned char* dst, int N, int C, int H, int W, int height, int width);
+int vf_image_hook2d(vf_ctx*, const void* src, int src_layout, float* out, int C, int H, int W, int height, int width, int fs, int w1, int h1, int flip);
+int vf_image_whole_frames(vf_ctx*, const void* src, int src_layout, float* out, int N, int C, int H, int W, int height, int width, int outh, int outw, const unsigned char* fill_mask, float fill_value);
+int vf_crop_stats(vf_ctx*, const float* clip, const unsigned char* mask, int C, int iH, int iW, int fs, int w1, int h1, double* out);
 int vf_channel_copy(vf_ctx*, const float* src, int Csrc, int c_src, float* dst, int Cdst, int c_dst, int Ccopy, int64_t npix);
 int vf_noise_fill(vf_ctx*, float* out, int64_t n, uint64_t seed, const int32_t* counter_dev, uint64_t counter, int normal);
 ]]
