@@ -383,6 +383,38 @@ int vf_image_whole_frames(vf_ctx* ctx, const void* src, int src_layout, float* o
 int vf_crop_stats(vf_ctx* ctx, const float* clip, const unsigned char* mask, int C, int iH, int iW, int fs, int w1, int h1,
                   double* out);
 
+/* ---- baseline JPEG decode (vf_jpeg.hip) -------------------------------------------------------------
+ * image.load of data/donkey_folder.lua and datavid/donkey_folder.lua (libjpeg's default decompression) on the device,
+ * byte for byte: islow IDCT, fancy upsampling, ycc_rgb_convert.  Supported: SOF0 / SOF1, 8-bit samples, Huffman
+ * coding, ONE scan (interleaved for YCbCr), 1 component or 3 in YCbCr with luma sampling 1x1, 2x1 or 2x2 and chroma
+ * 1x1 (4:4:4, 4:2:2, 4:2:0), sides up to 16384, with or without restart intervals.  Everything else is unsupported.
+ * vf_jpeg_inspect (host only, no GPU): parse the markers of one file.  info (int64[12]) = {width, height, components,
+ * luma h, luma v, restart interval (MCUs, 0: none), scan begin, scan end (byte range of the entropy-coded data),
+ * supported (0 / 1), SOF marker (0xC0 ...), restart segments, sample precision}; when not supported, reason (may be
+ * NULL) receives why.  scan_walk 0 reads the headers only (cheap; whether the file is supported is known from them):
+ * scan end and restart segments are then -1.  scan_walk 1 also walks the entropy-coded data for them.  Returns
+ * non-zero, with vf_last_error(), for a file that is malformed: truncated headers, no SOS, a Huffman table whose code
+ * counts overflow their lengths, a component listed twice in the scan; with scan_walk, also restart markers out of
+ * sequence or missing, and 0xFF fill bytes inside the entropy-coded data. */
+enum { VF_JPEG_OK = 0, VF_JPEG_BAD_CODE = 1, VF_JPEG_SHORT_DATA = 2 };   /* per-image status words of vf_jpeg_decode */
+int vf_jpeg_inspect(const unsigned char* data, size_t len, int scan_walk, int64_t* info, char* reason, int reason_cap);
+/* Sizes for one batch: the n files are data[offs[i] .. offs[i+1]) (HOST memory).  ws_bytes: the DEVICE workspace
+ * vf_jpeg_decode needs; stage_bytes: its HOST staging buffer (pinned memory keeps the one upload asynchronous).  Read
+ * from the headers alone, so they are upper bounds (the scan data is walked once, by vf_jpeg_decode).
+ * subseq_bytes (>= 8): length of the subsequences the Huffman decoder synchronises over.  Fails, naming the image,
+ * on a file that is malformed (2) or unsupported (3). */
+int vf_jpeg_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
+                            size_t* stage_bytes);
+/* Decode the batch on the context's stream: image i becomes uint8 H x W x channels at out + out_offs[i] (DEVICE out,
+ * HOST out_offs).  channels 3: RGB (a grayscale file is replicated, as image.load(path, 3)); 1: grayscale files only.
+ * status (DEVICE int32[n]) receives VF_JPEG_* per image, rounds (DEVICE int32[1]) the largest number of
+ * synchronisation rounds any segment needed.  The host parses and packs every file into stage (caller-owned, >=
+ * stage_bytes) and enqueues one upload into ws (caller-owned DEVICE memory, >= ws_bytes); stage must stay untouched
+ * until the stream reaches this call's work.  Nothing is allocated and nothing synchronises. */
+int vf_jpeg_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes,
+                   const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
+                   int32_t* status, int32_t* rounds);
+
 /* ---- option branches of train.lua: noiseGen (:109-124, 319-327) and conditionAdv (:158-180) -----------------------
  * nn.JoinTable(2) over NHWC tensors: dst[p][c_dst + c] = src[p][c_src + c] for c < Ccopy, p < npix (forward: one call
  * per table element into the joined tensor; updateGradInput: one call per element out of the joined gradient).

@@ -8,6 +8,7 @@ itself never constructs anything else and never falls back.
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -201,6 +202,27 @@ def nhwc_empty(B, Cc, H, W, device, dtype=torch.float32):
 
 def to_nhwc(t):
     return t if is_nhwc(t) else t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+
+
+JPEG_STATUS = {0: "ok", 1: "bad Huffman code", 2: "short data"}
+
+
+def jpeg_inspect(data, walk=True):
+    """The host-only parse of one JPEG file (vf_jpeg_inspect; no GPU needed) -> dict(width, height, components, h_samp,
+    v_samp, restart_interval, scan_begin, scan_end, supported, sof, segments, precision, reason).  walk=False reads the
+    headers only (scan_end and segments are -1).  Raises ValueError for a malformed file."""
+    lib = _lib.load()
+    data = bytes(data)
+    info = (C.c_int64 * 12)()
+    why = C.create_string_buffer(160)
+    if lib.vf_jpeg_inspect(data, len(data), 1 if walk else 0, info, why, 160) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    keys = ("width", "height", "components", "h_samp", "v_samp", "restart_interval", "scan_begin", "scan_end", "supported",
+            "sof", "segments", "precision")
+    d = {k: int(v) for k, v in zip(keys, info)}
+    d["supported"] = bool(d["supported"])
+    d["reason"] = why.value.decode()
+    return d
 
 
 class HipBackend:
@@ -776,6 +798,48 @@ class HipBackend:
         if mask is not None:
             assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (iH, iW)
         self._c("vf_crop_stats", _ptr(clip), _ptr(mask), Cc, iH, iW, fs, w1, h1, _ptr(out))
+
+    # ---- baseline JPEG decode (vf_jpeg.hip)
+    def jpeg_decode(self, files, channels=3, subseq_bytes=256, infos=None):
+        """Decode a batch of supported JPEG files (bytes each) into one device uint8 buffer.  -> (out, offsets, status,
+        rounds): image i is out[offsets[i]:offsets[i+1]] as H x W x channels; status (device int32[n]) holds VF_JPEG_*
+        per image and rounds (device int32[1]) the synchronisation rounds; both are valid once the stream gets there.
+        infos: the files' jpeg_inspect results, if the caller has them.  The workspace query reads the headers only;
+        vf_jpeg_decode is the one call that walks the scan data."""
+        n = len(files)
+        shapes = infos if infos is not None else [jpeg_inspect(f, walk=False) for f in files]
+        sizes = [s["height"] * s["width"] * channels for s in shapes]
+        offs = np.zeros(n + 1, np.int64)
+        offs[1:] = np.cumsum([len(f) for f in files])
+        out_offs = np.zeros(n + 1, np.int64)
+        out_offs[1:] = np.cumsum(sizes)
+        data = b"".join(files)
+        ws_b, st_b = C.c_size_t(), C.c_size_t()
+        _lib.check(self.lib.vf_jpeg_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), n, subseq_bytes, C.byref(ws_b),
+                                                    C.byref(st_b)))
+        ws = getattr(self, "_jpeg_ws", None)
+        if ws is None or ws.numel() < ws_b.value:
+            self._jpeg_ws = ws = torch.empty(max(ws_b.value, 1 << 20), dtype=torch.uint8, device=self.device)
+        # two pinned staging buffers, used in turn: packing this batch overlaps the device work of the one before, and
+        # waits only for the batch before that (its upload has then left the buffer)
+        if not hasattr(self, "_jpeg_stage"):
+            self._jpeg_stage, self._jpeg_done, self._jpeg_turn = [None, None], [None, None], 0
+        t = self._jpeg_turn
+        self._jpeg_turn = 1 - t
+        if self._jpeg_done[t] is not None:
+            self._jpeg_done[t].synchronize()
+        stage = self._jpeg_stage[t]
+        if stage is None or stage.numel() < st_b.value:
+            self._jpeg_stage[t] = stage = torch.empty(max(st_b.value, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        out = torch.empty(max(int(out_offs[-1]), 1), dtype=torch.uint8, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        rounds = torch.empty(1, dtype=torch.int32, device=self.device)
+        self._c("vf_jpeg_decode", data, offs.ctypes.data_as(C.c_void_p), n, channels, subseq_bytes,
+                out_offs.ctypes.data_as(C.c_void_p), _ptr(out), C.c_void_p(stage.data_ptr()), stage.numel(), _ptr(ws), ws.numel(),
+                _ptr(status), _ptr(rounds))
+        self._jpeg_done[t] = torch.cuda.Event()
+        self._jpeg_done[t].record(torch.cuda.current_stream(self.device))
+        return out, out_offs, status, rounds
 
     def channel_copy(self, src, c_src, dst, c_dst, ncopy):
         """dst[:, c_dst:c_dst+ncopy] = src[:, c_src:c_src+ncopy] on NHWC tensors of equal B, H, W (nn.JoinTable(2))."""

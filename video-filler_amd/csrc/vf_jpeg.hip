@@ -1,0 +1,1149 @@
+// vf_jpeg.hip — batched baseline-JPEG decode on the device, byte for byte libjpeg's default decompression.
+//   * vf_jpeg_inspect (host only): markers, geometry, sampling, restart interval, scan range, supported or why not;
+//   * vf_jpeg_workspace_bytes: device workspace and host staging sizes of one batch;
+//   * vf_jpeg_decode: N files -> N uint8 H x W x C images at caller-given offsets of one buffer.
+// Pipeline (the launch count does not depend on N): the host parses the headers, builds the Huffman decode tables
+// (9-bit lookahead + max-code fallback), the natural-order dequantisation tables and the restart segments, and packs
+// them with every scan's bytes into one staging buffer -> one upload.  Then
+//   k_jpeg_unstuff   one wave per 4 KiB chunk drops the stuffed 0x00 bytes; the host found every 0xFF
+//                    while it parsed, so each chunk's output offset is known and the chunks are independent;
+//   k_jpeg_huffman   one block per segment: parallel Huffman decoding by self-synchronisation (Weißenberger & Schmidt,
+//                    ICPP 2018) over fixed-size subsequences, then the write pass (de-zigzagged int16 coefficients) and
+//                    the DC prediction as a segmented scan per component;
+//   k_jpeg_idct      one thread per 8x8 block: dequantise, jpeg_idct_islow, range-limit into uint8 component planes;
+//   k_jpeg_color     one thread per output pixel: fancy upsampling, ycc_rgb_convert, crop into H x W x C.
+// Everything is integer arithmetic.
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "vf_common.h"
+
+namespace {
+
+constexpr int kJpgMaxSide = 16384;
+constexpr int kHuffThreads = 1024;                        // one block per restart segment (the lanes loop over its subsequences)
+constexpr int kChunk = 4096;                              // stuffed bytes per unstuffing wave
+constexpr int kLook = 9;                                  // lookahead bits of the fast Huffman table
+enum { ST_OK = VF_JPEG_OK, ST_BAD = VF_JPEG_BAD_CODE, ST_SHORT = VF_JPEG_SHORT_DATA };
+constexpr uint64_t kDead = ~0ull;                         // decoder state of a lane that stopped on an invalid code / overrun
+
+// one Huffman table in decode form (jdhuff.c jpeg_make_d_derived_tbl, with a 9-bit lookahead)
+struct JpgHuff {
+  uint16_t look[1 << kLook];   // (length << 8) | symbol for codes of <= kLook bits; 0: longer code
+  int32_t maxcode[18];         // largest code of each length, -1 if none; [17]: sentinel
+  int32_t valoff[18];          // symbol index = code + valoff[length]
+  uint8_t val[256];
+};
+
+struct JpgImage {
+  int64_t coef_base;           // first 8x8 block of the image in the coefficient array
+  int64_t plane_base[3];       // first byte of each component plane
+  int64_t out_off;             // first byte of the H x W x C output
+  int32_t W, H, ncomp, channels;
+  int32_t mcux, mcuy, bpm, nblocks;
+  int32_t pw[3], ph[3];        // padded plane sizes (whole MCUs)
+  int32_t cw[3], ch[3];        // real component sizes: ceil(W * h / hmax), ceil(H * v / vmax)
+  int32_t hs, vs;              // luma sampling (1, 1 for grayscale)
+  int32_t tab0;                // first of the image's 4 tables: DC0, DC1, AC0, AC1
+  int32_t bcomp[6], bx[6], by[6], dct[6], act[6];   // per block of the MCU: component, block offset in it, tables
+  int32_t q[3][64];            // natural-order quantisation values per component
+};
+
+struct JpgSeg {
+  int64_t src;                 // first byte in the scan-byte section of the upload (stuffed)
+  int64_t dst;                 // first byte in `bits` (compacted; 16-byte aligned, 16 bytes of slack behind)
+  int64_t sub0;                // first subsequence
+  int32_t slen, len;           // stuffed / compacted bytes
+  int32_t img, mcu0, nmcu, nsub;
+};
+
+// a piece of one segment's stuffed bytes and where its kept bytes go
+struct JpgChunk {
+  int64_t src, dst;
+  int32_t n, keep;             // stuffed bytes, kept bytes
+  int32_t lo;                  // 1: the segment goes on before the chunk (the byte before it may be read)
+};
+
+struct JpgBatch {
+  const JpgImage* img;
+  const JpgSeg* seg;
+  const JpgChunk* chunk;
+  const JpgHuff* huff;
+  const uint8_t* scan;         // stuffed bytes (uploaded)
+  uint8_t* bits;               // compacted bytes
+  uint64_t* E;                 // per subsequence: entry state
+  uint64_t* X;                 //                  exit state
+  int32_t* Nb;                 //                  DC symbols decoded (then: exclusive prefix)
+  uint8_t* D;                  //                  re-decode flag
+  int16_t* coef;
+  uint8_t* planes;
+  uint8_t* out;
+  int32_t* status;
+  int32_t* rounds;
+  int nseg, nchunk, sub_bits;
+};
+
+__host__ __device__ constexpr int zz_natural(int k) {
+  // jpeg_natural_order: zig-zag index -> natural (row-major) index
+  constexpr int8_t t[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                            41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                            30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+  return t[k];
+}
+[[maybe_unused]] __constant__ int8_t c_natural[80] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33,
+                                     40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36,
+                                     29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54,
+                                     47, 55, 62, 63,
+                                     // extra entries for safety in decoder, as jutils.c: k > 63 lands on 63
+                                     63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63};
+
+#define VF_HD __host__ __device__ __forceinline__
+
+// jpeg_natural_order[k] with k > 63 landing on 63, as jutils.c pads it for corrupt run lengths
+VF_HD int natural(int k) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return c_natural[k];
+#else
+  return k > 63 ? 63 : zz_natural(k);
+#endif
+}
+
+__device__ __forceinline__ uint64_t st_pack(uint32_t p, int b, int k) { return ((uint64_t)p << 16) | ((uint64_t)b << 8) | (uint64_t)k; }
+
+// ---- bit reader over one compacted segment (16-byte aligned, 16 bytes of slack behind it): a 64-bit window plus the next
+// dword, loaded one dword ahead of use.  Positions only move forward, by at most 31 bits per symbol; the decoder checks
+// every symbol against the segment's length, so the slack bytes (whatever they hold) never decide a result.
+struct BitWin {
+  const uint32_t* s;
+  uint32_t wbyte;   // byte index of w's first byte (a multiple of 4)
+  uint64_t w;       // bytes [wbyte, wbyte + 8), big-endian
+  uint32_t nxt;     // bytes [wbyte + 8, wbyte + 12), big-endian
+  VF_HD static uint32_t be(uint32_t v) { return __builtin_bswap32(v); }
+  VF_HD void seek(uint32_t p) {
+    wbyte = (p >> 3) & ~3u;
+    const uint32_t d = wbyte >> 2;
+    w = ((uint64_t)be(s[d]) << 32) | be(s[d + 1]);
+    nxt = be(s[d + 2]);
+  }
+  // 32 bits starting at bit p (p at most 62 bits past the window start)
+  VF_HD uint32_t peek(uint32_t p) {
+    uint32_t o = p - 8u * wbyte;
+    if (o >= 32) {
+      w = (w << 32) | nxt;
+      wbyte += 4;
+      nxt = be(s[(wbyte >> 2) + 2]);
+      o -= 32;
+    }
+    return (uint32_t)((w << o) >> 32);
+  }
+};
+
+// one Huffman symbol at the top of `bits` (32-bit window): length (0: invalid code) and symbol
+VF_HD int huff_decode(const JpgHuff& t, uint32_t bits, int& sym) {
+  const uint32_t e = t.look[bits >> (32 - kLook)];
+  if (e) {
+    sym = e & 0xff;
+    return (int)(e >> 8);
+  }
+  for (int l = kLook + 1; l <= 16; ++l) {
+    const int code = (int)(bits >> (32 - l));
+    if (code <= t.maxcode[l]) {
+      sym = t.val[(code + t.valoff[l]) & 0xff];
+      return l;
+    }
+  }
+  return 0;
+}
+
+VF_HD int huff_extend(uint32_t r, int s) {  // HUFF_EXTEND
+  return (int)r - ((r < (1u << (s - 1))) ? (1 << s) - 1 : 0);
+}
+
+enum { LANE_END = 0, LANE_DONE = 1, LANE_BAD = 2, LANE_SHORT = 3 };
+
+// Decode symbols from state (p, b, k) while the next symbol starts before pend.  WRITE: store the coefficients (DC as
+// the difference) of block nb - 1 / nb ... at coef (the segment's first block), stop once `total` blocks are complete.
+// Returns LANE_*; (p, b, k) is the state at the stop, ndc the number of DC symbols decoded.
+template <bool WRITE>
+__host__ __device__ int decode_lane(const JpgImage& im, const JpgHuff* tabs, BitWin& bw, uint32_t nbits, uint32_t& p, int& b, int& k,
+                           uint32_t pend, int& ndc, int64_t nb, int64_t total, int16_t* coef) {
+  ndc = 0;
+  bw.seek(p);
+  for (;;) {
+    if (WRITE && k == 0 && nb >= total) return LANE_DONE;
+    if (p >= pend) return LANE_END;
+    const uint32_t w = bw.peek(p);
+    int sym;
+    if (k == 0) {
+      const int l = huff_decode(tabs[im.dct[b]], w, sym);
+      if (!l) return LANE_BAD;
+      const int s = sym;       // DC tables hold categories <= 15 (checked on the host)
+      if (p + (uint32_t)(l + s) > nbits) return LANE_SHORT;
+      int diff = 0;
+      if (s) diff = huff_extend((w << l) >> (32 - s), s);
+      p += l + s;
+      if (WRITE) coef[nb * 64] = (int16_t)diff;
+      ++nb;
+      ++ndc;
+      k = 1;
+    } else {
+      const int l = huff_decode(tabs[im.act[b]], w, sym);
+      if (!l) return LANE_BAD;
+      const int r = sym >> 4, s = sym & 15;
+      if (p + (uint32_t)(l + s) > nbits) return LANE_SHORT;
+      if (s) {
+        k += r;
+        if (WRITE && nb > 0) coef[(nb - 1) * 64 + natural(k)] = (int16_t)huff_extend((w << l) >> (32 - s), s);
+        ++k;
+      } else if (r == 15) {
+        k += 16;
+      } else {
+        k = 64;   // EOB
+      }
+      p += l + s;
+    }
+    if (k >= 64) {
+      k = 0;
+      if (++b == im.bpm) b = 0;
+    }
+  }
+}
+
+// block-wide exclusive scan of one int per thread (kHuffThreads threads); returns the prefix, `total` the sum
+__device__ int block_scan(int v, int* sh, int& total) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int o = 1; o < kHuffThreads; o <<= 1) {
+    const int a = t >= o ? sh[t - o] : 0;
+    __syncthreads();
+    sh[t] += a;
+    __syncthreads();
+  }
+  total = sh[kHuffThreads - 1];
+  const int r = sh[t] - v;
+  __syncthreads();
+  return r;
+}
+
+// one wave per chunk: keep every byte but the 0x00 after a 0xFF (stuffing)
+__global__ void k_jpeg_unstuff(const JpgBatch B) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (c >= B.nchunk) return;
+  const JpgChunk ck = B.chunk[c];
+  const uint8_t* in = B.scan + ck.src;
+  uint8_t* out = B.bits + ck.dst;
+  int base = 0;
+  for (int c0 = 0; c0 < ck.n; c0 += 64) {
+    const int i = c0 + lane;
+    bool keep = false;
+    uint8_t v = 0;
+    if (i < ck.n) {
+      v = in[i];
+      keep = !(v == 0 && (i > 0 || ck.lo) && in[i - 1] == 0xFF);
+    }
+    const uint64_t m = __ballot(keep);
+    const int pos = base + (int)__popcll(m & ((1ull << lane) - 1));
+    if (keep && pos < ck.keep) out[pos] = v;
+    base += (int)__popcll(m);
+  }
+}
+
+// one block per restart segment
+__global__ __launch_bounds__(kHuffThreads) void k_jpeg_huffman(const JpgBatch B) {
+  __shared__ JpgHuff tabs[4];
+  __shared__ int sh[kHuffThreads];
+  __shared__ int sh3[3][kHuffThreads];
+  __shared__ int changed;
+  const int t = threadIdx.x;
+  const int s = blockIdx.x;
+  const JpgSeg sg = B.seg[s];
+  const JpgImage& im = B.img[sg.img];
+  {
+    const uint32_t* src = (const uint32_t*)(B.huff + im.tab0);
+    uint32_t* dst = (uint32_t*)tabs;
+    for (int i = t; i < (int)(4 * sizeof(JpgHuff) / 4); i += kHuffThreads) dst[i] = src[i];
+  }
+  __syncthreads();
+  const uint32_t* bits = (const uint32_t*)(B.bits + sg.dst);
+  const uint32_t nbits = 8u * (uint32_t)sg.len;
+  const uint32_t sb = (uint32_t)B.sub_bits;
+  const int nsub = sg.nsub;
+  uint64_t* E = B.E + sg.sub0;
+  uint64_t* X = B.X + sg.sub0;
+  int32_t* Nb = B.Nb + sg.sub0;
+  uint8_t* D = B.D + sg.sub0;
+  const int64_t total = (int64_t)sg.nmcu * im.bpm;
+  int16_t* coef = B.coef + (im.coef_base + (int64_t)sg.mcu0 * im.bpm) * 64;
+  BitWin bw{bits, 0, 0, 0};
+
+  auto run = [&](int i, uint64_t e) {
+    uint32_t p = (uint32_t)(e >> 16);
+    int b = (int)((e >> 8) & 0xff), k = (int)(e & 0xff), ndc;
+    const uint32_t pend = min(nbits, (uint32_t)(i + 1) * sb);
+    const int r = decode_lane<false>(im, tabs, bw, nbits, p, b, k, pend, ndc, 0, 0, nullptr);
+    X[i] = r == LANE_END ? st_pack(p, b, k) : kDead;
+    Nb[i] = ndc;
+  };
+  // speculative start of every subsequence at its first bit, at the start of an MCU
+  for (int i = t; i < nsub; i += kHuffThreads) {
+    const uint64_t e = st_pack((uint32_t)i * sb, 0, 0);
+    E[i] = e;
+    run(i, e);
+  }
+  // synchronise: a lane whose entry state differs from its predecessor's exit state decodes again from it.  A dead exit
+  // (the predecessor stopped on an invalid code) is no information: the lane keeps its state, otherwise the dead state
+  // would travel one lane per round to the end of the segment with the corrections behind it
+  int nround = 0;
+  for (;;) {
+    if (t == 0) changed = 0;
+    __syncthreads();
+    for (int i = t; i < nsub; i += kHuffThreads) {
+      D[i] = 0;
+      if (i == 0) continue;
+      const uint64_t x = X[i - 1];
+      if (x != E[i] && x != kDead) {
+        E[i] = x;
+        D[i] = 1;
+        changed = 1;
+      }
+    }
+    __syncthreads();
+    if (!changed) break;
+    ++nround;
+    for (int i = t; i < nsub; i += kHuffThreads)
+      if (D[i]) run(i, E[i]);
+    __syncthreads();
+  }
+  if (t == 0) atomicMax(B.rounds, nround);
+  // exclusive scan of the DC symbols per subsequence -> index of the first block each lane starts
+  {
+    int carry = 0;
+    for (int c = 0; c < nsub; c += kHuffThreads) {
+      const int i = c + t;
+      const int v = i < nsub ? Nb[i] : 0;
+      int tot;
+      const int pre = block_scan(v, sh, tot);
+      if (i < nsub) Nb[i] = carry + pre;
+      carry += tot;
+    }
+  }
+  __syncthreads();
+  // write pass from the synchronised states.  Behind a dead exit the chain is broken: that predecessor meets the invalid
+  // code in its own write pass, and this lane writes nothing (an error only if it still owes blocks)
+  int err = ST_OK;
+  for (int i = t; i < nsub; i += kHuffThreads) {
+    const uint64_t e = E[i];
+    const int64_t nb = Nb[i];
+    if (i > 0 && X[i - 1] == kDead) {
+      if (nb < total) err = ST_BAD;
+      continue;
+    }
+    uint32_t p = (uint32_t)(e >> 16);
+    int b = (int)((e >> 8) & 0xff), k = (int)(e & 0xff), ndc;
+    const uint32_t pend = min(nbits, (uint32_t)(i + 1) * sb);
+    const int r = decode_lane<true>(im, tabs, bw, nbits, p, b, k, pend, ndc, nb, total, coef);
+    if (r == LANE_BAD) err = ST_BAD;
+    else if (r == LANE_SHORT || (r == LANE_END && i == nsub - 1)) err = max(err, (int)ST_SHORT);
+  }
+  if (err != ST_OK) atomicMax(B.status + sg.img, err);
+  __syncthreads();
+  // DC prediction: per component, a running sum over the segment's blocks in MCU order (reset at every segment)
+  int carry[3] = {0, 0, 0};
+  for (int c = 0; c < sg.nmcu; c += kHuffThreads) {
+    const int m = c + t;
+    int sum[3] = {0, 0, 0};
+    if (m < sg.nmcu)
+      for (int b = 0; b < im.bpm; ++b) sum[im.bcomp[b]] += coef[((int64_t)m * im.bpm + b) * 64];
+    for (int ci = 0; ci < 3; ++ci) sh3[ci][t] = sum[ci];
+    __syncthreads();
+    for (int o = 1; o < kHuffThreads; o <<= 1) {
+      int a[3];
+      for (int ci = 0; ci < 3; ++ci) a[ci] = t >= o ? sh3[ci][t - o] : 0;
+      __syncthreads();
+      for (int ci = 0; ci < 3; ++ci) sh3[ci][t] += a[ci];
+      __syncthreads();
+    }
+    if (m < sg.nmcu) {
+      int run[3];
+      for (int ci = 0; ci < 3; ++ci) run[ci] = carry[ci] + sh3[ci][t] - sum[ci];
+      for (int b = 0; b < im.bpm; ++b) {
+        int16_t* dc = coef + ((int64_t)m * im.bpm + b) * 64;
+        const int ci = im.bcomp[b];
+        run[ci] += *dc;
+        *dc = (int16_t)run[ci];
+      }
+    }
+    for (int ci = 0; ci < 3; ++ci) carry[ci] += sh3[ci][kHuffThreads - 1];
+    __syncthreads();
+  }
+}
+
+// ---- jidctint.c jpeg_idct_islow
+constexpr int CONST_BITS = 13, PASS1_BITS = 2;
+constexpr int32_t FIX_0_298631336 = 2446, FIX_0_390180644 = 3196, FIX_0_541196100 = 4433, FIX_0_765366865 = 6270,
+                  FIX_0_899976223 = 7373, FIX_1_175875602 = 9633, FIX_1_501321110 = 12299, FIX_1_847759065 = 15137,
+                  FIX_1_961570560 = 16069, FIX_2_053119869 = 16819, FIX_2_562915447 = 20995, FIX_3_072711026 = 25172;
+
+VF_HD int32_t descale(int32_t x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// idct_range_limit[x & 1023] of jdmaster.c prepare_range_limit_table (the +128 level shift is part of the table)
+VF_HD uint8_t idct_limit(int32_t x) {
+  const int j = x & 1023;
+  return (uint8_t)(j < 128 ? j + 128 : j < 512 ? 255 : j < 896 ? 0 : j - 896);
+}
+
+// one 1-D pass of the islow IDCT over in[0], in[s], ..., in[7s] -> o0..o7 before the descale
+struct Idct8 {
+  int32_t t10, t11, t12, t13, t0, t1, t2, t3;
+  VF_HD void run(int32_t i0, int32_t i1, int32_t i2, int32_t i3, int32_t i4, int32_t i5, int32_t i6,
+                                      int32_t i7) {
+    int32_t z2 = i2, z3 = i6;
+    int32_t z1 = (z2 + z3) * FIX_0_541196100;
+    int32_t tmp2 = z1 + z3 * (-FIX_1_847759065);
+    int32_t tmp3 = z1 + z2 * FIX_0_765366865;
+    z2 = i0;
+    z3 = i4;
+    int32_t tmp0 = (z2 + z3) * (1 << CONST_BITS);
+    int32_t tmp1 = (z2 - z3) * (1 << CONST_BITS);
+    t10 = tmp0 + tmp3;
+    t13 = tmp0 - tmp3;
+    t11 = tmp1 + tmp2;
+    t12 = tmp1 - tmp2;
+    tmp0 = i7;
+    tmp1 = i5;
+    tmp2 = i3;
+    tmp3 = i1;
+    z1 = tmp0 + tmp3;
+    z2 = tmp1 + tmp2;
+    z3 = tmp0 + tmp2;
+    int32_t z4 = tmp1 + tmp3;
+    const int32_t z5 = (z3 + z4) * FIX_1_175875602;
+    tmp0 = tmp0 * FIX_0_298631336;
+    tmp1 = tmp1 * FIX_2_053119869;
+    tmp2 = tmp2 * FIX_3_072711026;
+    tmp3 = tmp3 * FIX_1_501321110;
+    z1 = z1 * (-FIX_0_899976223);
+    z2 = z2 * (-FIX_2_562915447);
+    z3 = z3 * (-FIX_1_961570560);
+    z4 = z4 * (-FIX_0_390180644);
+    z3 += z5;
+    z4 += z5;
+    t0 = tmp0 + z1 + z3;
+    t1 = tmp1 + z2 + z4;
+    t2 = tmp2 + z2 + z3;
+    t3 = tmp3 + z1 + z4;
+  }
+};
+
+// one 8x8 block: dequantise (natural order), jpeg_idct_islow, range-limit into dst (row stride `stride`)
+VF_HD void idct_islow(const int16_t* cf, const int32_t* q, uint8_t* dst, int stride) {
+  int32_t ws[64];
+  // pass 1: columns (the all-zero-AC shortcut of jidctint.c gives the same values, so it is not taken separately)
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    Idct8 d;
+    d.run(cf[c] * q[c], cf[8 + c] * q[8 + c], cf[16 + c] * q[16 + c], cf[24 + c] * q[24 + c], cf[32 + c] * q[32 + c],
+          cf[40 + c] * q[40 + c], cf[48 + c] * q[48 + c], cf[56 + c] * q[56 + c]);
+    constexpr int n = CONST_BITS - PASS1_BITS;
+    ws[c] = descale(d.t10 + d.t3, n);
+    ws[56 + c] = descale(d.t10 - d.t3, n);
+    ws[8 + c] = descale(d.t11 + d.t2, n);
+    ws[48 + c] = descale(d.t11 - d.t2, n);
+    ws[16 + c] = descale(d.t12 + d.t1, n);
+    ws[40 + c] = descale(d.t12 - d.t1, n);
+    ws[24 + c] = descale(d.t13 + d.t0, n);
+    ws[32 + c] = descale(d.t13 - d.t0, n);
+  }
+  // pass 2: rows
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int32_t* w = ws + 8 * r;
+    Idct8 d;
+    d.run(w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]);
+    constexpr int n = CONST_BITS + PASS1_BITS + 3;
+    uint8_t o[8];
+    o[0] = idct_limit(descale(d.t10 + d.t3, n));
+    o[7] = idct_limit(descale(d.t10 - d.t3, n));
+    o[1] = idct_limit(descale(d.t11 + d.t2, n));
+    o[6] = idct_limit(descale(d.t11 - d.t2, n));
+    o[2] = idct_limit(descale(d.t12 + d.t1, n));
+    o[5] = idct_limit(descale(d.t12 - d.t1, n));
+    o[3] = idct_limit(descale(d.t13 + d.t0, n));
+    o[4] = idct_limit(descale(d.t13 - d.t0, n));
+    uint8_t* row = dst + (int64_t)r * stride;
+    for (int x = 0; x < 8; ++x) row[x] = o[x];
+  }
+}
+
+__global__ void k_jpeg_idct(const JpgBatch B) {
+  const JpgImage& im = B.img[blockIdx.y];
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < im.nblocks; j += (int64_t)gridDim.x * blockDim.x) {
+    const int m = (int)(j / im.bpm), b = (int)(j % im.bpm);
+    const int ci = im.bcomp[b];
+    const int hc = ci == 0 ? im.hs : 1, vc = ci == 0 ? im.vs : 1;
+    const int bx = (m % im.mcux) * hc + im.bx[b], by = (m / im.mcux) * vc + im.by[b];
+    idct_islow(B.coef + (im.coef_base + j) * 64, im.q[ci], B.planes + im.plane_base[ci] + (int64_t)by * 8 * im.pw[ci] + bx * 8,
+               im.pw[ci]);
+  }
+}
+
+// ---- jdsample.c (fancy upsampling) and jdcolor.c ycc_rgb_convert
+VF_HD uint8_t clamp255(int v) { return (uint8_t)min(255, max(0, v)); }
+
+// chroma sample of component ci at full-resolution (x, y)
+VF_HD int chroma_at(const JpgBatch& B, const JpgImage& im, int ci, int x, int y) {
+  const uint8_t* pl = B.planes + im.plane_base[ci];
+  const int pw = im.pw[ci], cw = im.cw[ci], ch = im.ch[ci];
+  if (im.hs == 1) return pl[(int64_t)y * pw + x];                       // 4:4:4 (vs == 1 with hs == 1)
+  const int i = x >> 1;
+  if (cw <= 2) return pl[(int64_t)(im.vs == 2 ? y >> 1 : y) * pw + i];  // h2v1_upsample / h2v2_upsample (box)
+  if (im.vs == 1) {                                                     // h2v1_fancy_upsample
+    const uint8_t* in = pl + (int64_t)y * pw;
+    const int v3 = 3 * in[i];
+    if (x & 1) return i == cw - 1 ? in[i] : (v3 + in[i + 1] + 2) >> 2;
+    return i == 0 ? in[0] : (v3 + in[i - 1] + 1) >> 2;
+  }
+  // h2v2_fancy_upsample: the nearer row weighs 3, the farther 1; the rows beyond the edges replicate the edge rows
+  const int r0 = y >> 1;
+  const int r1 = (y & 1) ? min(r0 + 1, ch - 1) : max(r0 - 1, 0);
+  const uint8_t* in0 = pl + (int64_t)r0 * pw;
+  const uint8_t* in1 = pl + (int64_t)r1 * pw;
+  auto cs = [&](int c) { return 3 * in0[c] + in1[c]; };
+  const int c0 = cs(i);
+  if (x & 1) return i == cw - 1 ? (4 * c0 + 7) >> 4 : (3 * c0 + cs(i + 1) + 7) >> 4;
+  return i == 0 ? (4 * c0 + 8) >> 4 : (3 * c0 + cs(i - 1) + 8) >> 4;
+}
+
+__global__ void k_jpeg_color(const JpgBatch B) {
+  const JpgImage& im = B.img[blockIdx.y];
+  const int64_t npix = (int64_t)im.W * im.H;
+  uint8_t* out = B.out + im.out_off;
+  const uint8_t* yp = B.planes + im.plane_base[0];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(i / im.W), x = (int)(i % im.W);
+    const int Y = yp[(int64_t)y * im.pw[0] + x];
+    if (im.ncomp == 1) {
+      for (int c = 0; c < im.channels; ++c) out[i * im.channels + c] = (uint8_t)Y;
+      continue;
+    }
+    const int cb = chroma_at(B, im, 1, x, y) - 128, cr = chroma_at(B, im, 2, x, y) - 128;
+    constexpr int SCALEBITS = 16, ONE_HALF = 1 << 15;
+    const int r = Y + ((91881 * cr + ONE_HALF) >> SCALEBITS);
+    const int g = Y + ((-22554 * cb + ONE_HALF + -46802 * cr) >> SCALEBITS);
+    const int bl = Y + ((116130 * cb + ONE_HALF) >> SCALEBITS);
+    out[i * 3 + 0] = clamp255(r);
+    out[i * 3 + 1] = clamp255(g);
+    out[i * 3 + 2] = clamp255(bl);
+  }
+}
+
+// ================================================================================================ host side: parsing
+struct RawHuff {
+  uint8_t bits[17];
+  uint8_t val[256];
+  int nval;
+  bool present;
+  bool fits;   // the canonical codes fit their lengths, none all ones (jdhuff.c: else JERR_BAD_HUFF_TABLE)
+};
+
+// jpeg_make_d_derived_tbl's check: after the codes of length l, the next code must still fit in l bits
+inline bool huff_fits(const uint8_t* bits) {
+  int64_t code = 0;
+  for (int l = 1; l <= 16; ++l) {
+    code += bits[l];
+    if (code >= ((int64_t)1 << l)) return false;
+    code <<= 1;
+  }
+  return true;
+}
+
+struct JpgParsed {
+  int W = 0, H = 0, ncomp = 0, prec = 0, sof = -1, ri = 0, hmax = 1, vmax = 1;
+  int cid[4] = {}, hf[4] = {}, vf[4] = {}, tq[4] = {};
+  int ns = 0, scomp[4] = {}, td[4] = {}, ta[4] = {};
+  int ss = 0, se = 63, ahal = 0;
+  bool jfif = false, adobe = false;
+  int adobe_transform = -1;
+  int64_t scan_begin = 0, scan_end = 0;
+  bool supported = false;
+  std::string why;
+  uint16_t qt[4][64] = {};   // natural order
+  bool qt_ok[4] = {};
+  RawHuff hdc[4] = {}, hac[4] = {};
+  struct Seg {
+    int64_t begin, end, len;
+  };
+  std::vector<Seg> segs;
+  std::vector<int64_t> drops;   // positions of the bytes unstuffing drops, ascending
+};
+
+inline int rd16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
+
+// 0: headers parsed (P.supported says whether the decoder takes the file, P.why why not); else malformed (msg)
+int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool walk) {
+  auto unsupported = [&](const std::string& w) {
+    if (P.why.empty()) P.why = w;
+  };
+  if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) {
+    msg = "not a JPEG file (no SOI marker)";
+    return 2;
+  }
+  int64_t p = 2;
+  bool have_sos = false;
+  for (;;) {
+    // next marker: skip fill bytes
+    if (p >= n) {
+      msg = "truncated header (no SOS marker before the end of the data)";
+      return 2;
+    }
+    if (d[p] != 0xFF) {
+      msg = "malformed header: marker expected at byte " + std::to_string(p);
+      return 2;
+    }
+    while (p < n && d[p] == 0xFF) ++p;
+    if (p >= n) {
+      msg = "truncated header";
+      return 2;
+    }
+    const int m = d[p++];
+    if (m == 0xD9) {
+      msg = "no SOS marker (EOI before any scan)";
+      return 2;
+    }
+    if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;   // no payload
+    if (p + 2 > n) {
+      msg = "truncated header";
+      return 2;
+    }
+    const int L = rd16(d + p);
+    if (L < 2 || p + L > n) {
+      msg = "truncated header (marker 0x" + std::to_string(m) + " runs past the end of the data)";
+      return 2;
+    }
+    const uint8_t* s = d + p + 2;
+    const int sl = L - 2;
+    if (m == 0xC0 || m == 0xC1 || m == 0xC2 || m == 0xC3 || (m >= 0xC5 && m <= 0xC7) || (m >= 0xC9 && m <= 0xCB) ||
+        (m >= 0xCD && m <= 0xCF)) {
+      if (P.sof >= 0) {
+        msg = "more than one SOF marker";
+        return 2;
+      }
+      P.sof = m;
+      if (sl < 6) {
+        msg = "truncated SOF";
+        return 2;
+      }
+      P.prec = s[0];
+      P.H = rd16(s + 1);
+      P.W = rd16(s + 3);
+      P.ncomp = s[5];
+      if (sl < 6 + 3 * P.ncomp) {
+        msg = "truncated SOF";
+        return 2;
+      }
+      for (int c = 0; c < P.ncomp && c < 4; ++c) {
+        P.cid[c] = s[6 + 3 * c];
+        P.hf[c] = s[7 + 3 * c] >> 4;
+        P.vf[c] = s[7 + 3 * c] & 15;
+        P.tq[c] = s[8 + 3 * c];
+        P.hmax = std::max(P.hmax, P.hf[c]);
+        P.vmax = std::max(P.vmax, P.vf[c]);
+      }
+      if (m == 0xC2 || m == 0xC6 || m == 0xCA || m == 0xCE) unsupported("progressive");
+      else if (m == 0xC3 || m == 0xC7 || m == 0xCB || m == 0xCF) unsupported("lossless");
+      else if (m >= 0xC9) unsupported("arithmetic coding");
+      else if (m >= 0xC5) unsupported("hierarchical (differential)");
+      if (P.prec != 8) unsupported(std::to_string(P.prec) + "-bit samples");
+      if (P.ncomp == 4) unsupported("4 components (CMYK / YCCK)");
+      else if (P.ncomp != 1 && P.ncomp != 3) unsupported(std::to_string(P.ncomp) + " components");
+      if (P.W <= 0 || P.H <= 0) unsupported("height or width 0 (DNL)");
+      if (P.W > kJpgMaxSide || P.H > kJpgMaxSide) unsupported("larger than 16384 per side");
+      if (P.ncomp == 3) {
+        const bool ok = P.hf[1] == 1 && P.vf[1] == 1 && P.hf[2] == 1 && P.vf[2] == 1 &&
+                        ((P.hf[0] == 1 && P.vf[0] == 1) || (P.hf[0] == 2 && P.vf[0] == 1) || (P.hf[0] == 2 && P.vf[0] == 2));
+        if (!ok)
+          unsupported("sampling " + std::to_string(P.hf[0]) + "x" + std::to_string(P.vf[0]) + "," + std::to_string(P.hf[1]) +
+                      "x" + std::to_string(P.vf[1]) + "," + std::to_string(P.hf[2]) + "x" + std::to_string(P.vf[2]) +
+                      " (4:4:4, 4:2:2 and 4:2:0 only)");
+      }
+    } else if (m == 0xC4) {   // DHT
+      int q = 0;
+      while (q < sl) {
+        if (q + 17 > sl) {
+          msg = "truncated DHT";
+          return 2;
+        }
+        const int tc = s[q] >> 4, th = s[q] & 15;
+        int cnt = 0;
+        for (int l = 1; l <= 16; ++l) cnt += s[q + l];
+        if (q + 17 + cnt > sl || cnt > 256 || th > 3 || tc > 1) {
+          msg = "malformed DHT";
+          return 2;
+        }
+        RawHuff& h = tc ? P.hac[th] : P.hdc[th];
+        h.bits[0] = 0;
+        for (int l = 1; l <= 16; ++l) h.bits[l] = s[q + l];
+        memcpy(h.val, s + q + 17, cnt);
+        h.nval = cnt;
+        h.present = true;
+        h.fits = huff_fits(h.bits);
+        q += 17 + cnt;
+      }
+    } else if (m == 0xDB) {   // DQT
+      int q = 0;
+      while (q < sl) {
+        const int pq = s[q] >> 4, tqi = s[q] & 15;
+        const int need = 1 + 64 * (pq ? 2 : 1);
+        if (q + need > sl || tqi > 3 || pq > 1) {
+          msg = "malformed DQT";
+          return 2;
+        }
+        for (int k = 0; k < 64; ++k) P.qt[tqi][zz_natural(k)] = pq ? rd16(s + q + 1 + 2 * k) : s[q + 1 + k];
+        P.qt_ok[tqi] = true;
+        q += need;
+      }
+    } else if (m == 0xDD) {   // DRI
+      if (sl < 2) {
+        msg = "truncated DRI";
+        return 2;
+      }
+      P.ri = rd16(s);
+    } else if (m == 0xE0) {
+      if (sl >= 5 && !memcmp(s, "JFIF", 5)) P.jfif = true;
+    } else if (m == 0xEE) {
+      if (sl >= 12 && !memcmp(s, "Adobe", 5)) {
+        P.adobe = true;
+        P.adobe_transform = s[11];
+      }
+    } else if (m == 0xDA) {   // SOS
+      if (P.sof < 0) {
+        msg = "SOS before SOF";
+        return 2;
+      }
+      if (sl < 1) {
+        msg = "truncated SOS";
+        return 2;
+      }
+      P.ns = s[0];
+      if (sl < 1 + 2 * P.ns + 3 || P.ns < 1 || P.ns > 4) {
+        msg = "malformed SOS";
+        return 2;
+      }
+      for (int i = 0; i < P.ns; ++i) {
+        int f = -1;
+        for (int c = 0; c < P.ncomp && c < 4; ++c)
+          if (P.cid[c] == s[1 + 2 * i]) f = c;
+        if (f < 0) {
+          msg = "SOS names a component the frame does not have";
+          return 2;
+        }
+        for (int j = 0; j < i; ++j)
+          if (P.scomp[j] == f) {
+            msg = "SOS names a component twice";
+            return 2;
+          }
+        P.scomp[i] = f;
+        P.td[i] = s[2 + 2 * i] >> 4;
+        P.ta[i] = s[2 + 2 * i] & 15;
+      }
+      P.ss = s[1 + 2 * P.ns];
+      P.se = s[2 + 2 * P.ns];
+      P.ahal = s[3 + 2 * P.ns];
+      P.scan_begin = p + L;
+      have_sos = true;
+    }
+    p += L;
+    if (have_sos) break;
+  }
+  // colour space (jdapimin.c default_decompress_parms) and the scan
+  if (P.ncomp == 3) {
+    if (P.jfif) {
+    } else if (P.adobe) {
+      if (P.adobe_transform == 0) unsupported("RGB colour transform (Adobe transform 0)");
+      else if (P.adobe_transform != 1) unsupported("Adobe transform " + std::to_string(P.adobe_transform));
+    } else if (P.cid[0] == 82 && P.cid[1] == 71 && P.cid[2] == 66) {
+      unsupported("RGB components");
+    }
+  }
+  if (P.ns != P.ncomp && (P.ncomp == 1 || P.ncomp == 3)) unsupported("multi-scan sequential");
+  if (P.ss != 0 || P.se != 63 || P.ahal != 0) unsupported("non-baseline scan parameters");
+  for (int i = 0; i < P.ns && P.why.empty(); ++i) {
+    const int f = P.scomp[i];
+    if (P.tq[f] > 3 || !P.qt_ok[P.tq[f]]) unsupported("missing quantisation table");
+    if (P.td[i] > 1 || P.ta[i] > 1 || !P.hdc[P.td[i]].present || !P.hac[P.ta[i]].present)
+      unsupported("missing Huffman table (or one beyond baseline's two)");
+    else {
+      const RawHuff& h = P.hdc[P.td[i]];
+      for (int v = 0; v < h.nval; ++v)
+        if (h.val[v] > 15) unsupported("DC Huffman symbol above 15");
+    }
+  }
+  for (int i = 0; i < P.ns; ++i) {
+    // a table the scan uses whose codes overflow their lengths: libjpeg stops with JERR_BAD_HUFF_TABLE
+    const RawHuff* used[2] = {P.td[i] <= 1 ? &P.hdc[P.td[i]] : nullptr, P.ta[i] <= 1 ? &P.hac[P.ta[i]] : nullptr};
+    for (const RawHuff* h : used)
+      if (h && h->present && !h->fits) {
+        msg = "bad Huffman table: its code counts overflow the code lengths";
+        return 2;
+      }
+  }
+  if (!walk) {   // headers only: the scan's extent, restart segments and stuffing stay unknown
+    P.scan_end = -1;
+    P.supported = P.why.empty();
+    return 0;
+  }
+  // the entropy-coded data: every 0xFF is stuffing (0xFF00), a restart marker, or the end of the scan
+  const int64_t nmcu = P.ncomp == 1 ? vf_cdiv(P.W, 8) * vf_cdiv(P.H, 8)
+                                    : vf_cdiv(P.W, 8 * P.hmax) * vf_cdiv(P.H, 8 * P.vmax);
+  int64_t q = P.scan_begin, seg0 = q, drop = 0;
+  int nrst = 0;
+  int end_marker = -1;
+  for (;;) {
+    const uint8_t* f = q < n ? (const uint8_t*)memchr(d + q, 0xFF, (size_t)(n - q)) : nullptr;
+    if (!f) {
+      P.scan_end = n;
+      break;
+    }
+    const int64_t i = f - d;
+    int64_t j = i + 1;
+    while (j < n && d[j] == 0xFF) ++j;
+    if (j >= n) {
+      P.scan_end = i;
+      break;
+    }
+    const int c = d[j];
+    if (c == 0) {
+      if (j - i > 1) {
+        // fill bytes before a stuffed 0xFF: libjpeg-turbo's fast path reads them as a marker, its slow path (and
+        // jpeg-6b) skips them, so the file has no one libjpeg result.  No encoder writes them.
+        msg = "0xFF fill bytes inside the entropy-coded data at byte " + std::to_string(i);
+        return 2;
+      }
+      ++drop;
+      P.drops.push_back(j);   // the stuffed 0x00
+      q = j + 1;
+    } else if (c >= 0xD0 && c <= 0xD7) {
+      if (c != 0xD0 + (nrst & 7)) {
+        msg = "restart marker out of sequence";
+        return 2;
+      }
+      ++nrst;
+      P.segs.push_back({seg0, i, i - seg0 - drop});
+      seg0 = j + 1;
+      drop = 0;
+      q = j + 1;
+    } else {
+      P.scan_end = i;
+      end_marker = c;
+      break;
+    }
+  }
+  P.segs.push_back({seg0, P.scan_end, P.scan_end - seg0 - drop});
+  if (end_marker >= 0 && end_marker != 0xD9) {
+    // anything but EOI after the scan: a second scan makes it multi-scan; other markers are skipped
+    int64_t r = P.scan_end;
+    while (r + 1 < n) {
+      if (d[r] != 0xFF) break;
+      while (r < n && d[r] == 0xFF) ++r;
+      if (r >= n) break;
+      const int mm = d[r++];
+      if (mm == 0xD9) break;
+      if (mm == 0xDA) {
+        unsupported("multi-scan sequential");
+        break;
+      }
+      if (r + 2 > n) break;
+      r += rd16(d + r);
+    }
+  }
+  const int64_t want = P.ri > 0 ? vf_cdiv(nmcu, P.ri) : 1;
+  if (P.why.empty() && (int64_t)P.segs.size() != want) {
+    msg = "found " + std::to_string(P.segs.size()) + " restart segments, the restart interval gives " + std::to_string(want);
+    return 2;
+  }
+  for (const auto& sg : P.segs)
+    if (sg.end - sg.begin > (int64_t)1 << 28) unsupported("a restart segment above 256 MiB");
+  P.supported = P.why.empty();
+  return 0;
+}
+
+void build_huff(const RawHuff& r, JpgHuff& t) {
+  memset(&t, 0, sizeof(t));
+  if (!r.present || !r.fits) return;   // never used by a scan (jpg_parse rejects used ones); keeps `look` in bounds
+  int code = 0, k = 0;
+  for (int l = 1; l <= 16; ++l) {
+    t.valoff[l] = k - code;
+    for (int i = 0; i < r.bits[l]; ++i, ++k, ++code) {
+      if (l <= kLook) {
+        const int lo = code << (kLook - l), hi = lo + (1 << (kLook - l));
+        for (int e = lo; e < hi; ++e) t.look[e] = (uint16_t)((l << 8) | r.val[k]);
+      }
+    }
+    t.maxcode[l] = r.bits[l] ? code - 1 : -1;
+    code <<= 1;
+  }
+  t.maxcode[17] = 0x7fffffff;
+  memcpy(t.val, r.val, 256);
+}
+
+// sizes and section offsets of one batch
+struct JpgPlan {
+  std::vector<JpgParsed> P;
+  int64_t nseg = 0, nsub = 0, nblk = 0, plane_bytes = 0, scan_bytes = 0, bits_bytes = 0, nchunk = 0;
+  int64_t max_blocks = 0, max_pix = 0;
+  size_t o_img = 0, o_seg = 0, o_chunk = 0, o_huff = 0, o_scan = 0, stage = 0;   // staging layout (also the front of the workspace)
+  size_t o_bits = 0, o_E = 0, o_X = 0, o_N = 0, o_D = 0, o_coef = 0, o_planes = 0, ws = 0;
+};
+
+inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
+inline int64_t seg_bits_bytes(int64_t len) { return ((len + 15) & ~(int64_t)15) + 16; }   // BitWin reads up to 11 bytes past the end
+
+// walk: the exact sizes of a full parse (vf_jpeg_decode); else upper bounds from the headers alone
+// (vf_jpeg_workspace_bytes): a segment's compacted length is at most its stuffed length, and the segments share the
+// bytes from the scan's start to the end of the file
+int jpg_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes, JpgPlan& L, bool walk) {
+  VF_REQUIRE(n > 0 && data && offs, "vf_jpeg: empty batch");
+  VF_REQUIRE(sub_bytes >= 8 && sub_bytes <= (1 << 20), "vf_jpeg: subsequence size %d outside [8, 1 MiB]", sub_bytes);
+  L.P.resize(n);
+  for (int i = 0; i < n; ++i) {
+    std::string msg;
+    VF_REQUIRE(offs[i + 1] >= offs[i], "vf_jpeg: offsets decrease at image %d", i);
+    JpgParsed& P = L.P[i];
+    if (jpg_parse(data + offs[i], offs[i + 1] - offs[i], P, msg, walk)) {
+      vf_set_error("vf_jpeg: image %d: %s", i, msg.c_str());
+      return 2;
+    }
+    if (!P.supported) {
+      vf_set_error("vf_jpeg: image %d: unsupported: %s", i, P.why.c_str());
+      return 3;
+    }
+    const bool gray = P.ncomp == 1;
+    const int64_t mcux = gray ? vf_cdiv(P.W, 8) : vf_cdiv(P.W, 8 * P.hmax), mcuy = gray ? vf_cdiv(P.H, 8) : vf_cdiv(P.H, 8 * P.vmax);
+    const int bpm = gray ? 1 : P.hmax * P.vmax + 2;
+    L.nblk += mcux * mcuy * bpm;
+    L.max_blocks = std::max(L.max_blocks, mcux * mcuy * bpm);
+    L.max_pix = std::max(L.max_pix, (int64_t)P.W * P.H);
+    L.plane_bytes += mcux * mcuy * 64 * bpm;
+    L.plane_bytes = (int64_t)al((size_t)L.plane_bytes);
+    if (walk) {
+      L.nseg += (int64_t)P.segs.size();
+      for (const auto& s : P.segs) {
+        L.nsub += std::max<int64_t>(1, vf_cdiv(s.len, sub_bytes));
+        L.bits_bytes += seg_bits_bytes(s.len);
+        L.nchunk += vf_cdiv(s.end - s.begin, kChunk);
+      }
+      L.scan_bytes += (int64_t)al((size_t)(P.scan_end - P.scan_begin) + 8);
+    } else {
+      const int64_t nseg = P.ri > 0 ? vf_cdiv(mcux * mcuy, P.ri) : 1, sb = offs[i + 1] - offs[i] - P.scan_begin;
+      L.nseg += nseg;
+      L.nsub += vf_cdiv(sb, sub_bytes) + nseg;
+      L.bits_bytes += sb + 32 * nseg;
+      L.nchunk += vf_cdiv(sb, kChunk) + nseg;
+      L.scan_bytes += (int64_t)al((size_t)sb + 8);
+    }
+  }
+  L.o_img = 0;
+  L.o_seg = al(L.o_img + sizeof(JpgImage) * n);
+  L.o_chunk = al(L.o_seg + sizeof(JpgSeg) * L.nseg);
+  L.o_huff = al(L.o_chunk + sizeof(JpgChunk) * L.nchunk);
+  L.o_scan = al(L.o_huff + sizeof(JpgHuff) * 4 * n);
+  L.stage = al(L.o_scan + L.scan_bytes);
+  L.o_bits = L.stage;
+  L.o_E = al(L.o_bits + L.bits_bytes);
+  L.o_X = al(L.o_E + 8 * L.nsub);
+  L.o_N = al(L.o_X + 8 * L.nsub);
+  L.o_D = al(L.o_N + 4 * L.nsub);
+  L.o_coef = al(L.o_D + L.nsub);
+  L.o_planes = al(L.o_coef + 128 * L.nblk);
+  L.ws = al(L.o_planes + L.plane_bytes);
+  return 0;
+}
+
+// fill the staging buffer
+void jpg_pack(const uint8_t* data, const int64_t* offs, int n, int channels, int sub_bytes, const int64_t* out_offs, const JpgPlan& L,
+              uint8_t* st) {
+  JpgImage* imgs = (JpgImage*)(st + L.o_img);
+  JpgSeg* segs = (JpgSeg*)(st + L.o_seg);
+  JpgChunk* chunks = (JpgChunk*)(st + L.o_chunk);
+  JpgHuff* huffs = (JpgHuff*)(st + L.o_huff);
+  uint8_t* scan = st + L.o_scan;
+  int64_t coef = 0, plane = 0, sc = 0, sub = 0, dst = 0;
+  int si = 0, ci = 0;
+  for (int i = 0; i < n; ++i) {
+    const JpgParsed& P = L.P[i];
+    const uint8_t* d = data + offs[i];
+    JpgImage& im = imgs[i];
+    memset(&im, 0, sizeof(im));
+    const bool gray = P.ncomp == 1;
+    im.W = P.W;
+    im.H = P.H;
+    im.ncomp = P.ncomp;
+    im.channels = channels;
+    im.hs = gray ? 1 : P.hmax;
+    im.vs = gray ? 1 : P.vmax;
+    im.mcux = (int)(gray ? vf_cdiv(P.W, 8) : vf_cdiv(P.W, 8 * P.hmax));
+    im.mcuy = (int)(gray ? vf_cdiv(P.H, 8) : vf_cdiv(P.H, 8 * P.vmax));
+    im.tab0 = 4 * i;
+    // MCU composition in scan order
+    int b = 0;
+    for (int s = 0; s < P.ns; ++s) {
+      const int f = P.scomp[s];
+      const int h = gray ? 1 : P.hf[f], v = gray ? 1 : P.vf[f];
+      for (int y = 0; y < v; ++y)
+        for (int x = 0; x < h; ++x, ++b) {
+          im.bcomp[b] = f;
+          im.bx[b] = x;
+          im.by[b] = y;
+          im.dct[b] = P.td[s];
+          im.act[b] = 2 + P.ta[s];
+        }
+    }
+    im.bpm = b;
+    im.nblocks = im.mcux * im.mcuy * im.bpm;
+    im.coef_base = coef;
+    coef += im.nblocks;
+    for (int c = 0; c < P.ncomp; ++c) {
+      const int h = gray ? 1 : P.hf[c], v = gray ? 1 : P.vf[c];
+      im.pw[c] = im.mcux * 8 * h;
+      im.ph[c] = im.mcuy * 8 * v;
+      im.cw[c] = (int)vf_cdiv((int64_t)P.W * h, gray ? 1 : P.hmax);
+      im.ch[c] = (int)vf_cdiv((int64_t)P.H * v, gray ? 1 : P.vmax);
+      im.plane_base[c] = plane;
+      plane += (int64_t)im.pw[c] * im.ph[c];
+      for (int k = 0; k < 64; ++k) im.q[c][k] = P.qt[P.tq[c]][k];
+    }
+    plane = (int64_t)al((size_t)plane);
+    im.out_off = out_offs[i];
+    for (int t = 0; t < 2; ++t) {
+      build_huff(P.hdc[t], huffs[4 * i + t]);
+      build_huff(P.hac[t], huffs[4 * i + 2 + t]);
+    }
+    const int64_t nbytes = P.scan_end - P.scan_begin;
+    memcpy(scan + sc, d + P.scan_begin, (size_t)nbytes);
+    memset(scan + sc + nbytes, 0, al((size_t)nbytes + 8) - (size_t)nbytes);
+    const int64_t nmcu = (int64_t)im.mcux * im.mcuy;
+    for (size_t k = 0; k < P.segs.size(); ++k, ++si) {
+      const auto& s = P.segs[k];
+      JpgSeg& g = segs[si];
+      g.src = sc + (s.begin - P.scan_begin);
+      g.dst = dst;
+      size_t di = std::lower_bound(P.drops.begin(), P.drops.end(), s.begin) - P.drops.begin();
+      int64_t kept = 0;
+      for (int64_t c0 = s.begin; c0 < s.end; c0 += kChunk, ++ci) {
+        const int64_t c1 = std::min<int64_t>(c0 + kChunk, s.end);
+        int64_t nd = 0;
+        for (; di < P.drops.size() && P.drops[di] < c1; ++di) ++nd;
+        JpgChunk& k = chunks[ci];
+        k.src = sc + (c0 - P.scan_begin);
+        k.dst = dst + kept;
+        k.n = (int32_t)(c1 - c0);
+        k.keep = (int32_t)(c1 - c0 - nd);
+        k.lo = c0 > s.begin;
+        kept += k.keep;
+      }
+      dst += seg_bits_bytes(s.len);
+      g.slen = (int32_t)(s.end - s.begin);
+      g.len = (int32_t)s.len;
+      g.img = i;
+      g.mcu0 = (int32_t)(P.ri > 0 ? (int64_t)k * P.ri : 0);
+      g.nmcu = (int32_t)(P.ri > 0 ? std::min<int64_t>(P.ri, nmcu - g.mcu0) : nmcu);
+      g.nsub = (int32_t)std::max<int64_t>(1, vf_cdiv(s.len, sub_bytes));
+      g.sub0 = sub;
+      sub += g.nsub;
+    }
+    sc += (int64_t)al((size_t)nbytes + 8);
+  }
+}
+
+}  // namespace
+
+VF_API int vf_jpeg_inspect(const unsigned char* data, size_t len, int scan_walk, int64_t* info, char* reason, int reason_cap) {
+  VF_REQUIRE(data && info, "vf_jpeg_inspect: NULL argument");
+  JpgParsed P;
+  std::string msg;
+  const int rc = jpg_parse(data, (int64_t)len, P, msg, scan_walk != 0);
+  if (rc) {
+    vf_set_error("vf_jpeg_inspect: %s", msg.c_str());
+    return rc;
+  }
+  info[0] = P.W;
+  info[1] = P.H;
+  info[2] = P.ncomp;
+  info[3] = P.ncomp == 1 ? 1 : P.hf[0];
+  info[4] = P.ncomp == 1 ? 1 : P.vf[0];
+  info[5] = P.ri;
+  info[6] = P.scan_begin;
+  info[7] = P.scan_end;
+  info[8] = P.supported ? 1 : 0;
+  info[9] = P.sof;
+  info[10] = scan_walk ? (int64_t)P.segs.size() : -1;
+  info[11] = P.prec;
+  if (reason && reason_cap > 0) snprintf(reason, (size_t)reason_cap, "%s", P.why.c_str());
+  return 0;
+}
+
+VF_API int vf_jpeg_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
+                                   size_t* stage_bytes) {
+  JpgPlan L;
+  if (int e = jpg_plan(data, offs, n, subseq_bytes, L, false)) return e;
+  if (ws_bytes) *ws_bytes = L.ws;
+  if (stage_bytes) *stage_bytes = L.stage;
+  return 0;
+}
+
+VF_API int vf_jpeg_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes,
+                          const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
+                          int32_t* status, int32_t* rounds) {
+  VF_REQUIRE(channels == 1 || channels == 3, "vf_jpeg_decode: channels %d is not 1 or 3", channels);
+  VF_REQUIRE(out && out_offs && stage && ws && status && rounds, "vf_jpeg_decode: NULL argument");
+  JpgPlan L;
+  if (int e = jpg_plan(data, offs, n, subseq_bytes, L, true)) return e;
+  VF_REQUIRE(stage_bytes >= L.stage && ws_bytes >= L.ws, "vf_jpeg_decode: staging %zu / workspace %zu bytes, need %zu / %zu",
+             stage_bytes, ws_bytes, L.stage, L.ws);
+  for (int i = 0; i < n; ++i)
+    VF_REQUIRE(!(L.P[i].ncomp == 3 && channels == 1), "vf_jpeg_decode: image %d is YCbCr; channels=1 takes grayscale files only", i);
+  jpg_pack(data, offs, n, channels, subseq_bytes, out_offs, L, (uint8_t*)stage);
+  uint8_t* w = (uint8_t*)ws;
+  JpgBatch B;
+  B.img = (const JpgImage*)(w + L.o_img);
+  B.seg = (const JpgSeg*)(w + L.o_seg);
+  B.chunk = (const JpgChunk*)(w + L.o_chunk);
+  B.huff = (const JpgHuff*)(w + L.o_huff);
+  B.scan = w + L.o_scan;
+  B.bits = w + L.o_bits;
+  B.E = (uint64_t*)(w + L.o_E);
+  B.X = (uint64_t*)(w + L.o_X);
+  B.Nb = (int32_t*)(w + L.o_N);
+  B.D = w + L.o_D;
+  B.coef = (int16_t*)(w + L.o_coef);
+  B.planes = w + L.o_planes;
+  B.out = out;
+  B.status = status;
+  B.rounds = rounds;
+  B.nseg = (int)L.nseg;
+  B.nchunk = (int)L.nchunk;
+  B.sub_bits = 8 * subseq_bytes;
+  hipStream_t st = ctx->stream;
+  {
+    VfRange r("jpeg_upload");
+    VF_CHECK_HIP(hipMemcpyAsync(w, stage, L.stage, hipMemcpyHostToDevice, st));
+    VF_CHECK_HIP(hipMemsetAsync(w + L.o_coef, 0, (size_t)(128 * L.nblk), st));
+    VF_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t) * n, st));
+    VF_CHECK_HIP(hipMemsetAsync(rounds, 0, sizeof(int32_t), st));
+  }
+  const int64_t sb = L.scan_bytes;
+  VF_LAUNCH_TIMED(ctx, "jpeg_unstuff", 0.0, 2.0 * sb, k_jpeg_unstuff, dim3((unsigned)std::max<int64_t>(1, vf_cdiv(L.nchunk, 4))), dim3(256), B);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_huffman", 0.0, 3.0 * sb + 128.0 * L.nblk, k_jpeg_huffman, dim3((unsigned)L.nseg), dim3(kHuffThreads), B);
+  VF_LAUNCH_CHECK();
+  const unsigned gb = (unsigned)std::min<int64_t>(vf_cdiv(L.max_blocks, 256), 4096);
+  VF_LAUNCH_TIMED(ctx, "jpeg_idct", 0.0, 192.0 * L.nblk, k_jpeg_idct, dim3(gb, n), dim3(256), B);
+  VF_LAUNCH_CHECK();
+  const unsigned gp = (unsigned)std::min<int64_t>(vf_cdiv(L.max_pix, 256), 4096);
+  VF_LAUNCH_TIMED(ctx, "jpeg_color", 0.0, 2.0 * L.plane_bytes, k_jpeg_color, dim3(gp, n), dim3(256), B);
+  VF_LAUNCH_CHECK();
+  return 0;
+}

@@ -6,16 +6,101 @@ draws the random numbers; cropping, masking, flipping, the [0,1] -> [-1,1] map a
 kernel per sample, writing straight into the batch buffers the closures read (`vf_clip_prepare`, `vf_center_prepare`).
 The resize before them — Torch7's image.scale in the loaders' loadImage / loadContImages — is on the device too
 (vf_image.hip): `image_scale`, `ImageBatcher` (train.lua's loader, one fused launch per image) and
-`ClipBatcher.add_frames` take decoded frames, so JPEG decode is the only host step left.
+`ClipBatcher.add_frames` take decoded frames.  The decode before them — image.load, libjpeg underneath — is on the
+device as well (vf_jpeg.hip): `decode_jpeg` turns a batch of baseline JPEG files into those frames,
+byte for byte what libjpeg gives, so the host only reads the files and draws the random numbers.
 """
 import math
+import os
+import re
 
 import numpy as np
 import torch
 
-from .backend import get_backend, nhwc_empty
+from ._lib import VfError
+from .backend import JPEG_STATUS, get_backend, jpeg_inspect, nhwc_empty
 
 CENTER_FILL = (117.0, 104.0, 123.0)      # train.lua:287-289
+
+
+# ------------------------------------------------------------------------------------------------ JPEG (DESIGN 5.2)
+def _jpeg_bytes(item):
+    """bytes of one JPEG file given as bytes / bytearray / memoryview, a uint8 array or tensor, or a path."""
+    if isinstance(item, (bytes, bytearray, memoryview)):
+        return bytes(item)
+    if isinstance(item, (str, os.PathLike)):
+        with open(item, "rb") as fh:
+            return fh.read()
+    if isinstance(item, torch.Tensor):
+        item = item.cpu().numpy()
+    a = np.asarray(item)
+    assert a.dtype == np.uint8, "a JPEG file as an array is uint8"
+    return a.tobytes()
+
+
+def jpeg_info(item):
+    """The host-side inspection of one JPEG file (no GPU): dict(width, height, components, h_samp, v_samp,
+    restart_interval, scan_begin, scan_end, supported, sof, segments, precision, reason).  ValueError if its headers
+    cannot be parsed (truncated, no SOS)."""
+    return jpeg_inspect(_jpeg_bytes(item))
+
+
+def decode_jpeg(items, channels=3, stack=False, fallback=None, subseq_bytes=256):
+    """image.load(path, channels) of a batch of JPEG files, decoded on the device in one pass (vf_jpeg_decode):
+    uint8 H x W x channels device tensors, byte for byte what libjpeg's default decompression gives (Pillow's
+    decode; Torch7's image.load followed by :mul(255)).  channels 3 replicates grayscale files; 1 takes grayscale
+    files only.
+
+    items: bytes, uint8 arrays or paths.  Returns a list of views into one device buffer, or with stack=True one
+    N x H x W x channels tensor (all sizes must match; ClipBatcher.add_frames takes it).  Files the device decoder does
+    not support (progressive, arithmetic, 12-bit, CMYK / RGB, 4:4:0, 4:1:1, multi-scan) go to fallback(bytes), which
+    returns the decoded uint8 H x W x channels image; without it they raise ValueError naming the item and why.  A
+    malformed file raises ValueError naming the item (before anything is launched when the headers or the restart
+    markers show it; once the stream has synchronised when the entropy-coded data is corrupt)."""
+    B = get_backend()
+    assert channels in (1, 3), "channels is 1 or 3"
+    files = [_jpeg_bytes(it) for it in items]
+    infos, dev, out = [], [], [None] * len(files)
+    for i, f in enumerate(files):
+        try:
+            info = jpeg_inspect(f, walk=False)   # the headers say whether it is supported; the decode walks the scan
+        except ValueError as e:
+            raise ValueError("decode_jpeg: item %d: %s" % (i, e)) from None
+        if info["supported"] and channels == 1 and info["components"] != 1:
+            info = dict(info, supported=False, reason="YCbCr file with channels=1")
+        if not info["supported"]:
+            if fallback is None:
+                raise ValueError("decode_jpeg: item %d is not supported by the device decoder: %s" % (i, info["reason"]))
+            img = torch.as_tensor(np.ascontiguousarray(fallback(f)))
+            if img.dim() == 2:
+                img = img.unsqueeze(-1)
+            assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == channels, \
+                "fallback returns uint8 H x W x %d, got %s %s" % (channels, img.dtype, tuple(img.shape))
+            out[i] = B.from_host(img).contiguous()
+            continue
+        infos.append(info)
+        dev.append(i)
+    buf = None
+    if dev:
+        try:
+            buf, offs, status, _ = B.jpeg_decode([files[i] for i in dev], channels, subseq_bytes, infos)
+        except VfError as e:   # found while walking the scan data (restart markers, fill bytes): nothing was launched
+            m = re.search(r"image (\d+)", str(e))
+            if m is None:
+                raise
+            raise ValueError("decode_jpeg: item %d: %s" % (dev[int(m.group(1))], e)) from None
+        st = status.cpu().tolist()
+        for j, i in enumerate(dev):
+            if st[j] != 0:
+                raise ValueError("decode_jpeg: item %d: corrupt entropy-coded data (%s)" % (i, JPEG_STATUS.get(st[j], st[j])))
+            out[i] = buf[offs[j]:offs[j + 1]].view(infos[j]["height"], infos[j]["width"], channels)
+    if not stack:
+        return out
+    shapes = {tuple(t.shape) for t in out}
+    assert len(shapes) == 1, "stack=True needs images of one size, got %s" % sorted(shapes)
+    if len(dev) == len(out):
+        return buf[:len(out) * out[0].numel()].view(len(out), *out[0].shape)
+    return torch.stack(out)
 
 
 # ---------------------------------------------------------------------------------------------- image.scale (DESIGN 5.1)
