@@ -22,10 +22,13 @@ def bench_name(k):
     if m:
         return "igemm_%sx%s_%s_v%s%s%s" % (m.group(1), m.group(2), "kmajorB" if m.group(3) == "true" else "rowB", m.group(4),
                                           suf.get(m.group(5) or "0", ""), "_db" if m.group(7) == "true" else "")
-    # k_pconv_dma<BM, BN, NTAPS> / k_pconv<BM, BN, WM, WN, NTAPS, CH, PAIR>
-    m = re.match(r"void k_pwgrad_group<(\d+)(?:, (\d+))?(?:, (\d+))?>", k)          # <stages, planes per operand, fragment sets>
+    # k_pwgrad_group<planes per operand, fragment sets>; older traces spell <stages, planes, fragment sets>, <stages, planes> (planes 3)
+    # and <stages> (three planes)
+    m = re.match(r"void k_pwgrad_group<(\d+(?:, \d+)*)>", k)
     if m:
-        return "pwgrad_group_128x128x32" + ("_bf16" if m.group(2) == "1" else "")
+        a = m.group(1).split(", ")
+        planes = a[1] if len(a) == 3 or a[1:] == ["3"] else a[0] if len(a) == 2 else "3"
+        return "pwgrad_group_128x128x32" + ("_bf16" if planes == "1" else "")
     # k_pconv_dma<BM, BN, NTAPS, LDS stages (1: the two-blocks-per-CU form), planes per operand (1: the bf16-operand mode)>
     m = re.match(r"void k_pconv_dma<(\d+), (\d+), (\d+)(?:, (\w+))?(?:, (\w+))?>", k)
     if m:
@@ -35,7 +38,7 @@ def bench_name(k):
     m = re.search(r"k_pconv_patch_tr<(\d)>", k)                                   # <parity classes per block>
     if m:
         return "pconv_patch_128x64_t4_c" + m.group(1)
-    m = re.search(r"k_pconv_patch_g<(\d), \w+, (\w+)>", k)                       # <MODE, stamps, TR>
+    m = re.search(r"k_pconv_patch_g<(\d)(?:, \w+)?, (\w+)>", k)                  # <MODE, TR>; older traces: <MODE, stamps, TR>
     if m:
         return "pconv_patchg_128x64_%s_m%s" % ("t4" if m.group(2) == "true" else "t16", m.group(1))
     if "k_pconv_patch_h" in k:
@@ -51,7 +54,8 @@ def bench_name(k):
     m = re.search(r"k_smallm_(rowdot|axpy)", k)
     if m:
         return "smallm_" + m.group(1)
-    m = re.match(r"void k_pconv<(\d+), (\d+), \d+, \d+, (\d+), (\d+), (\w+)>", k)
+    # k_pconv<BM, BN, WM, WN, NTAPS, CH>; older traces carry a last PAIR argument
+    m = re.match(r"void k_pconv<(\d+), (\d+), \d+, \d+, (\d+), (\d+)(?:, (\w+))?>", k)
     if m:
         return "pconv_%sx%sx%s_t%s%s" % (m.group(1), m.group(2), m.group(4), m.group(3), "_pair" if m.group(5) == "true" else "")
     m = re.match(r"(?:void )?k_([a-z0-9_]+)", k)      # k_adam -> adam, k_bn_stats -> bn_stats ...

@@ -738,6 +738,9 @@ def test_counter_summary_keys_kernels_the_way_the_bench_line_names_them():
         "void k_pconv_patch_g<0, false, false>(PGemm)": "pconv_patchg_128x64_t16_m0",
         "void k_pconv_patch_g<1, false, false>(PGemm)": "pconv_patchg_128x64_t16_m1",
         "void k_pconv_patch_g<2, false, true>(PGemm)": "pconv_patchg_128x64_t4_m2",
+        "void k_pconv_patch_g<0, false>(PGemm)": "pconv_patchg_128x64_t16_m0",
+        "void k_pconv_patch_g<1, false>(PGemm)": "pconv_patchg_128x64_t16_m1",
+        "void k_pconv_patch_g<2, true>(PGemm)": "pconv_patchg_128x64_t4_m2",
         "void k_pconv_patch_tr<4>(PGemm)": "pconv_patch_128x64_t4_c4",
         "void k_pconv_patch_tr<2>(PGemm)": "pconv_patch_128x64_t4_c2",
         "void k_pconv_dma<128, 64, 4, 1, 3>(PGemm)": "pconv_dma_128x64x64_t4_1stage",
@@ -748,6 +751,13 @@ def test_counter_summary_keys_kernels_the_way_the_bench_line_names_them():
         "void k_pwgrad_group<1, 3>(VfPWGradGroup)": "pwgrad_group_128x128x32",
         "void k_pwgrad_group<1, 3, 1>(VfPWGradGroup)": "pwgrad_group_128x128x32",
         "void k_pwgrad_group<1, 1, 2>(VfPWGradGroup)": "pwgrad_group_128x128x32_bf16",
+        "void k_pwgrad_group<1>(VfPWGradGroup)": "pwgrad_group_128x128x32",
+        "void k_pwgrad_group<3, 1>(VfPWGradGroup)": "pwgrad_group_128x128x32",
+        "void k_pwgrad_group<1, 2>(VfPWGradGroup)": "pwgrad_group_128x128x32_bf16",
+        "void k_pconv<128, 64, 64, 32, 4, 32, false>(PGemm)": "pconv_128x64x32_t4",
+        "void k_pconv<128, 64, 64, 32, 4, 32>(PGemm)": "pconv_128x64x32_t4",
+        "void k_adam<false>(float*, float const*, float*, float*, long, float, float, float, float, float, int const*)": "adam",
+        "void k_adam(float*, float const*, float*, float*, long, float, float, float, float, float, int const*)": "adam",
         "void (anonymous namespace)::k_adam_fused_multi<4, 3>((anonymous namespace)::VfFusedTable)": "adam_fused_wgrad",
         "void (anonymous namespace)::k_conv_thin_in<3>(float const*, float const*)": "conv_thin_in_planes",
     }

@@ -81,8 +81,6 @@ static BnGeom bn_geom(int64_t npix, int C, int target_blocks = 2048) {
 // Reduction kernels write one partial row per block and a second stage walks those rows column by column: fewer,
 // fatter blocks keep that second stage short (2048 rows made it the longest of BatchNorm's three launches).
 static int bn_stat_blocks(int64_t npix, int C, int bytes_per_block) {
-  static const int forced = getenv("VF_BN_STAT_BLOCKS") ? atoi(getenv("VF_BN_STAT_BLOCKS")) : 0;
-  if (forced > 0) return forced;
   // measured (scripts/bench_bn.py sweep, gpurun_out/bn_sweep.log): one block per 32 KB of a tensor read once (forward
   // statistics, bias gradients), per 16 KB of a tensor read beside two others (backward), between 128 and 512 blocks
   const int64_t b = npix * C * 4 / bytes_per_block;

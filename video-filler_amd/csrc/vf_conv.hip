@@ -126,8 +126,10 @@ struct IGemm {
   int gm, gn, gz;                  // logical grid (the launch is 1-D, remapped per XCD)
   int ksplit, nk, nq;              // K steps (of 32), number of splits, 16-wide chunks on the vector path
   int klin;                        // K order of the vector path: 1 = tap outer, channel chunk inner (see next_chunk)
-  int dbg;                         // ablation switch (timing experiments only; wrong results): 1 = no operand reload
-  long long* stamps;               // timing experiments only: 8 stamp slots per block (VF_IGEMM_STAMPS=<file>)
+  // always 0 / NULL (nothing sets them any more); the kernel still tests them — without those branches the compiler allocates
+  // k_igemm differently (the double-buffered mode-3 form: 100 -> 101 VGPRs, scratch in others)
+  int dbg;
+  long long* stamps;
   int act;
   float slope;
   const float* dmask;              // optional: out = act'(dmask[same index]) * out — the backward of the in-place activation
@@ -179,18 +181,6 @@ __device__ __forceinline__ void vf_bn_tile_partials(const VfBnSt& st, float (&s1
 // Everything outside the LDS tile (addresses, loads, epilogue, split-K) is shared with the fp32 path.
 // KLIN: K walked in memory order (tap outer, channel chunk inner) — the 1x1-output bottleneck layers (see next_chunk);
 // a template parameter so that no other instantiation carries its counters.
-// -DVF_IGEMM_SPY (timing experiments; scripts/probe/spy_report.py): thread 0 of block 7 stamps the shader clock between
-// the phases of each of its first 32 K steps of the single-buffered mode-3 loop, into rows 4096.. of the VF_IGEMM_STAMPS
-// buffer.  Compiled out otherwise.
-#ifdef VF_IGEMM_SPY
-#define VF_SPY(slot)                                                                                             \
-  do {                                                                                                           \
-    if (p.stamps && blockIdx.x == 7 && tid == 0 && kt - kt0 < 32)                                                \
-      p.stamps[8 * 4096 + (kt - kt0) * 8 + (slot)] = (long long)__builtin_readcyclecounter();                    \
-  } while (0)
-#else
-#define VF_SPY(slot) do { } while (0)
-#endif
 template <int I> struct VfIC { static constexpr int value = I; };
 // DB (mode 3, V = 2 only): double-buffered LDS with the split and the LDS writes of step k+1 issued between the MFMAs of
 // step k and the global loads running two steps ahead in a second register set — for launches whose grid leaves at
@@ -625,11 +615,9 @@ __global__ __launch_bounds__(256) void k_igemm(const IGemm p) {
     for (int kt = kt0; kt < kt1; ++kt) {
       const int buf = NBUF == 2 ? ((kt - kt0) & 1) : 0;
       const __bf16* base = (const __bf16*)smem + buf * (NP * PL_SZ);
-      VF_SPY(0);
       begin_tile(kt + 1, kt + 1 < kt1);
 #pragma unroll
       for (int pc = 0; pc < A_CH + B_CH; ++pc) load_piece(pc, VfIC<0>{});
-      VF_SPY(1);
 #pragma unroll
       for (int g = 0; g < BK / 16; ++g) {
         bf16x8 a[NP][MT], b[NP][NT];
@@ -664,13 +652,9 @@ __global__ __launch_bounds__(256) void k_igemm(const IGemm p) {
       // keep the split of the next step's pieces below this step's MFMAs: hoisted above them (it depends on the loads
       // only) it makes the wave wait for a load it issued two MFMAs earlier
       if constexpr (NBUF == 1) __builtin_amdgcn_sched_barrier(0);
-      VF_SPY(2);
       if constexpr (NBUF == 1) __syncthreads();       // everyone has read the tile before it is overwritten
-      VF_SPY(3);
       store_tile(NBUF == 2 ? (buf ^ 1) : 0);
-      VF_SPY(4);
       __syncthreads();
-      VF_SPY(5);
     }
   } else {
   constexpr int NPC = A_CH + B_CH;             // operand pieces per K step
@@ -1449,8 +1433,7 @@ static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, bool top = 
     const Tile cand[3] = {{128, 128}, {128, 64}, {64, 64}};
     // mode 3's single-buffered three-plane tiles hide their two barriers per K step with co-resident blocks: they want
     // twice the blocks (measured: +2 % per step at 1024 and above)
-    static const int env_min_blocks = getenv("VF_TILE_MIN_BLOCKS") ? atoi(getenv("VF_TILE_MIN_BLOCKS")) : 0;
-    const int tune_min_blocks = env_min_blocks ? env_min_blocks : (ctx->mfma_bf16 == 3 ? 1024 : 512);
+    const int min_blocks = ctx->mfma_bf16 == 3 ? 1024 : 512;
     int pick = 2;
     for (int i = 0; i < 3; ++i) {
       if (cand[i].bn > 64 && g.N <= 64) continue;
@@ -1458,7 +1441,7 @@ static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, bool top = 
       // epilogue; four 64x64 blocks per CU cover each other's ends better (E2 data-gradient: 122 -> 112 us)
       if (g.parity && g.nk <= 8 && cand[i].bm > 64) continue;
       const int64_t blocks = vf_cdiv(g.M, cand[i].bm) * vf_cdiv(g.N, cand[i].bn) * zpar;
-      if (blocks >= tune_min_blocks) {
+      if (blocks >= min_blocks) {
         pick = i;
         break;
       }
@@ -1467,13 +1450,12 @@ static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, bool top = 
     // (tried: 256 x 64 tiles — four 64x64 wave tiles stacked in M, one block per CU — for the N = 64 layers: 153 us
     //  against 125 us for E2's data-gradient; one wave per SIMD does not cover its own LDS/global latency)
   }
-  static const int env_split_blocks = getenv("VF_SPLIT_BLOCKS") ? atoi(getenv("VF_SPLIT_BLOCKS")) : 0;
-  const int tune_split_blocks = env_split_blocks ? env_split_blocks : 512;     // (768 for the M <= 64 GEMMs: a wash)
+  constexpr int split_blocks = 512;     // (768 for the M <= 64 GEMMs: a wash)
   const int gm = (int)vf_cdiv(g.M, t.bm), gn = (int)vf_cdiv(g.N, t.bn);
   const int64_t blocks = (int64_t)gm * gn * zpar;
   int ksplit = 1;
-  if (blocks < tune_split_blocks * 3 / 4 && g.nk >= 8) {
-    ksplit = (int)std::min<int64_t>(g.nk / 4, vf_cdiv(tune_split_blocks, blocks));
+  if (blocks < split_blocks * 3 / 4 && g.nk >= 8) {
+    ksplit = (int)std::min<int64_t>(g.nk / 4, vf_cdiv(split_blocks, blocks));
     const size_t slab_bytes = (size_t)g.out_elems * sizeof(float);
     while (ksplit > 1 && (size_t)ksplit * slab_bytes > vf_ws_avail(ctx)) --ksplit;
     if (ksplit < 1) ksplit = 1;
@@ -1532,31 +1514,13 @@ static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, bool top = 
     }
     ctx->bnf.mode = 0;
   }
-  static const int tune_dbg = getenv("VF_IGEMM_DBG") ? atoi(getenv("VF_IGEMM_DBG")) : 0;
-  g.dbg = tune_dbg;
-  static const int tune_klin = getenv("VF_NO_KLIN") ? 0 : 1;
-  g.klin = tune_klin && !g.parity && g.lgMh == 0 && g.lgMw == 0 && g.TH * g.TW > 1 && t.bm == 64 && t.bn == 128 && !bkm && v == 2;
+  g.klin = !g.parity && g.lgMh == 0 && g.lgMw == 0 && g.TH * g.TW > 1 && t.bm == 64 && t.bn == 128 && !bkm && v == 2;
   g.gm = gm; g.gn = gn; g.gz = zpar * ksplit;
   dim3 grid((unsigned)gm * gn * zpar * ksplit);
-  // timing experiments only: per-block stamps; every 32nd launch is synchronised and appended to the file
-  // VF_IGEMM_STAMPS names (the launches in between run unsynchronised, so the dumped one sees sustained conditions)
-  static const char* stamp_file = getenv("VF_IGEMM_STAMPS");
-  static long long* stamp_buf = nullptr;
-  static unsigned stamp_count = 0;
-  g.stamps = nullptr;
-  bool stamp_dump = false;
-  if (stamp_file && grid.x <= 32768) {
-    if (!stamp_buf) VF_CHECK_HIP(hipHostMalloc((void**)&stamp_buf, 8 * 32768 * sizeof(long long), hipHostMallocDefault));
-    g.stamps = stamp_buf;
-    stamp_dump = (++stamp_count % 32) == 0;
-    if (stamp_dump) VF_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  }
   char pname[64];
   // one name per kernel symbol (what rocprofv3 lists): k_igemm<bm, bn, ., ., kmajorB, v, mode>
   // double-buffered schedule: where the grid leaves at most two blocks per CU anyway (its 66 KB tiles cost nothing then)
-  static const int tune_db = getenv("VF_IGEMM_DB") ? atoi(getenv("VF_IGEMM_DB")) : 1;
-  const bool db = ctx->mfma_bf16 == 3 && v == 2 && t.bm == 64 && t.bn == 64 &&
-                  (tune_db == 2 || (tune_db == 1 && (int64_t)grid.x <= 2 * 256));
+  const bool db = ctx->mfma_bf16 == 3 && v == 2 && t.bm == 64 && t.bn == 64 && (int64_t)grid.x <= 2 * 256;
   snprintf(pname, sizeof(pname), "igemm_%dx%d_%s_v%d%s%s", t.bm, t.bn, bkm ? "kmajorB" : "rowB", v,
            ctx->mfma_bf16 == 3 ? "_bf16x3" : (ctx->mfma_bf16 ? "_bf16" : ""), db ? "_db" : "");
   if (sm_form >= 0) {
@@ -1575,26 +1539,6 @@ static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, bool top = 
       launch_igemm_tile<64, 64, 32, 32>(ctx, g, grid, bkm, v, pname, fl, db);
   }
   VF_LAUNCH_CHECK();
-  if (stamp_dump) {
-    VF_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    if (FILE* f = fopen(stamp_file, "a")) {
-      fprintf(f, "# %s blocks=%u M=%d N=%d K=%d ksplit=%d\n", pname, grid.x, g.M, g.N, Ktot, ksplit);
-      for (unsigned b = 0; b < grid.x; ++b) {
-        fprintf(f, "%u", b);
-        for (int q = 0; q < 6; ++q) fprintf(f, " %lld", g.stamps[8 * b + q]);
-        fprintf(f, "\n");
-      }
-#ifdef VF_IGEMM_SPY
-      for (unsigned b = 4096; b < 4128; ++b) {
-        fprintf(f, "S%u", b);
-        for (int q = 0; q < 6; ++q) fprintf(f, " %lld", g.stamps[8 * b + q]);
-        fprintf(f, "\n");
-        for (int q = 0; q < 8; ++q) g.stamps[8 * b + q] = 0;
-      }
-#endif
-      fclose(f);
-    }
-  }
   if (ksplit > 1) {
     VfProf prof(ctx, slab_st ? "slab_reduce_igemm_bnstats" : "slab_reduce_igemm", 0.0, 4.0 * (double)g.out_elems * (ksplit + 1));
     if (slab_st) {
@@ -2022,11 +1966,9 @@ static int wgrad(vf_ctx* ctx, const float* U, const float* V, float* dW, int B, 
   // split-K target, blocks per layer.  The planes layers ride in ONE group launch of seven or more layers, which fills the chip as
   // a whole: half the splits per layer leave k_pwgrad_group's time where it was and halve the slabs it writes and the combine
   // reads (same-box: combine 2 x 37.4 -> 2 x 21.8 us); the fp32-fed thin layers' kernel wants the full 512 (62 -> 86 us at 256)
-  static const int env_wg_blocks = getenv("VF_WGRAD_BLOCKS") ? atoi(getenv("VF_WGRAD_BLOCKS")) : 0;
-  static const int env_pwg_blocks = getenv("VF_PWGRAD_BLOCKS") ? atoi(getenv("VF_PWGRAD_BLOCKS")) : 0;
-  const int tune_wg_blocks = use_pw ? (env_pwg_blocks ? env_pwg_blocks : (env_wg_blocks ? env_wg_blocks : 256)) : (env_wg_blocks ? env_wg_blocks : 512);
-  if (blocks < tune_wg_blocks * 3 / 4 && g.nk >= 16) {
-    ksplit = (int)std::min<int64_t>(g.nk / 8, vf_cdiv(tune_wg_blocks, blocks));
+  const int wg_blocks = use_pw ? 256 : 512;
+  if (blocks < wg_blocks * 3 / 4 && g.nk >= 16) {
+    ksplit = (int)std::min<int64_t>(g.nk / 8, vf_cdiv(wg_blocks, blocks));
     while (ksplit > 1 && (size_t)ksplit * total * sizeof(float) > vf_ws_avail(ctx)) --ksplit;
     if (ksplit < 1) ksplit = 1;
     const int steps = (int)vf_cdiv(g.nk, ksplit);
@@ -2163,11 +2105,8 @@ VF_API int vf_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const floa
   if (!main_net_shape(H, W, k, stride, pad)) return vf_internal_gconv_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, k, stride, pad, act, slope);
   if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
   if (stride == 2 && Cin == 3 && !ctx->bnf.mode) {      // the image-side layers: direct convolution (vf_conv_thin.hip)
-    static const int no_thin = getenv("VF_NO_THIN") ? 1 : 0;
-    if (!no_thin) {
-      const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, nullptr, B, H, W, Cin, Cout, act, slope);
-      if (rc >= 0) return rc;
-    }
+    const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, nullptr, B, H, W, Cin, Cout, act, slope);
+    if (rc >= 0) return rc;
   }
   return conv_like_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, stride, pad, act, slope);
 }

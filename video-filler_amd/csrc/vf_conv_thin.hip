@@ -244,8 +244,7 @@ __global__ __launch_bounds__(256) void k_deconv_thin_out(const float* __restrict
 // shape is not this kernel's (the caller keeps its GEMM + col2im path), 0 when launched, > 0 on a launch error.
 int vf_internal_deconv_thin_out(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int Hi, int Wi, int C,
                                 int N, int act, float slope) {
-  static const bool off = getenv("VF_NO_THIN_OUT") != nullptr;
-  if (off || ctx->mfma_bf16 == 1) return -1;      // (the bf16-operand mode rounds its operands: the GEMM kernels' business)
+  if (ctx->mfma_bf16 == 1) return -1;      // (the bf16-operand mode rounds its operands: the GEMM kernels' business)
   if (N != 3 || C % 64 != 0 || Hi % 8 != 0 || Wi % 8 != 0 || (((uintptr_t)x) & 15) != 0 || (((uintptr_t)w) & 15) != 0) return -1;
   const int tiles_x = Wi / 8, tiles_y = Hi / 8;
   VfProf prof(ctx, "deconv_thin_out", 2.0 * (double)B * Hi * Wi * C * 16 * N, 0.0);

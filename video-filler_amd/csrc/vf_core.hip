@@ -632,24 +632,15 @@ __global__ void k_adam_prep(int32_t* state, double lr, double b1, double b2) {
   state[1] = __float_as_int((float)(lr * sqrt(bc2) / bc1));
 }
 // One pass: read x,g,m,v (16 B) ; write x,m,v (12 B) = 28 B/param.  fp32 op order follows optim/adam.lua.
-template <bool NT>
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ x, const float* __restrict__ g, float* __restrict__ m,
                                               float* __restrict__ v, int64_t n, float b1, float omb1, float b2, float omb2,
                                               float eps, const int32_t* __restrict__ state) {
   const float step = __int_as_float(state[1]);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x, n4 = n >> 2;
   auto upd = [&](float& xv, float gv, float& mv, float& vv) { vf_adam_upd(xv, gv, mv, vv, b1, omb1, b2, omb2, eps, step); };
-  auto ld = [&](const float* p, int64_t i) {
-    if constexpr (NT) return __builtin_nontemporal_load((const f32x4*)p + i);
-    else return ((const f32x4*)p)[i];
-  };
-  auto st = [&](float* p, int64_t i, f32x4 val) {
-    if constexpr (NT) __builtin_nontemporal_store(val, (f32x4*)p + i);
-    else ((f32x4*)p)[i] = val;
-  };
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
-    f32x4 xv = ld(x, i), mv = ld(m, i), vv = ld(v, i);
-    const f32x4 gv = ld(g, i);
+    f32x4 xv = ((const f32x4*)x)[i], mv = ((const f32x4*)m)[i], vv = ((const f32x4*)v)[i];
+    const f32x4 gv = ((const f32x4*)g)[i];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float xe = xv[e], me = mv[e], ve = vv[e];
@@ -658,24 +649,19 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ x, const float
       mv[e] = me;
       vv[e] = ve;
     }
-    st(x, i, xv);
-    st(m, i, mv);
-    st(v, i, vv);
+    ((f32x4*)x)[i] = xv;
+    ((f32x4*)m)[i] = mv;
+    ((f32x4*)v)[i] = vv;
   }
   for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) upd(x[i], g[i], m[i], v[i]);
 }
+static constexpr int ADAM_BLOCKS = 2048;      // grid cap of the grid-stride Adam passes
 static int adam_apply(vf_ctx* ctx, float* x, const float* g, float* m, float* v, int64_t n, double beta1, double beta2, double eps,
                       const int32_t* t_dev) {
   VF_REQUIRE((((uintptr_t)x | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam operands must be 16-byte aligned");
-  static const int tune_nt = getenv("VF_ADAM_NT") ? atoi(getenv("VF_ADAM_NT")) : 0;
-  static const int tune_blocks = getenv("VF_ADAM_BLOCKS") ? atoi(getenv("VF_ADAM_BLOCKS")) : 2048;
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(vf_cdiv(n, 1024), tune_blocks));
-  if (tune_nt)
-    VF_LAUNCH_TIMED(ctx, "adam", 0.0, 28.0 * (double)n, k_adam<true>, dim3(blocks), dim3(256), x, g, m, v, n, (float)beta1,
-                    (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, t_dev);
-  else
-    VF_LAUNCH_TIMED(ctx, "adam", 0.0, 28.0 * (double)n, k_adam<false>, dim3(blocks), dim3(256), x, g, m, v, n, (float)beta1,
-                    (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, t_dev);
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(vf_cdiv(n, 1024), ADAM_BLOCKS));
+  VF_LAUNCH_TIMED(ctx, "adam", 0.0, 28.0 * (double)n, k_adam, dim3(blocks), dim3(256), x, g, m, v, n, (float)beta1,
+                  (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, t_dev);
   VF_LAUNCH_CHECK();
   return 0;
 }
@@ -730,8 +716,7 @@ VF_API int vf_adam_apply_ranges(vf_ctx* ctx, float* x, const float* g, float* m,
   R.n = k;
   if (k == 0) return 0;
   const int64_t n = 4 * R.end4[k];
-  static const int tune_blocks = getenv("VF_ADAM_BLOCKS") ? atoi(getenv("VF_ADAM_BLOCKS")) : 2048;
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(vf_cdiv(n, 1024), tune_blocks));
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(vf_cdiv(n, 1024), ADAM_BLOCKS));
   VF_LAUNCH_TIMED(ctx, "adam", 0.0, 28.0 * (double)n, k_adam_ranges, dim3(blocks), dim3(256), x, g, m, v, R, (float)beta1,
                   (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, t_dev);
   VF_LAUNCH_CHECK();

@@ -51,8 +51,6 @@ namespace {
 double g_gate_gflop = getenv("VF_PCONV_MIN_GFLOP") ? atof(getenv("VF_PCONV_MIN_GFLOP")) : 3.0;
 int g_gate_rows = getenv("VF_PCONV_MIN_ROWS") ? atoi(getenv("VF_PCONV_MIN_ROWS")) : 1024;
 const bool g_no_pconv = getenv("VF_NO_PCONV") != nullptr;
-const bool g_no_act_bits = getenv("VF_NO_ACT_BITS") != nullptr;
-const bool g_no_head_fuse = getenv("VF_NO_HEAD_FUSE") != nullptr;     // (A/B switch: the head's Sigmoid backward as a launch of its own)      // (A/B switch: derivative masks from the fp32 activations only)
 const bool g_no_bn_fuse = getenv("VF_NO_BN_FUSE") != nullptr;
 const bool g_pwgrad = !(getenv("VF_PWGRAD") && strcmp(getenv("VF_PWGRAD"), "1") != 0);
 
@@ -275,7 +273,7 @@ int conv_forward(vf_net* n, Layer& l, const float* x, const void* in_planes, int
   const float* b = n->params + l.b_off;
   const bool full = is_full(l);
   l.out_planes = nullptr;
-  // every branch below rewrites l.y: sign bits a previous forward left (another planes gate, product mode or VF_NO_THIN then) no longer
+  // every branch below rewrites l.y: sign bits a previous forward left (another planes gate or product mode then) no longer
   // describe it, whichever branch this forward takes
   l.bits_live = false;
   const bool simple_act = act == VF_ACT_NONE || relu_like(act);
@@ -283,13 +281,13 @@ int conv_forward(vf_net* n, Layer& l, const float* x, const void* in_planes, int
     if (int rc = ensure_planes(n, &l.yp, (int64_t)n->B * l.Ho * l.Wo * l.Co)) return rc;
     // the sign bits of the activated output, for the derivative mask of the data-gradient pass above (2 MB read there instead of the
     // 67 MB activation); not under an activation observer, whose edits of y the bits would not follow (tests/helpers.py KinkSync)
-    if (relu_like(act) && !n->observer && !g_no_act_bits) {
+    if (relu_like(act) && !n->observer) {
       if (!l.ybits)
         if (int rc = net_alloc(n->act_owned, (void**)&l.ybits, sizeof(unsigned) * (size_t)n->B * l.Ho * l.Wo * (l.Co / 32))) return rc;
       ctx->act_bits_out = l.ybits;
     }
     const int frc = vf_conv2d_fwd_planes(ctx, x, w, b, l.y, l.yp, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, act, slope);
-    l.bits_live = ctx->act_bits_out == nullptr && ctx->act_bits_written && relu_like(act) && !n->observer && !g_no_act_bits;
+    l.bits_live = ctx->act_bits_out == nullptr && ctx->act_bits_written && relu_like(act) && !n->observer;
     ctx->act_bits_out = nullptr;
     ctx->act_bits_written = 0;
     if (frc) return frc;
@@ -567,7 +565,7 @@ int net_walk_back(vf_net* n, const float* x_in, const float* gy, const float** g
       // netD's 512 -> 1 head (train.lua:195-196: conv 4x4 on the 4x4 map + Sigmoid): the Sigmoid's derivative rides in the two dot
       // kernels of its backward pass (vf_ctx::dot_act_y) instead of a launch of its own over B values
       const bool dot_head = l.d.kind == VF_L_CONV && l.Co == 1 && l.d.k == 4 && l.d.stride == 1 && l.d.pad == 0 && l.H == 4 && l.W == 4 &&
-                            l.fused_act != VF_ACT_NONE && !relu_like(l.fused_act) && !act_done && !g_no_head_fuse;
+                            l.fused_act != VF_ACT_NONE && !relu_like(l.fused_act) && !act_done;
       if (l.fused_act != VF_ACT_NONE && !act_done && !dot_head) {
         // undo the activation applied in this layer's epilogue: in place on the incoming gradient where that is ours (an
         // in-place module does exactly that), else — the caller's gradOutput, Tanh / Sigmoid — into a buffer of its own

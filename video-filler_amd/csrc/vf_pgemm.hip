@@ -227,9 +227,11 @@ struct PGemm {
   const unsigned* dbits;   // the same mask as sign bits (vf_common.h act_bits_out layout), or NULL: read by the epilogue prefetch
   int dact;
   float dslope;
-  long long* stamps;     // timing experiments only (VF_PG_STAMPS=<file>, k_pconv_patch_g<., true>): shader-clock stamps per wave and step
-  int dbg;               // timing experiments only (VF_PG_DBG; wrong results): 1 = no operand loads after the first step,
-                         // 2 = no LDS writes after the first step, 4 = no MFMAs, 8 = no output stores, 32 = no first stage either (k_pconv_patch_g)
+  // always NULL / 0 (nothing sets them any more).  The K loops still test `dbg` around their loads, MFMAs and stores, and the struct
+  // keeps its layout: without those uniform branches the compiler allocates the loops differently — k_pconv_dma<128, 64, 16, 1> went
+  // from 112 to 183 VGPRs (four waves per SIMD to two), k_pconv_patch_g<0> from 164 to 197
+  long long* stamps;
+  int dbg;
   VfBnSt st;
 };
 
@@ -382,14 +384,8 @@ __device__ __forceinline__ void pg_epilogue(const PGemm& p, f32x16 (&acc)[MT][NT
 //            buffer, one barrier.
 //   CH = 64: one buffer (48 KB for 64x64: three blocks per CU); loads of step s+1 issued, MFMAs of step s, barrier,
 //            pieces to LDS, barrier — half the steps, the same number of barriers per K.
-// PAIR: a workgroup of 512 threads = TWO such tiles (threads 0-255 and 256-511, each with its own LDS tile buffers) whose
-// steps run in ANTI-PHASE: between two consecutive workgroup barriers one half issues its loads and runs its MFMAs while
-// the other waits for its loads and writes them to LDS.  Two independent 256-thread blocks on one CU drift into lockstep
-// (both in the load wait, then both in the MFMAs, then both in the LDS writes — a K step of the pair took the SUM of the
-// phases: matrix pipe 25 %, TA 33 %, LDS 25 % busy, waves a third of their time in s_waitcnt); the pairing pins the
-// complementary schedule.
-template <int BM, int BN, int WM, int WN, int NTAPS, int CH, bool PAIR>
-__global__ __launch_bounds__(PAIR ? 512 : 256) void k_pconv(const PGemm p) {
+template <int BM, int BN, int WM, int WN, int NTAPS, int CH>
+__global__ __launch_bounds__(256) void k_pconv(const PGemm p) {
   constexpr int MT = WM / 32, NT = WN / 32, WAVES_N = BN / WN;
   static_assert((BM / WM) * WAVES_N == 4, "4 waves per block");
   static_assert(CH == 32 || CH == 64, "K step of 32 or 64 channels");
@@ -399,19 +395,18 @@ __global__ __launch_bounds__(PAIR ? 512 : 256) void k_pconv(const PGemm p) {
   constexpr int AH_SZ = BM * CH, BH_SZ = BN * CH, PL_SZ = AH_SZ + BH_SZ;      // bf16 elements
   constexpr int BUF_SZ = 3 * PL_SZ;
   constexpr int NBUF = CH == 32 ? 2 : 1;
-  __shared__ __attribute__((aligned(16))) __bf16 smem_all[(PAIR ? 2 : 1) * NBUF * BUF_SZ];
-  const int sub = PAIR ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;      // which tile of the pair (wave-uniform)
-  __bf16* smem = smem_all + sub * (NBUF * BUF_SZ);
+  __shared__ __attribute__((aligned(16))) __bf16 smem[NBUF * BUF_SZ];
   auto sw_off = [](int row, int octet) {
     if constexpr (CH == 32) return row * 32 + ((octet ^ ((row >> 2) & 3)) << 3);
     else return row * 64 + ((octet ^ ((row >> 1) & 7)) << 3);
   };
 
+  // (the mask is redundant under the 256-thread bound, but without it the 128 x 64 four-tap form takes 144 VGPRs instead of 140)
   const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave / WAVES_N) * WM, wn = (wave % WAVES_N) * WN;
   const int ntiles = p.gm * p.gn * p.gz;
-  int lid = PAIR ? 2 * pg_xcd_remap(blockIdx.x, gridDim.x) + sub : pg_xcd_remap(blockIdx.x, ntiles);
-  const bool tile_ok = lid < ntiles;       // (an odd tile count leaves the last pair's second half idle: it keeps the barriers)
+  int lid = pg_xcd_remap(blockIdx.x, ntiles);
+  const bool tile_ok = lid < ntiles;
   if (!tile_ok) lid = 0;
   int ph = 0, pw = 0;
   if (p.parity) {
@@ -420,7 +415,7 @@ __global__ __launch_bounds__(PAIR ? 512 : 256) void k_pconv(const PGemm p) {
     lid >>= 2;
   }
   const int bx = lid % p.gm, byz = lid / p.gm;
-  const int m0 = tile_ok ? bx * BM : p.M, n0 = (byz % p.gn) * BN;      // idle half: every row out of range
+  const int m0 = tile_ok ? bx * BM : p.M, n0 = (byz % p.gn) * BN;      // (no tile: every row out of range)
   const int ks = byz / p.gn;
   const int cps = (p.nchunks + p.ksplit - 1) / p.ksplit;          // channel chunks per split
   const int ch0 = ks * cps, ch1 = min(p.nchunks, ch0 + cps);
@@ -558,8 +553,6 @@ __global__ __launch_bounds__(PAIR ? 512 : 256) void k_pconv(const PGemm p) {
   }
   __syncthreads();
   static_assert(NTAPS % 2 == 0, "the two LDS buffers alternate with the tap parity");
-  static_assert(!PAIR || NBUF == 1, "the paired schedule is built on the single-buffered (64-channel) step");
-  if (PAIR && sub == 1) __syncthreads();              // the second half runs one phase behind the first
   for (int ch = ch0; ch < ch1; ++ch) {
     const bool more = ch + 1 < ch1;
     // (the five multipliers pass through an empty asm each iteration: left alone, the compiler hoists all 2 x NTAPS tap
@@ -580,7 +573,6 @@ __global__ __launch_bounds__(PAIR ? 512 : 256) void k_pconv(const PGemm p) {
       __syncthreads();
     });
   }
-  if (PAIR && sub == 0) __syncthreads();              // (the barrier that pairs with the second half's last one)
 
   const float none[16] = {};
   pg_epilogue<MT, NT, BM / WM, BN>(p, acc, (float*)smem, m0, n0, wm, wn, lane, tid, wave / WAVES_N, bx, ks, ooy0, oox0, ph, pw, tile_ok,
@@ -1068,7 +1060,7 @@ __global__ __launch_bounds__(512) void k_pconv_patch_tr(const PGemm p) {
 // (MODE 0) / (slot >> 1) & 7 (MODE 1, 2): every ds_read_b128 lane group covers the 64 banks once for all sixteen (class, tap)
 // windows (checked exhaustively against MI355X_MICROARCH.md's lane groups; padding lanes read the zero slots at the bank position
 // their out-of-image slot would have had).
-// Measured on E3's forward pass (4.3 GFLOP, 256 tiles of 16 steps; scripts/bench_pconv.py, VF_PG_DBG ablations, one box): 30.7 us against
+// Measured on E3's forward pass (4.3 GFLOP, 256 tiles of 16 steps; scripts/bench_pconv.py, ablation builds, one box): 30.7 us against
 // 33.2 for k_pconv_dma; an empty launch of the same shape 9.0, MFMAs alone 25.3, DMAs alone 19.4 (k_pconv_dma: 25.2) — the fill
 // stream is 1.6x shorter, the matrix phase (1.0 us per 24-MFMA step and wave pair, 0.7 of it pipe time) now bounds the tile.  Two
 // role splits between a SIMD's two waves were built on this kernel, bit-identical, and dropped (profiles/r05_*gather*): waves 4-7
@@ -1091,9 +1083,6 @@ __global__ __launch_bounds__(512) void k_pconv_patch_tr(const PGemm p) {
 // Same six-term products in the same K order per output element as k_pconv_dma: bit-identical results.  N % 64 == 0, C % 64 == 0,
 // split-K over channel chunks as k_pconv_dma.  Semantics: nn.SpatialConvolution forward (train.lua:89-101, 183-193) and
 // nn.SpatialFullConvolution's data-gradient (train.lua:134-146).
-// ST: diagnostic build (VF_PG_STAMPS): lane 0 of every wave of the first 64 blocks stamps the shader clock at four points of each of its
-// first 16 steps — after the barrier, after its DMA issue, after its last MFMA, after its s_waitcnt — into p.stamps
-// (scripts/probe/pg_stamp_report.py)
 // TR (MODE 1, 2): the TRANSPOSED passes (conv data-gradient, full-conv forward) whose low-resolution grid is a whole 8 x 8 / 4 x 4 map —
 // the ones k_pconv_patch_tr's 8 x 16 regions do not cover (E4 / E5 and netD's deeper data-gradients, D2 / D3 forward: 8 launches of
 // configs[1]).  A block serves ONE output-parity class (ph, pw) of its 128 low-resolution rows, as k_pconv_dma does (the grid keeps
@@ -1101,7 +1090,7 @@ __global__ __launch_bounds__(512) void k_pconv_patch_tr(const PGemm p) {
 // once per 64-channel chunk and read by the class's four taps (th, tw) at (my + ph - 1 + th, mx + pw - 1 + tw): a unit is a chunk,
 // four steps each — 12 + 24.6 KB of fill per step instead of 72.  Same planes schedule, same products, same K order as k_pconv_dma
 // <., ., 4>: bit-identical results.
-template <int MODE, bool ST = false, bool TR = false>
+template <int MODE, bool TR = false>
 __global__ __launch_bounds__(512) void k_pconv_patch_g(const PGemm p) {
   static_assert(!TR || MODE != 0, "the transposed form serves whole-map tiles (8 x 16 regions of larger maps: k_pconv_patch_tr)");
   constexpr int NS = TR ? 4 : 16;                           // steps per channel chunk
@@ -1340,11 +1329,6 @@ __global__ __launch_bounds__(512) void k_pconv_patch_g(const PGemm p) {
       const int pb = TR ? (c & 1) : (cls & 1);
       const bool last_unit = (c + 1 == cps) && (TR || cls == 3);
       const int nch = (TR || cls == 3) ? ch + 1 : ch, ncls = TR ? 0 : ((cls + 1) & 3);      // the next unit
-      auto stamp = [&](int slot) {
-        if constexpr (ST) {
-          if (c == 0 && lane == 0 && blockIdx.x < 64) p.stamps[(((int)blockIdx.x * 8 + wave) * 16 + s_) * 4 + slot] = (long long)__builtin_amdgcn_s_memtime();
-        }
-      };
       // this wave's DMAs of THIS step's weights have landed — and, at a unit's first step, of its patch — and its LDS reads have
       // returned (the lo fragments read ahead during step 2 in particular, whose plane the DMAs of step 3 overwrite); after the barrier
       // everybody's have.  The hi / mid planes of the NEXT unit, issued behind the weights of steps 0 / 1, are not needed before that
@@ -1356,9 +1340,7 @@ __global__ __launch_bounds__(512) void k_pconv_patch_g(const PGemm p) {
       } else {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       }
-      stamp(3);          // (of the step that just ended: its slot 3 is written here, one step late — see the dump's reader)
       asm volatile("s_barrier" ::: "memory");
-      stamp(0);
       __builtin_amdgcn_sched_barrier(0);
       if (!(p.dbg & 1)) {
         if constexpr (s_ + 1 < NS) dma_w(ch, VfIntC<s_ + 1>{}, wbuf ^ 1, true);
@@ -1369,9 +1351,7 @@ __global__ __launch_bounds__(512) void k_pconv_patch_g(const PGemm p) {
       }
       if constexpr (t == 2) read_lo_ahead(VfIntC<s_ + 1>{});
       __builtin_amdgcn_sched_barrier(0);
-      stamp(1);
       if (!(p.dbg & 4)) compute_step(S, pb, wbuf);
-      stamp(2);
     });
   }
   // every DMA has landed and nobody still reads a weight stage when the epilogue's partial sums go there
@@ -1389,13 +1369,13 @@ __global__ __launch_bounds__(512) void k_pconv_patch_g(const PGemm p) {
 // ds_read_b64_tr_b16 (8 consecutive pixels of one channel per lane: the 32x32x16 operand map).  Rows are unpadded (the DMA
 // image is lane-linear), so the four pixel rows one transposing read touches are spread over the banks by an XOR of the
 // 64-byte block index with (row & 3), applied in the per-lane SOURCE address.  8 waves of a 32 x 64 accumulator tile.
-// NST = 1 (default): ONE stage in LDS (48 KB, three blocks per CU): issue the stage's DMAs, wait, barrier, MFMAs, barrier — a
-// block does not overlap its own loads and MFMAs, its CU-mates do; these grids are heavily split (tiles of 8-16 K steps, ten
-// rounds of blocks), and what bounds them is the start-up and drain of each tile, which co-resident blocks cover.
-// FS = 1 (default since round 5): ONE fragment set per wave — 73 registers instead of 124, so that three blocks per CU fit the register
+// ONE stage in LDS (48 KB, three blocks per CU): issue the stage's DMAs, wait, barrier, MFMAs, barrier — a block does not overlap
+// its own loads and MFMAs, its CU-mates do; these grids are heavily split (tiles of 8-16 K steps, ten rounds of blocks), and what
+// bounds them is the start-up and drain of each tile, which co-resident blocks cover.  (Three stages — 144 KB, one block per CU, DMAs
+// of stage k+2 issued before the MFMAs of stage k — measured 20 % slower: 42.9 against 34.7 us per 4.3 GFLOP layer.)
+// FS = 1 (since round 5): ONE fragment set per wave — 73 registers instead of 124, so that three blocks per CU fit the register
 // file as well as LDS (with two sets it held two: the occupancy this form was built around was never reached); -0.8 % on the iteration.
-// NST = 3: three stages (144 KB, one block per CU), DMAs of stage k+2 issued before the MFMAs of stage k, `s_waitcnt vmcnt(6)`
-// lets the newest stage stay in flight, one barrier per step: 20 % slower here (VF_PWG_STAGES=3).
+// FS = 2 serves the one-plane (bf16) mode.
 // Layers WITHOUT planes (Up == NULL: the bottleneck pair, plain [K][Nu] x [K][16 Cv] fp32 matrices) are staged by the block
 // itself — float4 loads, exact three-way split, 8-byte LDS writes into the same swizzled image — so that they share the launch.  Whole tiles only (Nu % 128 == 0, Cv % 64 == 0, P % 32 == 0): the host keeps
 // everything else on vf_conv.hip's k_wgrad.
@@ -1412,8 +1392,8 @@ __device__ __forceinline__ bf16x8 pg_tr_frag(const __bf16* tile, int col0, int k
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-template <int NST, int NPL = 3, int FS = 1>
-__global__ __launch_bounds__(512, (NST == 1 && FS == 1) ? 6 : 1) void k_pwgrad_group(const VfPWGradGroup G) {
+template <int NPL = 3, int FS = 1>
+__global__ __launch_bounds__(512, FS == 1 ? 6 : 1) void k_pwgrad_group(const VfPWGradGroup G) {
   int l = 0;
   while (l + 1 < G.n && (int)blockIdx.x >= G.blk_off[l + 1]) ++l;
   const VfPWGrad& p = G.d[l];
@@ -1421,7 +1401,7 @@ __global__ __launch_bounds__(512, (NST == 1 && FS == 1) ? 6 : 1) void k_pwgrad_g
   const int ntiles = p.gx * p.gy * p.gz;
   if (local >= ntiles) return;                       // padding blocks (uniform exit)
   constexpr int BK = 32, TILE = BK * 128, PL_SZ = 2 * TILE, ST_SZ = NPL * PL_SZ;      // bf16 elements
-  __shared__ __attribute__((aligned(1024))) __bf16 smem[NST * ST_SZ];
+  __shared__ __attribute__((aligned(1024))) __bf16 smem[ST_SZ];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1449,14 +1429,14 @@ __global__ __launch_bounds__(512, (NST == 1 && FS == 1) ? 6 : 1) void k_pwgrad_g
   unsigned szero;
   asm volatile("s_mov_b32 %0, 0" : "=s"(szero));
 
-  auto dma_stage = [&](int kt, int st, bool live) {
+  auto dma_stage = [&](int kt) {
     const int pix = kt * BK + krow;
     const int mx = pix & (Mw - 1), my = (pix >> p.lgMw) & (Mh - 1), b = pix >> (p.lgMw + p.lgMh);
     const int iy = 2 * my + dy, ix = 2 * mx + dx;
-    const bool okv = live && (unsigned)iy < (unsigned)p.Hv && (unsigned)ix < (unsigned)p.Wv;
-    const unsigned uo = live ? u_off + 2u * (unsigned)(pix * p.Nu) : VF_OOB;
+    const bool okv = (unsigned)iy < (unsigned)p.Hv && (unsigned)ix < (unsigned)p.Wv;
+    const unsigned uo = u_off + 2u * (unsigned)(pix * p.Nu);
     const unsigned vo = okv ? 2u * (unsigned)(((b * p.Hv + iy) * p.Wv + ix) * p.Cv + cch) : VF_OOB;
-    const unsigned base = lds0 + 2u * (unsigned)(st * ST_SZ) + row_lds;
+    const unsigned base = lds0 + row_lds;
 #pragma unroll
     for (int q = 0; q < NPL; ++q) {
       pg_dma16(base + 2u * (unsigned)(q * PL_SZ), uo, rsU, szero + q * p.u_ps);
@@ -1501,8 +1481,8 @@ __global__ __launch_bounds__(512, (NST == 1 && FS == 1) ? 6 : 1) void k_pwgrad_g
   for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-  auto compute_stage = [&](int st) {
-    const __bf16* base = smem + st * ST_SZ;
+  auto compute_stage = [&]() {
+    const __bf16* base = smem;
     if constexpr (FS == 1) {
       // ONE fragment set: a k-group's fragments are read, then multiplied — 73 registers instead of 124, so that the three blocks per CU
       // the 48 KB stage was sized for really are resident (six waves per SIMD; with two sets the register file held two blocks).  The wave
@@ -1565,34 +1545,16 @@ __global__ __launch_bounds__(512, (NST == 1 && FS == 1) ? 6 : 1) void k_pwgrad_g
     for (int kt = kt0; kt < kt1; ++kt) {
       stage_fp32(kt);
       __syncthreads();
-      compute_stage(0);
+      compute_stage();
       __syncthreads();
     }
-  } else if constexpr (NST == 3) {
-    // ---- K loop: stages kt and kt + 1 are in flight when stage kt is waited for; every wave issues 6 DMAs per stage, live or not
-    dma_stage(kt0, 0, kt0 < kt1);
-    dma_stage(kt0 + 1, 1, kt0 + 1 < kt1);
-    int st = 0;
-    for (int kt = kt0; kt < kt1; ++kt) {
-      // the 6 newest DMAs of this wave (stage kt + 1) may stay outstanding; after the barrier everybody's stage kt has landed
-      // and nobody still reads the buffer stage kt + 2 goes to (it held stage kt - 1)
-      if constexpr (NPL == 3) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      const int st2 = st >= 1 ? st - 1 : 2;                        // (st + 2) % 3
-      dma_stage(kt + 2, st2, kt + 2 < kt1);
-      __builtin_amdgcn_sched_barrier(0);
-      compute_stage(st);
-      st = st == 2 ? 0 : st + 1;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the dead prefetches (zeros) have landed before the block ends
   } else {
     // ---- ONE stage (48 KB: three blocks per CU): a block does not overlap its own DMAs and MFMAs, its CU-mates do
     for (int kt = kt0; kt < kt1; ++kt) {
-      dma_stage(kt, 0, true);
+      dma_stage(kt);
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
-      compute_stage(0);
+      compute_stage();
       asm volatile("s_barrier" ::: "memory");
     }
   }
@@ -1617,28 +1579,22 @@ __global__ __launch_bounds__(512, (NST == 1 && FS == 1) ? 6 : 1) void k_pwgrad_g
 }
 
 int vf_internal_pwgrad_group(vf_ctx* ctx, const VfPWGradGroup& G, int blocks, const char* name, double flops) {
-  static const int env_nst = getenv("VF_PWG_STAGES") ? atoi(getenv("VF_PWG_STAGES")) : 1;   // 1: 48 KB, three blocks per CU (measured 34.7 vs 42.9 us per 4.3 GFLOP layer)
-  static const int env_fs = getenv("VF_PWG_FS") ? atoi(getenv("VF_PWG_FS")) : 1;            // fragment sets per wave: 1 (three blocks per CU fit the register file too), 2 (round 2-4)
-  if (ctx->mfma_bf16 == 1) {      // one rounded plane per operand: 16 KB stages
-    VF_LAUNCH_TIMED(ctx, "pwgrad_group_128x128x32_bf16", flops, 0.0, (k_pwgrad_group<1, 1, 2>), dim3((unsigned)blocks), dim3(512), G);
-    VF_LAUNCH_CHECK();
-    return 0;
-  }
-  if (env_nst == 1 && env_fs != 2) VF_LAUNCH_TIMED(ctx, name, flops, 0.0, (k_pwgrad_group<1, 3, 1>), dim3((unsigned)blocks), dim3(512), G);
-  else if (env_nst == 1) VF_LAUNCH_TIMED(ctx, name, flops, 0.0, (k_pwgrad_group<1, 3, 2>), dim3((unsigned)blocks), dim3(512), G);
-  else VF_LAUNCH_TIMED(ctx, name, flops, 0.0, (k_pwgrad_group<3, 3, 2>), dim3((unsigned)blocks), dim3(512), G);
+  if (ctx->mfma_bf16 == 1)      // one rounded plane per operand: 16 KB stages
+    VF_LAUNCH_TIMED(ctx, "pwgrad_group_128x128x32_bf16", flops, 0.0, (k_pwgrad_group<1, 2>), dim3((unsigned)blocks), dim3(512), G);
+  else
+    VF_LAUNCH_TIMED(ctx, name, flops, 0.0, (k_pwgrad_group<3, 1>), dim3((unsigned)blocks), dim3(512), G);
   VF_LAUNCH_CHECK();
   return 0;
 }
 
 // ================================================================================================ host
-// which kernel serves a planes pass is a tiling decision; the two patch-fed forms can be switched per process (A/B runs, and the tests
-// that compare them with k_pconv_dma bit for bit): defaults from VF_PG_GPATCH / VF_PG_PATCH, vf_pconv_set_routing overrides
-static int g_gather_patch = getenv("VF_PG_GPATCH") ? atoi(getenv("VF_PG_GPATCH")) : 1;     // 0 off, 1 on
-static int g_scatter_patch = getenv("VF_PG_PATCH") ? atoi(getenv("VF_PG_PATCH")) : 1;      // 0 off, 1 auto, 2 / 4 classes per block
+// which kernel serves a planes pass is a tiling decision; the two patch-fed forms can be switched off per process (A/B runs, and the
+// tests that compare them with k_pconv_dma bit for bit) through vf_pconv_set_routing
+static int g_gather_patch = 1;      // k_pconv_patch_g for the gather passes: 0 off, 1 on
+static int g_scatter_patch = 1;     // k_pconv_patch_tr and k_pconv_patch_g's TR form for the transposed passes: 0 off, 1 on
 VF_API int vf_pconv_set_routing(int gather_patch, int scatter_patch) {
-  if (gather_patch >= 0) g_gather_patch = gather_patch;
-  if (scatter_patch >= 0) g_scatter_patch = scatter_patch;
+  if (gather_patch >= 0) g_gather_patch = gather_patch != 0;
+  if (scatter_patch >= 0) g_scatter_patch = scatter_patch != 0;
   return 0;
 }
 
@@ -1654,32 +1610,38 @@ static bool pg_shape_ok(int B, int Hl, int Wl, int C, int N) {
   return C % 32 == 0 && N >= 32 && N % 4 == 0 && (int64_t)B * Hl * Wl > 64 && vf_is_pow2(Hl) && vf_is_pow2(Wl);
 }
 
+typedef void (*PgKernel)(PGemm);
+
+template <int BM, int NTAPS>
+static PgKernel pg_dma_kernel(bool one_plane, bool one_stage) {
+  if (one_plane) return k_pconv_dma<BM, 64, NTAPS, 2, 1>;
+  return one_stage ? k_pconv_dma<BM, 64, NTAPS, 1> : k_pconv_dma<BM, 64, NTAPS, 2>;
+}
+
+template <int BM, int WM, int NTAPS>
+static PgKernel pg_reg_kernel(int ch) {
+  return ch == 64 ? k_pconv<BM, 64, WM, 32, NTAPS, 64> : k_pconv<BM, 64, WM, 32, NTAPS, 32>;
+}
+
 static int launch_pconv(vf_ctx* ctx, PGemm& g, int ntaps, const char* what) {
+  // ---- channel step, tile, split-K
   const int zpar = g.parity ? 4 : 1;
-  static const int env_ch = getenv("VF_PG_CH") ? atoi(getenv("VF_PG_CH")) : 0;
-  const int ch = (g.C % 64 == 0 && env_ch != 32) ? 64 : 32;      // channels per K step: whole 128-byte lines where possible
+  const int ch = g.C % 64 == 0 ? 64 : 32;      // channels per K step: whole 128-byte lines where possible
   g.nchunks = g.C / ch;
-  // tile: 128x64 when that still fills the chip twice over, else 64x64; split-K over channel chunks for the small grids
-  struct Tile { int bm, bn; };
-  static const int env_tile = getenv("VF_PG_TILE") ? atoi(getenv("VF_PG_TILE")) : 0;
-  static const int env_dma0 = getenv("VF_PG_DMA") ? atoi(getenv("VF_PG_DMA")) : 1;
-  const Tile cand[2] = {{128, 64}, {64, 64}};
-  int pick = 1;
-  if (env_tile == 128) pick = 0;
-  else if (env_tile == 0 && vf_cdiv(g.M, 128) * vf_cdiv(g.N, 64) * zpar >= 1024) pick = 0;
-  // the LDS-DMA kernel: 64-channel stages, whole tiles (its row decode has no ragged edge), 128x64 tiles of 8 waves by default
-  bool use_dma = env_dma0 && ch == 64 && g.N % 64 == 0;
-  if (use_dma) {
-    if (env_tile == 0) pick = (g.M % 128 == 0) ? 0 : 1;
-    if (g.M % cand[pick].bm != 0) use_dma = false;
-  }
-  const Tile t = cand[pick];
-  const int gm = (int)vf_cdiv(g.M, t.bm), gn = (int)vf_cdiv(g.N, t.bn);
+  // the LDS-DMA kernels take 64-channel stages and whole tiles (their row decode has no ragged edge): 128 x 64 tiles where the rows
+  // divide, else 64 x 64; the register-staged k_pconv takes 128 x 64 when that still fills the chip twice over, else 64 x 64
+  constexpr int bn = 64;
+  const bool dma_shape = ch == 64 && g.N % bn == 0;
+  const int bm = dma_shape ? (g.M % 128 == 0 ? 128 : 64) : (vf_cdiv(g.M, 128) * vf_cdiv(g.N, bn) * zpar >= 1024 ? 128 : 64);
+  const bool use_dma = dma_shape && g.M % bm == 0;
+  const int gm = (int)vf_cdiv(g.M, bm), gn = (int)vf_cdiv(g.N, bn);
   const int64_t blocks = (int64_t)gm * gn * zpar;
+  // split-K over channel chunks for the small grids.  A grid of 256 tiles (one per CU) is left whole: measured 27.6 vs 39.2 us
+  // (E4 data-gradient) against splitting it in two
+  constexpr int SPLIT_BLOCKS = 340;
   int ksplit = 1;
-  static const int env_split = getenv("VF_PG_SPLIT_BLOCKS") ? atoi(getenv("VF_PG_SPLIT_BLOCKS")) : 340;   // a grid of 256 tiles (one per CU) is left whole: measured 27.6 vs 39.2 us (E4 data-gradient) against splitting it in two
-  if (blocks < env_split * 3 / 4 && g.nchunks >= 2) {
-    ksplit = (int)std::min<int64_t>(g.nchunks, vf_cdiv(env_split, blocks));
+  if (blocks < SPLIT_BLOCKS * 3 / 4 && g.nchunks >= 2) {
+    ksplit = (int)std::min<int64_t>(g.nchunks, vf_cdiv(SPLIT_BLOCKS, blocks));
     const size_t slab_bytes = (size_t)g.out_elems * sizeof(float);
     while (ksplit > 1 && (size_t)ksplit * slab_bytes > vf_ws_avail(ctx)) --ksplit;
     while (ksplit > 1 && g.nchunks % ksplit != 0) --ksplit;      // equal K ranges: every tile runs the same number of steps
@@ -1687,8 +1649,7 @@ static int launch_pconv(vf_ctx* ctx, PGemm& g, int ntaps, const char* what) {
   g.ksplit = ksplit;
   g.slab = ksplit > 1 ? (float*)vf_ws_ptr(ctx) : nullptr;
   g.gm = gm; g.gn = gn; g.gz = zpar * ksplit;
-  static const int env_dbg = getenv("VF_PG_DBG") ? atoi(getenv("VF_PG_DBG")) : 0;
-  g.dbg = env_dbg;
+  const unsigned nt = (unsigned)(blocks * ksplit);
   // ---- BatchNorm statistics attachment (vf_bn_fuse_next_*): same contract as vf_conv.hip's launch_igemm
   g.st.mode = 0;
   bool slab_st = false;
@@ -1699,7 +1660,7 @@ static int launch_pconv(vf_ctx* ctx, PGemm& g, int ntaps, const char* what) {
     bool fused = false;
     int bpg = 0;
     if (ksplit == 1) {
-      if (g.M % groups == 0 && (g.M / groups) % t.bm == 0 && (int64_t)(gm / groups) * zpar <= ctx->bnf_rows_cap) {
+      if (g.M % groups == 0 && (g.M / groups) % bm == 0 && (int64_t)(gm / groups) * zpar <= ctx->bnf_rows_cap) {
         st.tiles_per_group = gm / groups;
         st.zpar = zpar;
         st.rows_per_group = (gm / groups) * zpar;
@@ -1728,174 +1689,66 @@ static int launch_pconv(vf_ctx* ctx, PGemm& g, int ntaps, const char* what) {
   const bool one_plane = ctx->mfma_bf16 == 1;
   VF_REQUIRE(!one_plane || use_dma, "vf_pconv: in the bf16-operand mode the planes path serves whole 64-channel / 64-row tiles only "
              "(vf_pconv_supported_in_mode)");
+
+  // ---- kernel
+  const char* taps = ntaps == 16 ? "t16" : "t4";
+  const double fl = 2.0 * (double)g.M * g.N * (double)ntaps * g.C * zpar;
+  // algorithmic bytes of the DMA-fed kernels: operand planes and weight planes once, the output (or its split-K slabs), and what the
+  // epilogue reads (derivative mask, BatchNorm input) — bench.py prices a kernel against the LONGER of its two floors
+  const double dby = (double)g.a_bytes + (double)g.w_bytes + 4.0 * (double)g.out_elems * ksplit +
+                     (g.dmask ? (g.dbits ? 0.125 : 4.0) * (double)g.out_elems : 0.0) + (g.st.mode == 2 ? 4.0 * (double)g.out_elems : 0.0);
+  char name[64];
+  PgKernel kern;
+  dim3 grid(nt), block(bm == 128 ? 512 : 256);
+  double by = dby;
+  const int Ho = 1 << g.lgMh, Wo = 1 << g.lgMw;
+  const int gmode = (Wo % 16 == 0 && Ho % 8 == 0) ? 0 : (Ho == 8 && Wo == 8) ? 1 : (Ho == 4 && Wo == 4) ? 2 : -1;
   if (use_dma && one_plane) {
     // one rounded plane per operand: 128x64 stages of 24 KB (two stages: 48 KB, three blocks per CU), 64x64 of 16 KB
-    const unsigned nt = (unsigned)(gm * gn * zpar * ksplit);
-    char dname[64];
-    snprintf(dname, sizeof(dname), "pconv_dma_%dx%dx64_%s_bf16", t.bm, t.bn, ntaps == 16 ? "t16" : "t4");
-    const double dfl = 2.0 * (double)g.M * g.N * (double)ntaps * g.C * zpar;
-    // algorithmic bytes: operand planes and weight planes once, the output (or its split-K slabs), and what the epilogue reads
-    // (derivative mask, BatchNorm input) — bench.py prices a kernel against the LONGER of its two floors
-    const double dby = (double)g.a_bytes + (double)g.w_bytes + 4.0 * (double)g.out_elems * (ksplit > 1 ? ksplit : 1) +
-                       (g.dmask ? (g.dbits ? 0.125 : 4.0) * (double)g.out_elems : 0.0) + (g.st.mode == 2 ? 4.0 * (double)g.out_elems : 0.0);
-    if (t.bm == 128) {
-      if (ntaps == 16) VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<128, 64, 16, 2, 1>), dim3(nt), dim3(512), g);
-      else VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<128, 64, 4, 2, 1>), dim3(nt), dim3(512), g);
-    } else {
-      if (ntaps == 16) VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<64, 64, 16, 2, 1>), dim3(nt), dim3(256), g);
-      else VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<64, 64, 4, 2, 1>), dim3(nt), dim3(256), g);
-    }
-    VF_LAUNCH_CHECK();
-    if (ksplit > 1) {
-      VfProf prof(ctx, slab_st ? "slab_reduce_pconv_bnstats" : "slab_reduce_pconv", 0.0, 4.0 * (double)g.out_elems * (ksplit + 1));
-      return vf_internal_slab_reduce(ctx, g.slab, g.Y, g.bias, g.out_elems, g.N, ksplit, g.act, g.slope, g.dmask, g.dact, g.dslope,
-                                     slab_st ? &g.st : nullptr, st_groups);
-    }
-    return 0;
-  }
-  static const int env_dma = getenv("VF_PG_DMA") ? atoi(getenv("VF_PG_DMA")) : 1;
-  if (use_dma) {
-    const unsigned nt = (unsigned)(gm * gn * zpar * ksplit);
-    char dname[64];
-    snprintf(dname, sizeof(dname), "pconv_dma_%dx%dx64_%s", t.bm, t.bn, ntaps == 16 ? "t16" : "t4");
-    const double dfl = 2.0 * (double)g.M * g.N * (double)ntaps * g.C * zpar;
-    // algorithmic bytes: operand planes and weight planes once, the output (or its split-K slabs), and what the epilogue reads
-    // (derivative mask, BatchNorm input) — bench.py prices a kernel against the LONGER of its two floors
-    const double dby = (double)g.a_bytes + (double)g.w_bytes + 4.0 * (double)g.out_elems * (ksplit > 1 ? ksplit : 1) +
-                       (g.dmask ? (g.dbits ? 0.125 : 4.0) * (double)g.out_elems : 0.0) + (g.st.mode == 2 ? 4.0 * (double)g.out_elems : 0.0);
+    snprintf(name, sizeof(name), "pconv_dma_%dx%dx64_%s_bf16", bm, bn, taps);
+    kern = bm == 128 ? (ntaps == 16 ? pg_dma_kernel<128, 16>(true, false) : pg_dma_kernel<128, 4>(true, false))
+                     : (ntaps == 16 ? pg_dma_kernel<64, 16>(true, false) : pg_dma_kernel<64, 4>(true, false));
+  } else if (use_dma && g_scatter_patch && ntaps == 4 && g.parity && ksplit == 1 && bm == 128 && g.Wi % 16 == 0 && g.Hi % 8 == 0 &&
+             (g.act == VF_ACT_NONE || g.act == VF_ACT_LRELU || g.act == VF_ACT_RELU) &&
+             g.out_elems * 4 < ((int64_t)1 << 31)) {       // (its epilogue addresses the output through 32-bit buffer offsets)
+    // transposed passes on grids of at least 8 x 16: the patch kernel (k_pconv_patch_tr), 4 parity classes per block where that still
+    // gives two rounds of blocks, else 2
+    const unsigned tiles = (unsigned)(g.M / 128), slices = (unsigned)(g.N / 64);
+    const int cpb = tiles * slices >= 512 ? 4 : 2;
+    snprintf(name, sizeof(name), "pconv_patch_128x64_t4_c%d", cpb);
+    grid = dim3(tiles * slices * (cpb == 2 ? 2u : 1u));
+    kern = cpb == 4 ? k_pconv_patch_tr<4> : k_pconv_patch_tr<2>;
+  } else if (use_dma && g_gather_patch && ntaps == 16 && !g.parity && bm == 128 && g.sy == 2 && g.sx == 2 && gmode >= 0) {
+    // gather passes (conv forward, full-conv data-gradient) on whole 128-row tiles: the patch kernel (k_pconv_patch_g)
+    snprintf(name, sizeof(name), "pconv_patchg_128x64_t16_m%d", gmode);
+    kern = gmode == 0 ? k_pconv_patch_g<0> : gmode == 1 ? k_pconv_patch_g<1> : k_pconv_patch_g<2>;
+  } else if (use_dma && g_scatter_patch && ntaps == 4 && g.parity && bm == 128 && nt < 512 &&
+             ((g.Hi == 8 && g.Wi == 8) || (g.Hi == 4 && g.Wi == 4))) {
+    // transposed passes whose low-resolution grid is a whole 8 x 8 / 4 x 4 map (what k_pconv_patch_tr's 8 x 16 regions do not cover): the
+    // patch kernel's TR form, one output-parity class per block as k_pconv_dma
+    // (grids of one tile per CU only: from two rounds of blocks the single-stage k_pconv_dma, two blocks per CU, is faster —
+    //  netD's third conv at 2B, 512 blocks: 45.6 us against 46.5, with its derivative mask 51.9 against 59.7)
+    const int mode = g.Hi == 8 ? 1 : 2;
+    snprintf(name, sizeof(name), "pconv_patchg_128x64_t4_m%d", mode);
+    kern = mode == 1 ? k_pconv_patch_g<1, true> : k_pconv_patch_g<2, true>;
+  } else if (use_dma) {
     // a grid of at least two tiles per CU runs the single-stage variant, two blocks per CU (measured, scripts/bench_pconv.py:
     // E2 transposed pass 79 -> 67 us, E2 gather 68 -> 62, E3 transposed 31.2 -> 28.8, netD's first layer at 2B 58 -> 53;
     // with one tile per CU the second stage is what is needed instead: E3 gather 29.7 vs 39.8 single-stage)
-    // transposed passes on grids of at least 8 x 16: the patch kernel (k_pconv_patch_tr).  VF_PG_PATCH: 0 off, 2 / 4 = that many parity
-    // classes per block, 1 (default) = 4 where that still gives two rounds of blocks, else 2
-    const int env_patch = g_scatter_patch;
-    if (env_patch && ntaps == 4 && g.parity && g.N % 64 == 0 && ksplit == 1 && t.bm == 128 && g.Wi % 16 == 0 && g.Hi % 8 == 0 &&
-        (g.act == VF_ACT_NONE || g.act == VF_ACT_LRELU || g.act == VF_ACT_RELU) &&
-        g.out_elems * 4 < ((int64_t)1 << 31)) {       // (its epilogue addresses the output through 32-bit buffer offsets)
-      const unsigned tiles = (unsigned)(g.M / 128), slices = (unsigned)(g.N / 64);
-      const int cpb = env_patch == 2 || env_patch == 4 ? env_patch : (tiles * slices >= 512 ? 4 : 2);
-      snprintf(dname, sizeof(dname), "pconv_patch_128x64_t4_c%d", cpb);
-      const dim3 pgrid(tiles * slices * (cpb == 2 ? 2u : 1u));
-      if (cpb == 4) VF_LAUNCH_TIMED(ctx, dname, dfl, dby, k_pconv_patch_tr<4>, pgrid, dim3(512), g);
-      else VF_LAUNCH_TIMED(ctx, dname, dfl, dby, k_pconv_patch_tr<2>, pgrid, dim3(512), g);
-      VF_LAUNCH_CHECK();
-      return 0;
-    }
-    // gather passes (conv forward, full-conv data-gradient) on whole 128-row tiles: the patch kernel (k_pconv_patch_g).  VF_PG_GPATCH=0
-    // keeps k_pconv_dma's tap-by-tap stages
-    const int env_gpatch = g_gather_patch;
-    if (env_gpatch && ntaps == 16 && !g.parity && g.N % 64 == 0 && t.bm == 128 && g.sy == 2 && g.sx == 2) {
-      const int Ho = 1 << g.lgMh, Wo = 1 << g.lgMw;
-      const int mode = (Wo % 16 == 0 && Ho % 8 == 0) ? 0 : (Ho == 8 && Wo == 8) ? 1 : (Ho == 4 && Wo == 4) ? 2 : -1;
-      if (mode >= 0) {
-        snprintf(dname, sizeof(dname), "pconv_patchg_128x64_t16_m%d", mode);
-        // timing experiments only (VF_PG_STAMPS=<file>): the stamped build of the 8 x 16-tile form; every 16th launch is synchronised and dumped
-        static const char* stamp_file = getenv("VF_PG_STAMPS");
-        if (stamp_file && mode == 0 && ksplit == 1) {
-          static long long* stamp_buf = nullptr;
-          static unsigned stamp_count = 0;
-          constexpr size_t NST = (size_t)64 * 8 * 16 * 4;
-          if (!stamp_buf) VF_CHECK_HIP(hipHostMalloc((void**)&stamp_buf, NST * sizeof(long long), hipHostMallocDefault));
-          g.stamps = stamp_buf;
-          const bool dump = (++stamp_count % 16) == 0;
-          if (dump) {
-            VF_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-            memset(stamp_buf, 0, NST * sizeof(long long));
-          }
-          hipLaunchKernelGGL((k_pconv_patch_g<0, true>), dim3(nt), dim3(512), 0, ctx->stream, g);
-          VF_LAUNCH_CHECK();
-          if (dump) {
-            VF_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-            if (FILE* f = fopen(stamp_file, "ab")) {
-              const int hdr[4] = {(int)nt, g.M, g.N, g.C};
-              fwrite(hdr, sizeof(hdr), 1, f);
-              fwrite(stamp_buf, sizeof(long long), NST, f);
-              fclose(f);
-            }
-          }
-          return 0;
-        }
-        if (mode == 0) VF_LAUNCH_TIMED(ctx, dname, dfl, dby, k_pconv_patch_g<0>, dim3(nt), dim3(512), g);
-        else if (mode == 1) VF_LAUNCH_TIMED(ctx, dname, dfl, dby, k_pconv_patch_g<1>, dim3(nt), dim3(512), g);
-        else VF_LAUNCH_TIMED(ctx, dname, dfl, dby, k_pconv_patch_g<2>, dim3(nt), dim3(512), g);
-        VF_LAUNCH_CHECK();
-        if (ksplit > 1) {
-          VfProf prof(ctx, slab_st ? "slab_reduce_pconv_bnstats" : "slab_reduce_pconv", 0.0, 4.0 * (double)g.out_elems * (ksplit + 1));
-          return vf_internal_slab_reduce(ctx, g.slab, g.Y, g.bias, g.out_elems, g.N, ksplit, g.act, g.slope, g.dmask, g.dact, g.dslope,
-                                         slab_st ? &g.st : nullptr, st_groups);
-        }
-        return 0;
-      }
-    }
-    // transposed passes whose low-resolution grid is a whole 8 x 8 / 4 x 4 map (what k_pconv_patch_tr's 8 x 16 regions do not cover): the
-    // patch kernel's TR form, one output-parity class per block as here
-    // (grids of one tile per CU only: from two rounds of blocks the single-stage k_pconv_dma, two blocks per CU, is faster —
-    //  netD's third conv at 2B, 512 blocks: 45.6 us against 46.5, with its derivative mask 51.9 against 59.7)
-    if (env_patch && ntaps == 4 && g.parity && g.N % 64 == 0 && t.bm == 128 && nt < 512 &&
-        ((g.Hi == 8 && g.Wi == 8) || (g.Hi == 4 && g.Wi == 4))) {
-      const int mode = g.Hi == 8 ? 1 : 2;
-      snprintf(dname, sizeof(dname), "pconv_patchg_128x64_t4_m%d", mode);
-      if (mode == 1) VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_patch_g<1, false, true>), dim3(nt), dim3(512), g);
-      else VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_patch_g<2, false, true>), dim3(nt), dim3(512), g);
-      VF_LAUNCH_CHECK();
-      if (ksplit > 1) {
-        VfProf prof(ctx, slab_st ? "slab_reduce_pconv_bnstats" : "slab_reduce_pconv", 0.0, 4.0 * (double)g.out_elems * (ksplit + 1));
-        return vf_internal_slab_reduce(ctx, g.slab, g.Y, g.bias, g.out_elems, g.N, ksplit, g.act, g.slope, g.dmask, g.dact, g.dslope,
-                                       slab_st ? &g.st : nullptr, st_groups);
-      }
-      return 0;
-    }
-    static const int env_nbuf = getenv("VF_PG_NBUF") ? atoi(getenv("VF_PG_NBUF")) : 0;
-    const bool one_stage = env_nbuf ? env_nbuf == 1 : (t.bm == 128 && nt >= 512);
-    if (one_stage) snprintf(dname, sizeof(dname), "pconv_dma_%dx%dx64_%s_1stage", t.bm, t.bn, ntaps == 16 ? "t16" : "t4");
-    if (t.bm == 128) {
-      if (ntaps == 16) {
-        if (one_stage) VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<128, 64, 16, 1>), dim3(nt), dim3(512), g);
-        else VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<128, 64, 16, 2>), dim3(nt), dim3(512), g);
-      } else {
-        if (one_stage) VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<128, 64, 4, 1>), dim3(nt), dim3(512), g);
-        else VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<128, 64, 4, 2>), dim3(nt), dim3(512), g);
-      }
-    } else {
-      if (ntaps == 16) {
-        if (one_stage) VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<64, 64, 16, 1>), dim3(nt), dim3(256), g);
-        else VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<64, 64, 16, 2>), dim3(nt), dim3(256), g);
-      } else {
-        if (one_stage) VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<64, 64, 4, 1>), dim3(nt), dim3(256), g);
-        else VF_LAUNCH_TIMED(ctx, dname, dfl, dby, (k_pconv_dma<64, 64, 4, 2>), dim3(nt), dim3(256), g);
-      }
-    }
-    VF_LAUNCH_CHECK();
-    if (ksplit > 1) {
-      VfProf prof(ctx, slab_st ? "slab_reduce_pconv_bnstats" : "slab_reduce_pconv", 0.0, 4.0 * (double)g.out_elems * (ksplit + 1));
-      return vf_internal_slab_reduce(ctx, g.slab, g.Y, g.bias, g.out_elems, g.N, ksplit, g.act, g.slope, g.dmask, g.dact, g.dslope,
-                                     slab_st ? &g.st : nullptr, st_groups);
-    }
-    return 0;
+    const bool one_stage = bm == 128 && nt >= 512;
+    snprintf(name, sizeof(name), "pconv_dma_%dx%dx64_%s%s", bm, bn, taps, one_stage ? "_1stage" : "");
+    kern = bm == 128 ? (ntaps == 16 ? pg_dma_kernel<128, 16>(false, one_stage) : pg_dma_kernel<128, 4>(false, one_stage))
+                     : (ntaps == 16 ? pg_dma_kernel<64, 16>(false, one_stage) : pg_dma_kernel<64, 4>(false, one_stage));
+  } else {
+    snprintf(name, sizeof(name), "pconv_%dx%dx%d_%s", bm, bn, ch, taps);
+    kern = bm == 128 ? (ntaps == 16 ? pg_reg_kernel<128, 64, 16>(ch) : pg_reg_kernel<128, 64, 4>(ch))
+                     : (ntaps == 16 ? pg_reg_kernel<64, 32, 16>(ch) : pg_reg_kernel<64, 32, 4>(ch));
+    block = dim3(256);
+    by = 0.0;
   }
-  static const int env_pair = getenv("VF_PG_PAIR") ? atoi(getenv("VF_PG_PAIR")) : 0;
-  const bool pair = env_pair && ch == 64 && t.bm == 64;
-  const unsigned ntiles = (unsigned)(gm * gn * zpar * ksplit);
-  dim3 grid(pair ? (ntiles + 1) / 2 : ntiles), block(256);
-  char name[64];
-  snprintf(name, sizeof(name), "pconv_%dx%dx%d_%s%s", t.bm, t.bn, ch, ntaps == 16 ? "t16" : "t4", pair ? "_pair" : "");
-  const double fl = 2.0 * (double)g.M * g.N * (double)ntaps * g.C * zpar;
-#define PG_LAUNCH(BM_, BN_, WM_, WN_)                                                                                      \
-  do {                                                                                                                     \
-    if (pair) {                                                                                                            \
-      if (ntaps == 16) VF_LAUNCH_TIMED(ctx, name, fl, 0.0, (k_pconv<BM_, BN_, WM_, WN_, 16, 64, true>), grid, dim3(512), g); \
-      else VF_LAUNCH_TIMED(ctx, name, fl, 0.0, (k_pconv<BM_, BN_, WM_, WN_, 4, 64, true>), grid, dim3(512), g);              \
-    } else if (ch == 64) {                                                                                                 \
-      if (ntaps == 16) VF_LAUNCH_TIMED(ctx, name, fl, 0.0, (k_pconv<BM_, BN_, WM_, WN_, 16, 64, false>), grid, block, g);    \
-      else VF_LAUNCH_TIMED(ctx, name, fl, 0.0, (k_pconv<BM_, BN_, WM_, WN_, 4, 64, false>), grid, block, g);                 \
-    } else {                                                                                                               \
-      if (ntaps == 16) VF_LAUNCH_TIMED(ctx, name, fl, 0.0, (k_pconv<BM_, BN_, WM_, WN_, 16, 32, false>), grid, block, g);    \
-      else VF_LAUNCH_TIMED(ctx, name, fl, 0.0, (k_pconv<BM_, BN_, WM_, WN_, 4, 32, false>), grid, block, g);                 \
-    }                                                                                                                      \
-  } while (0)
-  if (t.bm == 128) PG_LAUNCH(128, 64, 64, 32);
-  else PG_LAUNCH(64, 64, 32, 32);
-#undef PG_LAUNCH
+
+  // ---- launch, split-K combine
+  VF_LAUNCH_TIMED(ctx, name, fl, by, kern, grid, block, g);
   VF_LAUNCH_CHECK();
   if (ksplit > 1) {
     VfProf prof(ctx, slab_st ? "slab_reduce_pconv_bnstats" : "slab_reduce_pconv", 0.0, 4.0 * (double)g.out_elems * (ksplit + 1));

@@ -178,11 +178,10 @@ __global__ __launch_bounds__(256) void k_smallm_axpy(const float* __restrict__ A
 // Plans a small-M pass.  form 0: row-dot (W = [N][K]); form 1: axpy (W = [K][N]).  Returns the split count (>= 2), or 0 when the
 // shape is not these kernels' (the caller keeps its tiled path).
 int vf_internal_smallm_plan(int form, int M, int N, int K, size_t ws_bytes) {
-  static const bool off = getenv("VF_NO_SMALLM") && atoi(getenv("VF_NO_SMALLM"));
   // (M = 16, train_vid_weighted.lua's batch: the axpy form took 84 us per 131 MB pass against 37 us for the tiled kernel —
   //  64 FMAs and 16 scalar operands per 16 bytes of weights make it issue-bound; the row-dot form would hold 128 accumulators)
-  if (off || M < 1 || M > 8) return 0;
-  static const int want_waves = getenv("VF_SMALLM_WAVES") ? atoi(getenv("VF_SMALLM_WAVES")) : 4096;      // ~4 per SIMD
+  if (M < 1 || M > 8) return 0;
+  constexpr int want_waves = 4096;      // ~4 per SIMD
   int ksplit = 0;
   if (form == 0) {
     if (K % 256 != 0 || N % 32 != 0) return 0;          // (four 8-row groups per block)

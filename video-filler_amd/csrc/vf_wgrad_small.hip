@@ -32,8 +32,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 namespace {
 
 // NJ = column blocks per wave (float2 / float4 of V per lane): 2 -> a 64 x 64 wave tile, 4 accumulator tiles (64 AGPRs: four or
-// five waves per SIMD cover the L2 latency of the operand loads by themselves); 4 -> 64 x 128 (one wave per SIMD: slower, kept
-// for the record)
+// five waves per SIMD cover the L2 latency of the operand loads by themselves); 4 -> 64 x 128 (one wave per SIMD: measured slower,
+// no longer instantiated)
 // FUSE: optim.adam applied in the epilogue (vf_wgrad_adam_outer): the gradient never makes the round trip through memory —
 // 24 B per weight (x, m, v read and written) instead of 4 (this kernel's store) + 28 (k_adam); A.g != NULL also stores it.
 struct VfAdamFuse {
@@ -353,22 +353,16 @@ __global__ __launch_bounds__(256, OCC) void k_adam_fused_multi(const VfFusedTabl
 // dW[Nu][Ncols] = beta * dW + sum_k U[k][Nu] * V[k][Ncols].  Returns -1 when the shape is not this kernel's (the caller keeps
 // its tiled path), 0 when launched, > 0 on a launch error.
 int vf_internal_wgrad_smallk(vf_ctx* ctx, const float* U, const float* V, float* dW, int K, int Nu, int Ncols, float beta) {
-  static const bool off = getenv("VF_NO_WGRAD_SMALLK") && atoi(getenv("VF_NO_WGRAD_SMALLK"));
-  if (off || ctx->mfma_bf16 == 1) return -1;                  // (the bf16-operand mode rounds its operands: not this kernel's arithmetic)
+  if (ctx->mfma_bf16 == 1) return -1;                  // (the bf16-operand mode rounds its operands: not this kernel's arithmetic)
   // measured (scripts/bench_bottleneck_wgrad.py): K = 4: 104 us against 192 (the write at memset speed, 6.0 TB/s); K = 16: 27.6
   // against 39.5; K = 64: 57 against 54 — there the fp32 MFMAs themselves (4.2 GFLOP at the f32 pipe's rate) take as long as
   // the tiled three-plane kernel, which besides shares its launch with the other layers of the group
-  static const int kmax = getenv("VF_WGRAD_SMALLK_MAX") ? atoi(getenv("VF_WGRAD_SMALLK_MAX")) : 32;
-  if (K < 1 || K > kmax || Ncols % 128 != 0 || Nu % 2 != 0 || Nu < 64) return -1;
+  if (K < 1 || K > 32 || Ncols % 128 != 0 || Nu % 2 != 0 || Nu < 64) return -1;
   if ((((uintptr_t)U) & 7) || (((uintptr_t)V) & 15) || (((uintptr_t)dW) & 15)) return -1;
-  static const int nj = getenv("VF_WGRAD_SMALLK_NJ") ? atoi(getenv("VF_WGRAD_SMALLK_NJ")) : 2;
-  const int tiles_c = Ncols / (32 * nj), tiles_r = (int)vf_cdiv(Nu, 64);
+  const int tiles_c = Ncols / 64, tiles_r = (int)vf_cdiv(Nu, 64);
   const int64_t wtiles = (int64_t)tiles_c * tiles_r;
   VfProf prof(ctx, "wgrad_smallk_f32", 2.0 * (double)K * Nu * Ncols, 4.0 * ((double)Nu * Ncols * (beta != 0.f ? 2 : 1) + (double)K * (Nu + Ncols)));
-  if (nj == 4)
-    hipLaunchKernelGGL((k_wgrad_smallk<4, false>), dim3((unsigned)vf_cdiv(wtiles, 4)), dim3(256), 0, ctx->stream, U, V, dW, K, Nu, Ncols, tiles_c, beta, VfAdamFuse{});
-  else
-    hipLaunchKernelGGL((k_wgrad_smallk<2, false>), dim3((unsigned)vf_cdiv(wtiles, 4)), dim3(256), 0, ctx->stream, U, V, dW, K, Nu, Ncols, tiles_c, beta, VfAdamFuse{});
+  hipLaunchKernelGGL((k_wgrad_smallk<2, false>), dim3((unsigned)vf_cdiv(wtiles, 4)), dim3(256), 0, ctx->stream, U, V, dW, K, Nu, Ncols, tiles_c, beta, VfAdamFuse{});
   VF_LAUNCH_CHECK();
   return 0;
 }
@@ -429,10 +423,9 @@ int vf_internal_adam_fused_multi(vf_ctx* ctx, const VfFusedLayer* layers, int nl
     bytes += (L.g_out ? 28.0 : 24.0) * n + 4.0 * L.K * ((double)L.Nu + L.Ncols);
   }
   // ---- three-plane mode, K >= 64: the gradient on the bf16 pipe from operands pre-split in fragment order (k_fused_planes_prep into the
-  // context's workspace; the fp32 pipe's 128 MFMAs of 64 cycles per 64 x 64 tile become 96 of 32).  VF_ADAM_PLANES=0 keeps the fp32 form.
+  // context's workspace; the fp32 pipe's 128 MFMAs of 64 cycles per 64 x 64 tile become 96 of 32).
   {
-    static const int env_pl = getenv("VF_ADAM_PLANES") ? atoi(getenv("VF_ADAM_PLANES")) : 1;
-    bool ok = env_pl && ctx->mfma_bf16 == 3;
+    bool ok = ctx->mfma_bf16 == 3;
     size_t need = 0;
     for (int i = 0; i < nl && ok; ++i) {
       ok = T.K[i] >= 64 && T.K[i] % 16 == 0;
