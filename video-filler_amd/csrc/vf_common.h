@@ -59,6 +59,26 @@ struct vf_ctx {
 };
 void vf_internal_wg_free(vf_ctx* ctx);
 
+// The one-shot attachments above (bnf, act_bits_out, dmask_bits, dot_act_y) are meant for the next launch of the call that
+// follows them.  A conv entry point that refuses its call (any error return) drops them, so that no later, unrelated launch
+// takes them: a stale mode-2 bnf would store that launch's output masked by another tensor's activation derivative.  Declared
+// first thing in each conv entry point; an error return is one that went through vf_set_error.
+unsigned vf_error_seq();
+struct VfOneShotScope {
+  vf_ctx* c;
+  unsigned seq;
+  explicit VfOneShotScope(vf_ctx* ctx) : c(ctx), seq(vf_error_seq()) {}
+  ~VfOneShotScope() {
+    if (!c || vf_error_seq() == seq) return;
+    c->bnf.mode = 0;
+    c->bnf_result_rows = 0;
+    c->act_bits_out = nullptr;
+    c->act_bits_written = 0;
+    c->dmask_bits = nullptr;
+    c->dot_act_y = nullptr;
+  }
+};
+
 static inline char* vf_ws_ptr(vf_ctx* c) { return (char*)c->ws + c->ws_front; }
 static inline size_t vf_ws_avail(vf_ctx* c) { return c->ws_bytes > c->ws_front ? c->ws_bytes - c->ws_front : 0; }
 
@@ -85,7 +105,9 @@ void vf_set_error(const char* fmt, ...);
 
 // per-launch profiling scope (active only between vf_prof_begin / vf_prof_end)
 bool vf_prof_enabled();
-void vf_prof_push(vf_ctx* ctx, const char* name, double flops, double bytes, bool begin);
+// begin: appends a record and returns its index; end (begin false): records the stop event of record `idx` (scopes nest: an
+// inner VfProf or a timed launch inside a scope appends records of its own)
+int vf_prof_push(vf_ctx* ctx, const char* name, double flops, double bytes, bool begin, int idx = -1);
 // roctx range around a launch site (vf_trace.hip): active with vf_trace_enable(1) / VF_ROCTX=1, free otherwise
 bool vf_trace_enabled();
 extern "C" int vf_range_push(const char* name);
@@ -103,11 +125,12 @@ struct VfProf {
   vf_ctx* c;
   bool on;
   VfRange range;
+  int idx = -1;
   VfProf(vf_ctx* ctx, const char* name, double flops, double bytes) : c(ctx), on(vf_prof_enabled()), range(name) {
-    if (on) vf_prof_push(c, name, flops, bytes, true);
+    if (on) idx = vf_prof_push(c, name, flops, bytes, true);
   }
   ~VfProf() {
-    if (on) vf_prof_push(c, nullptr, 0, 0, false);
+    if (on) vf_prof_push(c, nullptr, 0, 0, false, idx);
   }
 };
 

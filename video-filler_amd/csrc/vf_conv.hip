@@ -1989,6 +1989,7 @@ static int wgrad(vf_ctx* ctx, const float* U, const float* V, float* dW, int B, 
     const size_t need = ksplit > 1 ? (((size_t)ksplit * total * sizeof(float) + 255) & ~(size_t)255) : 0;
     if (R->ws_used + need > vf_ws_avail(ctx)) {
       if (int rc = wg_flush(ctx)) return rc;
+      R->ws_used = 0;      // nothing is recorded any more (a partial end keeps ws_used with an empty record list)
     }
     VF_REQUIRE(need <= vf_ws_avail(ctx), "workspace too small for this layer's split-K slabs");
     if (ksplit > 1) g.slab = (float*)(vf_ws_ptr(ctx) + R->ws_used);
@@ -2102,6 +2103,7 @@ int vf_internal_conv_thin_fwd(vf_ctx* ctx, const float* x, const float* w, const
                               int W, int Cin, int Cout, int act, float slope);      // vf_conv_thin.hip
 VF_API int vf_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
                          int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
+  VfOneShotScope one_shot(ctx);
   if (!main_net_shape(H, W, k, stride, pad)) return vf_internal_gconv_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, k, stride, pad, act, slope);
   if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
   if (stride == 2 && Cin == 3 && !ctx->bnf.mode) {      // the image-side layers: direct convolution (vf_conv_thin.hip)
@@ -2113,6 +2115,7 @@ VF_API int vf_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const floa
 
 VF_API int vf_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin,
                               int Cout, int k, int stride, int pad) {
+  VfOneShotScope one_shot(ctx);
   if (!main_net_shape(H, W, k, stride, pad)) return vf_internal_gconv_bwd_data(ctx, gy, w, gx, B, H, W, Cin, Cout, k, stride, pad);
   if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
   const int Ho = (H + 2 * pad - 4) / stride + 1, Wo = (W + 2 * pad - 4) / stride + 1;
@@ -2133,6 +2136,7 @@ VF_API int vf_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, floa
 
 VF_API int vf_conv2d_bwd_data_act(vf_ctx* ctx, const float* gy, const float* w, float* gx, const float* x_act, int act,
                                   float slope, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad) {
+  VfOneShotScope one_shot(ctx);
   if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
   VF_REQUIRE(x_act != nullptr && (act == VF_ACT_LRELU || act == VF_ACT_RELU),
              "vf_conv2d_bwd_data_act: needs the activated input and a (leaky) ReLU");
@@ -2145,6 +2149,7 @@ static int conv2d_bwd_weight_impl(vf_ctx* ctx, const float* x, const float* gy, 
                                   float* gw, float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, float beta);
 VF_API int vf_conv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, int B, int H, int W,
                                 int Cin, int Cout, int k, int stride, int pad, float beta) {
+  VfOneShotScope one_shot(ctx);
   return conv2d_bwd_weight_impl(ctx, x, gy, nullptr, nullptr, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
 }
 // the same with the bf16 planes of both operands at hand (vf_planes_split layout): the weight gradient then runs on the
@@ -2152,6 +2157,7 @@ VF_API int vf_conv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, fl
 VF_API int vf_conv2d_bwd_weight_planes(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
                                        float* gw, float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                                        float beta) {
+  VfOneShotScope one_shot(ctx);
   return conv2d_bwd_weight_impl(ctx, x, gy, x_planes, gy_planes, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
 }
 static int conv2d_bwd_weight_impl(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
@@ -2177,6 +2183,7 @@ static int conv2d_bwd_weight_impl(vf_ctx* ctx, const float* x, const float* gy, 
 
 VF_API int vf_deconv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
                            int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
+  VfOneShotScope one_shot(ctx);
   VF_REQUIRE(k == 4 && ((stride == 2 && pad == 1) || (stride == 1 && pad == 0)), "unsupported full-conv shape");
   VF_REQUIRE(vf_is_pow2(H) && vf_is_pow2(W), "spatial sizes must be powers of two");
   return conv_like_bwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, stride, pad, act, slope);
@@ -2184,6 +2191,7 @@ VF_API int vf_deconv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const fl
 
 VF_API int vf_deconv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin,
                                 int Cout, int k, int stride, int pad) {
+  VfOneShotScope one_shot(ctx);
   VF_REQUIRE(k == 4 && ((stride == 2 && pad == 1) || (stride == 1 && pad == 0)), "unsupported full-conv shape");
   const int Ho = (H - 1) * stride - 2 * pad + 4, Wo = (W - 1) * stride - 2 * pad + 4;
   VF_REQUIRE(vf_is_pow2(H) && vf_is_pow2(W), "spatial sizes must be powers of two");
@@ -2204,10 +2212,12 @@ static int deconv2d_bwd_weight_impl(vf_ctx* ctx, const float* x, const float* gy
 }
 VF_API int vf_deconv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, int B, int H, int W,
                                   int Cin, int Cout, int k, int stride, int pad, float beta) {
+  VfOneShotScope one_shot(ctx);
   return deconv2d_bwd_weight_impl(ctx, x, gy, nullptr, nullptr, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
 }
 VF_API int vf_deconv2d_bwd_weight_planes(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
                                          float* gw, float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                                          float beta) {
+  VfOneShotScope one_shot(ctx);
   return deconv2d_bwd_weight_impl(ctx, x, gy, x_planes, gy_planes, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
 }

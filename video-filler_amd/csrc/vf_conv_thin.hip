@@ -283,6 +283,7 @@ extern "C" int vf_planes_split(vf_ctx* ctx, const float* x, void* planes, int64_
 // can (the thin-input layers above), else by a pass over y.
 VF_API int vf_conv2d_fwd_planes(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B,
                                 int H, int W, int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
+  VfOneShotScope one_shot(ctx);
   VF_REQUIRE(y_planes != nullptr, "vf_conv2d_fwd_planes: y_planes is NULL (use vf_conv2d_fwd)");
   if (k == 4 && stride == 2 && pad == 1) {
     const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, y_planes, B, H, W, Cin, Cout, act, slope);

@@ -9,8 +9,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------ errors / ctx
 static thread_local char g_err[1024] = "";
+static thread_local unsigned g_err_seq = 0;      // errors set so far on this thread (VfOneShotScope)
 
+unsigned vf_error_seq() { return g_err_seq; }
 void vf_set_error(const char* fmt, ...) {
+  ++g_err_seq;
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
@@ -117,7 +120,7 @@ static bool g_prof_on = false;
 static std::vector<ProfRec> g_prof_recs;
 static std::vector<ProfAgg> g_prof_agg;
 bool vf_prof_enabled() { return g_prof_on; }
-void vf_prof_push(vf_ctx* ctx, const char* name, double flops, double bytes, bool begin) {
+int vf_prof_push(vf_ctx* ctx, const char* name, double flops, double bytes, bool begin, int idx) {
   if (begin) {
     ProfRec r;
     r.name = name;
@@ -127,9 +130,10 @@ void vf_prof_push(vf_ctx* ctx, const char* name, double flops, double bytes, boo
     hipEventCreate(&r.e1);
     hipEventRecord(r.e0, ctx->stream);
     g_prof_recs.push_back(r);
-  } else if (!g_prof_recs.empty()) {
-    hipEventRecord(g_prof_recs.back().e1, ctx->stream);
+    return (int)g_prof_recs.size() - 1;
   }
+  if (idx >= 0 && idx < (int)g_prof_recs.size()) hipEventRecord(g_prof_recs[idx].e1, ctx->stream);
+  return idx;
 }
 bool vf_prof_ext(const char* name, double flops, double bytes, hipEvent_t* e0, hipEvent_t* e1) {
   if (!g_prof_on) return false;

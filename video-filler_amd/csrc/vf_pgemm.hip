@@ -1859,12 +1859,14 @@ VF_API int vf_pconv_supported_in_mode(int mfma_mode, int B, int H, int W, int Ci
 /* conv forward / full-conv data-gradient: gather planes `ap` [B][H][W][Cin], weight planes `wp` [Cout][16][Cin] */
 VF_API int vf_pconv_gather(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
                            int Cout, int act, float slope) {
+  VfOneShotScope one_shot(ctx);
   VF_REQUIRE(vf_pconv_supported_in_mode(ctx->mfma_bf16, B, H, W, Cin, Cout, 4, 2, 1, 0), "vf_pconv_gather: unsupported shape B=%d %dx%d %d->%d (product mode %d)", B, H, W, Cin, Cout, ctx->mfma_bf16);
   return pconv_like_fwd(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope);
 }
 /* conv data-gradient / full-conv forward: low-res planes `ap` [B][H][W][Cin] -> y [B][2H][2W][Cout], weight planes [Cout][16][Cin] */
 VF_API int vf_pconv_scatter(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
                             int Cout, int act, float slope, const float* dmask, int dact, float dslope) {
+  VfOneShotScope one_shot(ctx);
   VF_REQUIRE(vf_pconv_supported_in_mode(ctx->mfma_bf16, B, H, W, Cin, Cout, 4, 2, 1, 1), "vf_pconv_scatter: unsupported shape B=%d %dx%d %d->%d (product mode %d)", B, H, W, Cin, Cout, ctx->mfma_bf16);
   VF_REQUIRE(!(dmask && bias), "vf_pconv_scatter: the activation-backward epilogue is for data-gradient passes (no bias)");
   return pconv_like_tr(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope, dmask, dact, dslope);
