@@ -243,6 +243,14 @@ int vf_bn_bwd_pre(vf_ctx* ctx, const double* part, int rows_per_group, const flo
                   float* ggamma, float* gbeta, const float* gamma, const float* save_mean, const float* save_invstd,
                   double* sums, int64_t npix_per_group, int C, int groups, float pbeta, void* gx_planes);
 
+/* ---- pointwise modules, criteria, Adam, layout (vf_core.hip): common rules ------------------------------------------
+ * n <= 0 (an empty tensor; for vf_gdl_* H = W = 1, for the transposes B*C*H*W = 0, for vf_zero_segments nseg <= 0): the call
+ *   returns 0, launches nothing over its operands and writes nothing — not the output, not the loss slot.  (vf_adam_step still
+ *   advances t_dev: it is vf_adam_prep + vf_adam_apply.)
+ * alignment: the pointwise modules and vf_mse_fwd read 16 bytes at a time when every operand is 16-byte aligned; otherwise they
+ *   take a scalar route for n <= 65536 (sub-batch views of small tensors) and refuse larger n.  vf_recon_grad_mix takes its
+ *   scalar kernel for any n when an operand is not 16-byte aligned or n % 4 != 0.  vf_adam_* refuse unaligned operands.
+ *   Every float operand must be 4-byte aligned. */
 /* ---- pointwise modules (nn.LeakyReLU / ReLU / Tanh / Sigmoid; train.lua:90,146,196) --------- */
 int vf_act_fwd(vf_ctx* ctx, const float* x, float* y, int64_t n, int act, float slope); /* y may alias x */
 /* gx = gy * act'(.) evaluated from the ACTIVATED output y (in-place semantics); gx may alias gy */
@@ -274,7 +282,8 @@ int vf_mse_bwd(vf_ctx* ctx, const float* x, const float* t, float* gx, int64_t n
  *   df_dg = alpha*df_dg + (2/n)(x-t) * wgt,   wgt = c0 + c1*mask[i]            (mask != NULL)
  *                                             wgt = inside band ? c0 : c0 + c1  (mask == NULL, band > 0:
  *                                                   rows/cols [band, HW-band) of an HW x HW image are "inside")
- * n = B*HW*HW*C elements, NHWC. */
+ * n = B*HW*HW*C elements, NHWC.  The band form is for SQUARE maps only (the call takes one HW for rows and columns and refuses
+ * an n that is not a multiple of HW*HW*C); the mask form and band = 0 take any n, HW and C are then unused. */
 int vf_recon_grad_mix(vf_ctx* ctx, float* df_dg, const float* x, const float* t, const float* mask, float alpha,
                       float c0, float c1, int band, int HW, int C, int64_t n, double* loss);
 /* nn.GDLCriterion(1):forward (gdl_criterion.lua:38-45) incl. the flattened-pairing quirk. */

@@ -230,3 +230,27 @@ def grads_reference_order(tr, net, gref):
         for lo, hi in ranges:
             flat[lo:hi] = want[lo:hi]
     return from_internal(net, flat)
+
+
+# ---- guarded device buffers (tests/test_gpu_workspace.py, tests/test_gpu_elementwise.py)
+TAIL32 = 0x7FA5A5A5              # float32 guard words: a NaN payload no kernel computes
+FILL64 = 0x7FF5A5A5A5A5A5A5      # float64 words of the BatchNorm partial buffers (body and tail): also a NaN payload
+
+
+def guarded(b, n, dtype=torch.float32, pad=4096):
+    """a flat buffer of n elements and a pad-element guard tail.  float32: body NaN; float64 (BatchNorm partials): body and
+    tail FILL64, so that rows no launch wrote can be told apart"""
+    buf = torch.empty(n + pad, dtype=dtype, device=b.device)
+    if dtype == torch.float32:
+        buf[:n].fill_(float("nan"))
+        buf[n:].view(torch.int32).fill_(TAIL32)
+    else:
+        buf.view(torch.int64).fill_(FILL64)
+    return buf
+
+
+def untouched(buf, lo, hi=None):
+    seg = buf[lo:hi]
+    if buf.dtype == torch.float32:
+        return bool((seg.view(torch.int32) == TAIL32).all())
+    return bool((seg.view(torch.int64) == FILL64).all())

@@ -20,6 +20,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from helpers import FILL64, TAIL32, guarded, untouched  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5           # against fp64, relative to the max-norm
@@ -29,8 +31,6 @@ TOL = 2e-5           # against fp64, relative to the max-norm
 AGREE = 4e-6
 U = 2.0 ** -24       # unit roundoff of fp32
 WS_FILL = 0xA5                   # workspace guard bytes
-TAIL32 = 0x7FA5A5A5              # float32 guard words: a NaN payload no kernel computes
-FILL64 = 0x7FF5A5A5A5A5A5A5      # float64 words of the BatchNorm partial buffers (body and tail): also a NaN payload
 SLOPE = 0.2
 
 
@@ -82,25 +82,6 @@ def workspace(b, nbytes, guard=1 << 20):
         b.__dict__.pop("_colsum_plans", None)
         _set_ws(b, old.data_ptr(), old.numel())
     assert intact, "a kernel wrote past the end of a %d-byte workspace" % nbytes
-
-
-def guarded(b, n, dtype=torch.float32, pad=4096):
-    """a flat buffer of n elements and a pad-element guard tail.  float32: body NaN; float64 (BatchNorm partials): body and
-    tail FILL64, so that rows no launch wrote can be told apart"""
-    buf = torch.empty(n + pad, dtype=dtype, device=b.device)
-    if dtype == torch.float32:
-        buf[:n].fill_(float("nan"))
-        buf[n:].view(torch.int32).fill_(TAIL32)
-    else:
-        buf.view(torch.int64).fill_(FILL64)
-    return buf
-
-
-def untouched(buf, lo, hi=None):
-    seg = buf[lo:hi]
-    if buf.dtype == torch.float32:
-        return bool((seg.view(torch.int32) == TAIL32).all())
-    return bool((seg.view(torch.int64) == FILL64).all())
 
 
 def g_act(b, B, Cc, H, W):

@@ -881,6 +881,8 @@ class HipBackend:
 
     def recon_grad_mix(self, df_dg, x, t, mask, alpha, c0, c1, band, loss):
         B, Cc, H, W = x.shape
+        if mask is None and band > 0 and H != W:
+            raise ValueError("recon_grad_mix: the band form is for square maps (vf_recon_grad_mix takes one HW), got %d x %d" % (H, W))
         self._c("vf_recon_grad_mix", _ptr(df_dg), _ptr(x), _ptr(t), _ptr(mask), alpha, c0, c1, band, H, Cc, x.numel(),
                 _ptr(loss))
 

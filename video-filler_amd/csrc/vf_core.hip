@@ -227,12 +227,14 @@ __global__ void k_transpose(const float* __restrict__ src, float* __restrict__ d
 }
 VF_API int vf_nchw_to_nhwc(vf_ctx* ctx, const float* src, float* dst, int B, int C, int H, int W) {
   const int S = H * W;
+  if (B <= 0 || C <= 0 || S <= 0) return 0;
   hipLaunchKernelGGL(k_transpose, dim3((int)vf_cdiv(S, 32), (int)vf_cdiv(C, 32), B), dim3(32, 8), 0, ctx->stream, src, dst, C, S);
   VF_LAUNCH_CHECK();
   return 0;
 }
 VF_API int vf_nhwc_to_nchw(vf_ctx* ctx, const float* src, float* dst, int B, int C, int H, int W) {
   const int S = H * W;
+  if (B <= 0 || C <= 0 || S <= 0) return 0;
   hipLaunchKernelGGL(k_transpose, dim3((int)vf_cdiv(C, 32), (int)vf_cdiv(S, 32), B), dim3(32, 8), 0, ctx->stream, src, dst, S, C);
   VF_LAUNCH_CHECK();
   return 0;
@@ -241,9 +243,11 @@ VF_API int vf_nhwc_to_nchw(vf_ctx* ctx, const float* src, float* dst, int B, int
 // ------------------------------------------------------------------------------------------------ pointwise
 enum { OP_ACT_FWD, OP_ACT_BWD, OP_AXPBY, OP_CMUL, OP_SCALE_SHIFT, OP_COMPOSE, OP_MSE_BWD };
 
+// (no __restrict__: vf_act_fwd runs with y == x and vf_act_bwd with gx == gy — nn.py's in-place activations and the thin conv path;
+//  every element is read and written by the one thread that owns it, so aliasing an input with `out` is well defined)
 template <int OP>
-__global__ void k_pointwise(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c,
-                            float* __restrict__ out, int64_t n, float f0, float f1, int act, int vec) {
+__global__ void k_pointwise(const float* a, const float* b, const float* c, float* out, int64_t n, float f0, float f1, int act,
+                            int vec) {
   const int64_t n4 = vec ? n >> 2 : 0;      // vec = 0: some operand is not 16-byte aligned (a sub-batch view of a tiny tensor)
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   auto op = [&](float av, float bv, float cv, float ov) -> float {
@@ -377,17 +381,20 @@ __global__ __launch_bounds__(256) void k_bce_fwd_bwd(const float* __restrict__ x
 VF_API int vf_bce_fwd_bwd(vf_ctx* ctx, const float* x, float label0, float label1, int n_per_group, int groups, double* loss0,
                           double* loss1, float* gx) {
   VF_REQUIRE(groups == 1 || groups == 2, "vf_bce_fwd_bwd: groups must be 1 or 2 (got %d)", groups);
-  VF_REQUIRE(x && gx && loss0 && (groups == 1 || loss1) && n_per_group > 0, "vf_bce_fwd_bwd: bad arguments");
+  if (n_per_group <= 0) return 0;
+  VF_REQUIRE(x && gx && loss0 && (groups == 1 || loss1), "vf_bce_fwd_bwd: bad arguments");
   hipLaunchKernelGGL(k_bce_fwd_bwd, dim3(groups), dim3(256), 0, ctx->stream, x, label0, label1, n_per_group, loss0, loss1, gx);
   VF_LAUNCH_CHECK();
   return 0;
 }
 VF_API int vf_bce_fwd(vf_ctx* ctx, const float* x, float label, int n, double* loss) {
+  if (n <= 0) return 0;
   hipLaunchKernelGGL(k_bce_fwd, dim3(1), dim3(256), 0, ctx->stream, x, label, n, loss);
   VF_LAUNCH_CHECK();
   return 0;
 }
 VF_API int vf_bce_bwd(vf_ctx* ctx, const float* x, float label, float* gx, int n) {
+  if (n <= 0) return 0;
   hipLaunchKernelGGL(k_bce_bwd, dim3((int)vf_cdiv(n, 256)), dim3(256), 0, ctx->stream, x, label, gx, n);
   VF_LAUNCH_CHECK();
   return 0;
@@ -395,8 +402,8 @@ VF_API int vf_bce_bwd(vf_ctx* ctx, const float* x, float label, float* gx, int n
 
 // sum((x-t)^2)/n -> loss (double atomics across blocks; order only perturbs the 16th digit)
 __global__ __launch_bounds__(256) void k_mse_fwd(const float* __restrict__ x, const float* __restrict__ t, int64_t n,
-                                                 double inv_n, double* __restrict__ loss) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x, n4 = n >> 2;
+                                                 double inv_n, double* __restrict__ loss, int vec) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, n4 = vec ? n >> 2 : 0;      // vec = 0: as k_pointwise
   float s = 0.f;
   double sd = 0;
   int cnt = 0;
@@ -417,9 +424,16 @@ __global__ __launch_bounds__(256) void k_mse_fwd(const float* __restrict__ x, co
   block_add_double(sd * inv_n, loss);
 }
 VF_API int vf_mse_fwd(vf_ctx* ctx, const float* x, const float* t, int64_t n, double* loss) {
+  if (n <= 0) return 0;
+  // the operand rule of launch_pw: the criterion is handed whole tensors (16-byte aligned by their allocator), and a sub-batch view
+  // of a small one takes the scalar route
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)t;
+  VF_REQUIRE((bits & 3) == 0, "vf_mse_fwd: operands must be float aligned");
+  const int vec = (bits & 15) == 0;
+  VF_REQUIRE(vec || n <= (1 << 16), "vf_mse_fwd: operands of this size must be 16-byte aligned");
   VF_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(double), ctx->stream));
   VfProf prof(ctx, "mse_fwd", 0.0, 8.0 * (double)n);
-  hipLaunchKernelGGL(k_mse_fwd, dim3(grid_for(n, 16)), dim3(256), 0, ctx->stream, x, t, n, 1.0 / (double)n, loss);
+  hipLaunchKernelGGL(k_mse_fwd, dim3(grid_for(n, 16)), dim3(256), 0, ctx->stream, x, t, n, 1.0 / (double)n, loss, vec);
   VF_LAUNCH_CHECK();
   return 0;
 }
@@ -504,17 +518,23 @@ __global__ __launch_bounds__(256) void k_recon_grad_mix4(float* __restrict__ dfd
 }
 VF_API int vf_recon_grad_mix(vf_ctx* ctx, float* df_dg, const float* x, const float* t, const float* mask, float alpha,
                              float c0, float c1, int band, int HW, int C, int64_t n, double* loss) {
+  if (n <= 0) return 0;
+  VF_REQUIRE(((((uintptr_t)df_dg) | ((uintptr_t)x) | ((uintptr_t)t) | ((uintptr_t)mask)) & 3) == 0,
+             "vf_recon_grad_mix: operands must be float aligned");
+  VF_REQUIRE(mask || band <= 0 || (HW > 0 && C > 0 && n % ((int64_t)HW * HW * C) == 0),
+             "vf_recon_grad_mix: the band form needs n = B * HW * HW * C (got n = %lld, HW = %d, C = %d)", (long long)n, HW, C);
   VF_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(double), ctx->stream));
-  VfProf prof(ctx, "recon_grad_mix", 0.0, 4.0 * (double)n * (mask ? 5 : 4));
   if (n % 4 == 0 && n < ((int64_t)1 << 31) && ((((uintptr_t)df_dg) | ((uintptr_t)x) | ((uintptr_t)t) | ((uintptr_t)mask)) & 15) == 0) {
     int lgHW = -1;
     if (HW > 0 && (HW & (HW - 1)) == 0)
       for (lgHW = 0; (1 << lgHW) < HW; ++lgHW) {}
+    VfProf prof(ctx, "recon_grad_mix", 0.0, 4.0 * (double)n * (mask ? 5 : 4));
     hipLaunchKernelGGL(k_recon_grad_mix4, dim3(grid_for(n / 4, 4)), dim3(256), 0, ctx->stream, df_dg, x, t, mask, alpha, c0, c1, band,
                        HW, lgHW, C, n / 4, 2.f / (float)n, 1.0 / (double)n, loss);
     VF_LAUNCH_CHECK();
     return 0;
   }
+  VfProf prof(ctx, "recon_grad_mix_scalar", 0.0, 4.0 * (double)n * (mask ? 5 : 4));      // the route is visible to vf_prof_*
   hipLaunchKernelGGL(k_recon_grad_mix, dim3(grid_for(n, 8)), dim3(256), 0, ctx->stream, df_dg, x, t, mask, alpha, c0, c1, band,
                      HW, C, n, 2.f / (float)n, 1.0 / (double)n, loss);
   VF_LAUNCH_CHECK();
@@ -547,8 +567,9 @@ __global__ __launch_bounds__(256) void k_gdl_fwd(const float* __restrict__ yh, c
 }
 VF_API int vf_gdl_fwd(vf_ctx* ctx, const float* yhat, const float* y, int B, int H, int W, int C, double* loss) {
   VF_REQUIRE(H == W, "GDLCriterion needs square maps (the reference's CSubTable pairs H x (W-1) with (H-1) x W)");
-  VF_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(double), ctx->stream));
   const int64_t cnt = (int64_t)B * C * (H - 1) * W;
+  if (cnt <= 0) return 0;
+  VF_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(double), ctx->stream));
   hipLaunchKernelGGL(k_gdl_fwd, dim3(grid_for(cnt, 8)), dim3(256), 0, ctx->stream, yhat, y, B, H, W, C, 1.0 / (double)cnt, loss);
   VF_LAUNCH_CHECK();
   return 0;
@@ -591,6 +612,7 @@ __global__ __launch_bounds__(256) void k_gdl_bwd(const float* __restrict__ yh, c
 VF_API int vf_gdl_bwd(vf_ctx* ctx, const float* yhat, const float* y, float* gyhat, int B, int H, int W, int C) {
   VF_REQUIRE(H == W, "GDLCriterion needs square maps (the reference's CSubTable pairs H x (W-1) with (H-1) x W)");
   const int64_t cnt = (int64_t)B * C * (H - 1) * W;
+  if (cnt <= 0) return 0;
   hipLaunchKernelGGL(k_gdl_bwd, dim3(grid_for((int64_t)B * C * H * W, 4)), dim3(256), 0, ctx->stream, yhat, y, gyhat, B, H, W, C,
                      (float)(1.0 / (double)cnt));
   VF_LAUNCH_CHECK();
@@ -613,6 +635,7 @@ __global__ __launch_bounds__(256) void k_masked_mse(const float* __restrict__ x,
 }
 VF_API int vf_masked_mse_fwd(vf_ctx* ctx, const float* x, const float* xhat, const uint8_t* mask, float w, int64_t n,
                              double* loss) {
+  if (n <= 0) return 0;
   VF_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(double), ctx->stream));
   hipLaunchKernelGGL(k_masked_mse, dim3(grid_for(n, 8)), dim3(256), 0, ctx->stream, x, xhat, mask, w, (float*)nullptr, n,
                      1.0 / (double)n, loss);
@@ -621,6 +644,7 @@ VF_API int vf_masked_mse_fwd(vf_ctx* ctx, const float* x, const float* xhat, con
 }
 VF_API int vf_masked_mse_bwd(vf_ctx* ctx, const float* x, const float* xhat, const uint8_t* mask, float w, float* gx,
                              int64_t n) {
+  if (n <= 0) return 0;
   hipLaunchKernelGGL(k_masked_mse, dim3(grid_for(n, 8)), dim3(256), 0, ctx->stream, x, xhat, mask, w, gx, n, 1.0 / (double)n,
                      (double*)nullptr);
   VF_LAUNCH_CHECK();
@@ -662,6 +686,7 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ x, const float
 static constexpr int ADAM_BLOCKS = 2048;      // grid cap of the grid-stride Adam passes
 static int adam_apply(vf_ctx* ctx, float* x, const float* g, float* m, float* v, int64_t n, double beta1, double beta2, double eps,
                       const int32_t* t_dev) {
+  if (n <= 0) return 0;
   VF_REQUIRE((((uintptr_t)x | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam operands must be 16-byte aligned");
   const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(vf_cdiv(n, 1024), ADAM_BLOCKS));
   VF_LAUNCH_TIMED(ctx, "adam", 0.0, 28.0 * (double)n, k_adam, dim3(blocks), dim3(256), x, g, m, v, n, (float)beta1,
