@@ -95,13 +95,13 @@ def test_lua_binding_declares_the_header_faithfully():
 
 
 def test_descriptor_mirror_matches_the_device_struct():
-    """backend.COLSUM_DESC mirrors struct VfColsumDesc of csrc/vf_bn.hip field for field (64 bytes, no padding)."""
+    """backend.COLSUM_DESC mirrors struct VfColsumDesc of csrc/vf_common.h field for field (64 bytes, no padding)."""
     import re
     import numpy as np
     from video_filler_amd.backend import COLSUM_DESC
     dt = np.dtype(COLSUM_DESC)
     assert dt.itemsize == 64
-    src = open(os.path.join(ROOT, "video-filler_amd", "csrc", "vf_bn.hip")).read()
+    src = open(os.path.join(ROOT, "video-filler_amd", "csrc", "vf_common.h")).read()
     body = re.search(r"struct VfColsumDesc \{(.*?)\};", src, flags=re.S).group(1)
     body = re.sub(r"//[^\n]*", "", body)
     names = []

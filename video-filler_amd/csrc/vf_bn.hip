@@ -461,18 +461,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ 
 
 // ---- every conv bias gradient of one backward walk in TWO launches (instead of two per layer): the column sums are
 // not needed before Adam, and each layer's gradOutput lives in its module's own buffer until the walk is over.  The
-// host builds the descriptor table once per (buffers, betas) combination and keeps it on the device.
-struct VfColsumDesc {      // mirrored by video-filler_amd/backend.py (COLSUM_DESC); 64 bytes
-  const float* g;          // [P][C] gradOutput
-  float* gb;               // [C]   gradBias:  gb = beta*gb + column sums
-  double* part;            // [gx][C] scratch partials
-  int64_t P;
-  int C, cq, rows_per_block, gx, gy;
-  int blk1_off, blk2_off;  // first block of this layer in stage 1 / stage 2
-  float beta;
-};
-static_assert(sizeof(VfColsumDesc) == 64, "descriptor layout is shared with the host mirror");
-
+// host builds the descriptor table (VfColsumDesc, vf_common.h) once per (buffers, betas) combination and keeps it on the device.
 __device__ __forceinline__ int vf_find_layer(const VfColsumDesc* __restrict__ d, int n, int blk, bool stage2) {
   int l = 0;
   while (l + 1 < n && blk >= (stage2 ? d[l + 1].blk2_off : d[l + 1].blk1_off)) ++l;

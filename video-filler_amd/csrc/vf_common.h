@@ -12,9 +12,9 @@
 
 #define VF_API extern "C" __attribute__((visibility("default")))
 
-// BatchNorm statistics as a by-product of the GEMM that produces the tensor (vf_bn_fuse_next_fwd / _bwd): the epilogue (or
-// the split-K slab reduce) of the NEXT conv-like launch leaves per-tile partial sums that vf_bn_train_fwd_pre /
-// vf_bn_bwd_pre finalize, so the tensor is not read again just to be summed.
+// BatchNorm statistics as a by-product of the GEMM that produces the tensor: the epilogue (or the split-K slab reduce) of a
+// conv-like launch leaves per-tile partial sums that vf_bn_train_fwd_pre / vf_bn_bwd_pre finalize, so the tensor is not read
+// again just to be summed.
 struct VfBnSt {
   int mode;               // 0 none; 1 forward: s1 = sum(v - shift), s2 = sum((v - shift)^2); 2 backward: s1 = sum(g), s2 = sum(g*(x - mean)),
                           //   g = the launch's output masked by the activation derivative (the output IS stored masked)
@@ -24,6 +24,35 @@ struct VfBnSt {
   int rows_per_group;     // partial rows each group ends up with (what the finalize kernels walk)
   int tiles_per_group;    // GEMM epilogue: row tiles per batch group; slab reduce: blocks per group
   int zpar;               // GEMM epilogue: output-parity classes sharing a row tile (1 or 4)
+};
+// the request for them: st carries mode, vec, x and part; the launch that takes it fills in the plan (vf_plan_bn_stats)
+struct VfBnRequest {
+  VfBnSt st = {};
+  const float* yact = nullptr;  // mode 2: activated BatchNorm output (the derivative mask), its activation
+  int act = 0;
+  float slope = 0.f;
+  int groups = 1, rows_cap = 0;
+};
+
+// What one conv-like pass does beyond its convolution: arguments of the internal entry points (vf_internal_conv2d_* and the
+// hosts below them), so that what a launch does is visible where it is called.  A default-constructed value is a plain pass.
+struct VfConvExtras {
+  VfBnRequest bn;               // BatchNorm statistics of the output; bn_result_rows: rows_per_group written, 0: this pass could not
+  int bn_result_rows = 0;
+  // sign bits of an activated tensor (vf_net.hip).  act_bits_out: the thin-input conv forward (vf_conv_thin.hip) also writes, per
+  // output pixel and 64-channel group, two words — bit j of word h = (channel 2j + h) > 0; act_bits_written says whether it did.
+  // dmask_bits: the planes-fed transposed pass (vf_pgemm.hip) reads its activation-derivative mask from such bits (a broadcast
+  // word per pixel) instead of the fp32 activation — 2 MB instead of 67 MB for E2's data-gradient (train.lua:90: the LeakyReLU
+  // below the second conv)
+  unsigned* act_bits_out = nullptr;
+  int act_bits_written = 0;
+  const unsigned* dmask_bits = nullptr;
+  // the 512 -> 1 head passes of vf_conv.hip (k_dot_bwd_data / k_dot_bwd_weight: netD's last conv, train.lua:195-196) multiply
+  // their gradOutput by the derivative of the Sigmoid fused into that conv, evaluated from the activated output — instead of a
+  // pass of its own over B values in front of them
+  const float* dot_act_y = nullptr;
+  int dot_act = 0;
+  float dot_act_slope = 0.f;
 };
 
 struct vf_ctx {
@@ -35,49 +64,24 @@ struct vf_ctx {
   int mfma_bf16;    // 0: native f32 MFMA; 1: operands rounded to bf16; 3 (default): exact three-plane bf16 split
   int wg_active;    // a weight-gradient group is being recorded (vf_wgrad_group_begin .. _end)
   void* wg_rec;     // the recorder (vf_conv.hip)
-  // one-shot attachment for the next conv-like launch (vf_bn_fuse_next_*), and what that launch made of it
-  VfBnSt bnf;
-  const float* bnf_yact;  // mode 2: activated BatchNorm output (the derivative mask), its activation
-  int bnf_act;
-  float bnf_slope;
-  int bnf_groups, bnf_rows_cap;
-  int bnf_result_rows;    // rows_per_group of the fused launch; 0: not fused
-  // sign bits of an activated tensor (vf_net.hip): one-shot attachments like bnf.  act_bits_out: the next thin-input conv forward
-  // (vf_conv_thin.hip) also writes, per output pixel and 64-channel group, two words — bit j of word h = (channel 2j + h) > 0;
-  // act_bits_written says whether it did.  dmask_bits: the next planes-fed transposed pass (vf_pgemm.hip) reads its activation-
-  // derivative mask from such bits (a broadcast word per pixel) instead of the fp32 activation — 2 MB instead of 67 MB for E2's
-  // data-gradient (train.lua:90: the LeakyReLU below the second conv)
-  unsigned* act_bits_out;
-  int act_bits_written;
-  const unsigned* dmask_bits;
-  // one-shot (vf_net.hip): the next 512 -> 1 head pass of vf_conv.hip (k_dot_bwd_data / k_dot_bwd_weight: netD's last conv,
-  // train.lua:195-196) multiplies its gradOutput by the derivative of the Sigmoid fused into that conv, evaluated from the
-  // activated output — instead of a pass of its own over B values in front of it
-  const float* dot_act_y;
-  int dot_act;
-  float dot_act_slope;
+  // the public two-call protocol around a conv (module-by-module hosts): vf_bn_fuse_next_* leave a request here, the next
+  // forward / data-gradient entry point takes it, unconditionally (vf_take_pending), and vf_bn_fuse_result reads what it made of it
+  VfBnRequest bn_pending;
+  int bn_result_rows = 0;
 };
 void vf_internal_wg_free(vf_ctx* ctx);
 
-// The one-shot attachments above (bnf, act_bits_out, dmask_bits, dot_act_y) are meant for the next launch of the call that
-// follows them.  A conv entry point that refuses its call (any error return) drops them, so that no later, unrelated launch
-// takes them: a stale mode-2 bnf would store that launch's output masked by another tensor's activation derivative.  Declared
-// first thing in each conv entry point; an error return is one that went through vf_set_error.
-unsigned vf_error_seq();
-struct VfOneShotScope {
-  vf_ctx* c;
-  unsigned seq;
-  explicit VfOneShotScope(vf_ctx* ctx) : c(ctx), seq(vf_error_seq()) {}
-  ~VfOneShotScope() {
-    if (!c || vf_error_seq() == seq) return;
-    c->bnf.mode = 0;
-    c->bnf_result_rows = 0;
-    c->act_bits_out = nullptr;
-    c->act_bits_written = 0;
-    c->dmask_bits = nullptr;
-    c->dot_act_y = nullptr;
-  }
-};
+// A public forward / data-gradient entry point: moves the pending request out of the context before anything else, so that a
+// refused call leaves nothing behind for an unrelated later launch, and hands it to the pass as an argument.
+template <class F>
+static inline int vf_take_pending(vf_ctx* ctx, F&& pass) {
+  VfConvExtras ex;
+  ex.bn = ctx->bn_pending;
+  ctx->bn_pending.st.mode = 0;
+  const int rc = pass(&ex);
+  if (ex.bn.st.mode) ctx->bn_result_rows = rc ? 0 : ex.bn_result_rows;
+  return rc;
+}
 
 static inline char* vf_ws_ptr(vf_ctx* c) { return (char*)c->ws + c->ws_front; }
 static inline size_t vf_ws_avail(vf_ctx* c) { return c->ws_bytes > c->ws_front ? c->ws_bytes - c->ws_front : 0; }
@@ -191,6 +195,92 @@ static inline int vf_ilog2(int v) {  // v must be a power of two
 }
 static inline bool vf_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline int64_t vf_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline bool vf_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+#define VF_OOB 0x80000000u   // byte offset that is always out of range of a buffer descriptor (operands are < 2 GiB)
+
+// Descriptor tables of the one-launch-per-net kernels, built by the hosts (vf_net.hip; video-filler_amd/backend.py mirrors the
+// layouts as COLSUM_DESC / WPLANES_DESC).  VfColsumDesc: every conv bias gradient of a backward walk (vf_bn.hip,
+// vf_bias_grad_multi).  VfWpDesc: every weight of a net to planes (vf_pgemm.hip, vf_weight_planes_multi).
+struct VfColsumDesc {
+  const float* g;          // [P][C] gradOutput
+  float* gb;               // [C]   gradBias:  gb = beta*gb + column sums
+  double* part;            // [gx][C] scratch partials
+  int64_t P;
+  int C, cq, rows_per_block, gx, gy;
+  int blk1_off, blk2_off;  // first block of this layer in stage 1 / stage 2
+  float beta;
+};
+static_assert(sizeof(VfColsumDesc) == 64, "descriptor layout is shared with the host mirror");
+struct VfWpDesc {
+  const float* w;        // physical [d0][16][d1]
+  void* nat;             // planes [3][d0][16][d1]
+  void* tr;              // planes [3][d1][16][d0]
+  int d0, d1;
+  int gx, gz;            // 32-wide tiles over d0 and d1
+  int blk_off;           // first block of this weight
+  int pad;
+};
+static_assert(sizeof(VfWpDesc) == 48, "descriptor layout is shared with the host mirror");
+
+// The split-K combine of the GEMM hosts (vf_conv.hip), plain or leaving BatchNorm statistics partials (st), and whether a shape
+// fits the latter
+int vf_internal_slab_reduce(vf_ctx* ctx, const float* slab, float* dst, const float* bias, int64_t total, int N, int ksplit, int act,
+                            float slope, const float* dmask, int dact, float dslope, const VfBnSt* st, int st_groups);
+bool vf_internal_slab_st_ok(int64_t total, int N, int groups, int rows_cap, int* blocks_per_group);
+
+// The statistics plan of a GEMM launch (launch_igemm's IGemm, launch_pconv's PGemm; g.ksplit is set, bm x . tiles in gm rows,
+// zpar parity classes).  With one K range per tile the epilogue leaves a partial row per row tile and parity class, where the
+// batch groups are whole tiles; under split-K the slab reduce leaves them (returns true: the combine gets &g.st).  A shape that
+// fits neither, or no request (ex NULL: an inner launch), leaves g.st.mode 0.  Mode 2 stores the output masked by the
+// activation derivative: what BatchNorm's backward sums.
+template <class G>
+static inline bool vf_plan_bn_stats(VfConvExtras* ex, G& g, int bm, int gm, int zpar) {
+  g.st.mode = 0;
+  if (!ex || !ex->bn.st.mode) return false;
+  const VfBnRequest& r = ex->bn;
+  VfBnSt st = r.st;
+  st.zpar = g.ksplit == 1 ? zpar : 1;
+  if (g.ksplit == 1) {
+    if (g.M % r.groups != 0 || (g.M / r.groups) % bm != 0 || (int64_t)(gm / r.groups) * zpar > r.rows_cap) return false;
+    st.tiles_per_group = gm / r.groups;
+  } else if (!vf_internal_slab_st_ok(g.out_elems, g.N, r.groups, r.rows_cap, &st.tiles_per_group)) {
+    return false;
+  }
+  st.rows_per_group = st.tiles_per_group * st.zpar;
+  g.st = st;
+  ex->bn_result_rows = st.rows_per_group;
+  if (st.mode == 2) {
+    g.dmask = r.yact;
+    g.dact = r.act;
+    g.dslope = r.slope;
+  }
+  return g.ksplit > 1;
+}
+
+// The conv entry points with their extras as an argument (ex is never NULL); the C-ABI forms wrap them (vf_take_pending)
+int vf_internal_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
+                           int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex);
+int vf_internal_conv2d_fwd_planes(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B, int H,
+                                  int W, int Cin, int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex);
+int vf_internal_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin, int Cout, int k,
+                                int stride, int pad, VfConvExtras* ex);
+int vf_internal_conv2d_bwd_data_act(vf_ctx* ctx, const float* gy, const float* w, float* gx, const float* x_act, int act, float slope,
+                                    int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, VfConvExtras* ex);
+int vf_internal_conv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes, float* gw,
+                                  float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, float beta,
+                                  const VfConvExtras* ex);
+int vf_internal_deconv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
+                             int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex);
+int vf_internal_deconv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin, int Cout, int k,
+                                  int stride, int pad, VfConvExtras* ex);
+int vf_internal_pconv_gather(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
+                             int Cout, int act, float slope, VfConvExtras* ex);
+int vf_internal_pconv_scatter(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
+                              int Cout, int act, float slope, const float* dmask, int dact, float dslope, VfConvExtras* ex);
+// a BatchNorm request as vf_bn_fuse_next_fwd / _bwd form it (vf_conv.hip)
+int vf_internal_bn_request_fwd(VfBnRequest* r, const float* shift, double* part, int part_rows_cap, int groups);
+int vf_internal_bn_request_bwd(VfBnRequest* r, const float* x, const float* y_act, int act, float slope, const float* save_mean,
+                               double* part, int part_rows_cap, int groups);
 
 // optim/adam.lua's element update, fp32 in the reference's operation order (one definition for k_adam and for the weight-gradient
 // kernel that applies it in its epilogue, vf_wgrad_small.hip): step = lr * sqrt(1 - b2^t) / (1 - b1^t)

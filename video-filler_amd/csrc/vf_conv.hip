@@ -45,7 +45,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 // Buffer loads with hardware range checking: an offset past num_records returns 0, so padding taps, ragged
 // tile edges and split-K tails need neither a branch nor a select — the loads stay in flight across the MFMAs.
-#define VF_OOB 0x80000000u   // byte offset that is always out of range (operands are < 2 GiB)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t vf_rsrc(const void* p, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
 }
@@ -1357,8 +1356,6 @@ __global__ __launch_bounds__(256) void k_col2im4x4(const float* __restrict__ col
 }
 
 // ================================================================================================ host
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 template <int BM, int BN, int WM, int WN, int BF>
 static void launch_igemm_tile_m(vf_ctx* ctx, const IGemm& g, dim3 grid, bool bkm, int v, const char* name, double flops,
                                 bool db = false) {
@@ -1406,11 +1403,11 @@ static void launch_igemm_tile(vf_ctx* ctx, const IGemm& g, dim3 grid, bool bkm, 
     launch_igemm_tile_m<BM, BN, WM, WN, 0>(ctx, g, grid, bkm, v, name, flops);
 }
 
-// vecA / vecB: 16-byte loads legal for the A / B operand.  top: this launch writes the pass's output tensor itself (an inner
-// GEMM into a column buffer does not), so a pending BatchNorm-statistics attachment (vf_bn_fuse_next_*) applies to it.
+// vecA / vecB: 16-byte loads legal for the A / B operand.  ex: the extras of the pass whose output tensor this launch writes
+// (BatchNorm statistics: vf_plan_bn_stats); NULL for an inner GEMM into a column buffer.
 int vf_internal_smallm_plan(int form, int M, int N, int K, size_t ws_bytes);                                                   // vf_smallm.hip
 int vf_internal_smallm_launch(vf_ctx* ctx, int form, const float* A, const float* W, float* slab, int M, int N, int K, int ksplit);
-static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, bool top = true) {
+static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, VfConvExtras* ex) {
   const int zpar = g.parity ? 4 : 1;
   const bool bkm = g.wsN == 1 && g.wsC != 1;
   const int64_t a_elems = (int64_t)(g.M >> (g.lgMh + g.lgMw)) * g.Hi * g.Wi * g.C;
@@ -1479,41 +1476,8 @@ static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, bool top = 
   }
   g.ksplit = ksplit;
   g.slab = ksplit > 1 ? (float*)vf_ws_ptr(ctx) : nullptr;
-  // ---- BatchNorm statistics as a by-product (one-shot attachment): from the epilogue, or from the slab reduce under split-K
-  g.st.mode = 0;
-  bool slab_st = false;
-  int st_upb = 0, st_bpg = 0, st_ncc = 0;
-  int64_t st_units = 0;
-  if (top && ctx->bnf.mode) {
-    const int groups = ctx->bnf_groups;
-    VfBnSt st = ctx->bnf;
-    bool fused = false;
-    if (ksplit == 1) {
-      if (g.M % groups == 0 && (g.M / groups) % t.bm == 0 && (int64_t)(gm / groups) * zpar <= ctx->bnf_rows_cap) {
-        st.tiles_per_group = gm / groups;
-        st.zpar = zpar;
-        st.rows_per_group = (gm / groups) * zpar;
-        g.st = st;
-        fused = true;
-      }
-    } else if (g.out_elems % 4 == 0 && slab_st_plan(g.out_elems, g.N, groups, ctx->bnf_rows_cap, &st_upb, &st_bpg, &st_ncc, &st_units)) {
-      st.tiles_per_group = st_bpg;
-      st.zpar = 1;
-      st.rows_per_group = st_bpg;
-      g.st = st;            // (the GEMM kernel ignores it under split-K; launch_slab_reduce_st gets it)
-      slab_st = true;
-      fused = true;
-    }
-    if (fused) {
-      ctx->bnf_result_rows = st.rows_per_group;
-      if (st.mode == 2) {   // the output is stored masked by the activation derivative: what BatchNorm's backward sums
-        g.dmask = ctx->bnf_yact;
-        g.dact = ctx->bnf_act;
-        g.dslope = ctx->bnf_slope;
-      }
-    }
-    ctx->bnf.mode = 0;
-  }
+  // ---- BatchNorm statistics as a by-product: from the epilogue, or from the slab reduce under split-K
+  const bool slab_st = vf_plan_bn_stats(ex, g, t.bm, gm, zpar);
   g.klin = !g.parity && g.lgMh == 0 && g.lgMw == 0 && g.TH * g.TW > 1 && t.bm == 64 && t.bn == 128 && !bkm && v == 2;
   g.gm = gm; g.gn = gn; g.gz = zpar * ksplit;
   dim3 grid((unsigned)gm * gn * zpar * ksplit);
@@ -1541,14 +1505,8 @@ static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, bool top = 
   VF_LAUNCH_CHECK();
   if (ksplit > 1) {
     VfProf prof(ctx, slab_st ? "slab_reduce_igemm_bnstats" : "slab_reduce_igemm", 0.0, 4.0 * (double)g.out_elems * (ksplit + 1));
-    if (slab_st) {
-      hipLaunchKernelGGL(k_slab_reduce_st, dim3((unsigned)(st_bpg * ctx->bnf_groups), (unsigned)st_ncc), dim3(256), 0, ctx->stream,
-                         (const float*)g.slab, g.Y, g.bias, g.out_elems / 4, g.N, ksplit, g.act, g.slope, g.dmask, g.dact, g.dslope,
-                         st_upb, st_units, st_ncc, g.st);
-      VF_LAUNCH_CHECK();
-      return 0;
-    }
-    return launch_slab_reduce(ctx, g.slab, g.Y, g.bias, g.out_elems, g.N, ksplit, g.act, g.slope, 0.f, g.dmask, g.dact, g.dslope);
+    return vf_internal_slab_reduce(ctx, g.slab, g.Y, g.bias, g.out_elems, g.N, ksplit, g.act, g.slope, g.dmask, g.dact, g.dslope,
+                                   slab_st ? &g.st : nullptr, slab_st ? ex->bn.groups : 1);
   }
   return 0;
 }
@@ -1574,40 +1532,50 @@ int vf_internal_slab_reduce(vf_ctx* ctx, const float* slab, float* dst, const fl
   return launch_slab_reduce(ctx, slab, dst, bias, total, N, ksplit, act, slope, 0.f, dmask, dact, dslope);
 }
 
-// ---- BatchNorm statistics attachment (see VfBnSt; consumed by the next conv-like launch of this context)
-VF_API int vf_bn_fuse_next_fwd(vf_ctx* ctx, const float* shift, double* part, int part_rows_cap, int groups) {
+// ---- BatchNorm statistics request (VfBnRequest).  The public protocol: vf_bn_fuse_next_* leave one in the context, the next
+// forward / data-gradient entry point takes it, unconditionally (vf_take_pending), vf_bn_fuse_result reads what it made of it.
+int vf_internal_bn_request_fwd(VfBnRequest* r, const float* shift, double* part, int part_rows_cap, int groups) {
   VF_REQUIRE(shift && part && part_rows_cap > 0 && groups >= 1 && groups <= 64, "vf_bn_fuse_next_fwd: bad arguments");
-  memset(&ctx->bnf, 0, sizeof(ctx->bnf));
-  ctx->bnf.mode = 1;
-  ctx->bnf.vec = shift;
-  ctx->bnf.part = part;
-  ctx->bnf_groups = groups;
-  ctx->bnf_rows_cap = part_rows_cap / groups;
-  ctx->bnf_result_rows = 0;
+  *r = VfBnRequest();
+  r->st.mode = 1;
+  r->st.vec = shift;
+  r->st.part = part;
+  r->groups = groups;
+  r->rows_cap = part_rows_cap / groups;
+  return 0;
+}
+int vf_internal_bn_request_bwd(VfBnRequest* r, const float* x, const float* y_act, int act, float slope, const float* save_mean,
+                               double* part, int part_rows_cap, int groups) {
+  VF_REQUIRE(x && save_mean && part && part_rows_cap > 0 && groups >= 1 && groups <= 64, "vf_bn_fuse_next_bwd: bad arguments");
+  VF_REQUIRE(act == VF_ACT_NONE || y_act != nullptr, "vf_bn_fuse_next_bwd: the activation derivative needs the activated output");
+  *r = VfBnRequest();
+  r->st.mode = 2;
+  r->st.vec = save_mean;
+  r->st.x = x;
+  r->st.part = part;
+  r->yact = act == VF_ACT_NONE ? nullptr : y_act;
+  r->act = act;
+  r->slope = slope;
+  r->groups = groups;
+  r->rows_cap = part_rows_cap / groups;
+  return 0;
+}
+VF_API int vf_bn_fuse_next_fwd(vf_ctx* ctx, const float* shift, double* part, int part_rows_cap, int groups) {
+  if (int rc = vf_internal_bn_request_fwd(&ctx->bn_pending, shift, part, part_rows_cap, groups)) return rc;
+  ctx->bn_result_rows = 0;
   return 0;
 }
 VF_API int vf_bn_fuse_next_bwd(vf_ctx* ctx, const float* x, const float* y_act, int act, float slope, const float* save_mean,
                                double* part, int part_rows_cap, int groups) {
-  VF_REQUIRE(x && save_mean && part && part_rows_cap > 0 && groups >= 1 && groups <= 64, "vf_bn_fuse_next_bwd: bad arguments");
-  VF_REQUIRE(act == VF_ACT_NONE || y_act != nullptr, "vf_bn_fuse_next_bwd: the activation derivative needs the activated output");
-  memset(&ctx->bnf, 0, sizeof(ctx->bnf));
-  ctx->bnf.mode = 2;
-  ctx->bnf.vec = save_mean;
-  ctx->bnf.x = x;
-  ctx->bnf.part = part;
-  ctx->bnf_yact = act == VF_ACT_NONE ? nullptr : y_act;
-  ctx->bnf_act = act;
-  ctx->bnf_slope = slope;
-  ctx->bnf_groups = groups;
-  ctx->bnf_rows_cap = part_rows_cap / groups;
-  ctx->bnf_result_rows = 0;
+  if (int rc = vf_internal_bn_request_bwd(&ctx->bn_pending, x, y_act, act, slope, save_mean, part, part_rows_cap, groups)) return rc;
+  ctx->bn_result_rows = 0;
   return 0;
 }
 VF_API int vf_bn_fuse_result(vf_ctx* ctx, int* rows_per_group) {
   VF_REQUIRE(rows_per_group != nullptr, "vf_bn_fuse_result: NULL");
-  *rows_per_group = ctx->bnf_result_rows;
-  ctx->bnf_result_rows = 0;
-  ctx->bnf.mode = 0;      // an attachment no launch took (thin or generic shapes) does not linger
+  *rows_per_group = ctx->bn_result_rows;
+  ctx->bn_result_rows = 0;
+  ctx->bn_pending.st.mode = 0;      // a request no entry point took does not linger
   return 0;
 }
 
@@ -1626,7 +1594,7 @@ static int check_conv_args(int B, int H, int W, int Cin, int Cout, int k, int st
 // (conv forward: A = x, n = Cout, weights [n][kh][kw][c];  full-conv data-grad: A = gy, n = Cin_full,
 //  weights [n][kh][kw][c] as well — same physical layout by construction.)
 static int conv_like_fwd(vf_ctx* ctx, const float* A, const float* w, const float* bias, float* Y, int B, int Hi, int Wi,
-                         int C, int N, int stride, int pad, int act, float slope) {
+                         int C, int N, int stride, int pad, int act, float slope, VfConvExtras* ex) {
   const int Ho = (Hi + 2 * pad - 4) / stride + 1, Wo = (Wi + 2 * pad - 4) / stride + 1;
   VF_REQUIRE(vf_is_pow2(Ho) && vf_is_pow2(Wo), "output spatial sizes must be powers of two");
   if (N == 1 && stride == 1 && Hi == 4 && Wi == 4) {
@@ -1647,7 +1615,7 @@ static int conv_like_fwd(vf_ctx* ctx, const float* A, const float* w, const floa
   g.outH = Ho; g.outW = Wo; g.osy = 1; g.osx = 1;
   g.out_elems = (int64_t)g.M * N;
   g.act = act; g.slope = slope;
-  return launch_igemm(ctx, g, (C % 16 == 0) && aligned16(A), (C % 16 == 0) && aligned16(w));
+  return launch_igemm(ctx, g, (C % 16 == 0) && vf_aligned16(A), (C % 16 == 0) && vf_aligned16(w), ex);
 }
 
 // Generic "transposed" pass: Y[b,oh,ow,n] = sum_{kh,kw,c : oh = 2i-1+kh ...} A[b,i,j,c] * Wt[c][kh][kw][n]
@@ -1656,9 +1624,9 @@ extern "C" int vf_act_bwd(vf_ctx* ctx, const float* y, const float* gy, float* g
 int vf_internal_deconv_thin_out(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int Hi, int Wi, int C,
                                 int N, int act, float slope);      // vf_conv_thin.hip
 static int conv_like_bwd(vf_ctx* ctx, const float* A, const float* w, const float* bias, float* Y, int B, int Hi, int Wi,
-                         int C, int N, int stride, int pad, int act, float slope, const float* dmask = nullptr, int dact = 0,
-                         float dslope = 0.f) {
-  if (stride == 2 && pad == 1 && N <= 4 && !dmask && !ctx->bnf.mode) {      // the image side: direct kernel, no column matrix
+                         int C, int N, int stride, int pad, int act, float slope, VfConvExtras* ex, const float* dmask = nullptr,
+                         int dact = 0, float dslope = 0.f) {
+  if (stride == 2 && pad == 1 && N <= 4 && !dmask && !ex->bn.st.mode) {      // the image side: direct kernel, no column matrix
     const int rc = vf_internal_deconv_thin_out(ctx, A, w, bias, Y, B, Hi, Wi, C, N, act, slope);
     if (rc >= 0) return rc;
   }
@@ -1669,9 +1637,9 @@ static int conv_like_bwd(vf_ctx* ctx, const float* A, const float* w, const floa
   g.Hi = Hi; g.Wi = Wi; g.C = C; g.N = N;
   g.wsN = 1; g.wsC = 16 * N; g.wsTap = N;
   g.act = act; g.slope = slope;
-  const bool vecA = (C % 16 == 0) && aligned16(A);
-  bool vecB = (N % 4 == 0) && aligned16(w);
-  if (stride == 2 && N < 32 && vecA && aligned16(w) && ctx->ws_front == 0) {
+  const bool vecA = (C % 16 == 0) && vf_aligned16(A);
+  bool vecB = (N % 4 == 0) && vf_aligned16(w);
+  if (stride == 2 && N < 32 && vecA && vf_aligned16(w) && ctx->ws_front == 0) {
     const int64_t Mi = (int64_t)B * Hi * Wi;
     const size_t col_bytes = (size_t)Mi * 16 * N * sizeof(float);
     if (col_bytes + ((size_t)32 << 20) <= ctx->ws_bytes) {
@@ -1689,7 +1657,7 @@ static int conv_like_bwd(vf_ctx* ctx, const float* A, const float* w, const floa
       q.outH = 1; q.outW = 1; q.osy = 1; q.osx = 1;
       q.out_elems = Mi * 16 * N;
       q.act = VF_ACT_NONE;
-      const int rc = launch_igemm(ctx, q, true, true, false);
+      const int rc = launch_igemm(ctx, q, true, true, nullptr);
       ctx->ws_front = 0;
       if (rc) return rc;
       const int64_t total = Mi * 4 * N;
@@ -1722,7 +1690,7 @@ static int conv_like_bwd(vf_ctx* ctx, const float* A, const float* w, const floa
     g.wsC = 16 * N; g.wsTap = 0;
     g.outH = 1; g.outW = 1; g.osy = 1; g.osx = 1;
     g.out_elems = (int64_t)B * 16 * N;
-    vecB = ((16 * N) % 4 == 0) && aligned16(w);
+    vecB = ((16 * N) % 4 == 0) && vf_aligned16(w);
   }
   VF_REQUIRE(!(dmask && bias), "activation-backward epilogue is for data-gradient passes (no bias)");
   const float* real_bias = bias;
@@ -1732,7 +1700,7 @@ static int conv_like_bwd(vf_ctx* ctx, const float* A, const float* w, const floa
     g.act = VF_ACT_NONE;
   }
   // (the 1x1 -> 4x4 form's GEMM columns are (kh, kw, n): not one channel per column, so no statistics by-product there)
-  if (int rc = launch_igemm(ctx, g, vecA, vecB, stride == 2)) return rc;
+  if (int rc = launch_igemm(ctx, g, vecA, vecB, stride == 2 ? ex : nullptr)) return rc;
   if (stride == 1 && real_bias) {
     const int64_t total = (int64_t)B * 16 * N;
     const int nb = (int)std::min<int64_t>(vf_cdiv(total, 256), 4096);
@@ -1951,8 +1919,8 @@ static int wgrad(vf_ctx* ctx, const float* U, const float* V, float* dW, int B, 
              "operand exceeds the 2 GiB buffer-descriptor range");
   g.u_bytes = (unsigned)((int64_t)g.P * Nu * 4);
   g.v_bytes = (unsigned)((int64_t)B * Hv * Wv * Cv * 4);
-  const bool vecU = (Nu % 4 == 0) && aligned16(U);
-  const bool vecV = (Cv % 4 == 0) && aligned16(V);
+  const bool vecU = (Nu % 4 == 0) && vf_aligned16(U);
+  const bool vecV = (Cv % 4 == 0) && vf_aligned16(V);
   g.beta = beta;
   const int BM = Nu > 64 ? 128 : 64;
   const int gy = (int)vf_cdiv(Nu, BM), gx = (int)vf_cdiv(ntaps * (int64_t)Cv, 128);
@@ -2100,77 +2068,79 @@ static bool main_net_shape(int H, int W, int k, int stride, int pad) {
 VF_API int vf_conv_is_fast(int H, int W, int k, int stride, int pad) { return main_net_shape(H, W, k, stride, pad) ? 1 : 0; }
 
 int vf_internal_conv_thin_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B, int H,
-                              int W, int Cin, int Cout, int act, float slope);      // vf_conv_thin.hip
-VF_API int vf_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
-                         int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
-  VfOneShotScope one_shot(ctx);
+                              int W, int Cin, int Cout, int act, float slope, VfConvExtras* ex);      // vf_conv_thin.hip
+int vf_internal_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
+                           int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex) {
   if (!main_net_shape(H, W, k, stride, pad)) return vf_internal_gconv_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, k, stride, pad, act, slope);
   if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
-  if (stride == 2 && Cin == 3 && !ctx->bnf.mode) {      // the image-side layers: direct convolution (vf_conv_thin.hip)
-    const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, nullptr, B, H, W, Cin, Cout, act, slope);
+  if (stride == 2 && Cin == 3 && !ex->bn.st.mode) {      // the image-side layers: direct convolution (vf_conv_thin.hip)
+    const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, nullptr, B, H, W, Cin, Cout, act, slope, ex);
     if (rc >= 0) return rc;
   }
-  return conv_like_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, stride, pad, act, slope);
+  return conv_like_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, stride, pad, act, slope, ex);
+}
+VF_API int vf_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
+                         int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
+    return vf_internal_conv2d_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, k, stride, pad, act, slope, ex);
+  });
 }
 
-VF_API int vf_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin,
-                              int Cout, int k, int stride, int pad) {
-  VfOneShotScope one_shot(ctx);
+int vf_internal_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin, int Cout, int k,
+                                int stride, int pad, VfConvExtras* ex) {
   if (!main_net_shape(H, W, k, stride, pad)) return vf_internal_gconv_bwd_data(ctx, gy, w, gx, B, H, W, Cin, Cout, k, stride, pad);
   if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
   const int Ho = (H + 2 * pad - 4) / stride + 1, Wo = (W + 2 * pad - 4) / stride + 1;
   if (stride == 1) {
     VF_REQUIRE(H == 4 && W == 4, "stride-1 conv data-grad is built for the 4x4 bottleneck input only");
-    if (Cout == 1) {
+    if (Cout == 1) {      // the 512 -> 1 head, with the derivative of the activation fused into this conv (VfConvExtras::dot_act_y)
       const int64_t n = (int64_t)B * 16 * Cin;
-      const float* ya = ctx->dot_act_y;      // one-shot: the derivative of the activation fused into this conv (vf_net.hip)
-      ctx->dot_act_y = nullptr;
-      hipLaunchKernelGGL(k_dot_bwd_data, dim3((int)vf_cdiv(n, 256)), dim3(256), 0, ctx->stream, gy, w, gx, B, 16 * Cin, ya, ctx->dot_act,
-                         ctx->dot_act_slope);
+      hipLaunchKernelGGL(k_dot_bwd_data, dim3((int)vf_cdiv(n, 256)), dim3(256), 0, ctx->stream, gy, w, gx, B, 16 * Cin, ex->dot_act_y,
+                         ex->dot_act, ex->dot_act_slope);
       VF_LAUNCH_CHECK();
       return 0;
     }
   }
-  return conv_like_bwd(ctx, gy, w, nullptr, gx, B, Ho, Wo, Cout, Cin, stride, pad, VF_ACT_NONE, 0.f);
+  return conv_like_bwd(ctx, gy, w, nullptr, gx, B, Ho, Wo, Cout, Cin, stride, pad, VF_ACT_NONE, 0.f, ex);
+}
+VF_API int vf_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin,
+                              int Cout, int k, int stride, int pad) {
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
+    return vf_internal_conv2d_bwd_data(ctx, gy, w, gx, B, H, W, Cin, Cout, k, stride, pad, ex);
+  });
 }
 
-VF_API int vf_conv2d_bwd_data_act(vf_ctx* ctx, const float* gy, const float* w, float* gx, const float* x_act, int act,
-                                  float slope, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad) {
-  VfOneShotScope one_shot(ctx);
+int vf_internal_conv2d_bwd_data_act(vf_ctx* ctx, const float* gy, const float* w, float* gx, const float* x_act, int act, float slope,
+                                    int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, VfConvExtras* ex) {
   if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
   VF_REQUIRE(x_act != nullptr && (act == VF_ACT_LRELU || act == VF_ACT_RELU),
              "vf_conv2d_bwd_data_act: needs the activated input and a (leaky) ReLU");
   VF_REQUIRE(stride == 2, "vf_conv2d_bwd_data_act: only the stride-2 layers follow a bare conv + activation pair");
   const int Ho = (H + 2 * pad - 4) / stride + 1, Wo = (W + 2 * pad - 4) / stride + 1;
-  return conv_like_bwd(ctx, gy, w, nullptr, gx, B, Ho, Wo, Cout, Cin, stride, pad, VF_ACT_NONE, 0.f, x_act, act, slope);
+  return conv_like_bwd(ctx, gy, w, nullptr, gx, B, Ho, Wo, Cout, Cin, stride, pad, VF_ACT_NONE, 0.f, ex, x_act, act, slope);
+}
+VF_API int vf_conv2d_bwd_data_act(vf_ctx* ctx, const float* gy, const float* w, float* gx, const float* x_act, int act,
+                                  float slope, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad) {
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
+    return vf_internal_conv2d_bwd_data_act(ctx, gy, w, gx, x_act, act, slope, B, H, W, Cin, Cout, k, stride, pad, ex);
+  });
 }
 
-static int conv2d_bwd_weight_impl(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
-                                  float* gw, float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, float beta);
-VF_API int vf_conv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, int B, int H, int W,
-                                int Cin, int Cout, int k, int stride, int pad, float beta) {
-  VfOneShotScope one_shot(ctx);
-  return conv2d_bwd_weight_impl(ctx, x, gy, nullptr, nullptr, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
-}
-// the same with the bf16 planes of both operands at hand (vf_planes_split layout): the weight gradient then runs on the
-// planes-fed kernel where its shape allows (whole 128 x 128 x 32 tiles), on the fp32 operands otherwise
-VF_API int vf_conv2d_bwd_weight_planes(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
-                                       float* gw, float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad,
-                                       float beta) {
-  VfOneShotScope one_shot(ctx);
-  return conv2d_bwd_weight_impl(ctx, x, gy, x_planes, gy_planes, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
-}
-static int conv2d_bwd_weight_impl(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
-                                  float* gw, float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, float beta) {
+// The weight-gradient entry points leave a pending BatchNorm request alone.  x_planes / gy_planes: the bf16 planes of both
+// operands (vf_planes_split layout), or NULL: the weight gradient runs on the planes-fed kernel where they are at hand and its
+// shape allows (whole 128 x 128 x 32 tiles), on the fp32 operands otherwise.  ex (NULL: plain): the 512 -> 1 head's dot_act_y
+int vf_internal_conv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes, float* gw,
+                                  float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, float beta,
+                                  const VfConvExtras* ex) {
   if (!main_net_shape(H, W, k, stride, pad))
     return vf_internal_gconv_bwd_weight(ctx, x, gy, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
   if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
   const int Ho = (H + 2 * pad - 4) / stride + 1, Wo = (W + 2 * pad - 4) / stride + 1;
   if (Cout == 1 && stride == 1 && H == 4 && W == 4) {
-    const float* ya = ctx->dot_act_y;      // (see vf_conv2d_bwd_data)
-    ctx->dot_act_y = nullptr;
+    const VfConvExtras plain;
+    if (!ex) ex = &plain;
     hipLaunchKernelGGL(k_dot_bwd_weight, dim3((int)vf_cdiv(16 * Cin, 64)), dim3(512), 0, ctx->stream, x, gy, gw, gb, B,
-                       16 * Cin, beta, ya, ctx->dot_act, ctx->dot_act_slope);
+                       16 * Cin, beta, ex->dot_act_y, ex->dot_act, ex->dot_act_slope);
     VF_LAUNCH_CHECK();
     return 0;
   }
@@ -2180,23 +2150,42 @@ static int conv2d_bwd_weight_impl(vf_ctx* ctx, const float* x, const float* gy, 
   if (gb) return bias_grad(ctx, gy, gb, (int64_t)B * Ho * Wo, Cout, beta);
   return 0;
 }
-
-VF_API int vf_deconv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
-                           int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
-  VfOneShotScope one_shot(ctx);
-  VF_REQUIRE(k == 4 && ((stride == 2 && pad == 1) || (stride == 1 && pad == 0)), "unsupported full-conv shape");
-  VF_REQUIRE(vf_is_pow2(H) && vf_is_pow2(W), "spatial sizes must be powers of two");
-  return conv_like_bwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, stride, pad, act, slope);
+VF_API int vf_conv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, int B, int H, int W,
+                                int Cin, int Cout, int k, int stride, int pad, float beta) {
+  return vf_internal_conv2d_bwd_weight(ctx, x, gy, nullptr, nullptr, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta, nullptr);
+}
+VF_API int vf_conv2d_bwd_weight_planes(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
+                                       float* gw, float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad,
+                                       float beta) {
+  return vf_internal_conv2d_bwd_weight(ctx, x, gy, x_planes, gy_planes, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta, nullptr);
 }
 
-VF_API int vf_deconv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin,
-                                int Cout, int k, int stride, int pad) {
-  VfOneShotScope one_shot(ctx);
+int vf_internal_deconv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
+                             int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex) {
+  VF_REQUIRE(k == 4 && ((stride == 2 && pad == 1) || (stride == 1 && pad == 0)), "unsupported full-conv shape");
+  VF_REQUIRE(vf_is_pow2(H) && vf_is_pow2(W), "spatial sizes must be powers of two");
+  return conv_like_bwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, stride, pad, act, slope, ex);
+}
+VF_API int vf_deconv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
+                           int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
+    return vf_internal_deconv2d_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, k, stride, pad, act, slope, ex);
+  });
+}
+
+int vf_internal_deconv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin, int Cout, int k,
+                                  int stride, int pad, VfConvExtras* ex) {
   VF_REQUIRE(k == 4 && ((stride == 2 && pad == 1) || (stride == 1 && pad == 0)), "unsupported full-conv shape");
   const int Ho = (H - 1) * stride - 2 * pad + 4, Wo = (W - 1) * stride - 2 * pad + 4;
   VF_REQUIRE(vf_is_pow2(H) && vf_is_pow2(W), "spatial sizes must be powers of two");
   // conv of gy (Ho x Wo, Cout channels) with weights [Cin][kh][kw][Cout] -> gx (H x W, Cin channels)
-  return conv_like_fwd(ctx, gy, w, nullptr, gx, B, Ho, Wo, Cout, Cin, stride, pad, VF_ACT_NONE, 0.f);
+  return conv_like_fwd(ctx, gy, w, nullptr, gx, B, Ho, Wo, Cout, Cin, stride, pad, VF_ACT_NONE, 0.f, ex);
+}
+VF_API int vf_deconv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin,
+                                int Cout, int k, int stride, int pad) {
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
+    return vf_internal_deconv2d_bwd_data(ctx, gy, w, gx, B, H, W, Cin, Cout, k, stride, pad, ex);
+  });
 }
 
 static int deconv2d_bwd_weight_impl(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
@@ -2212,12 +2201,10 @@ static int deconv2d_bwd_weight_impl(vf_ctx* ctx, const float* x, const float* gy
 }
 VF_API int vf_deconv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, int B, int H, int W,
                                   int Cin, int Cout, int k, int stride, int pad, float beta) {
-  VfOneShotScope one_shot(ctx);
   return deconv2d_bwd_weight_impl(ctx, x, gy, nullptr, nullptr, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
 }
 VF_API int vf_deconv2d_bwd_weight_planes(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
                                          float* gw, float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                                          float beta) {
-  VfOneShotScope one_shot(ctx);
   return deconv2d_bwd_weight_impl(ctx, x, gy, x_planes, gy_planes, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
 }

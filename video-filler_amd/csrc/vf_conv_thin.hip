@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void k_conv_thin_in(const float* __restrict__ 
       f32x2 v = {a0, a1};
       *(f32x2*)(y + o) = v;
       if (bits) {
-        // the sign bits a later data-gradient pass masks with (ctx->act_bits_out): lanes 0-31 / 32-63 of a wave hold the 64
+        // the sign bits a later data-gradient pass masks with (VfConvExtras::act_bits_out): lanes 0-31 / 32-63 of a wave hold the 64
         // channels of ONE pixel each (two per lane): word h of the pixel's group = the ballot over channels 2j + h
         const unsigned long long k0 = __ballot(a0 > 0.f), k1 = __ballot(a1 > 0.f);
         if ((tid & 31) == 0) {
@@ -255,9 +255,10 @@ int vf_internal_deconv_thin_out(vf_ctx* ctx, const float* x, const float* w, con
 }
 
 // conv forward with 3 input channels, 4x4 stride 2 pad 1; act in {none, LeakyReLU, ReLU}.  Returns -1 if the shape is not this
-// kernel's (the caller keeps the implicit-GEMM path), 0 when launched, > 0 on a launch error.
+// kernel's (the caller keeps the implicit-GEMM path), 0 when launched, > 0 on a launch error.  ex->act_bits_out: also leave the sign
+// bits of the activated output.
 int vf_internal_conv_thin_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B, int H,
-                              int W, int Cin, int Cout, int act, float slope) {
+                              int W, int Cin, int Cout, int act, float slope, VfConvExtras* ex) {
   if (ctx->mfma_bf16 == 1) return -1;       // (the bf16-operand mode rounds its operands: that is the GEMM kernels' business)
   if (Cin != 3 || Cout % 64 != 0 || H % (2 * TP) != 0 || W % (2 * TP) != 0) return -1;
   if (!(act == VF_ACT_NONE || act == VF_ACT_LRELU || act == VF_ACT_RELU)) return -1;
@@ -266,30 +267,31 @@ int vf_internal_conv_thin_fwd(vf_ctx* ctx, const float* x, const float* w, const
   const int tiles_x = W / (2 * TP), tiles_y = H / (2 * TP);
   const int64_t out = (int64_t)B * (H / 2) * (W / 2) * Cout;
   VfProf prof(ctx, y_planes ? "conv_thin_in_planes" : "conv_thin_in", 2.0 * (double)out * 16 * Cin, 0.0);
-  unsigned* bits = ctx->act_bits_out;      // one-shot (vf_net.hip): also leave the sign bits of the activated output
-  ctx->act_bits_out = nullptr;
-  ctx->act_bits_written = bits != nullptr;
+  ex->act_bits_written = ex->act_bits_out != nullptr;
   hipLaunchKernelGGL((k_conv_thin_in<3>), dim3((unsigned)(B * tiles_y), (unsigned)(Cout / 64)), dim3(256), 0, ctx->stream, x, w,
-                     bias, y, (unsigned short*)y_planes, out, H, W, Cout, tiles_x, tiles_y, neg, bits);
+                     bias, y, (unsigned short*)y_planes, out, H, W, Cout, tiles_x, tiles_y, neg, ex->act_bits_out);
   VF_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int vf_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
-                             int Cout, int k, int stride, int pad, int act, float slope);
 extern "C" int vf_planes_split(vf_ctx* ctx, const float* x, void* planes, int64_t n);
 
 // vf_conv2d_fwd that also leaves the three bf16 planes of y (for a planes-fed consumer): in the epilogue where the kernel
 // can (the thin-input layers above), else by a pass over y.
-VF_API int vf_conv2d_fwd_planes(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B,
-                                int H, int W, int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
-  VfOneShotScope one_shot(ctx);
+int vf_internal_conv2d_fwd_planes(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B, int H,
+                                  int W, int Cin, int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex) {
   VF_REQUIRE(y_planes != nullptr, "vf_conv2d_fwd_planes: y_planes is NULL (use vf_conv2d_fwd)");
   if (k == 4 && stride == 2 && pad == 1) {
-    const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, y_planes, B, H, W, Cin, Cout, act, slope);
+    const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, y_planes, B, H, W, Cin, Cout, act, slope, ex);
     if (rc >= 0) return rc;
   }
-  if (int rc = vf_conv2d_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, k, stride, pad, act, slope)) return rc;
+  if (int rc = vf_internal_conv2d_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, k, stride, pad, act, slope, ex)) return rc;
   const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
   return vf_planes_split(ctx, y, y_planes, (int64_t)B * Ho * Wo * Cout);
+}
+VF_API int vf_conv2d_fwd_planes(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B,
+                                int H, int W, int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
+    return vf_internal_conv2d_fwd_planes(ctx, x, w, bias, y, y_planes, B, H, W, Cin, Cout, k, stride, pad, act, slope, ex);
+  });
 }

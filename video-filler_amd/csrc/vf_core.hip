@@ -9,11 +9,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------ errors / ctx
 static thread_local char g_err[1024] = "";
-static thread_local unsigned g_err_seq = 0;      // errors set so far on this thread (VfOneShotScope)
 
-unsigned vf_error_seq() { return g_err_seq; }
 void vf_set_error(const char* fmt, ...) {
-  ++g_err_seq;
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
@@ -38,20 +35,7 @@ VF_API int vf_ctx_create(vf_ctx** out, int device, void* stream) {
   c->ws_front = 0;
   c->wg_active = 0;
   c->wg_rec = nullptr;
-  memset(&c->bnf, 0, sizeof(c->bnf));
-  c->bnf_yact = nullptr;
-  c->bnf_act = 0;
-  c->bnf_slope = 0.f;
-  c->bnf_groups = 1;
-  c->bnf_rows_cap = 0;
-  c->bnf_result_rows = 0;
   c->mfma_bf16 = 3;      // fp32 operands as three exact bf16 planes (see vf_ctx_set_mfma_mode)
-  c->act_bits_out = nullptr;
-  c->act_bits_written = 0;
-  c->dmask_bits = nullptr;
-  c->dot_act_y = nullptr;
-  c->dot_act = 0;
-  c->dot_act_slope = 0.f;
   *out = c;
   return 0;
 }

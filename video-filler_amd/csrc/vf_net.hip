@@ -10,11 +10,13 @@
 //     net:zeroGradParameters(), :training(), :evaluate()
 // This file is that net: the layer list the reference builds with netG:add(...) / netD:add(...) (train.lua:87-199,
 // train_vid_weighted.lua:112-236) executed with every cross-layer shortcut of the hot path, on the host side of the same
-// entry points a module-by-module host would call (vf_conv2d_*, vf_pconv_*, vf_bn_*, ...):
+// entry points a module-by-module host would call (vf_conv2d_*, vf_pconv_*, vf_bn_*, ...) — the convolutions through their
+// internal forms, which take what a pass does beyond its convolution as an argument (VfConvExtras, vf_common.h: BatchNorm
+// statistics, sign bits, the head's activation derivative); this file writes no field of the context:
 //   * an in-place LeakyReLU / ReLU (and a Tanh / Sigmoid right behind a convolution) is applied in its producer's epilogue
 //     and undone in the producer's backward — or, for conv -> LeakyReLU -> conv, in the NEXT conv's data-gradient epilogue;
 //   * BatchNorm statistics are a by-product of the GEMM that produces the tensor (forward) and of the data-gradient GEMM
-//     above it (backward): vf_bn_fuse_next_* / vf_bn_*_pre — no statistics pass over the tensor;
+//     above it (backward): VfConvExtras::bn / vf_bn_*_pre — no statistics pass over the tensor;
 //   * operands of the 4x4 stride-2 passes are bf16 PLANES split once by their producer (BatchNorm apply / backward, the
 //     thin-input convolution) and handed to the consumer (vf_pconv_*, k_pwgrad_group); weight planes of the whole net are
 //     refreshed in one launch per parameter update;
@@ -54,24 +56,6 @@ const bool g_no_pconv = getenv("VF_NO_PCONV") != nullptr;
 const bool g_no_bn_fuse = getenv("VF_NO_BN_FUSE") != nullptr;
 const bool g_pwgrad = !(getenv("VF_PWGRAD") && strcmp(getenv("VF_PWGRAD"), "1") != 0);
 
-struct VfColsumDescH {      // = VfColsumDesc of vf_bn.hip (64 bytes)
-  const float* g;
-  float* gb;
-  double* part;
-  int64_t P;
-  int C, cq, rows_per_block, gx, gy;
-  int blk1_off, blk2_off;
-  float beta;
-};
-static_assert(sizeof(VfColsumDescH) == 64, "descriptor layout is shared with vf_bn.hip");
-struct VfWpDescH {          // = VfWpDesc of vf_pgemm.hip (48 bytes)
-  const float* w;
-  void* nat;
-  void* tr;
-  int d0, d1, gx, gz, blk_off, pad;
-};
-static_assert(sizeof(VfWpDescH) == 48, "descriptor layout is shared with vf_pgemm.hip");
-
 struct Layer {
   vf_layer_desc d;
   int C = 0, H = 0, W = 0;       // input shape of the layer
@@ -91,7 +75,7 @@ struct Layer {
   void* gp = nullptr;            // conv: split of its gradOutput for the data-gradient pass
   void* yp = nullptr;            // BatchNorm / thin-input conv: planes of the own output, written beside it
   void* bgp = nullptr;           // BatchNorm: planes of its gradInput, written by its backward
-  unsigned* ybits = nullptr;     // thin-input conv + (Leaky)ReLU: sign bits of its output (vf_common.h act_bits_out), for the data-gradient above
+  unsigned* ybits = nullptr;     // thin-input conv + (Leaky)ReLU: sign bits of its output (VfConvExtras::act_bits_out), for the data-gradient above
   bool bits_live = false;        // ... written by the last forward (and nobody has edited y since)
   const void* out_planes = nullptr;     // set by the last forward: planes of y (or NULL)
   const void* grad_planes = nullptr;    // set by the last backward: planes of gx (or NULL)
@@ -246,18 +230,18 @@ int refresh_weight_planes(vf_net* n) {
     if (n->L[i].wp_live && n->L[i].wp_mode == n->ctx->mfma_bf16) live.push_back((int)i);
   if (live.empty()) return 0;
   if (live != n->wp_key || !n->wp_table) {
-    std::vector<VfWpDescH> desc(live.size());
+    std::vector<VfWpDesc> desc(live.size());
     int blocks = 0;
     for (size_t j = 0; j < live.size(); ++j) {
       Layer& l = n->L[live[j]];
       const int d0 = is_full(l) ? l.d.nin : l.d.nout, d1 = is_full(l) ? l.d.nout : l.d.nin;
       const int gx = (d0 + 31) / 32, gz = (d1 + 31) / 32;
-      desc[j] = VfWpDescH{n->params + l.w_off, l.wp_nat, l.wp_tr, d0, d1, gx, gz, blocks, 0};
+      desc[j] = VfWpDesc{n->params + l.w_off, l.wp_nat, l.wp_tr, d0, d1, gx, gz, blocks, 0};
       blocks += gx * 16 * gz;
     }
     void* dev = nullptr;       // a fresh table: a launch still in flight may be reading the old one (kept until destroy)
-    if (int rc = net_alloc(n->owned, &dev, desc.size() * sizeof(VfWpDescH))) return rc;
-    VF_CHECK_HIP(hipMemcpy(dev, desc.data(), desc.size() * sizeof(VfWpDescH), hipMemcpyHostToDevice));
+    if (int rc = net_alloc(n->owned, &dev, desc.size() * sizeof(VfWpDesc))) return rc;
+    VF_CHECK_HIP(hipMemcpy(dev, desc.data(), desc.size() * sizeof(VfWpDesc), hipMemcpyHostToDevice));
     n->wp_table = dev;
     n->wp_n = (int)live.size();
     n->wp_blocks = blocks;
@@ -267,7 +251,9 @@ int refresh_weight_planes(vf_net* n) {
 }
 
 // ---- forward pieces ------------------------------------------------------------------------------------------------
-int conv_forward(vf_net* n, Layer& l, const float* x, const void* in_planes, int Bn, int act, float slope, bool want_planes) {
+// ex: what the pass does beyond the convolution (the caller's BatchNorm request; this function adds the sign bits)
+int conv_forward(vf_net* n, Layer& l, const float* x, const void* in_planes, int Bn, int act, float slope, bool want_planes,
+                 VfConvExtras* ex) {
   vf_ctx* ctx = n->ctx;
   const float* w = n->params + l.w_off;
   const float* b = n->params + l.b_off;
@@ -284,12 +270,10 @@ int conv_forward(vf_net* n, Layer& l, const float* x, const void* in_planes, int
     if (relu_like(act) && !n->observer) {
       if (!l.ybits)
         if (int rc = net_alloc(n->act_owned, (void**)&l.ybits, sizeof(unsigned) * (size_t)n->B * l.Ho * l.Wo * (l.Co / 32))) return rc;
-      ctx->act_bits_out = l.ybits;
+      ex->act_bits_out = l.ybits;
     }
-    const int frc = vf_conv2d_fwd_planes(ctx, x, w, b, l.y, l.yp, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, act, slope);
-    l.bits_live = ctx->act_bits_out == nullptr && ctx->act_bits_written && relu_like(act) && !n->observer;
-    ctx->act_bits_out = nullptr;
-    ctx->act_bits_written = 0;
+    const int frc = vf_internal_conv2d_fwd_planes(ctx, x, w, b, l.y, l.yp, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, act, slope, ex);
+    l.bits_live = ex->act_bits_written && relu_like(act) && !n->observer;
     if (frc) return frc;
     l.out_planes = l.yp;
     l.x_seen = nullptr;
@@ -306,12 +290,12 @@ int conv_forward(vf_net* n, Layer& l, const float* x, const void* in_planes, int
     l.xp_seen = xp;
     const void* wp = nullptr;
     if (int rc = weight_planes(n, l, full, &wp)) return rc;
-    return full ? vf_pconv_scatter(ctx, xp, wp, b, l.y, Bn, l.H, l.W, l.C, l.Co, act, slope, nullptr, VF_ACT_NONE, 0.f)
-                : vf_pconv_gather(ctx, xp, wp, b, l.y, Bn, l.H, l.W, l.C, l.Co, act, slope);
+    return full ? vf_internal_pconv_scatter(ctx, xp, wp, b, l.y, Bn, l.H, l.W, l.C, l.Co, act, slope, nullptr, VF_ACT_NONE, 0.f, ex)
+                : vf_internal_pconv_gather(ctx, xp, wp, b, l.y, Bn, l.H, l.W, l.C, l.Co, act, slope, ex);
   }
   l.x_seen = nullptr;
-  return full ? vf_deconv2d_fwd(ctx, x, w, b, l.y, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, act, slope)
-              : vf_conv2d_fwd(ctx, x, w, b, l.y, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, act, slope);
+  return full ? vf_internal_deconv2d_fwd(ctx, x, w, b, l.y, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, act, slope, ex)
+              : vf_internal_conv2d_fwd(ctx, x, w, b, l.y, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, act, slope, ex);
 }
 
 int bn_forward(vf_net* n, Layer& l, const float* x, int Bn, int act, float slope, int pre_rows, bool want_planes) {
@@ -353,8 +337,10 @@ int bn_forward(vf_net* n, Layer& l, const float* x, int Bn, int act, float slope
 
 // ---- backward pieces -----------------------------------------------------------------------------------------------
 // in_act != NONE: `x` is the in-place activated output of the module below; its updateGradInput rides in this epilogue
+// (ex->dmask_bits: the mask `x` as sign bits, where its producer left them).  ex also carries the BatchNorm request and the head's
+// activation derivative
 int conv_bwd_data(vf_net* n, Layer& l, const float* x, const float* go, int Bn, int in_act, float in_slope, const void* g_planes,
-                  const unsigned* in_bits = nullptr) {
+                  VfConvExtras* ex) {
   vf_ctx* ctx = n->ctx;
   const float* w = n->params + l.w_off;
   const bool full = is_full(l);
@@ -369,18 +355,15 @@ int conv_bwd_data(vf_net* n, Layer& l, const float* x, const float* go, int Bn, 
     l.gp_seen = gp;
     const void* wp = nullptr;
     if (int rc = weight_planes(n, l, !full, &wp)) return rc;
-    if (full) return vf_pconv_gather(ctx, gp, wp, nullptr, l.gx, Bn, l.Ho, l.Wo, l.Co, l.C, VF_ACT_NONE, 0.f);
-    ctx->dmask_bits = in_act != VF_ACT_NONE ? in_bits : nullptr;      // (one-shot: the mask `x` as sign bits, where its producer left them)
-    const int rc = vf_pconv_scatter(ctx, gp, wp, nullptr, l.gx, Bn, l.Ho, l.Wo, l.Co, l.C, VF_ACT_NONE, 0.f,
-                                    in_act != VF_ACT_NONE ? x : nullptr, in_act, in_slope);
-    ctx->dmask_bits = nullptr;
-    return rc;
+    if (full) return vf_internal_pconv_gather(ctx, gp, wp, nullptr, l.gx, Bn, l.Ho, l.Wo, l.Co, l.C, VF_ACT_NONE, 0.f, ex);
+    return vf_internal_pconv_scatter(ctx, gp, wp, nullptr, l.gx, Bn, l.Ho, l.Wo, l.Co, l.C, VF_ACT_NONE, 0.f,
+                                     in_act != VF_ACT_NONE ? x : nullptr, in_act, in_slope, ex);
   }
   l.g_seen = nullptr;
   if (in_act != VF_ACT_NONE)
-    return vf_conv2d_bwd_data_act(ctx, go, w, l.gx, x, in_act, in_slope, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad);
-  return full ? vf_deconv2d_bwd_data(ctx, go, w, l.gx, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad)
-              : vf_conv2d_bwd_data(ctx, go, w, l.gx, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad);
+    return vf_internal_conv2d_bwd_data_act(ctx, go, w, l.gx, x, in_act, in_slope, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, ex);
+  return full ? vf_internal_deconv2d_bwd_data(ctx, go, w, l.gx, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, ex)
+              : vf_internal_conv2d_bwd_data(ctx, go, w, l.gx, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, ex);
 }
 
 struct Deferred {
@@ -391,7 +374,7 @@ struct Deferred {
   float beta;
 };
 
-int conv_acc(vf_net* n, Layer& l, const float* x, const float* go, int Bn, std::vector<Deferred>* deferred) {
+int conv_acc(vf_net* n, Layer& l, const float* x, const float* go, int Bn, std::vector<Deferred>* deferred, const VfConvExtras* ex) {
   vf_ctx* ctx = n->ctx;
   const bool full = is_full(l);
   float* gw = n->grads + l.w_off;
@@ -419,11 +402,9 @@ int conv_acc(vf_net* n, Layer& l, const float* x, const float* go, int Bn, std::
   const void *xp = l.xp_seen, *gp = l.gp_seen;
   l.g_seen = nullptr;        // single use: only a data-gradient pass of THIS walk may hand its planes over
   l.gp_seen = nullptr;
-  if (planes)
-    return full ? vf_deconv2d_bwd_weight_planes(ctx, x, go, xp, gp, gw, gb, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, beta)
-                : vf_conv2d_bwd_weight_planes(ctx, x, go, xp, gp, gw, gb, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, beta);
-  return full ? vf_deconv2d_bwd_weight(ctx, x, go, gw, gb, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, beta)
-              : vf_conv2d_bwd_weight(ctx, x, go, gw, gb, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, beta);
+  if (!planes) xp = gp = nullptr;
+  return full ? vf_deconv2d_bwd_weight_planes(ctx, x, go, xp, gp, gw, gb, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, beta)
+              : vf_internal_conv2d_bwd_weight(ctx, x, go, xp, gp, gw, gb, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, beta, ex);
 }
 
 // gsel >= 0: x / gy / y_act hold batch group gsel only (a pass over one of the concatenated batches): its saved statistics.
@@ -482,7 +463,7 @@ int bias_grad_flush(vf_net* n, const std::vector<Deferred>& items) {
   std::string key((const char*)items.data(), items.size() * sizeof(Deferred));
   auto it = n->colsum_plans.find(key);
   if (it == n->colsum_plans.end()) {
-    std::vector<VfColsumDescH> desc(items.size());
+    std::vector<VfColsumDesc> desc(items.size());
     char* ws = vf_ws_ptr(n->ctx);
     size_t off = 0;
     int b1 = 0, b2 = 0;
@@ -490,15 +471,15 @@ int bias_grad_flush(vf_net* n, const std::vector<Deferred>& items) {
       const Deferred& d = items[i];
       int cq, rpb, gx, gy;
       if (int rc = vf_bias_grad_plan(d.P, d.C, &cq, &rpb, &gx, &gy)) return rc;
-      desc[i] = VfColsumDescH{d.g, d.gb, (double*)(ws + off), d.P, d.C, cq, rpb, gx, gy, b1, b2, d.beta};
+      desc[i] = VfColsumDesc{d.g, d.gb, (double*)(ws + off), d.P, d.C, cq, rpb, gx, gy, b1, b2, d.beta};
       off += ((size_t)gx * d.C * 8 + 255) / 256 * 256;
       b1 += gx * gy;
       b2 += (d.C + 3) / 4;
     }
     VF_REQUIRE(off <= vf_ws_avail(n->ctx), "vf_net: workspace too small for the bias-gradient partials");
     void* dev = nullptr;
-    if (int rc = net_alloc(n->owned, &dev, desc.size() * sizeof(VfColsumDescH))) return rc;
-    VF_CHECK_HIP(hipMemcpy(dev, desc.data(), desc.size() * sizeof(VfColsumDescH), hipMemcpyHostToDevice));
+    if (int rc = net_alloc(n->owned, &dev, desc.size() * sizeof(VfColsumDesc))) return rc;
+    VF_CHECK_HIP(hipMemcpy(dev, desc.data(), desc.size() * sizeof(VfColsumDesc), hipMemcpyHostToDevice));
     it = n->colsum_plans.emplace(key, std::make_pair(dev, std::vector<int>{(int)items.size(), b1, b2})).first;
   }
   const std::vector<int>& g = it->second.second;
@@ -562,8 +543,9 @@ int net_walk_back(vf_net* n, const float* x_in, const float* gy, const float** g
     }
     if (is_conv(l)) {
       const float* go = g;
+      VfConvExtras ex;      // what this layer's backward passes do beyond their convolutions
       // netD's 512 -> 1 head (train.lua:195-196: conv 4x4 on the 4x4 map + Sigmoid): the Sigmoid's derivative rides in the two dot
-      // kernels of its backward pass (vf_ctx::dot_act_y) instead of a launch of its own over B values
+      // kernels of its backward pass (VfConvExtras::dot_act_y) instead of a launch of its own over B values
       const bool dot_head = l.d.kind == VF_L_CONV && l.Co == 1 && l.d.k == 4 && l.d.stride == 1 && l.d.pad == 0 && l.H == 4 && l.W == 4 &&
                             l.fused_act != VF_ACT_NONE && !relu_like(l.fused_act) && !act_done;
       if (l.fused_act != VF_ACT_NONE && !act_done && !dot_head) {
@@ -605,28 +587,23 @@ int net_walk_back(vf_net* n, const float* x_in, const float* gy, const float** g
           const float* xbn = slice(entry_out(n, idx - 2, nullptr), (int64_t)pm.H * pm.W * pm.C);      // the BatchNorm's input
           const float* yact = pm.fused_act != VF_ACT_NONE ? x : nullptr;                              // (x IS pm's output)
           const float* smv = gi >= 0 ? pm.sm + (int64_t)gi * pm.C : pm.sm;
-          if ((rc = vf_bn_fuse_next_bwd(ctx, xbn, yact, pm.fused_act, pm.fused_slope, smv, pm.part, pm.part_rows_cap,
-                                        gi >= 0 ? 1 : n->groups)))
+          if ((rc = vf_internal_bn_request_bwd(&ex.bn, xbn, yact, pm.fused_act, pm.fused_slope, smv, pm.part, pm.part_rows_cap,
+                                               gi >= 0 ? 1 : n->groups)))
             break;
           fuse_below = true;
         }
       }
-      auto arm_head = [&]() {
-        ctx->dot_act_y = dot_head ? mout : nullptr;
-        ctx->dot_act = l.fused_act;
-        ctx->dot_act_slope = l.fused_slope;
-      };
+      ex.dot_act_y = dot_head ? mout : nullptr;
+      ex.dot_act = l.fused_act;
+      ex.dot_act_slope = l.fused_slope;
       if (want_gx) {
-        arm_head();
-        rc = conv_bwd_data(n, l, x, go, Bn, fuse_below ? VF_ACT_NONE : in_act, in_slope, g_pl, fuse_below ? nullptr : in_bits);
-        ctx->dot_act_y = nullptr;
-        if (fuse_below && !rc) rc = vf_bn_fuse_result(ctx, &pre);
+        if (!fuse_below && in_act != VF_ACT_NONE) ex.dmask_bits = in_bits;
+        rc = conv_bwd_data(n, l, x, go, Bn, fuse_below ? VF_ACT_NONE : in_act, in_slope, g_pl, &ex);
+        pre = ex.bn_result_rows;
         if (rc) break;
       }
       if (want_gp) {
-        arm_head();
-        rc = conv_acc(n, l, x, go, Bn, &deferred);
-        ctx->dot_act_y = nullptr;
+        rc = conv_acc(n, l, x, go, Bn, &deferred, &ex);
         if (rc) break;
       }
       g = want_gx ? l.gx : nullptr;
@@ -1123,18 +1100,19 @@ VF_API int vf_net_forward(vf_net* n, const float* x, const float** y) {
       n->fwd_wait_comm = nullptr;
     }
     if (is_conv(l)) {
+      VfConvExtras ex;
       if (l.fused_act == VF_ACT_NONE && nxt && nxt->d.kind == VF_L_BN && bn_fusable(n, *nxt) && nxt->d.nout == l.Co) {
         // the BatchNorm behind this convolution gets its statistics from the convolution's own epilogue
-        if ((rc = vf_bn_fuse_next_fwd(ctx, nxt->rm, nxt->part, nxt->part_rows_cap, n->groups))) return rc;
-        if ((rc = conv_forward(n, l, cur, cur_pl, n->B, VF_ACT_NONE, 0.f, false))) return rc;
-        if ((rc = vf_bn_fuse_result(ctx, &pre_rows))) return rc;
+        if ((rc = vf_internal_bn_request_fwd(&ex.bn, nxt->rm, nxt->part, nxt->part_rows_cap, n->groups))) return rc;
+        if ((rc = conv_forward(n, l, cur, cur_pl, n->B, VF_ACT_NONE, 0.f, false, &ex))) return rc;
+        pre_rows = ex.bn_result_rows;
         cur = l.y;
         cur_pl = nullptr;
         continue;
       }
       const bool want_pl = nxt && is_conv(*nxt) && pconv_layer(*nxt) &&
                            pconv_ok(n, *nxt, n->B, l.Ho, l.Wo, nxt->d.nin, nxt->d.nout, is_full(*nxt));
-      if ((rc = conv_forward(n, l, cur, cur_pl, n->B, l.fused_act, l.fused_slope, want_pl))) return rc;
+      if ((rc = conv_forward(n, l, cur, cur_pl, n->B, l.fused_act, l.fused_slope, want_pl, &ex))) return rc;
       cur = l.y;
       cur_pl = l.out_planes;
       if (relu_like(l.fused_act) && (rc = run_observer(n, e.act, l.y, (int64_t)n->B * l.Ho * l.Wo * l.Co, cur_pl))) return rc;

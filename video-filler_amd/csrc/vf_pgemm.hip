@@ -26,7 +26,6 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-#define VF_OOB 0x80000000u
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t pg_rsrc(const void* p, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
 }
@@ -128,17 +127,7 @@ __global__ __launch_bounds__(256) void k_weight_planes(const float* __restrict__
 }
 
 // every weight of a net in ONE launch (the nets refresh their weight planes once per parameter update: three launches per
-// training iteration instead of one per layer).  Descriptor table on the device, mirrored by backend.WPLANES_DESC.
-struct VfWpDesc {
-  const float* w;        // physical [d0][16][d1]
-  void* nat;             // planes [3][d0][16][d1]
-  void* tr;              // planes [3][d1][16][d0]
-  int d0, d1;
-  int gx, gz;            // 32-wide tiles over d0 and d1
-  int blk_off;           // first block of this weight
-  int pad;
-};
-static_assert(sizeof(VfWpDesc) == 48, "descriptor layout is shared with the host mirror");
+// training iteration instead of one per layer).  Descriptor table on the device: VfWpDesc (vf_common.h).
 __global__ __launch_bounds__(256) void k_weight_planes_multi(const VfWpDesc* __restrict__ d, int n, int npl) {
   int l = 0;
   while (l + 1 < n && (int)blockIdx.x >= d[l + 1].blk_off) ++l;
@@ -1598,13 +1587,6 @@ VF_API int vf_pconv_set_routing(int gather_patch, int scatter_patch) {
   return 0;
 }
 
-static inline bool pg_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// shared with vf_conv.hip: the split-K combine (plain and with BatchNorm statistics)
-int vf_internal_slab_reduce(vf_ctx* ctx, const float* slab, float* dst, const float* bias, int64_t total, int N, int ksplit, int act,
-                            float slope, const float* dmask, int dact, float dslope, const VfBnSt* st, int st_groups);
-bool vf_internal_slab_st_ok(int64_t total, int N, int groups, int rows_cap, int* blocks_per_group);
-
 // what the shapes must satisfy for the planes GEMM (callers fall back to vf_conv.hip's kernels otherwise)
 static bool pg_shape_ok(int B, int Hl, int Wl, int C, int N) {
   return C % 32 == 0 && N >= 32 && N % 4 == 0 && (int64_t)B * Hl * Wl > 64 && vf_is_pow2(Hl) && vf_is_pow2(Wl);
@@ -1623,7 +1605,7 @@ static PgKernel pg_reg_kernel(int ch) {
   return ch == 64 ? k_pconv<BM, 64, WM, 32, NTAPS, 64> : k_pconv<BM, 64, WM, 32, NTAPS, 32>;
 }
 
-static int launch_pconv(vf_ctx* ctx, PGemm& g, int ntaps, const char* what) {
+static int launch_pconv(vf_ctx* ctx, PGemm& g, int ntaps, VfConvExtras* ex) {
   // ---- channel step, tile, split-K
   const int zpar = g.parity ? 4 : 1;
   const int ch = g.C % 64 == 0 ? 64 : 32;      // channels per K step: whole 128-byte lines where possible
@@ -1650,42 +1632,8 @@ static int launch_pconv(vf_ctx* ctx, PGemm& g, int ntaps, const char* what) {
   g.slab = ksplit > 1 ? (float*)vf_ws_ptr(ctx) : nullptr;
   g.gm = gm; g.gn = gn; g.gz = zpar * ksplit;
   const unsigned nt = (unsigned)(blocks * ksplit);
-  // ---- BatchNorm statistics attachment (vf_bn_fuse_next_*): same contract as vf_conv.hip's launch_igemm
-  g.st.mode = 0;
-  bool slab_st = false;
-  int st_groups = 1;
-  if (ctx->bnf.mode) {
-    const int groups = ctx->bnf_groups;
-    VfBnSt st = ctx->bnf;
-    bool fused = false;
-    int bpg = 0;
-    if (ksplit == 1) {
-      if (g.M % groups == 0 && (g.M / groups) % bm == 0 && (int64_t)(gm / groups) * zpar <= ctx->bnf_rows_cap) {
-        st.tiles_per_group = gm / groups;
-        st.zpar = zpar;
-        st.rows_per_group = (gm / groups) * zpar;
-        g.st = st;
-        fused = true;
-      }
-    } else if (vf_internal_slab_st_ok(g.out_elems, g.N, groups, ctx->bnf_rows_cap, &bpg)) {
-      st.tiles_per_group = bpg;
-      st.zpar = 1;
-      st.rows_per_group = bpg;
-      g.st = st;
-      slab_st = true;
-      st_groups = groups;
-      fused = true;
-    }
-    if (fused) {
-      ctx->bnf_result_rows = st.rows_per_group;
-      if (st.mode == 2) {
-        g.dmask = ctx->bnf_yact;
-        g.dact = ctx->bnf_act;
-        g.dslope = ctx->bnf_slope;
-      }
-    }
-    ctx->bnf.mode = 0;
-  }
+  // ---- BatchNorm statistics as a by-product: from the epilogue, or from the slab reduce under split-K
+  const bool slab_st = vf_plan_bn_stats(ex, g, bm, gm, zpar);
   const bool one_plane = ctx->mfma_bf16 == 1;
   VF_REQUIRE(!one_plane || use_dma, "vf_pconv: in the bf16-operand mode the planes path serves whole 64-channel / 64-row tiles only "
              "(vf_pconv_supported_in_mode)");
@@ -1753,7 +1701,7 @@ static int launch_pconv(vf_ctx* ctx, PGemm& g, int ntaps, const char* what) {
   if (ksplit > 1) {
     VfProf prof(ctx, slab_st ? "slab_reduce_pconv_bnstats" : "slab_reduce_pconv", 0.0, 4.0 * (double)g.out_elems * (ksplit + 1));
     return vf_internal_slab_reduce(ctx, g.slab, g.Y, g.bias, g.out_elems, g.N, ksplit, g.act, g.slope, g.dmask, g.dact, g.dslope,
-                                   slab_st ? &g.st : nullptr, st_groups);
+                                   slab_st ? &g.st : nullptr, slab_st ? ex->bn.groups : 1);
   }
   return 0;
 }
@@ -1773,7 +1721,7 @@ static int pg_fill_common(vf_ctx* ctx, PGemm& g, const void* a, int64_t a_elems,
 
 // conv-like pass: Y[b,oy,ox,n] = sum_{kh,kw,c} A[b, 2oy-1+kh, 2ox-1+kw, c] * Wp[n][kh][kw][c]      (4x4, stride 2, pad 1)
 static int pconv_like_fwd(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* Y, int B, int Hi, int Wi, int C,
-                          int N, int act, float slope) {
+                          int N, int act, float slope, VfConvExtras* ex) {
   const int Ho = Hi / 2, Wo = Wi / 2;
   PGemm g;
   if (int rc = pg_fill_common(ctx, g, ap, (int64_t)B * Hi * Wi * C, wp, (int64_t)N * 16 * C, bias, Y)) return rc;
@@ -1786,12 +1734,12 @@ static int pconv_like_fwd(vf_ctx* ctx, const void* ap, const void* wp, const flo
   g.outH = Ho; g.outW = Wo; g.osy = 1; g.osx = 1;
   g.out_elems = (int64_t)g.M * N;
   g.act = act; g.slope = slope;
-  return launch_pconv(ctx, g, 16, "fwd");
+  return launch_pconv(ctx, g, 16, ex);
 }
 // transposed pass: Y[b,oh,ow,n] = sum_{kh,kw,c : oh = 2i-1+kh, ow = 2j-1+kw} A[b,i,j,c] * Wp[n][kh][kw][c]; per output parity
 // (ph, pw) a 2x2-tap GEMM over the low-res grid: window rows i = my + ph - 1 + th, filter row kh = 3 - ph - 2*th
 static int pconv_like_tr(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* Y, int B, int Hi, int Wi, int C, int N,
-                         int act, float slope, const float* dmask = nullptr, int dact = 0, float dslope = 0.f) {
+                         int act, float slope, const float* dmask, int dact, float dslope, VfConvExtras* ex) {
   PGemm g;
   if (int rc = pg_fill_common(ctx, g, ap, (int64_t)B * Hi * Wi * C, wp, (int64_t)N * 16 * C, bias, Y)) return rc;
   g.lgMh = vf_ilog2(Hi); g.lgMw = vf_ilog2(Wi);
@@ -1805,15 +1753,14 @@ static int pconv_like_tr(vf_ctx* ctx, const void* ap, const void* wp, const floa
   g.out_elems = (int64_t)B * g.outH * g.outW * N;
   g.act = act; g.slope = slope;
   g.dmask = dmask; g.dact = dact; g.dslope = dslope;
-  // one-shot (vf_net.hip): the same mask as sign bits, where the tensor's producer left them and the channel count is whole groups
-  g.dbits = (dmask && N % 64 == 0) ? ctx->dmask_bits : nullptr;
-  ctx->dmask_bits = nullptr;
-  return launch_pconv(ctx, g, 4, "tr");
+  // the same mask as sign bits, where the tensor's producer left them (vf_net.hip) and the channel count is whole groups
+  g.dbits = (dmask && N % 64 == 0) ? ex->dmask_bits : nullptr;
+  return launch_pconv(ctx, g, 4, ex);
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
 VF_API int vf_planes_split(vf_ctx* ctx, const float* x, void* planes, int64_t n) {
-  VF_REQUIRE(n % 4 == 0 && pg_aligned16(x) && ((uintptr_t)planes & 7) == 0, "vf_planes_split: n %% 4 == 0 and aligned buffers");
+  VF_REQUIRE(n % 4 == 0 && vf_aligned16(x) && ((uintptr_t)planes & 7) == 0, "vf_planes_split: n %% 4 == 0 and aligned buffers");
   const int64_t n4 = n / 4;
   const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(vf_cdiv(n4, 256 * 2), 4096));
   if (ctx->mfma_bf16 == 1) {
@@ -1857,17 +1804,25 @@ VF_API int vf_pconv_supported_in_mode(int mfma_mode, int B, int H, int W, int Ci
   return (Cin % 64 == 0 && Cout % 64 == 0 && M % 64 == 0) ? 1 : 0;
 }
 /* conv forward / full-conv data-gradient: gather planes `ap` [B][H][W][Cin], weight planes `wp` [Cout][16][Cin] */
+int vf_internal_pconv_gather(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
+                             int Cout, int act, float slope, VfConvExtras* ex) {
+  VF_REQUIRE(vf_pconv_supported_in_mode(ctx->mfma_bf16, B, H, W, Cin, Cout, 4, 2, 1, 0), "vf_pconv_gather: unsupported shape B=%d %dx%d %d->%d (product mode %d)", B, H, W, Cin, Cout, ctx->mfma_bf16);
+  return pconv_like_fwd(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope, ex);
+}
 VF_API int vf_pconv_gather(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
                            int Cout, int act, float slope) {
-  VfOneShotScope one_shot(ctx);
-  VF_REQUIRE(vf_pconv_supported_in_mode(ctx->mfma_bf16, B, H, W, Cin, Cout, 4, 2, 1, 0), "vf_pconv_gather: unsupported shape B=%d %dx%d %d->%d (product mode %d)", B, H, W, Cin, Cout, ctx->mfma_bf16);
-  return pconv_like_fwd(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope);
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) { return vf_internal_pconv_gather(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope, ex); });
 }
 /* conv data-gradient / full-conv forward: low-res planes `ap` [B][H][W][Cin] -> y [B][2H][2W][Cout], weight planes [Cout][16][Cin] */
-VF_API int vf_pconv_scatter(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
-                            int Cout, int act, float slope, const float* dmask, int dact, float dslope) {
-  VfOneShotScope one_shot(ctx);
+int vf_internal_pconv_scatter(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
+                              int Cout, int act, float slope, const float* dmask, int dact, float dslope, VfConvExtras* ex) {
   VF_REQUIRE(vf_pconv_supported_in_mode(ctx->mfma_bf16, B, H, W, Cin, Cout, 4, 2, 1, 1), "vf_pconv_scatter: unsupported shape B=%d %dx%d %d->%d (product mode %d)", B, H, W, Cin, Cout, ctx->mfma_bf16);
   VF_REQUIRE(!(dmask && bias), "vf_pconv_scatter: the activation-backward epilogue is for data-gradient passes (no bias)");
-  return pconv_like_tr(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope, dmask, dact, dslope);
+  return pconv_like_tr(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope, dmask, dact, dslope, ex);
+}
+VF_API int vf_pconv_scatter(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
+                            int Cout, int act, float slope, const float* dmask, int dact, float dslope) {
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
+    return vf_internal_pconv_scatter(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope, dmask, dact, dslope, ex);
+  });
 }
