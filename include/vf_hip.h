@@ -391,6 +391,21 @@ int vf_image_whole_frames(vf_ctx* ctx, const void* src, int src_layout, float* o
  * double; max of the same crop of the mask}.  One block, fixed order: deterministic. */
 int vf_crop_stats(vf_ctx* ctx, const float* clip, const unsigned char* mask, int C, int iH, int iW, int fs, int w1, int h1,
                   double* out);
+/* datavid/donkey_wholeim.lua:141-215 (trainHook of train_wholeim_input.lua's loader) for ONE 3-channel frame, the
+ * module-global mask already scaled (:72; mask: DEVICE uint8 height x width, non-zero = masked, or NULL: all zero):
+ * image.scale to height x width; maskedFill with mask_value; frame, masked frame and mask shifted up-left by
+ * (crop_h-1, crop_w-1) — both 1-based draws — with ZERO bands bottom and right; all three mirrored over the full width
+ * if flip; windows of fs x fs at steps floor((height-fs)/(arr_h-1)), floor((width-fs)/(arr_w-1)), rows outermost;
+ * mul(2):add(-1) on the frames.  Channels-last rows of the loader batch: masked fs x fs x (3*arr_h*arr_w) (every
+ * window of the masked frame), full and maskout fs x fs x 12 (windows (0,0), (0,1), (1,0), (1,1) of the frame and of
+ * the mask as 0/1 floats).  sum (DEVICE double[1]): the sum of window (0,0) of the shifted, mirrored, unmasked frame
+ * before the [-1,1] map (the dark test of :188-189), accumulated in double in a fixed order.  Only the windows' pixels
+ * are evaluated; the scaled frame is never stored.  The geometry the reference is not defined for is an error before
+ * anything is launched: steps below 2, a window loop that does not visit arr_h x arr_w windows, arrays below 2 x 2, a
+ * crop beyond the scaled frame.  Uses fs doubles of the workspace. */
+int vf_patch_array_prepare(vf_ctx* ctx, const void* src, int src_layout, const unsigned char* mask, float* masked, float* full,
+                           float* maskout, double* sum, int H, int W, int height, int width, int fs, int arr_h, int arr_w,
+                           int crop_w, int crop_h, int flip, float mask_value);
 
 /* ---- baseline JPEG decode (vf_jpeg.hip) -------------------------------------------------------------
  * image.load of data/donkey_folder.lua and datavid/donkey_folder.lua (libjpeg's default decompression) on the device,

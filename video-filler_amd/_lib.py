@@ -84,6 +84,7 @@ SIGNATURES = {
     "vf_image_hook2d": (i32, [vp, vp, i32, vp] + [i32] * 9),
     "vf_image_whole_frames": (i32, [vp, vp, i32, vp] + [i32] * 8 + [vp, f32]),
     "vf_crop_stats": (i32, [vp, vp, vp] + [i32] * 6 + [vp]),
+    "vf_patch_array_prepare": (i32, [vp, vp, i32] + [vp] * 5 + [i32] * 10 + [f32]),
     "vf_jpeg_inspect": (i32, [vp, sz, i32, vp, C.c_char_p, i32]),
     "vf_jpeg_workspace_bytes": (i32, [vp, vp, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_jpeg_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp]),

@@ -799,6 +799,24 @@ class HipBackend:
             assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (iH, iW)
         self._c("vf_crop_stats", _ptr(clip), _ptr(mask), Cc, iH, iW, fs, w1, h1, _ptr(out))
 
+    def patch_array_prepare(self, src, hwc, mask, masked, full, maskout, total, height, width, arr_h, arr_w, crop_w, crop_h,
+                            flip, mask_value):
+        """datavid/donkey_wholeim.lua:141-215 for one frame (src: 1 frame, 3 channels).  mask: uint8 height x width or None;
+        masked / full / maskout: 1 x (3*arr_h*arr_w | 12 | 12) x fs x fs channels-last rows; total: float64[1], device — the
+        sum of the top-left window (the dark test).  crop_w, crop_h: the 1-based draws."""
+        fs = full.shape[-1]
+        H, W = (src.shape[1], src.shape[2]) if hwc else (src.shape[2], src.shape[3])
+        assert src.is_contiguous() and src.shape[0] == 1 and src.dtype == (torch.uint8 if hwc else torch.float32)
+        assert (src.shape[3] if hwc else src.shape[1]) == 3, "the patch-array hook takes 3-channel frames"
+        assert tuple(masked.shape) == (1, 3 * arr_h * arr_w, fs, fs) and is_nhwc(masked) and masked.dtype == torch.float32
+        for t in (full, maskout):
+            assert tuple(t.shape) == (1, 12, fs, fs) and is_nhwc(t) and t.dtype == torch.float32
+        assert total.dtype == torch.float64 and total.numel() >= 1
+        if mask is not None:
+            assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (height, width)
+        self._c("vf_patch_array_prepare", _ptr(src), 1 if hwc else 0, _ptr(mask), _ptr(masked), _ptr(full), _ptr(maskout),
+                _ptr(total), H, W, height, width, fs, arr_h, arr_w, crop_w, crop_h, int(bool(flip)), mask_value)
+
     # ---- baseline JPEG decode (vf_jpeg.hip, DESIGN.md 5.2)
     def jpeg_decode(self, files, channels=3, subseq_bytes=256, infos=None):
         """Decode a batch of supported JPEG files (bytes each) into one device uint8 buffer.  -> (out, offsets, status,

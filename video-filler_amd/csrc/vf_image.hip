@@ -3,7 +3,10 @@
 //   * vf_image_hook2d: data/donkey_folder.lua:40-88 for ONE decoded image — resize, crop at (w1, h1), hflip, [0,1] -> [-1,1]
 //     into one row of the loader batch, evaluating only the crop's pixels;
 //   * vf_image_whole_frames: test_vid_wholeim.lua:109-141 — resize, maskedFill, pad bottom-right, [0,1] -> [-1,1];
-//   * vf_crop_stats: the dark-crop mean and the mask test of datavid/donkey_folder.lua:148-165 as one device pair.
+//   * vf_crop_stats: the dark-crop mean and the mask test of datavid/donkey_folder.lua:148-165 as one device pair;
+//   * vf_patch_array_prepare: datavid/donkey_wholeim.lua:141-215 for ONE decoded frame — resize, maskedFill, shift, hflip, the
+//     arr_h x arr_w window array and its four output windows, [0,1] -> [-1,1], into one row of the three channels-last batch
+//     tensors, with the dark test's sum.
 // One fused kernel: every output pixel recomputes the few row-pass values (`tmp` of scaleBilinear) its column pass
 // reads, so the scaled image is never materialised.  The arithmetic is the restatement's float32, one rounding per
 // operation in its order (the library builds with -ffp-contract=off; IEEE division): results are bit-identical to
@@ -169,6 +172,92 @@ __global__ void __launch_bounds__(256) k_crop_stats(const float* __restrict__ cl
   }
 }
 
+// datavid/donkey_wholeim.lua:141-215 (trainHook of train_wholeim_input.lua's loader) for ONE frame, after its loadImage: the
+// frame scaled to h x w is shifted up-left by (crop_h-1, crop_w-1) with ZERO bands bottom and right (the masked copy and the
+// mask too), mirrored over the full width if flip, and cut into arr_h x arr_w windows of fs x fs, steph / stepw apart.
+struct PatchArray {
+  const void* src;
+  const unsigned char* mask;   // h x w Byte, or NULL
+  float *masked, *full, *maskout;
+  double* part;                // [fs] row partials of the top-left window's sum
+  int H, W, h, w, fs, arr_h, arr_w, steph, stepw, dy, dx, flip;   // dy = crop_h-1, dx = crop_w-1
+  float mask_value;
+};
+
+// Block y writes output row y of every window.  Item i = x * P + p (P windows, p fastest): the three channels of pixel (y, x)
+// of window p, so neighbouring threads store neighbouring 12-byte pieces of the fs x fs x 3P record array, and the (at most) four
+// threads of a pixel that own an output window store its 48-byte records of `full` and `maskout`.  The scaled pixel is evaluated
+// once per window.  Window 0 of the unmasked input, before the [-1,1] map, is the dark test's patch (:188-189): its sum is
+// accumulated in double, per thread in item order, then over the block in a fixed tree — the same bits on every run.
+template <int SRC>
+__global__ void __launch_bounds__(256) k_patch_array(const PatchArray p) {
+  __shared__ double ssum[256];
+  const int y = blockIdx.x, P = p.arr_h * p.arr_w, C3 = 3 * P;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < p.fs * P; i += 256) {
+    const int x = i / P, win = i - x * P;
+    const int ih = win / p.arr_w, iw = win - ih * p.arr_w;
+    const int X = iw * p.stepw + x;
+    const int sy = ih * p.steph + y + p.dy, sx = (p.flip ? p.w - 1 - X : X) + p.dx;
+    const bool in = sy < p.h && sx < p.w;
+    const bool m = in && p.mask && p.mask[(int64_t)sy * p.w + sx];
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      v[c] = 0.f;
+      if (in) {
+        auto load = [&](int j, int k) -> float {
+          if (SRC == SRC_F32_CHW) return ((const float*)p.src)[((int64_t)c * p.H + j) * p.W + k];
+          return (float)((const unsigned char*)p.src)[((int64_t)j * p.W + k) * 3 + c] / 255.f;
+        };
+        v[c] = vf_rowcol_at<false>(sy, p.H, p.h, [&](int j) { return vf_rowcol_at<false>(sx, p.W, p.w, [&](int k) { return load(j, k); }); });
+      }
+    }
+    if (win == 0) {
+      s += (double)v[0];
+      s += (double)v[1];
+      s += (double)v[2];
+    }
+    const int64_t pix = (int64_t)y * p.fs + x;
+    float* mo = p.masked + pix * C3 + 3 * win;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float t = (m ? p.mask_value : v[c]) * 2.f;
+      mo[c] = t + -1.f;
+    }
+    if (ih <= 1 && iw <= 1) {                  // h1 = ih, w1 = iw for steps >= 2 (:201-203)
+      const int64_t o = pix * 12 + 3 * (2 * ih + iw);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float t = v[c] * 2.f;
+        p.full[o + c] = t + -1.f;
+        p.maskout[o + c] = m ? 1.f : 0.f;
+      }
+    }
+  }
+  ssum[threadIdx.x] = s;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) ssum[threadIdx.x] += ssum[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) p.part[y] = ssum[0];
+}
+
+// the n row partials of k_patch_array into out[0]: one block, fixed order
+__global__ void __launch_bounds__(256) k_sum_partials(const double* __restrict__ part, int n, double* __restrict__ out) {
+  __shared__ double ssum[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += part[i];
+  ssum[threadIdx.x] = s;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) ssum[threadIdx.x] += ssum[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = ssum[0];
+}
+
 }  // namespace
 
 VF_API int vf_image_scale(vf_ctx* ctx, const void* src, int src_layout, float* dst, int N, int C, int H, int W, int height,
@@ -217,6 +306,41 @@ VF_API int vf_crop_stats(vf_ctx* ctx, const float* clip, const unsigned char* ma
              "vf_crop_stats: crop (%d,%d)+%d outside the %dx%d clip", w1, h1, fs, iW, iH);
   VfProf prof(ctx, "crop_stats", 0.0, 4.0 * (double)C * fs * fs);
   hipLaunchKernelGGL(k_crop_stats, dim3(1), dim3(256), 0, ctx->stream, clip, mask, C, iH, iW, fs, w1, h1, out);
+  VF_LAUNCH_CHECK();
+  return 0;
+}
+
+VF_API int vf_patch_array_prepare(vf_ctx* ctx, const void* src, int src_layout, const unsigned char* mask, float* masked, float* full,
+                                  float* maskout, double* sum, int H, int W, int height, int width, int fs, int arr_h, int arr_w,
+                                  int crop_w, int crop_h, int flip, float mask_value) {
+  if (int e = scale_check("vf_patch_array_prepare", 1, 3, H, W, height, width)) return e;
+  VF_REQUIRE(src_layout == SRC_F32_CHW || src_layout == SRC_U8_HWC,
+             "vf_patch_array_prepare: src_layout %d is not 0 (float CHW) or 1 (uint8 HWC)", src_layout);
+  VF_REQUIRE(fs > 0 && arr_h >= 2 && arr_w >= 2 && arr_h <= 64 && arr_w <= 64,
+             "vf_patch_array_prepare: fineSize %d, a %dx%d patch array (needs fineSize > 0 and 2 to 64 windows a side)", fs, arr_h, arr_w);
+  const int steph = height >= fs ? (height - fs) / (arr_h - 1) : 0, stepw = width >= fs ? (width - fs) / (arr_w - 1) : 0;
+  VF_REQUIRE(steph >= 2 && stepw >= 2,
+             "vf_patch_array_prepare: the %dx%d scaled frame and a %dx%d array of %d-pixel windows give steps %d and %d (both must be "
+             ">= 2)", height, width, arr_h, arr_w, fs, steph, stepw);
+  VF_REQUIRE((height - fs) / steph + 1 == arr_h && (width - fs) / stepw + 1 == arr_w,
+             "vf_patch_array_prepare: steps %d and %d over the %dx%d scaled frame visit %dx%d windows of %d pixels, not the %dx%d of the "
+             "array", steph, stepw, height, width, (height - fs) / steph + 1, (width - fs) / stepw + 1, fs, arr_h, arr_w);
+  VF_REQUIRE(crop_h >= 1 && crop_w >= 1 && crop_h <= height && crop_w <= width,
+             "vf_patch_array_prepare: crop (%d,%d) outside the %dx%d scaled frame (1-based, at most the frame's sides)", crop_w, crop_h,
+             height, width);
+  VF_REQUIRE(vf_ws_avail(ctx) >= (size_t)fs * sizeof(double), "vf_patch_array_prepare: the workspace holds %zu bytes, the row partials need %zu",
+             vf_ws_avail(ctx), (size_t)fs * sizeof(double));
+  PatchArray p;
+  p.src = src; p.mask = mask; p.masked = masked; p.full = full; p.maskout = maskout;
+  p.part = (double*)vf_ws_ptr(ctx);
+  p.H = H; p.W = W; p.h = height; p.w = width; p.fs = fs; p.arr_h = arr_h; p.arr_w = arr_w; p.steph = steph; p.stepw = stepw;
+  p.dy = crop_h - 1; p.dx = crop_w - 1; p.flip = flip ? 1 : 0; p.mask_value = mask_value;
+  VfProf prof(ctx, "patch_array_prepare", 0.0,
+              (src_layout == SRC_F32_CHW ? 12.0 : 3.0) * (double)H * W + (double)height * width + 4.0 * (double)fs * fs * (3 * arr_h * arr_w + 24));
+  if (src_layout == SRC_F32_CHW) hipLaunchKernelGGL(k_patch_array<SRC_F32_CHW>, dim3(fs), dim3(256), 0, ctx->stream, p);
+  else hipLaunchKernelGGL(k_patch_array<SRC_U8_HWC>, dim3(fs), dim3(256), 0, ctx->stream, p);
+  VF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, (const double*)p.part, fs, sum);
   VF_LAUNCH_CHECK();
   return 0;
 }

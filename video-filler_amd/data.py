@@ -6,7 +6,9 @@ draws the random numbers; cropping, masking, flipping, the [0,1] -> [-1,1] map a
 kernel per sample, writing straight into the batch buffers the closures read (`vf_clip_prepare`, `vf_center_prepare`).
 The resize before them — Torch7's image.scale in the loaders' loadImage / loadContImages — is on the device too
 (vf_image.hip): `image_scale`, `ImageBatcher` (train.lua's loader, one fused launch per image) and
-`ClipBatcher.add_frames` take decoded frames.  The decode before them — image.load, libjpeg underneath — is on the
+`ClipBatcher.add_frames` take decoded frames, and `PatchArrayBatcher` (train_wholeim_input.lua's loader: the 3 x 3
+patch array of datavid/donkey_wholeim.lua, one fused launch per frame, `vf_patch_array_prepare`) does the same for the
+widest net.  The decode before them — image.load, libjpeg underneath — is on the
 device as well (vf_jpeg.hip): `decode_jpeg` turns a batch of baseline JPEG files into those frames,
 byte for byte what libjpeg gives, so the host only reads the files and draws the random numbers.
 """
@@ -123,6 +125,46 @@ def load_size(H, W, loadSize, scalef=None):
 def draw_scalef(loadSize, rng):
     """The random scale of loadSize < 0: uniform in [0.5, 1.5] for -1, in [1, 3] for any other negative value."""
     return float(rng.uniform(0.5, 1.5)) if loadSize == -1 else float(rng.uniform(1, 3))
+
+
+def _patch_array_shape(nc, array_h, array_w):
+    """the conditions of the patch-array hook that do not depend on a frame"""
+    if nc != 3:
+        raise ValueError("patch array: nc=%d, the hook writes channel triples (nc must be 3)" % nc)
+    if array_h < 2 or array_w < 2:
+        raise ValueError("patch array: a %dx%d array needs at least 2 windows a side" % (array_h, array_w))
+
+
+def patch_array_steps(height, width, fineSize, array_h=3, array_w=3, nc=3, crop_h=1, crop_w=1):
+    """(steph, stepw) of the window loop of datavid/donkey_wholeim.lua:153-154,196-197 over a height x width scaled frame,
+    or ValueError naming the geometry where the reference is not defined: the hook hard-codes 3 channels; a step below 2
+    leaves `out` channels unwritten (floor(h/steph) no longer numbers the rows from 0); a loop that visits more than
+    array_h x array_w windows indexes past `masked`; a crop beyond the frame has no source."""
+    fs = int(fineSize)
+    where = "a %dx%d array of %d-pixel windows over the %dx%d scaled frame" % (array_h, array_w, fs, height, width)
+    _patch_array_shape(nc, array_h, array_w)
+    steph = (height - fs) // (array_h - 1) if height >= fs else 0
+    stepw = (width - fs) // (array_w - 1) if width >= fs else 0
+    if steph < 2 or stepw < 2:
+        raise ValueError("patch array: %s gives steps %d and %d (both must be >= 2)" % (where, steph, stepw))
+    nh, nw = (height - fs) // steph + 1, (width - fs) // stepw + 1
+    if (nh, nw) != (array_h, array_w):
+        raise ValueError("patch array: %s: steps %d and %d visit %dx%d windows" % (where, steph, stepw, nh, nw))
+    if not (1 <= crop_h <= height and 1 <= crop_w <= width):
+        raise ValueError("patch array: crop (%d,%d) outside the %dx%d scaled frame" % (crop_w, crop_h, height, width))
+    return steph, stepw
+
+
+def draw_patch_array(H, W, loadSize, rng):
+    """The random decisions of train_wholeim_input.lua's loader for an H x W frame, in its order (host only):
+    scalef when loadSize < 0 (datavid/donkey_wholeim.lua:61-67), crop_w = torch.random(100), crop_h = torch.random(70)
+    (:167-168, 1-based), the flip uniform > 0.6 (:177).  -> {height, width, crop_w, crop_h, flip}."""
+    scalef = draw_scalef(loadSize, rng) if loadSize < 0 else None
+    height, width = load_size(H, W, loadSize, scalef)
+    crop_w = int(rng.integers(1, 101))
+    crop_h = int(rng.integers(1, 71))
+    flip = bool(rng.uniform() > 0.6)
+    return dict(height=height, width=width, crop_w=crop_w, crop_h=crop_h, flip=flip)
 
 
 def byte_mask(decoded):
@@ -361,6 +403,72 @@ class ClipBatcher:
 
     def batch(self):
         """(real_ctx, real_full, real_mask) — the loader contract of datavid/dataset.lua:426."""
+        assert self.n == self.B, "batch holds %d of %d samples" % (self.n, self.B)
+        self.n = 0
+        return self.masked, self.full, self.mask
+
+
+class PatchArrayBatcher:
+    """train_wholeim_input.lua's loader (datavid/donkey_wholeim.lua:49-74 loadImage, :141-215 trainHook) feeding the
+    (ctx, full, mask) batch of datavid/dataset_wholeim.lua:400-429 to VidTrainer(nc_in=3*array_h*array_w, nc_out=12).
+
+    set_mask(mask) takes the loader's module-global Byte mask (`byte_mask`).  add(image) takes ONE decoded frame (uint8
+    H x W x 3, or float 3 x H x W in [0,1]; host or device — a view returned by `decode_jpeg` too), rescales the mask
+    state from its previous state (on EVERY call, rejected samples included), draws the loader's random numbers from
+    `rng` in its order (`draw_patch_array`) and launches one kernel that resizes, fills, shifts, flips and cuts the
+    array_h x array_w windows straight into row `n` of the three channels-last batch tensors; the dark test reads the
+    top-left window's sum back (double, fixed order) and draws its extra uniform only for a dark sample.  A rejected
+    sample does not advance the row: the next one overwrites it.  batch() returns (masked, full, mask)."""
+
+    mask_state = last = None
+
+    def __init__(self, batchSize, nc=3, fineSize=128, loadSize=360, array_h=3, array_w=3, maskValue=110.0 / 255.0, rng=None):
+        B = get_backend()
+        _patch_array_shape(nc, array_h, array_w)
+        self.B, self.nc, self.fs, self.loadSize = batchSize, nc, fineSize, loadSize
+        self.arr_h, self.arr_w, self.maskValue = array_h, array_w, float(maskValue)
+        self.rng = rng or np.random.default_rng()
+        dev = B.device
+        self.masked = nhwc_empty(batchSize, nc * array_h * array_w, fineSize, fineSize, dev)
+        self.full = nhwc_empty(batchSize, nc * 4, fineSize, fineSize, dev)
+        self.mask = nhwc_empty(batchSize, nc * 4, fineSize, fineSize, dev)
+        self.total = B.empty(1, dtype=torch.float64)
+        self.n = 0
+
+    def set_mask(self, mask):
+        """0/1 uint8 [1 x] H x W; add rescales it in place of the old one on every call (datavid/donkey_wholeim.lua:72)."""
+        m = torch.as_tensor(mask)
+        assert m.dtype == torch.uint8, "the mask is a ByteTensor (byte_mask)"
+        self.mask_state = get_backend().from_host(m.reshape(1, m.shape[-2], m.shape[-1])).contiguous()
+
+    def add(self, image, decisions=None):
+        """decisions: {height, width, crop_w, crop_h, flip} instead of the draws (the dark rule still draws from `rng`).
+        Returns True unless the sample is rejected; `last` holds the sizes and decisions, `mean` and `rejected`."""
+        B = get_backend()
+        assert self.n < self.B, "batch is full"
+        assert self.mask_state is not None, "set_mask() first: the loader's mask is part of its state"
+        t = torch.as_tensor(image)
+        hwc = t.dtype == torch.uint8
+        src, N, C, H, W = _frames(t, hwc)
+        assert N == 1 and C == self.nc, "one %d-channel frame, got %d x %d channels" % (self.nc, N, C)
+        d = dict(decisions) if decisions is not None else draw_patch_array(H, W, self.loadSize, self.rng)
+        height, width = d["height"], d["width"]
+        patch_array_steps(height, width, self.fs, self.arr_h, self.arr_w, self.nc, d["crop_h"], d["crop_w"])
+        mask = B.empty(1, height, width, dtype=torch.uint8)
+        B.image_scale_u8(self.mask_state.unsqueeze(0), mask.unsqueeze(0))          # :72, before the hook, on every call
+        self.mask_state = mask
+        n = self.n
+        B.patch_array_prepare(src, hwc, mask[0], self.masked[n:n + 1], self.full[n:n + 1], self.mask[n:n + 1], self.total,
+                              height, width, self.arr_h, self.arr_w, d["crop_w"], d["crop_h"], d["flip"], self.maskValue)
+        mean = self.total.item() / (self.nc * self.fs * self.fs)              # :188-189, TH's mean: a double sum / n
+        rejected = bool(mean < 0.1 and self.rng.uniform() > 0.1)              # :189-193
+        self.last = dict(d, mean=mean, rejected=rejected)
+        if not rejected:
+            self.n += 1
+        return not rejected
+
+    def batch(self):
+        """(real_ctx, real_full, real_mask) as train_wholeim_input.lua:394 reads them."""
         assert self.n == self.B, "batch holds %d of %d samples" % (self.n, self.B)
         self.n = 0
         return self.masked, self.full, self.mask
