@@ -439,6 +439,24 @@ int vf_jpeg_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, 
                    const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
                    int32_t* status, int32_t* rounds);
 
+/* ---- PNG encode (vf_png.hip) ---------------------------------------------------------------------------
+ * image.save of test_vid.lua:138, test_vid_wholeim.lua:229-242 and test_more_complex.lua:200-214 on the device: a batch
+ * of n frames of one H x W x C in, n whole PNG files out, back to back.  8-bit samples, C = 3 (colour type 2) or 1
+ * (colour type 0), no interlace, sides 1 to 16384, n up to 65535; anything else is an error naming the geometry,
+ * before anything is launched.  kind 0: float n x C x H x W, every value through image.savePNG's rule
+ * b = (uint8) trunc(255f * min(max(x, 0), 1)) in float32 (NaN: 0); kind 1: uint8 n x H x W x C, taken as they are.
+ * Rows carry the adaptive filter libpng chooses by default (smallest sum of absolute filtered values, None, Sub, Up,
+ * Average, Paeth in that order on ties); the filtered stream is deflated in independent 8 KiB chunks, one IDAT each,
+ * dynamic Huffman codes over LZ77 tokens or a stored block when that is not smaller.  A file's bytes depend on its own
+ * frame only, and are the same on every run.
+ * vf_png_workspace_bytes (host only, no GPU): the DEVICE workspace and an upper bound on the output for the batch. */
+int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, size_t* out_bytes);
+/* Encode on the context's stream.  ws (>= ws_bytes) and out (out_cap >= the bound above) are caller-owned DEVICE memory;
+ * offsets (DEVICE int64[n + 1]) receives the files' places: file i is out[offsets[i] .. offsets[i + 1]).  Nothing is
+ * allocated and nothing synchronises. */
+int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, void* ws, size_t ws_bytes,
+                  unsigned char* out, size_t out_cap, int64_t* offsets);
+
 /* ---- option branches of train.lua: noiseGen (:109-124, 319-327) and conditionAdv (:158-180) -----------------------
  * nn.JoinTable(2) over NHWC tensors: dst[p][c_dst + c] = src[p][c_src + c] for c < Ccopy, p < npix (forward: one call
  * per table element into the joined tensor; updateGradInput: one call per element out of the joined gradient).

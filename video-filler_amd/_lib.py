@@ -88,6 +88,8 @@ SIGNATURES = {
     "vf_jpeg_inspect": (i32, [vp, sz, i32, vp, C.c_char_p, i32]),
     "vf_jpeg_workspace_bytes": (i32, [vp, vp, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_jpeg_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp]),
+    "vf_png_workspace_bytes": (i32, [i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
+    "vf_png_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_channel_copy": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, i64]),
     "vf_noise_fill": (i32, [vp, vp, i64, u64, vp, u64, i32]),
     "vf_bce_fwd": (i32, [vp, vp, f32, i32, vp]),

@@ -225,6 +225,20 @@ def jpeg_inspect(data, walk=True):
     return d
 
 
+PNG_CHUNK = 8192     # filtered bytes per deflate block and IDAT chunk (csrc/vf_png.hip)
+
+
+def png_workspace_bytes(n, H, W, channels):
+    """(device workspace bytes, upper bound on the output bytes) of a PNG batch of n frames of H x W x channels
+    (vf_png_workspace_bytes; host only, no GPU needed).  ValueError, naming the geometry, for what the encoder does not
+    take: channels other than 1 or 3, a side outside 1..16384."""
+    lib = _lib.load()
+    ws_b, out_b = C.c_size_t(), C.c_size_t()
+    if lib.vf_png_workspace_bytes(int(n), int(H), int(W), int(channels), C.byref(ws_b), C.byref(out_b)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return ws_b.value, out_b.value
+
+
 class HipBackend:
     name = "hip-gfx950"
 
@@ -858,6 +872,27 @@ class HipBackend:
         self._jpeg_done[t] = torch.cuda.Event()
         self._jpeg_done[t].record(torch.cuda.current_stream(self.device))
         return out, out_offs, status, rounds
+
+    # ---- PNG encode (vf_png.hip)
+    def png_encode(self, frames):
+        """Encode a batch of frames of one size as PNG files on the device.  frames: device uint8 N x H x W x C (taken as
+        they are) or float32 N x C x H x W (through image.savePNG's truncating byte rule inside the filter kernel), C = 1
+        or 3, contiguous.  -> (buffer, offsets): file i is buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8
+        tensor of the upper bound's size, offsets a device int64[N + 1]; both are valid once the stream gets there."""
+        assert frames.dim() == 4 and frames.is_contiguous() and frames.device == self.device
+        if frames.dtype == torch.uint8:
+            kind, (n, H, W, Cc) = 1, frames.shape
+        else:
+            assert frames.dtype == torch.float32, "frames are uint8 N x H x W x C or float32 N x C x H x W"
+            kind, (n, Cc, H, W) = 0, frames.shape
+        ws_b, out_b = png_workspace_bytes(n, H, W, Cc)
+        ws = getattr(self, "_png_ws", None)
+        if ws is None or ws.numel() < ws_b:
+            self._png_ws = ws = torch.empty(max(ws_b, 1 << 20), dtype=torch.uint8, device=self.device)
+        out = torch.empty(out_b, dtype=torch.uint8, device=self.device)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        self._c("vf_png_encode", _ptr(frames), kind, n, H, W, Cc, _ptr(ws), ws.numel(), _ptr(out), out.numel(), _ptr(offsets))
+        return out, offsets
 
     def channel_copy(self, src, c_src, dst, c_dst, ncopy):
         """dst[:, c_dst:c_dst+ncopy] = src[:, c_src:c_src+ncopy] on NHWC tensors of equal B, H, W (nn.JoinTable(2))."""

@@ -1,0 +1,791 @@
+// vf_png.hip — batched PNG encoder: frames on the device in, whole PNG files out.
+//   k_png_filter    one block per row: the row's bytes (from float planar through image.savePNG's truncating byte rule, or from
+//                   interleaved bytes), the five PNG filters, libpng's minimum-sum-of-absolute-values choice, the filtered row.
+//   k_png_deflate   one block per PNG_CHUNK bytes of a frame's filtered stream: LZ77 matches from an LDS hash table (resolved by
+//                   position, so the result does not depend on which lane gets there first), a greedy parse, dynamic Huffman
+//                   codes, the bits, or a stored block if that is not smaller; the chunk's IDAT with its CRC-32, its Adler sums.
+//   k_png_frame_scan / k_png_offsets / k_png_pack   chunk and file offsets, the Adler-32 of every frame, the files back to back.
+// No window crosses a chunk, so chunks are independent and a file's bytes depend on its own frame only.
+#include "vf_common.h"
+
+namespace {
+
+constexpr int PNG_CHUNK = 8192;          // filtered bytes per deflate block / IDAT chunk (backend.PNG_CHUNK mirrors it)
+constexpr int PNG_SLOT = 8224;           // a chunk's IDAT in the workspace: 12 framing + 2 zlib header + 5 stored header + chunk + 4 Adler
+constexpr int PNG_MAX_SIDE = 16384;
+constexpr int HASH_BITS = 11;
+constexpr int MAX_MATCH = 258, MIN_MATCH = 3;
+constexpr unsigned CRC_POLY = 0xEDB88320u;
+constexpr int CRC_SEG = 36;              // bytes per thread of the block-wide CRC: 256 * 36 >= the longest IDAT type + data
+constexpr unsigned ADLER_MOD = 65521u;
+constexpr int DIST0 = 288;               // the distance alphabet's place in the frequency / length / code arrays
+
+struct PngArgs {
+  const void* src;
+  unsigned char* stream;   // [n][stream_len]: filter byte + filtered row, row after row
+  unsigned char* slots;    // [n][nchunks][PNG_SLOT]
+  unsigned* meta;          // [n][nchunks][4]: IDAT data bytes, Adler byte sum, Adler weighted sum, running CRC register
+  unsigned* chunk_off;     // [n][nchunks]: offset of the chunk's IDAT behind the file's IHDR
+  unsigned* adler;         // [n]
+  unsigned char* out;
+  int64_t* offsets;        // [n + 1]
+  int n, H, W, C, rb, nchunks;
+  long long stream_len;
+};
+
+// ------------------------------------------------------------------------------------------------------------- filter
+// image.savePNG on a float tensor: saturate to [0,1], times 255 in float32, then libpng's C cast, which truncates; NaN -> 0
+__device__ __forceinline__ int png_byte_of(float x) {
+  const float v = fminf(fmaxf(x, 0.f), 1.f);
+  return (int)(255.f * v);
+}
+
+template <int KIND>
+__device__ __forceinline__ int png_px(const PngArgs& a, long long f, int y, int i) {
+  if (KIND == 1) return ((const unsigned char*)a.src)[(f * a.H + y) * (long long)a.rb + i];
+  const int x = a.C == 3 ? i / 3 : i, c = a.C == 3 ? i - 3 * x : 0;
+  return png_byte_of(((const float*)a.src)[((f * a.C + c) * a.H + y) * (long long)a.W + x]);
+}
+
+__device__ __forceinline__ int png_paeth(int a, int b, int c) {
+  const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+  return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+}
+
+__device__ __forceinline__ int png_filtered(int t, int x, int a, int b, int c) {
+  switch (t) {
+    case 0: return x & 255;
+    case 1: return (x - a) & 255;
+    case 2: return (x - b) & 255;
+    case 3: return (x - ((a + b) >> 1)) & 255;
+    default: return (x - png_paeth(a, b, c)) & 255;
+  }
+}
+
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_png_filter(PngArgs a) {
+  __shared__ unsigned s_part[4][5];
+  __shared__ int s_best;
+  const int y = blockIdx.x, C = a.C, rb = a.rb;
+  const long long f = blockIdx.y;
+  unsigned s[5] = {0, 0, 0, 0, 0};
+  for (int i = threadIdx.x; i < rb; i += 256) {
+    const int x = png_px<KIND>(a, f, y, i), l = i >= C ? png_px<KIND>(a, f, y, i - C) : 0;
+    const int u = y > 0 ? png_px<KIND>(a, f, y - 1, i) : 0, ul = (y > 0 && i >= C) ? png_px<KIND>(a, f, y - 1, i - C) : 0;
+#pragma unroll
+    for (int t = 0; t < 5; ++t) {
+      const int v = png_filtered(t, x, l, u, ul);
+      s[t] += v < 128 ? v : 256 - v;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 5; ++t) {
+    const unsigned w = wave_sum(s[t]);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6][t] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int best = 0;
+    unsigned mn = 0xFFFFFFFFu;
+    for (int t = 0; t < 5; ++t) {                 // ties: the first of None, Sub, Up, Average, Paeth
+      const unsigned v = s_part[0][t] + s_part[1][t] + s_part[2][t] + s_part[3][t];
+      if (v < mn) { mn = v; best = t; }
+    }
+    s_best = best;
+  }
+  __syncthreads();
+  const int best = s_best;
+  unsigned char* dst = a.stream + f * a.stream_len + (long long)y * (rb + 1);
+  if (threadIdx.x == 0) dst[0] = (unsigned char)best;
+  for (int i = threadIdx.x; i < rb; i += 256) {
+    const int x = png_px<KIND>(a, f, y, i), l = i >= C ? png_px<KIND>(a, f, y, i - C) : 0;
+    const int u = y > 0 ? png_px<KIND>(a, f, y - 1, i) : 0, ul = (y > 0 && i >= C) ? png_px<KIND>(a, f, y - 1, i - C) : 0;
+    dst[1 + i] = (unsigned char)png_filtered(best, x, l, u, ul);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------ deflate
+__device__ __forceinline__ void len_code(int len, int& code, int& eb, int& ev) {   // RFC 1951 3.2.5
+  const int l = len - MIN_MATCH;
+  if (len == MAX_MATCH) { code = 285; eb = 0; ev = 0; }
+  else if (l < 8) { code = 257 + l; eb = 0; ev = 0; }
+  else { eb = (31 - __clz(l)) - 2; code = 261 + 4 * eb + ((l >> eb) & 3); ev = l & ((1 << eb) - 1); }
+}
+__device__ __forceinline__ void dist_code(int dist, int& code, int& eb, int& ev) {
+  const int d = dist - 1;
+  if (d < 4) { code = d; eb = 0; ev = 0; }
+  else { eb = (31 - __clz(d)) - 1; code = 2 * eb + 2 + ((d >> eb) & 1); ev = d & ((1 << eb) - 1); }
+}
+
+constexpr int MATCH_GAIN = 16;           // 1/16 bit: a match must save a bit against its literals
+__device__ __forceinline__ int match_cost(int len, int dist) {   // 1/16 bit
+  int c, eb1, eb2, ev;
+  len_code(len, c, eb1, ev);
+  dist_code(dist, c, eb2, ev);
+  return (8 + eb1 + 5 + eb2) * 16;
+}
+
+__device__ __forceinline__ unsigned crc_mulmod(unsigned a, unsigned b) {   // a * b mod the CRC-32 polynomial, reflected: bit 31 is x^0
+  unsigned p = 0;
+  for (int i = 0; i < 32; ++i) {
+    if (a & (0x80000000u >> i)) p ^= b;
+    b = (b & 1) ? (b >> 1) ^ CRC_POLY : b >> 1;
+  }
+  return p;
+}
+__device__ __forceinline__ unsigned crc_byte(unsigned c, unsigned byte) {
+  c ^= byte;
+  for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ CRC_POLY : c >> 1;
+  return c;
+}
+
+// Code lengths of a Huffman code over the m used symbols sorted[0..m) (ascending frequency, ties by symbol), at most maxbits long.
+// One thread.  The tree comes from the two-queue merge (leaves and internal nodes are both in non-decreasing weight order); depths
+// beyond maxbits are cut to maxbits and the Kraft sum is repaired by moving one code at a time from the longest shorter length
+// down, then the lengths go to the symbols by rank: the rarest get the longest.  lens[] must be zero on entry.  m >= 2.
+__device__ void huff_lengths(const unsigned* freq, const unsigned short* sorted, int m, int maxbits, unsigned char* lens, unsigned* w,
+                             unsigned short* par, unsigned char* depth) {
+  // nodes 0..m-1: leaves in sorted order; m..2m-2: internal, in creation order; w[] holds internal weights only
+  int li = 0, ii = 0, made = 0;
+  for (; made < m - 1; ++made) {
+    unsigned wsum = 0;
+    for (int k = 0; k < 2; ++k) {
+      const bool leaf = li < m && (ii >= made || freq[sorted[li]] <= w[ii]);
+      if (leaf) { wsum += freq[sorted[li]]; par[li++] = (unsigned short)(m + made); }
+      else { wsum += w[ii]; par[m + ii++] = (unsigned short)(m + made); }
+    }
+    w[made] = wsum;
+  }
+  unsigned cnt[16];
+  for (int i = 0; i < 16; ++i) cnt[i] = 0;
+  depth[m - 2] = 0;                                          // the root is internal node m - 2
+  for (int i = m - 3; i >= 0; --i) depth[i] = (unsigned char)min(depth[par[m + i] - m] + 1, 40);
+  for (int i = 0; i < m; ++i) cnt[min(depth[par[i] - m] + 1, maxbits)]++;
+  unsigned total = 0;
+  for (int l = 1; l <= maxbits; ++l) total += cnt[l] << (maxbits - l);
+  while (total > (1u << maxbits)) {
+    cnt[maxbits]--;
+    for (int l = maxbits - 1; l > 0; --l)
+      if (cnt[l]) { cnt[l]--; cnt[l + 1] += 2; break; }
+    total--;
+  }
+  int idx = 0;
+  for (int l = maxbits; l >= 1; --l)
+    for (unsigned k = 0; k < cnt[l]; ++k) lens[sorted[idx++]] = (unsigned char)l;
+}
+
+__device__ __forceinline__ unsigned bit_reverse(unsigned code, int len) { return __brev(code) >> (32 - len); }
+
+// the canonical code of symbol s in an alphabet of n lengths (RFC 1951 3.2.2), bit-reversed for the LSB-first stream
+__device__ __forceinline__ unsigned canon_code(const unsigned char* lens, int n, int s) {
+  const int len = lens[s];
+  if (!len) return 0;
+  unsigned code = 0;
+  for (int t = 0; t < n; ++t) {
+    const int lt = lens[t];
+    if (lt && lt < len) code += 1u << (len - lt);
+    else if (lt == len && t < s) code++;
+  }
+  return bit_reverse(code, len);
+}
+
+struct BitW {   // serial writer into a zeroed word buffer
+  unsigned* buf;
+  unsigned pos;
+  __device__ void put(unsigned v, int nbits) {
+    if (!nbits) return;
+    const unsigned w = pos >> 5, o = pos & 31;
+    buf[w] |= v << o;
+    if (o + nbits > 32) buf[w + 1] |= v >> (32 - o);
+    pos += nbits;
+  }
+};
+
+// The header of a dynamic block (RFC 1951 3.2.7), by one thread, into the zeroed bit buffer: BFINAL, BTYPE 10, HLIT, HDIST,
+// HCLEN, the code-length code (7 bits at most), the two length tables in 16 / 17 / 18 form.  lens: literal/length lengths at
+// 0, distance lengths at DIST0; seq: room for 316 entries, symbol | extra << 8.  -> the bits written.
+__device__ unsigned png_block_header(const unsigned char* lens, bool last, unsigned* buf, unsigned short* seq) {
+  int hlit = 286, hdist = 30;
+  while (hlit > 257 && !lens[hlit - 1]) --hlit;
+  while (hdist > 1 && !lens[DIST0 + hdist - 1]) --hdist;
+  const int total = hlit + hdist;
+  int ns = 0;
+  unsigned clf[19];
+  for (int i = 0; i < 19; ++i) clf[i] = 0;
+  for (int i = 0; i < total;) {
+    const int v = i < hlit ? lens[i] : lens[DIST0 + i - hlit];
+    int run = 1;
+    while (i + run < total && (i + run < hlit ? lens[i + run] : lens[DIST0 + i + run - hlit]) == v) ++run;
+    i += run;
+    if (v == 0) {
+      while (run >= 11) { const int r = min(run, 138); seq[ns++] = (unsigned short)(18 | ((r - 11) << 8)); clf[18]++; run -= r; }
+      if (run >= 3) { seq[ns++] = (unsigned short)(17 | ((run - 3) << 8)); clf[17]++; run = 0; }
+    } else {
+      seq[ns++] = (unsigned short)v; clf[v]++; --run;
+      while (run >= 3) { const int r = min(run, 6); seq[ns++] = (unsigned short)(16 | ((r - 3) << 8)); clf[16]++; run -= r; }
+    }
+    for (; run > 0; --run) { seq[ns++] = (unsigned short)v; clf[v]++; }
+  }
+  // the code-length code, 7 bits at most
+  unsigned short srt[19];
+  unsigned char cll[19];
+  int m = 0;
+  for (int i = 0; i < 19; ++i) {
+    cll[i] = 0;
+    if (!clf[i]) continue;
+    int j = m++;
+    for (; j > 0 && clf[srt[j - 1]] > clf[i]; --j) srt[j] = srt[j - 1];
+    srt[j] = (unsigned short)i;
+  }
+  if (m == 1) cll[srt[0]] = cll[srt[0] ? 0 : 1] = 1;   // a complete code needs two
+  else {
+    unsigned w[19];
+    unsigned short par[40];
+    unsigned char dep[19];
+    huff_lengths(clf, srt, m, 7, cll, w, par, dep);
+  }
+  const unsigned char order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+  int hclen = 19;
+  while (hclen > 4 && !cll[order[hclen - 1]]) --hclen;
+  BitW bw{buf, 0};
+  bw.put(last ? 1u : 0u, 1);
+  bw.put(2u, 2);
+  bw.put(hlit - 257, 5);
+  bw.put(hdist - 1, 5);
+  bw.put(hclen - 4, 4);
+  for (int i = 0; i < hclen; ++i) bw.put(cll[order[i]], 3);
+  for (int i = 0; i < ns; ++i) {
+    const int sym = seq[i] & 255, ex = seq[i] >> 8;
+    bw.put(canon_code(cll, 19, sym), cll[sym]);
+    if (sym == 16) bw.put(ex, 2);
+    else if (sym == 17) bw.put(ex, 3);
+    else if (sym == 18) bw.put(ex, 7);
+  }
+  return bw.pos;
+}
+
+struct DeflateLds {                        // all of k_png_deflate's LDS, in one place so that its size is checked
+  unsigned match[PNG_CHUNK];               // length | distance << 16 | token start << 31
+  unsigned tab[PNG_CHUNK / 4 + 4];         // hash table (position + 1), then tree scratch, then the bit buffer
+  unsigned freq[320];
+  unsigned crc[256];
+  unsigned red[8];
+  unsigned x[8];
+  unsigned bits[1];                        // header bits
+  int m[2];
+  unsigned short sorted[320];
+  unsigned short code[320];
+  unsigned short cost[256];                // a literal's price, 1/16 bit
+  unsigned short seq[320];                 // the two length tables in 16 / 17 / 18 form
+  unsigned char len[320];
+  unsigned char data[PNG_CHUNK + 8];
+};
+// 54308 B: three blocks fit a CU's 160 KiB with 916 B to spare.  Anything added here must keep that.
+static_assert(3 * sizeof(DeflateLds) <= 160 * 1024, "k_png_deflate: three blocks per CU no longer fit the LDS");
+
+__global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
+  __shared__ DeflateLds lds;
+  auto& s_data = lds.data;
+  auto& s_match = lds.match;
+  auto& s_tab = lds.tab;
+  auto& s_freq = lds.freq;
+  auto& s_sorted = lds.sorted;
+  auto& s_len = lds.len;
+  auto& s_code = lds.code;
+  auto& s_red = lds.red;
+  auto& s_crc = lds.crc;
+  auto& s_x = lds.x;
+  auto& s_m = lds.m;
+  auto& s_bits = lds.bits;
+  auto& s_cost = lds.cost;
+  auto& s_seq = lds.seq;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k = blockIdx.x;
+  const long long f = blockIdx.y;
+  const long long begin = (long long)k * PNG_CHUNK;
+  const int n = (int)min((long long)PNG_CHUNK, a.stream_len - begin);
+  const bool last = k == a.nchunks - 1;
+  const unsigned char* in = a.stream + f * a.stream_len + begin;
+
+  // ---- load, Adler partial sums, clear
+  unsigned ad_a = 0, ad_b = 0;
+  for (int p = tid; p < PNG_CHUNK + 8; p += 256) {
+    const unsigned d = p < n ? in[p] : 0;
+    s_data[p] = (unsigned char)d;
+    ad_a += d;
+    if (p < n) ad_b = (ad_b + (unsigned)(n - p) * d) % ADLER_MOD;
+  }
+  for (int i = tid; i < PNG_CHUNK / 4 + 4; i += 256) s_tab[i] = 0;
+  for (int i = tid; i < 320; i += 256) { s_freq[i] = 0; s_len[i] = 0; s_code[i] = 0; }
+  ad_a = wave_sum(ad_a);
+  ad_b = wave_sum(ad_b);
+  if (lane == 0) { s_red[wave] = ad_a; s_red[4 + wave] = ad_b; }
+  __syncthreads();
+  if (tid == 0) {
+    unsigned* mt = a.meta + (f * a.nchunks + k) * 4;
+    mt[1] = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) % ADLER_MOD;
+    mt[2] = (s_red[4] + s_red[5] + s_red[6] + s_red[7]) % ADLER_MOD;
+  }
+
+  // ---- what a byte costs as a literal, in 1/16 bit: log2(n / count) from the chunk's byte histogram (the leading bit and four
+  // mantissa bits of the ratio), at least one bit.  A match is worth taking only where it beats that: in photographic rows
+  // three-byte repeats at long distances abound and cost more than the literals they replace.
+  for (int p = tid; p < n; p += 256) atomicAdd(&s_freq[s_data[p]], 1u);
+  __syncthreads();
+  {
+    const unsigned fr = s_freq[tid];
+    unsigned c = 15 * 16;
+    if (fr) {
+      const unsigned r = ((unsigned)n << 8) / fr;
+      const int e = 31 - __clz((int)r);
+      c = min(max((unsigned)((e - 8) << 4) + ((r >> (e - 4)) & 15u), 16u), 15u * 16u);
+    }
+    s_cost[tid] = (unsigned short)c;
+  }
+  __syncthreads();
+  for (int i = tid; i < 320; i += 256) s_freq[i] = 0;
+
+  // ---- matches.  Positions go through the table 256 at a time: a position sees the latest earlier-batch position with its hash
+  // (atomicMax: by position, not by arrival), and its predecessor (runs).  Each is priced at 8 bits for the length symbol, 5 for
+  // the distance symbol and their extra bits; the one that saves more against the literals it covers wins, the nearer on a tie,
+  // and one that saves less than MATCH_GAIN is dropped.
+  for (int base = 0; base < n; base += 256) {
+    const int p = base + tid;
+    const bool h3 = p + 2 < n;
+    unsigned h = 0, cand = 0;
+    if (h3) {
+      h = ((s_data[p] | (s_data[p + 1] << 8) | (s_data[p + 2] << 16)) * 0x9E3779B1u) >> (32 - HASH_BITS);
+      cand = s_tab[h];
+    }
+    __syncthreads();
+    if (h3) atomicMax(&s_tab[h], (unsigned)(p + 1));
+    if (p < n) {
+      const int maxl = min(MAX_MATCH, n - p);
+      int l1 = 0, l2 = 0;
+      if (cand) {
+        const int q = (int)cand - 1;
+        while (l1 < maxl && s_data[q + l1] == s_data[p + l1]) ++l1;
+      }
+      if (p >= 1)
+        while (l2 < maxl && s_data[p - 1 + l2] == s_data[p + l2]) ++l2;
+      int lit1 = 0, lit2 = 0, acc = 0;
+      for (int i = 0; i < max(l1, l2); ++i) {
+        acc += s_cost[s_data[p + i]];
+        if (i + 1 == l1) lit1 = acc;
+        if (i + 1 == l2) lit2 = acc;
+      }
+      int bl = 0, bd = 0, bg = 0;
+      if (l1 >= MIN_MATCH) {
+        const int g = lit1 - match_cost(l1, p + 1 - (int)cand);
+        if (g >= MATCH_GAIN) { bg = g; bl = l1; bd = p + 1 - (int)cand; }
+      }
+      if (l2 >= MIN_MATCH) {
+        const int g = lit2 - match_cost(l2, 1);
+        if (g >= MATCH_GAIN && (!bl || g >= bg)) { bl = l2; bd = 1; }
+      }
+      s_match[p] = bl ? (unsigned)bl | ((unsigned)bd << 16) : 0u;
+    }
+    __syncthreads();
+  }
+
+  // ---- greedy parse by one wave: 64 positions at a time, up to and including the first match
+  if (wave == 0) {
+    int pos = 0;
+    while (pos < n) {
+      const int p = pos + lane;
+      const unsigned m = p < n ? s_match[p] : 0u;
+      const unsigned long long mask = __ballot(m != 0);
+      const int first = mask ? __ffsll((long long)mask) - 1 : 64;
+      if (p < n && lane <= first) s_match[p] = m | 0x80000000u;
+      if (first == 64) pos += 64;
+      else pos += first + (int)(__shfl(m, first) & 0x1FFu);
+    }
+  }
+  __syncthreads();
+
+  // ---- histograms
+  for (int p = tid; p < n; p += 256) {
+    const unsigned m = s_match[p];
+    if (m & 0x80000000u) {
+      const int len = m & 0x1FF;
+      if (len) {
+        int c, eb, ev;
+        len_code(len, c, eb, ev);
+        atomicAdd(&s_freq[c], 1u);
+        dist_code((m >> 16) & 0x7FFF, c, eb, ev);
+        atomicAdd(&s_freq[DIST0 + c], 1u);
+      } else {
+        atomicAdd(&s_freq[s_data[p]], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    s_freq[256] = 1;
+    int used = 0;
+    for (int i = 0; i < 30; ++i) used += s_freq[DIST0 + i] != 0;
+    for (int i = 0; i < 30 && used < 2; ++i)       // at least two distance codes, as zlib sends
+      if (!s_freq[DIST0 + i]) { s_freq[DIST0 + i] = 1; ++used; }
+  }
+  __syncthreads();
+
+  // ---- rank sort of the used symbols of both alphabets
+  for (int s = tid; s < 316; s += 256) {
+    const int lo = s < 286 ? 0 : DIST0, cnt = s < 286 ? 286 : 30, me = s < 286 ? s : s - 286;
+    const unsigned fr = s_freq[lo + me];
+    if (fr) {
+      int r = 0;
+      for (int t = 0; t < cnt; ++t) {
+        const unsigned ft = s_freq[lo + t];
+        r += ft && (ft < fr || (ft == fr && t < me));
+      }
+      s_sorted[lo + r] = (unsigned short)me;
+    }
+  }
+  if (tid == 64 || tid == 128) {
+    const int lo = tid == 64 ? 0 : DIST0, cnt = tid == 64 ? 286 : 30;
+    int m = 0;
+    for (int t = 0; t < cnt; ++t) m += s_freq[lo + t] != 0;
+    s_m[tid == 64 ? 0 : 1] = m;
+  }
+  __syncthreads();
+  if (tid == 0 || tid == 64) {
+    const int w = tid == 64;
+    unsigned* scratch = s_tab + w * 700;             // 288 weights, 288 words of parents, 72 of depths
+    huff_lengths(s_freq + (w ? DIST0 : 0), s_sorted + (w ? DIST0 : 0), s_m[w], 15, s_len + (w ? DIST0 : 0), scratch,
+                 (unsigned short*)(scratch + 288), (unsigned char*)(scratch + 288 + 144 + 144));
+  }
+  __syncthreads();
+  for (int i = tid; i < PNG_CHUNK / 4 + 4; i += 256) s_tab[i] = 0;
+  for (int s = tid; s < 316; s += 256) {
+    const int lo = s < 286 ? 0 : DIST0, cnt = s < 286 ? 286 : 30, me = s < 286 ? s : s - 286;
+    s_code[lo + me] = (unsigned short)canon_code(s_len + lo, cnt, me);
+  }
+  __syncthreads();
+
+  // ---- the block header
+  if (tid == 0) s_bits[0] = png_block_header(s_len, last, s_tab, s_seq);
+  __syncthreads();
+
+  // ---- token bits: each thread owns 32 consecutive positions
+  const int p0 = tid * (PNG_CHUNK / 256);
+  unsigned mybits = 0;
+  for (int p = p0; p < p0 + PNG_CHUNK / 256 && p < n; ++p) {
+    const unsigned m = s_match[p];
+    if (!(m & 0x80000000u)) continue;
+    const int len = m & 0x1FF;
+    if (len) {
+      int c, eb, ev;
+      len_code(len, c, eb, ev);
+      mybits += s_len[c] + eb;
+      dist_code((m >> 16) & 0x7FFF, c, eb, ev);
+      mybits += s_len[DIST0 + c] + eb;
+    } else {
+      mybits += s_len[s_data[p]];
+    }
+  }
+  unsigned inc = mybits;                               // inclusive scan over the block
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_up(inc, o);
+    if (lane >= o) inc += t;
+  }
+  if (lane == 63) s_red[wave] = inc;
+  __syncthreads();
+  unsigned wbase = 0;
+  for (int w = 0; w < wave; ++w) wbase += s_red[w];
+  const unsigned tok_bits = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+  const unsigned hdr_bits = s_bits[0];
+  const unsigned body_bits = hdr_bits + tok_bits + s_len[256] + (last ? 0u : 3u);   // + the empty stored block's header
+  const unsigned body_bytes = (body_bits + 7) >> 3;
+  const unsigned coded_bytes = body_bytes + (last ? 0u : 4u);
+  const bool coded = coded_bytes < (unsigned)n;        // not smaller than the raw bytes: stored
+  const unsigned zh = k == 0 ? 2u : 0u;
+  unsigned char* slot = a.slots + (f * a.nchunks + k) * (long long)PNG_SLOT;
+  unsigned char* dat = slot + 8 + zh;
+  unsigned dlen;
+  if (coded) {
+    unsigned bp = hdr_bits + wbase + inc - mybits;
+    for (int p = p0; p < p0 + PNG_CHUNK / 256 && p < n; ++p) {
+      const unsigned m = s_match[p];
+      if (!(m & 0x80000000u)) continue;
+      const int len = m & 0x1FF;
+      unsigned long long v;
+      int nb;
+      if (len) {
+        int c, eb, ev;
+        len_code(len, c, eb, ev);
+        v = s_code[c]; nb = s_len[c];
+        v |= (unsigned long long)ev << nb; nb += eb;
+        dist_code((m >> 16) & 0x7FFF, c, eb, ev);
+        v |= (unsigned long long)s_code[DIST0 + c] << nb; nb += s_len[DIST0 + c];
+        v |= (unsigned long long)ev << nb; nb += eb;
+      } else {
+        v = s_code[s_data[p]]; nb = s_len[s_data[p]];
+      }
+      const unsigned w = bp >> 5, o = bp & 31;
+      atomicOr(&s_tab[w], (unsigned)(v << o));
+      if (o + nb > 32) atomicOr(&s_tab[w + 1], (unsigned)(v >> (32 - o)));
+      if (o + nb > 64) atomicOr(&s_tab[w + 2], (unsigned)(v >> (64 - o)));
+      bp += nb;
+    }
+    if (tid == 255) {                                  // end of block
+      const unsigned e = hdr_bits + tok_bits, w = e >> 5, o = e & 31;
+      const unsigned v = s_code[256];
+      atomicOr(&s_tab[w], v << o);
+      if (o + s_len[256] > 32) atomicOr(&s_tab[w + 1], v >> (32 - o));
+    }
+    __syncthreads();
+    for (unsigned i = tid; i < body_bytes; i += 256) dat[i] = (unsigned char)(s_tab[i >> 2] >> (8 * (i & 3)));
+    if (!last && tid < 4) dat[body_bytes + tid] = tid < 2 ? 0x00 : 0xFF;       // LEN 0, NLEN ffff: ends on a byte boundary
+    dlen = zh + coded_bytes;
+  } else {
+    if (tid == 0) {
+      dat[0] = last ? 1 : 0;
+      dat[1] = (unsigned char)(n & 255); dat[2] = (unsigned char)(n >> 8);
+      dat[3] = (unsigned char)(~n & 255); dat[4] = (unsigned char)((~n >> 8) & 255);
+    }
+    for (int i = tid; i < n; i += 256) dat[5 + i] = s_data[i];
+    dlen = zh + 5 + (unsigned)n;
+  }
+  if (tid == 0) {
+    slot[4] = 'I'; slot[5] = 'D'; slot[6] = 'A'; slot[7] = 'T';
+    if (zh) { slot[8] = 0x78; slot[9] = 0x9C; }
+    const unsigned fl = dlen + (last ? 4u : 0u);       // the frame's last IDAT also carries the Adler-32 (k_png_pack)
+    slot[0] = (unsigned char)(fl >> 24); slot[1] = (unsigned char)(fl >> 16); slot[2] = (unsigned char)(fl >> 8); slot[3] = (unsigned char)fl;
+    unsigned x = 0x80000000u;                          // x^(8 * CRC_SEG) and its squares
+    for (int i = 0; i < 8 * CRC_SEG; ++i) x = (x & 1) ? (x >> 1) ^ CRC_POLY : x >> 1;
+    for (int l = 0; l < 8; ++l) { s_x[l] = x; x = crc_mulmod(x, x); }
+  }
+  __syncthreads();
+
+  // ---- CRC-32 of type + data.  The register of a message is linear in the message once its first four bytes are complemented
+  // (the all-ones preset), and leading zero bytes leave it at zero: the message is right-aligned in 256 segments of CRC_SEG bytes,
+  // each thread takes one, and a tree folds them, the left half times x^(8 * bytes to its right).
+  {
+    const int L = 4 + (int)dlen, shift = 256 * CRC_SEG - L;
+    unsigned c = 0;
+    for (int j = 0; j < CRC_SEG; ++j) {
+      const int r = tid * CRC_SEG + j - shift;
+      if (r >= 0) c = crc_byte(c, (unsigned)slot[4 + r] ^ (r < 4 ? 0xFFu : 0u));
+    }
+    s_crc[tid] = c;
+    __syncthreads();
+    for (int l = 0; l < 8; ++l) {
+      const int stride = 1 << l;
+      if ((tid & (2 * stride - 1)) == 0) s_crc[tid] = crc_mulmod(s_crc[tid], s_x[l]) ^ s_crc[tid + stride];
+      __syncthreads();
+    }
+    if (tid == 0) {
+      unsigned* mt = a.meta + (f * a.nchunks + k) * 4;
+      mt[0] = dlen;
+      mt[3] = s_crc[0];
+      if (!last) {
+        const unsigned crc = ~s_crc[0];
+        unsigned char* t = slot + 8 + dlen;
+        t[0] = (unsigned char)(crc >> 24); t[1] = (unsigned char)(crc >> 16); t[2] = (unsigned char)(crc >> 8); t[3] = (unsigned char)crc;
+      }
+    }
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------- pack
+__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned* s_w, unsigned& total) {   // 256 threads
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned inc = v;
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_up(inc, o);
+    if (lane >= o) inc += t;
+  }
+  __syncthreads();
+  if (lane == 63) s_w[wave] = inc;
+  __syncthreads();
+  unsigned base = 0;
+  for (int w = 0; w < wave; ++w) base += s_w[w];
+  total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  return base + inc - v;
+}
+
+constexpr int PNG_HEAD = 8 + 25, PNG_TAIL = 12;   // signature + IHDR; IEND
+
+// one block per frame: where each IDAT goes, the frame's Adler-32, the file's size (offsets[f + 1], summed by k_png_offsets)
+__global__ __launch_bounds__(256) void k_png_frame_scan(PngArgs a) {
+  __shared__ unsigned s_w[4];
+  const long long f = blockIdx.x;
+  const unsigned* meta = a.meta + f * a.nchunks * 4;
+  unsigned run = 0;
+  for (int base = 0; base < a.nchunks; base += 256) {
+    const int k = base + threadIdx.x;
+    const unsigned v = k < a.nchunks ? 12u + meta[4 * k] + (k == a.nchunks - 1 ? 4u : 0u) : 0u;
+    unsigned total;
+    const unsigned e = block_excl_scan(v, s_w, total);
+    if (k < a.nchunks) a.chunk_off[f * a.nchunks + k] = run + e;
+    run += total;
+  }
+  // The Adler-32: appending a piece (byte sum A, weighted sum B, length L) to sums (s1, s2) gives (s1 + A, s2 + L * s1 + B), and
+  // that is associative.  Each thread folds a run of consecutive chunks from (0, 0), thread 0 folds the 256 runs from (1, 0): at
+  // the largest frame (98 305 chunks) that is 385 + 256 dependent steps, not 98 305.
+  __shared__ unsigned s_a[256], s_b[256];
+  __shared__ unsigned long long s_l[256];
+  {
+    const int per = (a.nchunks + 255) / 256, k0 = min(threadIdx.x * per, (unsigned)a.nchunks), k1 = min(k0 + per, a.nchunks);
+    unsigned long long s1 = 0, s2 = 0, tot = 0;
+    for (int k = k0; k < k1; ++k) {
+      const unsigned long long len = (unsigned long long)min((long long)PNG_CHUNK, a.stream_len - (long long)k * PNG_CHUNK);
+      s2 = (s2 + len * s1 + meta[4 * k + 2]) % ADLER_MOD;
+      s1 = (s1 + meta[4 * k + 1]) % ADLER_MOD;
+      tot += len;
+    }
+    s_a[threadIdx.x] = (unsigned)s1; s_b[threadIdx.x] = (unsigned)s2; s_l[threadIdx.x] = tot;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long s1 = 1, s2 = 0;
+    for (int t = 0; t < 256; ++t) {
+      s2 = (s2 + (s_l[t] % ADLER_MOD) * s1 + s_b[t]) % ADLER_MOD;
+      s1 = (s1 + s_a[t]) % ADLER_MOD;
+    }
+    a.adler[f] = (unsigned)((s2 << 16) | s1);
+    a.offsets[f + 1] = (int64_t)PNG_HEAD + run + PNG_TAIL;
+  }
+}
+
+// one block: offsets[f] = sum of the sizes before file f (in: sizes at [f + 1])
+__global__ __launch_bounds__(256) void k_png_offsets(int64_t* offsets, int n) {
+  __shared__ unsigned long long s_v[256];
+  __shared__ unsigned long long s_run;
+  if (threadIdx.x == 0) { s_run = 0; offsets[0] = 0; }
+  __syncthreads();
+  for (int base = 0; base < n; base += 256) {
+    const int f = base + threadIdx.x;
+    s_v[threadIdx.x] = f < n ? (unsigned long long)offsets[f + 1] : 0ull;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+      const unsigned long long t = threadIdx.x >= o ? s_v[threadIdx.x - o] : 0ull;
+      __syncthreads();
+      s_v[threadIdx.x] += t;
+      __syncthreads();
+    }
+    if (f < n) offsets[f + 1] = (int64_t)(s_run + s_v[threadIdx.x]);
+    __syncthreads();
+    if (threadIdx.x == 0) s_run += s_v[255];
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ void put_be32(unsigned char* p, unsigned v) {
+  p[0] = (unsigned char)(v >> 24); p[1] = (unsigned char)(v >> 16); p[2] = (unsigned char)(v >> 8); p[3] = (unsigned char)v;
+}
+
+__global__ __launch_bounds__(256) void k_png_pack(PngArgs a) {
+  const int k = blockIdx.x;
+  const long long f = blockIdx.y;
+  const bool last = k == a.nchunks - 1;
+  const unsigned* mt = a.meta + (f * a.nchunks + k) * 4;
+  const unsigned dlen = mt[0];
+  const unsigned char* slot = a.slots + (f * a.nchunks + k) * (long long)PNG_SLOT;
+  unsigned char* file = a.out + a.offsets[f];
+  unsigned char* dst = file + PNG_HEAD + a.chunk_off[f * a.nchunks + k];
+  const unsigned ncopy = 8 + dlen + (last ? 0u : 4u);
+  for (unsigned i = threadIdx.x; i < ncopy; i += 256) dst[i] = slot[i];
+  if (threadIdx.x == 0 && last) {                      // the Adler-32 goes through the chunk's CRC register, then IEND
+    const unsigned ad = a.adler[f];
+    unsigned c = mt[3];
+    for (int i = 0; i < 4; ++i) c = crc_byte(c, (ad >> (24 - 8 * i)) & 255);
+    put_be32(dst + 8 + dlen, ad);
+    put_be32(dst + 12 + dlen, ~c);
+    unsigned char* e = dst + 16 + dlen;
+    const unsigned char iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xAE, 0x42, 0x60, 0x82};
+    for (int i = 0; i < 12; ++i) e[i] = iend[i];
+  }
+  if (threadIdx.x == 64 && k == 0) {
+    const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    for (int i = 0; i < 8; ++i) file[i] = sig[i];
+    unsigned char* h = file + 8;
+    put_be32(h, 13);
+    h[4] = 'I'; h[5] = 'H'; h[6] = 'D'; h[7] = 'R';
+    put_be32(h + 8, (unsigned)a.W);
+    put_be32(h + 12, (unsigned)a.H);
+    h[16] = 8; h[17] = a.C == 3 ? 2 : 0; h[18] = 0; h[19] = 0; h[20] = 0;
+    unsigned c = 0xFFFFFFFFu;
+    for (int i = 4; i < 21; ++i) c = crc_byte(c, h[i]);
+    put_be32(h + 21, ~c);
+  }
+}
+
+struct PngPlan {
+  long long rb, stream_len, nchunks;
+  size_t o_slots, o_meta, o_off, o_adler, ws_bytes, out_bytes;
+};
+
+int png_plan(const char* who, int n, int H, int W, int C, PngPlan* p) {
+  VF_REQUIRE(C == 1 || C == 3, "%s: %d channels (a PNG frame here is grey, 1 channel, or RGB, 3)", who, C);
+  VF_REQUIRE(H >= 1 && W >= 1 && H <= PNG_MAX_SIDE && W <= PNG_MAX_SIDE, "%s: a %dx%d frame (sides are 1 to %d)", who, H, W, PNG_MAX_SIDE);
+  VF_REQUIRE(n >= 1 && n <= 65535, "%s: a batch of %d frames (1 to 65535)", who, n);
+  p->rb = (long long)W * C;
+  p->stream_len = (long long)H * (p->rb + 1);
+  p->nchunks = vf_cdiv(p->stream_len, PNG_CHUNK);
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t chunks = (size_t)n * p->nchunks;
+  p->o_slots = up((size_t)n * p->stream_len);
+  p->o_meta = p->o_slots + up(chunks * PNG_SLOT);
+  p->o_off = p->o_meta + up(chunks * 16);
+  p->o_adler = p->o_off + up(chunks * 4);
+  p->ws_bytes = p->o_adler + up((size_t)n * 4);
+  // every chunk stored: 5 bytes of block header and 12 of IDAT framing each; zlib header and Adler-32; signature, IHDR, IEND
+  p->out_bytes = (size_t)n * ((size_t)p->stream_len + (size_t)p->nchunks * 17 + 6 + PNG_HEAD + PNG_TAIL);
+  return 0;
+}
+
+}  // namespace
+
+VF_API int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, size_t* out_bytes) {
+  PngPlan p;
+  if (int e = png_plan("vf_png_workspace_bytes", n, H, W, C, &p)) return e;
+  if (ws_bytes) *ws_bytes = p.ws_bytes;
+  if (out_bytes) *out_bytes = p.out_bytes;
+  return 0;
+}
+
+VF_API int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, void* ws, size_t ws_bytes,
+                         unsigned char* out, size_t out_cap, int64_t* offsets) {
+  PngPlan p;
+  if (int e = png_plan("vf_png_encode", n, H, W, C, &p)) return e;
+  VF_REQUIRE(kind == 0 || kind == 1, "vf_png_encode: kind %d is not 0 (float N x C x H x W) or 1 (uint8 N x H x W x C)", kind);
+  VF_REQUIRE(ws_bytes >= p.ws_bytes, "vf_png_encode: the workspace holds %zu bytes, %d frames of %dx%dx%d need %zu", ws_bytes, n, H, W, C,
+             p.ws_bytes);
+  VF_REQUIRE(out_cap >= p.out_bytes, "vf_png_encode: the output holds %zu bytes, %d frames of %dx%dx%d may take %zu", out_cap, n, H, W, C,
+             p.out_bytes);
+  PngArgs a;
+  a.src = src;
+  a.stream = (unsigned char*)ws;
+  a.slots = (unsigned char*)ws + p.o_slots;
+  a.meta = (unsigned*)((char*)ws + p.o_meta);
+  a.chunk_off = (unsigned*)((char*)ws + p.o_off);
+  a.adler = (unsigned*)((char*)ws + p.o_adler);
+  a.out = out;
+  a.offsets = offsets;
+  a.n = n; a.H = H; a.W = W; a.C = C; a.rb = (int)p.rb; a.nchunks = (int)p.nchunks;
+  a.stream_len = p.stream_len;
+  const double px = (double)n * H * W * C, stream = (double)n * p.stream_len;
+  if (kind == 0) VF_LAUNCH_TIMED(ctx, "png_filter", 0.0, 8.0 * px + stream, k_png_filter<0>, dim3(H, n), dim3(256), a);
+  else VF_LAUNCH_TIMED(ctx, "png_filter", 0.0, 2.0 * px + stream, k_png_filter<1>, dim3(H, n), dim3(256), a);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "png_deflate", 0.0, 2.0 * stream, k_png_deflate, dim3((unsigned)p.nchunks, n), dim3(256), a);
+  VF_LAUNCH_CHECK();
+  {
+    VfProf prof(ctx, "png_pack", 0.0, 2.0 * stream);
+    hipLaunchKernelGGL(k_png_frame_scan, dim3(n), dim3(256), 0, ctx->stream, a);
+    VF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_png_offsets, dim3(1), dim3(256), 0, ctx->stream, offsets, n);
+    VF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_png_pack, dim3((unsigned)p.nchunks, n), dim3(256), 0, ctx->stream, a);
+    VF_LAUNCH_CHECK();
+  }
+  return 0;
+}

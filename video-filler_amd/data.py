@@ -105,6 +105,25 @@ def decode_jpeg(items, channels=3, stack=False, fallback=None, subseq_bytes=256)
     return torch.stack(out)
 
 
+# ------------------------------------------------------------------------------------------------- PNG
+def encode_png(frames):
+    """image.save of a batch of frames as PNG, encoded on the device in one call (vf_png_encode): a list of `bytes`, one
+    whole PNG file per frame.  frames: uint8 N x H x W x C (stored as they are) or float N x C x H x W (image.savePNG's
+    rule: saturated to [0,1], times 255 in float32, truncated); C = 1 (grey) or 3 (RGB); host or device.  Decoding a
+    file gives exactly those bytes; the file bytes depend on the frame alone and are the same on every run.  One
+    device-to-host copy brings the batch back."""
+    B = get_backend()
+    t = torch.as_tensor(frames)
+    assert t.dim() == 4, "encode_png takes a batch: uint8 N x H x W x C or float N x C x H x W"
+    if t.dtype != torch.uint8:
+        assert t.is_floating_point(), "frames are uint8 or float"
+        t = t.float()
+    buf, offsets = B.png_encode(B.from_host(t).contiguous())
+    offs = offsets.cpu().tolist()                     # synchronises; the files end at offs[-1]
+    host = buf[:offs[-1]].cpu().numpy().tobytes()
+    return [host[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
+
+
 # ---------------------------------------------------------------------------------------------- image.scale (DESIGN 5.1)
 def load_size(H, W, loadSize, scalef=None):
     """(height, width) that loadImage / loadContImages (data/donkey_folder.lua:40-62, datavid/donkey_folder.lua:84-102)

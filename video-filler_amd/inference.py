@@ -121,3 +121,34 @@ class WholeImageInpainter:
         for t in (outImages, inpaint, fullv):         # :222-224
             B.scale_shift(t, 0.5, 0.5)
         return outImages, inpaint, fullv.view(predLen, nc, H, W)
+
+
+def save_frames(dirname, outImages=None, inpaintImages=None, fullImages=None, **named):
+    """test_vid_wholeim.lua:226-242 (and test_more_complex.lua:200-214): `image.save` of every frame of the three results
+    of WholeImageInpainter as dirname/pred_%d.png, inpaint_%d.png and orig_%d.png, numbered from 1.  The directory is
+    created; all 3 * predLen frames are encoded on the device in ONE call (data.encode_png) and the host only writes
+    the files.  Tensors are predLen x nc x H x W in [0,1] (image.savePNG's truncating byte rule applies), or uint8
+    predLen x H x W x nc.  Other prefixes go by keyword: save_frames(dirname, pred=out_pred) is test_vid.lua:138's
+    pred_i.png.  Returns the paths, in the order pred, inpaint, orig (then the keywords'), frames innermost."""
+    import os
+    from .data import encode_png
+    groups = [(p, t) for p, t in (("pred", outImages), ("inpaint", inpaintImages), ("orig", fullImages)) if t is not None]
+    groups += list(named.items())
+    assert groups, "save_frames: nothing to save"
+    prefixes = [p for p, _ in groups]
+    assert len(set(prefixes)) == len(prefixes), "save_frames: prefix given twice (%s); one would overwrite the other" % ", ".join(prefixes)
+    B = get_backend()
+    ts = [B.from_host(torch.as_tensor(t)) for _, t in groups]
+    assert all(t.dim() == 4 for t in ts) and len({(t.dtype, tuple(t.shape[1:])) for t in ts}) == 1, \
+        "save_frames: the tensors of one call share one type and one frame size"
+    os.makedirs(dirname, exist_ok=True)
+    files = encode_png(torch.cat(ts, 0))
+    paths, k = [], 0
+    for (prefix, _), t in zip(groups, ts):
+        for i in range(t.shape[0]):
+            path = os.path.join(dirname, "%s_%d.png" % (prefix, i + 1))
+            with open(path, "wb") as fh:
+                fh.write(files[k])
+            k += 1
+            paths.append(path)
+    return paths
