@@ -457,6 +457,35 @@ int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, size_t*
 int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, void* ws, size_t ws_bytes,
                   unsigned char* out, size_t out_cap, int64_t* offsets);
 
+/* ---- contact sheets of the inference scripts (vf_display.hip) -----------------------------------------
+ * image.toDisplayTensor(input, padding, nrow, scaleeach, min, max, symmetric, saturate) of test.lua:129, demo.lua:96 and
+ * test_vid.lua:149 for the one input form they use: a packed float tensor N x C x h x w, C = 1 or 3 (src_layout 0:
+ * planar; 1: NHWC, N x h x w x C).  grid: float planar C x (h+padding)*ymaps x (w+padding)*xmaps, xmaps = min(nrow, N),
+ * ymaps = ceil(N / xmaps); image k (row-major, 0-based) sits in cell (k / xmaps, k % xmaps) at offset padding/2; the
+ * padding and the cells past N hold the pack's maximum; then image.minmax runs over the grid — or, with scaleeach, over
+ * every image before the layout (the fill is then the maximum of the scaled pack).  minmax: with neither bound given
+ * saturate is dropped; min absent: -max(|tmin|, |tmax|) if symmetric, else tmin; t += (float)(-min) unless min == 0;
+ * the divisor is (float)(2 max(|tmin|, |tmax|)) (max absent, symmetric), the shifted tensor's maximum (max absent), or
+ * (float)((double)max - (double)min); t /= divisor unless it is 0 (IEEE float32 division); clamp to [0,1] if saturate.
+ * has_min / has_max say whether min / max are given (Lua's nil otherwise).  Bit-identical to tests/display_ref.py and the
+ * same on every run; inputs must be finite.  Odd or negative padding, C outside {1, 3} and grids of 2^31 elements or more
+ * than 65535 cells are errors naming the argument or the shape, before anything is launched.  Two launches; the first
+ * (min / max partials into the context workspace) is skipped when the extremes are not needed: both bounds given, no
+ * scaleeach, and no padding or empty cell to fill.
+ * vf_display_workspace_bytes (host only, no GPU): the bytes of the context workspace the call uses. */
+int vf_display_workspace_bytes(int N, int C, int h, int w, int padding, int nrow, int scaleeach, int has_min, int has_max,
+                               size_t* ws_bytes);
+int vf_display_tensor(vf_ctx* ctx, const float* packed, int src_layout, float* grid, int N, int C, int h, int w, int padding,
+                      int nrow, int scaleeach, int has_min, double min, int has_max, double max, int symmetric, int saturate);
+/* test.lua:98-128 (= demo.lua:73-95) in one pass.  ctx_nhwc: the generator input B x fs x fs x C in [-1,1], hole painted
+ * (vf_center_prepare); pred_nhwc: the prediction B x fs/2 x fs/2 x C.  pretty (planar 2B x C x fs x fs, [0,1]): row 2i is
+ * the input mapped by add(1):mul(0.5) with the hole [fs/4+ov, 3fs/4-ov)^2 set to exactly 1 (:122-124), row 2i+1 the context
+ * with pred[ov : fs/2-ov]^2 copied over the same hole (:98) and then mapped.  pasted (planar B x C x fs x fs; or NULL)
+ * receives row 2i+1 alone (image_ctx of :102), pred_mapped (planar B x C x fs/2 x fs/2; or NULL) the whole prediction
+ * mapped (:103).  fs % 4 != 0 or fs/2 - 2*overlapPred <= 0 is an error before anything is launched. */
+int vf_center_finish(vf_ctx* ctx, const float* ctx_nhwc, const float* pred_nhwc, float* pretty, float* pasted,
+                     float* pred_mapped, int B, int C, int fs, int overlapPred);
+
 /* ---- option branches of train.lua: noiseGen (:109-124, 319-327) and conditionAdv (:158-180) -----------------------
  * nn.JoinTable(2) over NHWC tensors: dst[p][c_dst + c] = src[p][c_src + c] for c < Ccopy, p < npix (forward: one call
  * per table element into the joined tensor; updateGradInput: one call per element out of the joined gradient).

@@ -894,6 +894,36 @@ class HipBackend:
         self._c("vf_png_encode", _ptr(frames), kind, n, H, W, Cc, _ptr(ws), ws.numel(), _ptr(out), out.numel(), _ptr(offsets))
         return out, offsets
 
+    # ---- contact sheets (vf_display.hip)
+    def display_tensor(self, packed, padding=0, nrow=6, scaleeach=False, min=None, max=None, symmetric=False, saturate=True):
+        """image.toDisplayTensor of a packed device float32 N x C x h x w tensor, C = 1 or 3, dense planar or dense
+        channels-last (read in place).  -> the float planar grid C x (h+padding)*ymaps x (w+padding)*xmaps."""
+        assert packed.dim() == 4 and packed.dtype == torch.float32 and packed.device == self.device
+        N, Cc, h, w = packed.shape
+        nhwc = not packed.is_contiguous()
+        assert not nhwc or is_nhwc(packed), "the pack is dense N x C x h x w, planar or channels-last"
+        args = (N, Cc, h, w, int(padding), int(nrow), int(bool(scaleeach)), int(min is not None), int(max is not None))
+        ws_b = C.c_size_t()
+        _lib.check(self.lib.vf_display_workspace_bytes(*args, C.byref(ws_b)))
+        assert ws_b.value <= self.workspace.numel(), "workspace too small for the (min, max) partials"
+        xmaps = int(nrow) if int(nrow) < N else N
+        ymaps = -(-N // xmaps)
+        grid = self.empty(Cc, (h + int(padding)) * ymaps, (w + int(padding)) * xmaps)
+        self._c("vf_display_tensor", _ptr(packed), int(nhwc), _ptr(grid), N, Cc, h, w, int(padding), int(nrow), int(bool(scaleeach)),
+                int(min is not None), float(min or 0.0), int(max is not None), float(max or 0.0), int(bool(symmetric)),
+                int(bool(saturate)))
+        return grid
+
+    def center_finish(self, ctx, pred, overlapPred, pretty, pasted=None, pred_mapped=None):
+        """test.lua:98-128.  ctx (B x C x fs x fs) and pred (B x C x fs/2 x fs/2): channels-last; pretty (2B x C x fs x fs),
+        pasted (B x C x fs x fs; optional), pred_mapped (B x C x fs/2 x fs/2; optional): contiguous planar."""
+        Bn, Cc, fs, _ = ctx.shape
+        assert is_nhwc(ctx) and is_nhwc(pred) and ctx.dtype == pred.dtype == torch.float32
+        assert tuple(ctx.shape) == (Bn, Cc, fs, fs) and tuple(pred.shape) == (Bn, Cc, fs // 2, fs // 2)
+        for t, shape in ((pretty, (2 * Bn, Cc, fs, fs)), (pasted, (Bn, Cc, fs, fs)), (pred_mapped, (Bn, Cc, fs // 2, fs // 2))):
+            assert t is None or (tuple(t.shape) == shape and t.is_contiguous() and t.dtype == torch.float32)
+        self._c("vf_center_finish", _ptr(ctx), _ptr(pred), _ptr(pretty), _ptr(pasted), _ptr(pred_mapped), Bn, Cc, fs, int(overlapPred))
+
     def channel_copy(self, src, c_src, dst, c_dst, ncopy):
         """dst[:, c_dst:c_dst+ncopy] = src[:, c_src:c_src+ncopy] on NHWC tensors of equal B, H, W (nn.JoinTable(2))."""
         Bn, Cs, H, W = src.shape

@@ -1,4 +1,5 @@
-"""Inference drivers: test_vid.lua (one forward of the clip) and test_vid_wholeim.lua (whole frames, tile loop).
+"""Inference drivers: test_vid.lua (one forward of the clip), test_vid_wholeim.lua (whole frames, tile loop), and
+test.lua / demo.lua (centre inpainting of the train.lua nets) with the contact sheets the scripts save.
 
 The generator runs in evaluate() mode (BatchNorm uses its running statistics), so tiles are independent and the
 whole-image loop — one net:forward per 128x128 tile in the reference (test_vid_wholeim.lua:159-205) — becomes ONE
@@ -9,7 +10,8 @@ import math
 
 import torch
 
-from .backend import get_backend, nhwc_empty
+from . import data
+from .backend import get_backend, is_nhwc, nhwc_empty, to_nhwc
 
 
 def predict_clip(net, input_image):
@@ -152,3 +154,91 @@ def save_frames(dirname, outImages=None, inpaintImages=None, fullImages=None, **
             k += 1
             paths.append(path)
     return paths
+
+
+# --------------------------------------------------------------------------- test.lua / demo.lua and the sheets
+def _check_display_args(x, padding, nrow):
+    """toDisplayTensor's argument checks, on the host and before any backend exists: -> the tensor."""
+    if isinstance(x, (list, tuple, dict)):
+        raise ValueError("display_tensor: a table of %d images; only a packed N x C x h x w tensor is laid out" % len(x))
+    t = torch.as_tensor(x)
+    if t.dim() != 4 or t.shape[1] not in (1, 3) or t.numel() == 0:
+        raise ValueError("display_tensor: a tensor of shape %s; only a packed N x C x h x w tensor with C = 1 or 3 is laid out "
+                         "(2-D images and K x h x w channel grids are not)" % (tuple(t.shape),))
+    if int(padding) != padding or padding < 0 or padding % 2:
+        raise ValueError("display_tensor: padding=%r must be an even integer >= 0 (images sit at padding/2)" % (padding,))
+    if int(nrow) != nrow or nrow < 1:
+        raise ValueError("display_tensor: nrow=%r must be an integer >= 1" % (nrow,))
+    return t
+
+
+def display_tensor(x, padding=0, nrow=6, scaleeach=False, min=None, max=None, symmetric=False, saturate=True):
+    """image.toDisplayTensor(x, padding, nrow, scaleeach, min, max, symmetric, saturate) on the device, for the input form
+    the scripts use: a packed float tensor N x C x h x w with C = 1 or 3, host or device; a channels-last tensor is read
+    where it lies.  Returns the device grid C x (h+padding)*ymaps x (w+padding)*xmaps, xmaps = min(nrow, N), normalised
+    by image.minmax (whole grid, or every image first with scaleeach); DESIGN.md 5.4 has the rule, tests/display_ref.py
+    pins it and the kernels equal it bit for bit.  Inputs must be finite: what NaN or Inf do is unspecified.  Tables,
+    2-D inputs, K x h x w channel grids, C outside {1, 3} and odd or negative padding raise ValueError."""
+    t = _check_display_args(x, padding, nrow)
+    B = get_backend()
+    t = B.from_host(t).float()
+    if not (t.is_contiguous() or is_nhwc(t)):
+        t = t.contiguous()
+    return B.display_tensor(t, int(padding), int(nrow), scaleeach, min, max, symmetric, saturate)
+
+
+def predict_center(net, image_ctx, overlapPred=0, noise=None, fill=data.CENTER_FILL):
+    """test.lua:39,79-104 (= demo.lua:31,59-79): net:evaluate(); cut the centre out of the loader's batch (image_ctx:
+    B x 3 x fs x fs in [-1,1], host or device) and paint the hole with the mean colour (data.center_prepare); pred =
+    net:forward(input), or net:forward({input, noise}) for a noiseGen net (noise: B x nz x 1 x 1); paste pred into the
+    hole, map everything by add(1):mul(0.5) and build the script's pretty_output — one kernel (vf_center_finish).
+    Returns (pretty_output 2B x 3 x fs x fs, image_ctx B x 3 x fs x fs, pred_center and real_center B x 3 x fs/2 x fs/2),
+    all in [0,1] on the device; pretty_output's rows 2i / 2i+1 are the input with a white hole / the context with the
+    prediction pasted in."""
+    B = get_backend()
+    net.evaluate()
+    x = torch.as_tensor(image_ctx)
+    assert x.dim() == 4 and x.shape[1] == 3, "test.lua paints channels 1-3 by name (:82-84, :122-124): nc = 3, got %s" % (tuple(x.shape),)
+    ctx, real_center = data.center_prepare(x, overlapPred, fill)
+    pred = net.forward(ctx if noise is None else [ctx, B.from_host(torch.as_tensor(noise)).float()])
+    nB, nc, fs, _ = ctx.shape
+    pretty, pasted, pred_center = B.empty(2 * nB, nc, fs, fs), B.empty(nB, nc, fs, fs), B.empty(nB, nc, fs // 2, fs // 2)
+    B.center_finish(ctx, to_nhwc(pred), overlapPred, pretty, pasted, pred_center)
+    # add(1):mul(0.5) and scale_shift's x * 0.5 + 0.5 give the same bits: halving is exact, so either form rounds once, the sum
+    # x + 1 at its own binade — no second mapping kernel for the one tensor that only needs the map
+    B.scale_shift(real_center, 0.5, 0.5)
+    return pretty, pasted, pred_center, real_center
+
+
+def load_demo_images(images, inputSize=128):
+    """demo.lua:49-55: decoded frames (uint8 N x H x W x 3, or float N x 3 x H x W in [0,1]; host or device) ->
+    image.scale to inputSize x inputSize -> mul(2):add(-1): the N x 3 x inputSize x inputSize batch predict_center takes."""
+    B = get_backend()
+    t = torch.as_tensor(images)
+    hwc = t.dtype == torch.uint8
+    src, N, nc, H, W = data._frames(t, hwc)
+    out = B.empty(N, nc, int(inputSize), int(inputSize))
+    B.image_scale(src, hwc, out)
+    B.scale_shift(out, 2.0, -1.0)
+    return out
+
+
+def save_sheet(path, x, **display_args):
+    """image.save(path, image.toDisplayTensor(x, ...)) (test.lua:129, demo.lua:96): display_tensor, data.encode_png of the
+    one grid (image.savePNG's byte rule is applied inside the encoder; no byte copy of the sheet is made), then the file
+    is written.  Returns path."""
+    grid = display_tensor(x, **display_args)
+    (png,) = data.encode_png(grid.unsqueeze(0))
+    with open(path, "wb") as fh:
+        fh.write(png)
+    return path
+
+
+def save_clip_sheet(path, input_image, pred_image):
+    """test_vid.lua:131-137,149: pretty_output[2i-1] = input_image[i], pretty_output[2i] = pred_image[i] (predict_clip's two
+    results, predLen x nc x fs x fs in [0,1]), saved as toDisplayTensor(pretty_output, 0, 10)."""
+    B = get_backend()
+    a, b = B.from_host(torch.as_tensor(input_image)).float(), B.from_host(torch.as_tensor(pred_image)).float()
+    assert a.dim() == 4 and a.shape == b.shape, "input_image and pred_image are predLen x nc x fs x fs"
+    pretty = torch.stack([a, b], 1).reshape(2 * a.shape[0], *a.shape[1:])
+    return save_sheet(path, pretty, padding=0, nrow=10)

@@ -144,6 +144,9 @@ int vf_crop_stats(vf_ctx*, const float* clip, const unsigned char* mask, int C, 
 int vf_patch_array_prepare(vf_ctx*, const void* src, int src_layout, const unsigned char* mask, float* masked, float* full, float* maskout, double* sum, int H, int W, int height, int width, int fs, int arr_h, int arr_w, int crop_w, int crop_h, int flip, float mask_value);
 int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, size_t* out_bytes);
 int vf_png_encode(vf_ctx*, const void* src, int kind, int n, int H, int W, int C, void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
+int vf_display_workspace_bytes(int N, int C, int h, int w, int padding, int nrow, int scaleeach, int has_min, int has_max, size_t* ws_bytes);
+int vf_display_tensor(vf_ctx*, const float* packed, int src_layout, float* grid, int N, int C, int h, int w, int padding, int nrow, int scaleeach, int has_min, double min, int has_max, double max, int symmetric, int saturate);
+int vf_center_finish(vf_ctx*, const float* ctx_nhwc, const float* pred_nhwc, float* pretty, float* pasted, float* pred_mapped, int B, int C, int fs, int overlapPred);
 int vf_channel_copy(vf_ctx*, const float* src, int Csrc, int c_src, float* dst, int Cdst, int c_dst, int Ccopy, int64_t npix);
 int vf_noise_fill(vf_ctx*, float* out, int64_t n, uint64_t seed, const int32_t* counter_dev, uint64_t counter, int normal);
 ]]
