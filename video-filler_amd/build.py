@@ -1,4 +1,5 @@
 """Build the gfx950 HIP library in-tree: video-filler_amd/lib/libvf_hip.so (hipcc cross-compiles without a GPU)."""
+import glob
 import os
 import subprocess
 import sys
@@ -26,7 +27,7 @@ def build(force=False, verbose=False):
     csrc = os.path.join(HERE, "csrc")
     objdir = os.path.join(HERE, "lib", "obj")
     os.makedirs(objdir, exist_ok=True)
-    hdrs = [os.path.join(csrc, "vf_common.h"), os.path.join(HERE, "..", "include", "vf_hip.h")]
+    hdrs = glob.glob(os.path.join(csrc, "*.h")) + [os.path.join(HERE, "..", "include", "vf_hip.h")]
     hdr_m = max(os.path.getmtime(h) for h in hdrs)
     objs, rebuilt = [], False
     procs = []

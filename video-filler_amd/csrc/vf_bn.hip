@@ -13,43 +13,20 @@
 // row segments are latency-bound.)
 #include <algorithm>
 
-#include "vf_common.h"
+#include "vf_device.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-// Exact three-way split of four fp32 values into bf16 planes (hi + mid + lo == x bit for bit; the arithmetic of
-// vf_pgemm.hip's pg_split4): the BatchNorm apply / backward passes write the planes of their output beside it, so the
-// convolution that consumes it (vf_pconv_*) finds its operand already split.  plane q of element i: planes[q * pstride + i].
-// npl = 1 (the bf16-operand mode): ONE plane, rounded to nearest-even — the rounding vf_conv.hip's BF = 1 kernels apply inside
-// the GEMM, done once by the producer (vf_pgemm.hip pg_rne16).
-__device__ __forceinline__ unsigned bn_rne16(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
+// The BatchNorm apply / backward passes write the bf16 planes of their output beside it, so the convolution that consumes it
+// (vf_pconv_*) finds its operand already split.  plane q of element i: planes[q * pstride + i]; npl = 3: the exact split
+// (vf_split3), npl = 1 (the bf16-operand mode): ONE plane, rounded to nearest-even (vf_round4).
 __device__ __forceinline__ void bn_store_planes(unsigned short* __restrict__ planes, int64_t pstride, int64_t i, f32x4 v, int npl) {
   if (npl == 1) {
-    u32x2 o;
-    o[0] = bn_rne16(v[0]) | (bn_rne16(v[1]) << 16);
-    o[1] = bn_rne16(v[2]) | (bn_rne16(v[3]) << 16);
-    *(u32x2*)(planes + i) = o;
+    *(u32x2*)(planes + i) = vf_round4(v);
     return;
   }
-  float r0 = v[0], r1 = v[1], r2 = v[2], r3 = v[3];
+  u32x2 o[3];
+  vf_split3(v, o);
 #pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const unsigned u0 = __float_as_uint(r0), u1 = __float_as_uint(r1), u2 = __float_as_uint(r2), u3 = __float_as_uint(r3);
-    u32x2 o;
-    o[0] = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
-    o[1] = __builtin_amdgcn_perm(u3, u2, 0x07060302u);
-    *(u32x2*)(planes + q * pstride + i) = o;
-    if (q < 2) {
-      r0 -= __uint_as_float(u0 & 0xffff0000u);
-      r1 -= __uint_as_float(u1 & 0xffff0000u);
-      r2 -= __uint_as_float(u2 & 0xffff0000u);
-      r3 -= __uint_as_float(u3 & 0xffff0000u);
-    }
-  }
+  for (int q = 0; q < 3; ++q) *(u32x2*)(planes + q * pstride + i) = o[q];
 }
 
 struct BnGeom {

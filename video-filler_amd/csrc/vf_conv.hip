@@ -35,25 +35,7 @@
 #include <vector>
 #include <cstdlib>
 
-#include "vf_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-// Buffer loads with hardware range checking: an offset past num_records returns 0, so padding taps, ragged
-// tile edges and split-K tails need neither a branch nor a select — the loads stay in flight across the MFMAs.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t vf_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 vf_bload4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
-}
-__device__ __forceinline__ float vf_bload1(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
-}
+#include "vf_device.h"
 
 // bf16 MFMA operand (32 rows x 16 k, 8 consecutive k per lane) out of a K-MAJOR bf16 tile [k][LD] in LDS, with gfx950's
 // transposing read: per 16-lane group ds_read_b64_tr_b16 takes a 4(k) x 16(column) block and hands lane i column i's four
@@ -68,40 +50,6 @@ __device__ __forceinline__ bf16x8 vf_tr_frag(const __bf16* tile, int col0, int k
   const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)a);
   const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(a + 4 * LD));
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// Exact three-way split of four fp32 values into bf16 planes by TRUNCATION (mode 3): plane q holds the top 16 bits of the
-// running residual, the residual loses exactly those bits (v - float(top16(v)) is exact), and after two steps at most 8
-// significant bits are left, so hi + mid + lo == v bit for bit.  No conversion instruction is needed: a v_perm_b32
-// packs the top halves of two residuals into one bf16x2 word (6 perms + 8 ands + 8 subs per four elements; the
-// round-to-nearest form through v_cvt_pk_bf16_f32 cost 30).
-struct VfPlanes3 { uint2 p[3]; };
-__device__ __forceinline__ VfPlanes3 vf_split3(f32x4 v) {
-  VfPlanes3 o;
-  float r0 = v[0], r1 = v[1], r2 = v[2], r3 = v[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const unsigned u0 = __float_as_uint(r0), u1 = __float_as_uint(r1), u2 = __float_as_uint(r2), u3 = __float_as_uint(r3);
-    o.p[q].x = __builtin_amdgcn_perm(u1, u0, 0x07060302u);      // (u1 & 0xffff0000) | (u0 >> 16)
-    o.p[q].y = __builtin_amdgcn_perm(u3, u2, 0x07060302u);
-    if (q < 2) {
-      r0 -= __uint_as_float(u0 & 0xffff0000u);
-      r1 -= __uint_as_float(u1 & 0xffff0000u);
-      r2 -= __uint_as_float(u2 & 0xffff0000u);
-      r3 -= __uint_as_float(u3 & 0xffff0000u);
-    }
-  }
-  return o;
-}
-
-// XCD-aware block order.  The dispatcher deals consecutive workgroup ids round-robin over the 8 XCDs (each with its
-// own 4 MiB L2), so neighbouring tiles — which share input halos (k_igemm) or the whole gathered operand (k_wgrad's
-// column tiles) — land on different L2s and every one of them fetches the shared rows from the fabric again
-// (measured with FETCH_SIZE: 3-5x the algorithmic bytes).  This bijective remap gives each XCD one contiguous run of
-// logical tile ids instead; it only ever changes speed, never results.
-__device__ __forceinline__ int vf_xcd_remap(int h, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = h & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (h >> 3);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -137,38 +85,6 @@ struct IGemm {
   VfBnSt st;                       // BatchNorm statistics of the output as a by-product of the epilogue (mode 0: none)
 };
 
-// Per-channel partial sums of one block's output tile -> one partial row (see VfBnSt).  Lane l of a wave holds column
-// l % 32 of its 32-wide fragments and 16 rows per fragment: the per-lane sums over those rows are combined across the two
-// lane halves with a shuffle, across the waves stacked in M through LDS in a fixed order (deterministic), and the block
-// writes doubles.  `red` = 2 * WAVES_M * BN floats of LDS that nothing else uses any more.
-template <int NT, int WAVES_M, int BN>
-__device__ __forceinline__ void vf_bn_tile_partials(const VfBnSt& st, float (&s1)[NT], float (&s2)[NT], float* red, int wave_m,
-                                                    int wn, int lane, int tid, int n0, int N, int bx, int pz) {
-  const int lr = lane & 31;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    s1[nt] += __shfl_xor(s1[nt], 32, 64);
-    s2[nt] += __shfl_xor(s2[nt], 32, 64);
-    if (lane < 32) {
-      red[(wave_m * 2 + 0) * BN + wn + nt * 32 + lr] = s1[nt];
-      red[(wave_m * 2 + 1) * BN + wn + nt * 32 + lr] = s2[nt];
-    }
-  }
-  __syncthreads();
-  if (tid < BN && n0 + tid < N) {
-    double a = 0, b = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES_M; ++w) {
-      a += (double)red[(w * 2 + 0) * BN + tid];
-      b += (double)red[(w * 2 + 1) * BN + tid];
-    }
-    const int g = bx / st.tiles_per_group, local = bx - g * st.tiles_per_group;
-    double* o = st.part + ((int64_t)(g * st.rows_per_group + local * st.zpar + pz) * 2) * N;
-    o[n0 + tid] = a;
-    o[N + n0 + tid] = b;
-  }
-}
-
 // V = 2: 16-byte loads for A and B (C % 16 == 0);  V = 1: 16-byte A, scalar B (k-major B with N % 4 != 0);
 // V = 0: scalar loads with a flattened (tap, c) K index (first/last layers: C = 3, 12, 27 ...).
 // BF = 1: bf16-operand mode (opt-in, vf_ctx_set_mfma_mode): the fp32 pieces are rounded to bf16 (RNE) on their way
@@ -180,7 +96,6 @@ __device__ __forceinline__ void vf_bn_tile_partials(const VfBnSt& st, float (&s1
 // Everything outside the LDS tile (addresses, loads, epilogue, split-K) is shared with the fp32 path.
 // KLIN: K walked in memory order (tap outer, channel chunk inner) — the 1x1-output bottleneck layers (see next_chunk);
 // a template parameter so that no other instantiation carries its counters.
-template <int I> struct VfIC { static constexpr int value = I; };
 // DB (mode 3, V = 2 only): double-buffered LDS with the split and the LDS writes of step k+1 issued between the MFMAs of
 // step k and the global loads running two steps ahead in a second register set — for launches whose grid leaves at
 // most two blocks per CU anyway (the 66 KB this needs costs no occupancy there; see launch_igemm).
@@ -463,7 +378,7 @@ __global__ __launch_bounds__(256) void k_igemm(const IGemm p) {
   auto load_tile = [&](int kt) {
     begin_tile(kt, true);
 #pragma unroll
-    for (int pc = 0; pc < A_CH + B_CH; ++pc) load_piece(pc, VfIC<0>{});
+    for (int pc = 0; pc < A_CH + B_CH; ++pc) load_piece(pc, VfIntC<0>{});
   };
 
   auto store_piece = [&](int buf, int pc, auto SET) {
@@ -476,9 +391,10 @@ __global__ __launch_bounds__(256) void k_igemm(const IGemm p) {
         if (256 * i + 255 < BM * 8 || id < BM * 8) {
           __bf16* dst = base + piece_off(id >> 3, kq);
           if constexpr (NP == 3) {
-            const VfPlanes3 s3 = vf_split3(ra[rs][i]);
+            u32x2 s3[3];
+            vf_split3(ra[rs][i], s3);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) *(uint2*)(dst + q * PL_SZ) = s3.p[q];
+            for (int q = 0; q < 3; ++q) *(u32x2*)(dst + q * PL_SZ) = s3[q];
           } else {
             *(bf16x4*)dst = __builtin_convertvector(ra[rs][i], bf16x4);
           }
@@ -496,9 +412,10 @@ __global__ __launch_bounds__(256) void k_igemm(const IGemm p) {
           }
           __bf16* dst = base + AH_SZ + off;
           if constexpr (NP == 3) {
-            const VfPlanes3 s3 = vf_split3(v);
+            u32x2 s3[3];
+            vf_split3(v, s3);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) *(uint2*)(dst + q * PL_SZ) = s3.p[q];
+            for (int q = 0; q < 3; ++q) *(u32x2*)(dst + q * PL_SZ) = s3[q];
           } else {
             *(bf16x4*)dst = __builtin_convertvector(v, bf16x4);
           }
@@ -525,7 +442,7 @@ __global__ __launch_bounds__(256) void k_igemm(const IGemm p) {
   };
   auto store_tile = [&](int buf) {
 #pragma unroll
-    for (int pc = 0; pc < A_CH + B_CH; ++pc) store_piece(buf, pc, VfIC<0>{});
+    for (int pc = 0; pc < A_CH + B_CH; ++pc) store_piece(buf, pc, VfIntC<0>{});
   };
 
   f32x16 acc[MT][NT];
@@ -557,7 +474,7 @@ __global__ __launch_bounds__(256) void k_igemm(const IGemm p) {
     static_assert(2 * NPC <= SLOTS, "loads and LDS writes of one K step must fit between its MFMAs");
     begin_tile(kt0 + 1, kt0 + 1 < kt1);
 #pragma unroll
-    for (int pc = 0; pc < NPC; ++pc) load_piece(pc, VfIC<1>{});
+    for (int pc = 0; pc < NPC; ++pc) load_piece(pc, VfIntC<1>{});
     auto step = [&](int kt, auto SET) {
       constexpr int S = decltype(SET)::value;
       const __bf16* base = (const __bf16*)smem + S * (NP * PL_SZ);
@@ -599,15 +516,15 @@ __global__ __launch_bounds__(256) void k_igemm(const IGemm p) {
               if (slot < NPC) load_piece(slot, SET);
               // (unconditional: on the last step this writes zeros into the buffer nobody reads again; a branch here
               //  makes the compiler drain every outstanding load at the top of each step)
-              if (slot >= SLOTS - NPC) store_piece(S ^ 1, slot - (SLOTS - NPC), VfIC<(S ^ 1)>{});
+              if (slot >= SLOTS - NPC) store_piece(S ^ 1, slot - (SLOTS - NPC), VfIntC<(S ^ 1)>{});
               __builtin_amdgcn_sched_barrier(0);
             }
       }
       __syncthreads();
     };
     for (int kt = kt0; kt < kt1; kt += 2) {
-      step(kt, VfIC<0>{});
-      if (kt + 1 < kt1) step(kt + 1, VfIC<1>{});
+      step(kt, VfIntC<0>{});
+      if (kt + 1 < kt1) step(kt + 1, VfIntC<1>{});
     }
   } else
   if constexpr (BF) {
@@ -616,7 +533,7 @@ __global__ __launch_bounds__(256) void k_igemm(const IGemm p) {
       const __bf16* base = (const __bf16*)smem + buf * (NP * PL_SZ);
       begin_tile(kt + 1, kt + 1 < kt1);
 #pragma unroll
-      for (int pc = 0; pc < A_CH + B_CH; ++pc) load_piece(pc, VfIC<0>{});
+      for (int pc = 0; pc < A_CH + B_CH; ++pc) load_piece(pc, VfIntC<0>{});
 #pragma unroll
       for (int g = 0; g < BK / 16; ++g) {
         bf16x8 a[NP][MT], b[NP][NT];
@@ -699,8 +616,8 @@ __global__ __launch_bounds__(256) void k_igemm(const IGemm p) {
           for (int nt = 0; nt < NT; ++nt) {
             acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ss & 1][mt][j], fb[ss & 1][nt][j], acc[mt][nt], 0, 0, 0);
             const int slot = ss * NMF + (j * MT + mt) * NT + nt;
-            if (slot < NPC) load_piece(slot, VfIC<0>{});
-            if (slot >= SLOTS - NPC) store_piece(buf ^ 1, slot - (SLOTS - NPC), VfIC<0>{});
+            if (slot < NPC) load_piece(slot, VfIntC<0>{});
+            if (slot >= SLOTS - NPC) store_piece(buf ^ 1, slot - (SLOTS - NPC), VfIntC<0>{});
             __builtin_amdgcn_sched_barrier(0);
           }
     }
@@ -1045,9 +962,10 @@ __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
         off = UH_SZ + ((tid >> 5) + 8 * i) * LDMV + 4 * cq;
       }
       if constexpr (NP == 3) {
-        const VfPlanes3 s3 = vf_split3(v);
+        u32x2 s3[3];
+        vf_split3(v, s3);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) *(uint2*)(base + q * PL_SZ + off) = s3.p[q];
+        for (int q = 0; q < 3; ++q) *(u32x2*)(base + q * PL_SZ + off) = s3[q];
       } else {
         *(bf16x4*)(base + off) = __builtin_convertvector(v, bf16x4);
       }

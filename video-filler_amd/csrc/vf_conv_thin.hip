@@ -11,10 +11,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "vf_common.h"
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "vf_device.h"
 
 namespace {
 
@@ -118,12 +115,8 @@ __global__ __launch_bounds__(256) void k_conv_thin_in(const float* __restrict__ 
         float r0 = a0, r1 = a1;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-          const unsigned u0 = __float_as_uint(r0), u1 = __float_as_uint(r1);
-          *(unsigned*)(planes + q * pstride + o) = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
-          if (q < 2) {
-            r0 -= __uint_as_float(u0 & 0xffff0000u);
-            r1 -= __uint_as_float(u1 & 0xffff0000u);
-          }
+          const unsigned lo = vf_trunc16(r0), hi = vf_trunc16(r1);
+          *(unsigned*)(planes + q * pstride + o) = lo | (hi << 16);
         }
       }
     }

@@ -3,9 +3,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "vf_common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "vf_device.h"
 
 // ------------------------------------------------------------------------------------------------ errors / ctx
 static thread_local char g_err[1024] = "";
@@ -449,7 +447,6 @@ __global__ __launch_bounds__(256) void k_recon_grad_mix(float* __restrict__ dfdg
 }
 // the same pass in 16-byte pieces, four of them per thread with every load issued before the first use (the scalar form is a chain of
 // 4-byte loads, eight per thread one after the other: 12.5 us for 786 432 elements that move 13 MB)
-typedef float vf_f32x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void k_recon_grad_mix4(float* __restrict__ dfdg, const float* __restrict__ x,
                                                          const float* __restrict__ t, const float* __restrict__ mask,
                                                          float alpha, float c0, float c1, int band, int HW, int lgHW, int C, int64_t n4,
@@ -459,22 +456,22 @@ __global__ __launch_bounds__(256) void k_recon_grad_mix4(float* __restrict__ dfd
   const int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   double sd = 0;
   for (int64_t base = i0; base < n4; base += NV * stride) {
-    vf_f32x4 xv[NV], tv[NV], gv[NV], mv[NV];
+    f32x4 xv[NV], tv[NV], gv[NV], mv[NV];
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
       const int64_t i = base + j * stride;
       if (i < n4) {
-        xv[j] = ((const vf_f32x4*)x)[i];
-        tv[j] = ((const vf_f32x4*)t)[i];
-        gv[j] = ((const vf_f32x4*)dfdg)[i];
-        if (mask) mv[j] = ((const vf_f32x4*)mask)[i];
+        xv[j] = ((const f32x4*)x)[i];
+        tv[j] = ((const f32x4*)t)[i];
+        gv[j] = ((const f32x4*)dfdg)[i];
+        if (mask) mv[j] = ((const f32x4*)mask)[i];
       }
     }
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
       const int64_t i = base + j * stride;
       if (i >= n4) continue;
-      vf_f32x4 o;
+      f32x4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float d = xv[j][e] - tv[j][e];
@@ -495,7 +492,7 @@ __global__ __launch_bounds__(256) void k_recon_grad_mix4(float* __restrict__ dfd
         }
         o[e] = alpha * gv[j][e] + (two_over_n * d) * w;
       }
-      ((vf_f32x4*)dfdg)[i] = o;
+      ((f32x4*)dfdg)[i] = o;
     }
   }
   block_add_double(sd * inv_n, loss);

@@ -17,63 +17,18 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "vf_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pg_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ int pg_xcd_remap(int h, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = h & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (h >> 3);
-}
+#include "vf_device.h"
 
 // ------------------------------------------------------------------------------------------------ plane producers
-// Exact three-way split by truncation (the same arithmetic as vf_conv.hip's vf_split3): plane q = top 16 bits of the
-// running residual; every residual subtraction is exact in fp32, after two steps at most 8 significant bits are left.
-__device__ __forceinline__ void pg_split4(f32x4 v, u32x2 (&o)[3]) {
-  float r0 = v[0], r1 = v[1], r2 = v[2], r3 = v[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const unsigned u0 = __float_as_uint(r0), u1 = __float_as_uint(r1), u2 = __float_as_uint(r2), u3 = __float_as_uint(r3);
-    o[q][0] = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
-    o[q][1] = __builtin_amdgcn_perm(u3, u2, 0x07060302u);
-    if (q < 2) {
-      r0 -= __uint_as_float(u0 & 0xffff0000u);
-      r1 -= __uint_as_float(u1 & 0xffff0000u);
-      r2 -= __uint_as_float(u2 & 0xffff0000u);
-      r3 -= __uint_as_float(u3 & 0xffff0000u);
-    }
-  }
-}
-// The bf16-operand mode (vf_ctx_set_mfma_mode 1; BASELINE configs[4]'s "bf16"): ONE plane, the operand rounded to nearest-even —
-// bit for bit the rounding vf_conv.hip's BF = 1 kernels apply inside the GEMM ((u + 0x7FFF + lsb) >> 16), done once here.
-// 2 bytes per element instead of 6, one MFMA per product instead of six.
-__device__ __forceinline__ unsigned pg_rne16(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ u32x2 pg_round4(f32x4 v) {
-  u32x2 o;
-  o[0] = pg_rne16(v[0]) | (pg_rne16(v[1]) << 16);
-  o[1] = pg_rne16(v[2]) | (pg_rne16(v[3]) << 16);
-  return o;
-}
 template <int NPL>
 __global__ __launch_bounds__(256) void k_planes_split(const float* __restrict__ x, __bf16* __restrict__ planes, int64_t n4,
                                                       int64_t pstride) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     if constexpr (NPL == 1) {
-      *(u32x2*)(planes + 4 * i) = pg_round4(((const f32x4*)x)[i]);
+      *(u32x2*)(planes + 4 * i) = vf_round4(((const f32x4*)x)[i]);
     } else {
       u32x2 o[3];
-      pg_split4(((const f32x4*)x)[i], o);
+      vf_split3(((const f32x4*)x)[i], o);
 #pragma unroll
       for (int q = 0; q < 3; ++q) *(u32x2*)(planes + q * pstride + 4 * i) = o[q];
     }
@@ -95,14 +50,11 @@ __global__ __launch_bounds__(256) void k_weight_planes(const float* __restrict__
     if (a < d0 && b < d1) {
       float r = v;
       if (npl == 1) {
-        ((unsigned short*)nat)[((int64_t)a * 16 + tap) * d1 + b] = (unsigned short)pg_rne16(r);
+        ((unsigned short*)nat)[((int64_t)a * 16 + tap) * d1 + b] = (unsigned short)vf_rne16(r);
       } else {
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          const unsigned u = __float_as_uint(r) & 0xffff0000u;
-          ((unsigned short*)nat)[q * pstride + ((int64_t)a * 16 + tap) * d1 + b] = (unsigned short)(u >> 16);
-          r -= __uint_as_float(u);
-        }
+        for (int q = 0; q < 3; ++q)
+          ((unsigned short*)nat)[q * pstride + ((int64_t)a * 16 + tap) * d1 + b] = (unsigned short)vf_trunc16(r);
       }
     }
   }
@@ -113,14 +65,11 @@ __global__ __launch_bounds__(256) void k_weight_planes(const float* __restrict__
     if (a < d0 && b < d1) {
       float r = tile[tx][j];
       if (npl == 1) {
-        ((unsigned short*)tr)[((int64_t)b * 16 + tap) * d0 + a] = (unsigned short)pg_rne16(r);
+        ((unsigned short*)tr)[((int64_t)b * 16 + tap) * d0 + a] = (unsigned short)vf_rne16(r);
       } else {
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          const unsigned u = __float_as_uint(r) & 0xffff0000u;
-          ((unsigned short*)tr)[q * pstride + ((int64_t)b * 16 + tap) * d0 + a] = (unsigned short)(u >> 16);
-          r -= __uint_as_float(u);
-        }
+        for (int q = 0; q < 3; ++q)
+          ((unsigned short*)tr)[q * pstride + ((int64_t)b * 16 + tap) * d0 + a] = (unsigned short)vf_trunc16(r);
       }
     }
   }
@@ -145,14 +94,10 @@ __global__ __launch_bounds__(256) void k_weight_planes_multi(const VfWpDesc* __r
     const int a = t0 + j, b = u0 + tx;
     float r = (a < d0 && b < d1) ? L.w[((int64_t)a * 16 + tap) * d1 + b] : 0.f;
     if (npl == 1) {
-      t[0][j][tx] = (unsigned short)pg_rne16(r);
+      t[0][j][tx] = (unsigned short)vf_rne16(r);
     } else {
 #pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const unsigned u = __float_as_uint(r) & 0xffff0000u;
-        t[q][j][tx] = (unsigned short)(u >> 16);
-        r -= __uint_as_float(u);
-      }
+      for (int q = 0; q < 3; ++q) t[q][j][tx] = (unsigned short)vf_trunc16(r);
     }
   }
   __syncthreads();
@@ -223,35 +168,6 @@ struct PGemm {
   int dbg;
   VfBnSt st;
 };
-
-// per-channel partial sums of one block's output tile (see vf_conv.hip vf_bn_tile_partials: same layout, same order)
-template <int NT, int WAVES_M, int BN>
-__device__ __forceinline__ void pg_bn_tile_partials(const VfBnSt& st, float (&s1)[NT], float (&s2)[NT], float* red, int wave_m, int wn,
-                                                    int lane, int tid, int n0, int N, int bx, int pz) {
-  const int lr = lane & 31;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    s1[nt] += __shfl_xor(s1[nt], 32, 64);
-    s2[nt] += __shfl_xor(s2[nt], 32, 64);
-    if (lane < 32) {
-      red[(wave_m * 2 + 0) * BN + wn + nt * 32 + lr] = s1[nt];
-      red[(wave_m * 2 + 1) * BN + wn + nt * 32 + lr] = s2[nt];
-    }
-  }
-  __syncthreads();
-  if (tid < BN && n0 + tid < N) {
-    double a = 0, b = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES_M; ++w) {
-      a += (double)red[(w * 2 + 0) * BN + tid];
-      b += (double)red[(w * 2 + 1) * BN + tid];
-    }
-    const int g = bx / st.tiles_per_group, local = bx - g * st.tiles_per_group;
-    double* o = st.part + ((int64_t)(g * st.rows_per_group + local * st.zpar + pz) * 2) * N;
-    o[n0 + tid] = a;
-    o[N + n0 + tid] = b;
-  }
-}
 
 // ---- epilogue shared by the GEMM kernels below: C/D layout col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
 // The store loop is instantiated per (derivative mask present, statistics mode) and the (leaky) ReLU is a select of the
@@ -339,7 +255,7 @@ __device__ __forceinline__ void pg_epilogue_at(const PGemm& p, f32x16 (&acc)[MT]
     else store_all(VfIntC<0>{}, VfIntC<0>{});
   }
   if (stm)
-    pg_bn_tile_partials<NT, WAVES_M, BN>(p.st, st1, st2, red, wave_m, wn, lane, tid, n0, tile_ok ? p.N : 0, bx,
+    vf_bn_tile_partials<NT, WAVES_M, BN>(p.st, st1, st2, red, wave_m, wn, lane, tid, n0, tile_ok ? p.N : 0, bx,
                                          p.parity ? ((ph << 1) | pw) : 0);
 }
 
@@ -394,7 +310,7 @@ __global__ __launch_bounds__(256) void k_pconv(const PGemm p) {
   const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave / WAVES_N) * WM, wn = (wave % WAVES_N) * WN;
   const int ntiles = p.gm * p.gn * p.gz;
-  int lid = pg_xcd_remap(blockIdx.x, ntiles);
+  int lid = vf_xcd_remap(blockIdx.x, ntiles);
   const bool tile_ok = lid < ntiles;
   if (!tile_ok) lid = 0;
   int ph = 0, pw = 0;
@@ -444,7 +360,7 @@ __global__ __launch_bounds__(256) void k_pconv(const PGemm p) {
     w_byte[i] = n < p.N ? 2u * (unsigned)(n * 16 * p.C + 8 * oct) : VF_OOB;
     b_lds[i] = AH_SZ + sw_off(row, oct);
   }
-  const __amdgpu_buffer_rsrc_t rsA = pg_rsrc(p.A, p.a_bytes), rsW = pg_rsrc(p.W, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t rsA = vf_rsrc(p.A, p.a_bytes), rsW = vf_rsrc(p.W, p.w_bytes);
   // wave-uniform byte offsets of window tap (th, tw): th * row + tw * col (+ the filter tap's base for the weights); th and
   // tw are compile-time constants at every use, so each offset is two scalar multiply-adds (a table of 2 x 16 offsets held
   // in SGPRs spilled: 106 SGPRs, 36-68 bytes of scratch per lane)
@@ -605,7 +521,7 @@ __global__ __launch_bounds__((BM / 32) * (BN / 32) * 64) void k_pconv_dma(const 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = (wave / WAVES_N) * 32, wn = (wave % WAVES_N) * 32;
   const int ntiles = p.gm * p.gn * p.gz;
-  int lid = pg_xcd_remap(blockIdx.x, ntiles);
+  int lid = vf_xcd_remap(blockIdx.x, ntiles);
   int ph = 0, pw = 0;
   if (p.parity) {
     ph = (lid >> 1) & 1;
@@ -655,7 +571,7 @@ __global__ __launch_bounds__((BM / 32) * (BN / 32) * 64) void k_pconv_dma(const 
     w_byte[i] = n < p.N ? 2u * (unsigned)(n * 16 * p.C + 8 * oct) : VF_OOB;
     b_lds[i] = 2u * (unsigned)(AH_SZ + grp * 8 * 64);
   }
-  const __amdgpu_buffer_rsrc_t rsA = pg_rsrc(p.A, p.a_bytes), rsW = pg_rsrc(p.W, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t rsA = vf_rsrc(p.A, p.a_bytes), rsW = vf_rsrc(p.W, p.w_bytes);
   int rowA = 2 * p.Wi * p.C, colA = 2 * p.C;
   int w0 = 2 * (kh0 * 4 + kw0) * p.C, rowW = 8 * p.khs * p.C, colW = 2 * p.kws * p.C;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;      // LDS byte address of the buffers
@@ -816,7 +732,7 @@ __global__ __launch_bounds__(512) void k_pconv_patch_tr(const PGemm p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
   const int lr = lane & 31, lh = lane >> 5;
-  int lid = pg_xcd_remap(blockIdx.x, gridDim.x);
+  int lid = vf_xcd_remap(blockIdx.x, gridDim.x);
   const int n0 = 64 * (lid % p.gn);                         // this block's column slice (neighbours in the grid share the patch's lines)
   lid /= p.gn;
   int ph_blk = 0;
@@ -851,7 +767,7 @@ __global__ __launch_bounds__(512) void k_pconv_patch_tr(const PGemm p) {
   const int wrow = 8 * wave + (lane >> 3);
   const unsigned w_byte = 2u * (unsigned)((n0 + wrow) * 16 * p.C + 8 * ((lane & 7) ^ ((wrow >> 1) & 7)));
   const unsigned w_lds = (unsigned)(wave * 8 * 128);
-  const __amdgpu_buffer_rsrc_t rsA = pg_rsrc(p.A, p.a_bytes), rsW = pg_rsrc(p.W, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t rsA = vf_rsrc(p.A, p.a_bytes), rsW = vf_rsrc(p.W, p.w_bytes);
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
   unsigned szero;
   asm volatile("s_mov_b32 %0, 0" : "=s"(szero));
@@ -936,8 +852,8 @@ __global__ __launch_bounds__(512) void k_pconv_patch_tr(const PGemm p) {
   const float neg = p.act == VF_ACT_LRELU ? p.slope : (p.act == VF_ACT_RELU ? 0.f : 1.f);
   const float dneg = p.dact == VF_ACT_LRELU ? p.dslope : (p.dact == VF_ACT_RELU ? 0.f : 1.f);
   const unsigned ybytes = (unsigned)(p.out_elems * 4);
-  const __amdgpu_buffer_rsrc_t rsY = pg_rsrc(p.Y, ybytes), rsD = pg_rsrc(p.dbits ? (const void*)p.dbits : (const void*)p.dmask, p.dbits ? ybytes / 32 : ybytes),
-                               rsX = pg_rsrc(p.st.x, ybytes);
+  const __amdgpu_buffer_rsrc_t rsY = vf_rsrc(p.Y, ybytes), rsD = vf_rsrc(p.dbits ? (const void*)p.dbits : (const void*)p.dmask, p.dbits ? ybytes / 32 : ybytes),
+                               rsX = vf_rsrc(p.st.x, ybytes);
   // output pixel of (row r of this lane, class (ph, pw)), 32-bit (the host checks the extent): row = wm + (r & 3) + 4 lh + 8 (r >> 2),
   // (oy, ox) = (2 (ry0 + row / 16) + ph, 2 (rx0 + row % 16) + pw) = pix0 + (ph outW + pw) + (r >> 3) 2 outW + 2 ((r & 3) + 8 ((r >> 2) & 1))
   unsigned pix0 = (unsigned)(((b * p.outH + 2 * (ry0 + 2 * (wave >> 1))) * p.outW) + 2 * (rx0 + 4 * lh));
@@ -980,7 +896,7 @@ __global__ __launch_bounds__(512) void k_pconv_patch_tr(const PGemm p) {
       }
       acc[cls][r] = v;         // the finished value stays in the accumulator's registers: the stores leave after the last step
     }
-    if (stm) pg_bn_tile_partials<1, 4, 64>(p.st, st1, st2, red, wave >> 1, wn, lane, tid, n0, N, bx, (ph << 1) | pw);
+    if (stm) vf_bn_tile_partials<1, 4, 64>(p.st, st1, st2, red, wave >> 1, wn, lane, tid, n0, N, bx, (ph << 1) | pw);
   };
   // (every step begins with s_waitcnt vmcnt(0) for its DMAs, which would also wait for any store still on its way: 16 stores per lane
   //  and class, issued between the classes, stalled the next step for the whole write latency — in the iteration, with the memory
@@ -1097,7 +1013,7 @@ __global__ __launch_bounds__(512) void k_pconv_patch_g(const PGemm p) {
   const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
   const int lr = lane & 31, lh = lane >> 5;
   const int ntiles = p.gm * p.gn * p.gz;
-  int lid = pg_xcd_remap(blockIdx.x, ntiles);
+  int lid = vf_xcd_remap(blockIdx.x, ntiles);
   int ph = 0, pw = 0;                                       // TR: this block's output-parity class
   if constexpr (TR) {
     ph = (lid >> 1) & 1;
@@ -1155,7 +1071,7 @@ __global__ __launch_bounds__(512) void k_pconv_patch_g(const PGemm p) {
   const int wrow = 8 * wave + (lane >> 3);
   const unsigned w_byte = 2u * (unsigned)((n0 + wrow) * 16 * p.C + 8 * ((lane & 7) ^ ((wrow >> 1) & 7)));
   const unsigned w_lds = (unsigned)(wave * 8 * 128);
-  const __amdgpu_buffer_rsrc_t rsA = pg_rsrc(p.A, p.a_bytes), rsW = pg_rsrc(p.W, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t rsA = vf_rsrc(p.A, p.a_bytes), rsW = vf_rsrc(p.W, p.w_bytes);
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
   unsigned szero;
   asm volatile("s_mov_b32 %0, 0" : "=s"(szero));
@@ -1395,7 +1311,7 @@ __global__ __launch_bounds__(512, FS == 1 ? 6 : 1) void k_pwgrad_group(const VfP
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = (wave >> 1) * 32, wn = (wave & 1) * 64;
-  const int lid = pg_xcd_remap(local, ntiles);
+  const int lid = vf_xcd_remap(local, ntiles);
   const int jx = __builtin_amdgcn_readfirstlane(lid % p.gx), rest = __builtin_amdgcn_readfirstlane(lid / p.gx);
   const int n0 = __builtin_amdgcn_readfirstlane(rest % p.gy) * 128, j0 = jx * 128;
   const int ks = __builtin_amdgcn_readfirstlane(rest / p.gy);
@@ -1412,7 +1328,7 @@ __global__ __launch_bounds__(512, FS == 1 ? 6 : 1) void k_pwgrad_group(const VfP
   const int tap = col / p.Cv, cch = col - tap * p.Cv;
   const int dy = (tap >> 2) - 1, dx = (tap & 3) - 1;                           // stride 2, pad 1
   const int Mw = 1 << p.lgMw, Mh = 1 << p.lgMh;
-  const __amdgpu_buffer_rsrc_t rsU = pg_rsrc(p.Up, (unsigned)NPL * p.u_ps), rsV = pg_rsrc(p.Vp, (unsigned)NPL * p.v_ps);
+  const __amdgpu_buffer_rsrc_t rsU = vf_rsrc(p.Up, (unsigned)NPL * p.u_ps), rsV = vf_rsrc(p.Vp, (unsigned)NPL * p.v_ps);
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
   const unsigned row_lds = 2u * (unsigned)(4 * wave * 128);                    // this wave's four rows inside a tile (bytes)
   unsigned szero;
@@ -1450,12 +1366,12 @@ __global__ __launch_bounds__(512, FS == 1 ? 6 : 1) void k_pwgrad_group(const VfP
       }
       const int off = k * 128 + (((c4 >> 5) ^ (k & 3)) << 5) + (c4 & 31);      // bf16 elements inside a tile
       if constexpr (NPL == 1) {
-        *(u32x2*)(smem + off) = pg_round4(u);
-        *(u32x2*)(smem + TILE + off) = pg_round4(v);
+        *(u32x2*)(smem + off) = vf_round4(u);
+        *(u32x2*)(smem + TILE + off) = vf_round4(v);
       } else {
         u32x2 up[3], vp[3];
-        pg_split4(u, up);
-        pg_split4(v, vp);
+        vf_split3(u, up);
+        vf_split3(v, vp);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           *(u32x2*)(smem + q * PL_SZ + off) = up[q];

@@ -20,20 +20,9 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "vf_common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "vf_device.h"
 
 namespace {
-
-__device__ __forceinline__ float sm_rne(float f) {
-  const unsigned u = __float_as_uint(f);
-  return __uint_as_float(((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16) << 16);
-}
-__device__ __forceinline__ f32x4 sm_rne4(f32x4 v) {
-  f32x4 o = {sm_rne(v[0]), sm_rne(v[1]), sm_rne(v[2]), sm_rne(v[3])};
-  return o;
-}
 
 // ---- row-dot: slab[ks][b][n] = sum_{k in range ks} A[b][k] W[n][k]
 // grid: (N / 8 row groups) x ksplit waves, four waves per block (consecutive row groups of the same K range)
@@ -71,9 +60,9 @@ __global__ __launch_bounds__(256) void k_smallm_rowdot(const float* __restrict__
     for (int b = 0; b < MT; ++b) st.x[b] = st.x[b] * xm[b];
     if (rb) {
 #pragma unroll
-      for (int b = 0; b < MT; ++b) st.x[b] = sm_rne4(st.x[b]);
+      for (int b = 0; b < MT; ++b) st.x[b] = vf_rne(st.x[b]);
 #pragma unroll
-      for (int r = 0; r < R; ++r) st.w[r] = sm_rne4(st.w[r]);
+      for (int r = 0; r < R; ++r) st.w[r] = vf_rne(st.w[r]);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -145,11 +134,11 @@ __global__ __launch_bounds__(256) void k_smallm_axpy(const float* __restrict__ A
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
       f32x4 w = st.w[j];
-      if (rb) w = sm_rne4(w);
+      if (rb) w = vf_rne(w);
 #pragma unroll
       for (int b = 0; b < MT; ++b) {
         float a = A[(int64_t)(b < M ? b : 0) * C + c0 + c + j];       // wave-uniform: a scalar load (rows past M: row 0, unused)
-        if (rb) a = sm_rne(a);
+        if (rb) a = vf_rne(a);
         acc[b] += a * w;
       }
     }

@@ -22,12 +22,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "vf_common.h"
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "vf_device.h"
 
 namespace {
 
@@ -52,10 +47,6 @@ struct VfAdamFuse {
   const bf16x8* vf;
   int kg;
 };
-__device__ __forceinline__ float ws_rne(float f) {
-  const unsigned u = __float_as_uint(f);
-  return __uint_as_float(((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16) << 16);
-}
 // RB: rows of x, m, v in flight per epilogue batch; OCC: waves per SIMD the register budget is held to; PF: the first batch is
 // loaded BEFORE the K loop, so it travels under the matrix-core phase
 // wt: this wave's tile, column tiles fastest (the four waves of a block share U rows); ldu: floats per batch row of U (>= Nu)
@@ -107,10 +98,10 @@ __device__ __forceinline__ void wgrad_smallk_body(const float* __restrict__ U, c
     for (int j = 0; j < NJ; ++j) b[j] = p.b[j] * p.mb;
     if constexpr (FUSE) {
       if (A.round_bf16) {
-        a[0] = ws_rne(a[0]);
-        a[1] = ws_rne(a[1]);
+        a[0] = vf_rne(a[0]);
+        a[1] = vf_rne(a[1]);
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) b[j] = ws_rne(b[j]);
+        for (int j = 0; j < NJ; ++j) b[j] = vf_rne(b[j]);
       }
     }
 #pragma unroll
@@ -283,7 +274,7 @@ struct VfFusedTable {
 };
 // Operands of the fused update as bf16 planes in FRAGMENT order (the three-plane form above): entry (tile t, half h, k-group g, plane q,
 // lane l) = the eight k values 16 g + 8 (l / 32) .. + 7 of operand row / column 64 t + 2 (l % 32) + h, exact three-way split (hi + mid + lo
-// == x bit for bit: vf_pgemm.hip pg_split4's arithmetic), zeros past the matrix edge.  One thread per (operand, t, h, g, l): eight strided
+// == x bit for bit: vf_device.h vf_split3's arithmetic), zeros past the matrix edge.  One thread per (operand, t, h, g, l): eight strided
 // fp32 loads (32 lanes cover one 256-byte run between them and their h-partner), three 16-byte stores.  1.5 + 3.1 MB per layer at K = 64.
 struct VfPrepTable {
   int nl;
@@ -331,11 +322,7 @@ __global__ __launch_bounds__(256) void k_fused_planes_prep(const VfFusedTable T,
     typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
     u16x8 o;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const unsigned u = __float_as_uint(x[q]);
-      o[q] = (unsigned short)(u >> 16);
-      x[q] -= __uint_as_float(u & 0xffff0000u);
-    }
+    for (int q = 0; q < 8; ++q) o[q] = (unsigned short)vf_trunc16(x[q]);
     *(u16x8*)(dst + p * 64) = o;
   }
 }
