@@ -457,6 +457,26 @@ int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, size_t*
 int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, void* ws, size_t ws_bytes,
                   unsigned char* out, size_t out_cap, int64_t* offsets);
 
+/* ---- animated GIF encode (vf_gif.hip) ------------------------------------------------------------------
+ * The `convert -delay D pred_1.png ... x_result.gif` that ends test_vid.lua:140-147, test_vid_wholeim.lua:244-257 and
+ * test_more_complex.lua:216-229, on the device: `clips` clips of `frames` RGB frames of one H x W in, `clips` whole
+ * GIF89a files out, back to back.  Sides 1 to 16384, 1 to 65535 frames per clip, 1 to 65535 clips, delay 0 to 65535
+ * centiseconds; anything else is an error naming the argument, before anything is launched.  kind 0: float
+ * (clips*frames) x 3 x H x W, every value through image.savePNG's rule (see vf_png_encode); kind 1: uint8
+ * (clips*frames) x H x W x 3, taken as they are.  The rule is the project's own and all-integer (tests/gif_ref.py is its
+ * definition; ImageMagick's adaptive tree and dithering are not restated): a local table of 256 per frame, the frame's
+ * colours in ascending order when there are at most 256 (lossless), else median cut on the 5-bit histogram with box
+ * means; nearest entry per pixel, lowest index on a tie, no dithering; LZW with a Clear every 3824 pixels; loop count 0,
+ * disposal 0, no transparency, no frame differencing.  A file's bytes depend on its own frames and the delay only, a
+ * frame's bytes (graphic control extension to block terminator) on that frame and the delay only; the same on every run.
+ * vf_gif_workspace_bytes (host only, no GPU): the DEVICE workspace and an upper bound on the output for the batch. */
+int vf_gif_workspace_bytes(int clips, int frames, int H, int W, size_t* ws_bytes, size_t* out_bytes);
+/* Encode on the context's stream.  ws (>= ws_bytes) and out (out_cap >= the bound above) are caller-owned DEVICE memory;
+ * offsets (DEVICE int64[clips + 1]) receives the files' places: file i is out[offsets[i] .. offsets[i + 1]).  Nothing is
+ * allocated and nothing synchronises. */
+int vf_gif_encode(vf_ctx* ctx, const void* src, int kind, int clips, int frames, int H, int W, int delay_cs, void* ws,
+                  size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
+
 /* ---- contact sheets of the inference scripts (vf_display.hip) -----------------------------------------
  * image.toDisplayTensor(input, padding, nrow, scaleeach, min, max, symmetric, saturate) of test.lua:129, demo.lua:96 and
  * test_vid.lua:149 for the one input form they use: a packed float tensor N x C x h x w, C = 1 or 3 (src_layout 0:

@@ -1,0 +1,355 @@
+"""Host definition of the device GIF encoder (vf_gif.hip).  NumPy and the standard library only; all integer.
+The reference's drivers end in ImageMagick's `convert -delay D ... x.gif`, whose adaptive colour tree and default dithering
+cannot be restated byte for byte, so the rule is fixed here and the device equals THIS file's output byte for byte.
+
+Frame bytes: uint8 N x H x W x 3 as they are; float N x 3 x H x W through png_ref.chw_to_hwc_bytes (image.savePNG's rule:
+the bytes `convert` would read from the PNGs).
+
+`quantize(frame)`: a local colour table of 256 entries per frame and the index of every pixel.
+  * <= 256 distinct colours: the table is those colours in ascending order of r<<16 | g<<8 | b, zero-padded.
+  * otherwise median cut on the 5-bit-per-channel histogram (32 768 cells, cell = r>>3, g>>3, b>>3).  A box is an inclusive
+    range of cells on each axis, always shrunk to the occupied cells it holds.  Box 0 is the bounding box of all occupied
+    cells.  While there are fewer than 256 boxes: take the box with the most pixels among those holding more than one
+    occupied cell (lowest number on a tie; stop if there is none); its longest axis in cells (R, then G, then B on a tie),
+    lo..hi; the cut c is the smallest position with 2 * (pixels at lo..c) >= the box's pixels, but at most hi - 1; cells
+    lo..c stay box k, cells c+1..hi become the box with the next free number; both are shrunk.  Entry k is the mean of the
+    true 8-bit colours of box k's pixels, (2 * sum + count) // (2 * count) per channel; entries past the last box are zero.
+  * the index of a pixel is the entry (of all 256, padding included) at the smallest squared distance in 8-bit RGB, the
+    lowest index on a tie.  With <= 256 colours that is the colour itself: the frame is stored losslessly.  No dithering.
+
+`lzw(idx)`: GIF's variable-width LZW, minimum code size 8 (Clear 256, EOI 257, first free code 258), in independent
+chunks: a Clear at the start and again after every CHUNK pixels in raster order, EOI at the end.  258 + CHUNK <= 4096, so
+the dictionary never fills and no other Clear exists.  The m-th code after a Clear (m = 1, 2, ...) is max(9,
+bit_length(256 + m)) bits wide: that is the width a decoder reads it at, having added one entry per code after the first.
+A chunk of M codes is therefore followed by a Clear (or EOI) of the width of an (M + 1)-th code, one bit wider than the
+chunk's last code when 257 + M is a power of two.  Codes are packed LSB first with no padding between chunks.
+
+`encode(frames, delay)`: GIF89a; logical screen W x H, no global table (packed 0x70), background 0, aspect 0; the
+NETSCAPE2.0 application extension, loop count 0; per frame a graphic control extension (disposal 0, no transparency,
+delay in centiseconds), an image descriptor at (0,0) of W x H with a local table of 256, the 768 table bytes, the byte 08,
+the code bytes in 255-byte sub-blocks, the terminator 00; then 3B.  `read_gif` is the strict reader of exactly that.
+"""
+import struct
+
+import numpy as np
+
+CHUNK = 3824                                  # video_filler_amd.backend.GIF_CHUNK; <= 3838
+CLEAR, EOI, FIRST = 256, 257, 258
+MAX_SIDE, MAX_FRAMES, MAX_DELAY = 16384, 65535, 65535
+HEADER = b"GIF89a"
+NETSCAPE = b"\x21\xff\x0bNETSCAPE2.0\x03\x01\x00\x00\x00"
+
+
+class GifError(ValueError):
+    pass
+
+
+# --------------------------------------------------------------------------------------------------------- colour table
+def _shrink(hist, box):
+    r0, r1, g0, g1, b0, b1 = box
+    sub = hist[r0:r1 + 1, g0:g1 + 1, b0:b1 + 1]
+    occ = sub > 0
+    ext = []
+    for ax, lo in ((0, r0), (1, g0), (2, b0)):
+        on = np.flatnonzero(occ.any(axis=tuple(a for a in range(3) if a != ax)))
+        ext += [lo + int(on[0]), lo + int(on[-1])]
+    return tuple(ext), int(sub.sum()), int(occ.sum())
+
+
+def median_cut_boxes(hist):
+    """hist int64 [32][32][32] -> list of boxes (r0, r1, g0, g1, b0, b1), inclusive, in box-number order."""
+    boxes = [_shrink(hist, (0, 31, 0, 31, 0, 31))]
+    while len(boxes) < 256:
+        best = -1
+        for k, (_, pop, ncell) in enumerate(boxes):
+            if ncell > 1 and (best < 0 or pop > boxes[best][1]):
+                best = k
+        if best < 0:
+            break
+        box, pop, _ = boxes[best]
+        ext = [box[1] - box[0], box[3] - box[2], box[5] - box[4]]
+        ax = ext.index(max(ext))                                   # first of R, G, B on a tie
+        lo, hi = box[2 * ax], box[2 * ax + 1]
+        sub = hist[box[0]:box[1] + 1, box[2]:box[3] + 1, box[4]:box[5] + 1]
+        cum = np.cumsum(sub.sum(axis=tuple(a for a in range(3) if a != ax)))
+        c = min(lo + int(np.argmax(2 * cum >= pop)), hi - 1)
+        low, high = list(box), list(box)
+        low[2 * ax + 1], high[2 * ax] = c, c + 1
+        boxes[best] = _shrink(hist, low)
+        boxes.append(_shrink(hist, high))
+    return [b for b, _, _ in boxes]
+
+
+def nearest(px, table):
+    """px int [P][3], table [256][3] -> index of the nearest entry, the lowest on a tie."""
+    t = table.astype(np.int32)
+    out = np.empty(len(px), np.uint8)
+    for o in range(0, len(px), 8192):
+        d = ((px[o:o + 8192, None, :].astype(np.int32) - t[None]) ** 2).sum(axis=2)
+        out[o:o + 8192] = np.argmin(d, axis=1)                      # argmin: the first minimum
+    return out
+
+
+def quantize(frame):
+    """uint8 H x W x 3 -> (table uint8 [256][3], idx uint8 [H][W])."""
+    frame = np.asarray(frame)
+    assert frame.dtype == np.uint8 and frame.ndim == 3 and frame.shape[2] == 3, "a frame is uint8 H x W x 3"
+    H, W, _ = frame.shape
+    px = frame.reshape(-1, 3).astype(np.int64)
+    table = np.zeros((256, 3), np.uint8)
+    uniq = np.unique(px[:, 0] << 16 | px[:, 1] << 8 | px[:, 2])
+    if len(uniq) <= 256:
+        table[:len(uniq)] = np.stack([uniq >> 16, (uniq >> 8) & 255, uniq & 255], axis=1)
+    else:
+        cell = (px[:, 0] >> 3) << 10 | (px[:, 1] >> 3) << 5 | (px[:, 2] >> 3)
+        hist = np.bincount(cell, minlength=32768).reshape(32, 32, 32).astype(np.int64)
+        boxes = median_cut_boxes(hist)
+        of_cell = np.zeros((32, 32, 32), np.int64)
+        for k, (r0, r1, g0, g1, b0, b1) in enumerate(boxes):
+            of_cell[r0:r1 + 1, g0:g1 + 1, b0:b1 + 1] = k
+        box = of_cell.reshape(-1)[cell]
+        cnt = np.bincount(box, minlength=256).astype(np.int64)
+        for ch in range(3):
+            s = np.zeros(256, np.int64)
+            np.add.at(s, box, px[:, ch])
+            table[:len(boxes), ch] = ((2 * s + cnt)[:len(boxes)] // (2 * cnt[:len(boxes)]))
+    return table, nearest(px, table).reshape(H, W)
+
+
+# ------------------------------------------------------------------------------------------------------------------ LZW
+def code_width(m):
+    """bits of the m-th code after a Clear (m >= 1)"""
+    return max(9, (256 + m).bit_length())
+
+
+class _Bits:
+    def __init__(self):
+        self.acc, self.n, self.out = 0, 0, bytearray()
+
+    def put(self, v, w):
+        self.acc |= v << self.n
+        self.n += w
+        while self.n >= 8:
+            self.out.append(self.acc & 255)
+            self.acc >>= 8
+            self.n -= 8
+
+    def done(self):
+        if self.n:
+            self.out.append(self.acc & 255)
+        return bytes(self.out)
+
+
+def lzw(idx, chunk=None, want_stats=False):
+    """index plane -> the code bytes of the frame (before the cut into sub-blocks).  With want_stats also a dict: "codes",
+    and under 512 / 1024 / 2048 the number of chunks that end exactly where the dictionary reaches that size, so that
+    the Clear or EOI behind them is one bit wider than their last code."""
+    chunk = CHUNK if chunk is None else chunk
+    assert 1 <= chunk <= 3838
+    px = np.asarray(idx, np.uint8).reshape(-1).tolist()
+    bw = _Bits()
+    stats = {"codes": 0, 512: 0, 1024: 0, 2048: 0}
+    bw.put(CLEAR, 9)
+    for o in range(0, len(px), chunk):
+        part = px[o:o + chunk]
+        d, nxt, m = {}, FIRST, 0
+        prefix = part[0]
+        for b in part[1:]:
+            key = prefix << 8 | b
+            c = d.get(key)
+            if c is not None:
+                prefix = c
+                continue
+            m += 1
+            bw.put(prefix, code_width(m))
+            d[key] = nxt
+            nxt += 1
+            prefix = b
+        m += 1
+        bw.put(prefix, code_width(m))
+        stats["codes"] += m
+        if 257 + m in stats:
+            stats[257 + m] += 1
+        bw.put(EOI if o + chunk >= len(px) else CLEAR, code_width(m + 1))
+    data = bw.done()
+    return (data, stats) if want_stats else data
+
+
+def lzw_unchunked_size(idx):
+    """bytes of the same coder under the standard policy: one Clear at the start, another only when the dictionary reaches
+    4096 entries.  The size yardstick of the chunked stream."""
+    px = np.asarray(idx, np.uint8).reshape(-1).tolist()
+    bits, d, nxt, m = 9, {}, FIRST, 0
+    prefix = px[0]
+    for b in px[1:]:
+        key = prefix << 8 | b
+        c = d.get(key)
+        if c is not None:
+            prefix = c
+            continue
+        m += 1
+        bits += min(12, code_width(m))
+        d[key] = nxt
+        nxt += 1
+        prefix = b
+        if nxt == 4096:
+            bits += 12                                             # Clear
+            d, nxt, m = {}, FIRST, 0
+    bits += min(12, code_width(m + 1)) + min(12, code_width(m + 2))
+    return (bits + 7) // 8
+
+
+def boundary_chunk(codes, chunk=None):
+    """A chunk of `chunk` indices that the coder turns into exactly `codes` codes (255, 767 and 1791 end where the
+    dictionary reaches 512, 1024 and 2048): a stretch in which no pair of neighbours repeats, one code per index, then a
+    constant run, which takes few."""
+    chunk = CHUNK if chunk is None else chunk
+    seq = np.concatenate([(np.arange(256) * s) & 255 for s in range(1, 64, 2)]).astype(np.uint8)   # odd strides: no pair twice
+
+    def made(a):
+        part = np.concatenate([seq[:a], np.full(chunk - a, 7, np.uint8)])
+        return part, lzw(part, chunk, True)[1]["codes"]
+    lo, hi = 0, min(codes, chunk)                                   # codes made grow by 0 or 1 with every index added to the stretch
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if made(mid)[1] < codes:
+            lo = mid + 1
+        else:
+            hi = mid
+    part, got = made(lo)
+    assert got == codes, "no chunk of %d indices makes %d codes" % (chunk, codes)
+    return part
+
+
+# ----------------------------------------------------------------------------------------------------------------- file
+def sub_blocks(data):
+    out = bytearray()
+    for o in range(0, len(data), 255):
+        part = data[o:o + 255]
+        out.append(len(part))
+        out += part
+    out.append(0)
+    return bytes(out)
+
+
+def frame_body(frame):
+    """image descriptor .. block terminator of one frame: what does not depend on the delay"""
+    H, W, _ = frame.shape
+    table, idx = quantize(frame)
+    return b"\x2c" + struct.pack("<HHHH", 0, 0, W, H) + b"\x87" + table.tobytes() + b"\x08" + sub_blocks(lzw(idx))
+
+
+def control(delay):
+    """the graphic control extension: disposal 0, no transparency"""
+    return b"\x21\xf9\x04\x00" + struct.pack("<H", delay) + b"\x00\x00"
+
+
+def assemble(bodies, W, H, delay):
+    """frame_body of every frame -> the file"""
+    return HEADER + struct.pack("<HH", W, H) + b"\x70\x00\x00" + NETSCAPE + b"".join(control(delay) + b for b in bodies) + b"\x3b"
+
+
+def encode(frames, delay):
+    """uint8 N x H x W x 3 -> one GIF file."""
+    frames = np.asarray(frames)
+    assert frames.dtype == np.uint8 and frames.ndim == 4 and frames.shape[3] == 3, "frames are uint8 N x H x W x 3"
+    N, H, W, _ = frames.shape
+    assert 1 <= N <= MAX_FRAMES and 1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE and 0 <= delay <= MAX_DELAY
+    return assemble([frame_body(f) for f in frames], W, H, delay)
+
+
+def _unlzw(data, npix):
+    """strict decoder of lzw()'s stream: -> (indices, number of Clear codes)"""
+    pos, out, clears = 0, [], 0
+
+    def get(w):
+        nonlocal pos
+        if pos + w > 8 * len(data):
+            raise GifError("code stream ends inside a code")
+        v = 0
+        for i in range(w):
+            v |= ((data[(pos + i) >> 3] >> ((pos + i) & 7)) & 1) << i
+        pos += w
+        return v
+    if get(9) != CLEAR:
+        raise GifError("no Clear at the start")
+    clears, m, prev, ent = 1, 0, None, {}
+    while True:
+        m += 1
+        c = get(code_width(m))
+        if c == CLEAR:
+            clears, m, prev, ent = clears + 1, 0, None, {}
+            continue
+        if c == EOI:
+            break
+        nxt = FIRST + len(ent)
+        if prev is None:
+            if c > 255:
+                raise GifError("first code after a Clear is %d" % c)
+            s = [c]
+        else:
+            if c < 256:
+                s = [c]
+            elif c in ent:
+                s = ent[c]
+            elif c == nxt:
+                s = prev + [prev[0]]
+            else:
+                raise GifError("code %d before it is defined" % c)
+            if nxt > 4095:
+                raise GifError("dictionary overflow")
+            ent[nxt] = prev + [s[0]]
+        out += s
+        prev = s
+    if len(out) != npix:
+        raise GifError("%d indices decoded, %d expected" % (len(out), npix))
+    if (pos + 7) // 8 != len(data) or (pos & 7 and data[-1] >> (pos & 7)):
+        raise GifError("bytes or bits after EOI")
+    return np.array(out, np.uint8), clears
+
+
+def read_gif(data):
+    """bytes of one file -> dict(size=(W, H), loop, delays, tables [N][256][3], frames [N][H][W] of indices, clears).
+    Every structural byte is checked; GifError for anything the encoder does not write."""
+    data = bytes(data)
+
+    def need(cond, what):
+        if not cond:
+            raise GifError(what)
+    need(data[:6] == HEADER, "bad signature")
+    need(len(data) >= 13 + 19 + 1, "truncated")
+    W, H = struct.unpack("<HH", data[6:10])
+    need(W >= 1 and H >= 1 and data[10:13] == b"\x70\x00\x00", "logical screen descriptor")
+    need(data[13:32] == NETSCAPE, "NETSCAPE2.0 extension with loop count 0")
+    pos, delays, tables, frames, clears = 32, [], [], [], []
+    while True:
+        need(pos < len(data), "no trailer")
+        if data[pos] == 0x3B:
+            break
+        need(data[pos:pos + 4] == b"\x21\xf9\x04\x00" and data[pos + 6:pos + 8] == b"\x00\x00", "graphic control extension at %d" % pos)
+        delays.append(struct.unpack("<H", data[pos + 4:pos + 6])[0])
+        pos += 8
+        need(data[pos:pos + 10] == b"\x2c" + struct.pack("<HHHH", 0, 0, W, H) + b"\x87", "image descriptor at %d" % pos)
+        pos += 10
+        need(pos + 769 <= len(data), "truncated colour table")
+        tables.append(np.frombuffer(data[pos:pos + 768], np.uint8).reshape(256, 3))
+        need(data[pos + 768] == 8, "minimum code size at %d" % (pos + 768))
+        pos += 769
+        body = bytearray()
+        while True:
+            need(pos < len(data), "truncated sub-blocks")
+            n = data[pos]
+            pos += 1
+            if n == 0:
+                break
+            need(not body or len(body) % 255 == 0, "a short sub-block that is not the last, before %d" % pos)
+            need(pos + n <= len(data), "sub-block runs past the end")
+            body += data[pos:pos + n]
+            pos += n
+        idx, ncl = _unlzw(bytes(body), W * H)
+        need(ncl == -(-W * H // CHUNK), "%d Clear codes, %d expected" % (ncl, -(-W * H // CHUNK)))
+        frames.append(idx.reshape(H, W))
+        clears.append(ncl)
+    need(pos == len(data) - 1, "bytes after the trailer")
+    need(len(frames) >= 1, "no frame")
+    return dict(size=(W, H), loop=0, delays=delays, tables=np.stack(tables), frames=np.stack(frames), clears=clears)

@@ -90,6 +90,8 @@ SIGNATURES = {
     "vf_jpeg_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp]),
     "vf_png_workspace_bytes": (i32, [i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_png_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
+    "vf_gif_workspace_bytes": (i32, [i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
+    "vf_gif_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_display_workspace_bytes": (i32, [i32] * 9 + [C.POINTER(sz)]),
     "vf_display_tensor": (i32, [vp, vp, i32, vp] + [i32] * 8 + [f64, i32, f64, i32, i32]),
     "vf_center_finish": (i32, [vp] * 6 + [i32] * 4),

@@ -239,6 +239,20 @@ def png_workspace_bytes(n, H, W, channels):
     return ws_b.value, out_b.value
 
 
+GIF_CHUNK = 3824     # pixels between two Clear codes of a frame's LZW stream (csrc/vf_gif.hip)
+
+
+def gif_workspace_bytes(clips, frames, H, W):
+    """(device workspace bytes, upper bound on the output bytes) of a GIF batch of `clips` clips of `frames` RGB frames of
+    H x W (vf_gif_workspace_bytes; host only, no GPU needed).  ValueError, naming the argument, for what the encoder does
+    not take: a side outside 1..16384, a clip outside 1..65535 frames, a batch outside 1..65535 clips."""
+    lib = _lib.load()
+    ws_b, out_b = C.c_size_t(), C.c_size_t()
+    if lib.vf_gif_workspace_bytes(int(clips), int(frames), int(H), int(W), C.byref(ws_b), C.byref(out_b)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return ws_b.value, out_b.value
+
+
 class HipBackend:
     name = "hip-gfx950"
 
@@ -892,6 +906,31 @@ class HipBackend:
         out = torch.empty(out_b, dtype=torch.uint8, device=self.device)
         offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
         self._c("vf_png_encode", _ptr(frames), kind, n, H, W, Cc, _ptr(ws), ws.numel(), _ptr(out), out.numel(), _ptr(offsets))
+        return out, offsets
+
+    # ---- GIF encode (vf_gif.hip)
+    def gif_encode(self, clips, delay):
+        """Encode a batch of clips of one geometry as animated GIF files on the device.  clips: device uint8
+        G x N x H x W x 3 (taken as they are) or float32 G x N x 3 x H x W (through image.savePNG's truncating byte rule
+        inside the kernels), contiguous; delay in centiseconds.  -> (buffer, offsets): file i is
+        buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8 tensor of the upper bound's size, offsets a device
+        int64[G + 1]; both are valid once the stream gets there."""
+        assert clips.dim() == 5 and clips.is_contiguous() and clips.device == self.device
+        if clips.dtype == torch.uint8:
+            kind, (g, n, H, W, Cc) = 1, clips.shape
+        else:
+            assert clips.dtype == torch.float32, "clips are uint8 G x N x H x W x 3 or float32 G x N x 3 x H x W"
+            kind, (g, n, Cc, H, W) = 0, clips.shape
+        if Cc != 3:
+            raise ValueError("gif_encode: %d channels (a GIF frame here is RGB, 3)" % Cc)
+        ws_b, out_b = gif_workspace_bytes(g, n, H, W)
+        ws = getattr(self, "_gif_ws", None)
+        if ws is None or ws.numel() < ws_b:
+            self._gif_ws = ws = None                   # the old one goes before the new one comes
+            self._gif_ws = ws = torch.empty(max(ws_b, 1 << 20), dtype=torch.uint8, device=self.device)
+        out = torch.empty(out_b, dtype=torch.uint8, device=self.device)
+        offsets = torch.empty(g + 1, dtype=torch.int64, device=self.device)
+        self._c("vf_gif_encode", _ptr(clips), kind, g, n, H, W, int(delay), _ptr(ws), ws.numel(), _ptr(out), out.numel(), _ptr(offsets))
         return out, offsets
 
     # ---- contact sheets (vf_display.hip, DESIGN.md 5.4)

@@ -124,6 +124,34 @@ def encode_png(frames):
     return [host[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
 
 
+# ------------------------------------------------------------------------------------------------- GIF
+def encode_gif(clips, delay=10):
+    """`convert -delay D frame_1.png ... clip.gif` of a batch of clips, encoded on the device in one call
+    (vf_gif_encode): a list of `bytes`, one whole animated GIF89a file per clip, looping forever, `delay` centiseconds a
+    frame.  clips: uint8 G x N x H x W x 3 (taken as they are) or float G x N x 3 x H x W (image.savePNG's rule, the
+    bytes `convert` would read from the PNGs); a 4-D input is one clip; host or device; RGB only.  Every frame carries
+    its own table of 256 colours: its own colours when it has at most 256 (lossless), else a median cut; no dithering
+    (DESIGN 5.5 has the rule, which is this project's own, not ImageMagick's).  A file's bytes depend on its frames and
+    the delay alone and are the same on every run.  One device-to-host copy brings the batch back."""
+    t = torch.as_tensor(clips)
+    if t.dim() == 4:
+        t = t.unsqueeze(0)
+    if t.dim() != 5:
+        raise ValueError("encode_gif: a tensor of %d dimensions; clips are uint8 G x N x H x W x 3 or float G x N x 3 x H x W "
+                         "(4-D: one clip)" % t.dim())
+    if int(delay) != delay or not 0 <= delay <= 65535:
+        raise ValueError("encode_gif: delay=%r is not a whole number of centiseconds from 0 to 65535" % (delay,))
+    if t.dtype != torch.uint8:
+        if not t.is_floating_point():
+            raise ValueError("encode_gif: clips of type %s; they are uint8 or float" % t.dtype)
+        t = t.float()
+    B = get_backend()
+    buf, offsets = B.gif_encode(B.from_host(t).contiguous(), int(delay))
+    offs = offsets.cpu().tolist()                     # synchronises; the files end at offs[-1]
+    host = buf[:offs[-1]].cpu().numpy().tobytes()
+    return [host[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
+
+
 # ---------------------------------------------------------------------------------------------- image.scale (DESIGN 5.1)
 def load_size(H, W, loadSize, scalef=None):
     """(height, width) that loadImage / loadContImages (data/donkey_folder.lua:40-62, datavid/donkey_folder.lua:84-102)

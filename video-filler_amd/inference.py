@@ -156,6 +156,42 @@ def save_frames(dirname, outImages=None, inpaintImages=None, fullImages=None, **
     return paths
 
 
+def save_gifs(name, outImages=None, inpaintImages=None, fullImages=None, delay=10, **named):
+    """test_vid_wholeim.lua:244-257 (and test_more_complex.lua:216-229): the `convert -delay 10 pred_1.png ...
+    pred_{predLen-1}.png name_result.gif` that ends the video drivers, and the same for inpaint_* -> name_inpaint.gif and
+    orig_* -> name_orig.gif, without the PNGs and without ImageMagick: all clips are encoded on the device in ONE call
+    (data.encode_gif) and the host only writes the files.  Tensors are predLen x 3 x H x W in [0,1] (image.savePNG's
+    truncating byte rule applies) or uint8 predLen x H x W x 3.  Like the reference's shell loop
+    (`for ((a=1; a<predLen; a++))`) a clip holds frames 1 .. predLen-1: the LAST frame is not in it.  With predLen < 2
+    that command has no input; here that is a ValueError.  Other clips go by keyword as name_<key>.gif:
+    test_vid.lua:140-147 (`convert -delay 5 pred_*.png result.gif`) is save_gifs(dir + "/result", pred=pred_image,
+    delay=5), which writes dir/result_pred.gif.  The parent directory is created.  Returns the paths, in the order
+    result, inpaint, orig, then the keywords'."""
+    import os
+    groups = [(p, t) for p, t in (("result", outImages), ("inpaint", inpaintImages), ("orig", fullImages)) if t is not None]
+    groups += list(named.items())
+    if not groups:
+        raise ValueError("save_gifs: nothing to save")
+    keys = [p for p, _ in groups]
+    if len(set(keys)) != len(keys):
+        raise ValueError("save_gifs: clip given twice (%s); one would overwrite the other" % ", ".join(keys))
+    ts = [t if torch.is_tensor(t) else torch.as_tensor(t) for _, t in groups]
+    if not all(t.dim() == 4 for t in ts) or len({(t.dtype, tuple(t.shape)) for t in ts}) != 1:
+        raise ValueError("save_gifs: the clips of one call are 4-D and share one type, length and frame size")
+    if ts[0].shape[0] < 2:
+        raise ValueError("save_gifs: predLen = %d; the clip holds frames 1 .. predLen-1, which is none" % ts[0].shape[0])
+    from .data import encode_gif
+    B = get_backend()
+    files = encode_gif(torch.stack([B.from_host(t)[:-1] for t in ts]), delay)
+    os.makedirs(os.path.dirname(os.path.abspath(name)), exist_ok=True)
+    paths = []
+    for key, data in zip(keys, files):
+        paths.append("%s_%s.gif" % (name, key))
+        with open(paths[-1], "wb") as fh:
+            fh.write(data)
+    return paths
+
+
 # --------------------------------------------------------------------------- test.lua / demo.lua and the sheets (DESIGN 5.4)
 def _check_display_args(x, padding, nrow):
     """toDisplayTensor's argument checks, on the host and before any backend exists: -> the tensor."""
