@@ -97,9 +97,12 @@ def quantize(frame):
     H, W, _ = frame.shape
     px = frame.reshape(-1, 3).astype(np.int64)
     table = np.zeros((256, 3), np.uint8)
-    uniq = np.unique(px[:, 0] << 16 | px[:, 1] << 8 | px[:, 2])
+    uniq, rank = np.unique(px[:, 0] << 16 | px[:, 1] << 8 | px[:, 2], return_inverse=True)
     if len(uniq) <= 256:
         table[:len(uniq)] = np.stack([uniq >> 16, (uniq >> 8) & 255, uniq & 255], axis=1)
+        # every pixel is in the table, at distance 0 from its own entry alone (the zero padding behind the colours can only
+        # repeat black, which then stands first): nearest() would return the colour's rank, found here without the search
+        return table, rank.reshape(H, W).astype(np.uint8)
     else:
         cell = (px[:, 0] >> 3) << 10 | (px[:, 1] >> 3) << 5 | (px[:, 2] >> 3)
         hist = np.bincount(cell, minlength=32768).reshape(32, 32, 32).astype(np.int64)

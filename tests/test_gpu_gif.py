@@ -106,6 +106,36 @@ def test_more_chunks_than_dictionaries_take_turns(hipb):
     assert f == gif_ref.assemble([body[i] for i in pick], W, H, 10)
 
 
+def bands(H, W):
+    """at most 256 colours (the reference's lossless path), in runs of several lengths: chunks of many different bit counts"""
+    yy, xx = np.mgrid[0:H, 0:W]
+    g = (((xx // 7) * 3 + (yy // 5) * 11 + (xx * yy) // 4096) & 255).astype(np.uint8)
+    return np.stack([g, 255 - g, g // 2], -1)
+
+
+@pytest.mark.parametrize("geom", [(1024, 956), (1024, 957)])
+def test_a_frame_of_256_and_of_257_chunks(hipb, geom):
+    """1024 x 956 pixels are exactly 256 chunks, one whole 256-wide round of the frame's bit-offset scan; 1024 x 957 are 257,
+    one chunk into the second round"""
+    H, W = geom
+    assert -(-H * W // gif_ref.CHUNK) == (256 if W == 956 else 257) and (W != 956 or H * W % gif_ref.CHUNK == 0)
+    fr = bands(H, W)
+    assert len(np.unique(fr.reshape(-1, 3), axis=0)) <= 256
+    (f,) = enc(fr[None])
+    assert f == gif_ref.encode(fr[None], 10)
+    assert enc(fr[None]) == [f]
+
+
+def test_257_clips_stand_where_the_sizes_before_them_say(hipb):
+    """257 clips of one 1 x 1 frame: clip 257 is the first of the second 256-wide round of the file-offset scan"""
+    k = np.arange(257)
+    clips = np.stack([k & 255, (k * 7) & 255, k >> 8], -1).astype(np.uint8).reshape(257, 1, 1, 1, 3)
+    files = enc(clips)
+    assert len(files) == 257 and enc(clips) == files
+    for c, f in zip(clips, files):
+        assert f == gif_ref.encode(c, 10)
+
+
 def test_refusals_name_the_argument(hipb):
     with pytest.raises(ValueError, match="16385"):
         enc(np.zeros((1, 1, 1, 16385, 3), np.uint8))

@@ -108,8 +108,10 @@ def synth(H, W, C):
     return np.stack(planes, -1).astype(np.uint8)
 
 
+# (256, 8191, 1) and (257, 8191, 1): rows of 8192 filtered bytes, so exactly 256 chunks, one whole 256-wide round of the frame's
+# chunk-offset scan, and 257, one chunk into the second round
 @pytest.mark.parametrize("shape", [(1, 1, 3), (1, 1, 1), (1, 300, 3), (300, 1, 3), (1, 9000, 1), (129, 131, 3), (128, 128, 1),
-                                   (384, 512, 3), (1024, 1024, 3)])
+                                   (384, 512, 3), (1024, 1024, 3), (256, 8191, 1), (257, 8191, 1)])
 def test_geometries(hipb, shape):
     from video_filler_amd.backend import PNG_CHUNK
     a = synth(*shape)
@@ -121,6 +123,20 @@ def test_geometries(hipb, shape):
     if shape[0] == 1024:
         assert len(idats) >= 300, "a stream several hundred chunks long"
     assert enc(a[None]) == files[:1]
+
+
+def test_257_files_of_one_batch_stand_where_the_sizes_before_them_say(hipb):
+    """257 frames of 1 x 1 x 1: file 257 is the first of the second 256-wide round of the file-offset scan"""
+    a = ((np.arange(257) * 37) & 255).astype(np.uint8).reshape(257, 1, 1, 1)
+    buf, offsets = hipb.png_encode(torch.from_numpy(a).cuda())
+    offs = offsets.cpu().tolist()
+    files = enc(a)
+    assert len(files) == 257 and enc(a) == files
+    assert offs == np.concatenate([[0], np.cumsum([len(f) for f in files])]).tolist()
+    assert buf[:offs[-1]].cpu().numpy().tobytes() == b"".join(files)
+    for i, f in enumerate(files):
+        check_file(f, a[i])
+    assert [files[255], files[256]] == enc(a[255:256]) + enc(a[256:])
 
 
 def test_determinism_over_repeats_and_batch_compositions(hipb):

@@ -225,6 +225,15 @@ def jpeg_inspect(data, walk=True):
     return d
 
 
+def _encoder_bytes(entry, *geometry):
+    """(workspace bytes, output bound) from a vf_*_workspace_bytes entry point; a refusal is a ValueError with its text."""
+    lib = _lib.load()
+    ws_b, out_b = C.c_size_t(), C.c_size_t()
+    if getattr(lib, entry)(*map(int, geometry), C.byref(ws_b), C.byref(out_b)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return ws_b.value, out_b.value
+
+
 PNG_CHUNK = 8192     # filtered bytes per deflate block and IDAT chunk (csrc/vf_png.hip)
 
 
@@ -232,11 +241,7 @@ def png_workspace_bytes(n, H, W, channels):
     """(device workspace bytes, upper bound on the output bytes) of a PNG batch of n frames of H x W x channels
     (vf_png_workspace_bytes; host only, no GPU needed).  ValueError, naming the geometry, for what the encoder does not
     take: channels other than 1 or 3, a side outside 1..16384."""
-    lib = _lib.load()
-    ws_b, out_b = C.c_size_t(), C.c_size_t()
-    if lib.vf_png_workspace_bytes(int(n), int(H), int(W), int(channels), C.byref(ws_b), C.byref(out_b)) != 0:
-        raise ValueError(lib.vf_last_error().decode())
-    return ws_b.value, out_b.value
+    return _encoder_bytes("vf_png_workspace_bytes", n, H, W, channels)
 
 
 GIF_CHUNK = 3824     # pixels between two Clear codes of a frame's LZW stream (csrc/vf_gif.hip)
@@ -246,11 +251,7 @@ def gif_workspace_bytes(clips, frames, H, W):
     """(device workspace bytes, upper bound on the output bytes) of a GIF batch of `clips` clips of `frames` RGB frames of
     H x W (vf_gif_workspace_bytes; host only, no GPU needed).  ValueError, naming the argument, for what the encoder does
     not take: a side outside 1..16384, a clip outside 1..65535 frames, a batch outside 1..65535 clips."""
-    lib = _lib.load()
-    ws_b, out_b = C.c_size_t(), C.c_size_t()
-    if lib.vf_gif_workspace_bytes(int(clips), int(frames), int(H), int(W), C.byref(ws_b), C.byref(out_b)) != 0:
-        raise ValueError(lib.vf_last_error().decode())
-    return ws_b.value, out_b.value
+    return _encoder_bytes("vf_gif_workspace_bytes", clips, frames, H, W)
 
 
 class HipBackend:
@@ -845,6 +846,17 @@ class HipBackend:
         self._c("vf_patch_array_prepare", _ptr(src), 1 if hwc else 0, _ptr(mask), _ptr(masked), _ptr(full), _ptr(maskout),
                 _ptr(total), H, W, height, width, fs, arr_h, arr_w, crop_w, crop_h, int(bool(flip)), mask_value)
 
+    def _scratch(self, name, nbytes):
+        """The device byte buffer of one codec stage (`name`), kept between calls and grown on demand, 1 MiB at least."""
+        attr = "_%s_ws" % name
+        ws = getattr(self, attr, None)
+        if ws is None or ws.numel() < nbytes:
+            ws = None                                  # the old one goes before the new one comes
+            setattr(self, attr, None)
+            ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=self.device)
+            setattr(self, attr, ws)
+        return ws
+
     # ---- baseline JPEG decode (vf_jpeg.hip, DESIGN.md 5.2)
     def jpeg_decode(self, files, channels=3, subseq_bytes=256, infos=None):
         """Decode a batch of supported JPEG files (bytes each) into one device uint8 buffer.  -> (out, offsets, status,
@@ -863,9 +875,7 @@ class HipBackend:
         ws_b, st_b = C.c_size_t(), C.c_size_t()
         _lib.check(self.lib.vf_jpeg_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), n, subseq_bytes, C.byref(ws_b),
                                                     C.byref(st_b)))
-        ws = getattr(self, "_jpeg_ws", None)
-        if ws is None or ws.numel() < ws_b.value:
-            self._jpeg_ws = ws = torch.empty(max(ws_b.value, 1 << 20), dtype=torch.uint8, device=self.device)
+        ws = self._scratch("jpeg", ws_b.value)
         # two pinned staging buffers, used in turn: packing this batch overlaps the device work of the one before, and
         # waits only for the batch before that (its upload has then left the buffer)
         if not hasattr(self, "_jpeg_stage"):
@@ -900,9 +910,7 @@ class HipBackend:
             assert frames.dtype == torch.float32, "frames are uint8 N x H x W x C or float32 N x C x H x W"
             kind, (n, Cc, H, W) = 0, frames.shape
         ws_b, out_b = png_workspace_bytes(n, H, W, Cc)
-        ws = getattr(self, "_png_ws", None)
-        if ws is None or ws.numel() < ws_b:
-            self._png_ws = ws = torch.empty(max(ws_b, 1 << 20), dtype=torch.uint8, device=self.device)
+        ws = self._scratch("png", ws_b)
         out = torch.empty(out_b, dtype=torch.uint8, device=self.device)
         offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
         self._c("vf_png_encode", _ptr(frames), kind, n, H, W, Cc, _ptr(ws), ws.numel(), _ptr(out), out.numel(), _ptr(offsets))
@@ -924,10 +932,7 @@ class HipBackend:
         if Cc != 3:
             raise ValueError("gif_encode: %d channels (a GIF frame here is RGB, 3)" % Cc)
         ws_b, out_b = gif_workspace_bytes(g, n, H, W)
-        ws = getattr(self, "_gif_ws", None)
-        if ws is None or ws.numel() < ws_b:
-            self._gif_ws = ws = None                   # the old one goes before the new one comes
-            self._gif_ws = ws = torch.empty(max(ws_b, 1 << 20), dtype=torch.uint8, device=self.device)
+        ws = self._scratch("gif", ws_b)
         out = torch.empty(out_b, dtype=torch.uint8, device=self.device)
         offsets = torch.empty(g + 1, dtype=torch.int64, device=self.device)
         self._c("vf_gif_encode", _ptr(clips), kind, g, n, H, W, int(delay), _ptr(ws), ws.numel(), _ptr(out), out.numel(), _ptr(offsets))

@@ -196,6 +196,17 @@ static inline int vf_ilog2(int v) {  // v must be a power of two
 static inline bool vf_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline int64_t vf_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline bool vf_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline size_t vf_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// Regions of a workspace one behind the other, each starting on a 256-byte boundary: take(bytes) -> the region's offset; `at` is
+// the size of everything taken so far
+struct VfCarve {
+  size_t at = 0;
+  size_t take(size_t bytes) {
+    const size_t o = at;
+    at += vf_up256(bytes);
+    return o;
+  }
+};
 #define VF_OOB 0x80000000u   // byte offset that is always out of range of a buffer descriptor (operands are < 2 GiB)
 
 // Descriptor tables of the one-launch-per-net kernels, built by the hosts (vf_net.hip; video-filler_amd/backend.py mirrors the

@@ -1,6 +1,6 @@
 // vf_gif.hip — batched animated-GIF encoder: clips of frames on the device in, whole GIF89a files out.
-//   k_gif_table   one block per frame: the 5-bit-per-channel histogram in LDS (bytes from float planar through image.savePNG's
-//                 truncating rule, or interleaved bytes), then either the frame's <= 256 colours in ascending order (an LDS hash
+//   k_gif_table   one block per frame: the 5-bit-per-channel histogram in LDS (bytes from float planar through vf_savepng_byte,
+//                 or interleaved bytes), then either the frame's <= 256 colours in ascending order (an LDS hash
 //                 set of the 24-bit colours, sorted by rank) or the median cut of tests/gif_ref.py: up to 255 sequential splits,
 //                 each a block-wide argmax, a marginal histogram and the extents of the two halves; the box means from a second
 //                 walk over the pixels.  Integer counts and sums only: nothing depends on the order of arrival.
@@ -11,6 +11,7 @@
 //                 byte gathers its bits from the one or two slots that cover it; sub-block lengths, headers, tables, trailers.
 // A Clear after every GIF_CHUNK pixels keeps the dictionary below 4096 entries, so chunks are independent and a frame's bytes
 // depend on that frame and the delay only.
+#include "vf_block.h"
 #include "vf_common.h"
 
 namespace {
@@ -44,12 +45,6 @@ struct GifArgs {
   long long npix, px_stride;
 };
 
-// image.savePNG on a float tensor: saturate to [0,1], times 255 in float32, truncate; NaN -> 0
-__device__ __forceinline__ unsigned gif_byte_of(float x) {
-  const float v = fminf(fmaxf(x, 0.f), 1.f);
-  return (unsigned)(int)(255.f * v);
-}
-
 template <int KIND>
 __device__ __forceinline__ unsigned gif_rgb(const GifArgs& a, long long f, long long p) {   // r << 16 | g << 8 | b
   if (KIND == 1) {
@@ -57,7 +52,7 @@ __device__ __forceinline__ unsigned gif_rgb(const GifArgs& a, long long f, long 
     return ((unsigned)s[0] << 16) | ((unsigned)s[1] << 8) | s[2];
   }
   const float* s = (const float*)a.src + f * 3 * a.npix + p;
-  return (gif_byte_of(s[0]) << 16) | (gif_byte_of(s[a.npix]) << 8) | gif_byte_of(s[2 * a.npix]);
+  return (vf_savepng_byte(s[0]) << 16) | (vf_savepng_byte(s[a.npix]) << 8) | vf_savepng_byte(s[2 * a.npix]);
 }
 
 __device__ __forceinline__ int gif_cell(unsigned rgb) { return (int)(((rgb >> 19) << 10) | (((rgb >> 11) & 31) << 5) | ((rgb >> 3) & 31)); }
@@ -382,22 +377,6 @@ __global__ __launch_bounds__(64) void k_gif_lzw(GifArgs a) {
 }
 
 // --------------------------------------------------------------------------------------------------------------- pack
-__device__ __forceinline__ unsigned long long gif_block_excl_scan(unsigned long long v, unsigned long long* s_w, unsigned long long& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;   // 256 threads
-  unsigned long long inc = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  __syncthreads();
-  if (lane == 63) s_w[wave] = inc;
-  __syncthreads();
-  unsigned long long base = 0;
-  for (int w = 0; w < wave; ++w) base += s_w[w];
-  total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-  return base + inc - v;
-}
-
 // one block per frame: the bits before every chunk, the frame's code bytes and its size in the file
 __global__ __launch_bounds__(256) void k_gif_frame_scan(GifArgs a) {
   __shared__ unsigned long long s_w[4];
@@ -407,7 +386,7 @@ __global__ __launch_bounds__(256) void k_gif_frame_scan(GifArgs a) {
   for (int base = 0; base < a.nchunks; base += 256) {
     const int k = base + threadIdx.x;
     unsigned long long total;
-    const unsigned long long e = gif_block_excl_scan(k < a.nchunks ? len[k] : 0u, s_w, total);
+    const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(k < a.nchunks ? len[k] : 0u, s_w, total);
     if (k < a.nchunks) a.bitoff[f * a.nchunks + k] = run + e;
     run += total;
   }
@@ -426,7 +405,7 @@ __global__ __launch_bounds__(256) void k_gif_offsets(GifArgs a) {
   for (long long base = 0; base < frames_all; base += 256) {
     const long long f = base + threadIdx.x;
     unsigned long long total;
-    const unsigned long long e = gif_block_excl_scan(f < frames_all ? a.fpos[f] : 0ull, s_w, total);
+    const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(f < frames_all ? a.fpos[f] : 0ull, s_w, total);
     if (f < frames_all) {
       const long long c = f / a.frames;
       const unsigned long long file = run + e + (unsigned long long)c * (GIF_FILE_HEAD + 1);   // earlier files' headers and trailers
@@ -492,7 +471,7 @@ __global__ __launch_bounds__(256) void k_gif_pack(GifArgs a) {
 
 struct GifPlan {
   long long npix, px_stride, nchunks, frames_all, chunks_all, lanes;
-  size_t o_table, o_dict, o_slots, o_len, o_off, o_fpos, o_dbytes, ws_bytes, out_bytes;
+  size_t o_idx, o_table, o_dict, o_slots, o_len, o_off, o_fpos, o_dbytes, ws_bytes, out_bytes;
 };
 
 int gif_plan(const char* who, int clips, int frames, int H, int W, GifPlan* p) {
@@ -507,15 +486,16 @@ int gif_plan(const char* who, int clips, int frames, int H, int W, GifPlan* p) {
              clips, frames, H, W);
   p->chunks_all = p->frames_all * p->nchunks;
   p->lanes = (p->chunks_all < GIF_LANE_CAP ? p->chunks_all + 63 : GIF_LANE_CAP) / 64 * 64;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  p->o_table = up((size_t)p->frames_all * p->px_stride);
-  p->o_dict = p->o_table + up((size_t)p->frames_all * 768);
-  p->o_slots = p->o_dict + up((size_t)p->lanes * GIF_DICT * 4);
-  p->o_len = p->o_slots + up((size_t)p->chunks_all * GIF_SLOT_WORDS * 4);
-  p->o_off = p->o_len + up((size_t)p->chunks_all * 4);
-  p->o_fpos = p->o_off + up((size_t)p->chunks_all * 8);
-  p->o_dbytes = p->o_fpos + up((size_t)p->frames_all * 8);
-  p->ws_bytes = p->o_dbytes + up((size_t)p->frames_all * 8);
+  VfCarve ws;
+  p->o_idx = ws.take((size_t)p->frames_all * p->px_stride);
+  p->o_table = ws.take((size_t)p->frames_all * 768);
+  p->o_dict = ws.take((size_t)p->lanes * GIF_DICT * 4);
+  p->o_slots = ws.take((size_t)p->chunks_all * GIF_SLOT_WORDS * 4);
+  p->o_len = ws.take((size_t)p->chunks_all * 4);
+  p->o_off = ws.take((size_t)p->chunks_all * 8);
+  p->o_fpos = ws.take((size_t)p->frames_all * 8);
+  p->o_dbytes = ws.take((size_t)p->frames_all * 8);
+  p->ws_bytes = ws.at;
   // every pixel a 12-bit code of its own, a 12-bit Clear or EOI behind every chunk, the leading Clear
   const size_t d = ((size_t)p->npix * 12 + (size_t)p->nchunks * 12 + 9 + 7) / 8;
   p->out_bytes = (size_t)clips * (GIF_FILE_HEAD + 1 + (size_t)frames * (GIF_FRAME_HEAD + d + (d + 254) / 255 + 1));
@@ -545,7 +525,7 @@ VF_API int vf_gif_encode(vf_ctx* ctx, const void* src, int kind, int clips, int 
   GifArgs a;
   char* w = (char*)ws;
   a.src = src;
-  a.idx = (unsigned char*)w;
+  a.idx = (unsigned char*)(w + p.o_idx);
   a.table = (unsigned char*)(w + p.o_table);
   a.dict = (unsigned*)(w + p.o_dict);
   a.slots = (unsigned*)(w + p.o_slots);

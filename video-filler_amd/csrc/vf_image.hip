@@ -11,6 +11,7 @@
 // reads, so the scaled image is never materialised.  The arithmetic is the restatement's float32, one rounding per
 // operation in its order (the library builds with -ffp-contract=off; IEEE division): results are bit-identical to
 // tests/image_ref.py.  Threads run along the output row, so stores are coalesced; the sources stay in L2.
+#include "vf_block.h"
 #include "vf_common.h"
 
 namespace {
@@ -145,7 +146,9 @@ ScalePlace plain(const void* src, void* dst, int N, int C, int H, int W, int hei
 __global__ void __launch_bounds__(256) k_crop_stats(const float* __restrict__ clip, const unsigned char* __restrict__ mask, int C, int iH,
                                                     int iW, int fs, int w1, int h1, double* __restrict__ out) {
   __shared__ double ssum[256];
-  __shared__ int smax[256];
+  __shared__ int smax;
+  if (threadIdx.x == 0) smax = 0;
+  __syncthreads();
   double s = 0.0;
   int m = 0;
   const int64_t n = (int64_t)C * fs * fs;
@@ -156,19 +159,11 @@ __global__ void __launch_bounds__(256) k_crop_stats(const float* __restrict__ cl
     s += (double)clip[((int64_t)c * iH + h1 + y) * iW + w1 + x];
     if (mask && c == 0) m = max(m, (int)mask[(int64_t)(h1 + y) * iW + w1 + x]);
   }
-  ssum[threadIdx.x] = s;
-  smax[threadIdx.x] = m;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) {
-      ssum[threadIdx.x] += ssum[threadIdx.x + off];
-      smax[threadIdx.x] = max(smax[threadIdx.x], smax[threadIdx.x + off]);
-    }
-    __syncthreads();
-  }
+  atomicMax(&smax, m);                        // a max does not depend on the order; the sum's barriers stand behind it
+  const double total = vf_block_sum_f64<256>(s, ssum);
   if (threadIdx.x == 0) {
-    out[0] = ssum[0];
-    out[1] = (double)smax[0];
+    out[0] = total;
+    out[1] = (double)smax;
   }
 }
 
@@ -188,7 +183,7 @@ struct PatchArray {
 // of window p, so neighbouring threads store neighbouring 12-byte pieces of the fs x fs x 3P record array, and the (at most) four
 // threads of a pixel that own an output window store its 48-byte records of `full` and `maskout`.  The scaled pixel is evaluated
 // once per window.  Window 0 of the unmasked input, before the [-1,1] map, is the dark test's patch (:188-189): its sum is
-// accumulated in double, per thread in item order, then over the block in a fixed tree — the same bits on every run.
+// accumulated in double, per thread in item order, then over the block by vf_block_sum_f64 — the same bits on every run.
 template <int SRC>
 __global__ void __launch_bounds__(256) k_patch_array(const PatchArray p) {
   __shared__ double ssum[256];
@@ -235,13 +230,8 @@ __global__ void __launch_bounds__(256) k_patch_array(const PatchArray p) {
       }
     }
   }
-  ssum[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) ssum[threadIdx.x] += ssum[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) p.part[y] = ssum[0];
+  const double total = vf_block_sum_f64<256>(s, ssum);
+  if (threadIdx.x == 0) p.part[y] = total;
 }
 
 // the n row partials of k_patch_array into out[0]: one block, fixed order
@@ -249,13 +239,8 @@ __global__ void __launch_bounds__(256) k_sum_partials(const double* __restrict__
   __shared__ double ssum[256];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-  ssum[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) ssum[threadIdx.x] += ssum[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = ssum[0];
+  const double total = vf_block_sum_f64<256>(s, ssum);
+  if (threadIdx.x == 0) out[0] = total;
 }
 
 }  // namespace

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "vf_block.h"
 #include "vf_common.h"
 
 namespace {
@@ -210,23 +211,6 @@ __host__ __device__ int decode_lane(const JpgImage& im, const JpgHuff* tabs, Bit
   }
 }
 
-// block-wide exclusive scan of one int per thread (kHuffThreads threads); returns the prefix, `total` the sum
-__device__ int block_scan(int v, int* sh, int& total) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 1; o < kHuffThreads; o <<= 1) {
-    const int a = t >= o ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += a;
-    __syncthreads();
-  }
-  total = sh[kHuffThreads - 1];
-  const int r = sh[t] - v;
-  __syncthreads();
-  return r;
-}
-
 // one wave per chunk: keep every byte but the 0x00 after a 0xFF (stuffing)
 __global__ void k_jpeg_unstuff(const JpgBatch B) {
   const int lane = threadIdx.x & 63;
@@ -254,8 +238,7 @@ __global__ void k_jpeg_unstuff(const JpgBatch B) {
 // one block per restart segment
 __global__ __launch_bounds__(kHuffThreads) void k_jpeg_huffman(const JpgBatch B) {
   __shared__ JpgHuff tabs[4];
-  __shared__ int sh[kHuffThreads];
-  __shared__ int sh3[3][kHuffThreads];
+  __shared__ int s_w[kHuffThreads / 64];                  // wave totals of the block scans
   __shared__ int changed;
   const int t = threadIdx.x;
   const int s = blockIdx.x;
@@ -325,7 +308,7 @@ __global__ __launch_bounds__(kHuffThreads) void k_jpeg_huffman(const JpgBatch B)
       const int i = c + t;
       const int v = i < nsub ? Nb[i] : 0;
       int tot;
-      const int pre = block_scan(v, sh, tot);
+      const int pre = vf_block_excl_scan<int, kHuffThreads>(v, s_w, tot);
       if (i < nsub) Nb[i] = carry + pre;
       carry += tot;
     }
@@ -357,18 +340,13 @@ __global__ __launch_bounds__(kHuffThreads) void k_jpeg_huffman(const JpgBatch B)
     int sum[3] = {0, 0, 0};
     if (m < sg.nmcu)
       for (int b = 0; b < im.bpm; ++b) sum[im.bcomp[b]] += coef[((int64_t)m * im.bpm + b) * 64];
-    for (int ci = 0; ci < 3; ++ci) sh3[ci][t] = sum[ci];
-    __syncthreads();
-    for (int o = 1; o < kHuffThreads; o <<= 1) {
-      int a[3];
-      for (int ci = 0; ci < 3; ++ci) a[ci] = t >= o ? sh3[ci][t - o] : 0;
-      __syncthreads();
-      for (int ci = 0; ci < 3; ++ci) sh3[ci][t] += a[ci];
-      __syncthreads();
+    int run[3];
+    for (int ci = 0; ci < 3; ++ci) {
+      int tot;
+      run[ci] = carry[ci] + vf_block_excl_scan<int, kHuffThreads>(sum[ci], s_w, tot);
+      carry[ci] += tot;
     }
     if (m < sg.nmcu) {
-      int run[3];
-      for (int ci = 0; ci < 3; ++ci) run[ci] = carry[ci] + sh3[ci][t] - sum[ci];
       for (int b = 0; b < im.bpm; ++b) {
         int16_t* dc = coef + ((int64_t)m * im.bpm + b) * 64;
         const int ci = im.bcomp[b];
@@ -376,8 +354,6 @@ __global__ __launch_bounds__(kHuffThreads) void k_jpeg_huffman(const JpgBatch B)
         *dc = (int16_t)run[ci];
       }
     }
-    for (int ci = 0; ci < 3; ++ci) carry[ci] += sh3[ci][kHuffThreads - 1];
-    __syncthreads();
   }
 }
 
@@ -898,7 +874,6 @@ struct JpgPlan {
   size_t o_bits = 0, o_E = 0, o_X = 0, o_N = 0, o_D = 0, o_coef = 0, o_planes = 0, ws = 0;
 };
 
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int64_t seg_bits_bytes(int64_t len) { return ((len + 15) & ~(int64_t)15) + 16; }   // BitWin reads up to 11 bytes past the end
 
 // walk: the exact sizes of a full parse (vf_jpeg_decode); else upper bounds from the headers alone
@@ -927,7 +902,7 @@ int jpg_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes, Jpg
     L.max_blocks = std::max(L.max_blocks, mcux * mcuy * bpm);
     L.max_pix = std::max(L.max_pix, (int64_t)P.W * P.H);
     L.plane_bytes += mcux * mcuy * 64 * bpm;
-    L.plane_bytes = (int64_t)al((size_t)L.plane_bytes);
+    L.plane_bytes = (int64_t)vf_up256((size_t)L.plane_bytes);
     if (walk) {
       L.nseg += (int64_t)P.segs.size();
       for (const auto& s : P.segs) {
@@ -935,30 +910,31 @@ int jpg_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes, Jpg
         L.bits_bytes += seg_bits_bytes(s.len);
         L.nchunk += vf_cdiv(s.end - s.begin, kChunk);
       }
-      L.scan_bytes += (int64_t)al((size_t)(P.scan_end - P.scan_begin) + 8);
+      L.scan_bytes += (int64_t)vf_up256((size_t)(P.scan_end - P.scan_begin) + 8);
     } else {
       const int64_t nseg = P.ri > 0 ? vf_cdiv(mcux * mcuy, P.ri) : 1, sb = offs[i + 1] - offs[i] - P.scan_begin;
       L.nseg += nseg;
       L.nsub += vf_cdiv(sb, sub_bytes) + nseg;
       L.bits_bytes += sb + 32 * nseg;
       L.nchunk += vf_cdiv(sb, kChunk) + nseg;
-      L.scan_bytes += (int64_t)al((size_t)sb + 8);
+      L.scan_bytes += (int64_t)vf_up256((size_t)sb + 8);
     }
   }
-  L.o_img = 0;
-  L.o_seg = al(L.o_img + sizeof(JpgImage) * n);
-  L.o_chunk = al(L.o_seg + sizeof(JpgSeg) * L.nseg);
-  L.o_huff = al(L.o_chunk + sizeof(JpgChunk) * L.nchunk);
-  L.o_scan = al(L.o_huff + sizeof(JpgHuff) * 4 * n);
-  L.stage = al(L.o_scan + L.scan_bytes);
-  L.o_bits = L.stage;
-  L.o_E = al(L.o_bits + L.bits_bytes);
-  L.o_X = al(L.o_E + 8 * L.nsub);
-  L.o_N = al(L.o_X + 8 * L.nsub);
-  L.o_D = al(L.o_N + 4 * L.nsub);
-  L.o_coef = al(L.o_D + L.nsub);
-  L.o_planes = al(L.o_coef + 128 * L.nblk);
-  L.ws = al(L.o_planes + L.plane_bytes);
+  VfCarve ws;
+  L.o_img = ws.take(sizeof(JpgImage) * n);
+  L.o_seg = ws.take(sizeof(JpgSeg) * L.nseg);
+  L.o_chunk = ws.take(sizeof(JpgChunk) * L.nchunk);
+  L.o_huff = ws.take(sizeof(JpgHuff) * 4 * n);
+  L.o_scan = ws.take((size_t)L.scan_bytes);
+  L.stage = ws.at;
+  L.o_bits = ws.take((size_t)L.bits_bytes);
+  L.o_E = ws.take(8 * (size_t)L.nsub);
+  L.o_X = ws.take(8 * (size_t)L.nsub);
+  L.o_N = ws.take(4 * (size_t)L.nsub);
+  L.o_D = ws.take((size_t)L.nsub);
+  L.o_coef = ws.take(128 * (size_t)L.nblk);
+  L.o_planes = ws.take((size_t)L.plane_bytes);
+  L.ws = ws.at;
   return 0;
 }
 
@@ -1015,7 +991,7 @@ void jpg_pack(const uint8_t* data, const int64_t* offs, int n, int channels, int
       plane += (int64_t)im.pw[c] * im.ph[c];
       for (int k = 0; k < 64; ++k) im.q[c][k] = P.qt[P.tq[c]][k];
     }
-    plane = (int64_t)al((size_t)plane);
+    plane = (int64_t)vf_up256((size_t)plane);
     im.out_off = out_offs[i];
     for (int t = 0; t < 2; ++t) {
       build_huff(P.hdc[t], huffs[4 * i + t]);
@@ -1023,7 +999,7 @@ void jpg_pack(const uint8_t* data, const int64_t* offs, int n, int channels, int
     }
     const int64_t nbytes = P.scan_end - P.scan_begin;
     memcpy(scan + sc, d + P.scan_begin, (size_t)nbytes);
-    memset(scan + sc + nbytes, 0, al((size_t)nbytes + 8) - (size_t)nbytes);
+    memset(scan + sc + nbytes, 0, vf_up256((size_t)nbytes + 8) - (size_t)nbytes);
     const int64_t nmcu = (int64_t)im.mcux * im.mcuy;
     for (size_t k = 0; k < P.segs.size(); ++k, ++si) {
       const auto& s = P.segs[k];
@@ -1054,7 +1030,7 @@ void jpg_pack(const uint8_t* data, const int64_t* offs, int n, int channels, int
       g.sub0 = sub;
       sub += g.nsub;
     }
-    sc += (int64_t)al((size_t)nbytes + 8);
+    sc += (int64_t)vf_up256((size_t)nbytes + 8);
   }
 }
 

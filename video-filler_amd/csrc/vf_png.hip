@@ -1,11 +1,12 @@
 // vf_png.hip — batched PNG encoder: frames on the device in, whole PNG files out.
-//   k_png_filter    one block per row: the row's bytes (from float planar through image.savePNG's truncating byte rule, or from
-//                   interleaved bytes), the five PNG filters, libpng's minimum-sum-of-absolute-values choice, the filtered row.
+//   k_png_filter    one block per row: the row's bytes (from float planar through vf_savepng_byte, or from interleaved bytes),
+//                   the five PNG filters, libpng's minimum-sum-of-absolute-values choice, the filtered row.
 //   k_png_deflate   one block per PNG_CHUNK bytes of a frame's filtered stream: LZ77 matches from an LDS hash table (resolved by
 //                   position, so the result does not depend on which lane gets there first), a greedy parse, dynamic Huffman
 //                   codes, the bits, or a stored block if that is not smaller; the chunk's IDAT with its CRC-32, its Adler sums.
 //   k_png_frame_scan / k_png_offsets / k_png_pack   chunk and file offsets, the Adler-32 of every frame, the files back to back.
 // No window crosses a chunk, so chunks are independent and a file's bytes depend on its own frame only.
+#include "vf_block.h"
 #include "vf_common.h"
 
 namespace {
@@ -34,17 +35,11 @@ struct PngArgs {
 };
 
 // ------------------------------------------------------------------------------------------------------------- filter
-// image.savePNG on a float tensor: saturate to [0,1], times 255 in float32, then libpng's C cast, which truncates; NaN -> 0
-__device__ __forceinline__ int png_byte_of(float x) {
-  const float v = fminf(fmaxf(x, 0.f), 1.f);
-  return (int)(255.f * v);
-}
-
 template <int KIND>
 __device__ __forceinline__ int png_px(const PngArgs& a, long long f, int y, int i) {
   if (KIND == 1) return ((const unsigned char*)a.src)[(f * a.H + y) * (long long)a.rb + i];
   const int x = a.C == 3 ? i / 3 : i, c = a.C == 3 ? i - 3 * x : 0;
-  return png_byte_of(((const float*)a.src)[((f * a.C + c) * a.H + y) * (long long)a.W + x]);
+  return (int)vf_savepng_byte(((const float*)a.src)[((f * a.C + c) * a.H + y) * (long long)a.W + x]);
 }
 
 __device__ __forceinline__ int png_paeth(int a, int b, int c) {
@@ -490,16 +485,8 @@ __global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
       mybits += s_len[s_data[p]];
     }
   }
-  unsigned inc = mybits;                               // inclusive scan over the block
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) s_red[wave] = inc;
-  __syncthreads();
-  unsigned wbase = 0;
-  for (int w = 0; w < wave; ++w) wbase += s_red[w];
-  const unsigned tok_bits = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+  unsigned tok_bits;
+  const unsigned tok_at = vf_block_excl_scan<unsigned, 256>(mybits, s_red, tok_bits);
   const unsigned hdr_bits = s_bits[0];
   const unsigned body_bits = hdr_bits + tok_bits + s_len[256] + (last ? 0u : 3u);   // + the empty stored block's header
   const unsigned body_bytes = (body_bits + 7) >> 3;
@@ -510,7 +497,7 @@ __global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
   unsigned char* dat = slot + 8 + zh;
   unsigned dlen;
   if (coded) {
-    unsigned bp = hdr_bits + wbase + inc - mybits;
+    unsigned bp = hdr_bits + tok_at;
     for (int p = p0; p < p0 + PNG_CHUNK / 256 && p < n; ++p) {
       const unsigned m = s_match[p];
       if (!(m & 0x80000000u)) continue;
@@ -595,22 +582,6 @@ __global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
 }
 
 // --------------------------------------------------------------------------------------------------------------- pack
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned* s_w, unsigned& total) {   // 256 threads
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned inc = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  __syncthreads();
-  if (lane == 63) s_w[wave] = inc;
-  __syncthreads();
-  unsigned base = 0;
-  for (int w = 0; w < wave; ++w) base += s_w[w];
-  total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-  return base + inc - v;
-}
-
 constexpr int PNG_HEAD = 8 + 25, PNG_TAIL = 12;   // signature + IHDR; IEND
 
 // one block per frame: where each IDAT goes, the frame's Adler-32, the file's size (offsets[f + 1], summed by k_png_offsets)
@@ -623,7 +594,7 @@ __global__ __launch_bounds__(256) void k_png_frame_scan(PngArgs a) {
     const int k = base + threadIdx.x;
     const unsigned v = k < a.nchunks ? 12u + meta[4 * k] + (k == a.nchunks - 1 ? 4u : 0u) : 0u;
     unsigned total;
-    const unsigned e = block_excl_scan(v, s_w, total);
+    const unsigned e = vf_block_excl_scan<unsigned, 256>(v, s_w, total);
     if (k < a.nchunks) a.chunk_off[f * a.nchunks + k] = run + e;
     run += total;
   }
@@ -657,24 +628,16 @@ __global__ __launch_bounds__(256) void k_png_frame_scan(PngArgs a) {
 
 // one block: offsets[f] = sum of the sizes before file f (in: sizes at [f + 1])
 __global__ __launch_bounds__(256) void k_png_offsets(int64_t* offsets, int n) {
-  __shared__ unsigned long long s_v[256];
-  __shared__ unsigned long long s_run;
-  if (threadIdx.x == 0) { s_run = 0; offsets[0] = 0; }
-  __syncthreads();
+  __shared__ unsigned long long s_w[4];
+  if (threadIdx.x == 0) offsets[0] = 0;
+  unsigned long long run = 0;
   for (int base = 0; base < n; base += 256) {
     const int f = base + threadIdx.x;
-    s_v[threadIdx.x] = f < n ? (unsigned long long)offsets[f + 1] : 0ull;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-      const unsigned long long t = threadIdx.x >= o ? s_v[threadIdx.x - o] : 0ull;
-      __syncthreads();
-      s_v[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (f < n) offsets[f + 1] = (int64_t)(s_run + s_v[threadIdx.x]);
-    __syncthreads();
-    if (threadIdx.x == 0) s_run += s_v[255];
-    __syncthreads();
+    const unsigned long long v = f < n ? (unsigned long long)offsets[f + 1] : 0ull;
+    unsigned long long total;
+    const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(v, s_w, total);
+    if (f < n) offsets[f + 1] = (int64_t)(run + e + v);
+    run += total;
   }
 }
 
@@ -720,7 +683,7 @@ __global__ __launch_bounds__(256) void k_png_pack(PngArgs a) {
 
 struct PngPlan {
   long long rb, stream_len, nchunks;
-  size_t o_slots, o_meta, o_off, o_adler, ws_bytes, out_bytes;
+  size_t o_stream, o_slots, o_meta, o_off, o_adler, ws_bytes, out_bytes;
 };
 
 int png_plan(const char* who, int n, int H, int W, int C, PngPlan* p) {
@@ -730,13 +693,14 @@ int png_plan(const char* who, int n, int H, int W, int C, PngPlan* p) {
   p->rb = (long long)W * C;
   p->stream_len = (long long)H * (p->rb + 1);
   p->nchunks = vf_cdiv(p->stream_len, PNG_CHUNK);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t chunks = (size_t)n * p->nchunks;
-  p->o_slots = up((size_t)n * p->stream_len);
-  p->o_meta = p->o_slots + up(chunks * PNG_SLOT);
-  p->o_off = p->o_meta + up(chunks * 16);
-  p->o_adler = p->o_off + up(chunks * 4);
-  p->ws_bytes = p->o_adler + up((size_t)n * 4);
+  VfCarve ws;
+  p->o_stream = ws.take((size_t)n * p->stream_len);
+  p->o_slots = ws.take(chunks * PNG_SLOT);
+  p->o_meta = ws.take(chunks * 16);
+  p->o_off = ws.take(chunks * 4);
+  p->o_adler = ws.take((size_t)n * 4);
+  p->ws_bytes = ws.at;
   // every chunk stored: 5 bytes of block header and 12 of IDAT framing each; zlib header and Adler-32; signature, IHDR, IEND
   p->out_bytes = (size_t)n * ((size_t)p->stream_len + (size_t)p->nchunks * 17 + 6 + PNG_HEAD + PNG_TAIL);
   return 0;
@@ -763,7 +727,7 @@ VF_API int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, i
              p.out_bytes);
   PngArgs a;
   a.src = src;
-  a.stream = (unsigned char*)ws;
+  a.stream = (unsigned char*)ws + p.o_stream;
   a.slots = (unsigned char*)ws + p.o_slots;
   a.meta = (unsigned*)((char*)ws + p.o_meta);
   a.chunk_off = (unsigned*)((char*)ws + p.o_off);

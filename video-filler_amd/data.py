@@ -105,6 +105,14 @@ def decode_jpeg(items, channels=3, stack=False, fallback=None, subseq_bytes=256)
     return torch.stack(out)
 
 
+def _files_from(buf, offsets):
+    """The files of an encoder's (device buffer, device offsets) as a list of `bytes`: one offsets read, which synchronises,
+    and one device-to-host copy of the bytes in use (the files end at offsets[-1])."""
+    offs = offsets.cpu().tolist()
+    host = buf[:offs[-1]].cpu().numpy().tobytes()
+    return [host[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
+
+
 # ------------------------------------------------------------------------------------------------- PNG (DESIGN 5.3)
 def encode_png(frames):
     """image.save of a batch of frames as PNG, encoded on the device in one call (vf_png_encode): a list of `bytes`, one
@@ -118,10 +126,7 @@ def encode_png(frames):
     if t.dtype != torch.uint8:
         assert t.is_floating_point(), "frames are uint8 or float"
         t = t.float()
-    buf, offsets = B.png_encode(B.from_host(t).contiguous())
-    offs = offsets.cpu().tolist()                     # synchronises; the files end at offs[-1]
-    host = buf[:offs[-1]].cpu().numpy().tobytes()
-    return [host[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
+    return _files_from(*B.png_encode(B.from_host(t).contiguous()))
 
 
 # ------------------------------------------------------------------------------------------------- GIF
@@ -146,10 +151,7 @@ def encode_gif(clips, delay=10):
             raise ValueError("encode_gif: clips of type %s; they are uint8 or float" % t.dtype)
         t = t.float()
     B = get_backend()
-    buf, offsets = B.gif_encode(B.from_host(t).contiguous(), int(delay))
-    offs = offsets.cpu().tolist()                     # synchronises; the files end at offs[-1]
-    host = buf[:offs[-1]].cpu().numpy().tobytes()
-    return [host[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
+    return _files_from(*B.gif_encode(B.from_host(t).contiguous(), int(delay)))
 
 
 # ---------------------------------------------------------------------------------------------- image.scale

@@ -125,6 +125,14 @@ class WholeImageInpainter:
         return outImages, inpaint, fullv.view(predLen, nc, H, W)
 
 
+def _write_files(paths, blobs):
+    """One file per (path, bytes) pair -> the paths."""
+    for path, blob in zip(paths, blobs):
+        with open(path, "wb") as fh:
+            fh.write(blob)
+    return paths
+
+
 def save_frames(dirname, outImages=None, inpaintImages=None, fullImages=None, **named):
     """test_vid_wholeim.lua:226-242 (and test_more_complex.lua:200-214): `image.save` of every frame of the three results
     of WholeImageInpainter as dirname/pred_%d.png, inpaint_%d.png and orig_%d.png, numbered from 1.  The directory is
@@ -144,16 +152,8 @@ def save_frames(dirname, outImages=None, inpaintImages=None, fullImages=None, **
     assert all(t.dim() == 4 for t in ts) and len({(t.dtype, tuple(t.shape[1:])) for t in ts}) == 1, \
         "save_frames: the tensors of one call share one type and one frame size"
     os.makedirs(dirname, exist_ok=True)
-    files = encode_png(torch.cat(ts, 0))
-    paths, k = [], 0
-    for (prefix, _), t in zip(groups, ts):
-        for i in range(t.shape[0]):
-            path = os.path.join(dirname, "%s_%d.png" % (prefix, i + 1))
-            with open(path, "wb") as fh:
-                fh.write(files[k])
-            k += 1
-            paths.append(path)
-    return paths
+    paths = [os.path.join(dirname, "%s_%d.png" % (prefix, i + 1)) for (prefix, _), t in zip(groups, ts) for i in range(t.shape[0])]
+    return _write_files(paths, encode_png(torch.cat(ts, 0)))
 
 
 def save_gifs(name, outImages=None, inpaintImages=None, fullImages=None, delay=10, **named):
@@ -184,12 +184,7 @@ def save_gifs(name, outImages=None, inpaintImages=None, fullImages=None, delay=1
     B = get_backend()
     files = encode_gif(torch.stack([B.from_host(t)[:-1] for t in ts]), delay)
     os.makedirs(os.path.dirname(os.path.abspath(name)), exist_ok=True)
-    paths = []
-    for key, data in zip(keys, files):
-        paths.append("%s_%s.gif" % (name, key))
-        with open(paths[-1], "wb") as fh:
-            fh.write(data)
-    return paths
+    return _write_files(["%s_%s.gif" % (name, key) for key in keys], files)
 
 
 # --------------------------------------------------------------------------- test.lua / demo.lua and the sheets
