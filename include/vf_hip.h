@@ -439,6 +439,46 @@ int vf_jpeg_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, 
                    const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
                    int32_t* status, int32_t* rounds);
 
+/* ---- PNG decode (vf_png_decode.hip) ------------------------------------------------------------------
+ * image.load of a PNG file (the masks of datavid/donkey_folder.lua, test_vid_wholeim.lua:112 and
+ * test_more_complex.lua:102, demo.lua:51, and the frames vf_png_encode writes) on the device: the BYTES libpng gives
+ * with grey below 8 bits and palettes expanded.  Supported: colour types 0, 2, 3, 4, 6 at bit depths 1, 2, 4, 8, no
+ * interlace, sides up to 16384, any number of IDAT chunks, ancillary chunks, tRNS with a palette.  Unsupported (known
+ * from the headers): 16-bit samples, Adam7, IDAT data above 256 MiB.
+ * vf_png_inspect (host only, no GPU): walk the chunks of one file.  info (int64[12]) = {width, height, bit depth,
+ * colour type, interlace, channels after expansion (1 - 4: what image.load(path) gives), IDAT bytes in total, IDAT
+ * chunks, palette entries, tRNS entries, supported (0 / 1), inflated bytes expected H * (1 + ceil(W * bits / 8))};
+ * when not supported, reason (may be NULL) receives why.  Returns non-zero, with vf_last_error(), for a file that is
+ * malformed: a bad signature, IHDR not first or with illegal fields, no PLTE for colour type 3 or PLTE after IDAT,
+ * IDAT chunks not consecutive, no IEND, a chunk running past the file, a wrong CRC on IHDR, PLTE, tRNS, IDAT or IEND
+ * (other ancillary chunks are skipped unchecked), a zlib header that is not deflate with a window of at most 32 KiB,
+ * no preset dictionary and a valid FCHECK. */
+enum {
+  VF_PNG_OK = 0, VF_PNG_BAD_CODE = 1, VF_PNG_SHORT_DATA = 2, VF_PNG_BAD_DISTANCE = 3, VF_PNG_BAD_LENGTH = 4,
+  VF_PNG_BAD_FILTER = 5, VF_PNG_BAD_ADLER = 6, VF_PNG_BAD_INDEX = 7
+};   /* per-image status words of vf_png_decode */
+int vf_png_inspect(const unsigned char* data, size_t len, int64_t* info, char* reason, int reason_cap);
+/* Sizes for one batch: the n files are data[offs[i] .. offs[i+1]) (HOST memory).  ws_bytes: the DEVICE workspace
+ * vf_png_decode needs; stage_bytes: its HOST staging buffer (pinned memory keeps the one upload asynchronous).  Read
+ * from the chunk headers alone (no CRC is computed).  channels: 0 (the file's own, after expansion), 1 or 3.  Fails,
+ * naming the image, on a file that is malformed (2) or unsupported (3); unsupported here also: channels 1 on a colour
+ * file, channels 0 on a grey or RGB file with tRNS. */
+int vf_png_decode_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int channels, size_t* ws_bytes,
+                                  size_t* stage_bytes);
+/* Decode the batch on the context's stream: image i becomes uint8 H x W x C at out + out_offs[i] (DEVICE out, HOST
+ * out_offs), C = channels, or the file's own for channels 0.  channels 3 replicates grey, takes the grey of
+ * grey+alpha, drops the alpha of RGBA and gives RGB from a palette; channels 1 takes grey and grey+alpha files;
+ * a palette with tRNS gives RGBA for channels 0 (alpha 255 past the end of tRNS).  status (DEVICE int32[n]) receives
+ * VF_PNG_* per image.  The host checks the CRCs, concatenates each file's IDAT payloads (minus the two zlib header
+ * bytes) and packs them with PLTE / tRNS and a descriptor per image into stage (caller-owned, >= stage_bytes), and
+ * enqueues one upload into ws (caller-owned DEVICE memory, >= ws_bytes) and three launches; stage must stay untouched
+ * until the stream reaches this call's work.  Nothing is allocated and nothing synchronises. */
+int vf_png_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, const int64_t* out_offs,
+                  unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes, int32_t* status);
+/* image.load(path, nc, 'float') on top of the decoded bytes: dst[i] = src[i] / 255 in float32, an IEEE division
+ * (correctly rounded), n elements, DEVICE src and dst, on the context's stream. */
+int vf_png_bytes_to_float(vf_ctx* ctx, const unsigned char* src, float* dst, int64_t n);
+
 /* ---- PNG encode (vf_png.hip) ---------------------------------------------------------------------------
  * image.save of test_vid.lua:138, test_vid_wholeim.lua:229-242 and test_more_complex.lua:200-214 on the device: a batch
  * of n frames of one H x W x C in, n whole PNG files out, back to back.  8-bit samples, C = 3 (colour type 2) or 1

@@ -225,6 +225,48 @@ def jpeg_inspect(data, walk=True):
     return d
 
 
+PNG_STATUS = {0: "ok", 1: "bad code", 2: "short data", 3: "bad distance", 4: "bad length", 5: "bad filter", 6: "bad Adler-32",
+              7: "bad palette index"}
+
+
+def png_inspect(data):
+    """The host-only chunk walk of one PNG file (vf_png_inspect; no GPU needed) -> dict(width, height, bit_depth,
+    color_type, interlace, channels, idat_bytes, idat_chunks, palette_entries, trns_entries, supported, inflated_bytes,
+    reason).  channels: what image.load(path) gives after expansion (1 - 4).  Raises ValueError for a malformed file."""
+    lib = _lib.load()
+    data = bytes(data)
+    info = (C.c_int64 * 12)()
+    why = C.create_string_buffer(160)
+    if lib.vf_png_inspect(data, len(data), info, why, 160) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    keys = ("width", "height", "bit_depth", "color_type", "interlace", "channels", "idat_bytes", "idat_chunks", "palette_entries",
+            "trns_entries", "supported", "inflated_bytes")
+    d = {k: int(v) for k, v in zip(keys, info)}
+    d["supported"] = bool(d["supported"])
+    d["reason"] = why.value.decode()
+    return d
+
+
+def _joined(files):
+    """(the files back to back, int64 offsets[n + 1]) as the batch decoders take them."""
+    offs = np.zeros(len(files) + 1, np.int64)
+    offs[1:] = np.cumsum([len(f) for f in files])
+    return b"".join(files), offs
+
+
+def png_decode_workspace_bytes(files, channels=None):
+    """(device workspace bytes, host staging bytes) of one PNG batch (vf_png_decode_workspace_bytes; host only, no GPU
+    needed).  channels: None (each file's own), 1 or 3.  ValueError, naming the image, for a malformed or unsupported
+    file."""
+    lib = _lib.load()
+    data, offs = _joined(files)
+    ws_b, st_b = C.c_size_t(), C.c_size_t()
+    if lib.vf_png_decode_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), len(files), int(channels or 0), C.byref(ws_b),
+                                         C.byref(st_b)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return ws_b.value, st_b.value
+
+
 def _encoder_bytes(entry, *geometry):
     """(workspace bytes, output bound) from a vf_*_workspace_bytes entry point; a refusal is a ValueError with its text."""
     lib = _lib.load()
@@ -896,6 +938,49 @@ class HipBackend:
         self._jpeg_done[t] = torch.cuda.Event()
         self._jpeg_done[t].record(torch.cuda.current_stream(self.device))
         return out, out_offs, status, rounds
+
+    # ---- PNG decode (vf_png_decode.hip)
+    def png_decode(self, files, channels=None, infos=None):
+        """Decode a batch of supported PNG files (bytes each) into one device uint8 buffer.  -> (out, offsets, status):
+        image i is out[offsets[i]:offsets[i+1]] as H x W x C, C = channels or (None) the file's own after expansion;
+        status (device int32[n]) holds VF_PNG_* per image, valid once the stream gets there.  infos: the files'
+        png_inspect results, if the caller has them."""
+        n = len(files)
+        shapes = infos if infos is not None else [png_inspect(f) for f in files]
+        sizes = [s["height"] * s["width"] * (channels or s["channels"]) for s in shapes]
+        data, offs = _joined(files)
+        out_offs = np.zeros(n + 1, np.int64)
+        out_offs[1:] = np.cumsum(sizes)
+        ws_b, st_b = C.c_size_t(), C.c_size_t()
+        _lib.check(self.lib.vf_png_decode_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), n, int(channels or 0),
+                                                          C.byref(ws_b), C.byref(st_b)))
+        ws = self._scratch("pngd", ws_b.value)
+        # two pinned staging buffers, used in turn, as jpeg_decode's
+        if not hasattr(self, "_pngd_stage"):
+            self._pngd_stage, self._pngd_done, self._pngd_turn = [None, None], [None, None], 0
+        t = self._pngd_turn
+        self._pngd_turn = 1 - t
+        if self._pngd_done[t] is not None:
+            self._pngd_done[t].synchronize()
+        stage = self._pngd_stage[t]
+        if stage is None or stage.numel() < st_b.value:
+            self._pngd_stage[t] = stage = torch.empty(max(st_b.value, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        out = torch.empty(max(int(out_offs[-1]), 1), dtype=torch.uint8, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._c("vf_png_decode", data, offs.ctypes.data_as(C.c_void_p), n, int(channels or 0), out_offs.ctypes.data_as(C.c_void_p),
+                _ptr(out), C.c_void_p(stage.data_ptr()), stage.numel(), _ptr(ws), ws.numel(), _ptr(status))
+        self._pngd_done[t] = torch.cuda.Event()
+        self._pngd_done[t].record(torch.cuda.current_stream(self.device))
+        return out, out_offs, status
+
+    def png_bytes_to_float(self, t):
+        """image.load(path, nc, 'float') on top of decoded bytes: a device uint8 tensor -> float32 of the same shape,
+        b / 255 as a correctly rounded float32 division (vf_png_bytes_to_float)."""
+        assert t.dtype == torch.uint8 and t.device == self.device
+        t = t.contiguous()
+        out = torch.empty(t.shape, dtype=torch.float32, device=self.device)
+        self._c("vf_png_bytes_to_float", _ptr(t), _ptr(out), t.numel())
+        return out
 
     # ---- PNG encode (vf_png.hip, DESIGN.md 5.3)
     def png_encode(self, frames):

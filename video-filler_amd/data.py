@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from ._lib import VfError
-from .backend import JPEG_STATUS, get_backend, jpeg_inspect, nhwc_empty
+from .backend import JPEG_STATUS, PNG_STATUS, get_backend, jpeg_inspect, nhwc_empty, png_inspect
 
 CENTER_FILL = (117.0, 104.0, 123.0)      # train.lua:287-289
 
@@ -103,6 +103,125 @@ def decode_jpeg(items, channels=3, stack=False, fallback=None, subseq_bytes=256)
     if len(dev) == len(out):
         return buf[:len(out) * out[0].numel()].view(len(out), *out[0].shape)
     return torch.stack(out)
+
+
+# ------------------------------------------------------------------------------------------ PNG decode
+def png_info(item):
+    """The host-side inspection of one PNG file (no GPU): dict(width, height, bit_depth, color_type, interlace, channels,
+    idat_bytes, idat_chunks, palette_entries, trns_entries, supported, inflated_bytes, reason).  ValueError if the file
+    is malformed (signature, chunk order, CRC, zlib header)."""
+    return png_inspect(_jpeg_bytes(item))
+
+
+def decode_png(items, channels=None, stack=False, fallback=None, dtype="uint8"):
+    """image.load(path[, channels]) of a batch of PNG files, decoded on the device in one pass (vf_png_decode): uint8
+    H x W x C device tensors holding the bytes libpng gives with grey below 8 bits and palettes expanded (Torch7's
+    image.load followed by :mul(255)).  channels None keeps the file's own (1 grey, 2 grey+alpha, 3 RGB or palette, 4 RGBA
+    or palette with tRNS); 3 replicates grey, takes the grey of grey+alpha and drops the alpha of RGBA; 1 takes grey and
+    grey+alpha files only.  dtype "float" divides by 255 in float32 (image.load(path, nc, 'float')).
+
+    items: bytes, uint8 arrays or paths.  Returns a list of views into one device buffer, or with stack=True one
+    N x H x W x C tensor (all shapes must match).  Files the device decoder does not support (16-bit samples, Adam7
+    interlace, a colour file with channels=1, tRNS on a grey or RGB file with channels=None) go to fallback(bytes), which
+    returns the decoded uint8 H x W x C image; without it they raise ValueError naming the item and why.  A malformed
+    file raises ValueError naming the item before anything is launched; a corrupt stream raises it, with the status,
+    once the stream has synchronised."""
+    B = get_backend()
+    assert channels in (None, 1, 3), "channels is None (the file's own), 1 or 3"
+    assert dtype in ("uint8", "float"), "dtype is 'uint8' or 'float'"
+    files = [_jpeg_bytes(it) for it in items]
+    infos, dev, out = [], [], [None] * len(files)
+    for i, f in enumerate(files):
+        try:
+            info = png_inspect(f)
+        except ValueError as e:
+            raise ValueError("decode_png: item %d: %s" % (i, e)) from None
+        colour = info["color_type"] in (2, 3, 6)
+        if info["supported"] and channels == 1 and colour:
+            info = dict(info, supported=False, reason="colour file with channels=1")
+        if info["supported"] and channels is None and info["trns_entries"] and info["color_type"] != 3:
+            info = dict(info, supported=False, reason="tRNS on colour type %d with the file's channels" % info["color_type"])
+        if not info["supported"]:
+            if fallback is None:
+                raise ValueError("decode_png: item %d is not supported by the device decoder: %s" % (i, info["reason"]))
+            img = torch.as_tensor(np.ascontiguousarray(fallback(f)))
+            if img.dim() == 2:
+                img = img.unsqueeze(-1)
+            assert img.dtype == torch.uint8 and img.dim() == 3 and (channels is None or img.shape[2] == channels), \
+                "fallback returns uint8 H x W x %s, got %s %s" % (channels or "C", img.dtype, tuple(img.shape))
+            out[i] = B.from_host(img).contiguous()
+            continue
+        infos.append(info)
+        dev.append(i)
+    buf = None
+    if dev:
+        try:
+            buf, offs, status = B.png_decode([files[i] for i in dev], channels, infos)
+        except VfError as e:
+            m = re.search(r"image (\d+)", str(e))
+            if m is None:
+                raise
+            raise ValueError("decode_png: item %d: %s" % (dev[int(m.group(1))], e)) from None
+        st = status.cpu().tolist()
+        for j, i in enumerate(dev):
+            if st[j] != 0:
+                raise ValueError("decode_png: item %d: corrupt image data (%s)" % (i, PNG_STATUS.get(st[j], st[j])))
+            out[i] = buf[offs[j]:offs[j + 1]].view(infos[j]["height"], infos[j]["width"], channels or infos[j]["channels"])
+    if stack:
+        shapes = {tuple(t.shape) for t in out}
+        assert len(shapes) == 1, "stack=True needs images of one shape, got %s" % sorted(shapes)
+        if len(dev) == len(out):
+            out = buf[:len(out) * out[0].numel()].view(len(out), *out[0].shape)
+        else:
+            out = torch.stack(out)
+    if dtype == "float":
+        out = B.png_bytes_to_float(out) if stack else [B.png_bytes_to_float(t) for t in out]
+    return out
+
+
+def decode_image(items, channels=3, stack=False, fallback=None, dtype="uint8"):
+    """image.load(path, channels) for a mixed folder: every item's signature says whether it is a JPEG or a PNG file; the
+    JPEGs go to decode_jpeg and the PNGs to decode_png, one call each, and the results come back in the caller's order.
+    ValueError naming the item for a file that is neither."""
+    B = get_backend()
+    files = [_jpeg_bytes(it) for it in items]
+    jpg, png = [], []
+    for i, f in enumerate(files):
+        if f[:2] == b"\xff\xd8":
+            jpg.append(i)
+        elif f[:8] == b"\x89PNG\r\n\x1a\n":
+            png.append(i)
+        else:
+            raise ValueError("decode_image: item %d is neither a JPEG nor a PNG file" % i)
+    out = [None] * len(files)
+    for idx, dec, name in ((jpg, decode_jpeg, "decode_jpeg"), (png, decode_png, "decode_png")):
+        if not idx:
+            continue
+        try:
+            got = dec([files[i] for i in idx], channels=channels, fallback=fallback)
+        except ValueError as e:   # the item's number in the caller's list
+            m = re.match(r"%s: item (\d+)(.*)" % name, str(e), re.S)
+            if m is None:
+                raise
+            raise ValueError("%s: item %d%s" % (name, idx[int(m.group(1))], m.group(2))) from None
+        for i, t in zip(idx, got):
+            out[i] = t
+    if stack:
+        shapes = {tuple(t.shape) for t in out}
+        assert len(shapes) == 1, "stack=True needs images of one shape, got %s" % sorted(shapes)
+        out = torch.stack(out)
+    if dtype == "float":
+        out = B.png_bytes_to_float(out) if stack else [B.png_bytes_to_float(t) for t in out]
+    return out
+
+
+def load_mask(item):
+    """`image.load(maskName):byte()` of datavid/donkey_folder.lua for a PNG mask: the file's own channels decoded on the
+    device, then byte_mask (only 255 becomes 1).  uint8 H x W (a grey file) or H x W x C on the device, ready for
+    ClipBatcher.set_mask, PatchArrayBatcher.set_mask and inference.load_whole_frames."""
+    (m,) = decode_png([item])
+    m = byte_mask(m)
+    return m[..., 0].contiguous() if m.shape[2] == 1 else m
 
 
 def _files_from(buf, offsets):

@@ -142,6 +142,10 @@ int vf_image_hook2d(vf_ctx*, const void* src, int src_layout, float* out, int C,
 int vf_image_whole_frames(vf_ctx*, const void* src, int src_layout, float* out, int N, int C, int H, int W, int height, int width, int outh, int outw, const unsigned char* fill_mask, float fill_value);
 int vf_crop_stats(vf_ctx*, const float* clip, const unsigned char* mask, int C, int iH, int iW, int fs, int w1, int h1, double* out);
 int vf_patch_array_prepare(vf_ctx*, const void* src, int src_layout, const unsigned char* mask, float* masked, float* full, float* maskout, double* sum, int H, int W, int height, int width, int fs, int arr_h, int arr_w, int crop_w, int crop_h, int flip, float mask_value);
+int vf_png_inspect(const unsigned char* data, size_t len, int64_t* info, char* reason, int reason_cap);
+int vf_png_decode_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int channels, size_t* ws_bytes, size_t* stage_bytes);
+int vf_png_decode(vf_ctx*, const unsigned char* data, const int64_t* offs, int n, int channels, const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes, int32_t* status);
+int vf_png_bytes_to_float(vf_ctx*, const unsigned char* src, float* dst, int64_t n);
 int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, size_t* out_bytes);
 int vf_png_encode(vf_ctx*, const void* src, int kind, int n, int H, int W, int C, void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
 int vf_display_workspace_bytes(int N, int C, int h, int w, int padding, int nrow, int scaleeach, int has_min, int has_max, size_t* ws_bytes);
