@@ -546,6 +546,33 @@ int vf_display_tensor(vf_ctx* ctx, const float* packed, int src_layout, float* g
 int vf_center_finish(vf_ctx* ctx, const float* ctx_nhwc, const float* pred_nhwc, float* pretty, float* pasted,
                      float* pred_mapped, int B, int C, int fs, int overlapPred);
 
+/* ---- scores of result frames (vf_metrics.hip) ----------------------------------------------------------
+ * PSNR, SSIM, absolute error and flicker of N result frames `a` against N truth frames `b`, on the BYTES image.save
+ * would write.  kind 0: both float N x C x H x W, every value through image.savePNG's rule (see vf_png_encode); kind 1:
+ * both uint8 N x H x W x C, taken as they are.  C = 1 or 3, sides 1 to 16384, N 1 to 65535.  Only rows < vh and columns
+ * < vw count (1 <= vh <= H, 1 <= vw <= W); what lies outside is never read.  mask (DEVICE uint8 H x W, non-zero = hole)
+ * may be NULL.  clip != 0: the batch is one clip and the flicker term runs over it; 0: independent images, flicker 0.
+ * table (DEVICE int64[N][2][VF_METRICS_COLS]) receives, per frame and region (0: every valid pixel; 1: the valid pixels
+ * under the mask, all zero without one), summed over the channels, in this column order:
+ *   VF_METRICS_N       samples counted
+ *   VF_METRICS_SSE     sum (a - b)^2
+ *   VF_METRICS_SAE     sum |a - b|
+ *   VF_METRICS_SSIM_Q  sum over the windows of llrint(s * 2^30), s the window's SSIM (uniform 7 x 7, sample covariance,
+ *                      K1 0.01, K2 0.03, L 255, per channel; from the integer window sums by two IEEE double divisions
+ *                      and one multiplication); windows wholly inside the valid rectangle, a window
+ *                      belonging to region 1 when its centre pixel does
+ *   VF_METRICS_SSIM_N  windows counted
+ *   VF_METRICS_FLICKER sum |(a_t - a_{t-1}) - (b_t - b_{t-1})| for frames t >= 1 of a clip, else 0
+ * Every column is an integer sum: the table equals tests/metrics_ref.py exactly and is the same on every run.  One
+ * memset and one launch on the context's stream, whatever N; nothing is allocated and nothing synchronises.  Bad
+ * arguments are errors naming them, before anything is launched. */
+enum {
+  VF_METRICS_N = 0, VF_METRICS_SSE = 1, VF_METRICS_SAE = 2, VF_METRICS_SSIM_Q = 3, VF_METRICS_SSIM_N = 4,
+  VF_METRICS_FLICKER = 5, VF_METRICS_COLS = 6
+};
+int vf_frame_metrics(vf_ctx* ctx, const void* a, const void* b, int kind, int N, int C, int H, int W, int vh, int vw,
+                     const unsigned char* mask, int clip, int64_t* table);
+
 /* ---- option branches of train.lua: noiseGen (:109-124, 319-327) and conditionAdv (:158-180) -----------------------
  * nn.JoinTable(2) over NHWC tensors: dst[p][c_dst + c] = src[p][c_src + c] for c < Ccopy, p < npix (forward: one call
  * per table element into the joined tensor; updateGradInput: one call per element out of the joined gradient).

@@ -99,6 +99,7 @@ SIGNATURES = {
     "vf_display_workspace_bytes": (i32, [i32] * 9 + [C.POINTER(sz)]),
     "vf_display_tensor": (i32, [vp, vp, i32, vp] + [i32] * 8 + [f64, i32, f64, i32, i32]),
     "vf_center_finish": (i32, [vp] * 6 + [i32] * 4),
+    "vf_frame_metrics": (i32, [vp, vp, vp] + [i32] * 7 + [vp, i32, vp]),
     "vf_channel_copy": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, i64]),
     "vf_noise_fill": (i32, [vp, vp, i64, u64, vp, u64, i32]),
     "vf_bce_fwd": (i32, [vp, vp, f32, i32, vp]),

@@ -286,6 +286,7 @@ def png_workspace_bytes(n, H, W, channels):
     return _encoder_bytes("vf_png_workspace_bytes", n, H, W, channels)
 
 
+METRIC_COLUMNS = ("n", "sse", "sae", "ssim_q", "ssim_n", "flicker")     # VF_METRICS_* of include/vf_hip.h, in order
 GIF_CHUNK = 3824     # pixels between two Clear codes of a frame's LZW stream (csrc/vf_gif.hip)
 
 
@@ -1042,6 +1043,28 @@ class HipBackend:
                 int(min is not None), float(min or 0.0), int(max is not None), float(max or 0.0), int(bool(symmetric)),
                 int(bool(saturate)))
         return grid
+
+    # ---- scores of result frames (vf_metrics.hip)
+    def frame_metrics(self, a, b, mask=None, valid=None, clip=True):
+        """The integer sums behind PSNR, SSIM, absolute error and flicker of the frames a against b, on the bytes image.save
+        would write: both device float32 N x C x H x W (through image.savePNG's byte rule inside the kernel) or both device
+        uint8 N x H x W x C, contiguous, C = 1 or 3.  mask: device uint8 H x W (non-zero = hole) or None; valid: (vh, vw),
+        the rows / columns that count (what lies outside is never read), default the whole frame; clip: the flicker term
+        runs over the batch.  -> device int64 N x 2 x len(METRIC_COLUMNS) (regions: frame, hole), valid once the stream
+        gets there; one memset and one launch, whatever N."""
+        assert a.dim() == 4 and a.shape == b.shape and a.dtype == b.dtype and a.is_contiguous() and b.is_contiguous()
+        assert a.device == self.device and b.device == self.device
+        if a.dtype == torch.uint8:
+            kind, (n, H, W, Cc) = 1, a.shape
+        else:
+            assert a.dtype == torch.float32, "frames are uint8 N x H x W x C or float32 N x C x H x W"
+            kind, (n, Cc, H, W) = 0, a.shape
+        if mask is not None:
+            assert mask.dtype == torch.uint8 and tuple(mask.shape) == (H, W) and mask.is_contiguous() and mask.device == self.device
+        vh, vw = (H, W) if valid is None else valid
+        table = torch.empty(n, 2, len(METRIC_COLUMNS), dtype=torch.int64, device=self.device)
+        self._c("vf_frame_metrics", _ptr(a), _ptr(b), kind, n, Cc, H, W, int(vh), int(vw), _ptr(mask), int(bool(clip)), _ptr(table))
+        return table
 
     def center_finish(self, ctx, pred, overlapPred, pretty, pasted=None, pred_mapped=None):
         """test.lua:98-128.  ctx (B x C x fs x fs) and pred (B x C x fs/2 x fs/2): channels-last; pretty (2B x C x fs x fs),

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from ._lib import VfError
-from .backend import JPEG_STATUS, PNG_STATUS, get_backend, jpeg_inspect, nhwc_empty, png_inspect
+from .backend import JPEG_STATUS, METRIC_COLUMNS, PNG_STATUS, get_backend, jpeg_inspect, nhwc_empty, png_inspect
 
 CENTER_FILL = (117.0, 104.0, 123.0)      # train.lua:287-289
 
@@ -271,6 +271,55 @@ def encode_gif(clips, delay=10):
         t = t.float()
     B = get_backend()
     return _files_from(*B.gif_encode(B.from_host(t).contiguous(), int(delay)))
+
+
+# --------------------------------------------------------------------------------------------- scores
+def _check_metric_args(a, b, mask, valid):
+    """frame_metrics' argument checks, on the host and before any backend exists: -> (a, b, mask, (vh, vw)) as tensors,
+    floats as float32."""
+    a, b = torch.as_tensor(a), torch.as_tensor(b)
+    same_kind = (a.dtype == torch.uint8) == (b.dtype == torch.uint8) and (a.dtype == torch.uint8 or (a.is_floating_point() and b.is_floating_point()))
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape) or not same_kind:
+        raise ValueError("frame_metrics: a is %s %s and b is %s %s; both are float N x C x H x W or both uint8 N x H x W x C"
+                         % (str(a.dtype).replace("torch.", ""), tuple(a.shape), str(b.dtype).replace("torch.", ""), tuple(b.shape)))
+    if a.dtype == torch.uint8:
+        n, H, W, Cc = a.shape
+    else:
+        a, b = a.float(), b.float()
+        n, Cc, H, W = a.shape
+    if Cc not in (1, 3):
+        raise ValueError("frame_metrics: %d channels; frames have 1 (grey) or 3 (RGB)" % Cc)
+    if n < 1 or H < 1 or W < 1:
+        raise ValueError("frame_metrics: an empty batch of shape %s" % (tuple(a.shape),))
+    if mask is not None:
+        mask = torch.as_tensor(mask)
+        if mask.dtype == torch.bool:
+            mask = mask.to(torch.uint8)
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W):
+            raise ValueError("frame_metrics: the mask is %s %s; it is uint8 H x W = %d x %d, non-zero = hole"
+                             % (str(mask.dtype).replace("torch.", ""), tuple(mask.shape), H, W))
+    vh, vw = (H, W) if valid is None else valid
+    if int(vh) != vh or int(vw) != vw or not (1 <= vh <= H and 1 <= vw <= W):
+        raise ValueError("frame_metrics: valid=%r is outside 1..%d x 1..%d (rows, columns of the frame that count)" % (valid, H, W))
+    return a, b, mask, (int(vh), int(vw))
+
+
+def frame_metrics(a, b, mask=None, valid=None, clip=True):
+    """The scores of the result frames a against the truth b, computed where the frames are, in one call
+    (vf_frame_metrics): -> (table, METRIC_COLUMNS), table a device int64 tensor N x 2 x 6 — per frame and region (0: every
+    valid pixel; 1: the valid pixels under the mask, all zero without one), summed over the channels, the integer sums
+    n, sse, sae, ssim_q, ssim_n, flicker of DESIGN.md 5.7.  a, b: both float N x C x H x W in [0,1] (image.savePNG's rule
+    makes the bytes save_frames would write) or both uint8 N x H x W x C; C = 1 or 3; host or device.  mask: uint8 H x W,
+    non-zero = hole.  valid = (vh, vw): only rows < vh and columns < vw count; the rest (the bottom-right padding of the
+    whole-frame driver) is never read.  clip: the batch is one clip, and flicker — sum |(a_t - a_{t-1}) - (b_t - b_{t-1})|
+    for t >= 1 — runs over it; False: independent images, flicker 0.  Every column is an integer sum: the table equals
+    tests/metrics_ref.py exactly and is the same on every run.  ValueError, naming the argument, before anything is
+    launched, for a and b of different shapes or types, C outside {1, 3}, a mask of another shape, valid outside the frame.
+    inference.evaluate_frames turns the table into PSNR, SSIM, mean absolute error and flicker."""
+    a, b, mask, valid = _check_metric_args(a, b, mask, valid)
+    B = get_backend()
+    m = None if mask is None else B.from_host(mask).contiguous()
+    return B.frame_metrics(B.from_host(a).contiguous(), B.from_host(b).contiguous(), m, valid, clip), METRIC_COLUMNS
 
 
 # ---------------------------------------------------------------------------------------------- image.scale (DESIGN 5.1)

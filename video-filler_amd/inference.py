@@ -187,6 +187,54 @@ def save_gifs(name, outImages=None, inpaintImages=None, fullImages=None, delay=1
     return _write_files(["%s_%s.gif" % (name, key) for key in keys], files)
 
 
+# ------------------------------------------------------------------------------------------------- scores
+def scores_from_table(table):
+    """data.frame_metrics' int64 table N x 2 x 6 (a host array) -> the dict evaluate_frames returns: float64 from the
+    integers.  mse = sse / n is not returned; psnr = 10 log10(255^2 n / sse), inf for sse = 0; ssim = ssim_q /
+    (ssim_n 2^30); mae = sae / n; flicker / n.  A region without samples, or without windows, gives nan."""
+    import numpy as np
+    t = np.asarray(table, np.int64)
+    out = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for reg, pre in ((0, ""), (1, "hole_")):
+            n, sse, sae, sq, sn, fl = (t[:, reg, k].astype(np.float64) for k in range(len(data.METRIC_COLUMNS)))
+            out[pre + "psnr"] = 10.0 * np.log10(65025.0 * n / sse)
+            out[pre + "ssim"] = sq / (sn * float(1 << 30))
+            out[pre + "mae"] = sae / n
+            out[pre + "flicker"] = fl / n
+        out["mean"] = {k: (float(np.mean(v[1:])) if len(v) > 1 else 0.0) if k.endswith("flicker") else float(np.mean(v))
+                       for k, v in out.items()}
+    return out
+
+
+def evaluate_frames(result, truth, mask=None, valid=None):
+    """How good an inpainted clip is, from the tensors the drivers already hold on the device: one call
+    (data.frame_metrics), one small table read back.  result, truth: predLen frames each — what
+    WholeImageInpainter.__call__ returns and save_frames accepts: float predLen x nc x H x W in [0,1] or uint8
+    predLen x H x W x nc, nc = 1 or 3, host or device.  The scores are those of the BYTES save_frames would write
+    (image.savePNG's truncating rule), so they equal what anybody measures from the PNG files, without the files.
+    mask: the hole, uint8 H x W, non-zero = hole; the drivers' padmask (nc x H x W) is accepted and its first channel
+    taken.  valid = (vh, vw): the rows and columns that are picture; the bottom-right padding beyond them has no
+    influence.  `whole_frame_sizes` gives it — for test_vid_wholeim.lua:
+
+        inh, inw, outh, outw = whole_frame_sizes(loadSize)
+        outImages, inpaintImages, fullImages = WholeImageInpainter(net, predLen)(full, padmask)
+        scores = evaluate_frames(inpaintImages, gt, padmask, valid=(inh, inw))
+
+    with gt the frames of the data set's gt/ folder (:123-126) scaled and padded as `full` was, in [0,1].
+    Returns a dict of float64 arrays of predLen entries: psnr, ssim (uniform 7 x 7 windows, scikit-image's default
+    form, per channel), mae (in byte units), flicker (mean |(a_t - a_{t-1}) - (b_t - b_{t-1})|, 0 for the first frame),
+    and hole_psnr, hole_ssim, hole_mae, hole_flicker over the hole alone (a window belongs to the hole when its centre
+    does); and under "mean" the clip means of all eight (flicker over the frames t >= 1).  nan where a region has no
+    samples or no whole window (no mask; a frame below 7 x 7); psnr inf for identical frames.  DESIGN.md 5.7 has the
+    rule, tests/metrics_ref.py pins it."""
+    m = None if mask is None else torch.as_tensor(mask)
+    if m is not None and m.dim() == 3:
+        m = m[0]
+    table, _ = data.frame_metrics(result, truth, m, valid, clip=True)
+    return scores_from_table(table.cpu().numpy())
+
+
 # --------------------------------------------------------------------------- test.lua / demo.lua and the sheets (DESIGN 5.4)
 def _check_display_args(x, padding, nrow):
     """toDisplayTensor's argument checks, on the host and before any backend exists: -> the tensor."""

@@ -151,6 +151,7 @@ int vf_png_encode(vf_ctx*, const void* src, int kind, int n, int H, int W, int C
 int vf_display_workspace_bytes(int N, int C, int h, int w, int padding, int nrow, int scaleeach, int has_min, int has_max, size_t* ws_bytes);
 int vf_display_tensor(vf_ctx*, const float* packed, int src_layout, float* grid, int N, int C, int h, int w, int padding, int nrow, int scaleeach, int has_min, double min, int has_max, double max, int symmetric, int saturate);
 int vf_center_finish(vf_ctx*, const float* ctx_nhwc, const float* pred_nhwc, float* pretty, float* pasted, float* pred_mapped, int B, int C, int fs, int overlapPred);
+int vf_frame_metrics(vf_ctx*, const void* a, const void* b, int kind, int N, int C, int H, int W, int vh, int vw, const unsigned char* mask, int clip, int64_t* table);
 int vf_channel_copy(vf_ctx*, const float* src, int Csrc, int c_src, float* dst, int Cdst, int c_dst, int Ccopy, int64_t npix);
 int vf_noise_fill(vf_ctx*, float* out, int64_t n, uint64_t seed, const int32_t* counter_dev, uint64_t counter, int normal);
 ]]
