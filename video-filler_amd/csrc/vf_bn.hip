@@ -2,10 +2,14 @@
 //
 // Reference: THNN BatchNormalization.c (double accumulators) / THCUNN BatchNormalization.cu, reached from
 // train.lua:92-101,125,135-144,189-193.  HBM-bound: every kernel walks rows with the channel axis on the
-// lanes (16-byte loads, fully coalesced), per-thread fp32 partial sums over <= 64 rows, then DOUBLE partials
-// combined in a fixed order (deterministic).  Statistics are shifted by the running mean so that
-// var = E[(x-s)^2] - E[x-s]^2 does not cancel catastrophically; the two-phase split (stats | finalize+apply)
-// is the hook where a data-parallel caller all-reduces the per-channel sums (SyncBN).
+// lanes (16-byte loads, fully coalesced), per-thread fp32 partial sums over K = rows_per_block / rp rows, then DOUBLE
+// partials combined in a fixed order (deterministic).  K follows from bn_geom / bn_stat_blocks: with full column chunks
+// K <= 8 for the statistics of a tensor up to 16 MB, forward and backward, beyond that bytes / 2 MB (64 at 128 MB, 128
+// at 256 MB: there is no fixed cap); a nearly empty last chunk (C/4 = 65) doubles it.  Statistics are shifted
+// by the running mean so that var = E[(x-s)^2] - E[x-s]^2 does not cancel catastrophically: the relative error of the
+// variance is about (3K + 2) 2^-24 (1 + kappa), kappa = (mean - s)^2 / var (derived in tests/bn_ref.py).  The two-phase
+// split (stats | finalize+apply) is the hook where a data-parallel caller all-reduces the per-channel sums (SyncBN,
+// SURVEY 8(e)).
 // (Measured and rejected: a single-launch form in which a block owns one float4 channel column over all rows — 22 us
 // per 2 MB tensor against ~17 us for the three launches; too few blocks to pull L2 bandwidth.  A second attempt that keeps
 // the block's slice in registers — one read, one launch, 16 channels per block — took 16 us for the same tensor
@@ -203,7 +207,7 @@ __global__ __launch_bounds__(256) void k_reduce_partials(const double* __restric
           sums[(int64_t)g * ncol + C + c] = q2;
         }
         const double mean = shift + q1 / n;
-        double m2 = q2 - q1 * q1 / n;  // = sum (x - mean)^2
+        double m2 = n > 1.0 ? q2 - q1 * q1 / n : 0.0;  // = sum (x - mean)^2; a single row: exactly 0 (see k_bn_finalize)
         if (m2 < 0) m2 = 0;
         const float invstd = (m2 == 0 && eps == 0.f) ? 0.f : (float)(1.0 / sqrt(m2 / n + (double)eps));
         save_mean[(int64_t)g * C + c] = (float)mean;
@@ -265,7 +269,9 @@ __global__ void k_bn_finalize(const double* __restrict__ sums, float* __restrict
   const double shift = running_mean[c];
   const double s1 = sums[c], s2 = sums[C + c];
   const double mean = shift + s1 / n;
-  double m2 = s2 - s1 * s1 / n;  // = sum (x - mean)^2
+  // = sum (x - mean)^2.  A single row has none: s2 is the fp32-rounded square of s1, so the difference would be that rounding
+  // error, of either sign, and running_var below +inf where THNN's 0 / 0 gives NaN
+  double m2 = n > 1.0 ? s2 - s1 * s1 / n : 0.0;
   if (m2 < 0) m2 = 0;
   float invstd;
   if (m2 == 0 && eps == 0.f)
