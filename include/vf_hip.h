@@ -497,6 +497,28 @@ int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, size_t*
 int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, void* ws, size_t ws_bytes,
                   unsigned char* out, size_t out_cap, int64_t* offsets);
 
+/* ---- JPEG encode (vf_jpeg_enc.hip) ---------------------------------------------------------------------
+ * image.save('x.jpg') / image.compressJPG, the JPEG folders the loaders read and the payload of the training scripts'
+ * disp.image, on the device: a batch of n frames of one H x W x C in, n whole baseline JFIF files out, back to back,
+ * byte for byte what libjpeg's default compression writes (jpeg_set_defaults, jpeg_set_quality(quality, TRUE), the fixed
+ * Annex K Huffman tables, no restart intervals, the islow DCT; Pillow's save(format="JPEG", quality, subsampling) is the
+ * same).  8-bit samples, C = 3 (RGB in, YCbCr coded) or 1 (grey), sides 1 to 16384, n 1 to 65535, quality 1 to 100;
+ * subsampling 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 (luma 1x1, 2x1 or 2x2 against chroma 1x1; ignored for C = 1); anything else
+ * is an error naming the argument, before anything is launched.  kind 0: float n x C x H x W, every value through
+ * image.savePNG's rule (see vf_png_encode; Torch7's saveJPG clamps and truncates the same way); kind 1: uint8
+ * n x H x W x C, taken as they are.  A file's bytes depend on its own frame, the quality and the sampling only, and are
+ * the same on every run.
+ * vf_jpeg_encode_workspace_bytes (host only, no GPU): the DEVICE workspace and an upper bound on the output for the
+ * batch.  The bound: a block's code is at most 64 coefficients of 16 code bits + 11 value bits, 216 bytes; byte stuffing
+ * can at most double the stream; the header is at most 624 bytes and EOI 2:
+ * out_bytes = n * (2 * 216 * blocks per frame + 626), blocks counted in whole MCUs, dummies included. */
+int vf_jpeg_encode_workspace_bytes(int n, int H, int W, int C, int subsampling, size_t* ws_bytes, size_t* out_bytes);
+/* Encode on the context's stream.  ws (>= ws_bytes) and out (out_cap >= the bound above) are caller-owned DEVICE memory;
+ * offsets (DEVICE int64[n + 1]) receives the files' places: file i is out[offsets[i] .. offsets[i + 1]).  Nine launches
+ * whatever n is; nothing is allocated and nothing synchronises. */
+int vf_jpeg_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling,
+                   void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
+
 /* ---- animated GIF encode (vf_gif.hip) ------------------------------------------------------------------
  * The `convert -delay D pred_1.png ... x_result.gif` that ends test_vid.lua:140-147, test_vid_wholeim.lua:244-257 and
  * test_more_complex.lua:216-229, on the device: `clips` clips of `frames` RGB frames of one H x W in, `clips` whole

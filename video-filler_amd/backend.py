@@ -286,6 +286,16 @@ def png_workspace_bytes(n, H, W, channels):
     return _encoder_bytes("vf_png_workspace_bytes", n, H, W, channels)
 
 
+JPEG_SUBSAMPLING = {"444": 0, "422": 1, "420": 2}     # the `subsampling` argument of vf_jpeg_encode (Pillow's numbers)
+
+
+def jpeg_encode_workspace_bytes(n, H, W, channels, subsampling="420"):
+    """(device workspace bytes, upper bound on the output bytes) of a JPEG batch of n frames of H x W x channels
+    (vf_jpeg_encode_workspace_bytes; host only, no GPU needed).  ValueError, naming the argument, for what the encoder
+    does not take: channels other than 1 or 3, a side outside 1..16384, a batch outside 1..65535, an unknown sampling."""
+    return _encoder_bytes("vf_jpeg_encode_workspace_bytes", n, H, W, channels, JPEG_SUBSAMPLING.get(subsampling, -1))
+
+
 METRIC_COLUMNS = ("n", "sse", "sae", "ssim_q", "ssim_n", "flicker")     # VF_METRICS_* of include/vf_hip.h, in order
 GIF_CHUNK = 3824     # pixels between two Clear codes of a frame's LZW stream (csrc/vf_gif.hip)
 
@@ -1000,6 +1010,28 @@ class HipBackend:
         out = torch.empty(out_b, dtype=torch.uint8, device=self.device)
         offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
         self._c("vf_png_encode", _ptr(frames), kind, n, H, W, Cc, _ptr(ws), ws.numel(), _ptr(out), out.numel(), _ptr(offsets))
+        return out, offsets
+
+    # ---- JPEG encode (vf_jpeg_enc.hip)
+    def jpeg_encode(self, frames, quality=75, subsampling="420"):
+        """Encode a batch of frames of one size as baseline JPEG files on the device, byte for byte libjpeg's default
+        compression at `quality` (1 to 100) and `subsampling` ("444", "422" or "420"; ignored for grey frames).  frames:
+        device uint8 N x H x W x C (taken as they are) or float32 N x C x H x W (through image.savePNG's truncating byte
+        rule inside the first kernel), C = 1 or 3, contiguous.  -> (buffer, offsets): file i is
+        buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8 tensor of the upper bound's size, offsets a device
+        int64[N + 1]; both are valid once the stream gets there."""
+        assert frames.dim() == 4 and frames.is_contiguous() and frames.device == self.device
+        if frames.dtype == torch.uint8:
+            kind, (n, H, W, Cc) = 1, frames.shape
+        else:
+            assert frames.dtype == torch.float32, "frames are uint8 N x H x W x C or float32 N x C x H x W"
+            kind, (n, Cc, H, W) = 0, frames.shape
+        ws_b, out_b = jpeg_encode_workspace_bytes(n, H, W, Cc, subsampling)
+        ws = self._scratch("jpeg_enc", ws_b)
+        out = torch.empty(out_b, dtype=torch.uint8, device=self.device)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        self._c("vf_jpeg_encode", _ptr(frames), kind, n, H, W, Cc, int(quality), JPEG_SUBSAMPLING.get(subsampling, -1), _ptr(ws), ws.numel(),
+                _ptr(out), out.numel(), _ptr(offsets))
         return out, offsets
 
     # ---- GIF encode (vf_gif.hip, DESIGN.md 5.5)

@@ -1,4 +1,5 @@
-// vf_block.h — block-wide primitives shared by the device-side I/O stages (vf_image, vf_jpeg, vf_png, vf_gif).
+// vf_block.h — block-wide primitives shared by the device-side I/O stages (vf_image, vf_jpeg, vf_jpeg_enc, vf_png, vf_gif;
+// DESIGN.md 5).
 // vf_device.h stays the header of the MFMA and bf16-plane helpers; nothing on the training path includes this one.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,0 +1,591 @@
+// vf_jpeg_enc.hip — batched baseline JPEG encoder: frames on the device in, whole JFIF files out, byte for byte
+// what libjpeg's default compression writes (tests/jpeg_enc_ref.py is the rule in numpy).
+//   k_jenc_dct        one thread per 8x8 block in scan (MCU) order: the block's samples straight from the source (byte rule, colour
+//                     conversion, edge replication, chroma downsampling), jfdctint's two passes, the quantiser; int16 zig-zag.
+//   k_jenc_size       one thread per block: its code length in bits (the DC difference against the previous real block of its
+//                     component), an exclusive scan inside the tile of 256 blocks, the tile's sum.
+//   k_jenc_tile_scan  one workgroup per image: the tiles' bit offsets, the image's bit count.
+//   k_jenc_clear      zeros under each image's stream, as far as it goes.
+//   k_jenc_write      one thread per block: its codes at its bit offset into the zeroed stream.  A dword that lies wholly
+//                     inside a block is stored, the dwords at a block's two ends are OR-ed in.
+//   k_jenc_ff_count / k_jenc_ff_scan / k_jenc_offsets / k_jenc_stuff   0xFF bytes per chunk of 4096 stream bytes, their prefix
+//                     and the file sizes, the files' places, then header, stream with a 0x00 behind every 0xFF, 1-padding, EOI.
+// Nine launches whatever the batch; a file's bytes depend on its own frame, the quality and the sampling only.
+#include "vf_block.h"
+#include "vf_common.h"
+
+namespace {
+
+constexpr int JENC_MAX_SIDE = 16384;
+constexpr int JENC_TILE = 256;            // blocks per workgroup of k_jenc_size / k_jenc_write: one per thread
+constexpr int JENC_CHUNK = 4096;          // stream bytes per workgroup of the stuffing kernels: 16 per thread
+constexpr int JENC_BLOCK_BITS = 64 * 27;  // the bound on a block's code (vf_hip.h has the derivation), a multiple of 32
+constexpr int JENC_HDR_CAP = 624;         // the colour header is 623 bytes, the grey one 333
+
+// Annex K, read out of a file libjpeg wrote at quality 50 (there the scaled tables are the base tables).  Quantisation tables in
+// the file's zig-zag order; Huffman tables as their DHT segments carry them: BITS[16], then HUFFVAL.
+constexpr unsigned char K_QUANT[2][64] = {
+    {16, 11, 12, 14, 12, 10, 16, 14, 13, 14, 18, 17, 16, 19, 24, 40, 26, 24, 22, 22, 24, 49, 35, 37, 29, 40, 58, 51, 61, 60, 57, 51,
+     56, 55, 64, 72, 92, 78, 64, 68, 87, 69, 55, 56, 80, 109, 81, 87, 95, 98, 103, 104, 103, 62, 77, 113, 121, 112, 100, 120, 92, 101,
+     103, 99},
+    {17, 18, 18, 24, 21, 24, 47, 26, 26, 47, 99, 66, 56, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+constexpr unsigned char K_DC_BITS[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+constexpr unsigned char K_DC_VAL[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+constexpr unsigned char K_AC_BITS[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
+constexpr unsigned char K_AC_VAL[2][162] = {
+    {1, 2, 3, 0, 4, 17, 5, 18, 33, 49, 65, 6, 19, 81, 97, 7, 34, 113, 20, 50, 129, 145, 161, 8, 35, 66, 177, 193, 21, 82, 209, 240,
+     36, 51, 98, 114, 130, 9, 10, 22, 23, 24, 25, 26, 37, 38, 39, 40, 41, 42, 52, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72, 73,
+     74, 83, 84, 85, 86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 131, 132,
+     133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170, 178,
+     179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217,
+     218, 225, 226, 227, 228, 229, 230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250},
+    {0, 1, 2, 3, 17, 4, 5, 33, 49, 6, 18, 65, 81, 7, 97, 113, 19, 34, 50, 129, 8, 20, 66, 145, 161, 177, 193, 9, 35, 51, 82, 240,
+     21, 98, 114, 209, 10, 22, 36, 52, 225, 37, 241, 23, 24, 25, 26, 38, 39, 40, 41, 42, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71,
+     72, 73, 74, 83, 84, 85, 86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 130,
+     131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169,
+     170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215,
+     216, 217, 218, 226, 227, 228, 229, 230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249, 250}};
+// zig-zag position -> row-major position in the block
+constexpr unsigned char K_ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// symbol -> code << 8 | length, the canonical codes of the four tables (jchuff.c's jpeg_make_c_derived_tbl)
+struct JencLut {
+  unsigned dc[2][12];
+  unsigned ac[2][256];
+};
+constexpr JencLut jenc_make_lut() {
+  JencLut t{};
+  for (int s = 0; s < 2; ++s) {
+    unsigned code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+      for (int i = 0; i < K_DC_BITS[s][len - 1]; ++i) t.dc[s][K_DC_VAL[k++]] = code++ << 8 | (unsigned)len;
+      code <<= 1;
+    }
+    code = 0;
+    k = 0;
+    for (int len = 1; len <= 16; ++len) {
+      for (int i = 0; i < K_AC_BITS[s][len - 1]; ++i) t.ac[s][K_AC_VAL[s][k++]] = code++ << 8 | (unsigned)len;
+      code <<= 1;
+    }
+  }
+  return t;
+}
+__constant__ JencLut c_jenc_lut = jenc_make_lut();
+
+struct JencHdr {                 // everything in front of the entropy-coded data; the same for every file of a batch
+  unsigned w[JENC_HDR_CAP / 4];  // bytes in memory order
+  int len;
+};
+
+struct JencArgs {
+  const void* src;
+  short* coef;                   // [n][nb][64]: quantised coefficients, zig-zag, blocks in scan order (dummies are not written)
+  unsigned* blk_off;             // [n][nb]: bit offset of the block inside its tile
+  unsigned* tile_sum;            // [n][tiles]
+  unsigned long long* tile_off;  // [n][tiles]: bit offset of the tile inside its image's stream
+  unsigned long long* img_bits;  // [n]
+  unsigned* stream;              // [n][cap_words]: the unstuffed stream, big-endian dwords (bit p is bit 31 - p % 32 of dword p / 32)
+  unsigned* ff_cnt;              // [n][chunks]
+  unsigned long long* ff_pref;   // [n][chunks]: 0xFF bytes in front of the chunk
+  unsigned char* out;
+  int64_t* offsets;              // [n + 1]
+  long long cap_words;
+  int n, H, W, C, hs, vs;        // luma sampling factors; chroma is 1 x 1
+  int mcux, mcuy, bpm, nb;       // MCUs across and down, blocks per MCU, blocks per image
+  int wb, hb;                    // real luma blocks across and down
+  int tiles, chunks;
+  unsigned short quant[2][64];   // zig-zag order, times 8: the divisors of jcdctmgr.c
+};
+
+// where block g of an image's scan lies
+struct JencPos {
+  int comp, X, Y;                // component, block column and row inside the component
+  bool real;
+};
+__device__ __forceinline__ JencPos jenc_pos(const JencArgs& a, int g) {
+  const int m = g / a.bpm, j = g - m * a.bpm, my = m / a.mcux, mx = m - my * a.mcux, luma = a.hs * a.vs;
+  JencPos p;
+  if (j < luma) {
+    const int by = j / a.hs, bx = j - by * a.hs;
+    p.comp = 0; p.X = mx * a.hs + bx; p.Y = my * a.vs + by;
+    p.real = p.X < a.wb && p.Y < a.hb;
+  } else {                       // a chroma component has as many blocks as there are MCUs: none is a dummy
+    p.comp = j - luma + 1; p.X = mx; p.Y = my; p.real = true;
+  }
+  return p;
+}
+
+// ---------------------------------------------------------------------------------------------------- samples, FDCT, quantiser
+template <int KIND>
+__device__ __forceinline__ int jenc_px(const JencArgs& a, long long f, int y, int x, int c) {
+  if (KIND == 1) return ((const unsigned char*)a.src)[((f * a.H + y) * a.W + x) * a.C + c];
+  return (int)vf_savepng_byte(((const float*)a.src)[((f * a.C + c) * a.H + y) * (long long)a.W + x]);
+}
+// jccolor.c, SCALEBITS 16
+template <int KIND>
+__device__ __forceinline__ int jenc_comp(const JencArgs& a, long long f, int y, int x, int comp) {
+  if (a.C == 1) return jenc_px<KIND>(a, f, y, x, 0);
+  const int r = jenc_px<KIND>(a, f, y, x, 0), g = jenc_px<KIND>(a, f, y, x, 1), b = jenc_px<KIND>(a, f, y, x, 2);
+  if (comp == 0) return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+  if (comp == 1) return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+  return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+}
+// One sample of a component plane padded to whole MCUs (jcprepct.c, jcsample.c).  Columns: the source is replicated to the right.
+// Rows: the source is replicated down to a multiple of the luma vertical factor, the component is downsampled, and then ITS last
+// row is replicated down: row r of a chroma plane of ch rows comes from source rows vs * min(r, ch - 1) and the one below.
+template <int KIND>
+__device__ __forceinline__ int jenc_sample(const JencArgs& a, long long f, int comp, int r, int c) {
+  if (comp == 0 || a.hs == 1) return jenc_comp<KIND>(a, f, min(r, a.H - 1), min(c, a.W - 1), comp);
+  const int x0 = min(2 * c, a.W - 1), x1 = min(2 * c + 1, a.W - 1);
+  if (a.vs == 1) {               // h2v1: bias 0, 1, 0, 1 ...
+    const int y = min(r, a.H - 1);
+    return (jenc_comp<KIND>(a, f, y, x0, comp) + jenc_comp<KIND>(a, f, y, x1, comp) + (c & 1)) >> 1;
+  }
+  const int rc = min(r, (a.H + 1) / 2 - 1), y0 = min(2 * rc, a.H - 1), y1 = min(2 * rc + 1, a.H - 1);
+  return (jenc_comp<KIND>(a, f, y0, x0, comp) + jenc_comp<KIND>(a, f, y0, x1, comp) + jenc_comp<KIND>(a, f, y1, x0, comp) +
+          jenc_comp<KIND>(a, f, y1, x1, comp) + 1 + (c & 1)) >> 2;   // h2v2: bias 1, 2, 1, 2 ...
+}
+
+__device__ __forceinline__ int jenc_descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+// one pass of jfdctint.c over eight values; CONST_BITS 13, PASS1_BITS 2
+template <bool FIRST>
+__device__ __forceinline__ void jenc_fdct8(int& d0, int& d1, int& d2, int& d3, int& d4, int& d5, int& d6, int& d7) {
+  constexpr int N = FIRST ? 13 - 2 : 13 + 2;
+  int t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4;
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  d0 = FIRST ? (t10 + t11) << 2 : jenc_descale(t10 + t11, 2);
+  d4 = FIRST ? (t10 - t11) << 2 : jenc_descale(t10 - t11, 2);
+  int z1 = (t12 + t13) * 4433;
+  d2 = jenc_descale(z1 + t13 * 6270, N);
+  d6 = jenc_descale(z1 - t12 * 15137, N);
+  z1 = t4 + t7;
+  int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+  const int z5 = (z3 + z4) * 9633;
+  t4 *= 2446; t5 *= 16819; t6 *= 25172; t7 *= 12299;
+  z1 *= -7373; z2 *= -20995;
+  z3 = z3 * -16069 + z5;
+  z4 = z4 * -3196 + z5;
+  d7 = jenc_descale(t4 + z1 + z3, N);
+  d5 = jenc_descale(t5 + z2 + z4, N);
+  d3 = jenc_descale(t6 + z2 + z3, N);
+  d1 = jenc_descale(t7 + z1 + z4, N);
+}
+
+// Threads take the blocks in scan order: the luma and chroma blocks of an MCU sit in neighbouring lanes and fetch the same pixels.
+// (Luma blocks first and chroma after them, so that a wave's lanes do alike, measured 16 % slower: the pixels are fetched twice.)
+template <int KIND>
+__global__ __launch_bounds__(256) void k_jenc_dct(JencArgs a) {
+  __shared__ int s_q[2][64];
+  __shared__ float s_r[2][64];
+  if (threadIdx.x < 128) {
+    const int d = a.quant[threadIdx.x >> 6][threadIdx.x & 63];
+    s_q[threadIdx.x >> 6][threadIdx.x & 63] = d;
+    s_r[threadIdx.x >> 6][threadIdx.x & 63] = 1.f / (float)d;
+  }
+  __syncthreads();
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  const long long f = blockIdx.y;
+  if (g >= a.nb) return;
+  const JencPos p = jenc_pos(a, g);
+  if (!p.real) return;
+  int v[64];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[8 * i + j] = jenc_sample<KIND>(a, f, p.comp, 8 * p.Y + i, 8 * p.X + j) - 128;
+    jenc_fdct8<true>(v[8 * i], v[8 * i + 1], v[8 * i + 2], v[8 * i + 3], v[8 * i + 4], v[8 * i + 5], v[8 * i + 6], v[8 * i + 7]);
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) jenc_fdct8<false>(v[j], v[8 + j], v[16 + j], v[24 + j], v[32 + j], v[40 + j], v[48 + j], v[56 + j]);
+  const int* q = s_q[p.comp ? 1 : 0];
+  const float* r = s_r[p.comp ? 1 : 0];
+  unsigned w[32];
+#pragma unroll
+  for (int k = 0; k < 64; ++k) {                  // jcdctmgr.c: sign(c) * ((|c| + d / 2) / d)
+    // the integer quotient through a float estimate: |c| + d / 2 < 2^17 and d < 2^11 are exact floats, the product of two correctly
+    // rounded factors is off by less than one, and the two comparisons settle it
+    const int c = v[K_ZZ[k]], d = q[k], num = abs(c) + (d >> 1);
+    int m = (int)((float)num * r[k]);
+    m -= m * d > num;
+    m += (m + 1) * d <= num;
+    const unsigned h = (unsigned)(c < 0 ? -m : m) & 0xFFFFu;
+    if (k & 1) w[k >> 1] |= h << 16;
+    else w[k >> 1] = h;
+  }
+  uint4* dst = (uint4*)(a.coef + (f * a.nb + g) * 64);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) dst[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+}
+
+// ------------------------------------------------------------------------------------------------------------- entropy coding
+__device__ __forceinline__ void jenc_load_lut(JencLut& s) {   // the code tables into LDS: lanes look up different symbols
+  const unsigned* src = (const unsigned*)&c_jenc_lut;
+  unsigned* dst = (unsigned*)&s;
+  for (int i = threadIdx.x; i < (int)(sizeof(JencLut) / 4); i += 256) dst[i] = src[i];
+  __syncthreads();
+}
+
+// The DC value the difference of real block g is taken against: the DC of the previous real block of g's component in scan order,
+// 0 for the first.  A luma dummy keeps the predictor, so the walk steps over dummies (at most three) and over the chroma blocks.
+__device__ __forceinline__ int jenc_pred(const JencArgs& a, const short* coef, int g, const JencPos& p) {
+  if (p.comp) return g >= a.bpm ? coef[(long long)(g - a.bpm) * 64] : 0;
+  const int luma = a.hs * a.vs;
+  for (int q = g - 1; q >= 0; --q) {
+    const int j = q % a.bpm;
+    if (j >= luma) { q -= j - luma; continue; }   // on a chroma block: the loop's --q lands on the MCU's last luma block
+    if (jenc_pos(a, q).real) return coef[(long long)q * 64];
+  }
+  return 0;
+}
+
+// jchuff.c's encode_one_block of block g: put(bits, count) receives every code with its extra bits behind it, at most 26 bits
+template <class PUT>
+__device__ __forceinline__ void jenc_block_codes(const JencArgs& a, const JencLut& s, const short* coef, int g, PUT&& put) {
+  const JencPos p = jenc_pos(a, g);
+  const int t = p.comp ? 1 : 0;
+  if (!p.real) {                                   // a dummy: DC difference 0, then EOB
+    put(s.dc[t][0] >> 8, s.dc[t][0] & 255);
+    put(s.ac[t][0] >> 8, s.ac[t][0] & 255);
+    return;
+  }
+  const uint4* src = (const uint4*)(coef + (long long)g * 64);
+  unsigned w[32];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint4 u = src[i];
+    w[4 * i] = u.x; w[4 * i + 1] = u.y; w[4 * i + 2] = u.z; w[4 * i + 3] = u.w;
+  }
+  {
+    const int diff = (int)(short)(w[0] & 0xFFFFu) - jenc_pred(a, coef, g, p);
+    const int n = 32 - __clz(abs(diff));
+    const unsigned e = s.dc[t][n], ext = (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << n) - 1u);
+    put((e >> 8) << n | ext, (int)(e & 255) + n);
+  }
+  int run = 0;
+#pragma unroll
+  for (int k = 1; k < 64; ++k) {
+    const int c = (int)(short)((k & 1) ? w[k >> 1] >> 16 : w[k >> 1] & 0xFFFFu);
+    if (c == 0) { ++run; continue; }
+    for (; run > 15; run -= 16) put(s.ac[t][0xF0] >> 8, s.ac[t][0xF0] & 255);
+    const int n = 32 - __clz(abs(c));
+    const unsigned e = s.ac[t][run << 4 | n], ext = (unsigned)(c < 0 ? c - 1 : c) & ((1u << n) - 1u);
+    put((e >> 8) << n | ext, (int)(e & 255) + n);
+    run = 0;
+  }
+  if (run) put(s.ac[t][0] >> 8, s.ac[t][0] & 255);
+}
+
+__global__ __launch_bounds__(256) void k_jenc_size(JencArgs a) {
+  __shared__ JencLut s;
+  __shared__ unsigned s_w[4];
+  jenc_load_lut(s);
+  const int g = blockIdx.x * JENC_TILE + threadIdx.x;
+  const long long f = blockIdx.y;
+  unsigned bits = 0;
+  if (g < a.nb) jenc_block_codes(a, s, a.coef + f * a.nb * 64, g, [&](unsigned, int count) { bits += (unsigned)count; });
+  unsigned total;
+  const unsigned at = vf_block_excl_scan<unsigned, 256>(bits, s_w, total);
+  if (g < a.nb) a.blk_off[f * a.nb + g] = at;
+  if (threadIdx.x == 0) a.tile_sum[f * a.tiles + blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void k_jenc_tile_scan(JencArgs a) {
+  __shared__ unsigned long long s_w[4];
+  const long long f = blockIdx.x;
+  unsigned long long run = 0;
+  for (int base = 0; base < a.tiles; base += 256) {
+    const int t = base + threadIdx.x;
+    const unsigned long long v = t < a.tiles ? a.tile_sum[f * a.tiles + t] : 0ull;
+    unsigned long long total;
+    const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(v, s_w, total);
+    if (t < a.tiles) a.tile_off[f * a.tiles + t] = run + e;
+    run += total;
+  }
+  if (threadIdx.x == 0) a.img_bits[f] = run;
+}
+
+// zeros under the image's stream and no further: the chunks (of the stuffing kernels) that hold any of its bits
+__global__ __launch_bounds__(256) void k_jenc_clear(JencArgs a) {
+  const long long f = blockIdx.y;
+  const unsigned long long begin = (unsigned long long)blockIdx.x * JENC_CHUNK;
+  if (begin >= (a.img_bits[f] + 7) >> 3) return;
+  ((uint4*)(a.stream + f * a.cap_words + (long long)(begin >> 2)))[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ __launch_bounds__(256) void k_jenc_write(JencArgs a) {
+  __shared__ JencLut s;
+  jenc_load_lut(s);
+  const int g = blockIdx.x * JENC_TILE + threadIdx.x;
+  const long long f = blockIdx.y;
+  if (g >= a.nb) return;
+  const unsigned long long at = a.tile_off[f * a.tiles + blockIdx.x] + a.blk_off[f * a.nb + g];
+  unsigned* dst = a.stream + f * a.cap_words + (long long)(at >> 5);
+  // the bits in front of the block inside its first dword belong to earlier blocks: they enter as zeros, and that dword is OR-ed
+  unsigned long long acc = 0;
+  int cnt = (int)(at & 31);
+  bool first = true;
+  jenc_block_codes(a, s, a.coef + f * a.nb * 64, g, [&](unsigned bits, int count) {
+    acc = acc << count | bits;
+    cnt += count;
+    if (cnt >= 32) {
+      cnt -= 32;
+      const unsigned word = (unsigned)(acc >> cnt);
+      if (first) atomicOr(dst, word);
+      else *dst = word;
+      first = false;
+      ++dst;
+      acc &= (1ull << cnt) - 1ull;
+    }
+  });
+  if (cnt) atomicOr(dst, (unsigned)(acc << (32 - cnt)));
+}
+
+// -------------------------------------------------------------------------------------------------------------- byte stuffing
+// The 16 stream bytes of a thread, the last byte of the stream padded with 1-bits: -> how many of them exist, b[] their values
+__device__ __forceinline__ int jenc_bytes16(const JencArgs& a, long long f, unsigned long long bits, unsigned long long pos, unsigned* b) {
+  const unsigned long long nbytes = (bits + 7) >> 3;
+  if (pos >= nbytes) return 0;
+  const uint4 u = *(const uint4*)(a.stream + f * a.cap_words + (long long)(pos >> 2));
+  const unsigned w[4] = {u.x, u.y, u.z, u.w};
+  const int have = (int)min(16ull, nbytes - pos);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) b[i] = (w[i >> 2] >> (24 - 8 * (i & 3))) & 255u;
+  if (pos + have == nbytes && (bits & 7)) {
+    const unsigned pad = (1u << (8 - (int)(bits & 7))) - 1u;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (i == have - 1) b[i] |= pad;
+  }
+  return have;
+}
+
+__global__ __launch_bounds__(256) void k_jenc_ff_count(JencArgs a) {
+  __shared__ unsigned s_w[4];
+  const long long f = blockIdx.y;
+  const unsigned long long bits = a.img_bits[f], begin = (unsigned long long)blockIdx.x * JENC_CHUNK;
+  if (begin >= (bits + 7) >> 3) return;
+  unsigned b[16];
+  const int have = jenc_bytes16(a, f, bits, begin + threadIdx.x * 16, b);
+  unsigned cnt = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) cnt += i < have && b[i] == 255u;
+  unsigned total;
+  vf_block_excl_scan<unsigned, 256>(cnt, s_w, total);
+  if (threadIdx.x == 0) a.ff_cnt[f * a.chunks + blockIdx.x] = total;
+}
+
+// one workgroup per image: 0xFF bytes in front of every chunk, and the file's size at offsets[f + 1] (summed by k_jenc_offsets)
+__global__ __launch_bounds__(256) void k_jenc_ff_scan(JencArgs a, int hdr_len) {
+  __shared__ unsigned long long s_w[4];
+  const long long f = blockIdx.x;
+  const unsigned long long nbytes = (a.img_bits[f] + 7) >> 3;
+  const long long used = (long long)((nbytes + JENC_CHUNK - 1) / JENC_CHUNK);
+  unsigned long long run = 0;
+  for (long long base = 0; base < used; base += 256) {
+    const long long c = base + threadIdx.x;
+    const unsigned long long v = c < used ? a.ff_cnt[f * a.chunks + c] : 0ull;
+    unsigned long long total;
+    const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(v, s_w, total);
+    if (c < used) a.ff_pref[f * a.chunks + c] = run + e;
+    run += total;
+  }
+  if (threadIdx.x == 0) a.offsets[f + 1] = (int64_t)(hdr_len + nbytes + run + 2);
+}
+
+// one workgroup: offsets[f] = sum of the sizes before file f (in: sizes at [f + 1])
+__global__ __launch_bounds__(256) void k_jenc_offsets(int64_t* offsets, int n) {
+  __shared__ unsigned long long s_w[4];
+  if (threadIdx.x == 0) offsets[0] = 0;
+  unsigned long long run = 0;
+  for (int base = 0; base < n; base += 256) {
+    const int f = base + threadIdx.x;
+    const unsigned long long v = f < n ? (unsigned long long)offsets[f + 1] : 0ull;
+    unsigned long long total;
+    const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(v, s_w, total);
+    if (f < n) offsets[f + 1] = (int64_t)(run + e + v);
+    run += total;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_jenc_stuff(JencArgs a, JencHdr hdr) {
+  __shared__ unsigned s_w[4];
+  const long long f = blockIdx.y;
+  const unsigned long long bits = a.img_bits[f], nbytes = (bits + 7) >> 3, begin = (unsigned long long)blockIdx.x * JENC_CHUNK;
+  if (begin >= nbytes) return;
+  unsigned char* file = a.out + a.offsets[f];
+  unsigned b[16];
+  const int have = jenc_bytes16(a, f, bits, begin + threadIdx.x * 16, b);
+  unsigned cnt = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) cnt += i < have && b[i] == 255u;
+  unsigned total;
+  const unsigned before = vf_block_excl_scan<unsigned, 256>(cnt, s_w, total);
+  unsigned char* dst = file + hdr.len + begin + a.ff_pref[f * a.chunks + blockIdx.x] + threadIdx.x * 16 + before;
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    if (i < have) {
+      *dst++ = (unsigned char)b[i];
+      if (b[i] == 255u) *dst++ = 0;
+    }
+  if (blockIdx.x == 0)
+    for (int i = threadIdx.x; i < hdr.len; i += 256) file[i] = (unsigned char)(hdr.w[i >> 2] >> (8 * (i & 3)));
+  if (begin + JENC_CHUNK >= nbytes && threadIdx.x == 0) {
+    const int64_t size = a.offsets[f + 1] - a.offsets[f];
+    file[size - 2] = 0xFF;
+    file[size - 1] = 0xD9;
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------------------------- host
+struct JencPlan {
+  int hs, vs, mcux, mcuy, bpm, nb, tiles, chunks;
+  long long cap_bytes;           // an image's unstuffed stream, a whole number of chunks
+  size_t o_coef, o_blk, o_tsum, o_toff, o_bits, o_stream, o_ffc, o_ffp, ws_bytes, out_bytes;
+};
+
+int jenc_plan(const char* who, int n, int H, int W, int C, int subsampling, JencPlan* p) {
+  VF_REQUIRE(C == 1 || C == 3, "%s: C = %d channels (a JPEG frame here is grey, 1 channel, or RGB, 3)", who, C);
+  VF_REQUIRE(H >= 1 && H <= JENC_MAX_SIDE, "%s: H = %d (sides are 1 to %d)", who, H, JENC_MAX_SIDE);
+  VF_REQUIRE(W >= 1 && W <= JENC_MAX_SIDE, "%s: W = %d (sides are 1 to %d)", who, W, JENC_MAX_SIDE);
+  VF_REQUIRE(n >= 1 && n <= 65535, "%s: n = %d frames (1 to 65535)", who, n);
+  VF_REQUIRE(C == 1 || (subsampling >= 0 && subsampling <= 2), "%s: subsampling = %d is not 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)", who,
+             subsampling);
+  p->hs = C == 3 && subsampling >= 1 ? 2 : 1;
+  p->vs = C == 3 && subsampling == 2 ? 2 : 1;
+  p->mcux = (int)vf_cdiv(W, 8 * p->hs);
+  p->mcuy = (int)vf_cdiv(H, 8 * p->vs);
+  p->bpm = C == 3 ? p->hs * p->vs + 2 : 1;
+  p->nb = p->mcux * p->mcuy * p->bpm;
+  p->tiles = (int)vf_cdiv(p->nb, JENC_TILE);
+  p->cap_bytes = vf_cdiv((long long)p->nb * (JENC_BLOCK_BITS / 8), JENC_CHUNK) * JENC_CHUNK;
+  p->chunks = (int)(p->cap_bytes / JENC_CHUNK);
+  const size_t blocks = (size_t)n * p->nb;
+  VfCarve ws;
+  p->o_coef = ws.take(blocks * 128);
+  p->o_blk = ws.take(blocks * 4);
+  p->o_tsum = ws.take((size_t)n * p->tiles * 4);
+  p->o_toff = ws.take((size_t)n * p->tiles * 8);
+  p->o_bits = ws.take((size_t)n * 8);
+  p->o_stream = ws.take((size_t)n * p->cap_bytes);
+  p->o_ffc = ws.take((size_t)n * p->chunks * 4);
+  p->o_ffp = ws.take((size_t)n * p->chunks * 8);
+  p->ws_bytes = ws.at;
+  // every block at its bound, every stream byte stuffed; header and EOI
+  p->out_bytes = (size_t)n * ((size_t)p->nb * (JENC_BLOCK_BITS / 8) * 2 + JENC_HDR_CAP + 2);
+  return 0;
+}
+
+struct JencHdrW {
+  unsigned char b[JENC_HDR_CAP];
+  int len = 0;
+  void put(int v) { b[len++] = (unsigned char)v; }
+  void put16(int v) { put(v >> 8); put(v & 255); }
+};
+
+// SOI, APP0 (JFIF 1.1, density 1:1), DQT per table, SOF0, DHT per table, SOS; -> the divisors too
+void jenc_header(int H, int W, int C, int quality, int hs, int vs, JencHdr* hdr, unsigned short quant[2][64]) {
+  const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+  unsigned char qt[2][64];
+  for (int t = 0; t < 2; ++t)
+    for (int k = 0; k < 64; ++k) {
+      const int v = (K_QUANT[t][k] * scale + 50) / 100;
+      qt[t][k] = (unsigned char)(v < 1 ? 1 : v > 255 ? 255 : v);
+      quant[t][k] = (unsigned short)(8 * qt[t][k]);
+    }
+  JencHdrW h;
+  h.put(0xFF); h.put(0xD8);
+  h.put(0xFF); h.put(0xE0); h.put16(16);
+  for (const char c : {'J', 'F', 'I', 'F', '\0'}) h.put(c);
+  h.put(1); h.put(1); h.put(0); h.put16(1); h.put16(1); h.put(0); h.put(0);
+  for (int t = 0; t < (C == 3 ? 2 : 1); ++t) {
+    h.put(0xFF); h.put(0xDB); h.put16(67); h.put(t);
+    for (int k = 0; k < 64; ++k) h.put(qt[t][k]);
+  }
+  h.put(0xFF); h.put(0xC0); h.put16(8 + 3 * C); h.put(8); h.put16(H); h.put16(W); h.put(C);
+  for (int c = 0; c < C; ++c) { h.put(c + 1); h.put(c == 0 ? hs << 4 | vs : 0x11); h.put(c == 0 ? 0 : 1); }
+  for (int t = 0; t < (C == 3 ? 2 : 1); ++t) {
+    h.put(0xFF); h.put(0xC4); h.put16(2 + 1 + 16 + 12); h.put(t);
+    for (int i = 0; i < 16; ++i) h.put(K_DC_BITS[t][i]);
+    for (int i = 0; i < 12; ++i) h.put(K_DC_VAL[i]);
+    h.put(0xFF); h.put(0xC4); h.put16(2 + 1 + 16 + 162); h.put(0x10 | t);
+    for (int i = 0; i < 16; ++i) h.put(K_AC_BITS[t][i]);
+    for (int i = 0; i < 162; ++i) h.put(K_AC_VAL[t][i]);
+  }
+  h.put(0xFF); h.put(0xDA); h.put16(6 + 2 * C); h.put(C);
+  for (int c = 0; c < C; ++c) { h.put(c + 1); h.put(c == 0 ? 0x00 : 0x11); }
+  h.put(0); h.put(63); h.put(0);
+  memset(hdr->w, 0, sizeof(hdr->w));
+  memcpy(hdr->w, h.b, (size_t)h.len);
+  hdr->len = h.len;
+}
+
+}  // namespace
+
+VF_API int vf_jpeg_encode_workspace_bytes(int n, int H, int W, int C, int subsampling, size_t* ws_bytes, size_t* out_bytes) {
+  JencPlan p;
+  if (int e = jenc_plan("vf_jpeg_encode_workspace_bytes", n, H, W, C, subsampling, &p)) return e;
+  if (ws_bytes) *ws_bytes = p.ws_bytes;
+  if (out_bytes) *out_bytes = p.out_bytes;
+  return 0;
+}
+
+VF_API int vf_jpeg_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling, void* ws,
+                          size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
+  JencPlan p;
+  if (int e = jenc_plan("vf_jpeg_encode", n, H, W, C, subsampling, &p)) return e;
+  VF_REQUIRE(kind == 0 || kind == 1, "vf_jpeg_encode: kind %d is not 0 (float N x C x H x W) or 1 (uint8 N x H x W x C)", kind);
+  VF_REQUIRE(quality >= 1 && quality <= 100, "vf_jpeg_encode: quality = %d (1 to 100)", quality);
+  VF_REQUIRE(ws_bytes >= p.ws_bytes, "vf_jpeg_encode: the workspace holds %zu bytes, %d frames of %dx%dx%d need %zu", ws_bytes, n, H, W, C,
+             p.ws_bytes);
+  VF_REQUIRE(out_cap >= p.out_bytes, "vf_jpeg_encode: the output holds %zu bytes, %d frames of %dx%dx%d may take %zu", out_cap, n, H, W, C,
+             p.out_bytes);
+  JencArgs a;
+  JencHdr hdr;
+  jenc_header(H, W, C, quality, p.hs, p.vs, &hdr, a.quant);
+  char* w = (char*)ws;
+  a.src = src;
+  a.coef = (short*)(w + p.o_coef);
+  a.blk_off = (unsigned*)(w + p.o_blk);
+  a.tile_sum = (unsigned*)(w + p.o_tsum);
+  a.tile_off = (unsigned long long*)(w + p.o_toff);
+  a.img_bits = (unsigned long long*)(w + p.o_bits);
+  a.stream = (unsigned*)(w + p.o_stream);
+  a.ff_cnt = (unsigned*)(w + p.o_ffc);
+  a.ff_pref = (unsigned long long*)(w + p.o_ffp);
+  a.out = out;
+  a.offsets = offsets;
+  a.cap_words = p.cap_bytes / 4;
+  a.n = n; a.H = H; a.W = W; a.C = C; a.hs = p.hs; a.vs = p.vs;
+  a.mcux = p.mcux; a.mcuy = p.mcuy; a.bpm = p.bpm; a.nb = p.nb;
+  a.wb = (int)vf_cdiv(W, 8); a.hb = (int)vf_cdiv(H, 8);
+  a.tiles = p.tiles; a.chunks = p.chunks;
+  const double px = (double)n * H * W * C, coef = (double)n * p.nb * 128;
+  const dim3 per_tile((unsigned)p.tiles, n), per_chunk((unsigned)p.chunks, n);
+  if (kind == 0) VF_LAUNCH_TIMED(ctx, "jpeg_enc_dct", 0.0, 4.0 * px + coef, k_jenc_dct<0>, per_tile, dim3(256), a);
+  else VF_LAUNCH_TIMED(ctx, "jpeg_enc_dct", 0.0, px + coef, k_jenc_dct<1>, per_tile, dim3(256), a);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_enc_size", 0.0, coef, k_jenc_size, per_tile, dim3(256), a);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_enc_scan", 0.0, 12.0 * n * p.tiles, k_jenc_tile_scan, dim3(n), dim3(256), a);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_enc_clear", 0.0, 0.0, k_jenc_clear, per_chunk, dim3(256), a);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_enc_write", 0.0, coef, k_jenc_write, per_tile, dim3(256), a);
+  VF_LAUNCH_CHECK();
+  {
+    VfProf prof(ctx, "jpeg_enc_stuff", 0.0, 0.0);
+    hipLaunchKernelGGL(k_jenc_ff_count, per_chunk, dim3(256), 0, ctx->stream, a);
+    VF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jenc_ff_scan, dim3(n), dim3(256), 0, ctx->stream, a, hdr.len);
+    VF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jenc_offsets, dim3(1), dim3(256), 0, ctx->stream, offsets, n);
+    VF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jenc_stuff, per_chunk, dim3(256), 0, ctx->stream, a, hdr);
+    VF_LAUNCH_CHECK();
+  }
+  return 0;
+}

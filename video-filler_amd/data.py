@@ -248,6 +248,32 @@ def encode_png(frames):
     return _files_from(*B.png_encode(B.from_host(t).contiguous()))
 
 
+# ------------------------------------------------------------------------------------------------ JPEG
+def encode_jpeg(frames, quality=75, subsampling="420"):
+    """image.save('x.jpg') / image.compressJPG of a batch of frames, encoded on the device in one call (vf_jpeg_encode): a
+    list of `bytes`, one whole baseline JFIF file per frame, byte for byte what libjpeg's default compression — Pillow's
+    save(format="JPEG", quality=quality, subsampling=...) — writes.  frames: uint8 N x H x W x C (taken as they are) or
+    float N x C x H x W (image.savePNG's rule, which is saveJPG's too: saturated to [0,1], times 255 in float32,
+    truncated); C = 1 (grey) or 3 (RGB, coded as YCbCr); host or device.  quality: 1 to 100.  subsampling: "420" (the
+    default of libjpeg and Pillow), "422" or "444"; grey frames ignore it.  The files are what decode_jpeg reads.  A bad
+    quality, subsampling, rank or dtype is a ValueError naming the argument.  One device-to-host copy brings the batch back."""
+    import numbers
+    from .backend import JPEG_SUBSAMPLING
+    if isinstance(quality, bool) or not isinstance(quality, numbers.Integral) or not 1 <= quality <= 100:
+        raise ValueError("encode_jpeg: quality=%r is not an integer from 1 to 100" % (quality,))
+    if subsampling not in JPEG_SUBSAMPLING:
+        raise ValueError("encode_jpeg: subsampling=%r is not one of %s" % (subsampling, ", ".join(map(repr, sorted(JPEG_SUBSAMPLING)))))
+    t = torch.as_tensor(frames)
+    if t.dim() != 4:
+        raise ValueError("encode_jpeg: frames of %d dimensions; a batch is uint8 N x H x W x C or float N x C x H x W" % t.dim())
+    if t.dtype != torch.uint8:
+        if not t.is_floating_point():
+            raise ValueError("encode_jpeg: frames of dtype %s; they are uint8 or float" % t.dtype)
+        t = t.float()
+    B = get_backend()
+    return _files_from(*B.jpeg_encode(B.from_host(t).contiguous(), int(quality), subsampling))
+
+
 # ------------------------------------------------------------------------------------------------- GIF (DESIGN 5.5)
 def encode_gif(clips, delay=10):
     """`convert -delay D frame_1.png ... clip.gif` of a batch of clips, encoded on the device in one call

@@ -133,6 +133,25 @@ def _write_files(paths, blobs):
     return paths
 
 
+def _save_frame_groups(who, ext, encode, dirname, outImages, inpaintImages, fullImages, named):
+    """save_frames and save_frames_jpg: dirname/<prefix>_%d.<ext> for every frame of every group, numbered from 1, all of
+    them through ONE call of `encode` (a batch -> a list of bytes).  -> the paths: pred, inpaint, orig, then the keywords',
+    frames innermost."""
+    import os
+    groups = [(p, t) for p, t in (("pred", outImages), ("inpaint", inpaintImages), ("orig", fullImages)) if t is not None]
+    groups += list(named.items())
+    assert groups, "%s: nothing to save" % who
+    prefixes = [p for p, _ in groups]
+    assert len(set(prefixes)) == len(prefixes), "%s: prefix given twice (%s); one would overwrite the other" % (who, ", ".join(prefixes))
+    B = get_backend()
+    ts = [B.from_host(torch.as_tensor(t)) for _, t in groups]
+    assert all(t.dim() == 4 for t in ts) and len({(t.dtype, tuple(t.shape[1:])) for t in ts}) == 1, \
+        "%s: the tensors of one call share one type and one frame size" % who
+    os.makedirs(dirname, exist_ok=True)
+    paths = [os.path.join(dirname, "%s_%d.%s" % (prefix, i + 1, ext)) for (prefix, _), t in zip(groups, ts) for i in range(t.shape[0])]
+    return _write_files(paths, encode(torch.cat(ts, 0)))
+
+
 def save_frames(dirname, outImages=None, inpaintImages=None, fullImages=None, **named):
     """test_vid_wholeim.lua:226-242 (and test_more_complex.lua:200-214): `image.save` of every frame of the three results
     of WholeImageInpainter as dirname/pred_%d.png, inpaint_%d.png and orig_%d.png, numbered from 1.  The directory is
@@ -140,20 +159,18 @@ def save_frames(dirname, outImages=None, inpaintImages=None, fullImages=None, **
     the files.  Tensors are predLen x nc x H x W in [0,1] (image.savePNG's truncating byte rule applies), or uint8
     predLen x H x W x nc.  Other prefixes go by keyword: save_frames(dirname, pred=out_pred) is test_vid.lua:138's
     pred_i.png.  Returns the paths, in the order pred, inpaint, orig (then the keywords'), frames innermost."""
-    import os
     from .data import encode_png
-    groups = [(p, t) for p, t in (("pred", outImages), ("inpaint", inpaintImages), ("orig", fullImages)) if t is not None]
-    groups += list(named.items())
-    assert groups, "save_frames: nothing to save"
-    prefixes = [p for p, _ in groups]
-    assert len(set(prefixes)) == len(prefixes), "save_frames: prefix given twice (%s); one would overwrite the other" % ", ".join(prefixes)
-    B = get_backend()
-    ts = [B.from_host(torch.as_tensor(t)) for _, t in groups]
-    assert all(t.dim() == 4 for t in ts) and len({(t.dtype, tuple(t.shape[1:])) for t in ts}) == 1, \
-        "save_frames: the tensors of one call share one type and one frame size"
-    os.makedirs(dirname, exist_ok=True)
-    paths = [os.path.join(dirname, "%s_%d.png" % (prefix, i + 1)) for (prefix, _), t in zip(groups, ts) for i in range(t.shape[0])]
-    return _write_files(paths, encode_png(torch.cat(ts, 0)))
+    return _save_frame_groups("save_frames", "png", encode_png, dirname, outImages, inpaintImages, fullImages, named)
+
+
+def save_frames_jpg(dirname, outImages=None, inpaintImages=None, fullImages=None, quality=75, subsampling="420", **named):
+    """save_frames with `image.save` given a .jpg name: dirname/pred_%d.jpg, inpaint_%d.jpg and orig_%d.jpg, the frames a
+    JPEG folder of the loaders holds.  Same tensors, same rules, same order of the returned paths; all frames are encoded
+    on the device in ONE call (data.encode_jpeg at `quality` and `subsampling`: libjpeg's default compression, byte for
+    byte) and the host only writes the files."""
+    from .data import encode_jpeg
+    return _save_frame_groups("save_frames_jpg", "jpg", lambda t: encode_jpeg(t, quality, subsampling), dirname, outImages,
+                              inpaintImages, fullImages, named)
 
 
 def save_gifs(name, outImages=None, inpaintImages=None, fullImages=None, delay=10, **named):
@@ -311,6 +328,15 @@ def save_sheet(path, x, **display_args):
     with open(path, "wb") as fh:
         fh.write(png)
     return path
+
+
+def display_jpeg(x, quality=75, **display_args):
+    """The payload of the training scripts' disp.image(x, ...) (train_vid_weighted.lua:553-588, train.lua likewise): the
+    contact sheet display_tensor builds of x, compressed as one JPEG on the device (data.encode_jpeg at `quality`, 4:2:0
+    for an RGB sheet; image.savePNG's byte rule is applied inside the encoder).  Returns the file's bytes."""
+    grid = display_tensor(x, **display_args)
+    (jpg,) = data.encode_jpeg(grid.unsqueeze(0), quality)
+    return jpg
 
 
 def save_clip_sheet(path, input_image, pred_image):
