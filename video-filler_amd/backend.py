@@ -254,6 +254,38 @@ def _joined(files):
     return b"".join(files), offs
 
 
+class _Stager:
+    """A batch decoder's two pinned staging buffers, used in turn: packing this batch overlaps the device work of the one
+    before, and waits only for the batch before that (its upload has then left the buffer).  take(nbytes) -> this turn's
+    buffer, grown on demand, 1 MiB at least; done(stream) marks the call that read it.  One per decoder."""
+
+    def __init__(self):
+        self.stage, self.event, self.turn = [None, None], [None, None], 0
+
+    def take(self, nbytes):
+        t = self.cur = self.turn
+        self.turn = 1 - t
+        if self.event[t] is not None:
+            self.event[t].synchronize()
+        if self.stage[t] is None or self.stage[t].numel() < nbytes:
+            self.stage[t] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        return self.stage[t]
+
+    def done(self, stream):
+        self.event[self.cur] = torch.cuda.Event()
+        self.event[self.cur].record(stream)
+
+
+def _frame_kind(frames):
+    """(kind, n, H, W, C) of a 4-D batch as the C-ABI takes it: kind 1 is uint8 N x H x W x C, kind 0 float32 N x C x H x W."""
+    if frames.dtype == torch.uint8:
+        kind, (n, H, W, Cc) = 1, frames.shape
+    else:
+        assert frames.dtype == torch.float32, "frames are uint8 N x H x W x C or float32 N x C x H x W"
+        kind, (n, Cc, H, W) = 0, frames.shape
+    return kind, n, H, W, Cc
+
+
 def png_decode_workspace_bytes(files, channels=None):
     """(device workspace bytes, host staging bytes) of one PNG batch (vf_png_decode_workspace_bytes; host only, no GPU
     needed).  channels: None (each file's own), 1 or 3.  ValueError, naming the image, for a malformed or unsupported
@@ -910,6 +942,29 @@ class HipBackend:
             setattr(self, attr, ws)
         return ws
 
+    def _decode(self, name, query, entry, files, sizes, query_args, call_args, *results):
+        """One batch-decoder call: the files back to back, image i's place in `out` from sizes[i], the bounds from `query`,
+        the stage's scratch and its staging buffer of this turn, then `entry`.  -> (out, out_offs, status)."""
+        n = len(files)
+        data, offs = _joined(files)
+        offs_p = offs.ctypes.data_as(C.c_void_p)
+        out_offs = np.zeros(n + 1, np.int64)
+        out_offs[1:] = np.cumsum(sizes)
+        ws_b, st_b = C.c_size_t(), C.c_size_t()
+        _lib.check(getattr(self.lib, query)(data, offs_p, n, *query_args, C.byref(ws_b), C.byref(st_b)))
+        ws = self._scratch(name, ws_b.value)
+        attr = "_%s_stager" % name
+        if not hasattr(self, attr):
+            setattr(self, attr, _Stager())
+        stager = getattr(self, attr)
+        stage = stager.take(st_b.value)
+        out = torch.empty(max(int(out_offs[-1]), 1), dtype=torch.uint8, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._c(entry, data, offs_p, n, *call_args, out_offs.ctypes.data_as(C.c_void_p), _ptr(out), C.c_void_p(stage.data_ptr()),
+                stage.numel(), _ptr(ws), ws.numel(), _ptr(status), *map(_ptr, results))
+        stager.done(torch.cuda.current_stream(self.device))
+        return out, out_offs, status
+
     # ---- baseline JPEG decode (vf_jpeg.hip, DESIGN.md 5.2)
     def jpeg_decode(self, files, channels=3, subseq_bytes=256, infos=None):
         """Decode a batch of supported JPEG files (bytes each) into one device uint8 buffer.  -> (out, offsets, status,
@@ -917,37 +972,11 @@ class HipBackend:
         per image and rounds (device int32[1]) the synchronisation rounds; both are valid once the stream gets there.
         infos: the files' jpeg_inspect results, if the caller has them.  The workspace query reads the headers only;
         vf_jpeg_decode is the one call that walks the scan data."""
-        n = len(files)
         shapes = infos if infos is not None else [jpeg_inspect(f, walk=False) for f in files]
-        sizes = [s["height"] * s["width"] * channels for s in shapes]
-        offs = np.zeros(n + 1, np.int64)
-        offs[1:] = np.cumsum([len(f) for f in files])
-        out_offs = np.zeros(n + 1, np.int64)
-        out_offs[1:] = np.cumsum(sizes)
-        data = b"".join(files)
-        ws_b, st_b = C.c_size_t(), C.c_size_t()
-        _lib.check(self.lib.vf_jpeg_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), n, subseq_bytes, C.byref(ws_b),
-                                                    C.byref(st_b)))
-        ws = self._scratch("jpeg", ws_b.value)
-        # two pinned staging buffers, used in turn: packing this batch overlaps the device work of the one before, and
-        # waits only for the batch before that (its upload has then left the buffer)
-        if not hasattr(self, "_jpeg_stage"):
-            self._jpeg_stage, self._jpeg_done, self._jpeg_turn = [None, None], [None, None], 0
-        t = self._jpeg_turn
-        self._jpeg_turn = 1 - t
-        if self._jpeg_done[t] is not None:
-            self._jpeg_done[t].synchronize()
-        stage = self._jpeg_stage[t]
-        if stage is None or stage.numel() < st_b.value:
-            self._jpeg_stage[t] = stage = torch.empty(max(st_b.value, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        out = torch.empty(max(int(out_offs[-1]), 1), dtype=torch.uint8, device=self.device)
-        status = torch.empty(n, dtype=torch.int32, device=self.device)
         rounds = torch.empty(1, dtype=torch.int32, device=self.device)
-        self._c("vf_jpeg_decode", data, offs.ctypes.data_as(C.c_void_p), n, channels, subseq_bytes,
-                out_offs.ctypes.data_as(C.c_void_p), _ptr(out), C.c_void_p(stage.data_ptr()), stage.numel(), _ptr(ws), ws.numel(),
-                _ptr(status), _ptr(rounds))
-        self._jpeg_done[t] = torch.cuda.Event()
-        self._jpeg_done[t].record(torch.cuda.current_stream(self.device))
+        out, out_offs, status = self._decode("jpeg", "vf_jpeg_workspace_bytes", "vf_jpeg_decode", files,
+                                             [s["height"] * s["width"] * channels for s in shapes], (subseq_bytes,),
+                                             (channels, subseq_bytes), rounds)
         return out, out_offs, status, rounds
 
     # ---- PNG decode (vf_png_decode.hip, DESIGN.md 5.6)
@@ -956,33 +985,10 @@ class HipBackend:
         image i is out[offsets[i]:offsets[i+1]] as H x W x C, C = channels or (None) the file's own after expansion;
         status (device int32[n]) holds VF_PNG_* per image, valid once the stream gets there.  infos: the files'
         png_inspect results, if the caller has them."""
-        n = len(files)
         shapes = infos if infos is not None else [png_inspect(f) for f in files]
-        sizes = [s["height"] * s["width"] * (channels or s["channels"]) for s in shapes]
-        data, offs = _joined(files)
-        out_offs = np.zeros(n + 1, np.int64)
-        out_offs[1:] = np.cumsum(sizes)
-        ws_b, st_b = C.c_size_t(), C.c_size_t()
-        _lib.check(self.lib.vf_png_decode_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), n, int(channels or 0),
-                                                          C.byref(ws_b), C.byref(st_b)))
-        ws = self._scratch("pngd", ws_b.value)
-        # two pinned staging buffers, used in turn, as jpeg_decode's
-        if not hasattr(self, "_pngd_stage"):
-            self._pngd_stage, self._pngd_done, self._pngd_turn = [None, None], [None, None], 0
-        t = self._pngd_turn
-        self._pngd_turn = 1 - t
-        if self._pngd_done[t] is not None:
-            self._pngd_done[t].synchronize()
-        stage = self._pngd_stage[t]
-        if stage is None or stage.numel() < st_b.value:
-            self._pngd_stage[t] = stage = torch.empty(max(st_b.value, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        out = torch.empty(max(int(out_offs[-1]), 1), dtype=torch.uint8, device=self.device)
-        status = torch.empty(n, dtype=torch.int32, device=self.device)
-        self._c("vf_png_decode", data, offs.ctypes.data_as(C.c_void_p), n, int(channels or 0), out_offs.ctypes.data_as(C.c_void_p),
-                _ptr(out), C.c_void_p(stage.data_ptr()), stage.numel(), _ptr(ws), ws.numel(), _ptr(status))
-        self._pngd_done[t] = torch.cuda.Event()
-        self._pngd_done[t].record(torch.cuda.current_stream(self.device))
-        return out, out_offs, status
+        return self._decode("pngd", "vf_png_decode_workspace_bytes", "vf_png_decode", files,
+                            [s["height"] * s["width"] * (channels or s["channels"]) for s in shapes], (int(channels or 0),),
+                            (int(channels or 0),))
 
     def png_bytes_to_float(self, t):
         """image.load(path, nc, 'float') on top of decoded bytes: a device uint8 tensor -> float32 of the same shape,
@@ -993,6 +999,15 @@ class HipBackend:
         self._c("vf_png_bytes_to_float", _ptr(t), _ptr(out), t.numel())
         return out
 
+    def _encode(self, entry, scratch_name, src, files, bytes_pair, *args):
+        """One encoder call: the stage's scratch and an output of bytes_pair's (workspace, bound) sizes, offsets[files + 1],
+        then `entry` with `args` behind the source.  -> (out, offsets)."""
+        ws = self._scratch(scratch_name, bytes_pair[0])
+        out = torch.empty(bytes_pair[1], dtype=torch.uint8, device=self.device)
+        offsets = torch.empty(files + 1, dtype=torch.int64, device=self.device)
+        self._c(entry, _ptr(src), *args, _ptr(ws), ws.numel(), _ptr(out), out.numel(), _ptr(offsets))
+        return out, offsets
+
     # ---- PNG encode (vf_png.hip, DESIGN.md 5.3)
     def png_encode(self, frames):
         """Encode a batch of frames of one size as PNG files on the device.  frames: device uint8 N x H x W x C (taken as
@@ -1000,17 +1015,8 @@ class HipBackend:
         or 3, contiguous.  -> (buffer, offsets): file i is buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8
         tensor of the upper bound's size, offsets a device int64[N + 1]; both are valid once the stream gets there."""
         assert frames.dim() == 4 and frames.is_contiguous() and frames.device == self.device
-        if frames.dtype == torch.uint8:
-            kind, (n, H, W, Cc) = 1, frames.shape
-        else:
-            assert frames.dtype == torch.float32, "frames are uint8 N x H x W x C or float32 N x C x H x W"
-            kind, (n, Cc, H, W) = 0, frames.shape
-        ws_b, out_b = png_workspace_bytes(n, H, W, Cc)
-        ws = self._scratch("png", ws_b)
-        out = torch.empty(out_b, dtype=torch.uint8, device=self.device)
-        offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-        self._c("vf_png_encode", _ptr(frames), kind, n, H, W, Cc, _ptr(ws), ws.numel(), _ptr(out), out.numel(), _ptr(offsets))
-        return out, offsets
+        kind, n, H, W, Cc = _frame_kind(frames)
+        return self._encode("vf_png_encode", "png", frames, n, png_workspace_bytes(n, H, W, Cc), kind, n, H, W, Cc)
 
     # ---- JPEG encode (vf_jpeg_enc.hip, DESIGN.md 5.8)
     def jpeg_encode(self, frames, quality=75, subsampling="420"):
@@ -1021,18 +1027,9 @@ class HipBackend:
         buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8 tensor of the upper bound's size, offsets a device
         int64[N + 1]; both are valid once the stream gets there."""
         assert frames.dim() == 4 and frames.is_contiguous() and frames.device == self.device
-        if frames.dtype == torch.uint8:
-            kind, (n, H, W, Cc) = 1, frames.shape
-        else:
-            assert frames.dtype == torch.float32, "frames are uint8 N x H x W x C or float32 N x C x H x W"
-            kind, (n, Cc, H, W) = 0, frames.shape
-        ws_b, out_b = jpeg_encode_workspace_bytes(n, H, W, Cc, subsampling)
-        ws = self._scratch("jpeg_enc", ws_b)
-        out = torch.empty(out_b, dtype=torch.uint8, device=self.device)
-        offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-        self._c("vf_jpeg_encode", _ptr(frames), kind, n, H, W, Cc, int(quality), JPEG_SUBSAMPLING.get(subsampling, -1), _ptr(ws), ws.numel(),
-                _ptr(out), out.numel(), _ptr(offsets))
-        return out, offsets
+        kind, n, H, W, Cc = _frame_kind(frames)
+        return self._encode("vf_jpeg_encode", "jpeg_enc", frames, n, jpeg_encode_workspace_bytes(n, H, W, Cc, subsampling),
+                            kind, n, H, W, Cc, int(quality), JPEG_SUBSAMPLING.get(subsampling, -1))
 
     # ---- GIF encode (vf_gif.hip, DESIGN.md 5.5)
     def gif_encode(self, clips, delay):
@@ -1042,19 +1039,10 @@ class HipBackend:
         buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8 tensor of the upper bound's size, offsets a device
         int64[G + 1]; both are valid once the stream gets there."""
         assert clips.dim() == 5 and clips.is_contiguous() and clips.device == self.device
-        if clips.dtype == torch.uint8:
-            kind, (g, n, H, W, Cc) = 1, clips.shape
-        else:
-            assert clips.dtype == torch.float32, "clips are uint8 G x N x H x W x 3 or float32 G x N x 3 x H x W"
-            kind, (g, n, Cc, H, W) = 0, clips.shape
+        (g, n), (kind, _, H, W, Cc) = clips.shape[:2], _frame_kind(clips.flatten(0, 1))
         if Cc != 3:
             raise ValueError("gif_encode: %d channels (a GIF frame here is RGB, 3)" % Cc)
-        ws_b, out_b = gif_workspace_bytes(g, n, H, W)
-        ws = self._scratch("gif", ws_b)
-        out = torch.empty(out_b, dtype=torch.uint8, device=self.device)
-        offsets = torch.empty(g + 1, dtype=torch.int64, device=self.device)
-        self._c("vf_gif_encode", _ptr(clips), kind, g, n, H, W, int(delay), _ptr(ws), ws.numel(), _ptr(out), out.numel(), _ptr(offsets))
-        return out, offsets
+        return self._encode("vf_gif_encode", "gif", clips, g, gif_workspace_bytes(g, n, H, W), kind, g, n, H, W, int(delay))
 
     # ---- contact sheets (vf_display.hip, DESIGN.md 5.4)
     def display_tensor(self, packed, padding=0, nrow=6, scaleeach=False, min=None, max=None, symmetric=False, saturate=True):
@@ -1086,11 +1074,7 @@ class HipBackend:
         gets there; one memset and one launch, whatever N."""
         assert a.dim() == 4 and a.shape == b.shape and a.dtype == b.dtype and a.is_contiguous() and b.is_contiguous()
         assert a.device == self.device and b.device == self.device
-        if a.dtype == torch.uint8:
-            kind, (n, H, W, Cc) = 1, a.shape
-        else:
-            assert a.dtype == torch.float32, "frames are uint8 N x H x W x C or float32 N x C x H x W"
-            kind, (n, Cc, H, W) = 0, a.shape
+        kind, n, H, W, Cc = _frame_kind(a)
         if mask is not None:
             assert mask.dtype == torch.uint8 and tuple(mask.shape) == (H, W) and mask.is_contiguous() and mask.device == self.device
         vh, vw = (H, W) if valid is None else valid

@@ -1,5 +1,6 @@
-// vf_block.h — block-wide primitives shared by the device-side I/O stages (vf_image, vf_jpeg, vf_jpeg_enc, vf_png, vf_gif;
-// DESIGN.md 5).
+// vf_block.h — what the device-side I/O stages share on the device (vf_image, vf_jpeg, vf_jpeg_enc, vf_png, vf_png_decode, vf_gif,
+// vf_metrics): the block-wide scan and fp64 sum, the file-offsets kernel of the encoders, image.savePNG's byte rule
+// and the one reader of a batch of frames through it.
 // vf_device.h stays the header of the MFMA and bf16-plane helpers; nothing on the training path includes this one.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -43,9 +44,43 @@ __device__ __forceinline__ double vf_block_sum_f64(double v, double* ssum) {
   return ssum[0];
 }
 
+// One block of THREADS threads: offsets[f] = sum of the sizes before file f, f = 0 .. n (in: the sizes at [f + 1], as the stage's
+// per-frame scan left them).  The last step of the PNG and JPEG encoders; vf_gif.hip's k_gif_offsets is this loop with every
+// frame placed and a header term per file.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_vf_file_offsets(int64_t* offsets, int n) {
+  __shared__ unsigned long long s_w[THREADS / 64];
+  if (threadIdx.x == 0) offsets[0] = 0;
+  unsigned long long run = 0;
+  for (int base = 0; base < n; base += THREADS) {
+    const int f = base + threadIdx.x;
+    const unsigned long long v = f < n ? (unsigned long long)offsets[f + 1] : 0ull;
+    unsigned long long total;
+    const unsigned long long e = vf_block_excl_scan<unsigned long long, THREADS>(v, s_w, total);
+    if (f < n) offsets[f + 1] = (int64_t)(run + e + v);
+    run += total;
+  }
+}
+template <int THREADS = 256>   // a template too: only the stages that call it hold the kernel
+static inline void vf_launch_file_offsets(hipStream_t stream, int64_t* offsets, int n) {
+  hipLaunchKernelGGL(k_vf_file_offsets<THREADS>, dim3(1), dim3(THREADS), 0, stream, offsets, n);
+}
+
 // image.savePNG on a float tensor: saturate to [0,1], times 255 in float32, then libpng's C cast, which
 // truncates; NaN -> 0 (fmaxf returns the operand that is a number)
 __device__ __forceinline__ unsigned vf_savepng_byte(float x) {
   const float v = fminf(fmaxf(x, 0.f), 1.f);
   return (unsigned)(int)(255.f * v);
+}
+
+// A batch of frames as the encoders and the scores take it, and byte (frame f, channel c, row y, column x) of it: float planar
+// N x C x H x W through vf_savepng_byte (KIND 0), or uint8 interleaved N x H x W x C as it is (KIND 1).  64-bit arithmetic: f is.
+struct VfFrames {
+  const void* src;
+  int H, W, C;
+};
+template <int KIND>
+__device__ __forceinline__ unsigned vf_frame_byte(const VfFrames& fr, long long f, int c, int y, int x) {
+  if constexpr (KIND == 1) return ((const unsigned char*)fr.src)[((f * fr.H + y) * fr.W + x) * fr.C + c];
+  else return vf_savepng_byte(((const float*)fr.src)[((f * fr.C + c) * fr.H + y) * fr.W + x]);
 }

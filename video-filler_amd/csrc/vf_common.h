@@ -207,6 +207,15 @@ struct VfCarve {
     return o;
   }
 };
+// What every vf_*_encode entry requires behind its plan, before any launch: a known kind of source and room for the plan's two
+// bounds.  who names the entry, ch the channel count as its message writes it ("C" or "3"), batch the geometry in words.
+static inline int vf_check_encode_entry(const char* who, int kind, const char* ch, const char* batch, size_t ws_bytes, size_t ws_need,
+                                        size_t out_cap, size_t out_need) {
+  VF_REQUIRE(kind == 0 || kind == 1, "%s: kind %d is not 0 (float N x %s x H x W) or 1 (uint8 N x H x W x %s)", who, kind, ch, ch);
+  VF_REQUIRE(ws_bytes >= ws_need, "%s: the workspace holds %zu bytes, %s need %zu", who, ws_bytes, batch, ws_need);
+  VF_REQUIRE(out_cap >= out_need, "%s: the output holds %zu bytes, %s may take %zu", who, out_cap, batch, out_need);
+  return 0;
+}
 #define VF_OOB 0x80000000u   // byte offset that is always out of range of a buffer descriptor (operands are < 2 GiB)
 
 // Descriptor tables of the one-launch-per-net kernels, built by the hosts (vf_net.hip; video-filler_amd/backend.py mirrors the

@@ -47,6 +47,8 @@ struct GifArgs {
 
 template <int KIND>
 __device__ __forceinline__ unsigned gif_rgb(const GifArgs& a, long long f, long long p) {   // r << 16 | g << 8 | b
+  // not through vf_frame_byte: a pixel is its index p here, never (y, x), and the three bytes of one share a base; the reader's
+  // three separate indices cost k_gif_table 5 % (profiles/codec_host_isa_compare.txt).  The byte rule is the shared one.
   if (KIND == 1) {
     const unsigned char* s = (const unsigned char*)a.src + (f * a.npix + p) * 3;
     return ((unsigned)s[0] << 16) | ((unsigned)s[1] << 8) | s[2];
@@ -397,7 +399,8 @@ __global__ __launch_bounds__(256) void k_gif_frame_scan(GifArgs a) {
   }
 }
 
-// one block: fpos[f] becomes the place of frame f in out, offsets[c] the place of file c
+// one block: fpos[f] becomes the place of frame f in out, offsets[c] the place of file c.  k_vf_file_offsets (vf_block.h) is the
+// plain case, one frame per file and no header term; this one also places every frame inside its file.
 __global__ __launch_bounds__(256) void k_gif_offsets(GifArgs a) {
   __shared__ unsigned long long s_w[4];
   const long long frames_all = (long long)a.clips * a.frames;
@@ -516,12 +519,10 @@ VF_API int vf_gif_encode(vf_ctx* ctx, const void* src, int kind, int clips, int 
                          size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
   GifPlan p;
   if (int e = gif_plan("vf_gif_encode", clips, frames, H, W, &p)) return e;
-  VF_REQUIRE(kind == 0 || kind == 1, "vf_gif_encode: kind %d is not 0 (float N x 3 x H x W) or 1 (uint8 N x H x W x 3)", kind);
   VF_REQUIRE(delay_cs >= 0 && delay_cs <= GIF_MAX_DELAY, "vf_gif_encode: a delay of %d centiseconds (0 to %d)", delay_cs, GIF_MAX_DELAY);
-  VF_REQUIRE(ws_bytes >= p.ws_bytes, "vf_gif_encode: the workspace holds %zu bytes, %d clips of %d frames of %dx%d need %zu", ws_bytes,
-             clips, frames, H, W, p.ws_bytes);
-  VF_REQUIRE(out_cap >= p.out_bytes, "vf_gif_encode: the output holds %zu bytes, %d clips of %d frames of %dx%d may take %zu", out_cap,
-             clips, frames, H, W, p.out_bytes);
+  char batch[64];
+  snprintf(batch, sizeof(batch), "%d clips of %d frames of %dx%d", clips, frames, H, W);
+  if (int e = vf_check_encode_entry("vf_gif_encode", kind, "3", batch, ws_bytes, p.ws_bytes, out_cap, p.out_bytes)) return e;
   GifArgs a;
   char* w = (char*)ws;
   a.src = src;

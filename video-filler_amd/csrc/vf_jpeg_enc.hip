@@ -8,8 +8,9 @@
 //   k_jenc_clear      zeros under each image's stream, as far as it goes.
 //   k_jenc_write      one thread per block: its codes at its bit offset into the zeroed stream.  A dword that lies wholly
 //                     inside a block is stored, the dwords at a block's two ends are OR-ed in.
-//   k_jenc_ff_count / k_jenc_ff_scan / k_jenc_offsets / k_jenc_stuff   0xFF bytes per chunk of 4096 stream bytes, their prefix
-//                     and the file sizes, the files' places, then header, stream with a 0x00 behind every 0xFF, 1-padding, EOI.
+//   k_jenc_ff_count / k_jenc_ff_scan / k_vf_file_offsets (vf_block.h) / k_jenc_stuff   0xFF bytes per chunk of 4096 stream bytes,
+//                     their prefix and the file sizes, the files' places, then header, stream with a 0x00 behind every 0xFF,
+//                     1-padding, EOI.
 // Nine launches whatever the batch; a file's bytes depend on its own frame, the quality and the sampling only.
 #include "vf_block.h"
 #include "vf_common.h"
@@ -120,16 +121,13 @@ __device__ __forceinline__ JencPos jenc_pos(const JencArgs& a, int g) {
 }
 
 // ---------------------------------------------------------------------------------------------------- samples, FDCT, quantiser
-template <int KIND>
-__device__ __forceinline__ int jenc_px(const JencArgs& a, long long f, int y, int x, int c) {
-  if (KIND == 1) return ((const unsigned char*)a.src)[((f * a.H + y) * a.W + x) * a.C + c];
-  return (int)vf_savepng_byte(((const float*)a.src)[((f * a.C + c) * a.H + y) * (long long)a.W + x]);
-}
 // jccolor.c, SCALEBITS 16
 template <int KIND>
 __device__ __forceinline__ int jenc_comp(const JencArgs& a, long long f, int y, int x, int comp) {
-  if (a.C == 1) return jenc_px<KIND>(a, f, y, x, 0);
-  const int r = jenc_px<KIND>(a, f, y, x, 0), g = jenc_px<KIND>(a, f, y, x, 1), b = jenc_px<KIND>(a, f, y, x, 2);
+  const VfFrames fr{a.src, a.H, a.W, a.C};
+  if (a.C == 1) return (int)vf_frame_byte<KIND>(fr, f, 0, y, x);
+  const int r = (int)vf_frame_byte<KIND>(fr, f, 0, y, x), g = (int)vf_frame_byte<KIND>(fr, f, 1, y, x);
+  const int b = (int)vf_frame_byte<KIND>(fr, f, 2, y, x);
   if (comp == 0) return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
   if (comp == 1) return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
   return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
@@ -378,7 +376,7 @@ __global__ __launch_bounds__(256) void k_jenc_ff_count(JencArgs a) {
   if (threadIdx.x == 0) a.ff_cnt[f * a.chunks + blockIdx.x] = total;
 }
 
-// one workgroup per image: 0xFF bytes in front of every chunk, and the file's size at offsets[f + 1] (summed by k_jenc_offsets)
+// one workgroup per image: 0xFF bytes in front of every chunk, and the file's size at offsets[f + 1] (summed by k_vf_file_offsets)
 __global__ __launch_bounds__(256) void k_jenc_ff_scan(JencArgs a, int hdr_len) {
   __shared__ unsigned long long s_w[4];
   const long long f = blockIdx.x;
@@ -394,21 +392,6 @@ __global__ __launch_bounds__(256) void k_jenc_ff_scan(JencArgs a, int hdr_len) {
     run += total;
   }
   if (threadIdx.x == 0) a.offsets[f + 1] = (int64_t)(hdr_len + nbytes + run + 2);
-}
-
-// one workgroup: offsets[f] = sum of the sizes before file f (in: sizes at [f + 1])
-__global__ __launch_bounds__(256) void k_jenc_offsets(int64_t* offsets, int n) {
-  __shared__ unsigned long long s_w[4];
-  if (threadIdx.x == 0) offsets[0] = 0;
-  unsigned long long run = 0;
-  for (int base = 0; base < n; base += 256) {
-    const int f = base + threadIdx.x;
-    const unsigned long long v = f < n ? (unsigned long long)offsets[f + 1] : 0ull;
-    unsigned long long total;
-    const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(v, s_w, total);
-    if (f < n) offsets[f + 1] = (int64_t)(run + e + v);
-    run += total;
-  }
 }
 
 __global__ __launch_bounds__(256) void k_jenc_stuff(JencArgs a, JencHdr hdr) {
@@ -537,12 +520,10 @@ VF_API int vf_jpeg_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, 
                           size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
   JencPlan p;
   if (int e = jenc_plan("vf_jpeg_encode", n, H, W, C, subsampling, &p)) return e;
-  VF_REQUIRE(kind == 0 || kind == 1, "vf_jpeg_encode: kind %d is not 0 (float N x C x H x W) or 1 (uint8 N x H x W x C)", kind);
   VF_REQUIRE(quality >= 1 && quality <= 100, "vf_jpeg_encode: quality = %d (1 to 100)", quality);
-  VF_REQUIRE(ws_bytes >= p.ws_bytes, "vf_jpeg_encode: the workspace holds %zu bytes, %d frames of %dx%dx%d need %zu", ws_bytes, n, H, W, C,
-             p.ws_bytes);
-  VF_REQUIRE(out_cap >= p.out_bytes, "vf_jpeg_encode: the output holds %zu bytes, %d frames of %dx%dx%d may take %zu", out_cap, n, H, W, C,
-             p.out_bytes);
+  char batch[64];
+  snprintf(batch, sizeof(batch), "%d frames of %dx%dx%d", n, H, W, C);
+  if (int e = vf_check_encode_entry("vf_jpeg_encode", kind, "C", batch, ws_bytes, p.ws_bytes, out_cap, p.out_bytes)) return e;
   JencArgs a;
   JencHdr hdr;
   jenc_header(H, W, C, quality, p.hs, p.vs, &hdr, a.quant);
@@ -582,7 +563,7 @@ VF_API int vf_jpeg_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, 
     VF_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_jenc_ff_scan, dim3(n), dim3(256), 0, ctx->stream, a, hdr.len);
     VF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_jenc_offsets, dim3(1), dim3(256), 0, ctx->stream, offsets, n);
+    vf_launch_file_offsets(ctx->stream, offsets, n);
     VF_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_jenc_stuff, per_chunk, dim3(256), 0, ctx->stream, a, hdr);
     VF_LAUNCH_CHECK();

@@ -37,22 +37,6 @@ struct MetArgs {
   int N, C, H, W, vh, vw, clip;
 };
 
-template <int KIND>
-__device__ __forceinline__ unsigned met_byte(const void* p, int64_t i) {
-  if constexpr (KIND == 0)
-    return vf_savepng_byte(static_cast<const float*>(p)[i]);
-  else
-    return static_cast<const unsigned char*>(p)[i];
-}
-// element (n, c, y, x) of a batch: float planar N x C x H x W (KIND 0) or uint8 N x H x W x C
-template <int KIND>
-__device__ __forceinline__ int64_t met_at(const MetArgs& p, int n, int c, int y, int x) {
-  if constexpr (KIND == 0)
-    return (((int64_t)n * p.C + c) * p.H + y) * p.W + x;
-  else
-    return (((int64_t)n * p.H + y) * p.W + x) * p.C + c;
-}
-
 // One window from its integer sums (n = 49).  10^4 C1 = 65025 and 10^4 C2 = 585225: the four factors are exact integers below
 // 2^53, so their conversions are exact; two IEEE divisions, one multiplication (the library is built with -ffp-contract=off and
 // without fast-math: nothing is fused or taken through a reciprocal), times 2^30 (exact), to nearest-even.
@@ -86,6 +70,7 @@ __global__ __launch_bounds__(256) void k_frame_metrics(const MetArgs p) {
   const int px = t & (MT - 1), py = (t >> 5) * 4;
   const int gx = x0 + px;
   const bool flick = p.clip && n > 0;
+  const VfFrames fa{p.a, p.H, p.W, p.C}, fb{p.b, p.H, p.W, p.C};
   unsigned hole = 0;                  // bit i: pixel i is valid and under the mask
   if (p.mask && gx < p.vw)
     for (int i = 0; i < 4; ++i)
@@ -100,9 +85,8 @@ __global__ __launch_bounds__(256) void k_frame_metrics(const MetArgs p) {
       const int y = y0 - 3 + r, x = x0 - 3 + col;
       unsigned va = 0, vb = 0;
       if (y >= 0 && y < p.vh && x >= 0 && x < p.vw) {
-        const int64_t at = met_at<KIND>(p, n, c, y, x);
-        va = met_byte<KIND>(p.a, at);
-        vb = met_byte<KIND>(p.b, at);
+        va = vf_frame_byte<KIND>(fa, n, c, y, x);
+        vb = vf_frame_byte<KIND>(fb, n, c, y, x);
       }
       s_a[r * MPITCH + col] = (unsigned char)va;
       s_b[r * MPITCH + col] = (unsigned char)vb;
@@ -156,8 +140,7 @@ __global__ __launch_bounds__(256) void k_frame_metrics(const MetArgs p) {
         const unsigned ad = (unsigned)(d < 0 ? -d : d);
         unsigned fl = 0;
         if (flick) {
-          const int64_t at = met_at<KIND>(p, n - 1, c, gy, gx);
-          const int e = d - ((int)met_byte<KIND>(p.a, at) - (int)met_byte<KIND>(p.b, at));
+          const int e = d - ((int)vf_frame_byte<KIND>(fa, n - 1, c, gy, gx) - (int)vf_frame_byte<KIND>(fb, n - 1, c, gy, gx));
           fl = (unsigned)(e < 0 ? -e : e);
         }
         for (int reg = 0; reg < (in_hole ? 2 : 1); ++reg) {

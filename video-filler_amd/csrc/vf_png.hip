@@ -4,7 +4,8 @@
 //   k_png_deflate   one block per PNG_CHUNK bytes of a frame's filtered stream: LZ77 matches from an LDS hash table (resolved by
 //                   position, so the result does not depend on which lane gets there first), a greedy parse, dynamic Huffman
 //                   codes, the bits, or a stored block if that is not smaller; the chunk's IDAT with its CRC-32, its Adler sums.
-//   k_png_frame_scan / k_png_offsets / k_png_pack   chunk and file offsets, the Adler-32 of every frame, the files back to back.
+//   k_png_frame_scan / k_vf_file_offsets (vf_block.h) / k_png_pack   chunk and file offsets, the Adler-32 of every frame, the
+//                   files back to back.
 // No window crosses a chunk, so chunks are independent and a file's bytes depend on its own frame only.
 #include "vf_block.h"
 #include "vf_common.h"
@@ -36,10 +37,11 @@ struct PngArgs {
 
 // ------------------------------------------------------------------------------------------------------------- filter
 template <int KIND>
-__device__ __forceinline__ int png_px(const PngArgs& a, long long f, int y, int i) {
-  if (KIND == 1) return ((const unsigned char*)a.src)[(f * a.H + y) * (long long)a.rb + i];
+__device__ __forceinline__ int png_px(const PngArgs& a, long long f, int y, int i) {   // byte i of row y
+  // interleaved bytes are the row already: W * C pixels of one channel.  Planar floats: pixel i / C, channel i % C
+  if (KIND == 1) return (int)vf_frame_byte<1>(VfFrames{a.src, a.H, a.rb, 1}, f, 0, y, i);
   const int x = a.C == 3 ? i / 3 : i, c = a.C == 3 ? i - 3 * x : 0;
-  return (int)vf_savepng_byte(((const float*)a.src)[((f * a.C + c) * a.H + y) * (long long)a.W + x]);
+  return (int)vf_frame_byte<0>(VfFrames{a.src, a.H, a.W, a.C}, f, c, y, x);
 }
 
 __device__ __forceinline__ int png_paeth(int a, int b, int c) {
@@ -584,7 +586,7 @@ __global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
 // --------------------------------------------------------------------------------------------------------------- pack
 constexpr int PNG_HEAD = 8 + 25, PNG_TAIL = 12;   // signature + IHDR; IEND
 
-// one block per frame: where each IDAT goes, the frame's Adler-32, the file's size (offsets[f + 1], summed by k_png_offsets)
+// one block per frame: where each IDAT goes, the frame's Adler-32, the file's size (offsets[f + 1], summed by k_vf_file_offsets)
 __global__ __launch_bounds__(256) void k_png_frame_scan(PngArgs a) {
   __shared__ unsigned s_w[4];
   const long long f = blockIdx.x;
@@ -623,21 +625,6 @@ __global__ __launch_bounds__(256) void k_png_frame_scan(PngArgs a) {
     }
     a.adler[f] = (unsigned)((s2 << 16) | s1);
     a.offsets[f + 1] = (int64_t)PNG_HEAD + run + PNG_TAIL;
-  }
-}
-
-// one block: offsets[f] = sum of the sizes before file f (in: sizes at [f + 1])
-__global__ __launch_bounds__(256) void k_png_offsets(int64_t* offsets, int n) {
-  __shared__ unsigned long long s_w[4];
-  if (threadIdx.x == 0) offsets[0] = 0;
-  unsigned long long run = 0;
-  for (int base = 0; base < n; base += 256) {
-    const int f = base + threadIdx.x;
-    const unsigned long long v = f < n ? (unsigned long long)offsets[f + 1] : 0ull;
-    unsigned long long total;
-    const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(v, s_w, total);
-    if (f < n) offsets[f + 1] = (int64_t)(run + e + v);
-    run += total;
   }
 }
 
@@ -720,11 +707,9 @@ VF_API int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, i
                          unsigned char* out, size_t out_cap, int64_t* offsets) {
   PngPlan p;
   if (int e = png_plan("vf_png_encode", n, H, W, C, &p)) return e;
-  VF_REQUIRE(kind == 0 || kind == 1, "vf_png_encode: kind %d is not 0 (float N x C x H x W) or 1 (uint8 N x H x W x C)", kind);
-  VF_REQUIRE(ws_bytes >= p.ws_bytes, "vf_png_encode: the workspace holds %zu bytes, %d frames of %dx%dx%d need %zu", ws_bytes, n, H, W, C,
-             p.ws_bytes);
-  VF_REQUIRE(out_cap >= p.out_bytes, "vf_png_encode: the output holds %zu bytes, %d frames of %dx%dx%d may take %zu", out_cap, n, H, W, C,
-             p.out_bytes);
+  char batch[64];
+  snprintf(batch, sizeof(batch), "%d frames of %dx%dx%d", n, H, W, C);
+  if (int e = vf_check_encode_entry("vf_png_encode", kind, "C", batch, ws_bytes, p.ws_bytes, out_cap, p.out_bytes)) return e;
   PngArgs a;
   a.src = src;
   a.stream = (unsigned char*)ws + p.o_stream;
@@ -746,7 +731,7 @@ VF_API int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, i
     VfProf prof(ctx, "png_pack", 0.0, 2.0 * stream);
     hipLaunchKernelGGL(k_png_frame_scan, dim3(n), dim3(256), 0, ctx->stream, a);
     VF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_png_offsets, dim3(1), dim3(256), 0, ctx->stream, offsets, n);
+    vf_launch_file_offsets(ctx->stream, offsets, n);
     VF_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_png_pack, dim3((unsigned)p.nchunks, n), dim3(256), 0, ctx->stream, a);
     VF_LAUNCH_CHECK();

@@ -26,8 +26,8 @@ CENTER_FILL = (117.0, 104.0, 123.0)      # train.lua:287-289
 
 
 # ------------------------------------------------------------------------------------------------ JPEG
-def _jpeg_bytes(item):
-    """bytes of one JPEG file given as bytes / bytearray / memoryview, a uint8 array or tensor, or a path."""
+def _file_bytes(item):
+    """bytes of one image file (JPEG, PNG) given as bytes / bytearray / memoryview, a uint8 array or tensor, or a path."""
     if isinstance(item, (bytes, bytearray, memoryview)):
         return bytes(item)
     if isinstance(item, (str, os.PathLike)):
@@ -36,15 +36,67 @@ def _jpeg_bytes(item):
     if isinstance(item, torch.Tensor):
         item = item.cpu().numpy()
     a = np.asarray(item)
-    assert a.dtype == np.uint8, "a JPEG file as an array is uint8"
+    assert a.dtype == np.uint8, "a file as an array is uint8"
     return a.tobytes()
+
+
+def _stacked(out, buf, dev):
+    """stack=True: the images of one shape as one N x H x W x C tensor — a view of the decoder's buffer `buf` when all of
+    them came from it (dev names them all: they lie back to back), else a copy."""
+    shapes = {tuple(t.shape) for t in out}
+    assert len(shapes) == 1, "stack=True needs images of one shape, got %s" % sorted(shapes)
+    if buf is not None and len(dev) == len(out):
+        return buf[:len(out) * out[0].numel()].view(len(out), *out[0].shape)
+    return torch.stack(out)
+
+
+def _decode_files(who, files, channels, fallback, inspect, refuse, run, status_names, corrupt_text, shape_of, stack):
+    """The batch decoders' host side.  inspect(file) -> its info, or ValueError; refuse(info, channels) -> why a supported
+    file goes to the fallback after all, or None; run(files, infos) -> (buffer, offsets, status) of the device decode;
+    shape_of(info) -> the image's H, W, C.  Files the device decoder does not take go to fallback(bytes) or raise
+    ValueError; every error names the item by its place in `files`."""
+    B = get_backend()
+    infos, dev, out = [], [], [None] * len(files)
+    for i, f in enumerate(files):
+        try:
+            info = inspect(f)
+        except ValueError as e:
+            raise ValueError("%s: item %d: %s" % (who, i, e)) from None
+        why = refuse(info, channels) if info["supported"] else info["reason"]
+        if why is not None:
+            if fallback is None:
+                raise ValueError("%s: item %d is not supported by the device decoder: %s" % (who, i, why))
+            img = torch.as_tensor(np.ascontiguousarray(fallback(f)))
+            if img.dim() == 2:
+                img = img.unsqueeze(-1)
+            assert img.dtype == torch.uint8 and img.dim() == 3 and (channels is None or img.shape[2] == channels), \
+                "fallback returns uint8 H x W x %s, got %s %s" % (channels or "C", img.dtype, tuple(img.shape))
+            out[i] = B.from_host(img).contiguous()
+            continue
+        infos.append(info)
+        dev.append(i)
+    buf = None
+    if dev:
+        try:
+            buf, offs, status = run([files[i] for i in dev], infos)
+        except VfError as e:   # found on the host while the batch was planned: nothing was launched
+            m = re.search(r"image (\d+)", str(e))
+            if m is None:
+                raise
+            raise ValueError("%s: item %d: %s" % (who, dev[int(m.group(1))], e)) from None
+        st = status.cpu().tolist()
+        for j, i in enumerate(dev):
+            if st[j] != 0:
+                raise ValueError("%s: item %d: %s (%s)" % (who, i, corrupt_text, status_names.get(st[j], st[j])))
+            out[i] = buf[offs[j]:offs[j + 1]].view(*shape_of(infos[j]))
+    return _stacked(out, buf, dev) if stack else out
 
 
 def jpeg_info(item):
     """The host-side inspection of one JPEG file (no GPU): dict(width, height, components, h_samp, v_samp,
     restart_interval, scan_begin, scan_end, supported, sof, segments, precision, reason).  ValueError if its headers
     cannot be parsed (truncated, no SOS)."""
-    return jpeg_inspect(_jpeg_bytes(item))
+    return jpeg_inspect(_file_bytes(item))
 
 
 def decode_jpeg(items, channels=3, stack=False, fallback=None, subseq_bytes=256):
@@ -59,50 +111,14 @@ def decode_jpeg(items, channels=3, stack=False, fallback=None, subseq_bytes=256)
     returns the decoded uint8 H x W x channels image; without it they raise ValueError naming the item and why.  A
     malformed file raises ValueError naming the item (before anything is launched when the headers or the restart
     markers show it; once the stream has synchronised when the entropy-coded data is corrupt)."""
-    B = get_backend()
     assert channels in (1, 3), "channels is 1 or 3"
-    files = [_jpeg_bytes(it) for it in items]
-    infos, dev, out = [], [], [None] * len(files)
-    for i, f in enumerate(files):
-        try:
-            info = jpeg_inspect(f, walk=False)   # the headers say whether it is supported; the decode walks the scan
-        except ValueError as e:
-            raise ValueError("decode_jpeg: item %d: %s" % (i, e)) from None
-        if info["supported"] and channels == 1 and info["components"] != 1:
-            info = dict(info, supported=False, reason="YCbCr file with channels=1")
-        if not info["supported"]:
-            if fallback is None:
-                raise ValueError("decode_jpeg: item %d is not supported by the device decoder: %s" % (i, info["reason"]))
-            img = torch.as_tensor(np.ascontiguousarray(fallback(f)))
-            if img.dim() == 2:
-                img = img.unsqueeze(-1)
-            assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == channels, \
-                "fallback returns uint8 H x W x %d, got %s %s" % (channels, img.dtype, tuple(img.shape))
-            out[i] = B.from_host(img).contiguous()
-            continue
-        infos.append(info)
-        dev.append(i)
-    buf = None
-    if dev:
-        try:
-            buf, offs, status, _ = B.jpeg_decode([files[i] for i in dev], channels, subseq_bytes, infos)
-        except VfError as e:   # found while walking the scan data (restart markers, fill bytes): nothing was launched
-            m = re.search(r"image (\d+)", str(e))
-            if m is None:
-                raise
-            raise ValueError("decode_jpeg: item %d: %s" % (dev[int(m.group(1))], e)) from None
-        st = status.cpu().tolist()
-        for j, i in enumerate(dev):
-            if st[j] != 0:
-                raise ValueError("decode_jpeg: item %d: corrupt entropy-coded data (%s)" % (i, JPEG_STATUS.get(st[j], st[j])))
-            out[i] = buf[offs[j]:offs[j + 1]].view(infos[j]["height"], infos[j]["width"], channels)
-    if not stack:
-        return out
-    shapes = {tuple(t.shape) for t in out}
-    assert len(shapes) == 1, "stack=True needs images of one size, got %s" % sorted(shapes)
-    if len(dev) == len(out):
-        return buf[:len(out) * out[0].numel()].view(len(out), *out[0].shape)
-    return torch.stack(out)
+    B = get_backend()
+    return _decode_files(
+        "decode_jpeg", [_file_bytes(it) for it in items], channels, fallback,
+        lambda f: jpeg_inspect(f, walk=False),   # the headers say whether it is supported; the decode walks the scan
+        lambda info, ch: "YCbCr file with channels=1" if ch == 1 and info["components"] != 1 else None,
+        lambda files, infos: B.jpeg_decode(files, channels, subseq_bytes, infos)[:3], JPEG_STATUS,
+        "corrupt entropy-coded data", lambda info: (info["height"], info["width"], channels), stack)
 
 
 # ------------------------------------------------------------------------------------------ PNG decode (DESIGN 5.6)
@@ -110,7 +126,7 @@ def png_info(item):
     """The host-side inspection of one PNG file (no GPU): dict(width, height, bit_depth, color_type, interlace, channels,
     idat_bytes, idat_chunks, palette_entries, trns_entries, supported, inflated_bytes, reason).  ValueError if the file
     is malformed (signature, chunk order, CRC, zlib header)."""
-    return png_inspect(_jpeg_bytes(item))
+    return png_inspect(_file_bytes(item))
 
 
 def decode_png(items, channels=None, stack=False, fallback=None, dtype="uint8"):
@@ -126,57 +142,25 @@ def decode_png(items, channels=None, stack=False, fallback=None, dtype="uint8"):
     returns the decoded uint8 H x W x C image; without it they raise ValueError naming the item and why.  A malformed
     file raises ValueError naming the item before anything is launched; a corrupt stream raises it, with the status,
     once the stream has synchronised."""
-    B = get_backend()
     assert channels in (None, 1, 3), "channels is None (the file's own), 1 or 3"
     assert dtype in ("uint8", "float"), "dtype is 'uint8' or 'float'"
-    files = [_jpeg_bytes(it) for it in items]
-    infos, dev, out = [], [], [None] * len(files)
-    for i, f in enumerate(files):
-        try:
-            info = png_inspect(f)
-        except ValueError as e:
-            raise ValueError("decode_png: item %d: %s" % (i, e)) from None
-        colour = info["color_type"] in (2, 3, 6)
-        if info["supported"] and channels == 1 and colour:
-            info = dict(info, supported=False, reason="colour file with channels=1")
-        if info["supported"] and channels is None and info["trns_entries"] and info["color_type"] != 3:
-            info = dict(info, supported=False, reason="tRNS on colour type %d with the file's channels" % info["color_type"])
-        if not info["supported"]:
-            if fallback is None:
-                raise ValueError("decode_png: item %d is not supported by the device decoder: %s" % (i, info["reason"]))
-            img = torch.as_tensor(np.ascontiguousarray(fallback(f)))
-            if img.dim() == 2:
-                img = img.unsqueeze(-1)
-            assert img.dtype == torch.uint8 and img.dim() == 3 and (channels is None or img.shape[2] == channels), \
-                "fallback returns uint8 H x W x %s, got %s %s" % (channels or "C", img.dtype, tuple(img.shape))
-            out[i] = B.from_host(img).contiguous()
-            continue
-        infos.append(info)
-        dev.append(i)
-    buf = None
-    if dev:
-        try:
-            buf, offs, status = B.png_decode([files[i] for i in dev], channels, infos)
-        except VfError as e:
-            m = re.search(r"image (\d+)", str(e))
-            if m is None:
-                raise
-            raise ValueError("decode_png: item %d: %s" % (dev[int(m.group(1))], e)) from None
-        st = status.cpu().tolist()
-        for j, i in enumerate(dev):
-            if st[j] != 0:
-                raise ValueError("decode_png: item %d: corrupt image data (%s)" % (i, PNG_STATUS.get(st[j], st[j])))
-            out[i] = buf[offs[j]:offs[j + 1]].view(infos[j]["height"], infos[j]["width"], channels or infos[j]["channels"])
-    if stack:
-        shapes = {tuple(t.shape) for t in out}
-        assert len(shapes) == 1, "stack=True needs images of one shape, got %s" % sorted(shapes)
-        if len(dev) == len(out):
-            out = buf[:len(out) * out[0].numel()].view(len(out), *out[0].shape)
-        else:
-            out = torch.stack(out)
-    if dtype == "float":
-        out = B.png_bytes_to_float(out) if stack else [B.png_bytes_to_float(t) for t in out]
-    return out
+    B = get_backend()
+
+    def refuse(info, ch):
+        if ch == 1 and info["color_type"] in (2, 3, 6):
+            return "colour file with channels=1"
+        if ch is None and info["trns_entries"] and info["color_type"] != 3:
+            return "tRNS on colour type %d with the file's channels" % info["color_type"]
+
+    out = _decode_files("decode_png", [_file_bytes(it) for it in items], channels, fallback, png_inspect, refuse,
+                        lambda files, infos: B.png_decode(files, channels, infos), PNG_STATUS, "corrupt image data",
+                        lambda info: (info["height"], info["width"], channels or info["channels"]), stack)
+    return _as_float(B, out) if dtype == "float" else out
+
+
+def _as_float(B, out):
+    """dtype="float" of the PNG decoders: b / 255 of one tensor or of each of a list."""
+    return B.png_bytes_to_float(out) if torch.is_tensor(out) else [B.png_bytes_to_float(t) for t in out]
 
 
 def decode_image(items, channels=3, stack=False, fallback=None, dtype="uint8"):
@@ -184,7 +168,7 @@ def decode_image(items, channels=3, stack=False, fallback=None, dtype="uint8"):
     JPEGs go to decode_jpeg and the PNGs to decode_png, one call each, and the results come back in the caller's order.
     ValueError naming the item for a file that is neither."""
     B = get_backend()
-    files = [_jpeg_bytes(it) for it in items]
+    files = [_file_bytes(it) for it in items]
     jpg, png = [], []
     for i, f in enumerate(files):
         if f[:2] == b"\xff\xd8":
@@ -207,12 +191,8 @@ def decode_image(items, channels=3, stack=False, fallback=None, dtype="uint8"):
         for i, t in zip(idx, got):
             out[i] = t
     if stack:
-        shapes = {tuple(t.shape) for t in out}
-        assert len(shapes) == 1, "stack=True needs images of one shape, got %s" % sorted(shapes)
-        out = torch.stack(out)
-    if dtype == "float":
-        out = B.png_bytes_to_float(out) if stack else [B.png_bytes_to_float(t) for t in out]
-    return out
+        out = _stacked(out, None, [])
+    return _as_float(B, out) if dtype == "float" else out
 
 
 def load_mask(item):
@@ -232,6 +212,21 @@ def _files_from(buf, offsets):
     return [host[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
 
 
+def _as_frames(who, frames, ndim):
+    """An encoder's input as a tensor of `ndim` dimensions: uint8 as it is, any float as float32.  ValueError naming the
+    encoder for another rank or dtype."""
+    t = torch.as_tensor(frames)
+    if t.dim() != ndim:
+        raise ValueError("%s: frames of %d dimensions; a batch is %s" % (who, t.dim(), {
+            4: "uint8 N x H x W x C or float N x C x H x W",
+            5: "uint8 G x N x H x W x 3 or float G x N x 3 x H x W (4-D: one clip)"}[ndim]))
+    if t.dtype != torch.uint8:
+        if not t.is_floating_point():
+            raise ValueError("%s: frames of dtype %s; they are uint8 or float" % (who, t.dtype))
+        t = t.float()
+    return t
+
+
 # ------------------------------------------------------------------------------------------------- PNG (DESIGN 5.3)
 def encode_png(frames):
     """image.save of a batch of frames as PNG, encoded on the device in one call (vf_png_encode): a list of `bytes`, one
@@ -239,12 +234,8 @@ def encode_png(frames):
     rule: saturated to [0,1], times 255 in float32, truncated); C = 1 (grey) or 3 (RGB); host or device.  Decoding a
     file gives exactly those bytes; the file bytes depend on the frame alone and are the same on every run.  One
     device-to-host copy brings the batch back."""
+    t = _as_frames("encode_png", frames, 4)
     B = get_backend()
-    t = torch.as_tensor(frames)
-    assert t.dim() == 4, "encode_png takes a batch: uint8 N x H x W x C or float N x C x H x W"
-    if t.dtype != torch.uint8:
-        assert t.is_floating_point(), "frames are uint8 or float"
-        t = t.float()
     return _files_from(*B.png_encode(B.from_host(t).contiguous()))
 
 
@@ -263,13 +254,7 @@ def encode_jpeg(frames, quality=75, subsampling="420"):
         raise ValueError("encode_jpeg: quality=%r is not an integer from 1 to 100" % (quality,))
     if subsampling not in JPEG_SUBSAMPLING:
         raise ValueError("encode_jpeg: subsampling=%r is not one of %s" % (subsampling, ", ".join(map(repr, sorted(JPEG_SUBSAMPLING)))))
-    t = torch.as_tensor(frames)
-    if t.dim() != 4:
-        raise ValueError("encode_jpeg: frames of %d dimensions; a batch is uint8 N x H x W x C or float N x C x H x W" % t.dim())
-    if t.dtype != torch.uint8:
-        if not t.is_floating_point():
-            raise ValueError("encode_jpeg: frames of dtype %s; they are uint8 or float" % t.dtype)
-        t = t.float()
+    t = _as_frames("encode_jpeg", frames, 4)
     B = get_backend()
     return _files_from(*B.jpeg_encode(B.from_host(t).contiguous(), int(quality), subsampling))
 
@@ -284,17 +269,9 @@ def encode_gif(clips, delay=10):
     (DESIGN 5.5 has the rule, which is this project's own, not ImageMagick's).  A file's bytes depend on its frames and
     the delay alone and are the same on every run.  One device-to-host copy brings the batch back."""
     t = torch.as_tensor(clips)
-    if t.dim() == 4:
-        t = t.unsqueeze(0)
-    if t.dim() != 5:
-        raise ValueError("encode_gif: a tensor of %d dimensions; clips are uint8 G x N x H x W x 3 or float G x N x 3 x H x W "
-                         "(4-D: one clip)" % t.dim())
+    t = _as_frames("encode_gif", t.unsqueeze(0) if t.dim() == 4 else t, 5)
     if int(delay) != delay or not 0 <= delay <= 65535:
         raise ValueError("encode_gif: delay=%r is not a whole number of centiseconds from 0 to 65535" % (delay,))
-    if t.dtype != torch.uint8:
-        if not t.is_floating_point():
-            raise ValueError("encode_gif: clips of type %s; they are uint8 or float" % t.dtype)
-        t = t.float()
     B = get_backend()
     return _files_from(*B.gif_encode(B.from_host(t).contiguous(), int(delay)))
 
