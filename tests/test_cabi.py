@@ -151,3 +151,53 @@ def test_shipped_code_objects_hold_no_packed_fma_with_a_high_dword_src1_select()
     assert chk.PK.search("v_pk_fma_f32 v[12:13], v[22:23], v[18:19], v[12:13] op_sel:[0,1,0]")
     m = chk.PK.search("v_pk_fma_f32 v[4:5], v[26:27], v[6:7], v[4:5] op_sel:[1,0,0]")
     assert m and not any(int(b) for b in m.group(2).split(",")[1:])
+
+
+def _csrc_sources(ext):
+    """{file name: text without comments} of video-filler_amd/csrc/*<ext>"""
+    csrc = os.path.join(ROOT, "video-filler_amd", "csrc")
+    out = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(ext):
+            with open(os.path.join(csrc, f)) as fh:
+                out[f] = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S))
+    return out
+
+
+def _file_scope_prototypes(text):
+    """Names of the vf_* functions `text` declares without defining: a statement that starts in column 0 with a return type and a
+    vf_ name, and whose balanced parenthesis is followed by `;` (a definition is followed by `{`)."""
+    names = []
+    for m in re.finditer(r'^(?!return\b|else\b|case\b)(?:extern\s+"C"\s+)?(?:[A-Za-z_][\w:]*[\s\*&]+)+(vf_\w+)\s*\(', text, flags=re.M):
+        depth, i = 1, m.end()
+        while depth and i < len(text):
+            depth += {"(": 1, ")": -1}.get(text[i], 0)
+            i += 1
+        if re.match(r"\s*;", text[i:]):
+            names.append(m.group(1))
+    return names
+
+
+def test_no_hip_file_declares_a_vf_function_by_hand():
+    """A function that one .hip file defines and another calls is declared in a header, never at the place of use: the library
+    links with undefined symbols allowed, so a prototype that drifts from its definition builds and fails only at load time."""
+    assert _file_scope_prototypes("int vf_a(int x,\n         float (*f)(int));\nstatic int vf_b(int x) {\n}\n") == ["vf_a"]
+    assert _file_scope_prototypes('extern "C" const float* vf_c(void);\n  int vf_d(int);\nreturn vf_e(1);\n') == ["vf_c"]
+    hips = _csrc_sources(".hip")
+    assert len(hips) >= 20
+    found = {f: p for f, p in ((f, _file_scope_prototypes(t)) for f, t in hips.items()) if p}
+    assert not found, "prototypes of vf_* functions in .hip files: %s" % found
+
+
+def test_every_internal_entry_is_declared_in_exactly_one_header():
+    """Every vf_internal_* name a .hip file uses has one prototype, in one header of csrc/."""
+    declared = {}
+    for f, text in _csrc_sources(".h").items():
+        for name in _file_scope_prototypes(text):
+            declared.setdefault(name, []).append(f)
+    used = set()
+    for text in _csrc_sources(".hip").values():
+        used |= set(re.findall(r"\bvf_internal_\w+", text))
+    assert len(used) >= 25
+    bad = {n: declared.get(n, []) for n in sorted(used) if len(declared.get(n, [])) != 1}
+    assert not bad, "vf_internal_* names not declared exactly once in a header: %s" % bad

@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "../../include/vf_hip.h"
+#include "vf_internal.h"
 
 #define VF_API extern "C" __attribute__((visibility("default")))
 
@@ -69,7 +70,6 @@ struct vf_ctx {
   VfBnRequest bn_pending;
   int bn_result_rows = 0;
 };
-void vf_internal_wg_free(vf_ctx* ctx);
 
 // A public forward / data-gradient entry point: moves the pending request out of the context before anything else, so that a
 // refused call leaves nothing behind for an unrelated later launch, and hands it to the pass as an argument.
@@ -186,7 +186,6 @@ struct VfPWGradGroup {
   int blk_off[VF_PWG_MAX + 1];  // multiples of 8 (the XCD-aware tile order of a layer assumes blockIdx % 8 == local id % 8)
   VfPWGrad d[VF_PWG_MAX];
 };
-int vf_internal_pwgrad_group(vf_ctx* ctx, const VfPWGradGroup& G, int blocks, const char* name, double flops);
 
 static inline int vf_ilog2(int v) {  // v must be a power of two
   int l = 0;
@@ -242,12 +241,6 @@ struct VfWpDesc {
 };
 static_assert(sizeof(VfWpDesc) == 48, "descriptor layout is shared with the host mirror");
 
-// The split-K combine of the GEMM hosts (vf_conv.hip), plain or leaving BatchNorm statistics partials (st), and whether a shape
-// fits the latter
-int vf_internal_slab_reduce(vf_ctx* ctx, const float* slab, float* dst, const float* bias, int64_t total, int N, int ksplit, int act,
-                            float slope, const float* dmask, int dact, float dslope, const VfBnSt* st, int st_groups);
-bool vf_internal_slab_st_ok(int64_t total, int N, int groups, int rows_cap, int* blocks_per_group);
-
 // The statistics plan of a GEMM launch (launch_igemm's IGemm, launch_pconv's PGemm; g.ksplit is set, bm x . tiles in gm rows,
 // zpar parity classes).  With one K range per tile the epilogue leaves a partial row per row tile and parity class, where the
 // batch groups are whole tiles; under split-K the slab reduce leaves them (returns true: the combine gets &g.st).  A shape that
@@ -276,31 +269,6 @@ static inline bool vf_plan_bn_stats(VfConvExtras* ex, G& g, int bm, int gm, int 
   }
   return g.ksplit > 1;
 }
-
-// The conv entry points with their extras as an argument (ex is never NULL); the C-ABI forms wrap them (vf_take_pending)
-int vf_internal_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
-                           int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex);
-int vf_internal_conv2d_fwd_planes(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B, int H,
-                                  int W, int Cin, int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex);
-int vf_internal_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin, int Cout, int k,
-                                int stride, int pad, VfConvExtras* ex);
-int vf_internal_conv2d_bwd_data_act(vf_ctx* ctx, const float* gy, const float* w, float* gx, const float* x_act, int act, float slope,
-                                    int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, VfConvExtras* ex);
-int vf_internal_conv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes, float* gw,
-                                  float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, float beta,
-                                  const VfConvExtras* ex);
-int vf_internal_deconv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
-                             int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex);
-int vf_internal_deconv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin, int Cout, int k,
-                                  int stride, int pad, VfConvExtras* ex);
-int vf_internal_pconv_gather(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
-                             int Cout, int act, float slope, VfConvExtras* ex);
-int vf_internal_pconv_scatter(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
-                              int Cout, int act, float slope, const float* dmask, int dact, float dslope, VfConvExtras* ex);
-// a BatchNorm request as vf_bn_fuse_next_fwd / _bwd form it (vf_conv.hip)
-int vf_internal_bn_request_fwd(VfBnRequest* r, const float* shift, double* part, int part_rows_cap, int groups);
-int vf_internal_bn_request_bwd(VfBnRequest* r, const float* x, const float* y_act, int act, float slope, const float* save_mean,
-                               double* part, int part_rows_cap, int groups);
 
 // optim/adam.lua's element update, fp32 in the reference's operation order (one definition for k_adam and for the weight-gradient
 // kernel that applies it in its epilogue, vf_wgrad_small.hip): step = lr * sqrt(1 - b2^t) / (1 - b1^t)
@@ -332,8 +300,6 @@ struct VfFusedLayer {
   int row0, ldu;
 };
 #define VF_FUSED_MAX 4
-int vf_internal_adam_fused_multi(vf_ctx* ctx, const VfFusedLayer* layers, int nl, double beta1, double beta2, double eps,
-                                 const int32_t* t_dev);
 
 // fused activation
 __device__ __forceinline__ float vf_act_apply(float v, int act, float slope) {

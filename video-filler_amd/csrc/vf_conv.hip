@@ -1323,8 +1323,6 @@ static void launch_igemm_tile(vf_ctx* ctx, const IGemm& g, dim3 grid, bool bkm, 
 
 // vecA / vecB: 16-byte loads legal for the A / B operand.  ex: the extras of the pass whose output tensor this launch writes
 // (BatchNorm statistics: vf_plan_bn_stats); NULL for an inner GEMM into a column buffer.
-int vf_internal_smallm_plan(int form, int M, int N, int K, size_t ws_bytes);                                                   // vf_smallm.hip
-int vf_internal_smallm_launch(vf_ctx* ctx, int form, const float* A, const float* W, float* slab, int M, int N, int K, int ksplit);
 static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, VfConvExtras* ex) {
   const int zpar = g.parity ? 4 : 1;
   const bool bkm = g.wsN == 1 && g.wsC != 1;
@@ -1497,23 +1495,28 @@ VF_API int vf_bn_fuse_result(vf_ctx* ctx, int* rows_per_group) {
   return 0;
 }
 
-static int check_conv_args(int B, int H, int W, int Cin, int Cout, int k, int stride, int pad) {
-  VF_REQUIRE(k == 4, "only 4x4 kernels are built by the reference (got k=%d)", k);
-  VF_REQUIRE((stride == 2 && pad == 1) || (stride == 1 && pad == 0), "unsupported stride/pad %d/%d", stride, pad);
-  VF_REQUIRE(B > 0 && Cin > 0 && Cout > 0, "bad sizes B=%d Cin=%d Cout=%d", B, Cin, Cout);
-  VF_REQUIRE(vf_is_pow2(H) && vf_is_pow2(W), "spatial sizes must be powers of two (got %dx%d)", H, W);
-  if (stride == 1) VF_REQUIRE(H >= 4 && W >= 4, "4x4 stride-1 conv needs H,W >= 4");
-  if (stride == 2) VF_REQUIRE(H >= 2 && W >= 2, "stride-2 conv needs H,W >= 2");
-  VF_REQUIRE((int64_t)Cin * Cout * 16 < ((int64_t)1 << 31), "weight tensor too large for 32-bit element offsets");
+static int check_conv_args(const VfConvShape& s) {
+  VF_REQUIRE(s.k == 4, "only 4x4 kernels are built by the reference (got k=%d)", s.k);
+  VF_REQUIRE((s.stride == 2 && s.pad == 1) || (s.stride == 1 && s.pad == 0), "unsupported stride/pad %d/%d", s.stride, s.pad);
+  VF_REQUIRE(s.B > 0 && s.Cin > 0 && s.Cout > 0, "bad sizes B=%d Cin=%d Cout=%d", s.B, s.Cin, s.Cout);
+  VF_REQUIRE(s.pow2_map(), "spatial sizes must be powers of two (got %dx%d)", s.H, s.W);
+  if (s.stride == 1) VF_REQUIRE(s.H >= 4 && s.W >= 4, "4x4 stride-1 conv needs H,W >= 4");
+  if (s.stride == 2) VF_REQUIRE(s.H >= 2 && s.W >= 2, "stride-2 conv needs H,W >= 2");
+  VF_REQUIRE((int64_t)s.Cin * s.Cout * 16 < ((int64_t)1 << 31), "weight tensor too large for 32-bit element offsets");
+  return 0;
+}
+static int check_full_conv_args(const VfConvShape& s) {
+  VF_REQUIRE(s.main_net_taps(), "unsupported full-conv shape");
+  VF_REQUIRE(s.pow2_map(), "spatial sizes must be powers of two");
   return 0;
 }
 
 // Generic "conv-like" pass: Y[b,oy,ox,n] = sum_{kh,kw,c} A[b, oy*s-pad+kh, ox*s-pad+kw, c] * Wt(n,kh,kw,c)
 // (conv forward: A = x, n = Cout, weights [n][kh][kw][c];  full-conv data-grad: A = gy, n = Cin_full,
-//  weights [n][kh][kw][c] as well — same physical layout by construction.)
-static int conv_like_fwd(vf_ctx* ctx, const float* A, const float* w, const float* bias, float* Y, int B, int Hi, int Wi,
-                         int C, int N, int stride, int pad, int act, float slope, VfConvExtras* ex) {
-  const int Ho = (Hi + 2 * pad - 4) / stride + 1, Wo = (Wi + 2 * pad - 4) / stride + 1;
+//  weights [n][kh][kw][c] as well — same physical layout by construction.)  s: the pass as a conv (k = 4), A on its H x W map.
+static int conv_like_fwd(vf_ctx* ctx, const float* A, const float* w, const float* bias, float* Y, const VfConvShape& s, int act,
+                         float slope, VfConvExtras* ex) {
+  const int B = s.B, Hi = s.H, Wi = s.W, C = s.Cin, N = s.Cout, stride = s.stride, pad = s.pad, Ho = s.out_h(), Wo = s.out_w();
   VF_REQUIRE(vf_is_pow2(Ho) && vf_is_pow2(Wo), "output spatial sizes must be powers of two");
   if (N == 1 && stride == 1 && Hi == 4 && Wi == 4) {
     hipLaunchKernelGGL(k_dot_fwd, dim3(B), dim3(256), 0, ctx->stream, A, w, bias, Y, 16 * C, act, slope);
@@ -1537,15 +1540,13 @@ static int conv_like_fwd(vf_ctx* ctx, const float* A, const float* w, const floa
 }
 
 // Generic "transposed" pass: Y[b,oh,ow,n] = sum_{kh,kw,c : oh = 2i-1+kh ...} A[b,i,j,c] * Wt[c][kh][kw][n]
-// (conv data-grad: A = gy, c = Cout, n = Cin;  full-conv forward: A = x, c = Cin_full, n = Cout_full.)
-extern "C" int vf_act_bwd(vf_ctx* ctx, const float* y, const float* gy, float* gx, int64_t n, int act, float slope);
-int vf_internal_deconv_thin_out(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int Hi, int Wi, int C,
-                                int N, int act, float slope);      // vf_conv_thin.hip
-static int conv_like_bwd(vf_ctx* ctx, const float* A, const float* w, const float* bias, float* Y, int B, int Hi, int Wi,
-                         int C, int N, int stride, int pad, int act, float slope, VfConvExtras* ex, const float* dmask = nullptr,
-                         int dact = 0, float dslope = 0.f) {
+// (conv data-grad: A = gy, c = Cout, n = Cin;  full-conv forward: A = x, c = Cin_full, n = Cout_full.)  s: the pass as a
+// full-conv (k = 4), A on its H x W map.
+static int conv_like_bwd(vf_ctx* ctx, const float* A, const float* w, const float* bias, float* Y, const VfConvShape& s, int act,
+                         float slope, VfConvExtras* ex, const float* dmask = nullptr, int dact = 0, float dslope = 0.f) {
+  const int B = s.B, Hi = s.H, Wi = s.W, C = s.Cin, N = s.Cout, stride = s.stride, pad = s.pad;
   if (stride == 2 && pad == 1 && N <= 4 && !dmask && !ex->bn.st.mode) {      // the image side: direct kernel, no column matrix
-    const int rc = vf_internal_deconv_thin_out(ctx, A, w, bias, Y, B, Hi, Wi, C, N, act, slope);
+    const int rc = vf_internal_deconv_thin_out(ctx, A, w, bias, Y, s, act, slope);
     if (rc >= 0) return rc;
   }
   IGemm g;
@@ -1611,19 +1612,16 @@ static int conv_like_bwd(vf_ctx* ctx, const float* A, const float* w, const floa
     vecB = ((16 * N) % 4 == 0) && vf_aligned16(w);
   }
   VF_REQUIRE(!(dmask && bias), "activation-backward epilogue is for data-gradient passes (no bias)");
-  const float* real_bias = bias;
-  const int real_act = act;
   if (stride == 1 && bias) {  // bias index = column % N: apply bias + activation in a pointwise pass
     g.bias = nullptr;
     g.act = VF_ACT_NONE;
   }
   // (the 1x1 -> 4x4 form's GEMM columns are (kh, kw, n): not one channel per column, so no statistics by-product there)
   if (int rc = launch_igemm(ctx, g, vecA, vecB, stride == 2 ? ex : nullptr)) return rc;
-  if (stride == 1 && real_bias) {
+  if (stride == 1 && bias) {
     const int64_t total = (int64_t)B * 16 * N;
     const int nb = (int)std::min<int64_t>(vf_cdiv(total, 256), 4096);
-    hipLaunchKernelGGL(k_slab_reduce, dim3(nb), dim3(256), 0, ctx->stream, (const float*)Y, Y, real_bias, total, N, 0,
-                       real_act, slope, 1.f);
+    hipLaunchKernelGGL(k_slab_reduce, dim3(nb), dim3(256), 0, ctx->stream, (const float*)Y, Y, bias, total, N, 0, act, slope, 1.f);
     VF_LAUNCH_CHECK();
   }
   return 0;
@@ -1816,9 +1814,12 @@ VF_API int vf_wgrad_group_end_partial(vf_ctx* ctx, int count) {
   return rc;
 }
 
-int vf_internal_wgrad_smallk(vf_ctx* ctx, const float* U, const float* V, float* dW, int K, int Nu, int Ncols, float beta);  // vf_wgrad_small.hip
-static int wgrad(vf_ctx* ctx, const float* U, const float* V, float* dW, int B, int Hl, int Wl, int Nu, int Hv, int Wv,
-                 int Cv, int stride, int pad, float beta, int ntaps = 16, const void* Up = nullptr, const void* Vp = nullptr) {
+// s: the layer; U lives on its low-resolution map, V on the other (conv: gradOutput, input; full: input, gradOutput); Up / Vp: planes or NULL
+static int wgrad(vf_ctx* ctx, const float* U, const float* V, float* dW, const VfConvShape& s, bool full, float beta, const void* Up,
+                 const void* Vp) {
+  const int B = s.B, stride = s.stride, pad = s.pad, ntaps = 16;
+  const int Hl = full ? s.H : s.out_h(), Wl = full ? s.W : s.out_w(), Nu = full ? s.Cin : s.Cout;
+  const int Hv = full ? s.full_out_h() : s.H, Wv = full ? s.full_out_w() : s.W, Cv = full ? s.Cout : s.Cin;
   // the bottleneck pair (1x1 map on one side, 4x4 on the other): dW = U^T V with K = batch — write-bound, its own kernel
   if (Hl == 1 && Wl == 1 && Hv == 4 && Wv == 4 && stride == 1 && pad == 0 && ntaps == 16) {
     const int rc = vf_internal_wgrad_smallk(ctx, U, V, dW, B, Nu, 16 * Cv, beta);
@@ -1965,164 +1966,128 @@ static int wgrad(vf_ctx* ctx, const float* U, const float* V, float* dW, int B, 
   return 0;
 }
 
-int vf_internal_colsum(vf_ctx* ctx, const float* g, float* gb, int64_t P, int C, float beta);  // vf_bn.hip
-static int bias_grad(vf_ctx* ctx, const float* g, float* gb, int64_t P, int C, float beta) {
-  return vf_internal_colsum(ctx, g, gb, P, C, beta);
-}
-
-// ------------------------------------------------------------------------------------------------ C ABI
-// The option branches' convolutions (5x5 stride 2 pad 2 / 34, 1x1: train.lua:109-113,158-170) go to vf_conv_generic.hip.
-int vf_internal_gconv_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
-                          int Cout, int k, int stride, int pad, int act, float slope);
-int vf_internal_gconv_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin, int Cout,
-                               int k, int stride, int pad);
-int vf_internal_gconv_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, int B, int H, int W, int Cin,
-                                 int Cout, int k, int stride, int pad, float beta);
-static bool main_net_shape(int H, int W, int k, int stride, int pad) {
-  return k == 4 && ((stride == 2 && pad == 1) || (stride == 1 && pad == 0 && H == 4 && W == 4)) && vf_is_pow2(H) && vf_is_pow2(W);
-}
-
+// ----------------------------------------- C ABI: every entry builds its VfConvShape and calls the internal form
 // 1 if this geometry runs on the matrix-core kernels, 0 if vf_conv_generic.hip serves it (include/vf_hip.h, "Shapes")
-VF_API int vf_conv_is_fast(int H, int W, int k, int stride, int pad) { return main_net_shape(H, W, k, stride, pad) ? 1 : 0; }
+VF_API int vf_conv_is_fast(int H, int W, int k, int stride, int pad) { return VfConvShape{0, H, W, 0, 0, k, stride, pad}.matrix_core_conv(); }
 
-int vf_internal_conv_thin_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B, int H,
-                              int W, int Cin, int Cout, int act, float slope, VfConvExtras* ex);      // vf_conv_thin.hip
-int vf_internal_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
-                           int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex) {
-  if (!main_net_shape(H, W, k, stride, pad)) return vf_internal_gconv_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, k, stride, pad, act, slope);
-  if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
-  if (stride == 2 && Cin == 3 && !ex->bn.st.mode) {      // the image-side layers: direct convolution (vf_conv_thin.hip)
-    const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, nullptr, B, H, W, Cin, Cout, act, slope, ex);
+int vf_internal_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, const VfConvShape& s, int act,
+                           float slope, VfConvExtras* ex) {
+  if (!s.matrix_core_conv()) return vf_internal_gconv_fwd(ctx, x, w, bias, y, s, act, slope);
+  if (int rc = check_conv_args(s)) return rc;
+  if (s.stride == 2 && s.Cin == 3 && !ex->bn.st.mode) {      // the image-side layers: direct convolution (vf_conv_thin.hip)
+    const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, nullptr, s, act, slope, ex);
     if (rc >= 0) return rc;
   }
-  return conv_like_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, stride, pad, act, slope, ex);
+  return conv_like_fwd(ctx, x, w, bias, y, s, act, slope, ex);
 }
 VF_API int vf_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
                          int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
-  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
-    return vf_internal_conv2d_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, k, stride, pad, act, slope, ex);
-  });
+  const VfConvShape s{B, H, W, Cin, Cout, k, stride, pad};
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) { return vf_internal_conv2d_fwd(ctx, x, w, bias, y, s, act, slope, ex); });
 }
 
-int vf_internal_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin, int Cout, int k,
-                                int stride, int pad, VfConvExtras* ex) {
-  if (!main_net_shape(H, W, k, stride, pad)) return vf_internal_gconv_bwd_data(ctx, gy, w, gx, B, H, W, Cin, Cout, k, stride, pad);
-  if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
-  const int Ho = (H + 2 * pad - 4) / stride + 1, Wo = (W + 2 * pad - 4) / stride + 1;
-  if (stride == 1) {
-    VF_REQUIRE(H == 4 && W == 4, "stride-1 conv data-grad is built for the 4x4 bottleneck input only");
-    if (Cout == 1) {      // the 512 -> 1 head, with the derivative of the activation fused into this conv (VfConvExtras::dot_act_y)
-      const int64_t n = (int64_t)B * 16 * Cin;
-      hipLaunchKernelGGL(k_dot_bwd_data, dim3((int)vf_cdiv(n, 256)), dim3(256), 0, ctx->stream, gy, w, gx, B, 16 * Cin, ex->dot_act_y,
+int vf_internal_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, const VfConvShape& s, VfConvExtras* ex) {
+  if (!s.matrix_core_conv()) return vf_internal_gconv_bwd_data(ctx, gy, w, gx, s);
+  if (int rc = check_conv_args(s)) return rc;
+  if (s.stride == 1) {
+    VF_REQUIRE(s.H == 4 && s.W == 4, "stride-1 conv data-grad is built for the 4x4 bottleneck input only");
+    if (s.Cout == 1) {      // the 512 -> 1 head, with the derivative of the activation fused into this conv (VfConvExtras::dot_act_y)
+      const int64_t n = (int64_t)s.B * 16 * s.Cin;
+      hipLaunchKernelGGL(k_dot_bwd_data, dim3((int)vf_cdiv(n, 256)), dim3(256), 0, ctx->stream, gy, w, gx, s.B, 16 * s.Cin, ex->dot_act_y,
                          ex->dot_act, ex->dot_act_slope);
       VF_LAUNCH_CHECK();
       return 0;
     }
   }
-  return conv_like_bwd(ctx, gy, w, nullptr, gx, B, Ho, Wo, Cout, Cin, stride, pad, VF_ACT_NONE, 0.f, ex);
+  return conv_like_bwd(ctx, gy, w, nullptr, gx, s.gradient_of_conv(), VF_ACT_NONE, 0.f, ex);
 }
 VF_API int vf_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin,
                               int Cout, int k, int stride, int pad) {
-  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
-    return vf_internal_conv2d_bwd_data(ctx, gy, w, gx, B, H, W, Cin, Cout, k, stride, pad, ex);
-  });
+  const VfConvShape s{B, H, W, Cin, Cout, k, stride, pad};
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) { return vf_internal_conv2d_bwd_data(ctx, gy, w, gx, s, ex); });
 }
 
 int vf_internal_conv2d_bwd_data_act(vf_ctx* ctx, const float* gy, const float* w, float* gx, const float* x_act, int act, float slope,
-                                    int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, VfConvExtras* ex) {
-  if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
+                                    const VfConvShape& s, VfConvExtras* ex) {
+  if (int rc = check_conv_args(s)) return rc;
   VF_REQUIRE(x_act != nullptr && (act == VF_ACT_LRELU || act == VF_ACT_RELU),
              "vf_conv2d_bwd_data_act: needs the activated input and a (leaky) ReLU");
-  VF_REQUIRE(stride == 2, "vf_conv2d_bwd_data_act: only the stride-2 layers follow a bare conv + activation pair");
-  const int Ho = (H + 2 * pad - 4) / stride + 1, Wo = (W + 2 * pad - 4) / stride + 1;
-  return conv_like_bwd(ctx, gy, w, nullptr, gx, B, Ho, Wo, Cout, Cin, stride, pad, VF_ACT_NONE, 0.f, ex, x_act, act, slope);
+  VF_REQUIRE(s.stride == 2, "vf_conv2d_bwd_data_act: only the stride-2 layers follow a bare conv + activation pair");
+  return conv_like_bwd(ctx, gy, w, nullptr, gx, s.gradient_of_conv(), VF_ACT_NONE, 0.f, ex, x_act, act, slope);
 }
 VF_API int vf_conv2d_bwd_data_act(vf_ctx* ctx, const float* gy, const float* w, float* gx, const float* x_act, int act,
                                   float slope, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad) {
-  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
-    return vf_internal_conv2d_bwd_data_act(ctx, gy, w, gx, x_act, act, slope, B, H, W, Cin, Cout, k, stride, pad, ex);
-  });
+  const VfConvShape s{B, H, W, Cin, Cout, k, stride, pad};
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) { return vf_internal_conv2d_bwd_data_act(ctx, gy, w, gx, x_act, act, slope, s, ex); });
 }
 
 // The weight-gradient entry points leave a pending BatchNorm request alone.  x_planes / gy_planes: the bf16 planes of both
 // operands (vf_planes_split layout), or NULL: the weight gradient runs on the planes-fed kernel where they are at hand and its
 // shape allows (whole 128 x 128 x 32 tiles), on the fp32 operands otherwise.  ex (NULL: plain): the 512 -> 1 head's dot_act_y
 int vf_internal_conv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes, float* gw,
-                                  float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, float beta,
-                                  const VfConvExtras* ex) {
-  if (!main_net_shape(H, W, k, stride, pad))
-    return vf_internal_gconv_bwd_weight(ctx, x, gy, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
-  if (int rc = check_conv_args(B, H, W, Cin, Cout, k, stride, pad)) return rc;
-  const int Ho = (H + 2 * pad - 4) / stride + 1, Wo = (W + 2 * pad - 4) / stride + 1;
-  if (Cout == 1 && stride == 1 && H == 4 && W == 4) {
+                                  float* gb, const VfConvShape& s, float beta, const VfConvExtras* ex) {
+  if (!s.matrix_core_conv()) return vf_internal_gconv_bwd_weight(ctx, x, gy, gw, gb, s, beta);
+  if (int rc = check_conv_args(s)) return rc;
+  if (s.Cout == 1 && s.stride == 1 && s.H == 4 && s.W == 4) {
     const VfConvExtras plain;
     if (!ex) ex = &plain;
-    hipLaunchKernelGGL(k_dot_bwd_weight, dim3((int)vf_cdiv(16 * Cin, 64)), dim3(512), 0, ctx->stream, x, gy, gw, gb, B,
-                       16 * Cin, beta, ex->dot_act_y, ex->dot_act, ex->dot_act_slope);
+    hipLaunchKernelGGL(k_dot_bwd_weight, dim3((int)vf_cdiv(16 * s.Cin, 64)), dim3(512), 0, ctx->stream, x, gy, gw, gb, s.B,
+                       16 * s.Cin, beta, ex->dot_act_y, ex->dot_act, ex->dot_act_slope);
     VF_LAUNCH_CHECK();
     return 0;
   }
   // (tried: the bias gradient as a by-product of this kernel's own gy fragments — the waves that carried it made
   //  their blocks the slowest of every launch: +0.25 ms per step against the 0.19 ms of the separate column sums)
-  if (int rc = wgrad(ctx, gy, x, gw, B, Ho, Wo, Cout, H, W, Cin, stride, pad, beta, 16, gy_planes, x_planes)) return rc;
-  if (gb) return bias_grad(ctx, gy, gb, (int64_t)B * Ho * Wo, Cout, beta);
+  if (int rc = wgrad(ctx, gy, x, gw, s, false, beta, gy_planes, x_planes)) return rc;
+  if (gb) return vf_internal_colsum(ctx, gy, gb, (int64_t)s.B * s.out_h() * s.out_w(), s.Cout, beta);
   return 0;
 }
 VF_API int vf_conv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, int B, int H, int W,
                                 int Cin, int Cout, int k, int stride, int pad, float beta) {
-  return vf_internal_conv2d_bwd_weight(ctx, x, gy, nullptr, nullptr, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta, nullptr);
+  return vf_conv2d_bwd_weight_planes(ctx, x, gy, nullptr, nullptr, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
 }
 VF_API int vf_conv2d_bwd_weight_planes(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
                                        float* gw, float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                                        float beta) {
-  return vf_internal_conv2d_bwd_weight(ctx, x, gy, x_planes, gy_planes, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta, nullptr);
+  return vf_internal_conv2d_bwd_weight(ctx, x, gy, x_planes, gy_planes, gw, gb, VfConvShape{B, H, W, Cin, Cout, k, stride, pad}, beta, nullptr);
 }
 
-int vf_internal_deconv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
-                             int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex) {
-  VF_REQUIRE(k == 4 && ((stride == 2 && pad == 1) || (stride == 1 && pad == 0)), "unsupported full-conv shape");
-  VF_REQUIRE(vf_is_pow2(H) && vf_is_pow2(W), "spatial sizes must be powers of two");
-  return conv_like_bwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, stride, pad, act, slope, ex);
+int vf_internal_deconv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, const VfConvShape& s, int act,
+                             float slope, VfConvExtras* ex) {
+  if (int rc = check_full_conv_args(s)) return rc;
+  return conv_like_bwd(ctx, x, w, bias, y, s, act, slope, ex);
 }
 VF_API int vf_deconv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
                            int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
-  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
-    return vf_internal_deconv2d_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, k, stride, pad, act, slope, ex);
-  });
+  const VfConvShape s{B, H, W, Cin, Cout, k, stride, pad};
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) { return vf_internal_deconv2d_fwd(ctx, x, w, bias, y, s, act, slope, ex); });
 }
 
-int vf_internal_deconv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin, int Cout, int k,
-                                  int stride, int pad, VfConvExtras* ex) {
-  VF_REQUIRE(k == 4 && ((stride == 2 && pad == 1) || (stride == 1 && pad == 0)), "unsupported full-conv shape");
-  const int Ho = (H - 1) * stride - 2 * pad + 4, Wo = (W - 1) * stride - 2 * pad + 4;
-  VF_REQUIRE(vf_is_pow2(H) && vf_is_pow2(W), "spatial sizes must be powers of two");
-  // conv of gy (Ho x Wo, Cout channels) with weights [Cin][kh][kw][Cout] -> gx (H x W, Cin channels)
-  return conv_like_fwd(ctx, gy, w, nullptr, gx, B, Ho, Wo, Cout, Cin, stride, pad, VF_ACT_NONE, 0.f, ex);
+int vf_internal_deconv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, const VfConvShape& s, VfConvExtras* ex) {
+  if (int rc = check_full_conv_args(s)) return rc;
+  // conv of gy (its output map, Cout channels) with weights [Cin][kh][kw][Cout] -> gx (H x W, Cin channels)
+  return conv_like_fwd(ctx, gy, w, nullptr, gx, s.gradient_of_full(), VF_ACT_NONE, 0.f, ex);
 }
 VF_API int vf_deconv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin,
                                 int Cout, int k, int stride, int pad) {
-  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
-    return vf_internal_deconv2d_bwd_data(ctx, gy, w, gx, B, H, W, Cin, Cout, k, stride, pad, ex);
-  });
+  const VfConvShape s{B, H, W, Cin, Cout, k, stride, pad};
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) { return vf_internal_deconv2d_bwd_data(ctx, gy, w, gx, s, ex); });
 }
 
-static int deconv2d_bwd_weight_impl(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
-                                    float* gw, float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad,
-                                    float beta) {
-  VF_REQUIRE(k == 4 && ((stride == 2 && pad == 1) || (stride == 1 && pad == 0)), "unsupported full-conv shape");
-  VF_REQUIRE(vf_is_pow2(H) && vf_is_pow2(W), "spatial sizes must be powers of two");
-  const int Ho = (H - 1) * stride - 2 * pad + 4, Wo = (W - 1) * stride - 2 * pad + 4;
+int vf_internal_deconv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes, float* gw,
+                                    float* gb, const VfConvShape& s, float beta) {
+  if (int rc = check_full_conv_args(s)) return rc;
   // gw[ci][kh][kw][co] = sum_{b,i,j} x[b,i,j,ci] * gy[b, i*s-pad+kh, j*s-pad+kw, co]
-  if (int rc = wgrad(ctx, x, gy, gw, B, H, W, Cin, Ho, Wo, Cout, stride, pad, beta, 16, x_planes, gy_planes)) return rc;
-  if (gb) return bias_grad(ctx, gy, gb, (int64_t)B * Ho * Wo, Cout, beta);
+  if (int rc = wgrad(ctx, x, gy, gw, s, true, beta, x_planes, gy_planes)) return rc;
+  if (gb) return vf_internal_colsum(ctx, gy, gb, (int64_t)s.B * s.full_out_h() * s.full_out_w(), s.Cout, beta);
   return 0;
 }
 VF_API int vf_deconv2d_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, int B, int H, int W,
                                   int Cin, int Cout, int k, int stride, int pad, float beta) {
-  return deconv2d_bwd_weight_impl(ctx, x, gy, nullptr, nullptr, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
+  return vf_internal_deconv2d_bwd_weight(ctx, x, gy, nullptr, nullptr, gw, gb, VfConvShape{B, H, W, Cin, Cout, k, stride, pad}, beta);
 }
 VF_API int vf_deconv2d_bwd_weight_planes(vf_ctx* ctx, const float* x, const float* gy, const void* x_planes, const void* gy_planes,
                                          float* gw, float* gb, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                                          float beta) {
-  return deconv2d_bwd_weight_impl(ctx, x, gy, x_planes, gy_planes, gw, gb, B, H, W, Cin, Cout, k, stride, pad, beta);
+  return vf_internal_deconv2d_bwd_weight(ctx, x, gy, x_planes, gy_planes, gw, gb, VfConvShape{B, H, W, Cin, Cout, k, stride, pad}, beta);
 }

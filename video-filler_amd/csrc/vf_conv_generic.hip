@@ -11,8 +11,6 @@
 
 #include "vf_common.h"
 
-int vf_internal_colsum(vf_ctx* ctx, const float* g, float* gb, int64_t P, int C, float beta);
-
 namespace {
 
 struct GConv {
@@ -186,10 +184,7 @@ __global__ void k_gconv_slab_sum(const float* __restrict__ slab, int nslab, int 
   gw[i] = beta != 0.f ? beta * gw[i] + s : s;
 }
 
-GConv make(int B, int H, int W, int Cin, int Cout, int k, int stride, int pad) {
-  GConv g{B, H, W, Cin, Cout, k, stride, pad, (H + 2 * pad - k) / stride + 1, (W + 2 * pad - k) / stride + 1};
-  return g;
-}
+GConv make(const VfConvShape& s) { return {s.B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.pad, s.out_h(), s.out_w()}; }
 
 int check(const GConv& g) {
   VF_REQUIRE(g.B > 0 && g.Cin > 0 && g.Cout > 0 && g.k > 0 && g.stride > 0 && g.pad >= 0, "bad convolution sizes");
@@ -202,44 +197,42 @@ int grid_for(int64_t n) { return (int)std::min<int64_t>(vf_cdiv(n, 256), 256 * 3
 
 }  // namespace
 
-int vf_internal_gconv_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
-                          int Cout, int k, int stride, int pad, int act, float slope) {
-  const GConv g = make(B, H, W, Cin, Cout, k, stride, pad);
+int vf_internal_gconv_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, const VfConvShape& s, int act,
+                          float slope) {
+  const GConv g = make(s);
   if (int rc = check(g)) return rc;
-  const int64_t nw = (int64_t)Cout * k * k * Cin;
+  const int64_t nw = (int64_t)g.Cout * g.k * g.k * g.Cin;
   const int in_lds = nw <= GC_LDS_FLOATS;
-  const int64_t total = (int64_t)B * g.Ho * g.Wo * Cout;
-  VfProf prof(ctx, "gconv_fwd", 2.0 * (double)total * k * k * Cin, 4.0 * ((double)B * H * W * Cin + (double)total + (double)nw));
+  const int64_t total = (int64_t)g.B * g.Ho * g.Wo * g.Cout;
+  VfProf prof(ctx, "gconv_fwd", 2.0 * (double)total * g.k * g.k * g.Cin, 4.0 * ((double)g.B * g.H * g.W * g.Cin + (double)total + (double)nw));
   hipLaunchKernelGGL(k_gconv_fwd, dim3(grid_for(total)), dim3(256), in_lds ? (size_t)nw * 4 : 0, ctx->stream, x, w, bias, y, g, act,
                      slope, in_lds);
   VF_LAUNCH_CHECK();
   return 0;
 }
 
-int vf_internal_gconv_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin, int Cout,
-                               int k, int stride, int pad) {
-  const GConv g = make(B, H, W, Cin, Cout, k, stride, pad);
+int vf_internal_gconv_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, const VfConvShape& s) {
+  const GConv g = make(s);
   if (int rc = check(g)) return rc;
-  const int64_t nw = (int64_t)Cout * k * k * Cin;
+  const int64_t nw = (int64_t)g.Cout * g.k * g.k * g.Cin;
   const int in_lds = nw <= GC_LDS_FLOATS;
-  const int64_t total = (int64_t)B * H * W * Cin;
-  VfProf prof(ctx, "gconv_bwd_data", 2.0 * (double)B * g.Ho * g.Wo * Cout * k * k * Cin,
-              4.0 * ((double)total + (double)B * g.Ho * g.Wo * Cout + (double)nw));
+  const int64_t total = (int64_t)g.B * g.H * g.W * g.Cin;
+  VfProf prof(ctx, "gconv_bwd_data", 2.0 * (double)g.B * g.Ho * g.Wo * g.Cout * g.k * g.k * g.Cin,
+              4.0 * ((double)total + (double)g.B * g.Ho * g.Wo * g.Cout + (double)nw));
   hipLaunchKernelGGL(k_gconv_bwd_data, dim3(grid_for(total)), dim3(256), in_lds ? (size_t)nw * 4 : 0, ctx->stream, gy, w, gx, g,
                      in_lds);
   VF_LAUNCH_CHECK();
   return 0;
 }
 
-int vf_internal_gconv_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, int B, int H, int W, int Cin,
-                                 int Cout, int k, int stride, int pad, float beta) {
-  const GConv g = make(B, H, W, Cin, Cout, k, stride, pad);
+int vf_internal_gconv_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, const VfConvShape& s, float beta) {
+  const GConv g = make(s);
   if (int rc = check(g)) return rc;
-  const int K = k * k * Cin;
-  const int nout = Cout * K;
-  const int64_t P = (int64_t)B * g.Ho * g.Wo;
-  const size_t lds = (size_t)GC_PT * (Cout + K) * 4;
-  VF_REQUIRE(lds <= 64 * 1024, "generic weight gradient: Cout + k*k*Cin = %d exceeds the staging tile", Cout + K);
+  const int K = g.k * g.k * g.Cin;
+  const int nout = g.Cout * K;
+  const int64_t P = (int64_t)g.B * g.Ho * g.Wo;
+  const size_t lds = (size_t)GC_PT * (g.Cout + K) * 4;
+  VF_REQUIRE(lds <= 64 * 1024, "generic weight gradient: Cout + k*k*Cin = %d exceeds the staging tile", g.Cout + K);
   // enough blocks to fill the chip, but at least 4 staging rounds per block and slabs that fit the workspace
   const int ychunks = (int)vf_cdiv(nout, GC_OUT_PER_BLOCK);
   int64_t nslab = std::max<int64_t>(1, std::min<int64_t>(vf_cdiv(P, 4 * GC_PT), 1024 / ychunks));
@@ -250,13 +243,13 @@ int vf_internal_gconv_bwd_weight(vf_ctx* ctx, const float* x, const float* gy, f
   nslab = vf_cdiv(P, ppb);
   float* slab = (float*)vf_ws_ptr(ctx);
   {
-    VfProf prof(ctx, "gconv_bwd_weight", 2.0 * (double)P * nout, 4.0 * ((double)P * Cout + (double)B * H * W * Cin + (double)nout));
+    VfProf prof(ctx, "gconv_bwd_weight", 2.0 * (double)P * nout, 4.0 * ((double)P * g.Cout + (double)g.B * g.H * g.W * g.Cin + (double)nout));
     hipLaunchKernelGGL(k_gconv_bwd_weight, dim3((int)nslab, ychunks), dim3(256), lds, ctx->stream, x, gy, slab, g, ppb);
     VF_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_gconv_slab_sum, dim3((int)vf_cdiv(nout, 256)), dim3(256), 0, ctx->stream, (const float*)slab, (int)nslab,
                        nout, gw, beta);
     VF_LAUNCH_CHECK();
   }
-  if (gb) return vf_internal_colsum(ctx, gy, gb, P, Cout, beta);
+  if (gb) return vf_internal_colsum(ctx, gy, gb, P, g.Cout, beta);
   return 0;
 }

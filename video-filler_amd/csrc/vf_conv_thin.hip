@@ -235,14 +235,15 @@ __global__ __launch_bounds__(256) void k_deconv_thin_out(const float* __restrict
 // transposed 4x4 stride-2 pad-1 pass onto N = 3 channels: x [B][Hi][Wi][C] -> y [B][2Hi][2Wi][N], w physical [C][16][N] (a
 // full-conv weight [Cin][kH][kW][Cout], or a conv weight [Cout][kH][kW][Cin] read for its data-gradient).  Returns -1 if the
 // shape is not this kernel's (the caller keeps its GEMM + col2im path), 0 when launched, > 0 on a launch error.
-int vf_internal_deconv_thin_out(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int Hi, int Wi, int C,
-                                int N, int act, float slope) {
+// s: the pass as a full-conv (H x W the low-resolution map x lives on, Cin = C, Cout = N)
+int vf_internal_deconv_thin_out(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, const VfConvShape& s, int act,
+                                float slope) {
   if (ctx->mfma_bf16 == 1) return -1;      // (the bf16-operand mode rounds its operands: the GEMM kernels' business)
-  if (N != 3 || C % 64 != 0 || Hi % 8 != 0 || Wi % 8 != 0 || (((uintptr_t)x) & 15) != 0 || (((uintptr_t)w) & 15) != 0) return -1;
-  const int tiles_x = Wi / 8, tiles_y = Hi / 8;
-  VfProf prof(ctx, "deconv_thin_out", 2.0 * (double)B * Hi * Wi * C * 16 * N, 0.0);
-  hipLaunchKernelGGL((k_deconv_thin_out<3>), dim3((unsigned)(B * tiles_y * tiles_x)), dim3(256), 0, ctx->stream, x, w, bias, y, Hi, Wi,
-                     C, tiles_x, tiles_y, act, slope);
+  if (s.Cout != 3 || s.Cin % 64 != 0 || s.H % 8 != 0 || s.W % 8 != 0 || (((uintptr_t)x) & 15) != 0 || (((uintptr_t)w) & 15) != 0) return -1;
+  const int tiles_x = s.W / 8, tiles_y = s.H / 8;
+  VfProf prof(ctx, "deconv_thin_out", 2.0 * (double)s.B * s.H * s.W * s.Cin * 16 * s.Cout, 0.0);
+  hipLaunchKernelGGL((k_deconv_thin_out<3>), dim3((unsigned)(s.B * tiles_y * tiles_x)), dim3(256), 0, ctx->stream, x, w, bias, y, s.H, s.W,
+                     s.Cin, tiles_x, tiles_y, act, slope);
   VF_LAUNCH_CHECK();
   return 0;
 }
@@ -250,41 +251,37 @@ int vf_internal_deconv_thin_out(vf_ctx* ctx, const float* x, const float* w, con
 // conv forward with 3 input channels, 4x4 stride 2 pad 1; act in {none, LeakyReLU, ReLU}.  Returns -1 if the shape is not this
 // kernel's (the caller keeps the implicit-GEMM path), 0 when launched, > 0 on a launch error.  ex->act_bits_out: also leave the sign
 // bits of the activated output.
-int vf_internal_conv_thin_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B, int H,
-                              int W, int Cin, int Cout, int act, float slope, VfConvExtras* ex) {
+int vf_internal_conv_thin_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes,
+                              const VfConvShape& s, int act, float slope, VfConvExtras* ex) {
   if (ctx->mfma_bf16 == 1) return -1;       // (the bf16-operand mode rounds its operands: that is the GEMM kernels' business)
-  if (Cin != 3 || Cout % 64 != 0 || H % (2 * TP) != 0 || W % (2 * TP) != 0) return -1;
+  if (s.Cin != 3 || s.Cout % 64 != 0 || s.H % (2 * TP) != 0 || s.W % (2 * TP) != 0) return -1;
   if (!(act == VF_ACT_NONE || act == VF_ACT_LRELU || act == VF_ACT_RELU)) return -1;
   if ((((uintptr_t)y) & 7) != 0) return -1;
   const float neg = act == VF_ACT_LRELU ? slope : (act == VF_ACT_RELU ? 0.f : 1.f);
-  const int tiles_x = W / (2 * TP), tiles_y = H / (2 * TP);
-  const int64_t out = (int64_t)B * (H / 2) * (W / 2) * Cout;
-  VfProf prof(ctx, y_planes ? "conv_thin_in_planes" : "conv_thin_in", 2.0 * (double)out * 16 * Cin, 0.0);
+  const int tiles_x = s.W / (2 * TP), tiles_y = s.H / (2 * TP);
+  const int64_t out = (int64_t)s.B * (s.H / 2) * (s.W / 2) * s.Cout;
+  VfProf prof(ctx, y_planes ? "conv_thin_in_planes" : "conv_thin_in", 2.0 * (double)out * 16 * s.Cin, 0.0);
   ex->act_bits_written = ex->act_bits_out != nullptr;
-  hipLaunchKernelGGL((k_conv_thin_in<3>), dim3((unsigned)(B * tiles_y), (unsigned)(Cout / 64)), dim3(256), 0, ctx->stream, x, w,
-                     bias, y, (unsigned short*)y_planes, out, H, W, Cout, tiles_x, tiles_y, neg, ex->act_bits_out);
+  hipLaunchKernelGGL((k_conv_thin_in<3>), dim3((unsigned)(s.B * tiles_y), (unsigned)(s.Cout / 64)), dim3(256), 0, ctx->stream, x, w,
+                     bias, y, (unsigned short*)y_planes, out, s.H, s.W, s.Cout, tiles_x, tiles_y, neg, ex->act_bits_out);
   VF_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int vf_planes_split(vf_ctx* ctx, const float* x, void* planes, int64_t n);
-
 // vf_conv2d_fwd that also leaves the three bf16 planes of y (for a planes-fed consumer): in the epilogue where the kernel
 // can (the thin-input layers above), else by a pass over y.
-int vf_internal_conv2d_fwd_planes(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B, int H,
-                                  int W, int Cin, int Cout, int k, int stride, int pad, int act, float slope, VfConvExtras* ex) {
+int vf_internal_conv2d_fwd_planes(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes,
+                                  const VfConvShape& s, int act, float slope, VfConvExtras* ex) {
   VF_REQUIRE(y_planes != nullptr, "vf_conv2d_fwd_planes: y_planes is NULL (use vf_conv2d_fwd)");
-  if (k == 4 && stride == 2 && pad == 1) {
-    const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, y_planes, B, H, W, Cin, Cout, act, slope, ex);
+  if (s.k == 4 && s.stride == 2 && s.pad == 1) {
+    const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, y_planes, s, act, slope, ex);
     if (rc >= 0) return rc;
   }
-  if (int rc = vf_internal_conv2d_fwd(ctx, x, w, bias, y, B, H, W, Cin, Cout, k, stride, pad, act, slope, ex)) return rc;
-  const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-  return vf_planes_split(ctx, y, y_planes, (int64_t)B * Ho * Wo * Cout);
+  if (int rc = vf_internal_conv2d_fwd(ctx, x, w, bias, y, s, act, slope, ex)) return rc;
+  return vf_planes_split(ctx, y, y_planes, (int64_t)s.B * s.out_h() * s.out_w() * s.Cout);
 }
 VF_API int vf_conv2d_fwd_planes(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, void* y_planes, int B,
                                 int H, int W, int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
-  return vf_take_pending(ctx, [&](VfConvExtras* ex) {
-    return vf_internal_conv2d_fwd_planes(ctx, x, w, bias, y, y_planes, B, H, W, Cin, Cout, k, stride, pad, act, slope, ex);
-  });
+  const VfConvShape s{B, H, W, Cin, Cout, k, stride, pad};
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) { return vf_internal_conv2d_fwd_planes(ctx, x, w, bias, y, y_planes, s, act, slope, ex); });
 }

@@ -45,8 +45,6 @@
 
 #include "vf_common.h"
 
-int vf_internal_colsum(vf_ctx* ctx, const float* g, float* gb, int64_t P, int C, float beta);      // vf_bn.hip
-
 namespace {
 
 // where the planes kernels pay: from 3 GFLOP per pass and 1024 GEMM rows; process-wide, like nn.py's gate
@@ -95,6 +93,9 @@ struct Layer {
   bool fa = false;               // a layer the fused kernel takes
   const float *fa_u = nullptr, *fa_v = nullptr;
   int fa_k = 0;                  // 0: nothing pending (the gradient was accumulated the plain way, or no backward ran)
+  // a conv / full-conv layer's geometry for a batch of Bn, and that of the pass which computes its data-gradient
+  VfConvShape shape(int Bn) const { return {Bn, H, W, C, Co, d.k, d.stride, d.pad}; }
+  VfConvShape grad_shape(int Bn) const { return d.kind == VF_L_FULLCONV ? shape(Bn).gradient_of_full() : shape(Bn).gradient_of_conv(); }
 };
 
 struct Entry {
@@ -165,17 +166,18 @@ int net_alloc(std::vector<void*>& pool, void** out, size_t bytes) {
 bool sync_on(const vf_net* n) { return (n->comm && n->sync_world > 1) || n->sync_force; }
 bool bn_fusable(const vf_net* n, const Layer& l) { return n->train && !sync_on(n) && l.C % 4 == 0 && !g_no_bn_fuse; }
 
-// could any pass of this layer use the planes kernels (4x4 stride 2, wide enough)?
+// could any pass of this layer use the planes kernels (4x4 stride 2, wide enough)?  pconv_ok: can pass s of it (l.shape: the forward,
+// l.grad_shape: the data-gradient; transposed: it scatters from the low-resolution map s.H x s.W)?
 bool pconv_layer(const Layer& l) {
   return is_conv(l) && is_s2(l) && std::min(l.d.nin, l.d.nout) >= 32 && l.d.nin % 4 == 0 && l.d.nout % 4 == 0;
 }
-bool pconv_ok(const vf_net* n, const Layer& l, int Bn, int Hg, int Wg, int Cgather, int Cout, bool transposed) {
+bool pconv_ok(const vf_net* n, const Layer& l, const VfConvShape& s, bool transposed) {
   const int mode = n->ctx->mfma_bf16;      // 3: three exact planes; 1: one plane rounded to bf16 by the producer
   if (g_no_pconv || (mode != 3 && mode != 1) || !is_s2(l)) return false;
-  const int64_t rows = (int64_t)Bn * Hg * Wg / (transposed ? 1 : 4);
-  const double gflop = 2.0 * (double)rows * 16.0 * Cgather * Cout * 1e-9;
+  const int64_t rows = (int64_t)s.B * s.H * s.W / (transposed ? 1 : 4);
+  const double gflop = 2.0 * (double)rows * 16.0 * s.Cin * s.Cout * 1e-9;
   if (rows < g_gate_rows || gflop < g_gate_gflop) return false;
-  return vf_pconv_supported_in_mode(mode, Bn, Hg, Wg, Cgather, Cout, 4, 2, 1, transposed ? 1 : 0) != 0;
+  return vf_internal_pconv_supported(mode, s, transposed);
 }
 
 int ensure_planes(vf_net* n, void** slot, int64_t numel) {
@@ -258,6 +260,7 @@ int conv_forward(vf_net* n, Layer& l, const float* x, const void* in_planes, int
   const float* w = n->params + l.w_off;
   const float* b = n->params + l.b_off;
   const bool full = is_full(l);
+  const VfConvShape s = l.shape(Bn);
   l.out_planes = nullptr;
   // every branch below rewrites l.y: sign bits a previous forward left (another planes gate or product mode then) no longer
   // describe it, whichever branch this forward takes
@@ -272,14 +275,14 @@ int conv_forward(vf_net* n, Layer& l, const float* x, const void* in_planes, int
         if (int rc = net_alloc(n->act_owned, (void**)&l.ybits, sizeof(unsigned) * (size_t)n->B * l.Ho * l.Wo * (l.Co / 32))) return rc;
       ex->act_bits_out = l.ybits;
     }
-    const int frc = vf_internal_conv2d_fwd_planes(ctx, x, w, b, l.y, l.yp, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, act, slope, ex);
+    const int frc = vf_internal_conv2d_fwd_planes(ctx, x, w, b, l.y, l.yp, s, act, slope, ex);
     l.bits_live = ex->act_bits_written && relu_like(act) && !n->observer;
     if (frc) return frc;
     l.out_planes = l.yp;
     l.x_seen = nullptr;
     return 0;
   }
-  if (simple_act && pconv_ok(n, l, Bn, l.H, l.W, l.C, l.Co, full)) {
+  if (simple_act && pconv_ok(n, l, s, full)) {
     const void* xp = in_planes;
     if (!xp) {
       if (int rc = ensure_planes(n, &l.xp, (int64_t)n->B * l.H * l.W * l.C)) return rc;
@@ -290,12 +293,11 @@ int conv_forward(vf_net* n, Layer& l, const float* x, const void* in_planes, int
     l.xp_seen = xp;
     const void* wp = nullptr;
     if (int rc = weight_planes(n, l, full, &wp)) return rc;
-    return full ? vf_internal_pconv_scatter(ctx, xp, wp, b, l.y, Bn, l.H, l.W, l.C, l.Co, act, slope, nullptr, VF_ACT_NONE, 0.f, ex)
-                : vf_internal_pconv_gather(ctx, xp, wp, b, l.y, Bn, l.H, l.W, l.C, l.Co, act, slope, ex);
+    return full ? vf_internal_pconv_scatter(ctx, xp, wp, b, l.y, s, act, slope, nullptr, VF_ACT_NONE, 0.f, ex)
+                : vf_internal_pconv_gather(ctx, xp, wp, b, l.y, s, act, slope, ex);
   }
   l.x_seen = nullptr;
-  return full ? vf_internal_deconv2d_fwd(ctx, x, w, b, l.y, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, act, slope, ex)
-              : vf_internal_conv2d_fwd(ctx, x, w, b, l.y, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, act, slope, ex);
+  return full ? vf_internal_deconv2d_fwd(ctx, x, w, b, l.y, s, act, slope, ex) : vf_internal_conv2d_fwd(ctx, x, w, b, l.y, s, act, slope, ex);
 }
 
 int bn_forward(vf_net* n, Layer& l, const float* x, int Bn, int act, float slope, int pre_rows, bool want_planes) {
@@ -344,7 +346,8 @@ int conv_bwd_data(vf_net* n, Layer& l, const float* x, const float* go, int Bn, 
   vf_ctx* ctx = n->ctx;
   const float* w = n->params + l.w_off;
   const bool full = is_full(l);
-  if (pconv_ok(n, l, Bn, l.Ho, l.Wo, l.Co, l.C, !full) && (in_act == VF_ACT_NONE || !full)) {
+  const VfConvShape s = l.shape(Bn), gs = l.grad_shape(Bn);      // the planes passes take the gradient's own shape, the others the layer's
+  if (pconv_ok(n, l, gs, !full) && (in_act == VF_ACT_NONE || !full)) {
     const void* gp = g_planes;
     if (!gp) {
       if (int rc = ensure_planes(n, &l.gp, (int64_t)n->B * l.Ho * l.Wo * l.Co)) return rc;
@@ -355,15 +358,14 @@ int conv_bwd_data(vf_net* n, Layer& l, const float* x, const float* go, int Bn, 
     l.gp_seen = gp;
     const void* wp = nullptr;
     if (int rc = weight_planes(n, l, !full, &wp)) return rc;
-    if (full) return vf_internal_pconv_gather(ctx, gp, wp, nullptr, l.gx, Bn, l.Ho, l.Wo, l.Co, l.C, VF_ACT_NONE, 0.f, ex);
-    return vf_internal_pconv_scatter(ctx, gp, wp, nullptr, l.gx, Bn, l.Ho, l.Wo, l.Co, l.C, VF_ACT_NONE, 0.f,
-                                     in_act != VF_ACT_NONE ? x : nullptr, in_act, in_slope, ex);
+    if (full) return vf_internal_pconv_gather(ctx, gp, wp, nullptr, l.gx, gs, VF_ACT_NONE, 0.f, ex);
+    return vf_internal_pconv_scatter(ctx, gp, wp, nullptr, l.gx, gs, VF_ACT_NONE, 0.f, in_act != VF_ACT_NONE ? x : nullptr, in_act, in_slope,
+                                     ex);
   }
   l.g_seen = nullptr;
   if (in_act != VF_ACT_NONE)
-    return vf_internal_conv2d_bwd_data_act(ctx, go, w, l.gx, x, in_act, in_slope, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, ex);
-  return full ? vf_internal_deconv2d_bwd_data(ctx, go, w, l.gx, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, ex)
-              : vf_internal_conv2d_bwd_data(ctx, go, w, l.gx, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, ex);
+    return vf_internal_conv2d_bwd_data_act(ctx, go, w, l.gx, x, in_act, in_slope, s, ex);
+  return full ? vf_internal_deconv2d_bwd_data(ctx, go, w, l.gx, s, ex) : vf_internal_conv2d_bwd_data(ctx, go, w, l.gx, s, ex);
 }
 
 struct Deferred {
@@ -403,8 +405,8 @@ int conv_acc(vf_net* n, Layer& l, const float* x, const float* go, int Bn, std::
   l.g_seen = nullptr;        // single use: only a data-gradient pass of THIS walk may hand its planes over
   l.gp_seen = nullptr;
   if (!planes) xp = gp = nullptr;
-  return full ? vf_deconv2d_bwd_weight_planes(ctx, x, go, xp, gp, gw, gb, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, beta)
-              : vf_internal_conv2d_bwd_weight(ctx, x, go, xp, gp, gw, gb, Bn, l.H, l.W, l.C, l.Co, l.d.k, l.d.stride, l.d.pad, beta, ex);
+  return full ? vf_internal_deconv2d_bwd_weight(ctx, x, go, xp, gp, gw, gb, l.shape(Bn), beta)
+              : vf_internal_conv2d_bwd_weight(ctx, x, go, xp, gp, gw, gb, l.shape(Bn), beta, ex);
 }
 
 // gsel >= 0: x / gy / y_act hold batch group gsel only (a pass over one of the concatenated batches): its saved statistics.
@@ -532,7 +534,7 @@ int net_walk_back(vf_net* n, const float* x_in, const float* gy, const float** g
       if (want_gx && idx > 0) {
         const Layer& below = n->L[n->plan[idx - 1].main];
         want_pl = is_conv(below) && pconv_layer(below) && (idx - 1 > 0 || need_input_grad) &&
-                  pconv_ok(n, below, Bn, l.H, l.W, below.Co, below.C, !is_full(below));
+                  pconv_ok(n, below, below.grad_shape(Bn), !is_full(below));
       }
       rc = bn_backward(n, l, x, g, Bn, want_gx, want_gp, l.fused_act, l.fused_slope, l.fused_act != VF_ACT_NONE ? mout : nullptr,
                        gi, rows, want_pl);
@@ -665,16 +667,11 @@ int net_shape(vf_net* n, int B, int C, int H, int W) {
     l.Co = c; l.Ho = h; l.Wo = w;
     switch (l.d.kind) {
       case VF_L_CONV:
-        VF_REQUIRE(l.d.nin == c, "vf_net: layer %d expects %d input planes, gets %d", (int)i, l.d.nin, c);
-        l.Co = l.d.nout;
-        l.Ho = (h + 2 * l.d.pad - l.d.k) / l.d.stride + 1;
-        l.Wo = (w + 2 * l.d.pad - l.d.k) / l.d.stride + 1;
-        break;
       case VF_L_FULLCONV:
         VF_REQUIRE(l.d.nin == c, "vf_net: layer %d expects %d input planes, gets %d", (int)i, l.d.nin, c);
         l.Co = l.d.nout;
-        l.Ho = (h - 1) * l.d.stride - 2 * l.d.pad + l.d.k;
-        l.Wo = (w - 1) * l.d.stride - 2 * l.d.pad + l.d.k;
+        l.Ho = is_full(l) ? l.shape(B).full_out_h() : l.shape(B).out_h();
+        l.Wo = is_full(l) ? l.shape(B).full_out_w() : l.shape(B).out_w();
         break;
       case VF_L_BN:
         VF_REQUIRE(l.d.nout == c, "vf_net: BatchNorm layer %d has %d channels, gets %d", (int)i, l.d.nout, c);
@@ -753,11 +750,8 @@ VF_API int vf_net_create(vf_ctx* ctx, vf_net** out, const vf_layer_desc* layers,
     l.d = layers[i];
     switch (l.d.kind) {
       case VF_L_CONV:
-        l.w_n = (int64_t)l.d.nout * l.d.k * l.d.k * l.d.nin;
-        l.b_n = l.d.nout;
-        break;
       case VF_L_FULLCONV:
-        l.w_n = (int64_t)l.d.nin * l.d.k * l.d.k * l.d.nout;
+        l.w_n = (int64_t)l.d.nout * l.d.k * l.d.k * l.d.nin;
         l.b_n = l.d.nout;
         break;
       case VF_L_BN:
@@ -1111,7 +1105,7 @@ VF_API int vf_net_forward(vf_net* n, const float* x, const float** y) {
         continue;
       }
       const bool want_pl = nxt && is_conv(*nxt) && pconv_layer(*nxt) &&
-                           pconv_ok(n, *nxt, n->B, l.Ho, l.Wo, nxt->d.nin, nxt->d.nout, is_full(*nxt));
+                           pconv_ok(n, *nxt, nxt->shape(n->B), is_full(*nxt));
       if ((rc = conv_forward(n, l, cur, cur_pl, n->B, l.fused_act, l.fused_slope, want_pl, &ex))) return rc;
       cur = l.y;
       cur_pl = l.out_planes;
@@ -1122,7 +1116,7 @@ VF_API int vf_net_forward(vf_net* n, const float* x, const float** y) {
       const int rows = pre_rows;
       pre_rows = 0;
       const bool want_pl = n->train && nxt && is_conv(*nxt) && pconv_layer(*nxt) && (l.fused_act == VF_ACT_NONE || relu_like(l.fused_act)) &&
-                           pconv_ok(n, *nxt, n->B, l.H, l.W, nxt->d.nin, nxt->d.nout, is_full(*nxt));
+                           pconv_ok(n, *nxt, nxt->shape(n->B), is_full(*nxt));
       if ((rc = bn_forward(n, l, cur, n->B, l.fused_act, l.fused_slope, rows, want_pl))) return rc;
       cur = l.y;
       cur_pl = l.out_planes;

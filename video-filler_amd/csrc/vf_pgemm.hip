@@ -1503,11 +1503,6 @@ VF_API int vf_pconv_set_routing(int gather_patch, int scatter_patch) {
   return 0;
 }
 
-// what the shapes must satisfy for the planes GEMM (callers fall back to vf_conv.hip's kernels otherwise)
-static bool pg_shape_ok(int B, int Hl, int Wl, int C, int N) {
-  return C % 32 == 0 && N >= 32 && N % 4 == 0 && (int64_t)B * Hl * Wl > 64 && vf_is_pow2(Hl) && vf_is_pow2(Wl);
-}
-
 typedef void (*PgKernel)(PGemm);
 
 template <int BM, int NTAPS>
@@ -1622,9 +1617,11 @@ static int launch_pconv(vf_ctx* ctx, PGemm& g, int ntaps, VfConvExtras* ex) {
   return 0;
 }
 
-static int pg_fill_common(vf_ctx* ctx, PGemm& g, const void* a, int64_t a_elems, const void* w, int64_t w_elems, const float* bias, float* y) {
+static int pg_fill_common(vf_ctx* ctx, PGemm& g, const void* a, const void* w, const float* bias, float* y, const VfConvShape& s) {
   memset(&g, 0, sizeof(g));
   g.A = a; g.W = w; g.bias = bias; g.Y = y;
+  g.Hi = s.H; g.Wi = s.W; g.C = s.Cin; g.N = s.Cout;
+  const int64_t a_elems = (int64_t)s.B * s.H * s.W * s.Cin, w_elems = (int64_t)s.Cout * 16 * s.Cin;      // a [B][H][W][Cin], w [Cout][16][Cin]
   const int npl = ctx->mfma_bf16 == 1 ? 1 : 3;
   VF_REQUIRE(ctx->mfma_bf16 == 3 || ctx->mfma_bf16 == 1, "vf_pconv: the planes path serves product modes 3 (exact split) and 1 (bf16 operands)");
   VF_REQUIRE(a_elems * 2 * npl < ((int64_t)1 << 31) && w_elems * 2 * npl < ((int64_t)1 << 31), "planes exceed the 2 GiB buffer-descriptor range");
@@ -1636,41 +1633,39 @@ static int pg_fill_common(vf_ctx* ctx, PGemm& g, const void* a, int64_t a_elems,
 }
 
 // conv-like pass: Y[b,oy,ox,n] = sum_{kh,kw,c} A[b, 2oy-1+kh, 2ox-1+kw, c] * Wp[n][kh][kw][c]      (4x4, stride 2, pad 1)
-static int pconv_like_fwd(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* Y, int B, int Hi, int Wi, int C,
-                          int N, int act, float slope, VfConvExtras* ex) {
-  const int Ho = Hi / 2, Wo = Wi / 2;
+static int pconv_like_fwd(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* Y, const VfConvShape& s, int act,
+                          float slope, VfConvExtras* ex) {
+  const int Ho = s.H / 2, Wo = s.W / 2;
   PGemm g;
-  if (int rc = pg_fill_common(ctx, g, ap, (int64_t)B * Hi * Wi * C, wp, (int64_t)N * 16 * C, bias, Y)) return rc;
+  if (int rc = pg_fill_common(ctx, g, ap, wp, bias, Y, s)) return rc;
   g.lgMh = vf_ilog2(Ho); g.lgMw = vf_ilog2(Wo);
-  g.M = B * Ho * Wo;
-  g.Hi = Hi; g.Wi = Wi; g.C = C; g.N = N;
+  g.M = s.B * Ho * Wo;
   g.sy = 2; g.oy0 = -1; g.sx = 2; g.ox0 = -1;
   g.lgTW = 2;
   g.kh0 = 0; g.khs = 1; g.kw0 = 0; g.kws = 1;
   g.outH = Ho; g.outW = Wo; g.osy = 1; g.osx = 1;
-  g.out_elems = (int64_t)g.M * N;
+  g.out_elems = (int64_t)g.M * s.Cout;
   g.act = act; g.slope = slope;
   return launch_pconv(ctx, g, 16, ex);
 }
 // transposed pass: Y[b,oh,ow,n] = sum_{kh,kw,c : oh = 2i-1+kh, ow = 2j-1+kw} A[b,i,j,c] * Wp[n][kh][kw][c]; per output parity
 // (ph, pw) a 2x2-tap GEMM over the low-res grid: window rows i = my + ph - 1 + th, filter row kh = 3 - ph - 2*th
-static int pconv_like_tr(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* Y, int B, int Hi, int Wi, int C, int N,
-                         int act, float slope, const float* dmask, int dact, float dslope, VfConvExtras* ex) {
+static int pconv_like_tr(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* Y, const VfConvShape& s, int act,
+                         float slope, const float* dmask, int dact, float dslope, VfConvExtras* ex) {
   PGemm g;
-  if (int rc = pg_fill_common(ctx, g, ap, (int64_t)B * Hi * Wi * C, wp, (int64_t)N * 16 * C, bias, Y)) return rc;
-  g.lgMh = vf_ilog2(Hi); g.lgMw = vf_ilog2(Wi);
-  g.M = B * Hi * Wi;
-  g.Hi = Hi; g.Wi = Wi; g.C = C; g.N = N;
+  if (int rc = pg_fill_common(ctx, g, ap, wp, bias, Y, s)) return rc;
+  g.lgMh = vf_ilog2(s.H); g.lgMw = vf_ilog2(s.W);
+  g.M = s.B * s.H * s.W;
   g.sy = 1; g.oy0 = -1; g.sx = 1; g.ox0 = -1;      // (+ph, +pw in the kernel)
   g.lgTW = 1;
   g.khs = -2; g.kws = -2;                          // kh0 = 3 - ph, kw0 = 3 - pw in the kernel
   g.parity = 1;
-  g.outH = 2 * Hi; g.outW = 2 * Wi; g.osy = 2; g.osx = 2;
-  g.out_elems = (int64_t)B * g.outH * g.outW * N;
+  g.outH = 2 * s.H; g.outW = 2 * s.W; g.osy = 2; g.osx = 2;
+  g.out_elems = (int64_t)s.B * g.outH * g.outW * s.Cout;
   g.act = act; g.slope = slope;
   g.dmask = dmask; g.dact = dact; g.dslope = dslope;
   // the same mask as sign bits, where the tensor's producer left them (vf_net.hip) and the channel count is whole groups
-  g.dbits = (dmask && N % 64 == 0) ? ex->dmask_bits : nullptr;
+  g.dbits = (dmask && s.Cout % 64 == 0) ? ex->dmask_bits : nullptr;
   return launch_pconv(ctx, g, 4, ex);
 }
 
@@ -1706,39 +1701,44 @@ VF_API int vf_weight_planes_multi(vf_ctx* ctx, const void* desc_dev, int n, int 
   VF_LAUNCH_CHECK();
   return 0;
 }
-VF_API int vf_pconv_supported(int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, int transposed) {
-  if (k != 4 || stride != 2 || pad != 1) return 0;
-  // conv-like passes gather on the H x W grid with channels Cin and produce Cout; transposed ones walk the low-res grid
-  return pg_shape_ok(B, transposed ? H : H / 2, transposed ? W : W / 2, Cin, Cout) && H >= 2 && W >= 2 ? 1 : 0;
+// What a shape must satisfy for the planes GEMM (callers fall back to vf_conv.hip's kernels otherwise).  Gather passes walk the
+// H x W grid with channels Cin and produce Cout on H/2 x W/2; transposed ones walk the low-res grid H x W.  Product mode 1 (operands
+// rounded to bf16, ONE plane [1][n]) is served by the LDS-DMA kernel alone: whole 64-channel K steps and 64 x 64 tiles; modes but 3, 1: never
+bool vf_internal_pconv_supported(int mfma_mode, const VfConvShape& s, bool transposed) {
+  if ((mfma_mode != 3 && mfma_mode != 1) || s.k != 4 || s.stride != 2 || s.pad != 1 || s.H < 2 || s.W < 2) return false;
+  const int Hl = transposed ? s.H : s.H / 2, Wl = transposed ? s.W : s.W / 2;
+  const int64_t M = (int64_t)s.B * Hl * Wl;
+  if (s.Cin % 32 != 0 || s.Cout < 32 || s.Cout % 4 != 0 || M <= 64 || !vf_is_pow2(Hl) || !vf_is_pow2(Wl)) return false;
+  return mfma_mode == 3 || (s.Cin % 64 == 0 && s.Cout % 64 == 0 && M % 64 == 0);
 }
-// the same question for a product mode: 3 = vf_pconv_supported; 1 (operands rounded to bf16, ONE plane [1][n]) is served by the
-// LDS-DMA kernel alone: whole 64-channel K steps and whole 64 x 64 tiles; other modes: never
+VF_API int vf_pconv_supported(int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, int transposed) {
+  return vf_internal_pconv_supported(3, VfConvShape{B, H, W, Cin, Cout, k, stride, pad}, transposed != 0) ? 1 : 0;
+}
 VF_API int vf_pconv_supported_in_mode(int mfma_mode, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad, int transposed) {
-  if (mfma_mode == 3) return vf_pconv_supported(B, H, W, Cin, Cout, k, stride, pad, transposed);
-  if (mfma_mode != 1 || !vf_pconv_supported(B, H, W, Cin, Cout, k, stride, pad, transposed)) return 0;
-  const int64_t M = (int64_t)B * (transposed ? H : H / 2) * (transposed ? W : W / 2);
-  return (Cin % 64 == 0 && Cout % 64 == 0 && M % 64 == 0) ? 1 : 0;
+  return vf_internal_pconv_supported(mfma_mode, VfConvShape{B, H, W, Cin, Cout, k, stride, pad}, transposed != 0) ? 1 : 0;
 }
 /* conv forward / full-conv data-gradient: gather planes `ap` [B][H][W][Cin], weight planes `wp` [Cout][16][Cin] */
-int vf_internal_pconv_gather(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
-                             int Cout, int act, float slope, VfConvExtras* ex) {
-  VF_REQUIRE(vf_pconv_supported_in_mode(ctx->mfma_bf16, B, H, W, Cin, Cout, 4, 2, 1, 0), "vf_pconv_gather: unsupported shape B=%d %dx%d %d->%d (product mode %d)", B, H, W, Cin, Cout, ctx->mfma_bf16);
-  return pconv_like_fwd(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope, ex);
+int vf_internal_pconv_gather(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, const VfConvShape& s, int act,
+                             float slope, VfConvExtras* ex) {
+  VF_REQUIRE(vf_internal_pconv_supported(ctx->mfma_bf16, s, false), "vf_pconv_gather: unsupported shape B=%d %dx%d %d->%d (product mode %d)", s.B, s.H, s.W, s.Cin, s.Cout, ctx->mfma_bf16);
+  return pconv_like_fwd(ctx, ap, wp, bias, y, s, act, slope, ex);
 }
 VF_API int vf_pconv_gather(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
                            int Cout, int act, float slope) {
-  return vf_take_pending(ctx, [&](VfConvExtras* ex) { return vf_internal_pconv_gather(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope, ex); });
+  const VfConvShape s{B, H, W, Cin, Cout, 4, 2, 1};
+  return vf_take_pending(ctx, [&](VfConvExtras* ex) { return vf_internal_pconv_gather(ctx, ap, wp, bias, y, s, act, slope, ex); });
 }
 /* conv data-gradient / full-conv forward: low-res planes `ap` [B][H][W][Cin] -> y [B][2H][2W][Cout], weight planes [Cout][16][Cin] */
-int vf_internal_pconv_scatter(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
-                              int Cout, int act, float slope, const float* dmask, int dact, float dslope, VfConvExtras* ex) {
-  VF_REQUIRE(vf_pconv_supported_in_mode(ctx->mfma_bf16, B, H, W, Cin, Cout, 4, 2, 1, 1), "vf_pconv_scatter: unsupported shape B=%d %dx%d %d->%d (product mode %d)", B, H, W, Cin, Cout, ctx->mfma_bf16);
+int vf_internal_pconv_scatter(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, const VfConvShape& s, int act,
+                              float slope, const float* dmask, int dact, float dslope, VfConvExtras* ex) {
+  VF_REQUIRE(vf_internal_pconv_supported(ctx->mfma_bf16, s, true), "vf_pconv_scatter: unsupported shape B=%d %dx%d %d->%d (product mode %d)", s.B, s.H, s.W, s.Cin, s.Cout, ctx->mfma_bf16);
   VF_REQUIRE(!(dmask && bias), "vf_pconv_scatter: the activation-backward epilogue is for data-gradient passes (no bias)");
-  return pconv_like_tr(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope, dmask, dact, dslope, ex);
+  return pconv_like_tr(ctx, ap, wp, bias, y, s, act, slope, dmask, dact, dslope, ex);
 }
 VF_API int vf_pconv_scatter(vf_ctx* ctx, const void* ap, const void* wp, const float* bias, float* y, int B, int H, int W, int Cin,
                             int Cout, int act, float slope, const float* dmask, int dact, float dslope) {
+  const VfConvShape s{B, H, W, Cin, Cout, 4, 2, 1};
   return vf_take_pending(ctx, [&](VfConvExtras* ex) {
-    return vf_internal_pconv_scatter(ctx, ap, wp, bias, y, B, H, W, Cin, Cout, act, slope, dmask, dact, dslope, ex);
+    return vf_internal_pconv_scatter(ctx, ap, wp, bias, y, s, act, slope, dmask, dact, dslope, ex);
   });
 }
