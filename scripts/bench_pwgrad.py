@@ -1,5 +1,5 @@
 """Weight gradient from planes (k_pwgrad_group, vf_pgemm.hip) beside the fp32-operand kernel (k_wgrad, vf_conv.hip) on the layers of
-BASELINE.json configs[1]: back-to-back launches, one event pair around NB of them (split-K slab reduce included on both sides).
+BASELINE.json configs[1] (E2: 64 low-resolution channels, the 64-row tile form): back-to-back launches, one event pair around NB of them (split-K slab reduce included on both sides).
 python scripts/bench_pwgrad.py [B]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -9,7 +9,7 @@ from video_filler_amd.backend import get_backend
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 hb = get_backend()
-LAYERS = [("E3", 64, 32, 128), ("E4", 128, 16, 256), ("E5", 256, 8, 512), ("C1@2B", 64, 32, 128), ("C2@2B", 128, 16, 256),
+LAYERS = [("E2", 64, 64, 64), ("E3", 64, 32, 128), ("E4", 128, 16, 256), ("E5", 256, 8, 512), ("C1@2B", 64, 32, 128), ("C2@2B", 128, 16, 256),
           ("C3@2B", 256, 8, 512)]
 only = os.environ.get("ONLY", "")
 LAYERS = [l for l in LAYERS if not only or l[0] in only.split(",")]

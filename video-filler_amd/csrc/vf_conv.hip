@@ -1667,14 +1667,17 @@ static int wg_flush(vf_ctx* ctx) {
           r.blocks = r.pw.gx * r.pw.gy;
         }
     VfPWGradGroup G;
-    int blocks = 0;
+    int blocks = 0, n64 = 0;
     double fl = 0;
     G.n = 0;
     auto fire = [&]() -> int {
       if (G.n == 0) return 0;
       G.blk_off[G.n] = blocks;
-      const int rc = vf_internal_pwgrad_group(ctx, G, blocks, "pwgrad_group_128x128x32", fl);
+      // the label says which tile forms the launch holds (a planes layer with Nu == 64 runs the 64-row form)
+      const char* name = n64 == 0 ? "pwgrad_group_128x128x32" : (n64 == G.n ? "pwgrad_group_64x128x32" : "pwgrad_group_64+128x128x32");
+      const int rc = vf_internal_pwgrad_group(ctx, G, blocks, name, fl);
       G.n = 0;
+      n64 = 0;
       blocks = 0;
       fl = 0;
       return rc;
@@ -1684,6 +1687,7 @@ static int wg_flush(vf_ctx* ctx) {
       G.blk_off[G.n] = blocks;
       G.d[G.n] = r.pw;
       ++G.n;
+      n64 += r.pw.Up != nullptr && r.pw.Nu == 64;
       blocks += (r.blocks + 7) & ~7;
       fl += r.flops;
       if (G.n == VF_PWG_MAX)
@@ -1846,14 +1850,20 @@ static int wgrad(vf_ctx* ctx, const float* U, const float* V, float* dW, const V
   const int64_t blocks = (int64_t)gx * gy;
   const int64_t total = (int64_t)Nu * ntaps * Cv;
   int ksplit = 1;
-  // operands that arrive as planes (vf_*_bwd_weight_planes): the LDS-DMA kernel of vf_pgemm.hip, whole 128 x 128 x 32 tiles only
-  const bool use_pw = Up && Vp && (ctx->mfma_bf16 == 3 || ctx->mfma_bf16 == 1) && ntaps == 16 && stride == 2 && pad == 1 && Nu % 128 == 0 &&
+  // operands that arrive as planes (vf_*_bwd_weight_planes): the LDS-DMA kernel of vf_pgemm.hip, whole 128 x 128 x 32 tiles only —
+  // or, in the three-plane mode, ONE row tile of 64 (Nu == 64: its 64 x 128 x 32 tile form; the one-plane mode and every other
+  // Nu % 128 == 64 stay on the fp32-fed kernels)
+  const bool pw64 = Nu == 64 && ctx->mfma_bf16 == 3;
+  const bool use_pw = Up && Vp && (ctx->mfma_bf16 == 3 || ctx->mfma_bf16 == 1) && ntaps == 16 && stride == 2 && pad == 1 && (Nu % 128 == 0 || pw64) &&
                       Cv % 64 == 0 && g.P % 32 == 0 && (int64_t)g.P * Nu * 6 < ((int64_t)1 << 31) &&
                       (int64_t)B * Hv * Wv * Cv * 6 < ((int64_t)1 << 31) && total % 4 == 0;
   // split-K target, blocks per layer.  The planes layers ride in ONE group launch of seven or more layers, which fills the chip as
   // a whole: half the splits per layer leave k_pwgrad_group's time where it was and halve the slabs it writes and the combine
   // reads (same-box: combine 2 x 37.4 -> 2 x 21.8 us); the fp32-fed thin layers' kernel wants the full 512 (62 -> 86 us at 256)
-  const int wg_blocks = use_pw ? 256 : 512;
+  // A 64-row tile is half a 128-row tile's work per K step: 512 of them per layer keep its blocks as long as the launch's others
+  // (at 256, E2's blocks run 64 half steps against the 8 - 16 whole ones of its neighbours and end the launch alone: same-box, the
+  // iteration 2.851 ms at 256, 2.813 at 512, 2.842 before the form existed) — and the split is then the fp32-fed kernel's own: same bits
+  const int wg_blocks = use_pw && !pw64 ? 256 : 512;
   if (blocks < wg_blocks * 3 / 4 && g.nk >= 16) {
     ksplit = (int)std::min<int64_t>(g.nk / 8, vf_cdiv(wg_blocks, blocks));
     while (ksplit > 1 && (size_t)ksplit * total * sizeof(float) > vf_ws_avail(ctx)) --ksplit;

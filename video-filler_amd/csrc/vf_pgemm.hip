@@ -1283,7 +1283,8 @@ __global__ __launch_bounds__(512) void k_pconv_patch_g(const PGemm p) {
 // FS = 2 serves the one-plane (bf16) mode.
 // Layers WITHOUT planes (Up == NULL: the bottleneck pair, plain [K][Nu] x [K][16 Cv] fp32 matrices) are staged by the block
 // itself — float4 loads, exact three-way split, 8-byte LDS writes into the same swizzled image — so that they share the launch.  Whole tiles only (Nu % 128 == 0, Cv % 64 == 0, P % 32 == 0): the host keeps
-// everything else on vf_conv.hip's k_wgrad.
+// everything else on vf_conv.hip's k_wgrad — except a planes layer with Nu == 64, whose blocks take the 64-row tile form
+// (pwgrad_tile64 below) inside this kernel.
 __device__ __forceinline__ bf16x8 pg_tr_frag(const __bf16* tile, int col0, int k0, int lane) {
   // tile: [32][128] bf16, 256-byte rows, 64-byte block b of row k stored at block b ^ (k & 3).  Lane l gets column
   // col0 + l % 32 (col0 a multiple of 32), k = k0 + 8 * (l / 32) .. + 7
@@ -1295,6 +1296,102 @@ __device__ __forceinline__ bf16x8 pg_tr_frag(const __bf16* tile, int col0, int k
   const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)a);
   const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(a + 4 * 128));      // rows k + 4: the same (k & 3)
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+// The same fragment from a 64-column tile (the 64-row form's U operand): [32][64] bf16, 128-byte rows, so TWO rows span the 64
+// banks and rows k, k + 2 of a 4-row transposing read would meet on the same ones: 64-byte block b (0 / 1) of row k is stored at
+// block b ^ ((k >> 1) & 1).  A 32-lane half (one LDS cycle: the b64 lane groups) reads rows k .. k + 3 of one 64-byte block, which then
+// sit at bank bytes b * 64, 128 + b * 64, (b ^ 1) * 64, 128 + (b ^ 1) * 64: all 256, once each.
+__device__ __forceinline__ bf16x8 pg_tr_frag64(const __bf16* tile, int col0, int k0, int lane) {
+  const int grp = lane >> 4, i = lane & 15;
+  const int k = k0 + 8 * (grp >> 1) + (i >> 2);
+  const int blk = (col0 >> 5) ^ ((i >> 3) & 1);                 // ((k >> 1) & 1) == (i >> 3) & 1: k0 and 8 * (grp >> 1) are multiples of 4
+  const __bf16* a = tile + k * 64 + blk * 32 + 16 * (grp & 1) + 4 * (i & 3);
+  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)a);
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(a + 4 * 64));       // rows k + 4: the same ((k >> 1) & 1)
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// The 64-row tile form (a planes layer with Nu == 64: E2 of the generator): 64 (n) x 128 (tap, c) per block, eight waves of ONE
+// 32 x 32 accumulator (two rows of four), a stage [3 planes][U 32 x 64 | V 32 x 128] = 36 KB.  V moves as in the 128-row form (wave w:
+// rows 4w .. 4w + 3 of every plane); a DMA instruction covers EIGHT of U's 128-byte rows, so waves 0 - 3 move U (wave w: rows
+// 8w .. 8w + 7) and waves 4 - 7 none.  Per output element the same six product terms, smallest first, and the same K order as the
+// 128-row form.  It lives in the same kernel (a layer's blocks choose their form), so that such layers share the group launch.
+template <int NPL>
+__device__ __forceinline__ void pwgrad_tile64(const VfPWGrad& p, __bf16* smem, int tid, int lane, int wave, int j0, int ks, int kt0,
+                                              int kt1) {
+  constexpr int BK = 32, TILE_U = BK * 64, TILE_V = BK * 128, PL_SZ = TILE_U + TILE_V;      // bf16 elements
+  const int wm = (wave >> 2) * 32, wn = (wave & 3) * 32;
+  // V: as the 128-row form
+  const int krow = 4 * wave + (lane >> 4);
+  const int slot = lane & 15;
+  const int chunk = (((slot >> 2) ^ (krow & 3)) << 2) | (slot & 3);
+  const int col = j0 + 8 * chunk;
+  const int tap = col / p.Cv, cch = col - tap * p.Cv;
+  const int dy = (tap >> 2) - 1, dx = (tap & 3) - 1;
+  // U (waves 0 - 3): pixel row 8 * wave + lane / 8, 16-byte chunk lane % 8 of the 128-byte row, fetched from its swizzled source
+  const int krow_u = 8 * (wave & 3) + (lane >> 3);
+  const int slot_u = lane & 7;
+  const int chunk_u = (((slot_u >> 2) ^ ((krow_u >> 1) & 1)) << 2) | (slot_u & 3);
+  const unsigned u_off = 2u * (unsigned)(8 * chunk_u);                         // (one row tile: n0 = 0)
+  const int Mw = 1 << p.lgMw, Mh = 1 << p.lgMh;
+  const __amdgpu_buffer_rsrc_t rsU = vf_rsrc(p.Up, (unsigned)NPL * p.u_ps), rsV = vf_rsrc(p.Vp, (unsigned)NPL * p.v_ps);
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
+  const unsigned row_v = 2u * (unsigned)(TILE_U + 4 * wave * 128), row_u = 2u * (unsigned)(8 * (wave & 3) * 64);
+  unsigned szero;
+  asm volatile("s_mov_b32 %0, 0" : "=s"(szero));
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  for (int kt = kt0; kt < kt1; ++kt) {
+    {
+      const int pix = kt * BK + krow;
+      const int mx = pix & (Mw - 1), my = (pix >> p.lgMw) & (Mh - 1), b = pix >> (p.lgMw + p.lgMh);
+      const int iy = 2 * my + dy, ix = 2 * mx + dx;
+      const bool okv = (unsigned)iy < (unsigned)p.Hv && (unsigned)ix < (unsigned)p.Wv;
+      const unsigned vo = okv ? 2u * (unsigned)(((b * p.Hv + iy) * p.Wv + ix) * p.Cv + cch) : VF_OOB;
+      const unsigned uo = u_off + 2u * (unsigned)((kt * BK + krow_u) * 64);
+#pragma unroll
+      for (int q = 0; q < NPL; ++q) {
+        if (wave < 4) pg_dma16(lds0 + row_u + 2u * (unsigned)(q * PL_SZ), uo, rsU, szero + q * p.u_ps);      // (wave-uniform branch)
+        pg_dma16(lds0 + row_v + 2u * (unsigned)(q * PL_SZ), vo, rsV, szero + q * p.v_ps);
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int g = 0; g < BK / 16; ++g) {
+      bf16x8 a1[NPL], b1[NPL];
+#pragma unroll
+      for (int q = 0; q < NPL; ++q) {
+        a1[q] = pg_tr_frag64(smem + q * PL_SZ, wm, 16 * g, lane);
+        b1[q] = pg_tr_frag(smem + q * PL_SZ + TILE_U, wn, 16 * g, lane);
+      }
+      if constexpr (NPL == 3) {      // smallest terms first (the order of the 128-row form)
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[1], b1[1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b1[2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[2], b1[0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b1[1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[1], b1[0], acc, 0, 0, 0);
+      }
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b1[0], acc, 0, 0, 0);
+    }
+    asm volatile("s_barrier" ::: "memory");
+  }
+  // ---- epilogue: C/D layout col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+  const int lr = lane & 31, lh = lane >> 5;
+  const int Ncols = 16 * p.Cv;
+  const int64_t total = (int64_t)64 * Ncols;
+  float* out = p.out + (p.ksplit > 1 ? (int64_t)ks * total : 0);
+  const bool acc_old = p.ksplit == 1 && p.beta != 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int n = wm + (r & 3) + 8 * (r >> 2) + 4 * lh;
+    const int64_t idx = (int64_t)n * Ncols + j0 + wn + lr;
+    float v = acc[r];
+    if (acc_old) v += p.beta * out[idx];
+    out[idx] = v;
+  }
 }
 
 template <int NPL = 3, int FS = 1>
@@ -1317,6 +1414,12 @@ __global__ __launch_bounds__(512, FS == 1 ? 6 : 1) void k_pwgrad_group(const VfP
   const int ks = __builtin_amdgcn_readfirstlane(rest / p.gy);
   const int steps = (p.nk + p.ksplit - 1) / p.ksplit;
   const int kt0 = ks * steps, kt1 = min(p.nk, kt0 + steps);
+  if constexpr (NPL == 3) {
+    if (p.Up != nullptr && p.Nu == 64) {               // (uniform over the block) the 64-row tile form: gy = 1
+      pwgrad_tile64<NPL>(p, smem, tid, lane, wave, j0, ks, kt0, kt1);
+      return;
+    }
+  }
 
   // ---- this lane's piece of every stage: pixel row k = 4 * wave + lane / 16, 16-byte chunk lane % 16 of the 256-byte row;
   //      the chunk it FETCHES is the one whose swizzled home is that slot
