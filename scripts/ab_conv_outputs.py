@@ -1,6 +1,7 @@
 """Same answers from two builds of the library, where the test suite cannot see a difference: every conv pass of the C-ABI on
 NON-SQUARE maps with Cin != Cout, the bottleneck and head geometries, the generic path, the planes passes, pending BatchNorm
-requests, vf_net with the planes gate dropped — raw output bytes, and the messages of the calls that are refused.
+requests, vf_net with the planes gate dropped, weight-gradient groups under small workspaces and with every route in one walk
+— raw output bytes, and the messages of the calls that are refused.
 
     VF_HIP_LIB=/path/to/other/libvf_hip.so python scripts/ab_conv_outputs.py dump a.npz      # one fresh process per build
     python scripts/ab_conv_outputs.py dump b.npz                                             # the in-tree build
@@ -8,6 +9,7 @@ requests, vf_net with the planes gate dropped — raw output bytes, and the mess
 
 The criterion is equality between the builds, not correctness: a shape one build refuses or gets wrong must be refused or wrong
 identically by the other (the tool of a refactoring of the host code: profiles/README.md, "One conv geometry type")."""
+import contextlib
 import ctypes as C
 import json
 import os
@@ -256,6 +258,134 @@ def truth_tables(d):
     d.out["truth/pconv_supported"] = np.asarray(sup, np.uint8)
 
 
+class WgLayer:
+    """one weight gradient of a backward walk (4x4 taps): its operands, optionally their planes, gw and gb"""
+
+    def __init__(self, d, full, B, Cin, H, Cout, beta, bias, planes=False, stride=2):
+        hb = d.B
+        pad = 1 if stride == 2 else 0
+        Ho = ((H - 1) * stride - 2 * pad + 4) if full else ((H + 2 * pad - 4) // stride + 1)
+        self.x, self.gy = d.rand(B, Cin, H, H), d.rand(B, Cout, Ho, Ho, scale=0.1)
+        self.gw = d.rand(*((Cin, Cout, 4, 4) if full else (Cout, Cin, 4, 4)))
+        self.gb = d.rand(Cout) if bias else None
+        self.gw0, self.gb0 = self.gw.clone(), None if self.gb is None else self.gb.clone()
+        self.xp = self.gp = None
+        if planes:
+            self.xp, self.gp = hb.planes_split(self.x), hb.planes_split(self.gy)
+        fn = hb.deconv2d_bwd_weight if full else hb.conv2d_bwd_weight
+        self.launch = lambda: fn(self.x, self.gy, self.gw, self.gb, 4, stride, pad, float(beta), self.xp, self.gp)
+        self.total = self.gw.numel()
+
+    def reset(self):
+        self.gw.copy_(self.gw0)
+        if self.gb is not None:
+            self.gb.copy_(self.gb0)
+
+    def tensors(self):
+        return [self.gw] + ([] if self.gb is None else [self.gb])
+
+    def slab_need(self, hb):
+        """the slab bytes this layer reserves when recorded (256-byte rounding), from the split count its profile shows"""
+        self.reset()
+        hb.prof_begin()
+        try:
+            self.launch()
+        finally:
+            prof = hb.prof_end()
+        k = max([int(round(e["bytes"] / (4.0 * self.total) - 1)) for n, e in prof.items() if n in ("slab_reduce_wgrad", "slab_reduce_wgrad_group")] or [1])
+        return ((k * self.total * 4 + 255) // 256 * 256) if k > 1 else 0
+
+
+@contextlib.contextmanager
+def small_workspace(hb, nbytes):
+    from video_filler_amd import _lib
+    buf = torch.zeros(max(nbytes, 256), dtype=torch.uint8, device=hb.device)
+    old = hb.workspace
+    _lib.check(hb.lib.vf_ctx_set_workspace(hb.ctx, C.c_void_p(buf.data_ptr()), nbytes))
+    hb.workspace = buf[:nbytes]
+    hb.__dict__.pop("_colsum_plans", None)
+    try:
+        yield
+    finally:
+        hb.synchronize()
+        hb.workspace = old
+        hb.__dict__.pop("_colsum_plans", None)
+        _lib.check(hb.lib.vf_ctx_set_workspace(hb.ctx, C.c_void_p(old.data_ptr()), old.numel()))
+
+
+def wgrad_groups(d):
+    """vf_wgrad_group_*: the two walks of tests/test_gpu_workspace.py::test_wgrad_group_under_pressure with their small workspaces
+    (a flush in the middle of a walk, a single launch behind recorded slabs, a partial end), and in every product mode one walk
+    that holds every route: planes on the 128- and the 64-row tile, the bottleneck pair at a batch the small-K kernel takes and at
+    one it declines (there they ride with the planes layers), fp32-fed layers of both tile heights and a thin one launched singly"""
+    hb = d.B
+    hb.set_mfma_mode("f32_3xbf16")
+    L1 = WgLayer(d, False, 8, 64, 32, 128, 0, True)
+    L2 = WgLayer(d, True, 8, 128, 16, 64, 1, True)
+    L3 = WgLayer(d, False, 8, 128, 16, 256, 1, True, planes=True)
+    TH = WgLayer(d, False, 2, 3, 64, 64, 0, True)
+    L4 = WgLayer(d, False, 8, 64, 64, 128, 1, False)
+    n1, n2, n3, nt = (L.slab_need(hb) for L in (L1, L2, L3, TH))
+    d.out["wgrad_groups/slab_needs"] = np.frombuffer(np.asarray([n1, n2, n3, nt], np.int64).tobytes(), np.uint8)
+
+    def walk(name, ws, layers, steps):
+        counts = []
+
+        def go():
+            for L in layers:
+                L.reset()
+            with small_workspace(hb, ws):
+                try:
+                    steps(counts)
+                except RuntimeError:
+                    hb.wgrad_group_abort()
+                    raise
+        if d.run(name, go, *[t for L in layers for t in L.tensors()]):
+            d.out[name + "/counts"] = np.frombuffer(np.asarray(counts, np.int32).tobytes(), np.uint8)
+
+    def walk_a(counts):
+        hb.wgrad_group_begin()
+        for L in (L1, L2, L3, TH):
+            L.launch()
+            counts.append(hb.wgrad_group_count())
+        hb.wgrad_group_end_partial(hb.wgrad_group_count())
+        counts.append(hb.wgrad_group_count())
+        L4.launch()
+        counts.append(hb.wgrad_group_count())
+        hb.wgrad_group_end()
+
+    def walk_b(counts):
+        hb.wgrad_group_begin()
+        for L in (L1, L2, TH):
+            L.launch()
+            counts.append(hb.wgrad_group_count())
+        hb.wgrad_group_end()
+    walk("wgrad_groups/pressure_walk_a", n1 + n2 + n3 // 2, (L1, L2, L3, TH, L4), walk_a)
+    walk("wgrad_groups/pressure_walk_b", n1 + n2 + nt - 256, (L1, L2, TH), walk_b)
+
+    for mode in ("f32_3xbf16", "bf16", "f32"):
+        hb.set_mfma_mode(mode)
+        mixed = [WgLayer(d, False, 8, 64, 32, 128, 1, True, planes=True),             # planes, 128-row tile
+                 WgLayer(d, False, 8, 64, 32, 64, 0, True, planes=True),              # planes, 64-row tile (three-plane mode)
+                 WgLayer(d, False, 8, 128, 4, 128, 0, True, stride=1),                # bottleneck 4x4 -> 1x1, K = 8
+                 WgLayer(d, True, 8, 128, 1, 128, 1, True, stride=1),                 # bottleneck 1x1 -> 4x4
+                 WgLayer(d, False, 40, 128, 4, 128, 1, False, stride=1),              # the pair at K = 40: not the small-K kernel's
+                 WgLayer(d, True, 40, 128, 1, 128, 0, False, stride=1),
+                 WgLayer(d, True, 8, 128, 16, 64, 0, True),                           # fp32-fed, 128-row family
+                 WgLayer(d, False, 8, 32, 32, 64, 1, False),                          # fp32-fed, 64-row family
+                 WgLayer(d, False, 2, 3, 64, 64, 0, True)]                            # thin: launched singly while the group is open
+
+        def walk_mixed(counts):
+            hb.wgrad_group_begin()
+            for L in mixed:
+                L.launch()
+                counts.append(hb.wgrad_group_count())
+            hb.wgrad_group_end()
+        walk("wgrad_groups/%s/mixed_walk" % mode, hb.workspace.numel(), mixed, walk_mixed)
+        walk("wgrad_groups/%s/mixed_walk_64MB" % mode, 64 << 20, mixed, walk_mixed)
+    hb.set_mfma_mode("f32_3xbf16")
+
+
 def dump(path):
     from video_filler_amd import _lib, nn
     from video_filler_amd.backend import get_backend
@@ -289,6 +419,7 @@ def dump(path):
             net_passes(d, "%s/%s/net_head_B2" % (mode, gname), head, (2, 3, 16, 16))
             net_passes(d, "%s/%s/net_head_B3" % (mode, gname), head, (3, 3, 16, 16))
             net_passes(d, "%s/%s/net_bottleneck_B3" % (mode, gname), bottleneck, (3, 32, 8, 8))
+    wgrad_groups(d)
     np.savez(path, **d.out)
     n = sum(1 for k in d.out if k.startswith("refused:"))
     print("%s: %d records (%d refused), %d bytes, library %s" % (path, len(d.out), n, sum(v.size for v in d.out.values()), _lib.lib_path()))

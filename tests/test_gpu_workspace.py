@@ -550,6 +550,99 @@ def test_wgrad_group_under_pressure(wb):
         L.check("walk B")
 
 
+def test_wgrad_group_longer_than_a_table(wb):
+    """one walk that records more layers per kernel family than a descriptor table holds (16): 16 planes layers on the 128-row
+    tile and a 17th on the 64-row form, 17 fp32-fed layers on each of the 128- and 64-row families.  Every layer is B = 2 on an
+    8 x 8 map: one K step, so nothing splits.  Each layer has its own operands, so a descriptor in the wrong slot shows."""
+    b = wb
+    fams = {"planes": [WLayer(b, "planes conv 64->128 #%d" % i, False, 2, 64, 8, 128, i % 2, False, planes=True, seed=1000 + 10 * i)
+                       for i in range(16)]}
+    fams["planes"].append(WLayer(b, "planes conv 64->64 #16", False, 2, 64, 8, 64, 0, False, planes=True, seed=1160))
+    fams["fp32_128"] = [WLayer(b, "conv 32->128 #%d" % i, False, 2, 32, 8, 128, i % 2, False, seed=2000 + 10 * i) for i in range(17)]
+    fams["fp32_64"] = [WLayer(b, "conv 32->64 #%d" % i, False, 2, 32, 8, 64, i % 2, False, seed=3000 + 10 * i) for i in range(17)]
+    walk = fams["planes"] + fams["fp32_128"] + fams["fp32_64"]
+    for L in walk:
+        L.reset()
+    counts = []
+    with workspace(b, hint(b)):
+        def go():
+            b.wgrad_group_begin()
+            for L in walk:
+                L.launch()
+            counts.append(b.wgrad_group_count())
+            b.wgrad_group_end()
+            counts.append(b.wgrad_group_count())
+        prof = profiled(b, go)
+    assert counts == [len(walk), 0], counts
+    for L in walk:
+        L.check("one walk of %d layers" % len(walk))
+    launches = {n: e["launches"] for n, e in prof.items()}
+    print("launches:", launches)
+    assert launches.get("pwgrad_group_128x128x32") == 1, launches      # the first table: no 64-row layer counted into its label
+    assert launches.get("pwgrad_group_64x128x32") == 1, launches       # the 17th planes record, alone in the second table
+    assert "pwgrad_group_64+128x128x32" not in launches, launches
+    assert launches.get("wgrad_group_128x128_bf16x3") == 2, launches
+    assert launches.get("wgrad_group_64x128_bf16x3") == 2, launches
+    assert "slab_reduce_wgrad_group" not in launches and "slab_reduce_wgrad" not in launches, launches
+    # alone, outside a group, a layer runs the same tile code over the same single K range: the same bits
+    for fam, layers in fams.items():
+        for i in (0, 15, 16):
+            L = layers[i]
+            grouped = L.gw.clone()
+            L.reset()
+            with workspace(b, hint(b)):
+                L.launch()
+            L.check("alone")
+            assert torch.equal(L.gw, grouped), "%s: grouped and alone differ" % L.name
+
+
+def test_wgrad_group_protocol(wb):
+    """begin / end / abort / end_partial: what each leaves recorded, launched and open"""
+    b = wb
+    L = WLayer(b, "conv 32->128 8x8", False, 2, 32, 8, 128, 0, False, seed=4000)
+    M = WLayer(b, "conv 32->64 8x8", False, 2, 32, 8, 64, 0, False, seed=4010)
+
+    def all_nan(t):
+        b.synchronize()
+        return bool(torch.isnan(t).all())
+
+    with workspace(b, hint(b)):
+        with pytest.raises(RuntimeError, match="no group is open"):
+            b.wgrad_group_end()
+        # a walk abandoned before its end: the next begin drops its records, nothing of it is launched
+        L.reset()
+        b.wgrad_group_begin()
+        L.launch()
+        assert b.wgrad_group_count() == 1
+        b.wgrad_group_begin()
+        assert b.wgrad_group_count() == 0
+        b.wgrad_group_end()
+        assert all_nan(L.gw), "a record of the abandoned walk was launched"
+        # abort: records dropped, group closed; the next launch runs at once
+        b.wgrad_group_begin()
+        L.launch()
+        b.wgrad_group_abort()
+        assert b.wgrad_group_count() == 0
+        assert all_nan(L.gw), "abort launched a record"
+        L.launch()
+        L.check("ungrouped, after an abort")
+        with pytest.raises(RuntimeError, match="no group is open"):
+            b.wgrad_group_end()
+        # a partial end of at least everything recorded: all launched, the group stays open and takes further records
+        L.reset()
+        M.reset()
+        b.wgrad_group_begin()
+        L.launch()
+        b.wgrad_group_end_partial(5)
+        assert b.wgrad_group_count() == 0
+        L.check("launched by end_partial")
+        M.launch()
+        assert b.wgrad_group_count() == 1 and all_nan(M.gw)
+        b.wgrad_group_end()
+        M.check("recorded after end_partial")
+        L.check("after the end")
+
+
 # ---------------------------------------------------------------------------------------------------------------- routes
 def test_thin_output_column_buffer_threshold(wb):
     """the transposed passes with 4 < N < 32 outputs take the column buffer + col2im4x4 only if col_bytes + 32 MB fit: the video

@@ -63,8 +63,7 @@ struct vf_ctx {
   size_t ws_bytes;
   size_t ws_front;  // bytes at the front of ws currently held by an im2col / column buffer (thin-channel passes)
   int mfma_bf16;    // 0: native f32 MFMA; 1: operands rounded to bf16; 3 (default): exact three-plane bf16 split
-  int wg_active;    // a weight-gradient group is being recorded (vf_wgrad_group_begin .. _end)
-  void* wg_rec;     // the recorder (vf_conv.hip)
+  WgRecorder* wg;   // the weight-gradient group recorder and its open flag (vf_conv.hip: made on first use, freed by vf_internal_wg_free)
   // the public two-call protocol around a conv (module-by-module hosts): vf_bn_fuse_next_* leave a request here, the next
   // forward / data-gradient entry point takes it, unconditionally (vf_take_pending), and vf_bn_fuse_result reads what it made of it
   VfBnRequest bn_pending;

@@ -1628,350 +1628,356 @@ static int conv_like_bwd(vf_ctx* ctx, const float* A, const float* w, const floa
 }
 
 // dW[n][kh][kw][c] = beta*dW + sum_p U[p][n] * V[b, my*s-pad+kh, mx*s-pad+kw, c]
-// ---- recorder of a weight-gradient group (see k_wgrad_group)
-struct WgRec {
-  WGrad g;
-  int bm, bf;          // tile rows (128 / 64), matrix-core mode; bf = 4: operands are pre-split planes (pw, k_pwgrad_group)
-  VfPWGrad pw;
-  bool plain_ok;       // a bottleneck layer (fp32 operands, K = batch) that can ride in a k_pwgrad_group launch: pw is its
-                       // fp32-fed descriptor, used when the group has planes layers (else it stays with k_wgrad_group)
-  int blocks;
-  int64_t total;       // dW elements
-  double flops;
+// ---- the plan of one weight gradient: both sides of the layer, the kernel that serves it, its split over K
+enum WgRoute {
+  WG_SMALLK,        // the bottleneck pair: vf_wgrad_small.hip's kernel, where it takes the call (else fp32_route())
+  WG_PLANES_128,    // operands as planes: k_pwgrad_group (vf_pgemm.hip), whole 128 x 128 x 32 tiles
+  WG_PLANES_64,     //   ... its 64 x 128 x 32 tile form: ONE row tile of 64
+  WG_FP32_GROUP,    // fp32 operands that a group launch can take (k_wgrad_group: 16-byte loads on both sides)
+  WG_FP32_SINGLE    // fp32 operands, launched at once (k_wgrad)
 };
-struct WgRecorder {
-  std::vector<WgRec> recs;
-  size_t ws_used = 0;
+struct WgPlan {
+  int B, stride, pad;
+  int P, Hl, Wl, Nu;      // U's side, the low-resolution map: pixels, map, channels
+  int Hv, Wv, Cv;         // V's side
+  bool vecU, vecV;        // 16-byte loads are legal
+  int nk;                 // K steps of the kernel's BK
+  int bm, gx, gy;         // tile rows (128 / 64), column tiles, row tiles
+  int64_t total;          // dW elements
+  int target, ksplit;     // split-K: the blocks per layer aimed at, the K ranges taken
+  WgRoute route;
+  bool rider;             // a bottleneck layer that can ride in a planes launch, in the fp32-fed form of its descriptor
+  // the bottleneck pair (1x1 map on one side, 4x4 on the other): dW = U^T V with K = batch — write-bound
+  bool is_bottleneck() const { return Hl == 1 && Wl == 1 && Hv == 4 && Wv == 4 && stride == 1 && pad == 0; }
+  bool planes() const { return route == WG_PLANES_128 || route == WG_PLANES_64; }
+  int64_t u_elems() const { return (int64_t)P * Nu; }
+  int64_t v_elems() const { return (int64_t)B * Hv * Wv * Cv; }
+  // both operands inside the 2 GiB a buffer descriptor spans, at `bytes` per element (4: fp32; 6: three bf16 planes)
+  bool in_range(int bytes) const { return u_elems() * bytes < ((int64_t)1 << 31) && v_elems() * bytes < ((int64_t)1 << 31); }
+  WgRoute fp32_route() const { return vecU && vecV && (ksplit == 1 || total % 4 == 0) ? WG_FP32_GROUP : WG_FP32_SINGLE; }
+  int blocks() const { return gx * gy * ksplit; }
+  size_t slab_bytes() const { return ksplit > 1 ? vf_up256((size_t)ksplit * total * sizeof(float)) : 0; }
+  double flops() const { return 2.0 * (double)P * Nu * 16.0 * Cv; }
 };
-void vf_internal_wg_free(vf_ctx* ctx) {
-  delete (WgRecorder*)ctx->wg_rec;
-  ctx->wg_rec = nullptr;
-}
-template <int BM, int BF>
-static void launch_wg_group(vf_ctx* ctx, const WGradGroup& G, int blocks, const char* name, double flops) {
-  VF_LAUNCH_TIMED(ctx, name, flops, 0.0, (k_wgrad_group<BM, true, true, BF>), dim3(blocks), dim3(256), G);
-}
-static int wg_flush(vf_ctx* ctx) {
-  WgRecorder* R = (WgRecorder*)ctx->wg_rec;
-  if (!R || R->recs.empty()) return 0;
-  // the layers whose operands came as planes: one k_pwgrad_group launch (vf_pgemm.hip).  The bottleneck layers of the same
-  // walk go with them in their fp32-fed form: write-bound tiles (131 MB of dW from K = batch) that hide under the MFMA-bound
-  // ones of the same launch, as they did in k_wgrad_group
-  {
-    bool any_planes = false;
-    for (const WgRec& r : R->recs) any_planes |= (r.bf == 4);
-    if (any_planes)
-      for (WgRec& r : R->recs)
-        if ((r.bf == 3 || r.bf == 1) && r.plain_ok) {
-          r.bf = 4;
-          r.blocks = r.pw.gx * r.pw.gy;
-        }
-    VfPWGradGroup G;
-    int blocks = 0, n64 = 0;
-    double fl = 0;
-    G.n = 0;
-    auto fire = [&]() -> int {
-      if (G.n == 0) return 0;
-      G.blk_off[G.n] = blocks;
-      // the label says which tile forms the launch holds (a planes layer with Nu == 64 runs the 64-row form)
-      const char* name = n64 == 0 ? "pwgrad_group_128x128x32" : (n64 == G.n ? "pwgrad_group_64x128x32" : "pwgrad_group_64+128x128x32");
-      const int rc = vf_internal_pwgrad_group(ctx, G, blocks, name, fl);
-      G.n = 0;
-      n64 = 0;
-      blocks = 0;
-      fl = 0;
-      return rc;
-    };
-    for (const WgRec& r : R->recs) {
-      if (r.bf != 4) continue;
-      G.blk_off[G.n] = blocks;
-      G.d[G.n] = r.pw;
-      ++G.n;
-      n64 += r.pw.Up != nullptr && r.pw.Nu == 64;
-      blocks += (r.blocks + 7) & ~7;
-      fl += r.flops;
-      if (G.n == VF_PWG_MAX)
-        if (int rc = fire()) return rc;
-    }
-    if (int rc = fire()) return rc;
-  }
-  // one launch per (tile rows, mode) family, VF_WG_GROUP_MAX layers at a time
-  for (int bm : {128, 64})
-    for (int bf : {3, 1, 0}) {
-      WGradGroup G;
-      int blocks = 0;
-      double fl = 0;
-      G.n = 0;
-      auto fire = [&]() {
-        if (G.n == 0) return;
-        G.blk_off[G.n] = blocks;
-        char name[64];
-        snprintf(name, sizeof(name), "wgrad_group_%dx128%s", bm, bf == 3 ? "_bf16x3" : (bf ? "_bf16" : ""));
-        if (bm == 128) {
-          if (bf == 3) launch_wg_group<128, 3>(ctx, G, blocks, name, fl);
-          else if (bf == 1) launch_wg_group<128, 1>(ctx, G, blocks, name, fl);
-          else launch_wg_group<128, 0>(ctx, G, blocks, name, fl);
-        } else {
-          if (bf == 3) launch_wg_group<64, 3>(ctx, G, blocks, name, fl);
-          else if (bf == 1) launch_wg_group<64, 1>(ctx, G, blocks, name, fl);
-          else launch_wg_group<64, 0>(ctx, G, blocks, name, fl);
-        }
-        G.n = 0;
-        blocks = 0;
-        fl = 0;
-      };
-      for (const WgRec& r : R->recs) {
-        if (r.bm != bm || r.bf != bf) continue;
-        G.blk_off[G.n] = blocks;
-        G.d[G.n] = r.g;
-        ++G.n;
-        blocks += (r.blocks + 7) & ~7;
-        fl += r.flops;
-        if (G.n == VF_WG_GROUP_MAX) fire();
-      }
-      fire();
-    }
-  VF_LAUNCH_CHECK();
-  // the split-K slabs of all layers: one launch per VF_WG_GROUP_MAX layers
-  {
-    SlabGroup S;
-    int blocks = 0;
-    double bytes = 0;
-    S.n = 0;
-    auto fire = [&]() {
-      if (S.n == 0) return;
-      S.blk_off[S.n] = blocks;
-      VfProf prof(ctx, "slab_reduce_wgrad_group", 0.0, bytes);
-      hipLaunchKernelGGL(k_slab_reduce4_group, dim3(blocks), dim3(256), 0, ctx->stream, S);
-      S.n = 0;
-      blocks = 0;
-      bytes = 0;
-    };
-    for (const WgRec& r : R->recs) {
-      if (r.g.ksplit <= 1) continue;
-      S.blk_off[S.n] = blocks;
-      S.d[S.n].slab = r.g.slab;
-      S.d[S.n].dst = r.g.dW;
-      S.d[S.n].total4 = r.total / 4;
-      S.d[S.n].ksplit = r.g.ksplit;
-      S.d[S.n].beta = r.g.beta;
-      ++S.n;
-      blocks += (int)vf_cdiv(r.total / 4, 64);
-      bytes += 4.0 * (double)r.total * (r.g.ksplit + 1);
-      if (S.n == VF_WG_GROUP_MAX) fire();
-    }
-    fire();
-  }
-  VF_LAUNCH_CHECK();
-  R->recs.clear();
-  R->ws_used = 0;
-  return 0;
-}
-VF_API int vf_wgrad_group_begin(vf_ctx* ctx) {
-  if (!ctx->wg_rec) ctx->wg_rec = new WgRecorder();
-  if (ctx->wg_active) {      // the previous walk was abandoned before its _end (a host-side error): drop what it recorded
-    ((WgRecorder*)ctx->wg_rec)->recs.clear();
-    ((WgRecorder*)ctx->wg_rec)->ws_used = 0;
-  }
-  ctx->wg_active = 1;
-  return 0;
-}
-VF_API int vf_wgrad_group_abort(vf_ctx* ctx) {
-  if (ctx->wg_rec) {
-    ((WgRecorder*)ctx->wg_rec)->recs.clear();
-    ((WgRecorder*)ctx->wg_rec)->ws_used = 0;
-  }
-  ctx->wg_active = 0;
-  return 0;
-}
-VF_API int vf_wgrad_group_end(vf_ctx* ctx) {
-  VF_REQUIRE(ctx->wg_active, "vf_wgrad_group_end: no group is open");
-  ctx->wg_active = 0;
-  return wg_flush(ctx);
-}
-
-// weight gradients recorded so far in the open group (not yet launched)
-VF_API int vf_wgrad_group_count(vf_ctx* ctx, int* count) {
-  VF_REQUIRE(count != nullptr, "vf_wgrad_group_count: NULL");
-  *count = (ctx->wg_active && ctx->wg_rec) ? (int)((WgRecorder*)ctx->wg_rec)->recs.size() : 0;
-  return 0;
-}
-// launch the FIRST `count` recorded weight gradients (record order = walk order: the layers nearest the net's output) as one
-// group and keep the group open with the rest still recorded: a data-parallel host starts the exchange of the finished bucket
-// and then ends the group — both launches sit at the END of the backward walk, none in the middle of its data-gradient chain
-VF_API int vf_wgrad_group_end_partial(vf_ctx* ctx, int count) {
-  VF_REQUIRE(ctx->wg_active, "vf_wgrad_group_end_partial: no group is open");
-  WgRecorder* R = (WgRecorder*)ctx->wg_rec;
-  if (!R || R->recs.empty() || count <= 0) return 0;
-  if (count >= (int)R->recs.size()) {
-    const size_t used = R->ws_used;
-    const int rc = wg_flush(ctx);
-    R->ws_used = used;      // (later records must not reuse slab regions a launch in flight still reads)
-    return rc;
-  }
-  std::vector<WgRec> rest(R->recs.begin() + count, R->recs.end());
-  R->recs.resize((size_t)count);
-  const size_t used = R->ws_used;
-  const int rc = wg_flush(ctx);
-  R->recs = rest;
-  R->ws_used = used;
-  return rc;
-}
-
 // s: the layer; U lives on its low-resolution map, V on the other (conv: gradOutput, input; full: input, gradOutput); Up / Vp: planes or NULL
-static int wgrad(vf_ctx* ctx, const float* U, const float* V, float* dW, const VfConvShape& s, bool full, float beta, const void* Up,
-                 const void* Vp) {
-  const int B = s.B, stride = s.stride, pad = s.pad, ntaps = 16;
-  const int Hl = full ? s.H : s.out_h(), Wl = full ? s.W : s.out_w(), Nu = full ? s.Cin : s.Cout;
-  const int Hv = full ? s.full_out_h() : s.H, Wv = full ? s.full_out_w() : s.W, Cv = full ? s.Cout : s.Cin;
-  // the bottleneck pair (1x1 map on one side, 4x4 on the other): dW = U^T V with K = batch — write-bound, its own kernel
-  if (Hl == 1 && Wl == 1 && Hv == 4 && Wv == 4 && stride == 1 && pad == 0 && ntaps == 16) {
-    const int rc = vf_internal_wgrad_smallk(ctx, U, V, dW, B, Nu, 16 * Cv, beta);
-    if (rc >= 0) return rc;
-  }
-  WGrad g;
-  memset(&g, 0, sizeof(g));
-  g.U = U; g.V = V; g.dW = dW;
-  g.P = B * Hl * Wl;
-  g.lgMh = vf_ilog2(Hl); g.lgMw = vf_ilog2(Wl);
-  g.Nu = Nu; g.Cv = Cv; g.Hv = Hv; g.Wv = Wv;
-  g.stride = stride; g.pad = pad;
-  g.ntaps = ntaps;
-  g.nk = (int)vf_cdiv(g.P, ctx->mfma_bf16 ? 32 : 16);      // K steps of the kernel's BK
-  VF_REQUIRE((int64_t)g.P * Nu < ((int64_t)1 << 29) && (int64_t)B * Hv * Wv * Cv < ((int64_t)1 << 29),
-             "operand exceeds the 2 GiB buffer-descriptor range");
-  g.u_bytes = (unsigned)((int64_t)g.P * Nu * 4);
-  g.v_bytes = (unsigned)((int64_t)B * Hv * Wv * Cv * 4);
-  const bool vecU = (Nu % 4 == 0) && vf_aligned16(U);
-  const bool vecV = (Cv % 4 == 0) && vf_aligned16(V);
-  g.beta = beta;
-  const int BM = Nu > 64 ? 128 : 64;
-  const int gy = (int)vf_cdiv(Nu, BM), gx = (int)vf_cdiv(ntaps * (int64_t)Cv, 128);
-  const int64_t blocks = (int64_t)gx * gy;
-  const int64_t total = (int64_t)Nu * ntaps * Cv;
-  int ksplit = 1;
+static WgPlan wg_plan(vf_ctx* ctx, const VfConvShape& s, bool full, const float* U, const float* V, const void* Up, const void* Vp) {
+  const int mode = ctx->mfma_bf16;
+  WgPlan p;
+  p.B = s.B; p.stride = s.stride; p.pad = s.pad;
+  p.Hl = full ? s.H : s.out_h(); p.Wl = full ? s.W : s.out_w(); p.Nu = full ? s.Cin : s.Cout;
+  p.Hv = full ? s.full_out_h() : s.H; p.Wv = full ? s.full_out_w() : s.W; p.Cv = full ? s.Cout : s.Cin;
+  p.P = s.B * p.Hl * p.Wl;
+  p.vecU = (p.Nu % 4 == 0) && vf_aligned16(U);
+  p.vecV = (p.Cv % 4 == 0) && vf_aligned16(V);
+  p.nk = (int)vf_cdiv(p.P, mode ? 32 : 16);
+  p.bm = p.Nu > 64 ? 128 : 64;
+  p.gy = (int)vf_cdiv(p.Nu, p.bm);
+  p.gx = (int)vf_cdiv(16 * (int64_t)p.Cv, 128);
+  p.total = (int64_t)p.Nu * 16 * p.Cv;
   // operands that arrive as planes (vf_*_bwd_weight_planes): the LDS-DMA kernel of vf_pgemm.hip, whole 128 x 128 x 32 tiles only —
   // or, in the three-plane mode, ONE row tile of 64 (Nu == 64: its 64 x 128 x 32 tile form; the one-plane mode and every other
   // Nu % 128 == 64 stay on the fp32-fed kernels)
-  const bool pw64 = Nu == 64 && ctx->mfma_bf16 == 3;
-  const bool use_pw = Up && Vp && (ctx->mfma_bf16 == 3 || ctx->mfma_bf16 == 1) && ntaps == 16 && stride == 2 && pad == 1 && (Nu % 128 == 0 || pw64) &&
-                      Cv % 64 == 0 && g.P % 32 == 0 && (int64_t)g.P * Nu * 6 < ((int64_t)1 << 31) &&
-                      (int64_t)B * Hv * Wv * Cv * 6 < ((int64_t)1 << 31) && total % 4 == 0;
+  const bool pw64 = p.Nu == 64 && mode == 3;
+  const bool use_pw = Up && Vp && (mode == 3 || mode == 1) && s.stride == 2 && s.pad == 1 && (p.Nu % 128 == 0 || pw64) && p.Cv % 64 == 0 &&
+                      p.P % 32 == 0 && p.in_range(6) && p.total % 4 == 0;
   // split-K target, blocks per layer.  The planes layers ride in ONE group launch of seven or more layers, which fills the chip as
   // a whole: half the splits per layer leave k_pwgrad_group's time where it was and halve the slabs it writes and the combine
   // reads (same-box: combine 2 x 37.4 -> 2 x 21.8 us); the fp32-fed thin layers' kernel wants the full 512 (62 -> 86 us at 256)
   // A 64-row tile is half a 128-row tile's work per K step: 512 of them per layer keep its blocks as long as the launch's others
   // (at 256, E2's blocks run 64 half steps against the 8 - 16 whole ones of its neighbours and end the launch alone: same-box, the
   // iteration 2.851 ms at 256, 2.813 at 512, 2.842 before the form existed) — and the split is then the fp32-fed kernel's own: same bits
-  const int wg_blocks = use_pw && !pw64 ? 256 : 512;
-  if (blocks < wg_blocks * 3 / 4 && g.nk >= 16) {
-    ksplit = (int)std::min<int64_t>(g.nk / 8, vf_cdiv(wg_blocks, blocks));
-    while (ksplit > 1 && (size_t)ksplit * total * sizeof(float) > vf_ws_avail(ctx)) --ksplit;
-    if (ksplit < 1) ksplit = 1;
-    const int steps = (int)vf_cdiv(g.nk, ksplit);
-    ksplit = (int)vf_cdiv(g.nk, steps);
+  p.target = use_pw && !pw64 ? 256 : 512;
+  const int64_t tiles = (int64_t)p.gx * p.gy;
+  p.ksplit = 1;
+  if (tiles < p.target * 3 / 4 && p.nk >= 16) {
+    p.ksplit = (int)std::min<int64_t>(p.nk / 8, vf_cdiv(p.target, tiles));
+    while (p.ksplit > 1 && (size_t)p.ksplit * p.total * sizeof(float) > vf_ws_avail(ctx)) --p.ksplit;
+    if (p.ksplit < 1) p.ksplit = 1;
+    const int steps = (int)vf_cdiv(p.nk, p.ksplit);
+    p.ksplit = (int)vf_cdiv(p.nk, steps);
   }
-  g.ksplit = ksplit;
-  g.slab = ksplit > 1 ? (float*)vf_ws_ptr(ctx) : nullptr;
-  g.gx = gx; g.gy = gy; g.gz = ksplit;
-  dim3 grid((unsigned)gx * gy * ksplit), block(256);
-  const bool own_group = use_pw && !ctx->wg_active;      // a planes layer outside a group: a group of one, launched at once
-  if (own_group) {
-    if (!ctx->wg_rec) ctx->wg_rec = new WgRecorder();
-    ctx->wg_active = 1;
+  p.route = p.is_bottleneck() ? WG_SMALLK : use_pw ? (pw64 ? WG_PLANES_64 : WG_PLANES_128) : p.fp32_route();
+  p.rider = p.is_bottleneck() && (mode == 3 || mode == 1) && p.bm == 128 && p.ksplit == 1 && (16 * p.Cv) % 128 == 0 && p.vecU && p.vecV;
+  return p;
+}
+// ---- the three descriptor forms of a planned layer.  WGrad and VfPWGrad name what they share alike: wg_desc_base fills that
+template <class D>
+static D wg_desc_base(const WgPlan& p, float beta) {
+  D d;
+  memset(&d, 0, sizeof(d));
+  d.P = p.P; d.lgMh = vf_ilog2(p.Hl); d.lgMw = vf_ilog2(p.Wl);
+  d.Nu = p.Nu; d.Cv = p.Cv; d.Hv = p.Hv; d.Wv = p.Wv;
+  d.gx = p.gx; d.gy = p.gy; d.gz = p.ksplit;
+  d.ksplit = p.ksplit; d.nk = p.nk;
+  d.beta = beta;
+  return d;
+}
+// slab: the layer's split-K slabs (ksplit > 1) or NULL
+static WGrad wg_desc(const WgPlan& p, const float* U, const float* V, float* dW, float* slab, float beta) {
+  WGrad g = wg_desc_base<WGrad>(p, beta);
+  g.U = U; g.V = V; g.dW = dW; g.slab = slab;
+  g.u_bytes = (unsigned)(p.u_elems() * 4);
+  g.v_bytes = (unsigned)(p.v_elems() * 4);
+  g.stride = p.stride; g.pad = p.pad;
+  g.ntaps = 16;
+  return g;
+}
+static VfPWGrad wg_desc_planes(const WgPlan& p, const void* Up, const void* Vp, float* dW, float* slab, float beta) {
+  VfPWGrad w = wg_desc_base<VfPWGrad>(p, beta);
+  w.Up = Up; w.Vp = Vp;
+  w.out = p.ksplit > 1 ? slab : dW;
+  w.u_ps = (unsigned)(p.u_elems() * 2);
+  w.v_ps = (unsigned)(p.v_elems() * 2);
+  return w;
+}
+// the fp32-fed form a bottleneck layer (WgPlan::rider) carries: U [B][Nu], V [B][4][4][Cv] = [B][16 * Cv].  A rider is whole
+// 128 x 128 tiles over one K range of 32-deep steps: the plan's grid is the planes kernel's
+static VfPWGrad wg_desc_rider(const WgPlan& p, const float* U, const float* V, float* dW, float beta) {
+  VfPWGrad w = wg_desc_base<VfPWGrad>(p, beta);
+  w.Uf = U; w.Vf = V;
+  w.out = dW;
+  return w;
+}
+
+// ---- recorder of a weight-gradient group (see k_wgrad_group)
+struct WgRec {
+  WgPlan p;
+  WGrad g;
+  VfPWGrad pw;      // a planes layer's descriptor; p.rider: its fp32-fed form, used when the group has planes layers (else the layer
+                    // stays with k_wgrad_group)
+  int bf;           // the family it launches with: the matrix-core mode, or 4: k_pwgrad_group
+};
+struct WgRecorder {
+  std::vector<WgRec> recs;
+  size_t ws_used = 0;      // slab bytes of the workspace that are spoken for
+  bool open = false;       // between vf_wgrad_group_begin and _end: weight gradients are recorded, not launched
+  void clear() {
+    recs.clear();
+    ws_used = 0;
   }
-  if (ctx->wg_active && (use_pw || (vecU && vecV && (ksplit == 1 || total % 4 == 0)))) {
+  // `bytes` of slabs behind everything spoken for, in a workspace of `avail` bytes: their offset, or false — launch what is
+  // recorded (wg_flush) first.  ws_used may exceed what the records hold: a partial end keeps it over an empty record list,
+  // because later slabs must not land in regions that a launch in flight still reads.
+  bool reserve(size_t bytes, size_t avail, size_t* off) {
+    if (ws_used + bytes > avail) return false;
+    *off = ws_used;
+    ws_used += bytes;
+    return true;
+  }
+};
+static WgRecorder& wg_recorder(vf_ctx* ctx) {
+  if (!ctx->wg) ctx->wg = new WgRecorder();
+  return *ctx->wg;
+}
+void vf_internal_wg_free(vf_ctx* ctx) {
+  delete ctx->wg;
+  ctx->wg = nullptr;
+}
+// the run-time (tile rows, matrix-core mode) of a weight-gradient launch as constants: f(VfIntC<BM>{}, VfIntC<BF>{})
+template <class F>
+static void wg_dispatch(int bm, int bf, F&& f) {
+  auto with_mode = [&](auto BM) {
+    if (bf == 3) f(BM, VfIntC<3>{});
+    else if (bf) f(BM, VfIntC<1>{});
+    else f(BM, VfIntC<0>{});
+  };
+  if (bm == 128) with_mode(VfIntC<128>{});
+  else with_mode(VfIntC<64>{});
+}
+// One family of a flush: the records `pick` accepts go into descriptor tables of CAP layers (by value in the kernel arguments),
+// a launch per full table and one for the rest.  put(slot, record, work) fills a slot, adds the layer's flops or bytes to `work`
+// and returns its blocks; every layer starts at a multiple of `align` blocks.  launch(table, blocks, work) -> error code.
+template <class Table, int CAP, class Pick, class Put, class Launch>
+static int wg_pack(const std::vector<WgRec>& recs, int align, Pick&& pick, Put&& put, Launch&& launch) {
+  Table G;
+  int blocks = 0;
+  double work = 0;
+  G.n = 0;
+  auto fire = [&]() -> int {
+    if (G.n == 0) return 0;
+    G.blk_off[G.n] = blocks;
+    const int rc = launch(G, blocks, work);
+    G.n = 0;
+    blocks = 0;
+    work = 0;
+    return rc;
+  };
+  for (const WgRec& r : recs) {
+    if (!pick(r)) continue;
+    G.blk_off[G.n] = blocks;
+    blocks += (put(G.d[G.n], r, work) + align - 1) / align * align;
+    if (++G.n == CAP)
+      if (int rc = fire()) return rc;
+  }
+  return fire();
+}
+static int wg_flush(vf_ctx* ctx) {
+  WgRecorder& R = wg_recorder(ctx);
+  if (R.recs.empty()) return 0;
+  // the layers whose operands came as planes: one k_pwgrad_group launch (vf_pgemm.hip).  The bottleneck layers of the same
+  // walk go with them in their fp32-fed form: write-bound tiles (131 MB of dW from K = batch) that hide under the MFMA-bound
+  // ones of the same launch, as they did in k_wgrad_group
+  bool any_planes = false;
+  for (const WgRec& r : R.recs) any_planes |= (r.bf == 4);
+  if (any_planes)
+    for (WgRec& r : R.recs)
+      if (r.p.rider) r.bf = 4;
+  // (blocks in multiples of 8: the XCD-aware tile order of a layer assumes blockIdx % 8 == local id % 8)
+  const int rc = wg_pack<VfPWGradGroup, VF_PWG_MAX>(
+      R.recs, 8, [](const WgRec& r) { return r.bf == 4; },
+      [](VfPWGrad& d, const WgRec& r, double& fl) {
+        d = r.pw;
+        fl += r.p.flops();
+        return d.gx * d.gy * d.gz;
+      },
+      [&](const VfPWGradGroup& G, int blocks, double fl) {
+        // the label says which tile forms the launch holds (a planes layer with Nu == 64 runs the 64-row form)
+        int n64 = 0;
+        for (int i = 0; i < G.n; ++i) n64 += G.d[i].Up != nullptr && G.d[i].Nu == 64;
+        const char* name = n64 == 0 ? "pwgrad_group_128x128x32" : (n64 == G.n ? "pwgrad_group_64x128x32" : "pwgrad_group_64+128x128x32");
+        return vf_internal_pwgrad_group(ctx, G, blocks, name, fl);
+      });
+  if (rc) return rc;
+  // one launch per (tile rows, mode) family, VF_WG_GROUP_MAX layers at a time
+  for (int bm : {128, 64})
+    for (int bf : {3, 1, 0})
+      wg_pack<WGradGroup, VF_WG_GROUP_MAX>(
+          R.recs, 8, [&](const WgRec& r) { return r.p.bm == bm && r.bf == bf; },
+          [](WGrad& d, const WgRec& r, double& fl) {
+            d = r.g;
+            fl += r.p.flops();
+            return r.p.blocks();
+          },
+          [&](const WGradGroup& G, int blocks, double fl) {
+            char name[64];
+            snprintf(name, sizeof(name), "wgrad_group_%dx128%s", bm, bf == 3 ? "_bf16x3" : (bf ? "_bf16" : ""));
+            wg_dispatch(bm, bf, [&](auto BM, auto BF) {
+              VF_LAUNCH_TIMED(ctx, name, fl, 0.0, (k_wgrad_group<decltype(BM)::value, true, true, decltype(BF)::value>), dim3(blocks),
+                              dim3(256), G);
+            });
+            return 0;
+          });
+  VF_LAUNCH_CHECK();
+  // the split-K slabs of all layers: one launch per VF_WG_GROUP_MAX layers (64 float4 per block, no alignment between layers)
+  wg_pack<SlabGroup, VF_WG_GROUP_MAX>(
+      R.recs, 1, [](const WgRec& r) { return r.g.ksplit > 1; },
+      [](auto& d, const WgRec& r, double& bytes) {
+        d.slab = r.g.slab;
+        d.dst = r.g.dW;
+        d.total4 = r.p.total / 4;
+        d.ksplit = r.g.ksplit;
+        d.beta = r.g.beta;
+        bytes += 4.0 * (double)r.p.total * (r.g.ksplit + 1);
+        return (int)vf_cdiv(r.p.total / 4, 64);
+      },
+      [&](const SlabGroup& S, int blocks, double bytes) {
+        VfProf prof(ctx, "slab_reduce_wgrad_group", 0.0, bytes);
+        hipLaunchKernelGGL(k_slab_reduce4_group, dim3(blocks), dim3(256), 0, ctx->stream, S);
+        return 0;
+      });
+  VF_LAUNCH_CHECK();
+  R.clear();
+  return 0;
+}
+VF_API int vf_wgrad_group_begin(vf_ctx* ctx) {
+  WgRecorder& R = wg_recorder(ctx);
+  if (R.open) R.clear();      // the previous walk was abandoned before its _end (a host-side error): drop what it recorded
+  R.open = true;
+  return 0;
+}
+VF_API int vf_wgrad_group_abort(vf_ctx* ctx) {
+  WgRecorder& R = wg_recorder(ctx);
+  R.clear();
+  R.open = false;
+  return 0;
+}
+VF_API int vf_wgrad_group_end(vf_ctx* ctx) {
+  WgRecorder& R = wg_recorder(ctx);
+  VF_REQUIRE(R.open, "vf_wgrad_group_end: no group is open");
+  R.open = false;
+  return wg_flush(ctx);
+}
+
+// weight gradients recorded so far in the open group (not yet launched)
+VF_API int vf_wgrad_group_count(vf_ctx* ctx, int* count) {
+  VF_REQUIRE(count != nullptr, "vf_wgrad_group_count: NULL");
+  WgRecorder& R = wg_recorder(ctx);
+  *count = R.open ? (int)R.recs.size() : 0;
+  return 0;
+}
+// launch the FIRST `count` recorded weight gradients (record order = walk order: the layers nearest the net's output) as one
+// group and keep the group open with the rest still recorded: a data-parallel host starts the exchange of the finished bucket
+// and then ends the group — both launches sit at the END of the backward walk, none in the middle of its data-gradient chain
+VF_API int vf_wgrad_group_end_partial(vf_ctx* ctx, int count) {
+  WgRecorder& R = wg_recorder(ctx);
+  VF_REQUIRE(R.open, "vf_wgrad_group_end_partial: no group is open");
+  if (R.recs.empty() || count <= 0) return 0;
+  std::vector<WgRec> rest;
+  if (count < (int)R.recs.size()) {
+    rest.assign(R.recs.begin() + count, R.recs.end());
+    R.recs.resize((size_t)count);
+  }
+  const size_t used = R.ws_used;
+  const int rc = wg_flush(ctx);
+  R.recs = rest;
+  R.ws_used = used;      // (see WgRecorder::reserve)
+  return rc;
+}
+
+static int wgrad(vf_ctx* ctx, const float* U, const float* V, float* dW, const VfConvShape& s, bool full, float beta, const void* Up,
+                 const void* Vp) {
+  WgPlan p = wg_plan(ctx, s, full, U, V, Up, Vp);
+  if (p.route == WG_SMALLK) {
+    const int rc = vf_internal_wgrad_smallk(ctx, U, V, dW, p.B, p.Nu, 16 * p.Cv, beta);
+    if (rc >= 0) return rc;
+    p.route = p.fp32_route();
+  }
+  VF_REQUIRE(p.in_range(4), "operand exceeds the 2 GiB buffer-descriptor range");
+  WgRecorder& R = wg_recorder(ctx);
+  auto slab_at = [&](size_t off) { return p.ksplit > 1 ? (float*)(vf_ws_ptr(ctx) + off) : nullptr; };
+  size_t off = 0;
+  if (p.planes() || (R.open && p.route == WG_FP32_GROUP)) {
     // recorded, not launched: the group runs at vf_wgrad_group_end.  Every recorded layer keeps its own slab region.
-    WgRecorder* R = (WgRecorder*)ctx->wg_rec;
-    const size_t need = ksplit > 1 ? (((size_t)ksplit * total * sizeof(float) + 255) & ~(size_t)255) : 0;
-    if (R->ws_used + need > vf_ws_avail(ctx)) {
+    // A planes layer outside a group is a group of one, launched at once.
+    if (!R.reserve(p.slab_bytes(), vf_ws_avail(ctx), &off)) {
       if (int rc = wg_flush(ctx)) return rc;
-      R->ws_used = 0;      // nothing is recorded any more (a partial end keeps ws_used with an empty record list)
+      R.clear();
+      VF_REQUIRE(R.reserve(p.slab_bytes(), vf_ws_avail(ctx), &off), "workspace too small for this layer's split-K slabs");
     }
-    VF_REQUIRE(need <= vf_ws_avail(ctx), "workspace too small for this layer's split-K slabs");
-    if (ksplit > 1) g.slab = (float*)(vf_ws_ptr(ctx) + R->ws_used);
-    R->ws_used += need;
     WgRec r;
-    r.g = g;
-    r.bm = BM;
-    r.bf = ctx->mfma_bf16;
-    r.blocks = gx * gy * ksplit;
-    r.total = total;
-    r.flops = 2.0 * (double)g.P * Nu * (double)ntaps * Cv;
-    r.plain_ok = false;
-    if (!use_pw && (ctx->mfma_bf16 == 3 || ctx->mfma_bf16 == 1) && BM == 128 && ksplit == 1 && Hl == 1 && Wl == 1 && Hv == 4 && Wv == 4 && stride == 1 &&
-        pad == 0 && ntaps == 16 && Nu % 4 == 0 && (16 * Cv) % 128 == 0 && vecU && vecV) {
-      r.plain_ok = true;
-      VfPWGrad& w = r.pw;
-      memset(&w, 0, sizeof(w));
-      w.Uf = U; w.Vf = V;                  // U [B][Nu], V [B][4][4][Cv] = [B][16 * Cv]
-      w.out = dW;
-      w.P = g.P; w.Nu = Nu; w.Cv = Cv; w.Hv = Hv; w.Wv = Wv;
-      w.gx = (16 * Cv) / 128; w.gy = (int)vf_cdiv(Nu, 128); w.gz = 1;
-      w.ksplit = 1; w.nk = (int)vf_cdiv(g.P, 32);
-      w.beta = beta;
-    }
-    if (use_pw) {
-      r.bf = 4;
-      VfPWGrad& w = r.pw;
-      memset(&w, 0, sizeof(w));
-      w.Up = Up; w.Vp = Vp;
-      w.out = ksplit > 1 ? g.slab : dW;
-      w.u_ps = (unsigned)((int64_t)g.P * Nu * 2);
-      w.v_ps = (unsigned)((int64_t)B * Hv * Wv * Cv * 2);
-      w.P = g.P; w.lgMh = g.lgMh; w.lgMw = g.lgMw;
-      w.Nu = Nu; w.Cv = Cv; w.Hv = Hv; w.Wv = Wv;
-      w.gx = gx; w.gy = gy; w.gz = ksplit;
-      w.ksplit = ksplit; w.nk = g.nk;
-      w.beta = beta;
-    }
-    R->recs.push_back(r);
-    if (own_group) {
-      ctx->wg_active = 0;
-      return wg_flush(ctx);
-    }
-    return 0;
+    r.p = p;
+    r.g = wg_desc(p, U, V, dW, slab_at(off), beta);
+    r.bf = p.planes() ? 4 : ctx->mfma_bf16;
+    if (p.planes()) r.pw = wg_desc_planes(p, Up, Vp, dW, r.g.slab, beta);
+    else if (p.rider) r.pw = wg_desc_rider(p, U, V, dW, beta);
+    R.recs.push_back(r);
+    return R.open ? 0 : wg_flush(ctx);
   }
-  if (ctx->wg_active) {
+  float* slab = slab_at(0);
+  if (R.open) {
     // a launch outside the group must not overwrite recorded slabs: its own slabs go BEHIND them (the group stays recorded: a
     // thin-channel layer at the end of a walk no longer launches the group ahead of vf_wgrad_group_end / _end_partial); only if
     // the workspace cannot hold both is the group finished first
-    WgRecorder* R = (WgRecorder*)ctx->wg_rec;
-    const size_t need = ksplit > 1 ? (((size_t)ksplit * total * sizeof(float) + 255) & ~(size_t)255) : 0;
-    if (R && R->ws_used + need <= vf_ws_avail(ctx)) {
-      if (ksplit > 1) g.slab = (float*)(vf_ws_ptr(ctx) + R->ws_used);
-      R->ws_used += need;
-    } else if (int rc = wg_flush(ctx)) {
-      return rc;
-    }
+    if (R.reserve(p.slab_bytes(), vf_ws_avail(ctx), &off)) slab = slab_at(off);
+    else if (int rc = wg_flush(ctx)) return rc;
   }
-  {
-    const int bf = ctx->mfma_bf16;
-    const char* wname = BM == 128 ? (bf == 3 ? "wgrad_128x128_bf16x3" : bf ? "wgrad_128x128_bf16" : "wgrad_128x128")
+  const WGrad g = wg_desc(p, U, V, dW, slab, beta);
+  const int bf = ctx->mfma_bf16;
+  const char* wname = p.bm == 128 ? (bf == 3 ? "wgrad_128x128_bf16x3" : bf ? "wgrad_128x128_bf16" : "wgrad_128x128")
                                   : (bf == 3 ? "wgrad_64x128_bf16x3" : bf ? "wgrad_64x128_bf16" : "wgrad_64x128");
-    const double wfl = 2.0 * (double)g.P * Nu * (double)ntaps * Cv;
-#define VF_WG(BM_, BF_)                                                                              \
-  do {                                                                                              \
-    if (vecU && vecV)                                                                               \
-      VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<BM_, true, true, BF_>), grid, block, g);       \
-    else if (vecU)                                                                                  \
-      VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<BM_, true, false, BF_>), grid, block, g);      \
-    else if (vecV)                                                                                  \
-      VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<BM_, false, true, BF_>), grid, block, g);      \
-    else                                                                                            \
-      VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<BM_, false, false, BF_>), grid, block, g);     \
-  } while (0)
-    if (BM == 128) {
-      if (bf == 3) VF_WG(128, 3); else if (bf) VF_WG(128, 1); else VF_WG(128, 0);
-    } else {
-      if (bf == 3) VF_WG(64, 3); else if (bf) VF_WG(64, 1); else VF_WG(64, 0);
-    }
-#undef VF_WG
-  }
+  const double wfl = p.flops();
+  const dim3 grid((unsigned)p.blocks()), block(256);
+  wg_dispatch(p.bm, bf, [&](auto BM, auto BF) {
+    constexpr int bm_ = decltype(BM)::value, bf_ = decltype(BF)::value;
+    if (p.vecU && p.vecV) VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, true, true, bf_>), grid, block, g);
+    else if (p.vecU) VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, true, false, bf_>), grid, block, g);
+    else if (p.vecV) VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, false, true, bf_>), grid, block, g);
+    else VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, false, false, bf_>), grid, block, g);
+  });
   VF_LAUNCH_CHECK();
-  if (ksplit > 1) {
-    VfProf prof(ctx, "slab_reduce_wgrad", 0.0, 4.0 * (double)total * (ksplit + 1));
-    return launch_slab_reduce(ctx, g.slab, dW, nullptr, total, 1, ksplit, VF_ACT_NONE, 0.f, beta);
+  if (p.ksplit > 1) {
+    VfProf prof(ctx, "slab_reduce_wgrad", 0.0, 4.0 * (double)p.total * (p.ksplit + 1));
+    return launch_slab_reduce(ctx, g.slab, dW, nullptr, p.total, 1, p.ksplit, VF_ACT_NONE, 0.f, beta);
   }
   return 0;
 }

@@ -31,8 +31,7 @@ VF_API int vf_ctx_create(vf_ctx** out, int device, void* stream) {
   c->ws = nullptr;
   c->ws_bytes = 0;
   c->ws_front = 0;
-  c->wg_active = 0;
-  c->wg_rec = nullptr;
+  c->wg = nullptr;
   c->mfma_bf16 = 3;      // fp32 operands as three exact bf16 planes (see vf_ctx_set_mfma_mode)
   *out = c;
   return 0;

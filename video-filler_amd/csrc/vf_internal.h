@@ -1,7 +1,7 @@
 // vf_internal.h — what the .hip files of the library share among themselves: the geometry of a conv pass, and the one declaration
 // of every function that one file defines and another calls (grouped by the defining file).  Included by vf_common.h.
 #pragma once
-struct vf_ctx; struct VfBnSt; struct VfBnRequest; struct VfConvExtras; struct VfPWGradGroup; struct VfFusedLayer;
+struct vf_ctx; struct VfBnSt; struct VfBnRequest; struct VfConvExtras; struct VfPWGradGroup; struct VfFusedLayer; struct WgRecorder;
 
 // One conv layer's geometry as the entry points of include/vf_hip.h take it: batch, the H x W map with Cin channels the layer
 // reads (a full-conv's low-resolution side), Cout channels out, kernel size, stride, padding.
