@@ -501,7 +501,7 @@ int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, i
  * image.save('x.jpg') / image.compressJPG, the JPEG folders the loaders read and the payload of the training scripts'
  * disp.image, on the device: a batch of n frames of one H x W x C in, n whole baseline JFIF files out, back to back,
  * byte for byte what libjpeg's default compression writes (jpeg_set_defaults, jpeg_set_quality(quality, TRUE), the fixed
- * Annex K Huffman tables, no restart intervals, the islow DCT; Pillow's save(format="JPEG", quality, subsampling) is the
+ * Annex K Huffman tables, no restart intervals (vf_jpeg_encode_opts has both options), the islow DCT; Pillow's save(format="JPEG", quality, subsampling) is the
  * same).  8-bit samples, C = 3 (RGB in, YCbCr coded) or 1 (grey), sides 1 to 16384, n 1 to 65535, quality 1 to 100;
  * subsampling 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 (luma 1x1, 2x1 or 2x2 against chroma 1x1; ignored for C = 1); anything else
  * is an error naming the argument, before anything is launched.  kind 0: float n x C x H x W, every value through
@@ -518,6 +518,27 @@ int vf_jpeg_encode_workspace_bytes(int n, int H, int W, int C, int subsampling, 
  * whatever n is; nothing is allocated and nothing synchronises. */
 int vf_jpeg_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling,
                    void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
+/* The same with libjpeg's two save() options, byte for byte what libjpeg writes with them (Pillow's restart_marker_rows,
+ * restart_marker_blocks and optimize; tests/jpeg_enc_opts_ref.py is the rule in numpy).
+ * Restart intervals: restart_rows > 0 asks for an interval of that many rows of MCUs, clamped to 65535 MCUs; otherwise
+ * restart_blocks is the interval in MCUs; 0 and 0: none.  A DRI segment stands between the last DHT and SOS; in front of
+ * every interval but the first the stream is padded to a byte with 1-bits, RST0..RST7 in turn follows, and the DC
+ * predictors start again at 0.  restart_rows and restart_blocks are 0 to 65535 each.
+ * optimize = 1: every file carries Huffman tables made from its own symbol counts (jpeg_gen_optimal_table: codes of at most
+ * 16 bits, no all-ones code), in the four DHT segments of the default file (two for grey), each 21 bytes + its symbols;
+ * a file's header is then its own and no longer than the default one.  optimize is 0 or 1.
+ * Anything else is an error naming the argument, before anything is launched.  With all three 0 the bounds and the files
+ * are those of vf_jpeg_encode.  The bound: an interval adds DRI's 6 bytes and, per segment, a pad byte, its stuffing byte
+ * and two marker bytes: out_bytes = n * (2 * 216 * blocks per frame + 626 [+ 4 * segments + 6]); optimised codes are at
+ * most 16 bits too.  The workspace grows by 16 bytes per segment, and with optimize by the counters, the code table and
+ * the DHT segments of every image. */
+int vf_jpeg_encode_opts_workspace_bytes(int n, int H, int W, int C, int subsampling, int restart_rows, int restart_blocks,
+                                        int optimize, size_t* ws_bytes, size_t* out_bytes);
+/* As vf_jpeg_encode: ten launches with an interval alone, twelve and one memset with optimize, whatever n is; the counts,
+ * the tables and the headers are made on the device; nothing is allocated and nothing synchronises. */
+int vf_jpeg_encode_opts(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling,
+                        int restart_rows, int restart_blocks, int optimize, void* ws, size_t ws_bytes, unsigned char* out,
+                        size_t out_cap, int64_t* offsets);
 
 /* ---- animated GIF encode (vf_gif.hip) ------------------------------------------------------------------
  * The `convert -delay D pred_1.png ... x_result.gif` that ends test_vid.lua:140-147, test_vid_wholeim.lua:244-257 and

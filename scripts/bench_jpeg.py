@@ -10,7 +10,12 @@ Reports, as one JSON document (stdout, and --out FILE), for each subsequence siz
     data, packing, enqueueing);
   * the synchronisation rounds;
 then the header-only inspection alone, and Pillow's decode of the same files on 1 and on `--threads` host threads.
-Not a gate; evidence only.  Usage: python scripts/bench_jpeg.py [--reps 20] [--subs 128,256,512,1024] [--out FILE]"""
+--restart-rows 0,1,2,4,8,16 measures something else and nothing of the above: the configs[1] batch written by the device
+encoder (data.encode_jpeg, q90 4:2:0) once per listed restart interval in rows of MCUs (0: none), and the decoder's time,
+rate, kernels and synchronisation rounds on each set of files at --subs' first size, over --rounds alternating rounds: does
+a workgroup per restart segment make the decoder faster?
+Not a gate; evidence only.  Usage: python scripts/bench_jpeg.py [--reps 20] [--subs 128,256,512,1024] [--out FILE]
+[--restart-rows 0,1,2,4,8,16 [--rounds 5]]"""
 import argparse
 import io
 import json
@@ -53,12 +58,53 @@ def pillow_ms(files, threads):
         return (time.perf_counter() - t0) * 1e3
 
 
+def restart_sweep(B, rows, sub, args):
+    """the decoder on the same frames written with each restart interval"""
+    import torch
+    from video_filler_amd.backend import jpeg_inspect
+    from video_filler_amd.data import encode_jpeg
+    rng = np.random.default_rng(0)
+    frames = np.stack([photo(537, 936, rng) for _ in range(16)])
+    sets, sync = {}, {}
+    for r in rows:
+        base = encode_jpeg(frames, 90, "420", restart_rows=r)
+        files = [base[i % 16] for i in range(64)]
+        infos = [jpeg_inspect(f, walk=False) for f in files]
+        B.jpeg_decode(files, 3, sub, infos)                # warm
+        sets[r] = (files, infos, [], [])
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(args.rounds):                           # alternating over the intervals
+        for r, (files, infos, ms, kern) in sets.items():
+            a.record()
+            for _ in range(args.reps):
+                _, _, status, rounds = B.jpeg_decode(files, 3, sub, infos)
+            b.record()
+            torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b) / args.reps)
+            B.prof_begin()
+            B.jpeg_decode(files, 3, sub, infos)
+            kern.append(sum(v["ms"] for v in B.prof_end().values()))
+            assert status.cpu().tolist() == [0] * 64
+            sync[r] = int(rounds.item())
+    out = []
+    for r, (files, infos, ms, kern) in sets.items():
+        med, rounds = float(np.median(ms)), sync[r]
+        out.append(dict(restart_rows=r, segments_per_file=jpeg_inspect(files[0])["segments"], mean_file_bytes=int(np.mean([len(f) for f in files])),
+                        device_ms_per_batch=dict(median=round(med, 3), min=round(min(ms), 3), max=round(max(ms), 3)),
+                        device_files_per_s=round(64 / med * 1e3), kernels_ms=round(float(np.median(kern)), 3), sync_rounds=rounds))
+    return dict(case="configs[1] loader: 64 x 537x936 q90 4:2:0, written by encode_jpeg", subseq_bytes=sub, rounds=args.rounds,
+                reps=args.reps, rows=out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--subs", default="128,256,512,1024")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--restart-rows", default=None)
+    ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
     import torch
     import video_filler_amd  # noqa: F401
@@ -70,6 +116,14 @@ def main():
     rng = np.random.default_rng(0)
     subs = [int(v) for v in args.subs.split(",")]
     res = {"device": torch.cuda.get_device_name(0), "rows": []}
+    if args.restart_rows is not None:
+        res = {"device": res["device"], "restart_sweep": restart_sweep(B, [int(v) for v in args.restart_rows.split(",")], subs[0], args)}
+        out = json.dumps(res, indent=1)
+        print(out)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(out + "\n")
+        return
     base = {}
     for H, W in ((537, 936), (360, 480)):
         base[(H, W)] = [encode(photo(H, W, rng)) for _ in range(16)]

@@ -96,6 +96,8 @@ SIGNATURES = {
     "vf_png_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_jpeg_encode_workspace_bytes": (i32, [i32, i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_jpeg_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
+    "vf_jpeg_encode_opts_workspace_bytes": (i32, [i32] * 8 + [C.POINTER(sz), C.POINTER(sz)]),
+    "vf_jpeg_encode_opts": (i32, [vp, vp] + [i32] * 10 + [vp, sz, vp, sz, vp]),
     "vf_gif_workspace_bytes": (i32, [i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_gif_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_display_workspace_bytes": (i32, [i32] * 9 + [C.POINTER(sz)]),

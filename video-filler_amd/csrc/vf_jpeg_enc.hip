@@ -12,6 +12,18 @@
 //                     their prefix and the file sizes, the files' places, then header, stream with a 0x00 behind every 0xFF,
 //                     1-padding, EOI.
 // Nine launches whatever the batch; a file's bytes depend on its own frame, the quality and the sampling only.
+//
+// The options (vf_jpeg_encode_opts: restart intervals, optimised Huffman tables) run the same kernels as their OPTS instances,
+// which leave the code above as it is when every option is off, and four kernels of their own:
+//   k_jenc_hist       with optimize: one thread per block, its symbols counted per image and table (LDS first, then global).
+//   k_jenc_table      with optimize: one workgroup per image and table: jpeg_gen_optimal_table (the two smallest counts by a
+//                     reduction, a merge as one step of all threads), the limiting to 16 bits, the canonical codes into the image's
+//                     LUT, the table's DHT segment.
+//   k_jenc_seg_scan   one workgroup per image: every restart segment's byte start (its bits rounded up to a byte, summed), and
+//                     what has to be added to the image-wide bit offset of its blocks.
+//   k_jenc_write<1>   also pads a segment's last byte with 1-bits; k_jenc_stuff<1> puts RSTn behind a segment's last byte and the
+//                     image's own header (prefix, its DHT segments, DRI, SOS) in front.
+// Twelve launches and one memset with optimize, ten without; nothing synchronises.
 #include "vf_block.h"
 #include "vf_common.h"
 
@@ -22,6 +34,8 @@ constexpr int JENC_TILE = 256;            // blocks per workgroup of k_jenc_size
 constexpr int JENC_CHUNK = 4096;          // stream bytes per workgroup of the stuffing kernels: 16 per thread
 constexpr int JENC_BLOCK_BITS = 64 * 27;  // the bound on a block's code (vf_hip.h has the derivation), a multiple of 32
 constexpr int JENC_HDR_CAP = 624;         // the colour header is 623 bytes, the grey one 333
+constexpr int JENC_HDR_BUF = 632;         // ... and DRI adds 6
+constexpr int JENC_DHT_STRIDE = 288;      // a DHT segment is at most 2 + 2 + 1 + 16 + 256 bytes
 
 // Annex K, read out of a file libjpeg wrote at quality 50 (there the scaled tables are the base tables).  Quantisation tables in
 // the file's zig-zag order; Huffman tables as their DHT segments carry them: BITS[16], then HUFFVAL.
@@ -78,8 +92,9 @@ constexpr JencLut jenc_make_lut() {
 __constant__ JencLut c_jenc_lut = jenc_make_lut();
 
 struct JencHdr {                 // everything in front of the entropy-coded data; the same for every file of a batch
-  unsigned w[JENC_HDR_CAP / 4];  // bytes in memory order
+  unsigned w[JENC_HDR_BUF / 4];  // bytes in memory order
   int len;
+  int split;                     // with optimize the image's own DHT segments stand in front of byte `split`; else it is len
 };
 
 struct JencArgs {
@@ -100,6 +115,14 @@ struct JencArgs {
   int wb, hb;                    // real luma blocks across and down
   int tiles, chunks;
   unsigned short quant[2][64];   // zig-zag order, times 8: the divisors of jcdctmgr.c
+  // the options (the OPTS instances of the kernels read these, the others never)
+  int spb, nseg, optimize;       // blocks per restart segment (nb without restarts), segments per image, tables per image or 0
+  unsigned long long* seg_start; // [n][nseg]: byte offset of the segment inside its image's (padded, unstuffed) stream
+  long long* seg_shift;          // [n][nseg]: 8 * seg_start - the image-wide bit offset of the segment's first block
+  unsigned* counts;              // [n][4][256]: symbol counts of table 2 * (luma 0 / chroma 1) + (DC 0 / AC 1)
+  JencLut* lut;                  // [n]
+  unsigned char* dht;            // [n][4][JENC_DHT_STRIDE]: the DHT segments
+  int* dht_len;                  // [n][4]
 };
 
 // where block g of an image's scan lies
@@ -220,8 +243,11 @@ __global__ __launch_bounds__(256) void k_jenc_dct(JencArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------- entropy coding
-__device__ __forceinline__ void jenc_load_lut(JencLut& s) {   // the code tables into LDS: lanes look up different symbols
+template <bool OPTS>
+__device__ __forceinline__ void jenc_load_lut(JencLut& s, const JencArgs& a, long long f) {   // the code tables into LDS: lanes look up different symbols
   const unsigned* src = (const unsigned*)&c_jenc_lut;
+  if constexpr (OPTS)
+    if (a.optimize) src = (const unsigned*)(a.lut + f);
   unsigned* dst = (unsigned*)&s;
   for (int i = threadIdx.x; i < (int)(sizeof(JencLut) / 4); i += 256) dst[i] = src[i];
   __syncthreads();
@@ -229,10 +255,13 @@ __device__ __forceinline__ void jenc_load_lut(JencLut& s) {   // the code tables
 
 // The DC value the difference of real block g is taken against: the DC of the previous real block of g's component in scan order,
 // 0 for the first.  A luma dummy keeps the predictor, so the walk steps over dummies (at most three) and over the chroma blocks.
+// OPTS: a restart resets the predictors, so the walk stops at the first block of g's segment.
+template <bool OPTS>
 __device__ __forceinline__ int jenc_pred(const JencArgs& a, const short* coef, int g, const JencPos& p) {
-  if (p.comp) return g >= a.bpm ? coef[(long long)(g - a.bpm) * 64] : 0;
+  const int g0 = OPTS ? g / a.spb * a.spb : 0;
+  if (p.comp) return g - a.bpm >= g0 ? coef[(long long)(g - a.bpm) * 64] : 0;
   const int luma = a.hs * a.vs;
-  for (int q = g - 1; q >= 0; --q) {
+  for (int q = g - 1; q >= g0; --q) {
     const int j = q % a.bpm;
     if (j >= luma) { q -= j - luma; continue; }   // on a chroma block: the loop's --q lands on the MCU's last luma block
     if (jenc_pos(a, q).real) return coef[(long long)q * 64];
@@ -240,14 +269,15 @@ __device__ __forceinline__ int jenc_pred(const JencArgs& a, const short* coef, i
   return 0;
 }
 
-// jchuff.c's encode_one_block of block g: put(bits, count) receives every code with its extra bits behind it, at most 26 bits
-template <class PUT>
-__device__ __forceinline__ void jenc_block_codes(const JencArgs& a, const JencLut& s, const short* coef, int g, PUT&& put) {
+// jchuff.c's encode_one_block of block g: sym(class 0 DC / 1 AC, table 0 luma / 1 chroma, symbol, extra bits, their count)
+// receives every symbol in the order of the stream
+template <bool OPTS, class SYM>
+__device__ __forceinline__ void jenc_block_syms(const JencArgs& a, const short* coef, int g, SYM&& sym) {
   const JencPos p = jenc_pos(a, g);
   const int t = p.comp ? 1 : 0;
   if (!p.real) {                                   // a dummy: DC difference 0, then EOB
-    put(s.dc[t][0] >> 8, s.dc[t][0] & 255);
-    put(s.ac[t][0] >> 8, s.ac[t][0] & 255);
+    sym(0, t, 0, 0u, 0);
+    sym(1, t, 0, 0u, 0);
     return;
   }
   const uint4* src = (const uint4*)(coef + (long long)g * 64);
@@ -258,33 +288,40 @@ __device__ __forceinline__ void jenc_block_codes(const JencArgs& a, const JencLu
     w[4 * i] = u.x; w[4 * i + 1] = u.y; w[4 * i + 2] = u.z; w[4 * i + 3] = u.w;
   }
   {
-    const int diff = (int)(short)(w[0] & 0xFFFFu) - jenc_pred(a, coef, g, p);
+    const int diff = (int)(short)(w[0] & 0xFFFFu) - jenc_pred<OPTS>(a, coef, g, p);
     const int n = 32 - __clz(abs(diff));
-    const unsigned e = s.dc[t][n], ext = (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << n) - 1u);
-    put((e >> 8) << n | ext, (int)(e & 255) + n);
+    sym(0, t, n, (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << n) - 1u), n);
   }
   int run = 0;
 #pragma unroll
   for (int k = 1; k < 64; ++k) {
     const int c = (int)(short)((k & 1) ? w[k >> 1] >> 16 : w[k >> 1] & 0xFFFFu);
     if (c == 0) { ++run; continue; }
-    for (; run > 15; run -= 16) put(s.ac[t][0xF0] >> 8, s.ac[t][0xF0] & 255);
+    for (; run > 15; run -= 16) sym(1, t, 0xF0, 0u, 0);
     const int n = 32 - __clz(abs(c));
-    const unsigned e = s.ac[t][run << 4 | n], ext = (unsigned)(c < 0 ? c - 1 : c) & ((1u << n) - 1u);
-    put((e >> 8) << n | ext, (int)(e & 255) + n);
+    sym(1, t, run << 4 | n, (unsigned)(c < 0 ? c - 1 : c) & ((1u << n) - 1u), n);
     run = 0;
   }
-  if (run) put(s.ac[t][0] >> 8, s.ac[t][0] & 255);
+  if (run) sym(1, t, 0, 0u, 0);
+}
+// ... as codes: put(bits, count) receives every code with its extra bits behind it, at most 26 bits
+template <bool OPTS, class PUT>
+__device__ __forceinline__ void jenc_block_codes(const JencArgs& a, const JencLut& s, const short* coef, int g, PUT&& put) {
+  jenc_block_syms<OPTS>(a, coef, g, [&](int cls, int t, int v, unsigned ext, int n) {
+    const unsigned e = cls ? s.ac[t][v] : s.dc[t][v];
+    put((e >> 8) << n | ext, (int)(e & 255) + n);
+  });
 }
 
+template <bool OPTS>
 __global__ __launch_bounds__(256) void k_jenc_size(JencArgs a) {
   __shared__ JencLut s;
   __shared__ unsigned s_w[4];
-  jenc_load_lut(s);
   const int g = blockIdx.x * JENC_TILE + threadIdx.x;
   const long long f = blockIdx.y;
+  jenc_load_lut<OPTS>(s, a, f);
   unsigned bits = 0;
-  if (g < a.nb) jenc_block_codes(a, s, a.coef + f * a.nb * 64, g, [&](unsigned, int count) { bits += (unsigned)count; });
+  if (g < a.nb) jenc_block_codes<OPTS>(a, s, a.coef + f * a.nb * 64, g, [&](unsigned, int count) { bits += (unsigned)count; });
   unsigned total;
   const unsigned at = vf_block_excl_scan<unsigned, 256>(bits, s_w, total);
   if (g < a.nb) a.blk_off[f * a.nb + g] = at;
@@ -314,19 +351,21 @@ __global__ __launch_bounds__(256) void k_jenc_clear(JencArgs a) {
   ((uint4*)(a.stream + f * a.cap_words + (long long)(begin >> 2)))[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
 }
 
+template <bool OPTS>
 __global__ __launch_bounds__(256) void k_jenc_write(JencArgs a) {
   __shared__ JencLut s;
-  jenc_load_lut(s);
   const int g = blockIdx.x * JENC_TILE + threadIdx.x;
   const long long f = blockIdx.y;
+  jenc_load_lut<OPTS>(s, a, f);
   if (g >= a.nb) return;
-  const unsigned long long at = a.tile_off[f * a.tiles + blockIdx.x] + a.blk_off[f * a.nb + g];
+  unsigned long long at = a.tile_off[f * a.tiles + blockIdx.x] + a.blk_off[f * a.nb + g];
+  if constexpr (OPTS) at = (unsigned long long)((long long)at + a.seg_shift[f * a.nseg + g / a.spb]);
   unsigned* dst = a.stream + f * a.cap_words + (long long)(at >> 5);
   // the bits in front of the block inside its first dword belong to earlier blocks: they enter as zeros, and that dword is OR-ed
   unsigned long long acc = 0;
   int cnt = (int)(at & 31);
   bool first = true;
-  jenc_block_codes(a, s, a.coef + f * a.nb * 64, g, [&](unsigned bits, int count) {
+  jenc_block_codes<OPTS>(a, s, a.coef + f * a.nb * 64, g, [&](unsigned bits, int count) {
     acc = acc << count | bits;
     cnt += count;
     if (cnt >= 32) {
@@ -339,7 +378,162 @@ __global__ __launch_bounds__(256) void k_jenc_write(JencArgs a) {
       acc &= (1ull << cnt) - 1ull;
     }
   });
+  if constexpr (OPTS)                              // a segment's last block fills its last byte with 1-bits (cnt stays <= 32)
+    if ((g + 1 == a.nb || (g + 1) % a.spb == 0) && (cnt & 7)) {
+      const int k = 8 - (cnt & 7);
+      acc = acc << k | ((1ull << k) - 1ull);
+      cnt += k;
+    }
   if (cnt) atomicOr(dst, (unsigned)(acc << (32 - cnt)));
+}
+
+// ------------------------------------------------------------------------------------------------------- the options' kernels
+// the symbols of every block of the stream that will be written (DC differences against the segment-aware predictor), counted
+__global__ __launch_bounds__(256) void k_jenc_hist(JencArgs a) {
+  __shared__ unsigned s_h[4 * 256];
+  for (int i = threadIdx.x; i < 4 * 256; i += 256) s_h[i] = 0;
+  __syncthreads();
+  const int g = blockIdx.x * JENC_TILE + threadIdx.x;
+  const long long f = blockIdx.y;
+  if (g < a.nb)
+    jenc_block_syms<true>(a, a.coef + f * a.nb * 64, g, [&](int cls, int t, int v, unsigned, int) { atomicAdd(&s_h[(2 * t + cls) * 256 + v], 1u); });
+  __syncthreads();
+  for (int i = threadIdx.x; i < 4 * 256; i += 256)
+    if (s_h[i]) atomicAdd(a.counts + f * (4 * 256) + i, s_h[i]);
+}
+
+// the two smallest of two ascending pairs of distinct keys
+__device__ __forceinline__ void jenc_min2(unsigned long long& lo, unsigned long long& hi, unsigned long long lo2, unsigned long long hi2) {
+  if (lo2 < lo) {
+    hi = min(lo, hi2);
+    lo = lo2;
+  } else {
+    hi = min(hi, lo2);
+  }
+}
+
+// jpeg_gen_optimal_table of table blockIdx.x of image blockIdx.y.  Thread i owns symbol i, thread 256 the reserved code point (no
+// real symbol gets the all-ones code).  libjpeg's `others` chain behind a tree's head is the set of that tree's leaves, so a merge
+// is one step of all threads: the leaves of both trees grow by one bit and take the head's name.  The two smallest counts come
+// from a reduction over keys count << 32 | 511 - symbol: the smallest count, and among equals the LARGEST symbol, as jchuff.c's
+// `<=` scan finds them.  A code longer than 32 bits, which libjpeg refuses (it takes more than nine million symbols in Fibonacci
+// proportions), is not told apart here; the counters of the lengths have room for any tree.
+constexpr int JENC_TABLE_THREADS = 320;
+__global__ __launch_bounds__(JENC_TABLE_THREADS) void k_jenc_table(JencArgs a) {
+  constexpr int WAVES = JENC_TABLE_THREADS / 64;
+  constexpr unsigned long long NONE = ~0ull;
+  __shared__ unsigned long long s_min[2][WAVES][2];
+  __shared__ int s_size[256], s_bits[264], s_first[17], s_start[18];
+  const int k = blockIdx.x, i = threadIdx.x, lane = i & 63, wave = i >> 6;
+  const long long f = blockIdx.y;
+  unsigned freq = i < 256 ? a.counts[(f * 4 + k) * 256 + i] : i == 256 ? 1u : 0u;
+  int head = i, size = 0;
+  for (int it = 0;; ++it) {
+    unsigned long long lo = freq ? (unsigned long long)freq << 32 | (unsigned)(511 - i) : NONE, hi = NONE;
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned long long lo2 = __shfl_xor(lo, o), hi2 = __shfl_xor(hi, o);
+      jenc_min2(lo, hi, lo2, hi2);
+    }
+    if (lane == 0) {
+      s_min[it & 1][wave][0] = lo;
+      s_min[it & 1][wave][1] = hi;
+    }
+    __syncthreads();                               // one barrier a round: the next round writes the other half of s_min
+    lo = hi = NONE;
+    for (int w = 0; w < WAVES; ++w) jenc_min2(lo, hi, s_min[it & 1][w][0], s_min[it & 1][w][1]);
+    if (hi == NONE) break;                         // one tree left (the same in every thread)
+    const int c1 = 511 - (int)(unsigned)lo, c2 = 511 - (int)(unsigned)hi;
+    if (i == c1) freq += (unsigned)(hi >> 32);
+    if (i == c2) freq = 0;
+    if (head == c1 || head == c2) {
+      ++size;
+      head = c1;
+    }
+  }
+  if (i < 256) s_size[i] = size;
+  if (i < 264) s_bits[i] = 0;
+  __syncthreads();
+  if (i <= 256 && size) atomicAdd(&s_bits[min(size, 263)], 1);
+  __syncthreads();
+  if (i == 0) {
+    for (int l = 32; l > 16; --l)                  // the limiting to 16 bits of Annex K.2
+      while (s_bits[l] > 0) {
+        int j = l - 2;
+        while (j > 0 && s_bits[j] == 0) --j;
+        s_bits[l] -= 2;
+        s_bits[l - 1] += 1;
+        s_bits[j + 1] += 2;
+        s_bits[j] -= 1;
+      }
+    int l = 16;
+    while (l > 0 && s_bits[l] == 0) --l;
+    s_bits[l] -= 1;                                // the reserved code point leaves
+    int code = 0, at = 0;
+    for (l = 1; l <= 16; ++l) {
+      s_first[l] = code;
+      s_start[l] = at;
+      code = (code + s_bits[l]) << 1;
+      at += s_bits[l];
+    }
+    s_start[17] = at;
+  }
+  __syncthreads();
+  // HUFFVAL: the symbols by their UNLIMITED length, then by value; the limited lengths are dealt out along that order
+  const int cls = k & 1, t = k >> 1, nsym = s_start[17];
+  unsigned char* d = a.dht + (f * 4 + k) * JENC_DHT_STRIDE;
+  unsigned entry = 0;
+  if (i < 256 && size) {
+    int pos = 0;
+    for (int j = 0; j < 256; ++j) {
+      const int sj = s_size[j];
+      pos += (sj && sj < size) || (sj == size && j < i);
+    }
+    int l = 1;
+    while (l < 16 && pos >= s_start[l + 1]) ++l;
+    entry = (unsigned)(s_first[l] + pos - s_start[l]) << 8 | (unsigned)l;
+    d[21 + pos] = (unsigned char)i;
+  }
+  if (cls) {
+    if (i < 256) a.lut[f].ac[t][i] = entry;
+  } else if (i < 12) {
+    a.lut[f].dc[t][i] = entry;                     // a DC category is at most 11
+  }
+  if (i < 16) d[5 + i] = (unsigned char)s_bits[i + 1];
+  if (i == 0) {
+    d[0] = 0xFF;
+    d[1] = 0xC4;
+    d[2] = (unsigned char)((19 + nsym) >> 8);
+    d[3] = (unsigned char)((19 + nsym) & 255);
+    d[4] = (unsigned char)(cls << 4 | t);
+    a.dht_len[f * 4 + k] = 21 + nsym;
+  }
+}
+
+// One workgroup per image.  The image-wide scan gave every block its bit offset as if there were no restarts; segment s is the
+// bits between its first block and the next segment's, rounded up to a byte, and its blocks move by seg_shift.  The image's bit
+// count becomes that of the padded stream, a whole number of bytes, for the kernels that follow.
+__global__ __launch_bounds__(256) void k_jenc_seg_scan(JencArgs a) {
+  __shared__ unsigned long long s_w[4];
+  const long long f = blockIdx.x;
+  const unsigned long long all = a.img_bits[f];    // read before the first barrier; thread 0 replaces it behind the last
+  auto at = [&](long long g) { return a.tile_off[f * a.tiles + g / JENC_TILE] + a.blk_off[f * a.nb + g]; };
+  unsigned long long run = 0;
+  for (int base = 0; base < a.nseg; base += 256) {
+    const int s = base + threadIdx.x;
+    unsigned long long p0 = 0, v = 0;
+    if (s < a.nseg) {
+      p0 = at((long long)s * a.spb);
+      v = ((s + 1 < a.nseg ? at((long long)(s + 1) * a.spb) : all) - p0 + 7) >> 3;
+    }
+    unsigned long long total;
+    const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(v, s_w, total);
+    if (s < a.nseg) {
+      a.seg_start[f * a.nseg + s] = run + e;
+      a.seg_shift[f * a.nseg + s] = (long long)(8 * (run + e)) - (long long)p0;
+    }
+    run += total;
+  }
+  if (threadIdx.x == 0) a.img_bits[f] = 8 * run;
 }
 
 // -------------------------------------------------------------------------------------------------------------- byte stuffing
@@ -377,9 +571,19 @@ __global__ __launch_bounds__(256) void k_jenc_ff_count(JencArgs a) {
 }
 
 // one workgroup per image: 0xFF bytes in front of every chunk, and the file's size at offsets[f + 1] (summed by k_vf_file_offsets)
+// OPTS: the header is the image's own (its DHT segments), and two marker bytes stand behind every segment but the last
+template <bool OPTS>
+__device__ __forceinline__ int jenc_dht_bytes(const JencArgs& a, long long f) {
+  int d = 0;
+  if constexpr (OPTS)
+    for (int k = 0; k < a.optimize; ++k) d += a.dht_len[f * 4 + k];
+  return d;
+}
+template <bool OPTS>
 __global__ __launch_bounds__(256) void k_jenc_ff_scan(JencArgs a, int hdr_len) {
   __shared__ unsigned long long s_w[4];
   const long long f = blockIdx.x;
+  if constexpr (OPTS) hdr_len += jenc_dht_bytes<true>(a, f) + 2 * (a.nseg - 1);
   const unsigned long long nbytes = (a.img_bits[f] + 7) >> 3;
   const long long used = (long long)((nbytes + JENC_CHUNK - 1) / JENC_CHUNK);
   unsigned long long run = 0;
@@ -394,6 +598,9 @@ __global__ __launch_bounds__(256) void k_jenc_ff_scan(JencArgs a, int hdr_len) {
   if (threadIdx.x == 0) a.offsets[f + 1] = (int64_t)(hdr_len + nbytes + run + 2);
 }
 
+// OPTS: RSTn (not stuffed) behind the last byte of every segment but the last, so a byte of segment s stands 2 * s further on; the
+// header is hdr's bytes with the image's DHT segments let in at hdr.split.
+template <bool OPTS>
 __global__ __launch_bounds__(256) void k_jenc_stuff(JencArgs a, JencHdr hdr) {
   __shared__ unsigned s_w[4];
   const long long f = blockIdx.y;
@@ -401,20 +608,59 @@ __global__ __launch_bounds__(256) void k_jenc_stuff(JencArgs a, JencHdr hdr) {
   if (begin >= nbytes) return;
   unsigned char* file = a.out + a.offsets[f];
   unsigned b[16];
-  const int have = jenc_bytes16(a, f, bits, begin + threadIdx.x * 16, b);
+  const unsigned long long pos = begin + threadIdx.x * 16;
+  const int have = jenc_bytes16(a, f, bits, pos, b);
   unsigned cnt = 0;
 #pragma unroll
   for (int i = 0; i < 16; ++i) cnt += i < have && b[i] == 255u;
   unsigned total;
   const unsigned before = vf_block_excl_scan<unsigned, 256>(cnt, s_w, total);
-  unsigned char* dst = file + hdr.len + begin + a.ff_pref[f * a.chunks + blockIdx.x] + threadIdx.x * 16 + before;
+  const int dht = jenc_dht_bytes<OPTS>(a, f);
+  unsigned char* dst = file + hdr.len + dht + begin + a.ff_pref[f * a.chunks + blockIdx.x] + threadIdx.x * 16 + before;
+  if constexpr (OPTS) {
+    const unsigned long long* start = a.seg_start + f * a.nseg;
+    int s = 0;                                     // the segment of the thread's first byte: the last that starts at or before it
+    if (have)
+      for (int hi = a.nseg - 1; s < hi;) {
+        const int mid = (s + hi + 1) >> 1;
+        if (start[mid] <= pos) s = mid;
+        else hi = mid - 1;
+      }
+    dst += 2 * (long long)s;
+    unsigned long long next = s + 1 < a.nseg ? start[s + 1] : ~0ull;
 #pragma unroll
-  for (int i = 0; i < 16; ++i)
-    if (i < have) {
-      *dst++ = (unsigned char)b[i];
-      if (b[i] == 255u) *dst++ = 0;
-    }
-  if (blockIdx.x == 0)
+    for (int i = 0; i < 16; ++i)
+      if (i < have) {
+        *dst++ = (unsigned char)b[i];
+        if (b[i] == 255u) *dst++ = 0;
+        if (pos + i + 1 == next) {
+          *dst++ = 0xFF;
+          *dst++ = (unsigned char)(0xD0 + (s & 7));
+          ++s;
+          next = s + 1 < a.nseg ? start[s + 1] : ~0ull;
+        }
+      }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (i < have) {
+        *dst++ = (unsigned char)b[i];
+        if (b[i] == 255u) *dst++ = 0;
+      }
+  }
+  if constexpr (OPTS) {
+    if (blockIdx.x == 0)
+      for (int i = threadIdx.x; i < hdr.len + dht; i += 256) {
+        if (i >= hdr.split && i < hdr.split + dht) {
+          int k = 0, j = i - hdr.split;
+          for (; j >= a.dht_len[f * 4 + k]; ++k) j -= a.dht_len[f * 4 + k];
+          file[i] = a.dht[(f * 4 + k) * JENC_DHT_STRIDE + j];
+        } else {
+          const int j = i < hdr.split ? i : i - dht;
+          file[i] = (unsigned char)(hdr.w[j >> 2] >> (8 * (j & 3)));
+        }
+      }
+  } else if (blockIdx.x == 0)
     for (int i = threadIdx.x; i < hdr.len; i += 256) file[i] = (unsigned char)(hdr.w[i >> 2] >> (8 * (i & 3)));
   if (begin + JENC_CHUNK >= nbytes && threadIdx.x == 0) {
     const int64_t size = a.offsets[f + 1] - a.offsets[f];
@@ -426,17 +672,25 @@ __global__ __launch_bounds__(256) void k_jenc_stuff(JencArgs a, JencHdr hdr) {
 // ----------------------------------------------------------------------------------------------------------------------- host
 struct JencPlan {
   int hs, vs, mcux, mcuy, bpm, nb, tiles, chunks;
+  int interval, nseg, spb, tables;   // the options: MCUs per restart interval (0: none), segments, blocks per segment, optimised tables
   long long cap_bytes;           // an image's unstuffed stream, a whole number of chunks
   size_t o_coef, o_blk, o_tsum, o_toff, o_bits, o_stream, o_ffc, o_ffp, ws_bytes, out_bytes;
+  size_t o_sstart, o_sshift, o_counts, o_lut, o_dht, o_dlen;
+  bool opts() const { return interval || tables; }
 };
 
-int jenc_plan(const char* who, int n, int H, int W, int C, int subsampling, JencPlan* p) {
+int jenc_plan(const char* who, int n, int H, int W, int C, int subsampling, int restart_rows, int restart_blocks, int optimize,
+              JencPlan* p) {
   VF_REQUIRE(C == 1 || C == 3, "%s: C = %d channels (a JPEG frame here is grey, 1 channel, or RGB, 3)", who, C);
   VF_REQUIRE(H >= 1 && H <= JENC_MAX_SIDE, "%s: H = %d (sides are 1 to %d)", who, H, JENC_MAX_SIDE);
   VF_REQUIRE(W >= 1 && W <= JENC_MAX_SIDE, "%s: W = %d (sides are 1 to %d)", who, W, JENC_MAX_SIDE);
   VF_REQUIRE(n >= 1 && n <= 65535, "%s: n = %d frames (1 to 65535)", who, n);
   VF_REQUIRE(C == 1 || (subsampling >= 0 && subsampling <= 2), "%s: subsampling = %d is not 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)", who,
              subsampling);
+  VF_REQUIRE(restart_rows >= 0 && restart_rows <= 65535, "%s: restart_rows = %d (0 to 65535 rows of MCUs)", who, restart_rows);
+  VF_REQUIRE(restart_blocks >= 0 && restart_blocks <= 65535, "%s: restart_blocks = %d (0 to 65535 MCUs, what DRI can say)", who,
+             restart_blocks);
+  VF_REQUIRE(optimize == 0 || optimize == 1, "%s: optimize = %d is not 0 or 1", who, optimize);
   p->hs = C == 3 && subsampling >= 1 ? 2 : 1;
   p->vs = C == 3 && subsampling == 2 ? 2 : 1;
   p->mcux = (int)vf_cdiv(W, 8 * p->hs);
@@ -444,7 +698,14 @@ int jenc_plan(const char* who, int n, int H, int W, int C, int subsampling, Jenc
   p->bpm = C == 3 ? p->hs * p->vs + 2 : 1;
   p->nb = p->mcux * p->mcuy * p->bpm;
   p->tiles = (int)vf_cdiv(p->nb, JENC_TILE);
-  p->cap_bytes = vf_cdiv((long long)p->nb * (JENC_BLOCK_BITS / 8), JENC_CHUNK) * JENC_CHUNK;
+  // jcmaster.c: rows of MCUs win over MCUs and are clamped to what DRI can say
+  const int mcus = p->mcux * p->mcuy;
+  p->interval = restart_rows > 0 ? (restart_rows * p->mcux < 65535 ? restart_rows * p->mcux : 65535) : restart_blocks;
+  p->nseg = p->interval ? (int)vf_cdiv(mcus, p->interval) : 1;
+  p->spb = p->interval && p->interval < mcus ? p->interval * p->bpm : p->nb;
+  p->tables = optimize ? (C == 3 ? 4 : 2) : 0;
+  // every segment but the last may end in a pad byte of its own
+  p->cap_bytes = vf_cdiv((long long)p->nb * (JENC_BLOCK_BITS / 8) + (p->interval ? p->nseg : 0), JENC_CHUNK) * JENC_CHUNK;
   p->chunks = (int)(p->cap_bytes / JENC_CHUNK);
   const size_t blocks = (size_t)n * p->nb;
   VfCarve ws;
@@ -456,21 +717,33 @@ int jenc_plan(const char* who, int n, int H, int W, int C, int subsampling, Jenc
   p->o_stream = ws.take((size_t)n * p->cap_bytes);
   p->o_ffc = ws.take((size_t)n * p->chunks * 4);
   p->o_ffp = ws.take((size_t)n * p->chunks * 8);
+  if (p->opts()) {
+    p->o_sstart = ws.take((size_t)n * p->nseg * 8);
+    p->o_sshift = ws.take((size_t)n * p->nseg * 8);
+  }
+  if (p->tables) {
+    p->o_counts = ws.take((size_t)n * 4 * 256 * 4);
+    p->o_lut = ws.take((size_t)n * sizeof(JencLut));
+    p->o_dht = ws.take((size_t)n * 4 * JENC_DHT_STRIDE);
+    p->o_dlen = ws.take((size_t)n * 4 * 4);
+  }
   p->ws_bytes = ws.at;
-  // every block at its bound, every stream byte stuffed; header and EOI
-  p->out_bytes = (size_t)n * ((size_t)p->nb * (JENC_BLOCK_BITS / 8) * 2 + JENC_HDR_CAP + 2);
+  // every block at its bound, every stream byte stuffed; header and EOI.  With an interval: DRI, and per segment a pad byte, its
+  // stuffing byte and two marker bytes.  An optimised code is at most 16 bits too, and its DHT segments are no longer than Annex K's.
+  p->out_bytes = (size_t)n * ((size_t)p->nb * (JENC_BLOCK_BITS / 8) * 2 + JENC_HDR_CAP + 2 + (p->interval ? 4 * (size_t)p->nseg + 6 : 0));
   return 0;
 }
 
 struct JencHdrW {
-  unsigned char b[JENC_HDR_CAP];
+  unsigned char b[JENC_HDR_BUF];
   int len = 0;
   void put(int v) { b[len++] = (unsigned char)v; }
   void put16(int v) { put(v >> 8); put(v & 255); }
 };
 
-// SOI, APP0 (JFIF 1.1, density 1:1), DQT per table, SOF0, DHT per table, SOS; -> the divisors too
-void jenc_header(int H, int W, int C, int quality, int hs, int vs, JencHdr* hdr, unsigned short quant[2][64]) {
+// SOI, APP0 (JFIF 1.1, density 1:1), DQT per table, SOF0, DHT per table (with optimize: left out, the images bring their own),
+// DRI for a non-zero interval, SOS; -> the divisors too
+void jenc_header(int H, int W, int C, int quality, int hs, int vs, int interval, bool optimize, JencHdr* hdr, unsigned short quant[2][64]) {
   const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
   unsigned char qt[2][64];
   for (int t = 0; t < 2; ++t)
@@ -490,7 +763,7 @@ void jenc_header(int H, int W, int C, int quality, int hs, int vs, JencHdr* hdr,
   }
   h.put(0xFF); h.put(0xC0); h.put16(8 + 3 * C); h.put(8); h.put16(H); h.put16(W); h.put(C);
   for (int c = 0; c < C; ++c) { h.put(c + 1); h.put(c == 0 ? hs << 4 | vs : 0x11); h.put(c == 0 ? 0 : 1); }
-  for (int t = 0; t < (C == 3 ? 2 : 1); ++t) {
+  for (int t = 0; t < (C == 3 ? 2 : 1) && !optimize; ++t) {
     h.put(0xFF); h.put(0xC4); h.put16(2 + 1 + 16 + 12); h.put(t);
     for (int i = 0; i < 16; ++i) h.put(K_DC_BITS[t][i]);
     for (int i = 0; i < 12; ++i) h.put(K_DC_VAL[i]);
@@ -498,6 +771,8 @@ void jenc_header(int H, int W, int C, int quality, int hs, int vs, JencHdr* hdr,
     for (int i = 0; i < 16; ++i) h.put(K_AC_BITS[t][i]);
     for (int i = 0; i < 162; ++i) h.put(K_AC_VAL[t][i]);
   }
+  hdr->split = h.len;
+  if (interval) { h.put(0xFF); h.put(0xDD); h.put16(4); h.put16(interval); }
   h.put(0xFF); h.put(0xDA); h.put16(6 + 2 * C); h.put(C);
   for (int c = 0; c < C; ++c) { h.put(c + 1); h.put(c == 0 ? 0x00 : 0x11); }
   h.put(0); h.put(63); h.put(0);
@@ -506,27 +781,72 @@ void jenc_header(int H, int W, int C, int quality, int hs, int vs, JencHdr* hdr,
   hdr->len = h.len;
 }
 
-}  // namespace
-
-VF_API int vf_jpeg_encode_workspace_bytes(int n, int H, int W, int C, int subsampling, size_t* ws_bytes, size_t* out_bytes) {
+int jenc_workspace_bytes(const char* who, int n, int H, int W, int C, int subsampling, int restart_rows, int restart_blocks,
+                         int optimize, size_t* ws_bytes, size_t* out_bytes) {
   JencPlan p;
-  if (int e = jenc_plan("vf_jpeg_encode_workspace_bytes", n, H, W, C, subsampling, &p)) return e;
+  if (int e = jenc_plan(who, n, H, W, C, subsampling, restart_rows, restart_blocks, optimize, &p)) return e;
   if (ws_bytes) *ws_bytes = p.ws_bytes;
   if (out_bytes) *out_bytes = p.out_bytes;
   return 0;
 }
 
-VF_API int vf_jpeg_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling, void* ws,
-                          size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
+// The launches of one call.  OPTS false is the default file's nine; OPTS true lets in the counts and the tables behind the DCT
+// (optimize) and the segments' places behind the tile scan.
+template <bool OPTS>
+int jenc_launch(vf_ctx* ctx, const JencPlan& p, const JencArgs& a, const JencHdr& hdr, int kind) {
+  const int n = a.n;
+  const double px = (double)n * a.H * a.W * a.C, coef = (double)n * p.nb * 128;
+  const dim3 per_tile((unsigned)p.tiles, n), per_chunk((unsigned)p.chunks, n);
+  if (kind == 0) VF_LAUNCH_TIMED(ctx, "jpeg_enc_dct", 0.0, 4.0 * px + coef, k_jenc_dct<0>, per_tile, dim3(256), a);
+  else VF_LAUNCH_TIMED(ctx, "jpeg_enc_dct", 0.0, px + coef, k_jenc_dct<1>, per_tile, dim3(256), a);
+  VF_LAUNCH_CHECK();
+  if constexpr (OPTS)
+    if (p.tables) {
+      VfProf prof(ctx, "jpeg_enc_tables", 0.0, coef);
+      VF_CHECK_HIP(hipMemsetAsync(a.counts, 0, (size_t)n * 4 * 256 * 4, ctx->stream));
+      hipLaunchKernelGGL(k_jenc_hist, per_tile, dim3(256), 0, ctx->stream, a);
+      VF_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_jenc_table, dim3(p.tables, n), dim3(JENC_TABLE_THREADS), 0, ctx->stream, a);
+      VF_LAUNCH_CHECK();
+    }
+  VF_LAUNCH_TIMED(ctx, "jpeg_enc_size", 0.0, coef, k_jenc_size<OPTS>, per_tile, dim3(256), a);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_enc_scan", 0.0, 12.0 * n * p.tiles, k_jenc_tile_scan, dim3(n), dim3(256), a);
+  VF_LAUNCH_CHECK();
+  if constexpr (OPTS) {
+    VF_LAUNCH_TIMED(ctx, "jpeg_enc_segments", 0.0, 28.0 * n * p.nseg, k_jenc_seg_scan, dim3(n), dim3(256), a);
+    VF_LAUNCH_CHECK();
+  }
+  VF_LAUNCH_TIMED(ctx, "jpeg_enc_clear", 0.0, 0.0, k_jenc_clear, per_chunk, dim3(256), a);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_enc_write", 0.0, coef, k_jenc_write<OPTS>, per_tile, dim3(256), a);
+  VF_LAUNCH_CHECK();
+  {
+    VfProf prof(ctx, "jpeg_enc_stuff", 0.0, 0.0);
+    hipLaunchKernelGGL(k_jenc_ff_count, per_chunk, dim3(256), 0, ctx->stream, a);
+    VF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jenc_ff_scan<OPTS>, dim3(n), dim3(256), 0, ctx->stream, a, hdr.len);
+    VF_LAUNCH_CHECK();
+    vf_launch_file_offsets(ctx->stream, a.offsets, n);
+    VF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jenc_stuff<OPTS>, per_chunk, dim3(256), 0, ctx->stream, a, hdr);
+    VF_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+int jenc_encode(const char* who, vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling,
+                int restart_rows, int restart_blocks, int optimize, void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap,
+                int64_t* offsets) {
   JencPlan p;
-  if (int e = jenc_plan("vf_jpeg_encode", n, H, W, C, subsampling, &p)) return e;
-  VF_REQUIRE(quality >= 1 && quality <= 100, "vf_jpeg_encode: quality = %d (1 to 100)", quality);
+  if (int e = jenc_plan(who, n, H, W, C, subsampling, restart_rows, restart_blocks, optimize, &p)) return e;
+  VF_REQUIRE(quality >= 1 && quality <= 100, "%s: quality = %d (1 to 100)", who, quality);
   char batch[64];
   snprintf(batch, sizeof(batch), "%d frames of %dx%dx%d", n, H, W, C);
-  if (int e = vf_check_encode_entry("vf_jpeg_encode", kind, "C", batch, ws_bytes, p.ws_bytes, out_cap, p.out_bytes)) return e;
+  if (int e = vf_check_encode_entry(who, kind, "C", batch, ws_bytes, p.ws_bytes, out_cap, p.out_bytes)) return e;
   JencArgs a;
   JencHdr hdr;
-  jenc_header(H, W, C, quality, p.hs, p.vs, &hdr, a.quant);
+  jenc_header(H, W, C, quality, p.hs, p.vs, p.interval, p.tables != 0, &hdr, a.quant);
   char* w = (char*)ws;
   a.src = src;
   a.coef = (short*)(w + p.o_coef);
@@ -544,29 +864,36 @@ VF_API int vf_jpeg_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, 
   a.mcux = p.mcux; a.mcuy = p.mcuy; a.bpm = p.bpm; a.nb = p.nb;
   a.wb = (int)vf_cdiv(W, 8); a.hb = (int)vf_cdiv(H, 8);
   a.tiles = p.tiles; a.chunks = p.chunks;
-  const double px = (double)n * H * W * C, coef = (double)n * p.nb * 128;
-  const dim3 per_tile((unsigned)p.tiles, n), per_chunk((unsigned)p.chunks, n);
-  if (kind == 0) VF_LAUNCH_TIMED(ctx, "jpeg_enc_dct", 0.0, 4.0 * px + coef, k_jenc_dct<0>, per_tile, dim3(256), a);
-  else VF_LAUNCH_TIMED(ctx, "jpeg_enc_dct", 0.0, px + coef, k_jenc_dct<1>, per_tile, dim3(256), a);
-  VF_LAUNCH_CHECK();
-  VF_LAUNCH_TIMED(ctx, "jpeg_enc_size", 0.0, coef, k_jenc_size, per_tile, dim3(256), a);
-  VF_LAUNCH_CHECK();
-  VF_LAUNCH_TIMED(ctx, "jpeg_enc_scan", 0.0, 12.0 * n * p.tiles, k_jenc_tile_scan, dim3(n), dim3(256), a);
-  VF_LAUNCH_CHECK();
-  VF_LAUNCH_TIMED(ctx, "jpeg_enc_clear", 0.0, 0.0, k_jenc_clear, per_chunk, dim3(256), a);
-  VF_LAUNCH_CHECK();
-  VF_LAUNCH_TIMED(ctx, "jpeg_enc_write", 0.0, coef, k_jenc_write, per_tile, dim3(256), a);
-  VF_LAUNCH_CHECK();
-  {
-    VfProf prof(ctx, "jpeg_enc_stuff", 0.0, 0.0);
-    hipLaunchKernelGGL(k_jenc_ff_count, per_chunk, dim3(256), 0, ctx->stream, a);
-    VF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_jenc_ff_scan, dim3(n), dim3(256), 0, ctx->stream, a, hdr.len);
-    VF_LAUNCH_CHECK();
-    vf_launch_file_offsets(ctx->stream, offsets, n);
-    VF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_jenc_stuff, per_chunk, dim3(256), 0, ctx->stream, a, hdr);
-    VF_LAUNCH_CHECK();
-  }
-  return 0;
+  a.spb = p.spb; a.nseg = p.nseg; a.optimize = p.tables;
+  a.seg_start = p.opts() ? (unsigned long long*)(w + p.o_sstart) : nullptr;
+  a.seg_shift = p.opts() ? (long long*)(w + p.o_sshift) : nullptr;
+  a.counts = p.tables ? (unsigned*)(w + p.o_counts) : nullptr;
+  a.lut = p.tables ? (JencLut*)(w + p.o_lut) : nullptr;
+  a.dht = p.tables ? (unsigned char*)(w + p.o_dht) : nullptr;
+  a.dht_len = p.tables ? (int*)(w + p.o_dlen) : nullptr;
+  return p.opts() ? jenc_launch<true>(ctx, p, a, hdr, kind) : jenc_launch<false>(ctx, p, a, hdr, kind);
+}
+
+}  // namespace
+
+VF_API int vf_jpeg_encode_workspace_bytes(int n, int H, int W, int C, int subsampling, size_t* ws_bytes, size_t* out_bytes) {
+  return jenc_workspace_bytes("vf_jpeg_encode_workspace_bytes", n, H, W, C, subsampling, 0, 0, 0, ws_bytes, out_bytes);
+}
+
+VF_API int vf_jpeg_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling, void* ws,
+                          size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
+  return jenc_encode("vf_jpeg_encode", ctx, src, kind, n, H, W, C, quality, subsampling, 0, 0, 0, ws, ws_bytes, out, out_cap, offsets);
+}
+
+VF_API int vf_jpeg_encode_opts_workspace_bytes(int n, int H, int W, int C, int subsampling, int restart_rows, int restart_blocks,
+                                               int optimize, size_t* ws_bytes, size_t* out_bytes) {
+  return jenc_workspace_bytes("vf_jpeg_encode_opts_workspace_bytes", n, H, W, C, subsampling, restart_rows, restart_blocks, optimize,
+                              ws_bytes, out_bytes);
+}
+
+VF_API int vf_jpeg_encode_opts(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling,
+                               int restart_rows, int restart_blocks, int optimize, void* ws, size_t ws_bytes, unsigned char* out,
+                               size_t out_cap, int64_t* offsets) {
+  return jenc_encode("vf_jpeg_encode_opts", ctx, src, kind, n, H, W, C, quality, subsampling, restart_rows, restart_blocks, optimize,
+                     ws, ws_bytes, out, out_cap, offsets);
 }
