@@ -11,10 +11,14 @@ import sys
 # rocprof kernel name -> the name bench.py's kernel table uses (tests/test_host_logic.py pins the ones a bench line can choose)
 def bench_name(k):
     suf = {"0": "", "1": "_bf16", "3": "_bf16x3"}
-    m = re.match(r"void k_wgrad_group<(\d+), \w+, \w+, (\d)>", k)
+    # the third argument is the form of the gathered operand's loads: a bool in older traces, `(WgV)n` since (2: whole 3-channel pixels)
+    m = re.match(r"void k_wgrad_group<(\d+), \w+, [^,]+, (\d)>", k)
     if m:
         return "wgrad_group_%sx128%s" % (m.group(1), suf.get(m.group(2), ""))
-    m = re.match(r"void k_wgrad<(\d+), \w+, \w+(?:, (\d))?>", k)
+    m = re.match(r"void k_wgrad<(\d+), \w+, \(WgV\)2, (\d)>", k)
+    if m:
+        return "wgrad_%sx64_pix3%s" % (m.group(1), suf.get(m.group(2), ""))
+    m = re.match(r"void k_wgrad<(\d+), \w+, [^,>]+(?:, (\d))?>", k)
     if m:
         return "wgrad_%sx128%s" % (m.group(1), suf.get(m.group(2) or "0", ""))
     # k_igemm<BM, BN, WM, WN, kmajorB, V, mode, KLIN, DB>

@@ -860,16 +860,31 @@ struct WGrad {
   float beta;
 };
 
-// BM over n (64 or 128); BN = 128 columns (tap,c).  VU / VV: 16-byte loads legal for U / V.
+// how a thread fetches its piece of the gathered operand V
+enum WgV {
+  WGV_SCALAR,   // four columns (tap, c), each with its own address and range test: any Cv
+  WGV_VEC16,    // one 16-byte load: Cv % 4 == 0
+  WGV_PIX3      // Cv == 3: one 12-byte load of a whole pixel.  The block's columns are col4 = 4 * tap + c with c = 3 a phantom
+                // channel that is always zero, so the 16 taps fill a 64-column tile (BN = 64) and a thread owns one (pixel row, tap):
+                // one (iy, ix), one range test and one address per piece, where the scalar form spends four of each on a 128-column
+                // tile of which 48 columns exist
+};
+// BM over n (64 or 128); BN columns (tap,c): 128, or the 64 of WGV_PIX3.  VU: 16-byte loads legal for U; VV: the form of V's loads.
 // BF: bf16-operand mode — U and V go into LDS as k-major bf16 tiles (one 8-byte store per piece), the fragments come
 // out through the transposing read (vf_tr_frag) and the products run on v_mfma_f32_32x32x16_bf16, fp32 accumulation.
-template <int BM, bool VU, bool VV, int BF = 0>
+template <int BM, bool VU, WgV VV, int BF = 0, int BN = 128>
 __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
-  constexpr int BN = 128, BK = BF ? 32 : 16;      // bf16 mode: two 16-deep MFMA groups per barrier
+  static_assert(VV == WGV_PIX3 ? (BN == 64 && BF != 0) : BN == 128, "the whole-pixel form is a 64-column tile of the bf16 modes");
+  constexpr int BK = BF ? 32 : 16;                // bf16 mode: two 16-deep MFMA groups per barrier
   constexpr int LDU = BM + 4, LDV = BN + 4;
-  constexpr int WN = BM == 128 ? 64 : 32;
+  // four waves.  BN = 128: 64 x 32 each side by side (BM = 64) or 64 x 64 as 2 x 2 (BM = 128); BN = 64: 2 x 2 waves of 32 x 32
+  // (BM = 64) or 64 x 32 (BM = 128) — no wave holds columns that do not exist
+  constexpr int WN = (BM == 128 && BN == 128) ? 64 : 32;
   constexpr int NT = WN / 32;
   constexpr int WAVES_N = BN / WN;
+  constexpr int WM = BM / (4 / WAVES_N);
+  constexpr int MT = WM / 32;
+  constexpr int CQ = BN / 4;                 // threads across a V row (4 columns each); 256 / CQ pixel rows per piece
   constexpr int U_CH = (BK * BM / 4) / 256;  // 2 (BM=128) or 1 (BM=64)
   constexpr int V_CH = (BK * BN / 4) / 256;  // 2
   constexpr int U_SZ = BK * LDU, V_SZ = BK * LDV;
@@ -882,7 +897,7 @@ __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
   __shared__ __attribute__((aligned(16))) float smem[SMEM_F];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave / WAVES_N) * 64, wn = (wave % WAVES_N) * WN;
+  const int wm = (wave / WAVES_N) * WM, wn = (wave % WAVES_N) * WN;
   const int lid = vf_xcd_remap(block_id, p.gx * p.gy * p.gz);
   const int n0 = ((lid / p.gx) % p.gy) * BM, j0 = (lid % p.gx) * BN;
   const int ks = lid / (p.gx * p.gy);
@@ -892,7 +907,7 @@ __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
   const int Mw = 1 << p.lgMw, Mh = 1 << p.lgMh;
 
   // V columns owned by this thread: 4 consecutive columns starting at j0 + 4*cq
-  const int cq = tid & 31;
+  const int cq = tid % CQ, vrow = tid / CQ;
   int v_dy[4], v_dx[4], v_c[4];
   bool v_okc[4];
 #pragma unroll
@@ -928,11 +943,15 @@ __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
       }
     } else {
       const int i = pc - U_CH;
-      const int pp = kt * BK + (tid >> 5) + 8 * i;
+      const int pp = kt * BK + vrow + (256 / CQ) * i;
       const bool okp = live && pp < p.P;
       const int mx = pp & (Mw - 1), my = (pp >> p.lgMw) & (Mh - 1), b = pp >> (p.lgMw + p.lgMh);
       const int boff = b * p.Hv * p.Wv * p.Cv;
-      if constexpr (VV) {
+      if constexpr (VV == WGV_PIX3) {
+        const int iy = my * p.stride + (cq >> 2) - p.pad, ix = mx * p.stride + (cq & 3) - p.pad;      // cq is the tap
+        const bool ok = okp && (unsigned)iy < (unsigned)p.Hv && (unsigned)ix < (unsigned)p.Wv;
+        rv[i] = vf_bload3(rsV, ok ? 4u * (unsigned)(boff + (iy * p.Wv + ix) * 3) : VF_OOB);
+      } else if constexpr (VV == WGV_VEC16) {
         const int iy = my * p.stride + v_dy[0], ix = mx * p.stride + v_dx[0];
         const bool ok = okp && v_okc[0] && (unsigned)iy < (unsigned)p.Hv && (unsigned)ix < (unsigned)p.Wv;
         rv[i] = vf_bload4(rsV, ok ? 4u * (unsigned)(boff + (iy * p.Wv + ix) * p.Cv + v_c[0]) : VF_OOB);
@@ -959,7 +978,7 @@ __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
       } else {
         const int i = pc - U_CH;
         v = rv[i];
-        off = UH_SZ + ((tid >> 5) + 8 * i) * LDMV + 4 * cq;
+        off = UH_SZ + (vrow + (256 / CQ) * i) * LDMV + 4 * cq;
       }
       if constexpr (NP == 3) {
         u32x2 s3[3];
@@ -977,7 +996,7 @@ __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
       *(f32x4*)(Us + (ukk + pc * (1024 / BM)) * LDU + 4 * uq) = ru[pc];
     } else {
       const int i = pc - U_CH;
-      *(f32x4*)(Vs + ((tid >> 5) + 8 * i) * LDV + 4 * cq) = rv[i];
+      *(f32x4*)(Vs + (vrow + (256 / CQ) * i) * LDV + 4 * cq) = rv[i];
     }
   };
   constexpr int NPC = U_CH + V_CH;
@@ -990,9 +1009,9 @@ __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
     for (int pc = 0; pc < NPC; ++pc) store_piece(buf, pc);
   };
 
-  f32x16 acc[2][NT];
+  f32x16 acc[MT][NT];
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
+  for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -1013,18 +1032,18 @@ __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
       for (int pc = 0; pc < NPC; ++pc) load_piece(kt + 1, pc, more);
 #pragma unroll
       for (int g = 0; g < BK / 16; ++g) {
-        bf16x8 a[NP][2], b[NP][NT];
+        bf16x8 a[NP][MT], b[NP][NT];
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
           const __bf16* Uh = base + q * PL_SZ;
           const __bf16* Vh = Uh + UH_SZ;
 #pragma unroll
-          for (int mt = 0; mt < 2; ++mt) a[q][mt] = vf_tr_frag<LDMU>(Uh, wm + mt * 32, 16 * g, lane);
+          for (int mt = 0; mt < MT; ++mt) a[q][mt] = vf_tr_frag<LDMU>(Uh, wm + mt * 32, 16 * g, lane);
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt) b[q][nt] = vf_tr_frag<LDMV>(Vh, wn + nt * 32, 16 * g, lane);
         }
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
+        for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt) {
             if constexpr (NP == 3) {
@@ -1042,6 +1061,7 @@ __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
       __syncthreads();
     }
   } else {
+  static_assert(BF != 0 || MT == 2, "the fp32 schedule below is written for two row fragments per wave");
   constexpr int NMF = 4 * 2 * NT;              // MFMAs per 8-wide sub-step
   constexpr int SLOTS = 2 * NMF;               // MFMA slots per K step (BK = 16)
   static_assert(2 * NPC <= SLOTS, "loads and LDS writes of one K step must fit between its MFMAs");
@@ -1088,15 +1108,20 @@ __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
   const int64_t total = (int64_t)p.Nu * Ncols;
   float* out = p.ksplit > 1 ? p.slab + (int64_t)ks * total : p.dW;
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
+  for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int n = n0 + wm + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
       if (n >= p.Nu) continue;
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
-        const int col = j0 + wn + nt * 32 + lr;
-        if (col < Ncols) {
+        int col = j0 + wn + nt * 32 + lr;
+        bool okc = col < Ncols;
+        if constexpr (VV == WGV_PIX3) {      // col4 = 4 * tap + c -> 3 * tap + c; the phantom channel has no element
+          okc = (col & 3) != 3;
+          col = 3 * (col >> 2) + (col & 3);
+        }
+        if (okc) {
           const int64_t idx = (int64_t)n * Ncols + col;
           float v = acc[mt][nt][r];
           if (p.ksplit == 1 && p.beta != 0.f) v += p.beta * out[idx];
@@ -1106,9 +1131,9 @@ __device__ __forceinline__ void wgrad_body(const WGrad& p, const int block_id) {
     }
 }
 
-template <int BM, bool VU, bool VV, int BF = 0>
+template <int BM, bool VU, WgV VV, int BF = 0>
 __global__ __launch_bounds__(256) void k_wgrad(const WGrad p) {
-  wgrad_body<BM, VU, VV, BF>(p, blockIdx.x);
+  wgrad_body<BM, VU, VV, BF, VV == WGV_PIX3 ? 64 : 128>(p, blockIdx.x);
 }
 
 // Every weight gradient of a backward walk in ONE launch: dW_l needs only (input_l, gradOutput_l), both of which stay in
@@ -1122,7 +1147,7 @@ struct WGradGroup {
   WGrad d[VF_WG_GROUP_MAX];
 };
 static_assert(sizeof(WGradGroup) <= 3584, "kernel arguments are limited to 4 KB");
-template <int BM, bool VU, bool VV, int BF>
+template <int BM, bool VU, WgV VV, int BF>
 __global__ __launch_bounds__(256) void k_wgrad_group(const WGradGroup G) {
   int l = 0;
   while (l + 1 < G.n && (int)blockIdx.x >= G.blk_off[l + 1]) ++l;
@@ -1641,7 +1666,8 @@ struct WgPlan {
   int P, Hl, Wl, Nu;      // U's side, the low-resolution map: pixels, map, channels
   int Hv, Wv, Cv;         // V's side
   bool vecU, vecV;        // 16-byte loads are legal
-  int nk;                 // K steps of the kernel's BK
+  bool pix3;              // V is fetched as whole 3-channel pixels (WGV_PIX3): the image-side layers, in the bf16 modes
+  int nk;                // K steps of the kernel's BK
   int bm, gx, gy;         // tile rows (128 / 64), column tiles, row tiles
   int64_t total;          // dW elements
   int target, ksplit;     // split-K: the blocks per layer aimed at, the K ranges taken
@@ -1669,7 +1695,10 @@ static WgPlan wg_plan(vf_ctx* ctx, const VfConvShape& s, bool full, const float*
   p.P = s.B * p.Hl * p.Wl;
   p.vecU = (p.Nu % 4 == 0) && vf_aligned16(U);
   p.vecV = (p.Cv % 4 == 0) && vf_aligned16(V);
-  p.nk = (int)vf_cdiv(p.P, mode ? 32 : 16);
+  // the whole-pixel form needs dword alignment only, which every tensor has.  It changes the tile's columns (64, all of them taps,
+  // instead of 48 of 128), not the grid (gx = 1 either way), the K walk or the split below: the same sums in the same order
+  p.pix3 = p.Cv == 3 && p.vecU && mode != 0;
+  p.nk =(int)vf_cdiv(p.P, mode ? 32 : 16);
   p.bm = p.Nu > 64 ? 128 : 64;
   p.gy = (int)vf_cdiv(p.Nu, p.bm);
   p.gx = (int)vf_cdiv(16 * (int64_t)p.Cv, 128);
@@ -1852,7 +1881,7 @@ static int wg_flush(vf_ctx* ctx) {
             char name[64];
             snprintf(name, sizeof(name), "wgrad_group_%dx128%s", bm, bf == 3 ? "_bf16x3" : (bf ? "_bf16" : ""));
             wg_dispatch(bm, bf, [&](auto BM, auto BF) {
-              VF_LAUNCH_TIMED(ctx, name, fl, 0.0, (k_wgrad_group<decltype(BM)::value, true, true, decltype(BF)::value>), dim3(blocks),
+              VF_LAUNCH_TIMED(ctx, name, fl, 0.0, (k_wgrad_group<decltype(BM)::value, true, WGV_VEC16, decltype(BF)::value>), dim3(blocks),
                               dim3(256), G);
             });
             return 0;
@@ -1963,16 +1992,24 @@ static int wgrad(vf_ctx* ctx, const float* U, const float* V, float* dW, const V
   }
   const WGrad g = wg_desc(p, U, V, dW, slab, beta);
   const int bf = ctx->mfma_bf16;
-  const char* wname = p.bm == 128 ? (bf == 3 ? "wgrad_128x128_bf16x3" : bf ? "wgrad_128x128_bf16" : "wgrad_128x128")
-                                  : (bf == 3 ? "wgrad_64x128_bf16x3" : bf ? "wgrad_64x128_bf16" : "wgrad_64x128");
+  const char* wname = p.pix3 ? (p.bm == 128 ? (bf == 3 ? "wgrad_128x64_pix3_bf16x3" : "wgrad_128x64_pix3_bf16")
+                                            : (bf == 3 ? "wgrad_64x64_pix3_bf16x3" : "wgrad_64x64_pix3_bf16"))
+                      : p.bm == 128 ? (bf == 3 ? "wgrad_128x128_bf16x3" : bf ? "wgrad_128x128_bf16" : "wgrad_128x128")
+                                    : (bf == 3 ? "wgrad_64x128_bf16x3" : bf ? "wgrad_64x128_bf16" : "wgrad_64x128");
   const double wfl = p.flops();
   const dim3 grid((unsigned)p.blocks()), block(256);
   wg_dispatch(p.bm, bf, [&](auto BM, auto BF) {
     constexpr int bm_ = decltype(BM)::value, bf_ = decltype(BF)::value;
-    if (p.vecU && p.vecV) VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, true, true, bf_>), grid, block, g);
-    else if (p.vecU) VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, true, false, bf_>), grid, block, g);
-    else if (p.vecV) VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, false, true, bf_>), grid, block, g);
-    else VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, false, false, bf_>), grid, block, g);
+    if constexpr (bf_ != 0) {
+      if (p.pix3) {
+        VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, true, WGV_PIX3, bf_>), grid, block, g);
+        return;
+      }
+    }
+    if (p.vecU && p.vecV) VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, true, WGV_VEC16, bf_>), grid, block, g);
+    else if (p.vecU) VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, true, WGV_SCALAR, bf_>), grid, block, g);
+    else if (p.vecV) VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, false, WGV_VEC16, bf_>), grid, block, g);
+    else VF_LAUNCH_TIMED(ctx, wname, wfl, 0.0, (k_wgrad<bm_, false, WGV_SCALAR, bf_>), grid, block, g);
   });
   VF_LAUNCH_CHECK();
   if (p.ksplit > 1) {

@@ -7,6 +7,7 @@
 #include "vf_common.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x3 __attribute__((ext_vector_type(3)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -21,6 +22,12 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t vf_rsrc(const void* p, unsigne
 }
 __device__ __forceinline__ f32x4 vf_bload4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
+}
+// 12 bytes, dword-aligned: one whole 3-channel pixel (buffer_load_dwordx3); element 3 of the result is 0
+__device__ __forceinline__ f32x4 vf_bload3(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
+  const f32x3 v = __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(r, byte_off, 0, 0));
+  const f32x4 o = {v[0], v[1], v[2], 0.f};
+  return o;
 }
 __device__ __forceinline__ float vf_bload1(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
