@@ -439,6 +439,54 @@ int vf_jpeg_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, 
                    const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
                    int32_t* status, int32_t* rounds);
 
+/* ---- progressive JPEG decode (vf_jpeg.hip) -----------------------------------------------------------
+ * SOF2 files through the same dequantisation, IDCT, upsampling and colour conversion: for a progression that is
+ * complete, libjpeg's output is its output for the baseline file of the same coefficients, so the result is byte for
+ * byte libjpeg's.  The entropy decoding is jdphuff.c's.  Supported: SOF2, Huffman coding, 8-bit samples, components,
+ * colour spaces, samplings, sides and quantisation tables as for the baseline decoder, restart intervals or none (DRI
+ * may change between scans), up to 64 scans whose progression is ORDERLY (the first scan of every coefficient of every
+ * component has Ah = 0, every later one has Ah = the Al before it, a component's DC comes before its AC) and COMPLETE
+ * (every coefficient has reached Al = 0 by the end).  A file that is not orderly or not complete is unsupported, not
+ * malformed (libjpeg warns and block-smooths; there is no one result to pin).  Malformed (an error naming the scan):
+ * an SOS that breaks libjpeg's JERR_BAD_PROGRESSION conditions (Ss <= Se <= 63; Ss = 0 means Se = 0; Ss > 0 means one
+ * component; Al <= 13; Ah = 0 or Al = Ah - 1), or that names a Huffman slot no DHT has defined (a DC refinement scan
+ * needs none), and everything vf_jpeg_inspect calls malformed.  vf_jpeg_inspect itself is unchanged: to it a
+ * progressive file stays unsupported.
+ * vf_jpeg_scans_inspect (host only, no GPU): walk the whole file.  info (int64[12]) = {width, height, components, luma
+ * h, luma v, scans, supported (0 / 1), SOF marker, sample precision, scan levels, coefficient blocks, blocks per MCU}.
+ * scans (may be NULL; int64[scan_cap][16]) receives per scan {components, their places in the frame (4 entries, -1
+ * beyond), Ss, Se, Ah, Al, restart interval, begin, end (byte range of its entropy-coded data), restart segments,
+ * level, units (MCUs of an interleaved scan, real blocks of a single-component one), 0}.  A scan's level is one more
+ * than the highest level among the earlier scans that touch the same component and an overlapping band; scans of one
+ * level are independent.  A file whose headers already rule it out (CMYK, 12-bit, ...; reason as vf_jpeg_inspect) or
+ * that is not SOF2 ("not progressive") reports no scans; a progression found out of order stops the walk there. */
+int vf_jpeg_scans_inspect(const unsigned char* data, size_t len, int64_t* info, int64_t* scans, int scan_cap, char* reason,
+                          int reason_cap);
+/* Exact sizes for one batch of supported progressive files, as vf_jpeg_workspace_bytes (the files are walked);
+ * subseq_bytes as there, for the first scans. */
+int vf_jpeg_prog_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
+                                 size_t* stage_bytes);
+/* Decode the batch on the context's stream; arguments and rules as vf_jpeg_decode, so a caller can decode baseline
+ * and progressive files into one output buffer with one call each.  One upload, the unstuffing launch, one launch per
+ * scan level of the batch (3 for libjpeg's default scripts; never a function of n), then the baseline IDCT and colour
+ * launches.  Level 0 holds every first scan (Ah = 0), one block per (image, scan, restart segment), decoded by
+ * self-synchronisation over subsequences of subseq_bytes as the baseline scan is; the later levels hold the refinement
+ * scans, one lane per (image, scan, restart segment) walking it in order.  rounds (DEVICE int32[1]): the largest number
+ * of synchronisation rounds any first-scan segment needed; levels (HOST, may be NULL): the number of level launches. */
+int vf_jpeg_prog_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes,
+                        const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
+                        int32_t* status, int32_t* rounds, int32_t* levels);
+/* Host only, no GPU: the assembled quantised coefficients of ONE supported progressive file, from the same decode
+ * functions and the same packed batch the device runs.  subseq_bytes 0: every scan is walked in order, segment by
+ * segment (what the refinement lanes do); >= 8: the first scans go through the self-synchronising scheme instead, its
+ * lanes run one after the other (what the first-scan blocks do).  coef (HOST int16[coef_blocks][64], coef_blocks >=
+ * info[10] of vf_jpeg_scans_inspect): block m * bpm + b is block b of MCU m (MCUs in raster order; within one, the
+ * components in frame order, each component's blocks in raster order, dummy blocks included), its 64 values in natural
+ * (row-major) order.  status receives the worst VF_JPEG_* of any segment; corrupt data ends in a status and never reads
+ * or writes outside the buffers. */
+int vf_jpeg_prog_coefficients_host(const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef, size_t coef_blocks,
+                                   int32_t* status);
+
 /* ---- PNG decode (vf_png_decode.hip) ------------------------------------------------------------------
  * image.load of a PNG file (the masks of datavid/donkey_folder.lua, test_vid_wholeim.lua:112 and
  * test_more_complex.lua:102, demo.lua:51, and the frames vf_png_encode writes) on the device: the BYTES libpng gives

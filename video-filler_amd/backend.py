@@ -225,6 +225,68 @@ def jpeg_inspect(data, walk=True):
     return d
 
 
+JPEG_MAX_SCANS = 64     # kProgMaxScans of csrc/vf_jpeg.hip
+
+
+def jpeg_scans_inspect(data):
+    """The host-only walk of one progressive JPEG file (vf_jpeg_scans_inspect; no GPU needed) -> dict(width, height,
+    components, h_samp, v_samp, supported, sof, precision, levels, blocks, blocks_per_mcu, reason, scans), scans a list of
+    dict(components (their places in the frame), Ss, Se, Ah, Al, restart_interval, begin, end, segments, level, units).
+    supported: the device decoder takes the file (SOF2, an orderly and complete progression), else reason
+    says why not.  Raises ValueError for a malformed file (a scan with bad progression parameters or an undefined Huffman
+    table among them)."""
+    lib = _lib.load()
+    data = bytes(data)
+    info = (C.c_int64 * 12)()
+    rows = (C.c_int64 * (16 * JPEG_MAX_SCANS))()
+    why = C.create_string_buffer(160)
+    if lib.vf_jpeg_scans_inspect(data, len(data), info, rows, JPEG_MAX_SCANS, why, 160) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    keys = ("width", "height", "components", "h_samp", "v_samp", "nscans", "supported", "sof", "precision", "levels", "blocks",
+            "blocks_per_mcu")
+    d = {k: int(v) for k, v in zip(keys, info)}
+    d["supported"] = bool(d["supported"])
+    d["reason"] = why.value.decode()
+    skeys = ("Ss", "Se", "Ah", "Al", "restart_interval", "begin", "end", "segments", "level", "units")
+    d["scans"] = []
+    for i in range(d.pop("nscans")):
+        r = [int(v) for v in rows[16 * i:16 * i + 16]]
+        s = dict(zip(skeys, r[5:15]))
+        s["components"] = r[1:1 + r[0]]
+        d["scans"].append(s)
+    return d
+
+
+def jpeg_prog_workspace_bytes(files, subseq_bytes=256):
+    """(device workspace bytes, host staging bytes) of one batch of progressive files (vf_jpeg_prog_workspace_bytes; host
+    only, no GPU needed).  ValueError, naming the image, for a malformed or unsupported file."""
+    lib = _lib.load()
+    data, offs = _joined(files)
+    ws_b, st_b = C.c_size_t(), C.c_size_t()
+    if lib.vf_jpeg_prog_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), len(files), subseq_bytes, C.byref(ws_b), C.byref(st_b)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return ws_b.value, st_b.value
+
+
+def jpeg_prog_coefficients(data, info=None, subseq_bytes=0):
+    """The quantised coefficients of one supported progressive file, assembled on the host by the functions the device
+    runs (vf_jpeg_prog_coefficients_host; no GPU needed): every scan walked in order (subseq_bytes 0), or the first scans
+    through the self-synchronising scheme over subsequences of that size.  -> (coef, status): coef int16 [blocks, 64], block m *
+    blocks_per_mcu + b being block b of MCU m (the frame's components in order, each one's blocks in raster order, dummy
+    blocks included), values in natural order; status a key of JPEG_STATUS (0 unless the entropy-coded data is corrupt).
+    ValueError for a malformed or unsupported file."""
+    lib = _lib.load()
+    data = bytes(data)
+    info = info or jpeg_scans_inspect(data)
+    if not info["supported"]:
+        raise ValueError("jpeg_prog_coefficients: unsupported: %s" % info["reason"])
+    coef = np.zeros((info["blocks"], 64), np.int16)
+    status = C.c_int32(0)
+    if lib.vf_jpeg_prog_coefficients_host(data, len(data), subseq_bytes, coef.ctypes.data_as(C.c_void_p), info["blocks"], C.byref(status)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return coef, status.value
+
+
 PNG_STATUS = {0: "ok", 1: "bad code", 2: "short data", 3: "bad distance", 4: "bad length", 5: "bad filter", 6: "bad Adler-32",
               7: "bad palette index"}
 
@@ -950,14 +1012,19 @@ class HipBackend:
             setattr(self, attr, ws)
         return ws
 
-    def _decode(self, name, query, entry, files, sizes, query_args, call_args, *results):
+    def _decode(self, name, query, entry, files, sizes, query_args, call_args, *results, into=None):
         """One batch-decoder call: the files back to back, image i's place in `out` from sizes[i], the bounds from `query`,
-        the stage's scratch and its staging buffer of this turn, then `entry`.  -> (out, out_offs, status)."""
+        the stage's scratch and its staging buffer of this turn, then `entry`.  -> (out, out_offs, status).  into: (out,
+        starts) of a buffer the caller owns, image i going to out[starts[i]:] (sizes is then unused); out_offs is starts."""
         n = len(files)
         data, offs = _joined(files)
         offs_p = offs.ctypes.data_as(C.c_void_p)
-        out_offs = np.zeros(n + 1, np.int64)
-        out_offs[1:] = np.cumsum(sizes)
+        if into is not None:
+            out, out_offs = into[0], np.ascontiguousarray(into[1], np.int64)
+            assert out.dtype == torch.uint8 and out.device == self.device and len(out_offs) >= n
+        else:
+            out_offs = np.zeros(n + 1, np.int64)
+            out_offs[1:] = np.cumsum(sizes)
         ws_b, st_b = C.c_size_t(), C.c_size_t()
         _lib.check(getattr(self.lib, query)(data, offs_p, n, *query_args, C.byref(ws_b), C.byref(st_b)))
         ws = self._scratch(name, ws_b.value)
@@ -966,26 +1033,42 @@ class HipBackend:
             setattr(self, attr, _Stager())
         stager = getattr(self, attr)
         stage = stager.take(st_b.value)
-        out = torch.empty(max(int(out_offs[-1]), 1), dtype=torch.uint8, device=self.device)
+        if into is None:
+            out = torch.empty(max(int(out_offs[-1]), 1), dtype=torch.uint8, device=self.device)
         status = torch.empty(n, dtype=torch.int32, device=self.device)
         self._c(entry, data, offs_p, n, *call_args, out_offs.ctypes.data_as(C.c_void_p), _ptr(out), C.c_void_p(stage.data_ptr()),
-                stage.numel(), _ptr(ws), ws.numel(), _ptr(status), *map(_ptr, results))
+                stage.numel(), _ptr(ws), ws.numel(), _ptr(status), *(r if isinstance(r, C.c_void_p) else _ptr(r) for r in results))
         stager.done(torch.cuda.current_stream(self.device))
         return out, out_offs, status
 
     # ---- baseline JPEG decode (vf_jpeg.hip)
-    def jpeg_decode(self, files, channels=3, subseq_bytes=256, infos=None):
+    def jpeg_decode(self, files, channels=3, subseq_bytes=256, infos=None, into=None):
         """Decode a batch of supported JPEG files (bytes each) into one device uint8 buffer.  -> (out, offsets, status,
         rounds): image i is out[offsets[i]:offsets[i+1]] as H x W x channels; status (device int32[n]) holds VF_JPEG_*
         per image and rounds (device int32[1]) the synchronisation rounds; both are valid once the stream gets there.
         infos: the files' jpeg_inspect results, if the caller has them.  The workspace query reads the headers only;
-        vf_jpeg_decode is the one call that walks the scan data."""
+        vf_jpeg_decode is the one call that walks the scan data.  into: (buffer, starts) of the caller's own output
+        buffer instead of a new one (_decode)."""
         shapes = infos if infos is not None else [jpeg_inspect(f, walk=False) for f in files]
         rounds = torch.empty(1, dtype=torch.int32, device=self.device)
         out, out_offs, status = self._decode("jpeg", "vf_jpeg_workspace_bytes", "vf_jpeg_decode", files,
                                              [s["height"] * s["width"] * channels for s in shapes], (subseq_bytes,),
-                                             (channels, subseq_bytes), rounds)
+                                             (channels, subseq_bytes), rounds, into=into)
         return out, out_offs, status, rounds
+
+    # ---- progressive JPEG decode (vf_jpeg.hip, DESIGN.md 5.9)
+    def jpeg_prog_decode(self, files, channels=3, subseq_bytes=256, infos=None, into=None):
+        """Decode a batch of supported progressive JPEG files (bytes each) on the device.  -> (out, offsets, status,
+        rounds, levels) as jpeg_decode; rounds counts the first scans' synchronisation rounds, levels (int) is the number
+        of scan-level launches the batch took.  infos: the files' jpeg_scans_inspect (or jpeg_inspect) results, if the
+        caller has them; into: as jpeg_decode."""
+        shapes = infos if infos is not None else [jpeg_inspect(f, walk=False) for f in files]
+        rounds = torch.empty(1, dtype=torch.int32, device=self.device)
+        levels = C.c_int32(0)
+        out, out_offs, status = self._decode("jpegp", "vf_jpeg_prog_workspace_bytes", "vf_jpeg_prog_decode", files,
+                                             [s["height"] * s["width"] * channels for s in shapes], (subseq_bytes,),
+                                             (channels, subseq_bytes), rounds, C.cast(C.pointer(levels), C.c_void_p), into=into)
+        return out, out_offs, status, rounds, levels.value
 
     # ---- PNG decode (vf_png_decode.hip, DESIGN.md 5.6)
     def png_decode(self, files, channels=None, infos=None):

@@ -13,6 +13,9 @@
 //   k_jpeg_idct      one thread per 8x8 block: dequantise, jpeg_idct_islow, range-limit into uint8 component planes;
 //   k_jpeg_color     one thread per output pixel: fancy upsampling, ycc_rgb_convert, crop into H x W x C.
 // Everything is integer arithmetic.
+// Progressive (SOF2) files share all of it but k_jpeg_huffman: vf_jpeg_scans_inspect walks their scans,
+// vf_jpeg_prog_decode assembles the coefficients scan level by scan level and runs the same IDCT and colour launches,
+// vf_jpeg_prog_coefficients_host assembles them on the host with the same functions.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -542,6 +545,7 @@ struct JpgParsed {
   int ns = 0, scomp[4] = {}, td[4] = {}, ta[4] = {};
   int ss = 0, se = 63, ahal = 0;
   bool jfif = false, adobe = false;
+  bool take_sof2 = false;   // set by the progressive path: SOF2 is no reason, and the scan checks are left to it
   int adobe_transform = -1;
   int64_t scan_begin = 0, scan_end = 0;
   bool supported = false;
@@ -557,6 +561,134 @@ struct JpgParsed {
 };
 
 inline int rd16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
+
+// the payloads of DHT, DQT and SOS (s: sl bytes behind the length) into P; non-zero with msg if malformed
+int jpg_dht(const uint8_t* s, int sl, JpgParsed& P, std::string& msg) {
+  int q = 0;
+  while (q < sl) {
+    if (q + 17 > sl) {
+      msg = "truncated DHT";
+      return 2;
+    }
+    const int tc = s[q] >> 4, th = s[q] & 15;
+    int cnt = 0;
+    for (int l = 1; l <= 16; ++l) cnt += s[q + l];
+    if (q + 17 + cnt > sl || cnt > 256 || th > 3 || tc > 1) {
+      msg = "malformed DHT";
+      return 2;
+    }
+    RawHuff& h = tc ? P.hac[th] : P.hdc[th];
+    h.bits[0] = 0;
+    for (int l = 1; l <= 16; ++l) h.bits[l] = s[q + l];
+    memcpy(h.val, s + q + 17, cnt);
+    h.nval = cnt;
+    h.present = true;
+    h.fits = huff_fits(h.bits);
+    q += 17 + cnt;
+  }
+  return 0;
+}
+
+int jpg_dqt(const uint8_t* s, int sl, JpgParsed& P, std::string& msg) {
+  int q = 0;
+  while (q < sl) {
+    const int pq = s[q] >> 4, tqi = s[q] & 15;
+    const int need = 1 + 64 * (pq ? 2 : 1);
+    if (q + need > sl || tqi > 3 || pq > 1) {
+      msg = "malformed DQT";
+      return 2;
+    }
+    for (int k = 0; k < 64; ++k) P.qt[tqi][zz_natural(k)] = pq ? rd16(s + q + 1 + 2 * k) : s[q + 1 + k];
+    P.qt_ok[tqi] = true;
+    q += need;
+  }
+  return 0;
+}
+
+int jpg_sos(const uint8_t* s, int sl, JpgParsed& P, std::string& msg) {
+  if (sl < 1) {
+    msg = "truncated SOS";
+    return 2;
+  }
+  P.ns = s[0];
+  if (sl < 1 + 2 * P.ns + 3 || P.ns < 1 || P.ns > 4) {
+    msg = "malformed SOS";
+    return 2;
+  }
+  for (int i = 0; i < P.ns; ++i) {
+    int f = -1;
+    for (int c = 0; c < P.ncomp && c < 4; ++c)
+      if (P.cid[c] == s[1 + 2 * i]) f = c;
+    if (f < 0) {
+      msg = "SOS names a component the frame does not have";
+      return 2;
+    }
+    for (int j = 0; j < i; ++j)
+      if (P.scomp[j] == f) {
+        msg = "SOS names a component twice";
+        return 2;
+      }
+    P.scomp[i] = f;
+    P.td[i] = s[2 + 2 * i] >> 4;
+    P.ta[i] = s[2 + 2 * i] & 15;
+  }
+  P.ss = s[1 + 2 * P.ns];
+  P.se = s[2 + 2 * P.ns];
+  P.ahal = s[3 + 2 * P.ns];
+  return 0;
+}
+
+// One scan's entropy-coded data from byte `begin`: every 0xFF is stuffing (0xFF00), a restart marker, or the end of the
+// scan.  -> its restart segments, the stuffed 0x00s' positions (appended to drops), its end and the marker there (-1:
+// the data ran out)
+int jpg_walk(const uint8_t* d, int64_t n, int64_t begin, std::vector<JpgParsed::Seg>& segs, std::vector<int64_t>& drops,
+             int64_t& scan_end, int& end_marker, std::string& msg) {
+  int64_t q = begin, seg0 = q, drop = 0;
+  int nrst = 0;
+  end_marker = -1;
+  for (;;) {
+    const uint8_t* f = q < n ? (const uint8_t*)memchr(d + q, 0xFF, (size_t)(n - q)) : nullptr;
+    if (!f) {
+      scan_end = n;
+      break;
+    }
+    const int64_t i = f - d;
+    int64_t j = i + 1;
+    while (j < n && d[j] == 0xFF) ++j;
+    if (j >= n) {
+      scan_end = i;
+      break;
+    }
+    const int c = d[j];
+    if (c == 0) {
+      if (j - i > 1) {
+        // fill bytes before a stuffed 0xFF: libjpeg-turbo's fast path reads them as a marker, its slow path (and
+        // jpeg-6b) skips them, so the file has no one libjpeg result.  No encoder writes them.
+        msg = "0xFF fill bytes inside the entropy-coded data at byte " + std::to_string(i);
+        return 2;
+      }
+      ++drop;
+      drops.push_back(j);   // the stuffed 0x00
+      q = j + 1;
+    } else if (c >= 0xD0 && c <= 0xD7) {
+      if (c != 0xD0 + (nrst & 7)) {
+        msg = "restart marker out of sequence";
+        return 2;
+      }
+      ++nrst;
+      segs.push_back({seg0, i, i - seg0 - drop});
+      seg0 = j + 1;
+      drop = 0;
+      q = j + 1;
+    } else {
+      scan_end = i;
+      end_marker = c;
+      break;
+    }
+  }
+  segs.push_back({seg0, scan_end, scan_end - seg0 - drop});
+  return 0;
+}
 
 // 0: headers parsed (P.supported says whether the decoder takes the file, P.why why not); else malformed (msg)
 int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool walk) {
@@ -628,7 +760,8 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
         P.hmax = std::max(P.hmax, P.hf[c]);
         P.vmax = std::max(P.vmax, P.vf[c]);
       }
-      if (m == 0xC2 || m == 0xC6 || m == 0xCA || m == 0xCE) unsupported("progressive");
+      if (m == 0xC2 && P.take_sof2) {
+      } else if (m == 0xC2 || m == 0xC6 || m == 0xCA || m == 0xCE) unsupported("progressive");
       else if (m == 0xC3 || m == 0xC7 || m == 0xCB || m == 0xCF) unsupported("lossless");
       else if (m >= 0xC9) unsupported("arithmetic coding");
       else if (m >= 0xC5) unsupported("hierarchical (differential)");
@@ -645,42 +778,10 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
                       "x" + std::to_string(P.vf[1]) + "," + std::to_string(P.hf[2]) + "x" + std::to_string(P.vf[2]) +
                       " (4:4:4, 4:2:2 and 4:2:0 only)");
       }
-    } else if (m == 0xC4) {   // DHT
-      int q = 0;
-      while (q < sl) {
-        if (q + 17 > sl) {
-          msg = "truncated DHT";
-          return 2;
-        }
-        const int tc = s[q] >> 4, th = s[q] & 15;
-        int cnt = 0;
-        for (int l = 1; l <= 16; ++l) cnt += s[q + l];
-        if (q + 17 + cnt > sl || cnt > 256 || th > 3 || tc > 1) {
-          msg = "malformed DHT";
-          return 2;
-        }
-        RawHuff& h = tc ? P.hac[th] : P.hdc[th];
-        h.bits[0] = 0;
-        for (int l = 1; l <= 16; ++l) h.bits[l] = s[q + l];
-        memcpy(h.val, s + q + 17, cnt);
-        h.nval = cnt;
-        h.present = true;
-        h.fits = huff_fits(h.bits);
-        q += 17 + cnt;
-      }
-    } else if (m == 0xDB) {   // DQT
-      int q = 0;
-      while (q < sl) {
-        const int pq = s[q] >> 4, tqi = s[q] & 15;
-        const int need = 1 + 64 * (pq ? 2 : 1);
-        if (q + need > sl || tqi > 3 || pq > 1) {
-          msg = "malformed DQT";
-          return 2;
-        }
-        for (int k = 0; k < 64; ++k) P.qt[tqi][zz_natural(k)] = pq ? rd16(s + q + 1 + 2 * k) : s[q + 1 + k];
-        P.qt_ok[tqi] = true;
-        q += need;
-      }
+    } else if (m == 0xC4) {
+      if (int e = jpg_dht(s, sl, P, msg)) return e;
+    } else if (m == 0xDB) {
+      if (int e = jpg_dqt(s, sl, P, msg)) return e;
     } else if (m == 0xDD) {   // DRI
       if (sl < 2) {
         msg = "truncated DRI";
@@ -699,35 +800,7 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
         msg = "SOS before SOF";
         return 2;
       }
-      if (sl < 1) {
-        msg = "truncated SOS";
-        return 2;
-      }
-      P.ns = s[0];
-      if (sl < 1 + 2 * P.ns + 3 || P.ns < 1 || P.ns > 4) {
-        msg = "malformed SOS";
-        return 2;
-      }
-      for (int i = 0; i < P.ns; ++i) {
-        int f = -1;
-        for (int c = 0; c < P.ncomp && c < 4; ++c)
-          if (P.cid[c] == s[1 + 2 * i]) f = c;
-        if (f < 0) {
-          msg = "SOS names a component the frame does not have";
-          return 2;
-        }
-        for (int j = 0; j < i; ++j)
-          if (P.scomp[j] == f) {
-            msg = "SOS names a component twice";
-            return 2;
-          }
-        P.scomp[i] = f;
-        P.td[i] = s[2 + 2 * i] >> 4;
-        P.ta[i] = s[2 + 2 * i] & 15;
-      }
-      P.ss = s[1 + 2 * P.ns];
-      P.se = s[2 + 2 * P.ns];
-      P.ahal = s[3 + 2 * P.ns];
+      if (int e = jpg_sos(s, sl, P, msg)) return e;
       P.scan_begin = p + L;
       have_sos = true;
     }
@@ -743,6 +816,11 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
     } else if (P.cid[0] == 82 && P.cid[1] == 71 && P.cid[2] == 66) {
       unsupported("RGB components");
     }
+  }
+  if (P.take_sof2 && P.sof == 0xC2) {   // the scans are jpg_prog_parse's
+    P.scan_end = -1;
+    P.supported = P.why.empty();
+    return 0;
   }
   if (P.ns != P.ncomp && (P.ncomp == 1 || P.ncomp == 3)) unsupported("multi-scan sequential");
   if (P.ss != 0 || P.se != 63 || P.ahal != 0) unsupported("non-baseline scan parameters");
@@ -774,50 +852,8 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
   // the entropy-coded data: every 0xFF is stuffing (0xFF00), a restart marker, or the end of the scan
   const int64_t nmcu = P.ncomp == 1 ? vf_cdiv(P.W, 8) * vf_cdiv(P.H, 8)
                                     : vf_cdiv(P.W, 8 * P.hmax) * vf_cdiv(P.H, 8 * P.vmax);
-  int64_t q = P.scan_begin, seg0 = q, drop = 0;
-  int nrst = 0;
   int end_marker = -1;
-  for (;;) {
-    const uint8_t* f = q < n ? (const uint8_t*)memchr(d + q, 0xFF, (size_t)(n - q)) : nullptr;
-    if (!f) {
-      P.scan_end = n;
-      break;
-    }
-    const int64_t i = f - d;
-    int64_t j = i + 1;
-    while (j < n && d[j] == 0xFF) ++j;
-    if (j >= n) {
-      P.scan_end = i;
-      break;
-    }
-    const int c = d[j];
-    if (c == 0) {
-      if (j - i > 1) {
-        // fill bytes before a stuffed 0xFF: libjpeg-turbo's fast path reads them as a marker, its slow path (and
-        // jpeg-6b) skips them, so the file has no one libjpeg result.  No encoder writes them.
-        msg = "0xFF fill bytes inside the entropy-coded data at byte " + std::to_string(i);
-        return 2;
-      }
-      ++drop;
-      P.drops.push_back(j);   // the stuffed 0x00
-      q = j + 1;
-    } else if (c >= 0xD0 && c <= 0xD7) {
-      if (c != 0xD0 + (nrst & 7)) {
-        msg = "restart marker out of sequence";
-        return 2;
-      }
-      ++nrst;
-      P.segs.push_back({seg0, i, i - seg0 - drop});
-      seg0 = j + 1;
-      drop = 0;
-      q = j + 1;
-    } else {
-      P.scan_end = i;
-      end_marker = c;
-      break;
-    }
-  }
-  P.segs.push_back({seg0, P.scan_end, P.scan_end - seg0 - drop});
+  if (int e = jpg_walk(d, n, P.scan_begin, P.segs, P.drops, P.scan_end, end_marker, msg)) return e;
   if (end_marker >= 0 && end_marker != 0xD9) {
     // anything but EOI after the scan: a second scan makes it multi-scan; other markers are skipped
     int64_t r = P.scan_end;
@@ -1034,7 +1070,983 @@ void jpg_pack(const uint8_t* data, const int64_t* offs, int n, int channels, int
   }
 }
 
+// ===================================================================== progressive (SOF2) files: DESIGN.md 5.9
+// The entropy rule of jdphuff.c as four per-block functions (decode_mcu_DC_first, decode_mcu_AC_first,
+// decode_mcu_DC_refine, decode_mcu_AC_refine), host and device alike, and one walker that takes a restart segment
+// through them in order.  The scans of a batch are launched level by level (a scan's level is one more than the highest
+// level among the earlier scans of its file that touch the same component and an overlapping band of coefficients):
+// level 0 is every first scan (Ah = 0), decoded by self-synchronisation, a block per (image, scan, restart segment)
+// (k_jpeg_prog_first); the levels behind are the refinement scans, where one lane walks one (image, scan, restart
+// segment) in order (k_jpeg_prog_scan): what a block's bits mean depends on the coefficients it already has.
+constexpr int kProgMaxScans = 64;
+constexpr int kProgMaxMcuBlocks = 10;   // blocks of an interleaved MCU (libjpeg's D_MAX_BLOCKS_IN_MCU)
+
+struct ProgScan {
+  int32_t img;
+  int32_t ss, se, ah, al;
+  int32_t ns;                  // components
+  int32_t interleaved;         // 1: a unit is an MCU of the frame's grid; 0: a unit is one real block of the one component
+  int32_t nunit, nb;           // units in the scan; blocks per unit
+  int32_t bw, h, v, b0;        // one component: real blocks per row, its sampling, its first block in the MCU
+  int32_t boff[kProgMaxMcuBlocks];    // interleaved: each unit block's place in the frame's MCU ...
+  int32_t bslot[kProgMaxMcuBlocks];   // ... and its component's place in the scan (DC predictor, table)
+  int32_t tab[4];              // per scan component: its table in force at the SOS (DC for Ss = 0, else AC); -1: none
+};
+
+struct ProgSeg {
+  int64_t dst;                 // first byte in `bits` (compacted; 16-byte aligned, 16 bytes of slack behind)
+  int32_t len;                 // compacted bytes
+  int32_t scan;
+  int32_t u0, nu;              // its units
+  int32_t nsub;                // first scans: its subsequences, the first of them
+  int64_t sub0;
+};
+
+// block j of unit u -> its place among the image's blocks (the baseline layout: MCU by MCU)
+VF_HD int64_t prog_block(const JpgImage& im, const ProgScan& sc, int u, int j) {
+  if (sc.interleaved) return (int64_t)u * im.bpm + sc.boff[j];
+  const int by = u / sc.bw, bx = u % sc.bw;
+  return ((int64_t)(by / sc.v) * im.mcux + bx / sc.h) * im.bpm + sc.b0 + (by % sc.v) * sc.h + bx % sc.h;
+}
+
+// Bits of one segment, in order.  Every read is checked against the segment's length first, so p never passes nbits
+// and BitWin's loads stay inside the slack behind the segment.
+struct ProgReader {
+  BitWin bw;
+  uint32_t p, nbits;
+  // one Huffman symbol (0..255), or -ST_BAD / -ST_SHORT
+  VF_HD int symbol(const JpgHuff& t) {
+    int sym = 0;
+    const int l = huff_decode(t, bw.peek(p), sym);
+    if (!l) return -ST_BAD;
+    if (p + (uint32_t)l > nbits) return -ST_SHORT;
+    p += l;
+    return sym;
+  }
+  // n (1..16) bits into v; ST_OK or ST_SHORT
+  VF_HD int bits(int n, uint32_t& v) {
+    if (p + (uint32_t)n > nbits) return ST_SHORT;
+    v = bw.peek(p) >> (32 - n);
+    p += n;
+    return ST_OK;
+  }
+};
+
+VF_HD int prog_dc_first(ProgReader& R, const JpgHuff& t, int al, int& pred, int16_t* blk) {
+  const int s = R.symbol(t);
+  if (s < 0) return -s;
+  if (s > 15) return ST_BAD;
+  uint32_t v = 0;
+  if (s)
+    if (int e = R.bits(s, v)) return e;
+  pred = (int)((uint32_t)pred + (uint32_t)(s ? huff_extend(v, s) : 0));
+  blk[0] = (int16_t)((uint32_t)pred << al);
+  return ST_OK;
+}
+
+VF_HD int prog_dc_refine(ProgReader& R, int al, int16_t* blk) {
+  uint32_t b;
+  if (int e = R.bits(1, b)) return e;
+  if (b) blk[0] = (int16_t)(blk[0] | (1 << al));
+  return ST_OK;
+}
+
+VF_HD int prog_ac_first(ProgReader& R, const JpgHuff& t, int ss, int se, int al, int& eobrun, int16_t* blk) {
+  if (eobrun > 0) {
+    --eobrun;
+    return ST_OK;
+  }
+  for (int k = ss; k <= se;) {
+    const int rs = R.symbol(t);
+    if (rs < 0) return -rs;
+    const int r = rs >> 4, s = rs & 15;
+    uint32_t v = 0;
+    if (s) {
+      k += r;
+      if (k > se) return ST_BAD;
+      if (int e = R.bits(s, v)) return e;
+      blk[natural(k)] = (int16_t)(huff_extend(v, s) * (1 << al));
+      ++k;
+    } else if (r == 15) {
+      k += 16;
+    } else {
+      if (r)
+        if (int e = R.bits(r, v)) return e;
+      eobrun = (1 << r) + (int)v - 1;
+      break;
+    }
+  }
+  return ST_OK;
+}
+
+// one correction bit of an already nonzero coefficient
+VF_HD int prog_refine(ProgReader& R, int p1, int16_t* c) {
+  uint32_t b;
+  if (int e = R.bits(1, b)) return e;
+  const int v = *c;
+  if (b && (v & p1) == 0) *c = (int16_t)(v >= 0 ? v + p1 : v - p1);
+  return ST_OK;
+}
+
+VF_HD int prog_ac_refine(ProgReader& R, const JpgHuff& t, int ss, int se, int al, int& eobrun, int16_t* blk) {
+  const int p1 = 1 << al;
+  int k = ss;
+  if (eobrun == 0) {
+    while (k <= se) {
+      const int rs = R.symbol(t);
+      if (rs < 0) return -rs;
+      int r = rs >> 4, val = 0;
+      const int s = rs & 15;
+      uint32_t v = 0;
+      if (s) {
+        if (s != 1) return ST_BAD;
+        if (int e = R.bits(1, v)) return e;
+        val = v ? p1 : -p1;
+      } else if (r != 15) {
+        if (r)
+          if (int e = R.bits(r, v)) return e;
+        eobrun = (1 << r) + (int)v;
+        break;
+      }
+      for (; k <= se; ++k) {
+        int16_t* c = blk + natural(k);
+        if (*c) {
+          if (int e = prog_refine(R, p1, c)) return e;
+        } else if (--r < 0) {
+          break;
+        }
+      }
+      if (val) {
+        if (k > se) return ST_BAD;
+        blk[natural(k)] = (int16_t)val;
+      }
+      ++k;
+    }
+  }
+  if (eobrun > 0) {
+    for (; k <= se; ++k) {
+      int16_t* c = blk + natural(k);
+      if (*c)
+        if (int e = prog_refine(R, p1, c)) return e;
+    }
+    --eobrun;
+  }
+  return ST_OK;
+}
+
+// One restart segment of one scan, its units u0 .. u0 + nu in order; coef: the image's first coefficient.  The
+// predictors and the EOB run start at 0 (process_restart); a run that outlasts the segment's blocks is bad data.
+__host__ __device__ inline int prog_decode_segment(const JpgImage& im, const ProgScan& sc, const JpgHuff* huff, const uint32_t* bits,
+                                                   uint32_t nbits, int u0, int nu, int16_t* coef) {
+  ProgReader R{{bits, 0, 0, 0}, 0, nbits};
+  R.bw.seek(0);
+  int pred[4] = {0, 0, 0, 0};
+  int eobrun = 0;
+  for (int u = u0; u < u0 + nu; ++u)
+    for (int j = 0; j < sc.nb; ++j) {
+      int16_t* blk = coef + 64 * prog_block(im, sc, u, j);
+      const int slot = sc.interleaved ? sc.bslot[j] : 0;
+      int e;
+      if (sc.ss == 0) e = sc.ah == 0 ? prog_dc_first(R, huff[sc.tab[slot]], sc.al, pred[slot], blk) : prog_dc_refine(R, sc.al, blk);
+      else if (sc.ah == 0) e = prog_ac_first(R, huff[sc.tab[0]], sc.ss, sc.se, sc.al, eobrun, blk);
+      else e = prog_ac_refine(R, huff[sc.tab[0]], sc.ss, sc.se, sc.al, eobrun, blk);
+      if (e != ST_OK) return e;
+    }
+  return eobrun > 0 ? (int)ST_BAD : (int)ST_OK;
+}
+
+// ---- first scans (Ah = 0) by self-synchronisation: k_jpeg_huffman's scheme.  A lane's state is (p, j, k): the bit it is
+// at, the block of the unit it is in (interleaved DC scans) and the zig-zag index (AC scans; Ss at the start of a block).
+// An EOB run consumes no bits beyond its symbol, so it is taken whole where the symbol is read: it advances the block
+// count by its length and never enters the state.
+// Decode from (p, j, k) while the next symbol starts before pend.  g: the ordinal, among the segment's `total` blocks,
+// of the block the lane is in (the exclusive scan of the counts; 0 when counting).  WRITE: store the coefficients (a DC
+// value as its difference) and stop once `total` blocks are done; else count: g comes back as the blocks advanced,
+// capped at total + 1.  Returns LANE_*.
+template <bool WRITE>
+__host__ __device__ int prog_first_lane(const JpgImage& im, const ProgScan& sc, const JpgHuff* tabs, BitWin& bw, uint32_t nbits, uint32_t& p,
+                                        int& j, int& k, uint32_t pend, int64_t& g, int64_t total, int u0, int16_t* coef) {
+  const bool dc = sc.ss == 0;
+  bw.seek(p);
+  for (;;) {
+    if (!WRITE && g > total) g = total + 1;
+    if (WRITE && (dc || k == sc.ss) && g >= total) return g > total ? LANE_BAD : LANE_DONE;
+    if (p >= pend) return LANE_END;
+    const uint32_t w = bw.peek(p);
+    int sym;
+    if (dc) {
+      const int l = huff_decode(tabs[sc.bslot[j]], w, sym);
+      if (!l || sym > 15) return LANE_BAD;
+      const int s = sym;
+      if (p + (uint32_t)(l + s) > nbits) return LANE_SHORT;
+      if (WRITE) coef[64 * prog_block(im, sc, u0 + (int)(g / sc.nb), (int)(g % sc.nb))] = (int16_t)(s ? huff_extend((w << l) >> (32 - s), s) : 0);
+      p += l + s;
+      ++g;
+      if (++j == sc.nb) j = 0;
+      continue;
+    }
+    const int l = huff_decode(tabs[0], w, sym);
+    if (!l) return LANE_BAD;
+    const int r = sym >> 4, s = sym & 15;
+    if (s) {
+      if (p + (uint32_t)(l + s) > nbits) return LANE_SHORT;
+      k += r;
+      if (k > sc.se) return LANE_BAD;
+      if (WRITE) {
+        if (g >= total) return LANE_BAD;   // a lane that starts inside a block the scan does not have
+        coef[64 * prog_block(im, sc, u0 + (int)g, 0) + natural(k)] = (int16_t)(huff_extend((w << l) >> (32 - s), s) * (1 << sc.al));
+      }
+      ++k;
+      p += l + s;
+    } else if (r == 15) {
+      if (p + (uint32_t)l > nbits) return LANE_SHORT;
+      k += 16;
+      p += l;
+    } else {
+      if (p + (uint32_t)(l + r) > nbits) return LANE_SHORT;
+      g += (1 << r) + (int)(r ? (w << l) >> (32 - r) : 0);   // this block and the run's others
+      p += l + r;
+      k = sc.ss;
+      continue;
+    }
+    if (k > sc.se) {
+      ++g;
+      k = sc.ss;
+    }
+  }
+}
+
+// the DC values of one unit's blocks: differences -> predictions, point-transformed.  run: each scan component's
+// predictor before the unit
+VF_HD void prog_dc_unit(const JpgImage& im, const ProgScan& sc, int u, unsigned* run, int16_t* coef) {
+  for (int b = 0; b < sc.nb; ++b) {
+    int16_t* dc = coef + 64 * prog_block(im, sc, u, b);
+    run[sc.bslot[b]] += (unsigned)(int)*dc;
+    *dc = (int16_t)(run[sc.bslot[b]] << sc.al);
+  }
+}
+
+// one block per (image, first scan, restart segment)
+__global__ __launch_bounds__(kHuffThreads) void k_jpeg_prog_first(const JpgBatch B, const ProgScan* scans, const ProgSeg* segs) {
+  __shared__ JpgHuff tabs[4];
+  __shared__ unsigned long long s_w[kHuffThreads / 64];
+  __shared__ int changed;
+  const int t = threadIdx.x;
+  const ProgSeg sg = segs[blockIdx.x];
+  const ProgScan& sc = scans[sg.scan];
+  const JpgImage& im = B.img[sc.img];
+  for (int c = 0; c < sc.ns; ++c) {
+    const uint32_t* src = (const uint32_t*)(B.huff + sc.tab[c]);
+    uint32_t* dst = (uint32_t*)(tabs + c);
+    for (int i = t; i < (int)(sizeof(JpgHuff) / 4); i += kHuffThreads) dst[i] = src[i];
+  }
+  __syncthreads();
+  const uint32_t nbits = 8u * (uint32_t)sg.len;
+  const uint32_t sb = (uint32_t)B.sub_bits;
+  const int nsub = sg.nsub;
+  uint64_t* E = B.E + sg.sub0;
+  uint64_t* X = B.X + sg.sub0;
+  int32_t* Nb = B.Nb + sg.sub0;
+  uint8_t* D = B.D + sg.sub0;
+  const int64_t total = (int64_t)sg.nu * sc.nb;
+  int16_t* coef = B.coef + im.coef_base * 64;
+  BitWin bw{(const uint32_t*)(B.bits + sg.dst), 0, 0, 0};
+
+  auto run = [&](int i, uint64_t e) {
+    uint32_t p = (uint32_t)(e >> 16);
+    int j = (int)((e >> 8) & 0xff), k = (int)(e & 0xff);
+    int64_t g = 0;
+    const uint32_t pend = min(nbits, (uint32_t)(i + 1) * sb);
+    const int r = prog_first_lane<false>(im, sc, tabs, bw, nbits, p, j, k, pend, g, total, sg.u0, nullptr);
+    X[i] = r == LANE_END ? st_pack(p, j, k) : kDead;
+    Nb[i] = (int32_t)g;
+  };
+  for (int i = t; i < nsub; i += kHuffThreads) {
+    const uint64_t e = st_pack((uint32_t)i * sb, 0, sc.ss);
+    E[i] = e;
+    run(i, e);
+  }
+  // synchronise, as k_jpeg_huffman does
+  int nround = 0;
+  for (;;) {
+    if (t == 0) changed = 0;
+    __syncthreads();
+    for (int i = t; i < nsub; i += kHuffThreads) {
+      D[i] = 0;
+      if (i == 0) continue;
+      const uint64_t x = X[i - 1];
+      if (x != E[i] && x != kDead) {
+        E[i] = x;
+        D[i] = 1;
+        changed = 1;
+      }
+    }
+    __syncthreads();
+    if (!changed) break;
+    ++nround;
+    for (int i = t; i < nsub; i += kHuffThreads)
+      if (D[i]) run(i, E[i]);
+    __syncthreads();
+  }
+  if (t == 0) atomicMax(B.rounds, nround);
+  // exclusive scan of the blocks each lane advances -> the block each lane starts in (capped: total + 1 is "beyond")
+  {
+    unsigned long long carry = 0;
+    for (int c = 0; c < nsub; c += kHuffThreads) {
+      const int i = c + t;
+      const unsigned long long v = i < nsub ? (unsigned long long)Nb[i] : 0ull;
+      unsigned long long tot;
+      const unsigned long long pre = vf_block_excl_scan<unsigned long long, kHuffThreads>(v, s_w, tot);
+      if (i < nsub) Nb[i] = (int32_t)min(carry + pre, (unsigned long long)total + 1);
+      carry += tot;
+    }
+  }
+  __syncthreads();
+  int err = ST_OK;
+  for (int i = t; i < nsub; i += kHuffThreads) {
+    const uint64_t e = E[i];
+    int64_t g = Nb[i];
+    if (i > 0 && X[i - 1] == kDead) {
+      if (g < total) err = ST_BAD;
+      continue;
+    }
+    uint32_t p = (uint32_t)(e >> 16);
+    int j = (int)((e >> 8) & 0xff), k = (int)(e & 0xff);
+    const uint32_t pend = min(nbits, (uint32_t)(i + 1) * sb);
+    const int r = prog_first_lane<true>(im, sc, tabs, bw, nbits, p, j, k, pend, g, total, sg.u0, coef);
+    if (r == LANE_BAD) err = ST_BAD;
+    else if (r == LANE_SHORT || (r == LANE_END && i == nsub - 1)) err = max(err, (int)ST_SHORT);
+  }
+  if (err != ST_OK) atomicMax(B.status + sc.img, err);
+  if (sc.ss != 0) return;
+  __syncthreads();
+  // DC prediction: per scan component, a running sum over the segment's units
+  unsigned carry[4] = {0, 0, 0, 0};
+  unsigned* s_u = (unsigned*)s_w;
+  for (int c = 0; c < sg.nu; c += kHuffThreads) {
+    const int m = c + t;
+    unsigned sum[4] = {0, 0, 0, 0};
+    if (m < sg.nu)
+      for (int b = 0; b < sc.nb; ++b) sum[sc.bslot[b]] += (unsigned)(int)coef[64 * prog_block(im, sc, sg.u0 + m, b)];
+    unsigned pre[4];
+    for (int ci = 0; ci < 4; ++ci) {
+      unsigned tot;
+      pre[ci] = carry[ci] + vf_block_excl_scan<unsigned, kHuffThreads>(sum[ci], s_u, tot);
+      carry[ci] += tot;
+    }
+    if (m < sg.nu) prog_dc_unit(im, sc, sg.u0 + m, pre, coef);
+  }
+}
+
+// the same on the host, lane after lane: what vf_jpeg_prog_coefficients_host runs the first scans through
+inline int prog_first_segment_host(const JpgImage& im, const ProgScan& sc, const JpgHuff* huff, const uint32_t* bits, int len, int sub_bytes,
+                                   int u0, int nu, int16_t* coef) {
+  JpgHuff tabs[4];
+  for (int c = 0; c < sc.ns; ++c) tabs[c] = huff[sc.tab[c]];
+  const uint32_t nbits = 8u * (uint32_t)len, sb = 8u * (uint32_t)sub_bytes;
+  const int nsub = (int)std::max<int64_t>(1, vf_cdiv(len, sub_bytes));
+  const int64_t total = (int64_t)nu * sc.nb;
+  std::vector<uint64_t> E(nsub), X(nsub);
+  std::vector<int64_t> Nb(nsub);
+  BitWin bw{bits, 0, 0, 0};
+  auto state = [](uint32_t p, int j, int k) { return ((uint64_t)p << 16) | ((uint64_t)j << 8) | (uint64_t)k; };
+  auto run = [&](int i) {
+    uint32_t p = (uint32_t)(E[i] >> 16);
+    int j = (int)((E[i] >> 8) & 0xff), k = (int)(E[i] & 0xff);
+    int64_t g = 0;
+    const int r = prog_first_lane<false>(im, sc, tabs, bw, nbits, p, j, k, std::min(nbits, (uint32_t)(i + 1) * sb), g, total, u0, nullptr);
+    X[i] = r == LANE_END ? state(p, j, k) : kDead;
+    Nb[i] = g;
+  };
+  for (int i = 0; i < nsub; ++i) {
+    E[i] = state((uint32_t)i * sb, 0, sc.ss);
+    run(i);
+  }
+  for (bool changed = true; changed;) {
+    changed = false;
+    std::vector<int> again;
+    for (int i = 1; i < nsub; ++i)
+      if (X[i - 1] != E[i] && X[i - 1] != kDead) {
+        E[i] = X[i - 1];
+        again.push_back(i);
+      }
+    for (int i : again) run(i);   // after all the comparisons of the round, as the barrier has it
+    changed = !again.empty();
+  }
+  int64_t at = 0;
+  for (int i = 0; i < nsub; ++i) {
+    const int64_t v = Nb[i];
+    Nb[i] = std::min(at, total + 1);
+    at += v;
+  }
+  int err = ST_OK;
+  for (int i = 0; i < nsub; ++i) {
+    int64_t g = Nb[i];
+    if (i > 0 && X[i - 1] == kDead) {
+      if (g < total) err = ST_BAD;
+      continue;
+    }
+    uint32_t p = (uint32_t)(E[i] >> 16);
+    int j = (int)((E[i] >> 8) & 0xff), k = (int)(E[i] & 0xff);
+    const int r = prog_first_lane<true>(im, sc, tabs, bw, nbits, p, j, k, std::min(nbits, (uint32_t)(i + 1) * sb), g, total, u0, coef);
+    if (r == LANE_BAD) err = ST_BAD;
+    else if (r == LANE_SHORT || (r == LANE_END && i == nsub - 1)) err = std::max(err, (int)ST_SHORT);
+  }
+  if (sc.ss == 0) {
+    unsigned pred[4] = {0, 0, 0, 0};
+    for (int u = u0; u < u0 + nu; ++u) prog_dc_unit(im, sc, u, pred, coef);
+  }
+  return err;
+}
+
+// one lane per (image, scan, restart segment) of one level
+__global__ void k_jpeg_prog_scan(const JpgBatch B, const ProgScan* scans, const ProgSeg* segs, int first, int count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const ProgSeg sg = segs[first + i];
+  const ProgScan& sc = scans[sg.scan];
+  const JpgImage& im = B.img[sc.img];
+  const int e = prog_decode_segment(im, sc, B.huff, (const uint32_t*)(B.bits + sg.dst), 8u * (uint32_t)sg.len, sg.u0, sg.nu,
+                                    B.coef + im.coef_base * 64);
+  if (e != ST_OK) atomicMax(B.status + sc.img, e);
+}
+
+// ---- host side
+struct ProgScanHost {
+  int ns = 0, scomp[4] = {}, ss = 0, se = 0, ah = 0, al = 0, ri = 0, level = 0;
+  int tab[4] = {-1, -1, -1, -1};   // per scan component: its table among ProgParsed::tabs
+  int64_t begin = 0, end = 0, nunit = 0;
+  std::vector<JpgParsed::Seg> segs;
+  std::vector<int64_t> drops;
+};
+
+struct ProgParsed {
+  JpgParsed P;                 // the frame: geometry, sampling, and the table state as the parse goes
+  std::vector<ProgScanHost> scans;
+  std::vector<RawHuff> tabs;   // every table a scan uses, as it stood at that SOS
+  uint16_t q[3][64] = {};      // per component, latched at its first scan (jdinput.c latch_quant_tables)
+  int nlevel = 0;
+  bool gray() const { return P.ncomp == 1; }
+  int h(int c) const { return gray() ? 1 : P.hf[c]; }
+  int v(int c) const { return gray() ? 1 : P.vf[c]; }
+  int hmax() const { return gray() ? 1 : P.hmax; }
+  int vmax() const { return gray() ? 1 : P.vmax; }
+  int64_t mcux() const { return vf_cdiv(P.W, 8 * hmax()); }
+  int64_t mcuy() const { return vf_cdiv(P.H, 8 * vmax()); }
+  int bpm() const { return gray() ? 1 : P.hf[0] * P.vf[0] + 2; }
+  int64_t nblocks() const { return mcux() * mcuy() * bpm(); }
+};
+
+// 0: parsed (P.supported / P.why as jpg_parse); else malformed (msg).  Walks every scan.
+int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg) {
+  JpgParsed& P = G.P;
+  P.take_sof2 = true;
+  if (int e = jpg_parse(d, n, P, msg, false)) return e;
+  P.supported = false;
+  if (P.sof != 0xC2 && P.why.empty()) P.why = "not progressive";
+  if (!P.why.empty()) return 0;
+  int cov[3][64];              // the Al each coefficient was last coded at; -1: not yet
+  for (auto& c : cov)
+    for (int& k : c) k = -1;
+  bool latched[3] = {false, false, false};
+  int dc_at[4] = {-1, -1, -1, -1}, ac_at[4] = {-1, -1, -1, -1};   // the slots' places in G.tabs, -1 after a DHT
+  for (;;) {
+    // the scan whose SOS jpg_sos left in P
+    if ((int)G.scans.size() == kProgMaxScans) {
+      P.why = "more than " + std::to_string(kProgMaxScans) + " scans";
+      return 0;
+    }
+    const std::string at = "scan " + std::to_string(G.scans.size()) + ": ";
+    ProgScanHost sc;
+    sc.ns = P.ns;
+    sc.ss = P.ss;
+    sc.se = P.se;
+    sc.ah = P.ahal >> 4;
+    sc.al = P.ahal & 15;
+    sc.ri = P.ri;
+    sc.begin = P.scan_begin;
+    bool bad = sc.ss > sc.se || sc.se > 63 || (sc.ss == 0 && sc.se != 0) || (sc.ss > 0 && sc.ns != 1) || sc.al > 13 ||
+               (sc.ah != 0 && sc.al != sc.ah - 1) || sc.ns > P.ncomp;
+    if (bad) {   // jdphuff.c start_pass_phuff_decoder: JERR_BAD_PROGRESSION
+      msg = at + "bad progression parameters Ss=" + std::to_string(sc.ss) + " Se=" + std::to_string(sc.se) +
+            " Ah=" + std::to_string(sc.ah) + " Al=" + std::to_string(sc.al) + " with " + std::to_string(sc.ns) + " components";
+      return 2;
+    }
+    for (int i = 0; i < sc.ns; ++i) {
+      sc.scomp[i] = P.scomp[i];
+      if (sc.ss == 0 && sc.ah != 0) continue;   // DC refinement reads raw bits
+      const bool dc = sc.ss == 0;
+      const int slot = dc ? P.td[i] : P.ta[i];
+      const RawHuff* h = slot <= 3 ? (dc ? &P.hdc[slot] : &P.hac[slot]) : nullptr;
+      if (!h || !h->present) {
+        msg = at + "names " + (dc ? "DC" : "AC") + " Huffman table " + std::to_string(slot) + ", which no DHT has defined";
+        return 2;
+      }
+      if (!h->fits) {
+        msg = at + "bad Huffman table: its code counts overflow the code lengths";
+        return 2;
+      }
+      if (dc)
+        for (int v = 0; v < h->nval; ++v)
+          if (h->val[v] > 15 && P.why.empty()) P.why = "DC Huffman symbol above 15";
+      int& where = dc ? dc_at[slot] : ac_at[slot];
+      if (where < 0) {
+        where = (int)G.tabs.size();
+        G.tabs.push_back(*h);
+      }
+      sc.tab[i] = where;
+    }
+    // orderly: a first scan covers new ground, a refinement follows the Al before it, AC comes after the DC
+    for (int i = 0; i < sc.ns && P.why.empty(); ++i) {
+      const int c = sc.scomp[i];
+      if (sc.ss > 0 && cov[c][0] < 0) P.why = "progression out of order";
+      for (int k = sc.ss; k <= sc.se; ++k)
+        if (sc.ah == 0 ? cov[c][k] >= 0 : cov[c][k] != sc.ah) P.why = "progression out of order";
+      for (int k = sc.ss; k <= sc.se; ++k) cov[c][k] = sc.al;
+      if (!latched[c]) {
+        if (P.tq[c] > 3 || !P.qt_ok[P.tq[c]]) P.why = "missing quantisation table";
+        else memcpy(G.q[c], P.qt[P.tq[c]], sizeof(G.q[c]));
+        latched[c] = true;
+      }
+    }
+    if (!P.why.empty()) return 0;
+    if (sc.ns > 1) {
+      sc.nunit = G.mcux() * G.mcuy();
+      int nb = 0;
+      for (int i = 0; i < sc.ns; ++i) nb += G.h(sc.scomp[i]) * G.v(sc.scomp[i]);
+      if (nb > kProgMaxMcuBlocks) {
+        msg = at + "more than 10 blocks in an MCU";
+        return 2;
+      }
+    } else {
+      const int c = sc.scomp[0];
+      sc.nunit = vf_cdiv(vf_cdiv((int64_t)P.W * G.h(c), G.hmax()), 8) * vf_cdiv(vf_cdiv((int64_t)P.H * G.v(c), G.vmax()), 8);
+    }
+    for (size_t t = 0; t < G.scans.size(); ++t) {
+      const ProgScanHost& o = G.scans[t];
+      bool shares = false;
+      for (int i = 0; i < sc.ns; ++i)
+        for (int j = 0; j < o.ns; ++j) shares |= sc.scomp[i] == o.scomp[j];
+      if (shares && o.ss <= sc.se && sc.ss <= o.se) sc.level = std::max(sc.level, o.level + 1);
+    }
+    G.nlevel = std::max(G.nlevel, sc.level + 1);
+    int end_marker = -1;
+    if (int e = jpg_walk(d, n, sc.begin, sc.segs, sc.drops, sc.end, end_marker, msg)) {
+      msg = at + msg;
+      return e;
+    }
+    const int64_t want = sc.ri > 0 ? vf_cdiv(sc.nunit, sc.ri) : 1;
+    if ((int64_t)sc.segs.size() != want) {
+      msg = at + "found " + std::to_string(sc.segs.size()) + " restart segments, the restart interval gives " + std::to_string(want);
+      return 2;
+    }
+    for (const auto& sg : sc.segs)
+      if (sg.end - sg.begin > (int64_t)1 << 28) P.why = "a restart segment above 256 MiB";
+    int64_t p = sc.end;
+    G.scans.push_back(std::move(sc));
+    if (!P.why.empty()) return 0;
+    // the markers up to the next SOS or EOI; data that just stops ends the file (libjpeg inserts an EOI)
+    bool next = false;
+    while (!next) {
+      if (p >= n || d[p] != 0xFF) break;
+      while (p < n && d[p] == 0xFF) ++p;
+      if (p >= n) break;
+      const int m = d[p++];
+      if (m == 0xD9) break;
+      if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
+      if (p + 2 > n) break;
+      const int L = rd16(d + p);
+      if (L < 2 || p + L > n) {
+        msg = "truncated marker 0x" + std::to_string(m) + " after " + at.substr(0, at.size() - 2);
+        return 2;
+      }
+      const uint8_t* s = d + p + 2;
+      const int sl = L - 2;
+      if (m == 0xC4) {
+        if (int e = jpg_dht(s, sl, P, msg)) return e;
+        for (int t = 0; t < 4; ++t) dc_at[t] = ac_at[t] = -1;
+      } else if (m == 0xDB) {
+        if (int e = jpg_dqt(s, sl, P, msg)) return e;
+      } else if (m == 0xDD) {
+        if (sl < 2) {
+          msg = "truncated DRI";
+          return 2;
+        }
+        P.ri = rd16(s);
+      } else if (m == 0xDA) {
+        if (int e = jpg_sos(s, sl, P, msg)) return e;
+        P.scan_begin = p + L;
+        next = true;
+      } else if (m >= 0xC0 && m <= 0xCF && m != 0xC8 && m != 0xCC) {
+        msg = "more than one SOF marker";
+        return 2;
+      }
+      p += L;
+    }
+    if (!next) break;
+  }
+  for (int c = 0; c < P.ncomp; ++c)
+    for (int k = 0; k < 64; ++k)
+      if (cov[c][k] != 0) P.why = "incomplete progression";
+  P.supported = P.why.empty();
+  return 0;
+}
+
+struct ProgPlan {
+  std::vector<ProgParsed> G;
+  int64_t nscan = 0, nseg = 0, nsub = 0, ntab = 0, nblk = 0, plane_bytes = 0, scan_bytes = 0, bits_bytes = 0, nchunk = 0;
+  int64_t max_blocks = 0, max_pix = 0;
+  std::vector<int64_t> level_segs;   // segments per level
+  size_t o_img = 0, o_scans = 0, o_seg = 0, o_chunk = 0, o_huff = 0, o_scan = 0, stage = 0;
+  size_t o_bits = 0, o_E = 0, o_X = 0, o_N = 0, o_D = 0, o_coef = 0, o_planes = 0, ws = 0;
+};
+
+// sub_bytes: the subsequence size of the first scans' decode (0: none of them is decoded that way)
+int jpg_prog_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes, ProgPlan& L) {
+  VF_REQUIRE(n > 0 && data && offs, "vf_jpeg_prog: empty batch");
+  VF_REQUIRE(sub_bytes == 0 || (sub_bytes >= 8 && sub_bytes <= (1 << 20)), "vf_jpeg_prog: subsequence size %d outside [8, 1 MiB]", sub_bytes);
+  L.G.resize(n);
+  for (int i = 0; i < n; ++i) {
+    std::string msg;
+    VF_REQUIRE(offs[i + 1] >= offs[i], "vf_jpeg_prog: offsets decrease at image %d", i);
+    ProgParsed& G = L.G[i];
+    if (jpg_prog_parse(data + offs[i], offs[i + 1] - offs[i], G, msg)) {
+      vf_set_error("vf_jpeg_prog: image %d: %s", i, msg.c_str());
+      return 2;
+    }
+    if (!G.P.supported) {
+      vf_set_error("vf_jpeg_prog: image %d: unsupported: %s", i, G.P.why.c_str());
+      return 3;
+    }
+    L.nblk += G.nblocks();
+    L.max_blocks = std::max(L.max_blocks, G.nblocks());
+    L.max_pix = std::max(L.max_pix, (int64_t)G.P.W * G.P.H);
+    L.plane_bytes = (int64_t)vf_up256((size_t)(L.plane_bytes + G.nblocks() * 64));
+    L.nscan += (int64_t)G.scans.size();
+    L.ntab += (int64_t)G.tabs.size();
+    if ((int)L.level_segs.size() < G.nlevel) L.level_segs.resize(G.nlevel, 0);
+    for (const auto& sc : G.scans) {
+      L.nseg += (int64_t)sc.segs.size();
+      L.level_segs[sc.level] += (int64_t)sc.segs.size();
+      for (const auto& s : sc.segs) {
+        L.bits_bytes += seg_bits_bytes(s.len);
+        L.nchunk += vf_cdiv(s.end - s.begin, kChunk);
+        if (sc.level == 0 && sub_bytes) L.nsub += std::max<int64_t>(1, vf_cdiv(s.len, sub_bytes));
+      }
+      L.scan_bytes += (int64_t)vf_up256((size_t)(sc.end - sc.begin) + 8);
+    }
+  }
+  VF_REQUIRE(L.nseg < ((int64_t)1 << 31) && L.nchunk < ((int64_t)1 << 31), "vf_jpeg_prog: more than 2^31 restart segments or chunks");
+  VfCarve ws;
+  L.o_img = ws.take(sizeof(JpgImage) * n);
+  L.o_scans = ws.take(sizeof(ProgScan) * L.nscan);
+  L.o_seg = ws.take(sizeof(ProgSeg) * L.nseg);
+  L.o_chunk = ws.take(sizeof(JpgChunk) * L.nchunk);
+  L.o_huff = ws.take(sizeof(JpgHuff) * L.ntab);
+  L.o_scan = ws.take((size_t)L.scan_bytes);
+  L.stage = ws.at;
+  L.o_bits = ws.take((size_t)L.bits_bytes);
+  L.o_E = ws.take(8 * (size_t)L.nsub);
+  L.o_X = ws.take(8 * (size_t)L.nsub);
+  L.o_N = ws.take(4 * (size_t)L.nsub);
+  L.o_D = ws.take((size_t)L.nsub);
+  L.o_coef = ws.take(128 * (size_t)L.nblk);
+  L.o_planes = ws.take((size_t)L.plane_bytes);
+  L.ws = ws.at;
+  return 0;
+}
+
+// fill the staging buffer; the segments lie level by level
+void jpg_prog_pack(const uint8_t* data, const int64_t* offs, int n, int channels, int sub_bytes, const int64_t* out_offs, const ProgPlan& L,
+                   uint8_t* st) {
+  JpgImage* imgs = (JpgImage*)(st + L.o_img);
+  ProgScan* scans = (ProgScan*)(st + L.o_scans);
+  ProgSeg* segs = (ProgSeg*)(st + L.o_seg);
+  JpgChunk* chunks = (JpgChunk*)(st + L.o_chunk);
+  JpgHuff* huffs = (JpgHuff*)(st + L.o_huff);
+  uint8_t* scan = st + L.o_scan;
+  std::vector<int64_t> at(L.level_segs.size() + 1, 0);   // next free segment of each level
+  for (size_t l = 0; l < L.level_segs.size(); ++l) at[l + 1] = at[l] + L.level_segs[l];
+  int64_t coef = 0, plane = 0, sc_at = 0, dst = 0, sub = 0;
+  int si = 0, ci = 0, ti = 0;
+  for (int i = 0; i < n; ++i) {
+    const ProgParsed& G = L.G[i];
+    const JpgParsed& P = G.P;
+    const uint8_t* d = data + offs[i];
+    JpgImage& im = imgs[i];
+    memset(&im, 0, sizeof(im));
+    im.W = P.W;
+    im.H = P.H;
+    im.ncomp = P.ncomp;
+    im.channels = channels;
+    im.hs = G.hmax();
+    im.vs = G.vmax();
+    im.mcux = (int)G.mcux();
+    im.mcuy = (int)G.mcuy();
+    int cb0[3] = {0, 0, 0};   // each component's first block in the MCU (frame order)
+    int b = 0;
+    for (int c = 0; c < P.ncomp; ++c) {
+      cb0[c] = b;
+      for (int y = 0; y < G.v(c); ++y)
+        for (int x = 0; x < G.h(c); ++x, ++b) {
+          im.bcomp[b] = c;
+          im.bx[b] = x;
+          im.by[b] = y;
+        }
+    }
+    im.bpm = b;
+    im.nblocks = (int)G.nblocks();
+    im.coef_base = coef;
+    coef += im.nblocks;
+    for (int c = 0; c < P.ncomp; ++c) {
+      im.pw[c] = im.mcux * 8 * G.h(c);
+      im.ph[c] = im.mcuy * 8 * G.v(c);
+      im.cw[c] = (int)vf_cdiv((int64_t)P.W * G.h(c), G.hmax());
+      im.ch[c] = (int)vf_cdiv((int64_t)P.H * G.v(c), G.vmax());
+      im.plane_base[c] = plane;
+      plane += (int64_t)im.pw[c] * im.ph[c];
+      for (int k = 0; k < 64; ++k) im.q[c][k] = G.q[c][k];
+    }
+    plane = (int64_t)vf_up256((size_t)plane);
+    im.out_off = out_offs[i];
+    for (const RawHuff& r : G.tabs) build_huff(r, huffs[ti + (&r - G.tabs.data())]);
+    for (const ProgScanHost& h : G.scans) {
+      ProgScan& s = scans[si];
+      memset(&s, 0, sizeof(s));
+      s.img = i;
+      s.ns = h.ns;
+      s.ss = h.ss;
+      s.se = h.se;
+      s.ah = h.ah;
+      s.al = h.al;
+      s.nunit = (int32_t)h.nunit;
+      s.interleaved = h.ns > 1;
+      s.nb = 0;
+      for (int j = 0; j < h.ns; ++j) {
+        const int c = h.scomp[j];
+        s.tab[j] = h.tab[j] < 0 ? -1 : ti + h.tab[j];
+        for (int y = 0; y < G.v(c); ++y)
+          for (int x = 0; x < G.h(c); ++x, ++s.nb) {
+            s.boff[s.nb] = cb0[c] + y * G.h(c) + x;
+            s.bslot[s.nb] = j;
+          }
+      }
+      if (!s.interleaved) {
+        const int c = h.scomp[0];
+        s.nb = 1;
+        s.h = G.h(c);
+        s.v = G.v(c);
+        s.b0 = cb0[c];
+        s.bw = (int32_t)vf_cdiv(vf_cdiv((int64_t)P.W * s.h, G.hmax()), 8);
+      }
+      const int64_t nbytes = h.end - h.begin;
+      memcpy(scan + sc_at, d + h.begin, (size_t)nbytes);
+      memset(scan + sc_at + nbytes, 0, vf_up256((size_t)nbytes + 8) - (size_t)nbytes);
+      for (size_t k = 0; k < h.segs.size(); ++k) {
+        const auto& g = h.segs[k];
+        ProgSeg& o = segs[at[h.level]++];
+        size_t di = std::lower_bound(h.drops.begin(), h.drops.end(), g.begin) - h.drops.begin();
+        int64_t kept = 0;
+        for (int64_t c0 = g.begin; c0 < g.end; c0 += kChunk, ++ci) {
+          const int64_t c1 = std::min<int64_t>(c0 + kChunk, g.end);
+          int64_t nd = 0;
+          for (; di < h.drops.size() && h.drops[di] < c1; ++di) ++nd;
+          JpgChunk& ck = chunks[ci];
+          ck.src = sc_at + (c0 - h.begin);
+          ck.dst = dst + kept;
+          ck.n = (int32_t)(c1 - c0);
+          ck.keep = (int32_t)(c1 - c0 - nd);
+          ck.lo = c0 > g.begin;
+          kept += ck.keep;
+        }
+        o.dst = dst;
+        o.len = (int32_t)g.len;
+        o.scan = si;
+        o.u0 = (int32_t)(h.ri > 0 ? (int64_t)k * h.ri : 0);
+        o.nu = (int32_t)(h.ri > 0 ? std::min<int64_t>(h.ri, h.nunit - o.u0) : h.nunit);
+        o.nsub = h.level == 0 && sub_bytes ? (int32_t)std::max<int64_t>(1, vf_cdiv(g.len, sub_bytes)) : 0;
+        o.sub0 = sub;
+        sub += o.nsub;
+        dst += seg_bits_bytes(g.len);
+      }
+      sc_at += (int64_t)vf_up256((size_t)nbytes + 8);
+      ++si;
+    }
+    ti += (int)G.tabs.size();
+  }
+}
+
+// k_jpeg_unstuff's rule for one chunk, on the host
+void unstuff_host(const JpgChunk& ck, const uint8_t* scan, uint8_t* bits) {
+  const uint8_t* in = scan + ck.src;
+  uint8_t* out = bits + ck.dst;
+  int pos = 0;
+  for (int i = 0; i < ck.n; ++i) {
+    const bool keep = !(in[i] == 0 && (i > 0 || ck.lo) && in[i - 1] == 0xFF);
+    if (keep && pos < ck.keep) out[pos] = in[i];
+    pos += keep;
+  }
+}
+
 }  // namespace
+
+VF_API int vf_jpeg_scans_inspect(const unsigned char* data, size_t len, int64_t* info, int64_t* scans, int scan_cap, char* reason,
+                                 int reason_cap) {
+  VF_REQUIRE(data && info, "vf_jpeg_scans_inspect: NULL argument");
+  ProgParsed G;
+  std::string msg;
+  if (int rc = jpg_prog_parse(data, (int64_t)len, G, msg)) {
+    vf_set_error("vf_jpeg_scans_inspect: %s", msg.c_str());
+    return rc;
+  }
+  const JpgParsed& P = G.P;
+  const bool geo = P.ncomp == 1 || P.ncomp == 3;
+  info[0] = P.W;
+  info[1] = P.H;
+  info[2] = P.ncomp;
+  info[3] = P.ncomp == 1 ? 1 : P.hf[0];
+  info[4] = P.ncomp == 1 ? 1 : P.vf[0];
+  info[5] = (int64_t)G.scans.size();
+  info[6] = P.supported ? 1 : 0;
+  info[7] = P.sof;
+  info[8] = P.prec;
+  info[9] = G.nlevel;
+  info[10] = geo && P.W > 0 && P.H > 0 ? G.nblocks() : 0;
+  info[11] = geo ? G.bpm() : 0;
+  for (int i = 0; scans && i < scan_cap && i < (int)G.scans.size(); ++i) {
+    const ProgScanHost& s = G.scans[i];
+    int64_t* r = scans + 16 * i;
+    r[0] = s.ns;
+    for (int j = 0; j < 4; ++j) r[1 + j] = j < s.ns ? s.scomp[j] : -1;
+    r[5] = s.ss;
+    r[6] = s.se;
+    r[7] = s.ah;
+    r[8] = s.al;
+    r[9] = s.ri;
+    r[10] = s.begin;
+    r[11] = s.end;
+    r[12] = (int64_t)s.segs.size();
+    r[13] = s.level;
+    r[14] = s.nunit;
+    r[15] = 0;
+  }
+  if (reason && reason_cap > 0) snprintf(reason, (size_t)reason_cap, "%s", P.why.c_str());
+  return 0;
+}
+
+VF_API int vf_jpeg_prog_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
+                                        size_t* stage_bytes) {
+  VF_REQUIRE(subseq_bytes != 0, "vf_jpeg_prog: subsequence size 0 outside [8, 1 MiB]");
+  ProgPlan L;
+  if (int e = jpg_prog_plan(data, offs, n, subseq_bytes, L)) return e;
+  if (ws_bytes) *ws_bytes = L.ws;
+  if (stage_bytes) *stage_bytes = L.stage;
+  return 0;
+}
+
+VF_API int vf_jpeg_prog_coefficients_host(const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef, size_t coef_blocks,
+                                          int32_t* status) {
+  VF_REQUIRE(data && coef && status, "vf_jpeg_prog_coefficients_host: NULL argument");
+  const int64_t offs[2] = {0, (int64_t)len}, out_offs[2] = {0, 0};
+  ProgPlan L;
+  if (int e = jpg_prog_plan(data, offs, 1, subseq_bytes, L)) return e;
+  VF_REQUIRE((int64_t)coef_blocks >= L.nblk, "vf_jpeg_prog_coefficients_host: room for %zu blocks, the file has %lld", coef_blocks,
+             (long long)L.nblk);
+  std::vector<uint64_t> stage(L.stage / 8 + 1), bits((size_t)L.bits_bytes / 8 + 1, 0);
+  uint8_t* st = (uint8_t*)stage.data();
+  jpg_prog_pack(data, offs, 1, 3, subseq_bytes, out_offs, L, st);
+  const JpgChunk* chunks = (const JpgChunk*)(st + L.o_chunk);
+  for (int64_t c = 0; c < L.nchunk; ++c) unstuff_host(chunks[c], st + L.o_scan, (uint8_t*)bits.data());
+  memset(coef, 0, 128 * (size_t)L.nblk);
+  const JpgImage* im = (const JpgImage*)(st + L.o_img);
+  const ProgScan* scans = (const ProgScan*)(st + L.o_scans);
+  const ProgSeg* segs = (const ProgSeg*)(st + L.o_seg);
+  *status = VF_JPEG_OK;
+  for (int64_t s = 0; s < L.nseg; ++s) {   // level by level, as the device runs them
+    const ProgSeg& sg = segs[s];
+    const ProgScan& sc = scans[sg.scan];
+    const JpgHuff* huff = (const JpgHuff*)(st + L.o_huff);
+    const uint32_t* b = (const uint32_t*)((uint8_t*)bits.data() + sg.dst);
+    const int e = sc.ah == 0 && subseq_bytes ? prog_first_segment_host(*im, sc, huff, b, sg.len, subseq_bytes, sg.u0, sg.nu, coef)
+                                             : prog_decode_segment(*im, sc, huff, b, 8u * (uint32_t)sg.len, sg.u0, sg.nu, coef);
+    *status = std::max(*status, e);
+  }
+  return 0;
+}
+
+VF_API int vf_jpeg_prog_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes,
+                               const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
+                               int32_t* status, int32_t* rounds, int32_t* levels) {
+  VF_REQUIRE(channels == 1 || channels == 3, "vf_jpeg_prog_decode: channels %d is not 1 or 3", channels);
+  VF_REQUIRE(out && out_offs && stage && ws && status && rounds, "vf_jpeg_prog_decode: NULL argument");
+  VF_REQUIRE(subseq_bytes != 0, "vf_jpeg_prog: subsequence size 0 outside [8, 1 MiB]");
+  ProgPlan L;
+  if (int e = jpg_prog_plan(data, offs, n, subseq_bytes, L)) return e;
+  VF_REQUIRE(stage_bytes >= L.stage && ws_bytes >= L.ws, "vf_jpeg_prog_decode: staging %zu / workspace %zu bytes, need %zu / %zu",
+             stage_bytes, ws_bytes, L.stage, L.ws);
+  for (int i = 0; i < n; ++i)
+    VF_REQUIRE(!(L.G[i].P.ncomp == 3 && channels == 1), "vf_jpeg_prog_decode: image %d is YCbCr; channels=1 takes grayscale files only", i);
+  jpg_prog_pack(data, offs, n, channels, subseq_bytes, out_offs, L, (uint8_t*)stage);
+  uint8_t* w = (uint8_t*)ws;
+  JpgBatch B = {};
+  B.img = (const JpgImage*)(w + L.o_img);
+  B.chunk = (const JpgChunk*)(w + L.o_chunk);
+  B.huff = (const JpgHuff*)(w + L.o_huff);
+  B.scan = w + L.o_scan;
+  B.bits = w + L.o_bits;
+  B.E = (uint64_t*)(w + L.o_E);
+  B.X = (uint64_t*)(w + L.o_X);
+  B.Nb = (int32_t*)(w + L.o_N);
+  B.D = w + L.o_D;
+  B.coef = (int16_t*)(w + L.o_coef);
+  B.planes = w + L.o_planes;
+  B.out = out;
+  B.status = status;
+  B.rounds = rounds;
+  B.nseg = (int)L.nseg;
+  B.nchunk = (int)L.nchunk;
+  B.sub_bits = 8 * subseq_bytes;
+  hipStream_t st = ctx->stream;
+  {
+    VfRange r("jpeg_prog_upload");
+    VF_CHECK_HIP(hipMemcpyAsync(w, stage, L.stage, hipMemcpyHostToDevice, st));
+    VF_CHECK_HIP(hipMemsetAsync(w + L.o_coef, 0, (size_t)(128 * L.nblk), st));
+    VF_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t) * n, st));
+    VF_CHECK_HIP(hipMemsetAsync(rounds, 0, sizeof(int32_t), st));
+  }
+  const int64_t sb = L.scan_bytes;
+  VF_LAUNCH_TIMED(ctx, "jpeg_unstuff", 0.0, 2.0 * sb, k_jpeg_unstuff, dim3((unsigned)std::max<int64_t>(1, vf_cdiv(L.nchunk, 4))), dim3(256), B);
+  VF_LAUNCH_CHECK();
+  // one launch per level: level 0 holds the first scans (a first scan covers new ground, so it waits for nothing), a
+  // block each; the levels behind hold the refinements
+  const ProgScan* d_scans = (const ProgScan*)(w + L.o_scans);
+  const ProgSeg* d_segs = (const ProgSeg*)(w + L.o_seg);
+  int64_t first = 0;
+  for (size_t l = 0; l < L.level_segs.size(); ++l) {
+    const int64_t cnt = L.level_segs[l];
+    if (cnt > 0 && l == 0) {
+      VF_LAUNCH_TIMED(ctx, "jpeg_prog_first", 0.0, 3.0 * sb / (double)L.level_segs.size(), k_jpeg_prog_first, dim3((unsigned)cnt), dim3(kHuffThreads),
+                      B, d_scans, d_segs);
+      VF_LAUNCH_CHECK();
+    } else if (cnt > 0) {
+      // A refinement level with few segments gives each its own wave (one lane's walk is not slowed by the divergent
+      // walks of 63 others); many segments share waves
+      const int lanes = (int)std::min<int64_t>(64, std::max<int64_t>(1, vf_cdiv(cnt, 8192)));
+      VF_LAUNCH_TIMED(ctx, "jpeg_prog_refine", 0.0, 3.0 * sb / (double)L.level_segs.size(), k_jpeg_prog_scan, dim3((unsigned)vf_cdiv(cnt, lanes)),
+                      dim3(lanes), B, d_scans, d_segs, (int)first, (int)cnt);
+      VF_LAUNCH_CHECK();
+    }
+    first += cnt;
+  }
+  const unsigned gb = (unsigned)std::min<int64_t>(vf_cdiv(L.max_blocks, 256), 4096);
+  VF_LAUNCH_TIMED(ctx, "jpeg_idct", 0.0, 192.0 * L.nblk, k_jpeg_idct, dim3(gb, n), dim3(256), B);
+  VF_LAUNCH_CHECK();
+  const unsigned gp = (unsigned)std::min<int64_t>(vf_cdiv(L.max_pix, 256), 4096);
+  VF_LAUNCH_TIMED(ctx, "jpeg_color", 0.0, 2.0 * L.plane_bytes, k_jpeg_color, dim3(gp, n), dim3(256), B);
+  VF_LAUNCH_CHECK();
+  if (levels) *levels = (int32_t)L.level_segs.size();
+  return 0;
+}
 
 VF_API int vf_jpeg_inspect(const unsigned char* data, size_t len, int scan_walk, int64_t* info, char* reason, int reason_cap) {
   VF_REQUIRE(data && info, "vf_jpeg_inspect: NULL argument");
