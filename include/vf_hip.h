@@ -608,6 +608,48 @@ int vf_gif_workspace_bytes(int clips, int frames, int H, int W, size_t* ws_bytes
 int vf_gif_encode(vf_ctx* ctx, const void* src, int kind, int clips, int frames, int H, int W, int delay_cs, void* ws,
                   size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
 
+/* ---- animated GIF decode (vf_gif_decode.hip) --------------------------------------------------------
+ * GIF87a and GIF89a files (the ones vf_gif_encode writes among them) to the composited canvas of every frame, on the
+ * device and all-integer; tests/gif_decode_ref.py is the definition.  Container: logical screen, optional global table,
+ * any sequence of extensions (the graphic control extension gives disposal, transparency and delay, NETSCAPE2.0 the
+ * loop count, the others are skipped), image descriptors with an optional local table and interlace flag, the trailer;
+ * bytes behind the trailer are ignored.  LZW: minimum code size 2 to 8, a leading Clear optional, KwKwK, and a full
+ * dictionary of 4096 entries stays as it is until a Clear comes; decoding stops once the rectangle is full.
+ * Compositing is the browsers' rule: the RGBA canvas starts transparent; frame k paints its non-transparent indices as
+ * (table colour, 255) and the canvas is output frame k; then disposal 2 clears the rectangle to (0,0,0,0), 3 restores
+ * the canvas as it was before the frame, anything else keeps it.  RGB output is the colour planes (a transparent pixel
+ * is 0,0,0), RGBA adds alpha (0 or 255).
+ * vf_gif_inspect (host only, no GPU): walk one whole file.  info (int64[8]) = {width, height, frames, loop count or -1
+ * without a NETSCAPE2.0 block, supported (0/1), entries of the global table or 0, version (87 or 89), sum of the frame
+ * rectangles' pixels}; frames (may be NULL; int64[frame_cap][12]) receives, for the first frame_cap frames, {delay in
+ * centiseconds, disposal, x, y, w, h, interlace, transparent index or -1, entries of the active table, table is local,
+ * LZW minimum code size, bytes of image data}; reason receives why a parsable file is not supported (a side above
+ * 16384, more than 65535 frames, decoded frames of 2 GiB or more, frame rectangles above 256 Mi pixels, a frame's data
+ * above 256 MiB), else "".  Non-zero, with vf_last_error, for a malformed file: bad signature, truncation, no trailer,
+ * no frame, a rectangle that leaves the screen, a frame without any colour table, a minimum code size outside 2 .. 8. */
+enum {
+  VF_GIF_OK = 0, VF_GIF_BAD_CODE = 1, VF_GIF_SHORT_DATA = 2, VF_GIF_BAD_INDEX = 3
+};   /* per-file status words of vf_gif_decode: a code above the next free one, or a first code behind a Clear that is
+      * no root; EOI or the end of the data before the rectangle is full; an index that is painted and lies at or
+      * above the active table's size.  A file's word is the largest of its frames'; indices are only looked at when
+      * every frame's code stream was good. */
+int vf_gif_inspect(const unsigned char* data, size_t len, int64_t* info, int64_t* frames, int frame_cap, char* reason,
+                   int reason_cap);
+/* Host only, no GPU: ws_bytes receives the DEVICE workspace (the upload, then every frame's index plane) that
+ * vf_gif_decode needs; stage_bytes: its HOST staging buffer (pinned memory keeps the one upload asynchronous).  data
+ * holds the n files back to back, file i at offs[i] .. offs[i+1]; alpha 0: RGB output, 1: RGBA.  Error 2 for a malformed
+ * file, 3 for an unsupported one, naming the image. */
+int vf_gif_decode_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int alpha, size_t* ws_bytes,
+                                  size_t* stage_bytes);
+/* Decode on the context's stream: file i becomes uint8 frames_i x H_i x W_i x (3 | 4) at out + out_offs[i]; status
+ * (DEVICE int32[n]) receives VF_GIF_* per file.  The host walks each file, strips the sub-block length bytes so that
+ * every frame's code stream is contiguous, and packs the streams, one colour table and one descriptor per frame into
+ * stage -> ONE upload; then two launches whatever n and the frame counts (k_gifd_lzw: a block per frame; k_gifd_compose:
+ * a thread per canvas pixel of a file).  out, ws and status are caller-owned DEVICE memory, stage HOST memory that
+ * stays untouched until the stream has passed the upload.  Nothing is allocated and nothing synchronises. */
+int vf_gif_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int alpha, const int64_t* out_offs,
+                  unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes, int32_t* status);
+
 /* ---- contact sheets of the inference scripts (vf_display.hip) -----------------------------------------
  * image.toDisplayTensor(input, padding, nrow, scaleeach, min, max, symmetric, saturate) of test.lua:129, demo.lua:96 and
  * test_vid.lua:149 for the one input form they use: a packed float tensor N x C x h x w, C = 1 or 3 (src_layout 0:

@@ -1,0 +1,36 @@
+"""Builds scripts/gif_parse_sanitize.cpp — the GIF decoder's host-side parser and packer as a stand-alone program — with
+-fsanitize=address,undefined and runs it on every fixture of tests/gif_decode_cases.py (good, corrupt, malformed,
+unsupported), each whole and truncated at every byte offset.  Host only: no GPU, nothing loaded into Python.
+
+    python scripts/gif_parse_sanitize.py
+
+Prints the program's counts; any sanitizer report ends it with a non-zero status."""
+import os
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import gif_decode_cases as cases  # noqa: E402
+
+
+def main():
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "gif_parse_sanitize")
+        subprocess.check_call([hipcc, "-x", "c++", "-std=c++17", "-O1", "-g", "-Wall", "-Xarch_host", "-fsanitize=address,undefined",
+                               "-fno-sanitize-recover=undefined", os.path.join(ROOT, "scripts", "gif_parse_sanitize.cpp"), "-o", exe])
+        paths = []
+        for k, (name, c) in enumerate(sorted(cases.fixtures().items())):
+            paths.append(os.path.join(tmp, "%02d_%s.gif" % (k, name.replace("/", "_"))))
+            with open(paths[-1], "wb") as fh:
+                fh.write(c.data)
+        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+        rc = subprocess.call([exe] + paths, env=env)
+    print("gif_parse_sanitize: %d fixtures, exit status %d" % (len(paths), rc))
+    return rc
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -104,6 +104,9 @@ SIGNATURES = {
     "vf_jpeg_encode_opts": (i32, [vp, vp] + [i32] * 10 + [vp, sz, vp, sz, vp]),
     "vf_gif_workspace_bytes": (i32, [i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_gif_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
+    "vf_gif_inspect": (i32, [vp, sz, vp, vp, i32, C.c_char_p, i32]),
+    "vf_gif_decode_workspace_bytes": (i32, [vp, vp, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
+    "vf_gif_decode": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, sz, vp, sz, vp]),
     "vf_display_workspace_bytes": (i32, [i32] * 9 + [C.POINTER(sz)]),
     "vf_display_tensor": (i32, [vp, vp, i32, vp] + [i32] * 8 + [f64, i32, f64, i32, i32]),
     "vf_center_finish": (i32, [vp] * 6 + [i32] * 4),

@@ -409,6 +409,46 @@ def gif_workspace_bytes(clips, frames, H, W):
     return _encoder_bytes("vf_gif_workspace_bytes", clips, frames, H, W)
 
 
+GIF_DECODE_TOKENS = 1984     # tokens per batch of k_gifd_lzw (kTok of csrc/vf_gif_decode.hip): where a frame's codes change batch
+GIF_STATUS = {0: "ok", 1: "bad code", 2: "short data", 3: "bad colour index"}     # VF_GIF_* of include/vf_hip.h
+GIF_FRAME_KEYS = ("delay", "disposal", "x", "y", "w", "h", "interlace", "transparency", "table_size", "local_table", "min_code_size",
+                  "data_bytes")
+
+
+def gif_inspect(data):
+    """The host-only walk of one GIF file (vf_gif_inspect; no GPU needed) -> dict(width, height, frames, loop, supported,
+    global_table_size, version, rect_pixels, reason, frame_info), frame_info a list with one dict of GIF_FRAME_KEYS per
+    frame (transparency: the index or -1; delay in centiseconds).  loop is -1 without a NETSCAPE2.0 block.  Raises
+    ValueError for a malformed file."""
+    lib = _lib.load()
+    data = bytes(data)
+    info = (C.c_int64 * 8)()
+    why = C.create_string_buffer(160)
+    if lib.vf_gif_inspect(data, len(data), info, None, 0, why, 160) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    keys = ("width", "height", "frames", "loop", "supported", "global_table_size", "version", "rect_pixels")
+    d = {k: int(v) for k, v in zip(keys, info)}
+    rows = np.zeros((d["frames"], 12), np.int64)
+    if lib.vf_gif_inspect(data, len(data), info, rows.ctypes.data_as(C.c_void_p), d["frames"], why, 160) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    d["supported"] = bool(d["supported"])
+    d["reason"] = why.value.decode()
+    d["frame_info"] = [dict(zip(GIF_FRAME_KEYS, map(int, r))) for r in rows]
+    return d
+
+
+def gif_decode_workspace_bytes(files, alpha=False):
+    """(device workspace bytes, host staging bytes) of one GIF batch (vf_gif_decode_workspace_bytes; host only, no GPU
+    needed).  ValueError, naming the image, for a malformed or unsupported file."""
+    lib = _lib.load()
+    data, offs = _joined(files)
+    ws_b, st_b = C.c_size_t(), C.c_size_t()
+    if lib.vf_gif_decode_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), len(files), int(bool(alpha)), C.byref(ws_b),
+                                         C.byref(st_b)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return ws_b.value, st_b.value
+
+
 class HipBackend:
     name = "hip-gfx950"
 
@@ -1142,6 +1182,17 @@ class HipBackend:
         if Cc != 3:
             raise ValueError("gif_encode: %d channels (a GIF frame here is RGB, 3)" % Cc)
         return self._encode("vf_gif_encode", "gif", clips, g, gif_workspace_bytes(g, n, H, W), kind, g, n, H, W, int(delay))
+
+    # ---- GIF decode (vf_gif_decode.hip)
+    def gif_decode(self, files, alpha=False, infos=None):
+        """Decode a batch of supported GIF files (bytes each) into one device uint8 buffer.  -> (out, offsets, status):
+        file i is out[offsets[i]:offsets[i+1]] as frames x H x W x (4 if alpha else 3), the composited canvas of every
+        frame; status (device int32[n]) holds VF_GIF_* per file, valid once the stream gets there.  infos: the files'
+        gif_inspect results, if the caller has them."""
+        shapes = infos if infos is not None else [gif_inspect(f) for f in files]
+        oc = 4 if alpha else 3
+        return self._decode("gifd", "vf_gif_decode_workspace_bytes", "vf_gif_decode", files,
+                            [s["frames"] * s["height"] * s["width"] * oc for s in shapes], (int(bool(alpha)),), (int(bool(alpha)),))
 
     # ---- contact sheets (vf_display.hip, DESIGN.md 5.4)
     def display_tensor(self, packed, padding=0, nrow=6, scaleeach=False, min=None, max=None, symmetric=False, saturate=True):

@@ -21,8 +21,8 @@ import numpy as np
 import torch
 
 from ._lib import VfError
-from .backend import (JPEG_STATUS, METRIC_COLUMNS, PNG_STATUS, get_backend, jpeg_inspect, jpeg_scans_inspect, nhwc_empty,
-                      png_inspect)
+from .backend import (GIF_STATUS, JPEG_STATUS, METRIC_COLUMNS, PNG_STATUS, get_backend, gif_inspect, jpeg_inspect,
+                      jpeg_scans_inspect, nhwc_empty, png_inspect)
 
 CENTER_FILL = (117.0, 104.0, 123.0)      # train.lua:287-289
 
@@ -350,6 +350,65 @@ def encode_gif(clips, delay=10):
         raise ValueError("encode_gif: delay=%r is not a whole number of centiseconds from 0 to 65535" % (delay,))
     B = get_backend()
     return _files_from(*B.gif_encode(B.from_host(t).contiguous(), int(delay)))
+
+
+# ------------------------------------------------------------------------------------------ GIF decode
+def gif_info(item):
+    """The host-side walk of one GIF87a / GIF89a file (no GPU): dict(width, height, frames, loop (-1 without a NETSCAPE2.0
+    block), supported, global_table_size, version, rect_pixels, reason, frame_info), frame_info holding per frame
+    dict(delay, disposal, x, y, w, h, interlace, transparency (index or -1), table_size, local_table, min_code_size,
+    data_bytes).  ValueError if the file is malformed (signature, truncation, no trailer, a rectangle that leaves the
+    screen, a frame without a colour table, a minimum code size outside 2 .. 8)."""
+    return gif_inspect(_file_bytes(item))
+
+
+def decode_gif(items, alpha=False, fallback=None):
+    """The frames of a batch of GIF files, decoded and composited on the device in one call (vf_gif_decode): a list with
+    one device uint8 N x H x W x 3 tensor per file (N x H x W x 4 with alpha=True), views of one buffer.  Output frame k
+    is the canvas after frame k was painted, by the browsers' rule (tests/gif_decode_ref.py is the
+    definition): the canvas starts transparent, disposal 2 clears the frame's rectangle, 3 restores what was there; a
+    pixel nothing has painted is (0,0,0) and, with alpha, has alpha 0.  Files `encode_gif` wrote come back as their
+    quantised frames.
+
+    items: bytes, uint8 arrays or paths.  Files the device decoder does not take (a side above 16384, more than 65535
+    frames, 2 GiB of frames) go to fallback(bytes), which returns the uint8 N x H x W x C frames; without it they raise
+    ValueError naming the item and why.  A malformed file raises ValueError naming the item before anything is launched;
+    a corrupt code stream or a colour index beyond its table raises it, with the status, once the stream has
+    synchronised."""
+    B = get_backend()
+    oc = 4 if alpha else 3
+    files = [_file_bytes(it) for it in items]
+    infos, dev, out = [], [], [None] * len(files)
+    for i, f in enumerate(files):
+        try:
+            info = gif_inspect(f)
+        except ValueError as e:
+            raise ValueError("decode_gif: item %d: %s" % (i, e)) from None
+        if not info["supported"]:
+            if fallback is None:
+                raise ValueError("decode_gif: item %d is not supported by the device decoder: %s" % (i, info["reason"]))
+            fr = torch.as_tensor(np.ascontiguousarray(fallback(f)))
+            assert fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == oc, \
+                "fallback returns uint8 N x H x W x %d, got %s %s" % (oc, fr.dtype, tuple(fr.shape))
+            out[i] = B.from_host(fr).contiguous()
+            continue
+        infos.append(info)
+        dev.append(i)
+    if dev:
+        try:
+            buf, offs, status = B.gif_decode([files[i] for i in dev], alpha, infos)
+        except VfError as e:   # found on the host while the batch was planned: nothing was launched
+            m = re.search(r"image (\d+)", str(e))
+            if m is None:
+                raise
+            raise ValueError("decode_gif: item %d: %s" % (dev[int(m.group(1))], e)) from None
+        st = status.cpu().tolist()
+        for j, i in enumerate(dev):
+            if st[j] != 0:
+                raise ValueError("decode_gif: item %d: corrupt image data (%s)" % (i, GIF_STATUS.get(st[j], st[j])))
+            s = infos[j]
+            out[i] = buf[offs[j]:offs[j + 1]].view(s["frames"], s["height"], s["width"], oc)
+    return out
 
 
 # --------------------------------------------------------------------------------------------- scores (DESIGN 5.7)

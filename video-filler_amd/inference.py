@@ -207,6 +207,16 @@ def save_gifs(name, outImages=None, inpaintImages=None, fullImages=None, delay=1
     return _write_files(["%s_%s.gif" % (name, key) for key in keys], files)
 
 
+def load_gif_clip(item):
+    """A GIF file (bytes, a path, a uint8 array or tensor) as the clip the drivers hold: float N x 3 x H x W in [0,1] on the
+    device — every frame composited on the device (data.decode_gif), b / 255 as a correctly rounded
+    float32 division, then the layout change.  The form save_frames and evaluate_frames take:
+    evaluate_frames(load_gif_clip(name + "_result.gif"), load_gif_clip(name + "_orig.gif")) scores what save_gifs'
+    256-colour tables cost.  ValueError for a malformed, unsupported or corrupt file."""
+    (frames,) = data.decode_gif([item])
+    return get_backend().png_bytes_to_float(frames).permute(0, 3, 1, 2).contiguous()
+
+
 # ------------------------------------------------------------------------------------------------- scores (DESIGN 5.7)
 def scores_from_table(table):
     """data.frame_metrics' int64 table N x 2 x 6 (a host array) -> the dict evaluate_frames returns: float64 from the
