@@ -587,6 +587,25 @@ int vf_jpeg_encode_opts_workspace_bytes(int n, int H, int W, int C, int subsampl
 int vf_jpeg_encode_opts(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling,
                         int restart_rows, int restart_blocks, int optimize, void* ws, size_t ws_bytes, unsigned char* out,
                         size_t out_cap, int64_t* offsets);
+/* The same frames as progressive files (SOF2), byte for byte what libjpeg writes with jpeg_simple_progression (Pillow's
+ * progressive=True; tests/jpeg_enc_prog_ref.py is the rule in numpy): 10 scans for C = 3 (DC of all components, Y 1-5,
+ * Cr, Cb, Y 6-63, Y refined, DC refined, Cr, Cb and Y refined), 6 for C = 1, every scan but the DC refinement behind the
+ * DHT segments of its own optimal tables (libjpeg forces optimize_coding here).  The arguments, limits and errors are those
+ * of vf_jpeg_encode; restart intervals cannot be asked for.
+ * The bound.  Over all scans a luma block's code is at most: DC 16 code bits + 11 value bits, its refinement 1 bit; an AC
+ * coefficient's first scan 16 + 10 bits (63 coefficients), a refinement scan 16 + 1 sign bit or 1 correction bit per
+ * coefficient (twice 63), a ZRL less than that per coefficient it covers; and in each of the four AC scans one EOBn of
+ * 16 + 14 bits: 28 + 63 * 26 + 2 * 63 * 17 + 4 * 30 = 3928 bits, rounded up to 3968, 496 bytes (a chroma block has one
+ * refinement scan less; a dummy has only the DC bits).  Every scan ends in at most one pad byte; byte stuffing can at
+ * most double the stream; SOI to SOF2 is at most 192 bytes, a scan's header at most two DHT segments of 288 bytes and an
+ * SOS of 14; EOI 2:
+ * out_bytes = n * (2 * (496 * blocks per frame + scans) + 192 + scans * 590 + 2), blocks counted in whole MCUs. */
+int vf_jpeg_encode_prog_workspace_bytes(int n, int H, int W, int C, int subsampling, size_t* ws_bytes, size_t* out_bytes);
+/* As vf_jpeg_encode: twelve launches and two memsets whatever n and the scan count are (the kernels take the scan as a
+ * grid dimension); the runs, the counts, the tables and the headers are made on the device; nothing is allocated and
+ * nothing synchronises. */
+int vf_jpeg_encode_prog(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling,
+                        void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
 
 /* ---- animated GIF encode (vf_gif.hip) ------------------------------------------------------------------
  * The `convert -delay D pred_1.png ... x_result.gif` that ends test_vid.lua:140-147, test_vid_wholeim.lua:244-257 and

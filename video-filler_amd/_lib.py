@@ -102,6 +102,8 @@ SIGNATURES = {
     "vf_jpeg_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_jpeg_encode_opts_workspace_bytes": (i32, [i32] * 8 + [C.POINTER(sz), C.POINTER(sz)]),
     "vf_jpeg_encode_opts": (i32, [vp, vp] + [i32] * 10 + [vp, sz, vp, sz, vp]),
+    "vf_jpeg_encode_prog_workspace_bytes": (i32, [i32, i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
+    "vf_jpeg_encode_prog": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_gif_workspace_bytes": (i32, [i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_gif_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_gif_inspect": (i32, [vp, sz, vp, vp, i32, C.c_char_p, i32]),

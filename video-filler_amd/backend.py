@@ -398,6 +398,12 @@ def jpeg_encode_opts_workspace_bytes(n, H, W, channels, subsampling="420", resta
                           restart_rows, restart_blocks, optimize)
 
 
+def jpeg_encode_prog_workspace_bytes(n, H, W, channels, subsampling="420"):
+    """jpeg_encode_workspace_bytes for progressive files (vf_jpeg_encode_prog_workspace_bytes; host only): the stream's
+    bound is 496 bytes a block over the 10 (grey: 6) scans, and every scan brings its own tables."""
+    return _encoder_bytes("vf_jpeg_encode_prog_workspace_bytes", n, H, W, channels, JPEG_SUBSAMPLING.get(subsampling, -1))
+
+
 METRIC_COLUMNS = ("n", "sse", "sae", "ssim_q", "ssim_n", "flicker")     # VF_METRICS_* of include/vf_hip.h, in order
 GIF_CHUNK = 3824     # pixels between two Clear codes of a frame's LZW stream (csrc/vf_gif.hip)
 
@@ -1150,18 +1156,25 @@ class HipBackend:
         return self._encode("vf_png_encode", "png", frames, n, png_workspace_bytes(n, H, W, Cc), kind, n, H, W, Cc)
 
     # ---- JPEG encode (vf_jpeg_enc.hip)
-    def jpeg_encode(self, frames, quality=75, subsampling="420", restart_rows=0, restart_blocks=0, optimize=False):
+    def jpeg_encode(self, frames, quality=75, subsampling="420", restart_rows=0, restart_blocks=0, optimize=False, progressive=False):
         """Encode a batch of frames of one size as baseline JPEG files on the device, byte for byte libjpeg's default
         compression at `quality` (1 to 100) and `subsampling` ("444", "422" or "420"; ignored for grey frames); with
         restart_rows / restart_blocks (an interval of so many rows of MCUs, or MCUs; rows win) and optimize (Huffman
         tables from each file's own counts), byte for byte what libjpeg writes with those options
-        (vf_jpeg_encode_opts).  frames:
+        (vf_jpeg_encode_opts); with progressive the file is libjpeg's progressive one (vf_jpeg_encode_prog: SOF2, 10 or 6
+        scans, optimal tables whatever optimize says; restart intervals are a ValueError).  frames:
         device uint8 N x H x W x C (taken as they are) or float32 N x C x H x W (through image.savePNG's truncating byte
         rule inside the first kernel), C = 1 or 3, contiguous.  -> (buffer, offsets): file i is
         buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8 tensor of the upper bound's size, offsets a device
         int64[N + 1]; both are valid once the stream gets there."""
         assert frames.dim() == 4 and frames.is_contiguous() and frames.device == self.device
         kind, n, H, W, Cc = _frame_kind(frames)
+        if progressive:
+            for name, v in (("restart_rows", restart_rows), ("restart_blocks", restart_blocks)):
+                if v:
+                    raise ValueError("jpeg_encode: %s=%r with progressive=True (a progressive file has no restart intervals here)" % (name, v))
+            return self._encode("vf_jpeg_encode_prog", "jpeg_enc", frames, n, jpeg_encode_prog_workspace_bytes(n, H, W, Cc, subsampling),
+                                kind, n, H, W, Cc, int(quality), JPEG_SUBSAMPLING.get(subsampling, -1))
         if not (restart_rows or restart_blocks or optimize):
             return self._encode("vf_jpeg_encode", "jpeg_enc", frames, n, jpeg_encode_workspace_bytes(n, H, W, Cc, subsampling),
                                 kind, n, H, W, Cc, int(quality), JPEG_SUBSAMPLING.get(subsampling, -1))

@@ -24,6 +24,9 @@
 //   k_jenc_write<1>   also pads a segment's last byte with 1-bits; k_jenc_stuff<1> puts RSTn behind a segment's last byte and the
 //                     image's own header (prefix, its DHT segments, DRI, SOS) in front.
 // Twelve launches and one memset with optimize, ten without; nothing synchronises.
+//
+// The progressive file (vf_jpeg_encode_prog: SOF2, libjpeg's ten or six scans) shares k_jenc_dct, jenc_gen_table, k_jenc_clear
+// and k_jenc_ff_count with the above; its own kernels and their list stand at the end of this file.
 #include "vf_block.h"
 #include "vf_common.h"
 
@@ -412,21 +415,23 @@ __device__ __forceinline__ void jenc_min2(unsigned long long& lo, unsigned long 
   }
 }
 
-// jpeg_gen_optimal_table of table blockIdx.x of image blockIdx.y.  Thread i owns symbol i, thread 256 the reserved code point (no
+// jpeg_gen_optimal_table.  Thread i owns symbol i, thread 256 the reserved code point (no
 // real symbol gets the all-ones code).  libjpeg's `others` chain behind a tree's head is the set of that tree's leaves, so a merge
 // is one step of all threads: the leaves of both trees grow by one bit and take the head's name.  The two smallest counts come
 // from a reduction over keys count << 32 | 511 - symbol: the smallest count, and among equals the LARGEST symbol, as jchuff.c's
 // `<=` scan finds them.  A code longer than 32 bits, which libjpeg refuses (it takes more than nine million symbols in Fibonacci
 // proportions), is not told apart here; the counters of the lengths have room for any tree.
+//
+// jenc_gen_table is the table of one workgroup of JENC_TABLE_THREADS: 256 counts in, the canonical codes (symbol -> code << 8 |
+// length) of the first lut_n symbols into lut, the DHT segment of class and id tc_th into d, its length into *d_len.
 constexpr int JENC_TABLE_THREADS = 320;
-__global__ __launch_bounds__(JENC_TABLE_THREADS) void k_jenc_table(JencArgs a) {
+__device__ __forceinline__ void jenc_gen_table(const unsigned* counts, unsigned* lut, int lut_n, unsigned char* d, int* d_len, int tc_th) {
   constexpr int WAVES = JENC_TABLE_THREADS / 64;
   constexpr unsigned long long NONE = ~0ull;
   __shared__ unsigned long long s_min[2][WAVES][2];
   __shared__ int s_size[256], s_bits[264], s_first[17], s_start[18];
-  const int k = blockIdx.x, i = threadIdx.x, lane = i & 63, wave = i >> 6;
-  const long long f = blockIdx.y;
-  unsigned freq = i < 256 ? a.counts[(f * 4 + k) * 256 + i] : i == 256 ? 1u : 0u;
+  const int i = threadIdx.x, lane = i & 63, wave = i >> 6;
+  unsigned freq = i < 256 ? counts[i] : i == 256 ? 1u : 0u;
   int head = i, size = 0;
   for (int it = 0;; ++it) {
     unsigned long long lo = freq ? (unsigned long long)freq << 32 | (unsigned)(511 - i) : NONE, hi = NONE;
@@ -479,8 +484,7 @@ __global__ __launch_bounds__(JENC_TABLE_THREADS) void k_jenc_table(JencArgs a) {
   }
   __syncthreads();
   // HUFFVAL: the symbols by their UNLIMITED length, then by value; the limited lengths are dealt out along that order
-  const int cls = k & 1, t = k >> 1, nsym = s_start[17];
-  unsigned char* d = a.dht + (f * 4 + k) * JENC_DHT_STRIDE;
+  const int nsym = s_start[17];
   unsigned entry = 0;
   if (i < 256 && size) {
     int pos = 0;
@@ -493,20 +497,23 @@ __global__ __launch_bounds__(JENC_TABLE_THREADS) void k_jenc_table(JencArgs a) {
     entry = (unsigned)(s_first[l] + pos - s_start[l]) << 8 | (unsigned)l;
     d[21 + pos] = (unsigned char)i;
   }
-  if (cls) {
-    if (i < 256) a.lut[f].ac[t][i] = entry;
-  } else if (i < 12) {
-    a.lut[f].dc[t][i] = entry;                     // a DC category is at most 11
-  }
+  if (i < lut_n) lut[i] = entry;
   if (i < 16) d[5 + i] = (unsigned char)s_bits[i + 1];
   if (i == 0) {
     d[0] = 0xFF;
     d[1] = 0xC4;
     d[2] = (unsigned char)((19 + nsym) >> 8);
     d[3] = (unsigned char)((19 + nsym) & 255);
-    d[4] = (unsigned char)(cls << 4 | t);
-    a.dht_len[f * 4 + k] = 21 + nsym;
+    d[4] = (unsigned char)tc_th;
+    *d_len = 21 + nsym;
   }
+}
+// table blockIdx.x (2 * (luma 0 / chroma 1) + (DC 0 / AC 1)) of image blockIdx.y
+__global__ __launch_bounds__(JENC_TABLE_THREADS) void k_jenc_table(JencArgs a) {
+  const int k = blockIdx.x, cls = k & 1, t = k >> 1;
+  const long long f = blockIdx.y;
+  jenc_gen_table(a.counts + (f * 4 + k) * 256, cls ? a.lut[f].ac[t] : a.lut[f].dc[t], cls ? 256 : 12,   // a DC category is at most 11
+                 a.dht + (f * 4 + k) * JENC_DHT_STRIDE, a.dht_len + f * 4 + k, cls << 4 | t);
 }
 
 // One workgroup per image.  The image-wide scan gave every block its bit offset as if there were no restarts; segment s is the
@@ -874,7 +881,614 @@ int jenc_encode(const char* who, vf_ctx* ctx, const void* src, int kind, int n, 
   return p.opts() ? jenc_launch<true>(ctx, p, a, hdr, kind) : jenc_launch<false>(ctx, p, a, hdr, kind);
 }
 
+// ============================================================================================ the progressive encoder (SOF2)
+// vf_jpeg_encode_prog: libjpeg's jpeg_simple_progression and jcphuff.c (tests/jpeg_enc_prog_ref.py is the rule in numpy).  The
+// coefficients are k_jenc_dct's.  A scan walks its blocks (a DC scan every block of the interleaved order, an AC scan the real
+// blocks of its component in raster order), and every kernel below takes all scans of all images in one launch, the scan in
+// blockIdx.z (or .x where a workgroup owns a whole scan):
+//   k_jprog_sum       one thread per block of a walk: its symbols counted (LDS first), and for an AC scan its summary: does it
+//                     bring a symbol, does it end in zeros or correction bits and so join the EOB run, how many correction bits
+//                     trail its last symbol.
+//   k_jprog_runs      one wave per image and AC scan: jcphuff.c's EOBRUN and BE walked over the summaries, 64 blocks per step from
+//                     two ballots.  A run is emitted behind its FIRST block's own symbols (nothing stands between that place and
+//                     where libjpeg writes it), so the first block of a run receives the run's length and every other block 0,
+//                     and the EOBn symbols are counted.
+//   k_jprog_table     one workgroup per image and table: jenc_gen_table, two tables for the colour DC scan, none for a DC refinement.
+//   k_jprog_size / k_jprog_tile_scan / k_jenc_clear / k_jprog_write   as the baseline's: a block's bits are its symbols, its run's
+//                     EOBn code if it heads one, its trailing correction bits.  Every scan starts on a byte of the image's stream
+//                     and its last block pads it with 1-bits.
+//   k_jenc_ff_count / k_jprog_ff_scan / k_vf_file_offsets / k_jprog_stuff   the stuffing; the thread that holds a scan's first
+//                     byte writes the image's DHT segments and the SOS of that scan in front of it.
+// Twelve launches and two memsets whatever the batch and the scan count; nothing synchronises.
+constexpr int JPROG_MAX_SCANS = 10;
+constexpr int JPROG_BLOCK_BITS = 3968;    // the bound on a block's code over all scans (vf_hip.h has the derivation), a multiple of 32
+constexpr int JPROG_PREFIX_CAP = 192;     // SOI, APP0, two DQT, SOF2: 177 bytes in colour
+constexpr int JPROG_SOS_CAP = 14;
+constexpr int JPROG_MAX_RUN = 0x7FFF;     // jcphuff.c: an EOB run is emitted when it reaches this length ...
+constexpr int JPROG_MAX_BE = 937;         // ... or buffers more correction bits than MAX_CORR_BITS - DCTSIZE2 + 1
+
+struct JprogScan {
+  int comp;                      // the component of an AC scan; -1: all components interleaved (the DC scans)
+  int ss, se, ah, al;
+  int len, tiles;                // blocks of the walk, and their tiles of JENC_TILE
+  int ntab;                      // tables of its own: 2 for the colour DC scan, 0 for a DC refinement, else 1
+  unsigned char tc_th[2];        // their class << 4 | id
+  unsigned char sos[JPROG_SOS_CAP];
+  int sos_len;
+};
+
+struct JprogArgs {
+  JencArgs e;                    // the geometry, coef, stream, img_bits, ff_cnt, ff_pref, out, offsets; tiles: of the longest walk;
+                                 // blk_off [n][nscan][nb], tile_sum and tile_off [n][nscan][tiles]
+  JprogScan scan[JPROG_MAX_SCANS];
+  int nscan;
+  unsigned char* sum;            // [n][nscan][nb]: trailing correction bits | joins << 6 | has a symbol << 7
+  unsigned short* run;           // [n][nscan][nb]: the length of the EOB run this block heads, else 0
+  unsigned* counts;              // [n][nscan][2][256]
+  unsigned* lut;                 // [n][nscan][2][256]: symbol -> code << 8 | length
+  unsigned char* dht;            // [n][nscan][2][JENC_DHT_STRIDE]
+  int* dht_len;                  // [n][nscan][2]; 0 where the scan has no such table
+  unsigned long long* scan_start;  // [n][nscan]: byte offset of the scan inside its image's unstuffed stream
+  unsigned* hdr_before;          // [n][nscan]: the file's bytes in front of the scan's data that are not stream: prefix, DHTs, SOSs
+  unsigned char prefix[JPROG_PREFIX_CAP];
+  int prefix_len;
+};
+
+// block i of a scan's walk -> its place in the interleaved order of coef
+__device__ __forceinline__ int jprog_block(const JencArgs& a, const JprogScan& sc, int i) {
+  if (sc.comp < 0 || a.bpm == 1) return i;
+  if (sc.comp > 0) return i * a.bpm + a.hs * a.vs + sc.comp - 1;   // a chroma component has one block per MCU, none a dummy
+  const int Y = i / a.wb, X = i - Y * a.wb, my = Y / a.vs, mx = X / a.hs;
+  return (my * a.mcux + mx) * a.bpm + (Y - my * a.vs) * a.hs + (X - mx * a.hs);
+}
+
+struct JprogSum {
+  bool has, joins;
+  int tail;
+};
+
+// jcphuff.c's encode_mcu_* of block i of the walk, in the order of the stream: sym(table 0 / 1 of the scan, symbol, extra bits,
+// their count) for a code with its extra bits, raw(bits, count <= 63) for correction bits.  `run` is the length of the EOB run
+// the block heads (0: none, and what the passes in front of k_jprog_runs give): its EOBn follows the block's own symbols.
+template <class SYM, class RAW>
+__device__ __forceinline__ JprogSum jprog_block_items(const JencArgs& a, const JprogScan& sc, const short* coef, int i, int run, SYM&& sym,
+                                                      RAW&& raw) {
+  const int g = jprog_block(a, sc, i);
+  JprogSum r{false, false, 0};
+  if (sc.se == 0) {
+    // A dummy of the interleaved scan carries the DC of the previous real block of its component (jccoefct.c replicates it), the
+    // value jenc_pred finds: its difference is 0 and its refinement bit is that block's.
+    const JencPos p = jenc_pos(a, g);
+    const int prev = jenc_pred<false>(a, coef, g, p), dc = p.real ? (int)coef[(long long)g * 64] : prev;
+    if (sc.ah == 0) {
+      const int diff = (dc >> sc.al) - (prev >> sc.al);        // arithmetic shifts, as jcphuff.c's
+      const int n = 32 - __clz(abs(diff));
+      sym(p.comp ? 1 : 0, n, (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << n) - 1u), n);
+    } else {
+      raw((unsigned long long)((dc >> sc.al) & 1), 1);
+    }
+    return r;
+  }
+  const uint4* src = (const uint4*)(coef + (long long)g * 64);
+  unsigned w[32];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const uint4 u = src[j];
+    w[4 * j] = u.x; w[4 * j + 1] = u.y; w[4 * j + 2] = u.z; w[4 * j + 3] = u.w;
+  }
+  auto at = [&](int k) { return (int)(short)((k & 1) ? w[k >> 1] >> 16 : w[k >> 1] & 0xFFFFu); };
+  int zeros = 0, nbr = 0;
+  unsigned long long br = 0;                       // the correction bits since the last symbol, oldest highest
+  if (sc.ah == 0) {
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+      if (k < sc.ss || k > sc.se) continue;
+      const int c = at(k), m = abs(c) >> sc.al;
+      if (m == 0) { ++zeros; continue; }
+      r.has = true;
+      for (; zeros > 15; zeros -= 16) sym(0, 0xF0, 0u, 0);
+      const int n = 32 - __clz(m);
+      sym(0, zeros << 4 | n, (unsigned)(c < 0 ? ~m : m) & ((1u << n) - 1u), n);
+      zeros = 0;
+    }
+  } else {
+    int eob = 0;                                   // the last coefficient that becomes non-zero in this scan
+#pragma unroll
+    for (int k = 1; k < 64; ++k)
+      if (k >= sc.ss && k <= sc.se && (abs(at(k)) >> sc.al) == 1) eob = k;
+    r.has = eob != 0;
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+      if (k < sc.ss || k > sc.se) continue;
+      const int c = at(k), m = abs(c) >> sc.al;
+      if (m == 0) { ++zeros; continue; }
+      for (; zeros > 15 && k <= eob; zeros -= 16) {            // ZRL only while a symbol is still to come
+        sym(0, 0xF0, 0u, 0);
+        raw(br, nbr);
+        br = 0; nbr = 0;
+      }
+      if (m > 1) {                                             // already non-zero: one correction bit
+        br = br << 1 | (unsigned)(m & 1);
+        ++nbr;
+        continue;
+      }
+      sym(0, zeros << 4 | 1, c < 0 ? 0u : 1u, 1);
+      raw(br, nbr);
+      br = 0; nbr = 0; zeros = 0;
+    }
+  }
+  r.joins = zeros > 0 || nbr > 0;
+  r.tail = nbr;
+  if (run) {
+    const int n = 31 - __clz(run);
+    sym(0, n << 4, (unsigned)run & ((1u << n) - 1u), n);
+  }
+  raw(br, nbr);
+  return r;
+}
+
+__global__ __launch_bounds__(256) void k_jprog_sum(JprogArgs a) {
+  __shared__ unsigned s_h[2 * 256];
+  const int s = blockIdx.z;
+  const JprogScan& sc = a.scan[s];
+  if ((int)blockIdx.x >= sc.tiles || sc.ntab == 0) return;
+  for (int i = threadIdx.x; i < 2 * 256; i += 256) s_h[i] = 0;
+  __syncthreads();
+  const int i = blockIdx.x * JENC_TILE + threadIdx.x;
+  const long long f = blockIdx.y, fs = f * a.nscan + s;
+  if (i < sc.len) {
+    const JprogSum r = jprog_block_items(a.e, sc, a.e.coef + f * a.e.nb * 64, i, 0,
+                                         [&](int t, int v, unsigned, int) { atomicAdd(&s_h[t * 256 + v], 1u); }, [](unsigned long long, int) {});
+    a.sum[fs * a.e.nb + i] = (unsigned char)(r.tail | (r.joins ? 0x40 : 0) | (r.has ? 0x80 : 0));
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * 256; i += 256)
+    if (s_h[i]) atomicAdd(a.counts + fs * 512 + i, s_h[i]);
+}
+
+// One wave per image and AC scan, the walk in steps of 64 blocks; every lane holds the same state (EOBRUN, BE, the open run's
+// first block).  Every block has a symbol or joins the run (a block without a symbol ends in zeros or correction bits; one that
+// does not join ends in a symbol), so the blocks with a symbol cut a step into runs: a block with a symbol that joins heads
+// one, so does a block without a symbol behind one that does not join, and a run lasts up to the next block with a symbol.
+//   The step in parallel: the open run takes the blocks in front of the first symbol, every lane that heads a run finds its
+// end in the mask of the symbols, and the last run stays open; sums of trailing bits are popcounts of their six bit planes.
+// That holds where no run can reach a limit inside the step: the open run's length + 64 < 0x7FFF, and its buffered bits + all
+// trailing bits of the step <= 937.
+//   The step in order: else the blocks one by one as jcphuff.c does.  This is the part of the run resolution that stays
+// sequential: the 937-bit flush makes the cuts a greedy walk.  It costs 64 dependent iterations for a step that may hold a cut
+// (DESIGN.md 5.8 has the measurement).
+// Lane n counts the EOBn symbols; they enter the counts once at the end (k_jprog_sum counts no EOBn).
+__global__ __launch_bounds__(64) void k_jprog_runs(JprogArgs a) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const JprogScan& sc = a.scan[s];
+  if (sc.se == 0) return;
+  const long long fs = (long long)blockIdx.y * a.nscan + s;
+  const unsigned char* sum = a.sum + fs * a.e.nb;
+  unsigned short* run = a.run + fs * a.e.nb;
+  int len = 0, bits = 0, head = 0;
+  unsigned eobn = 0;
+  auto close = [&]() {
+    if (lane == 0) run[head] = (unsigned short)len;
+    if (lane == 31 - __clz(len)) ++eobn;
+    len = 0;
+    bits = 0;
+  };
+  unsigned ahead = lane < sc.len ? sum[lane] : 0u;  // the next step's summaries are on their way while this step is walked
+  for (int base = 0; base < sc.len; base += 64) {
+    const int i = base + lane, m = min(64, sc.len - base);
+    const unsigned v = ahead;
+    ahead = i + 64 < sc.len ? sum[i + 64] : 0u;
+    const unsigned long long joins = __ballot((v & 0x40u) != 0), has = __ballot((v & 0x80u) != 0);
+    const int tail = (int)(v & 63u);
+    unsigned long long plane[6] = {0, 0, 0, 0, 0, 0};          // bit k of the trailing bits of every block: sums over blocks are
+    if (sc.ah)                                                 // popcounts, scalar work (a first scan has no correction bits)
+      for (int k = 0; k < 6; ++k) plane[k] = __ballot((tail >> k & 1) != 0);
+    auto tails = [&](unsigned long long blocks) {
+      int t = 0;
+      for (int k = 0; k < 6; ++k) t += __popcll(plane[k] & blocks) << k;
+      return t;
+    };
+    auto below = [](int b) { return b >= 64 ? ~0ull : (1ull << b) - 1ull; };
+    const int p0 = has ? __ffsll((long long)has) - 1 : m;      // the first block with a symbol
+    const bool sym = has >> lane & 1, join = joins >> lane & 1;
+    const bool heads = lane < m && lane >= p0 && (sym ? join : lane > 0 && (has >> (lane - 1) & 1) && !(joins >> (lane - 1) & 1));
+    const unsigned long long rest = has & ~((2ull << lane) - 1ull);                // the symbols behind this block
+    const int end = rest ? __ffsll((long long)rest) - 1 : m;
+    const int lead = tails(below(p0)), total = tails(~0ull);
+    if (len + 64 < JPROG_MAX_RUN && bits + total <= JPROG_MAX_BE) {
+      if (p0 > 0) {
+        if (!len) head = base;
+        len += p0;
+        bits += lead;
+      }
+      if (len && p0 < m) close();
+      const bool whole = heads && end < m;
+      if (whole) run[i] = (unsigned short)(end - lane);
+      const int n = whole ? 31 - __clz(end - lane) : -1;
+      for (int k = 0; k < 6; ++k) {                // a run inside a step is shorter than 64
+        const unsigned long long of_k = __ballot(n == k);
+        if (lane == k) eobn += (unsigned)__popcll(of_k);
+      }
+      const unsigned long long open = __ballot(heads && end == m);                 // at most the last head
+      if (open) {
+        const int b = __ffsll((long long)open) - 1;
+        head = base + b;
+        len = m - b;
+        bits = tails(~below(b));
+      }
+      continue;
+    }
+    for (int b = 0; b < m; ++b) {
+      if ((has >> b & 1) && len) close();
+      if (joins >> b & 1) {
+        if (!len) head = base + b;
+        ++len;
+        bits += __builtin_amdgcn_readlane(tail, b);
+        if (len == JPROG_MAX_RUN || bits > JPROG_MAX_BE) close();
+      }
+    }
+  }
+  if (len) close();
+  if (lane < 15 && eobn) atomicAdd(a.counts + fs * 512 + (lane << 4), eobn);
+}
+
+__global__ __launch_bounds__(JENC_TABLE_THREADS) void k_jprog_table(JprogArgs a) {
+  const int s = blockIdx.x >> 1, j = blockIdx.x & 1;
+  const long long k = ((long long)blockIdx.y * a.nscan + s) * 2 + j;
+  if (j >= a.scan[s].ntab) {
+    if (threadIdx.x == 0) a.dht_len[k] = 0;
+    return;
+  }
+  jenc_gen_table(a.counts + k * 256, a.lut + k * 256, 256, a.dht + k * JENC_DHT_STRIDE, a.dht_len + k, a.scan[s].tc_th[j]);
+}
+
+__device__ __forceinline__ void jprog_load_lut(unsigned (&s_lut)[2][256], const JprogArgs& a, long long fs) {
+  for (int i = threadIdx.x; i < 512; i += 256) s_lut[i >> 8][i & 255] = a.lut[fs * 512 + i];
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_jprog_size(JprogArgs a) {
+  __shared__ unsigned s_lut[2][256];
+  __shared__ unsigned s_w[4];
+  const int s = blockIdx.z;
+  const JprogScan& sc = a.scan[s];
+  if ((int)blockIdx.x >= sc.tiles) return;
+  const int i = blockIdx.x * JENC_TILE + threadIdx.x;
+  const long long f = blockIdx.y, fs = f * a.nscan + s;
+  jprog_load_lut(s_lut, a, fs);
+  unsigned bits = 0;
+  if (i < sc.len)
+    jprog_block_items(a.e, sc, a.e.coef + f * a.e.nb * 64, i, sc.se ? (int)a.run[fs * a.e.nb + i] : 0,
+                      [&](int t, int v, unsigned, int n) { bits += (s_lut[t][v] & 255u) + (unsigned)n; },
+                      [&](unsigned long long, int n) { bits += (unsigned)n; });
+  unsigned total;
+  const unsigned at = vf_block_excl_scan<unsigned, 256>(bits, s_w, total);
+  if (i < sc.len) a.e.blk_off[fs * a.e.nb + i] = at;
+  if (threadIdx.x == 0) a.e.tile_sum[fs * a.e.tiles + blockIdx.x] = total;
+}
+
+// one workgroup per image: the tiles' bit offsets in the image's stream, scan behind scan, each from a byte boundary; the scans'
+// byte offsets, the image's bit count (whole bytes), and what stands in front of every scan's data in the file
+__global__ __launch_bounds__(256) void k_jprog_tile_scan(JprogArgs a) {
+  __shared__ unsigned long long s_w[4];
+  const long long f = blockIdx.x;
+  unsigned long long run = 0;
+  for (int s = 0; s < a.nscan; ++s) {
+    const long long fs = f * a.nscan + s;
+    run = (run + 7) & ~7ull;
+    if (threadIdx.x == 0) a.scan_start[fs] = run >> 3;
+    for (int base = 0; base < a.scan[s].tiles; base += 256) {
+      const int t = base + threadIdx.x;
+      const unsigned long long v = t < a.scan[s].tiles ? a.e.tile_sum[fs * a.e.tiles + t] : 0ull;
+      unsigned long long total;
+      const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(v, s_w, total);
+      if (t < a.scan[s].tiles) a.e.tile_off[fs * a.e.tiles + t] = run + e;
+      run += total;
+    }
+  }
+  if (threadIdx.x == 0) {
+    a.e.img_bits[f] = (run + 7) & ~7ull;
+    unsigned h = (unsigned)a.prefix_len;
+    for (int s = 0; s < a.nscan; ++s) {
+      const long long fs = f * a.nscan + s;
+      h += (unsigned)(a.dht_len[2 * fs] + a.dht_len[2 * fs + 1] + a.scan[s].sos_len);
+      a.hdr_before[fs] = h;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_jprog_write(JprogArgs a) {
+  __shared__ unsigned s_lut[2][256];
+  const int s = blockIdx.z;
+  const JprogScan& sc = a.scan[s];
+  if ((int)blockIdx.x >= sc.tiles) return;
+  const int i = blockIdx.x * JENC_TILE + threadIdx.x;
+  const long long f = blockIdx.y, fs = f * a.nscan + s;
+  jprog_load_lut(s_lut, a, fs);
+  if (i >= sc.len) return;
+  const unsigned long long at = a.e.tile_off[fs * a.e.tiles + blockIdx.x] + a.e.blk_off[fs * a.e.nb + i];
+  unsigned* dst = a.e.stream + f * a.e.cap_words + (long long)(at >> 5);
+  // as k_jenc_write: the dword the block starts in and the one it ends in are OR-ed, those between are stored
+  // ... and a block without a bit of its own (most blocks of a refinement scan over flat content) touches nothing
+  unsigned long long acc = 0;
+  int cnt = (int)(at & 31);
+  bool first = true, fresh = false;                // fresh: acc holds bits that are not in memory yet
+  auto put = [&](unsigned bits, int count) {       // count <= 32 on top of cnt < 32
+    acc = acc << count | bits;
+    cnt += count;
+    fresh = true;
+    if (cnt >= 32) {
+      cnt -= 32;
+      const unsigned word = (unsigned)(acc >> cnt);
+      if (first) atomicOr(dst, word);
+      else *dst = word;
+      first = false;
+      fresh = cnt > 0;
+      ++dst;
+      acc &= (1ull << cnt) - 1ull;
+    }
+  };
+  jprog_block_items(a.e, sc, a.e.coef + f * a.e.nb * 64, i, sc.se ? (int)a.run[fs * a.e.nb + i] : 0,
+                    [&](int t, int v, unsigned ext, int n) {
+                      const unsigned e = s_lut[t][v];
+                      put((e >> 8) << n | ext, (int)(e & 255u) + n);
+                    },
+                    [&](unsigned long long bits, int n) {
+                      if (n > 32) {
+                        put((unsigned)(bits >> 32), n - 32);
+                        put((unsigned)bits, 32);
+                      } else if (n) {
+                        put((unsigned)bits, n);
+                      }
+                    });
+  if (i + 1 == sc.len && (cnt & 7)) {              // the scan's last block fills its last byte with 1-bits
+    const int k = 8 - (cnt & 7);
+    acc = acc << k | ((1ull << k) - 1ull);
+    cnt += k;
+    fresh = true;
+  }
+  if (fresh) atomicOr(dst, (unsigned)(acc << (32 - cnt)));
+}
+
+__global__ __launch_bounds__(256) void k_jprog_ff_scan(JprogArgs a) {
+  __shared__ unsigned long long s_w[4];
+  const long long f = blockIdx.x;
+  const unsigned long long nbytes = a.e.img_bits[f] >> 3;
+  const long long used = (long long)((nbytes + JENC_CHUNK - 1) / JENC_CHUNK);
+  unsigned long long run = 0;
+  for (long long base = 0; base < used; base += 256) {
+    const long long c = base + threadIdx.x;
+    const unsigned long long v = c < used ? a.e.ff_cnt[f * a.e.chunks + c] : 0ull;
+    unsigned long long total;
+    const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(v, s_w, total);
+    if (c < used) a.e.ff_pref[f * a.e.chunks + c] = run + e;
+    run += total;
+  }
+  if (threadIdx.x == 0) a.e.offsets[f + 1] = (int64_t)(a.hdr_before[f * a.nscan + a.nscan - 1] + nbytes + run + 2);
+}
+
+// the DHT segments and the SOS of scan s of image f, ending at `end`
+__device__ __forceinline__ void jprog_put_scan_header(const JprogArgs& a, long long f, int s, unsigned char* end) {
+  const long long fs = f * a.nscan + s;
+  const int d0 = a.dht_len[2 * fs], d1 = a.dht_len[2 * fs + 1], sos = a.scan[s].sos_len;
+  unsigned char* p = end - (d0 + d1 + sos);
+  for (int i = 0; i < d0; ++i) *p++ = a.dht[2 * fs * JENC_DHT_STRIDE + i];
+  for (int i = 0; i < d1; ++i) *p++ = a.dht[(2 * fs + 1) * JENC_DHT_STRIDE + i];
+  for (int i = 0; i < sos; ++i) *p++ = a.scan[s].sos[i];
+}
+
+__global__ __launch_bounds__(256) void k_jprog_stuff(JprogArgs a) {
+  __shared__ unsigned s_w[4];
+  const long long f = blockIdx.y;
+  const unsigned long long bits = a.e.img_bits[f], nbytes = bits >> 3, begin = (unsigned long long)blockIdx.x * JENC_CHUNK;
+  if (begin >= nbytes) return;
+  unsigned char* file = a.e.out + a.e.offsets[f];
+  unsigned b[16];
+  const unsigned long long pos = begin + threadIdx.x * 16;
+  const int have = jenc_bytes16(a.e, f, bits, pos, b);
+  unsigned cnt = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) cnt += i < have && b[i] == 255u;
+  unsigned total;
+  const unsigned before = vf_block_excl_scan<unsigned, 256>(cnt, s_w, total);
+  const unsigned long long* start = a.scan_start + f * a.nscan;
+  const unsigned* hdr = a.hdr_before + f * a.nscan;
+  if (have) {
+    int s = 0;                                     // the scan of the thread's first byte: the last that starts at or before it
+    while (s + 1 < a.nscan && start[s + 1] <= pos) ++s;
+    unsigned char* dst = file + hdr[s] + begin + a.e.ff_pref[f * a.e.chunks + blockIdx.x] + threadIdx.x * 16 + before;
+    if (start[s] == pos) jprog_put_scan_header(a, f, s, dst);
+    unsigned long long next = s + 1 < a.nscan ? start[s + 1] : ~0ull;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (i < have) {
+        if (pos + i == next) {                     // the next scan begins with this byte: its header goes in front
+          ++s;
+          dst += hdr[s] - hdr[s - 1];
+          jprog_put_scan_header(a, f, s, dst);
+          next = s + 1 < a.nscan ? start[s + 1] : ~0ull;
+        }
+        *dst++ = (unsigned char)b[i];
+        if (b[i] == 255u) *dst++ = 0;
+      }
+  }
+  if (blockIdx.x == 0)
+    for (int i = threadIdx.x; i < a.prefix_len; i += 256) file[i] = a.prefix[i];
+  if (begin + JENC_CHUNK >= nbytes && threadIdx.x == 0) {
+    const int64_t size = a.e.offsets[f + 1] - a.e.offsets[f];
+    file[size - 2] = 0xFF;
+    file[size - 1] = 0xD9;
+  }
+}
+
+struct JprogPlan {
+  JencPlan b;                    // the geometry
+  int nscan;
+  long long cap_bytes;
+  int chunks;
+  size_t o_coef, o_blk, o_tsum, o_toff, o_bits, o_stream, o_ffc, o_ffp, o_sum, o_run, o_counts, o_lut, o_dht, o_dlen, o_sstart, o_hdr;
+  size_t ws_bytes, out_bytes;
+};
+
+int jprog_plan(const char* who, int n, int H, int W, int C, int subsampling, JprogPlan* p) {
+  if (int e = jenc_plan(who, n, H, W, C, subsampling, 0, 0, 0, &p->b)) return e;
+  const int nb = p->b.nb, S = p->nscan = C == 3 ? 10 : 6;
+  // every block at its bound, and a pad byte per scan
+  p->cap_bytes = vf_cdiv((long long)nb * (JPROG_BLOCK_BITS / 8) + S, JENC_CHUNK) * JENC_CHUNK;
+  p->chunks = (int)(p->cap_bytes / JENC_CHUNK);
+  const size_t walks = (size_t)n * S * nb, tiles = (size_t)n * S * p->b.tiles, tables = (size_t)n * S * 2;
+  VfCarve ws;
+  p->o_coef = ws.take((size_t)n * nb * 128);
+  p->o_blk = ws.take(walks * 4);
+  p->o_tsum = ws.take(tiles * 4);
+  p->o_toff = ws.take(tiles * 8);
+  p->o_bits = ws.take((size_t)n * 8);
+  p->o_stream = ws.take((size_t)n * p->cap_bytes);
+  p->o_ffc = ws.take((size_t)n * p->chunks * 4);
+  p->o_ffp = ws.take((size_t)n * p->chunks * 8);
+  p->o_sum = ws.take(walks);
+  p->o_run = ws.take(walks * 2);
+  p->o_counts = ws.take(tables * 256 * 4);
+  p->o_lut = ws.take(tables * 256 * 4);
+  p->o_dht = ws.take(tables * JENC_DHT_STRIDE);
+  p->o_dlen = ws.take(tables * 4);
+  p->o_sstart = ws.take((size_t)n * S * 8);
+  p->o_hdr = ws.take((size_t)n * S * 4);
+  p->ws_bytes = ws.at;
+  // every block at its bound and every scan's pad byte, every stream byte stuffed; the prefix, per scan two DHT segments and
+  // the SOS, EOI
+  p->out_bytes = (size_t)n * (((size_t)nb * (JPROG_BLOCK_BITS / 8) + S) * 2 + JPROG_PREFIX_CAP + (size_t)S * (2 * JENC_DHT_STRIDE + JPROG_SOS_CAP) + 2);
+  return 0;
+}
+
+// jcparam.c's jpeg_simple_progression: (component or -1 for all, Ss, Se, Ah, Al)
+constexpr int K_PROG_COLOUR[10][5] = {{-1, 0, 0, 0, 1}, {0, 1, 5, 0, 2},  {2, 1, 63, 0, 1}, {1, 1, 63, 0, 1}, {0, 6, 63, 0, 2},
+                                      {0, 1, 63, 2, 1}, {-1, 0, 0, 1, 0}, {2, 1, 63, 1, 0}, {1, 1, 63, 1, 0}, {0, 1, 63, 1, 0}};
+constexpr int K_PROG_GREY[6][5] = {{-1, 0, 0, 0, 1}, {0, 1, 5, 0, 2}, {0, 6, 63, 0, 2}, {0, 1, 63, 2, 1}, {-1, 0, 0, 1, 0}, {0, 1, 63, 1, 0}};
+
+// the scans with their walks and SOS segments, and the prefix: jenc_header's bytes up to its first DHT, SOF0 turned into SOF2
+void jprog_script(const JprogPlan& p, int H, int W, int C, int quality, JprogArgs* a) {
+  JencHdr hdr;
+  jenc_header(H, W, C, quality, p.b.hs, p.b.vs, 0, true, &hdr, a->e.quant);
+  a->prefix_len = hdr.split;
+  memcpy(a->prefix, hdr.w, (size_t)hdr.split);
+  a->prefix[hdr.split - (8 + 3 * C) - 1] = 0xC2;
+  a->nscan = p.nscan;
+  for (int s = 0; s < p.nscan; ++s) {
+    const int* k = C == 3 ? K_PROG_COLOUR[s] : K_PROG_GREY[s];
+    JprogScan& sc = a->scan[s];
+    sc.comp = k[0]; sc.ss = k[1]; sc.se = k[2]; sc.ah = k[3]; sc.al = k[4];
+    const bool dc = sc.se == 0;
+    sc.len = dc ? p.b.nb : sc.comp == 0 ? (int)(vf_cdiv(W, 8) * vf_cdiv(H, 8)) : p.b.mcux * p.b.mcuy;
+    sc.tiles = (int)vf_cdiv(sc.len, JENC_TILE);
+    sc.ntab = dc ? (sc.ah ? 0 : C == 3 ? 2 : 1) : 1;
+    sc.tc_th[0] = (unsigned char)(dc ? 0x00 : 0x10 | (sc.comp > 0));
+    sc.tc_th[1] = 0x01;
+    // jcmarker.c: a DC scan names no AC table, a DC refinement no table at all, an AC scan no DC table
+    const int comps = dc ? C : 1;
+    unsigned char* b = sc.sos;
+    *b++ = 0xFF; *b++ = 0xDA; *b++ = 0; *b++ = (unsigned char)(6 + 2 * comps); *b++ = (unsigned char)comps;
+    for (int c = 0; c < comps; ++c) {
+      const int id = dc ? c : sc.comp, t = id > 0;
+      *b++ = (unsigned char)(id + 1);
+      *b++ = (unsigned char)(dc ? (sc.ah ? 0 : t << 4) : t);
+    }
+    *b++ = (unsigned char)sc.ss; *b++ = (unsigned char)sc.se; *b++ = (unsigned char)(sc.ah << 4 | sc.al);
+    sc.sos_len = (int)(b - sc.sos);
+  }
+}
+
+int jprog_encode(const char* who, vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling,
+                 void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
+  JprogPlan p;
+  if (int e = jprog_plan(who, n, H, W, C, subsampling, &p)) return e;
+  VF_REQUIRE(quality >= 1 && quality <= 100, "%s: quality = %d (1 to 100)", who, quality);
+  char batch[64];
+  snprintf(batch, sizeof(batch), "%d frames of %dx%dx%d", n, H, W, C);
+  if (int e = vf_check_encode_entry(who, kind, "C", batch, ws_bytes, p.ws_bytes, out_cap, p.out_bytes)) return e;
+  JprogArgs a;
+  memset(&a, 0, sizeof(a));
+  jprog_script(p, H, W, C, quality, &a);
+  char* w = (char*)ws;
+  JencArgs& e = a.e;
+  e.src = src;
+  e.coef = (short*)(w + p.o_coef);
+  e.blk_off = (unsigned*)(w + p.o_blk);
+  e.tile_sum = (unsigned*)(w + p.o_tsum);
+  e.tile_off = (unsigned long long*)(w + p.o_toff);
+  e.img_bits = (unsigned long long*)(w + p.o_bits);
+  e.stream = (unsigned*)(w + p.o_stream);
+  e.ff_cnt = (unsigned*)(w + p.o_ffc);
+  e.ff_pref = (unsigned long long*)(w + p.o_ffp);
+  e.out = out;
+  e.offsets = offsets;
+  e.cap_words = p.cap_bytes / 4;
+  e.n = n; e.H = H; e.W = W; e.C = C; e.hs = p.b.hs; e.vs = p.b.vs;
+  e.mcux = p.b.mcux; e.mcuy = p.b.mcuy; e.bpm = p.b.bpm; e.nb = p.b.nb;
+  e.wb = (int)vf_cdiv(W, 8); e.hb = (int)vf_cdiv(H, 8);
+  e.tiles = p.b.tiles; e.chunks = p.chunks;
+  e.spb = p.b.nb; e.nseg = 1;
+  a.sum = (unsigned char*)(w + p.o_sum);
+  a.run = (unsigned short*)(w + p.o_run);
+  a.counts = (unsigned*)(w + p.o_counts);
+  a.lut = (unsigned*)(w + p.o_lut);
+  a.dht = (unsigned char*)(w + p.o_dht);
+  a.dht_len = (int*)(w + p.o_dlen);
+  a.scan_start = (unsigned long long*)(w + p.o_sstart);
+  a.hdr_before = (unsigned*)(w + p.o_hdr);
+  const int S = p.nscan;
+  const double px = (double)n * H * W * C, coef = (double)n * e.nb * 128;
+  const dim3 per_tile((unsigned)e.tiles, n), per_walk((unsigned)e.tiles, n, S), per_chunk((unsigned)e.chunks, n);
+  if (kind == 0) VF_LAUNCH_TIMED(ctx, "jpeg_prog_dct", 0.0, 4.0 * px + coef, k_jenc_dct<0>, per_tile, dim3(256), e);
+  else VF_LAUNCH_TIMED(ctx, "jpeg_prog_dct", 0.0, px + coef, k_jenc_dct<1>, per_tile, dim3(256), e);
+  VF_LAUNCH_CHECK();
+  {
+    VfProf prof(ctx, "jpeg_prog_sum", 0.0, coef * S / 2);
+    VF_CHECK_HIP(hipMemsetAsync(a.counts, 0, (size_t)n * S * 2 * 256 * 4, ctx->stream));
+    VF_CHECK_HIP(hipMemsetAsync(a.run, 0, (size_t)n * S * e.nb * 2, ctx->stream));
+    hipLaunchKernelGGL(k_jprog_sum, per_walk, dim3(256), 0, ctx->stream, a);
+    VF_LAUNCH_CHECK();
+  }
+  VF_LAUNCH_TIMED(ctx, "jpeg_prog_runs", 0.0, (double)n * S * e.nb, k_jprog_runs, dim3(S, n), dim3(64), a);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_prog_tables", 0.0, 0.0, k_jprog_table, dim3(2 * S, n), dim3(JENC_TABLE_THREADS), a);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_prog_size", 0.0, coef * S / 2, k_jprog_size, per_walk, dim3(256), a);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_prog_scan", 0.0, 12.0 * n * S * e.tiles, k_jprog_tile_scan, dim3(n), dim3(256), a);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_prog_clear", 0.0, 0.0, k_jenc_clear, per_chunk, dim3(256), e);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "jpeg_prog_write", 0.0, coef * S / 2, k_jprog_write, per_walk, dim3(256), a);
+  VF_LAUNCH_CHECK();
+  {
+    VfProf prof(ctx, "jpeg_prog_stuff", 0.0, 0.0);
+    hipLaunchKernelGGL(k_jenc_ff_count, per_chunk, dim3(256), 0, ctx->stream, e);
+    VF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jprog_ff_scan, dim3(n), dim3(256), 0, ctx->stream, a);
+    VF_LAUNCH_CHECK();
+    vf_launch_file_offsets(ctx->stream, e.offsets, n);
+    VF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jprog_stuff, per_chunk, dim3(256), 0, ctx->stream, a);
+    VF_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 }  // namespace
+
+VF_API int vf_jpeg_encode_prog_workspace_bytes(int n, int H, int W, int C, int subsampling, size_t* ws_bytes, size_t* out_bytes) {
+  JprogPlan p;
+  if (int e = jprog_plan("vf_jpeg_encode_prog_workspace_bytes", n, H, W, C, subsampling, &p)) return e;
+  if (ws_bytes) *ws_bytes = p.ws_bytes;
+  if (out_bytes) *out_bytes = p.out_bytes;
+  return 0;
+}
+
+VF_API int vf_jpeg_encode_prog(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling,
+                               void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
+  return jprog_encode("vf_jpeg_encode_prog", ctx, src, kind, n, H, W, C, quality, subsampling, ws, ws_bytes, out, out_cap, offsets);
+}
 
 VF_API int vf_jpeg_encode_workspace_bytes(int n, int H, int W, int C, int subsampling, size_t* ws_bytes, size_t* out_bytes) {
   return jenc_workspace_bytes("vf_jpeg_encode_workspace_bytes", n, H, W, C, subsampling, 0, 0, 0, ws_bytes, out_bytes);

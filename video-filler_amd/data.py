@@ -300,18 +300,24 @@ def encode_png(frames):
 
 
 # ------------------------------------------------------------------------------------------------ JPEG
-def _jpeg_options(who, restart_rows, restart_blocks, optimize):
-    """The encoder's options as (rows, blocks, optimize) of ints; ValueError naming the argument for a bad value."""
+def _jpeg_options(who, restart_rows, restart_blocks, optimize, progressive=False):
+    """The encoder's options as (rows, blocks, optimize, progressive) of ints; ValueError naming the argument for a bad value,
+    and for a restart interval asked of a progressive file."""
     import numbers
+    if not isinstance(progressive, (bool, np.bool_)):
+        raise ValueError("%s: progressive=%r is not True or False" % (who, progressive))
     for name, v in (("restart_rows", restart_rows), ("restart_blocks", restart_blocks)):
         if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v <= 65535:
             raise ValueError("%s: %s=%r is not an integer from 0 to 65535" % (who, name, v))
     if not isinstance(optimize, (bool, np.bool_)):
         raise ValueError("%s: optimize=%r is not True or False" % (who, optimize))
-    return int(restart_rows), int(restart_blocks), int(optimize)
+    for name, v in (("restart_rows", restart_rows), ("restart_blocks", restart_blocks)):
+        if progressive and v:
+            raise ValueError("%s: %s=%r with progressive=True (a progressive file has no restart intervals here)" % (who, name, v))
+    return int(restart_rows), int(restart_blocks), int(optimize), int(progressive)
 
 
-def encode_jpeg(frames, quality=75, subsampling="420", restart_rows=0, restart_blocks=0, optimize=False):
+def encode_jpeg(frames, quality=75, subsampling="420", restart_rows=0, restart_blocks=0, optimize=False, progressive=False):
     """image.save('x.jpg') / image.compressJPG of a batch of frames, encoded on the device in one call (vf_jpeg_encode): a
     list of `bytes`, one whole baseline JFIF file per frame, byte for byte what libjpeg's default compression — Pillow's
     save(format="JPEG", quality=quality, subsampling=...) — writes.  frames: uint8 N x H x W x C (taken as they are) or
@@ -321,7 +327,9 @@ def encode_jpeg(frames, quality=75, subsampling="420", restart_rows=0, restart_b
     restart_marker_rows, restart_marker_blocks and optimize, with the same bytes: a restart interval of so many rows of
     MCUs or of so many MCUs (0 to 65535 each; rows win, clamped to 65535 MCUs), which decode_jpeg decodes a segment per
     workgroup, and Huffman tables made from each file's own symbol counts (smaller files; the header differs from file to
-    file).  The defaults write the default file.  The files are what decode_jpeg reads.  A bad quality, subsampling,
+    file).  progressive: Pillow's progressive=True with the same bytes (vf_jpeg_encode_prog): SOF2, libjpeg's 10 scans (grey:
+    6), each behind its own optimal tables; optimize changes nothing then, as in libjpeg, and a non-zero restart_rows or
+    restart_blocks with it is a ValueError.  The defaults write the default file.  The files are what decode_jpeg reads.  A bad quality, subsampling,
     option, rank or dtype is a ValueError naming the argument.  One device-to-host copy brings the batch back."""
     import numbers
     from .backend import JPEG_SUBSAMPLING
@@ -329,7 +337,7 @@ def encode_jpeg(frames, quality=75, subsampling="420", restart_rows=0, restart_b
         raise ValueError("encode_jpeg: quality=%r is not an integer from 1 to 100" % (quality,))
     if subsampling not in JPEG_SUBSAMPLING:
         raise ValueError("encode_jpeg: subsampling=%r is not one of %s" % (subsampling, ", ".join(map(repr, sorted(JPEG_SUBSAMPLING)))))
-    opts = _jpeg_options("encode_jpeg", restart_rows, restart_blocks, optimize)
+    opts = _jpeg_options("encode_jpeg", restart_rows, restart_blocks, optimize, progressive)
     t = _as_frames("encode_jpeg", frames, 4)
     B = get_backend()
     return _files_from(*B.jpeg_encode(B.from_host(t).contiguous(), int(quality), subsampling, *opts))

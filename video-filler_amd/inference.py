@@ -164,16 +164,16 @@ def save_frames(dirname, outImages=None, inpaintImages=None, fullImages=None, **
 
 
 def save_frames_jpg(dirname, outImages=None, inpaintImages=None, fullImages=None, quality=75, subsampling="420", restart_rows=0,
-                    restart_blocks=0, optimize=False, **named):
+                    restart_blocks=0, optimize=False, progressive=False, **named):
     """save_frames with `image.save` given a .jpg name: dirname/pred_%d.jpg, inpaint_%d.jpg and orig_%d.jpg, the frames a
     JPEG folder of the loaders holds.  Same tensors, same rules, same order of the returned paths; all frames are encoded
     on the device in ONE call (data.encode_jpeg at `quality` and `subsampling`: libjpeg's default compression, byte for
-    byte; restart_rows, restart_blocks and optimize are encode_jpeg's) and the host only writes the files."""
+    byte; restart_rows, restart_blocks, optimize and progressive are encode_jpeg's) and the host only writes the files."""
     from .data import _jpeg_options, encode_jpeg
-    _jpeg_options("save_frames_jpg", restart_rows, restart_blocks, optimize)      # refused before the directory is made
+    _jpeg_options("save_frames_jpg", restart_rows, restart_blocks, optimize, progressive)      # refused before the directory is made
     return _save_frame_groups("save_frames_jpg", "jpg",
-                              lambda t: encode_jpeg(t, quality, subsampling, restart_rows, restart_blocks, optimize), dirname,
-                              outImages, inpaintImages, fullImages, named)
+                              lambda t: encode_jpeg(t, quality, subsampling, restart_rows, restart_blocks, optimize, progressive),
+                              dirname, outImages, inpaintImages, fullImages, named)
 
 
 def save_gifs(name, outImages=None, inpaintImages=None, fullImages=None, delay=10, **named):
@@ -343,14 +343,15 @@ def save_sheet(path, x, **display_args):
     return path
 
 
-def display_jpeg(x, quality=75, restart_rows=0, restart_blocks=0, optimize=False, **display_args):
+def display_jpeg(x, quality=75, restart_rows=0, restart_blocks=0, optimize=False, progressive=False, **display_args):
     """The payload of the training scripts' disp.image(x, ...) (train_vid_weighted.lua:553-588, train.lua likewise): the
     contact sheet display_tensor builds of x, compressed as one JPEG on the device (data.encode_jpeg at `quality`, 4:2:0
     for an RGB sheet; image.savePNG's byte rule is applied inside the encoder; restart_rows, restart_blocks and optimize
-    are encode_jpeg's: optimize=True is the smaller payload).  Returns the file's bytes."""
-    data._jpeg_options("display_jpeg", restart_rows, restart_blocks, optimize)      # refused before the sheet is built
+    and progressive are encode_jpeg's: optimize=True is the smaller payload, progressive=True the file a browser shows
+    while it arrives).  Returns the file's bytes."""
+    data._jpeg_options("display_jpeg", restart_rows, restart_blocks, optimize, progressive)      # refused before the sheet is built
     grid = display_tensor(x, **display_args)
-    (jpg,) = data.encode_jpeg(grid.unsqueeze(0), quality, "420", restart_rows, restart_blocks, optimize)
+    (jpg,) = data.encode_jpeg(grid.unsqueeze(0), quality, "420", restart_rows, restart_blocks, optimize, progressive)
     return jpg
 
 
