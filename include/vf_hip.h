@@ -492,7 +492,7 @@ int vf_jpeg_prog_coefficients_host(const unsigned char* data, size_t len, int su
  * test_more_complex.lua:102, demo.lua:51, and the frames vf_png_encode writes) on the device: the BYTES libpng gives
  * with grey below 8 bits and palettes expanded.  Supported: colour types 0, 2, 3, 4, 6 at bit depths 1, 2, 4, 8, no
  * interlace, sides up to 16384, any number of IDAT chunks, ancillary chunks, tRNS with a palette.  Unsupported (known
- * from the headers): 16-bit samples, Adam7, IDAT data above 256 MiB.
+ * from the headers): 16-bit samples, Adam7 (the *_full entries below take both), IDAT data above 256 MiB.
  * vf_png_inspect (host only, no GPU): walk the chunks of one file.  info (int64[12]) = {width, height, bit depth,
  * colour type, interlace, channels after expansion (1 - 4: what image.load(path) gives), IDAT bytes in total, IDAT
  * chunks, palette entries, tRNS entries, supported (0 / 1), inflated bytes expected H * (1 + ceil(W * bits / 8))};
@@ -526,6 +526,32 @@ int vf_png_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, i
 /* image.load(path, nc, 'float') on top of the decoded bytes: dst[i] = src[i] / 255 in float32, an IEEE division
  * (correctly rounded), n elements, DEVICE src and dst, on the context's stream. */
 int vf_png_bytes_to_float(vf_ctx* ctx, const unsigned char* src, float* dst, int64_t n);
+/* The full rule ("Interlaced and 16-bit files"): the three entries above keep their behaviour; these
+ * also take Adam7-interlaced files and 16-bit samples (colour types 0, 2, 4, 6; big-endian; a filter unit of up to 8
+ * bytes).  Adam7: the inflated stream holds up to seven sub-images, pass p = 1..7 taking the pixels (x0 + i dx,
+ * y0 + j dy) with (x0, y0, dx, dy) = (0,0,8,8) (4,0,8,8) (0,4,4,8) (2,0,4,4) (0,2,2,4) (1,0,2,2) (0,1,1,2), of
+ * w_p = ceil((W - x0) / dx) by h_p = ceil((H - y0) / dy) pixels; a pass with w_p or h_p zero is absent; each present
+ * pass has its own row length rb_p = ceil(w_p * samples * depth / 8), filter byte per row and zeros above its first
+ * row; the stream inflates to sum h_p * (1 + rb_p) bytes, else VF_PNG_BAD_LENGTH.  Decided: the uint8 result of a
+ * 16-bit sample is its HIGH byte (libpng's png_set_strip_16, Pillow's result).  Recalled, not checked against Torch:
+ * 'float' of a 16-bit file is sample / 65535 on the whole sample.  Still unsupported: a side above 16384, IDAT data
+ * above 256 MiB, an expected inflated size of 2^31 bytes or more (the decoder's sizes are int32), and by channels what
+ * vf_png_decode_workspace_bytes refuses.
+ * vf_png_inspect_full (host only, no GPU): vf_png_inspect's chunk walk and malformed-file errors; info[10], info[11]
+ * and reason follow the full rule; passes (int64[21], may be NULL) receives (w_p, h_p, rb_p) of the seven passes, zeros
+ * for an absent one; a file without interlace is one pass, the first. */
+int vf_png_inspect_full(const unsigned char* data, size_t len, int64_t* info, int64_t* passes, char* reason, int reason_cap);
+/* vf_png_decode_workspace_bytes and vf_png_decode under the full rule, with one more parameter.  out_kind 0: image i
+ * becomes uint8 H x W x C; 1: float32 H x W x C written by the expansion kernel, byte / 255 for files of up to 8 bits
+ * (the bits of vf_png_bytes_to_float) and sample / 65535 for 16-bit files, both IEEE divisions.  out_offs counts
+ * ELEMENTS of out (bytes or floats).  Files vf_png_decode takes may be in the batch and give its bytes.  The same
+ * contract otherwise: host files, one upload, three launches (inflate; unfilter, one wave per image and pass; expand),
+ * nothing allocated, nothing synchronised, VF_PNG_* per image in status. */
+int vf_png_decode_full_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int channels, int out_kind,
+                                       size_t* ws_bytes, size_t* stage_bytes);
+int vf_png_decode_full(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int out_kind,
+                       const int64_t* out_offs, void* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
+                       int32_t* status);
 
 /* ---- PNG encode (vf_png.hip) ---------------------------------------------------------------------------
  * image.save of test_vid.lua:138, test_vid_wholeim.lua:229-242 and test_more_complex.lua:200-214 on the device: a batch

@@ -96,6 +96,9 @@ SIGNATURES = {
     "vf_png_decode_workspace_bytes": (i32, [vp, vp, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_png_decode": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, sz, vp, sz, vp]),
     "vf_png_bytes_to_float": (i32, [vp, vp, vp, i64]),
+    "vf_png_inspect_full": (i32, [vp, sz, vp, vp, C.c_char_p, i32]),
+    "vf_png_decode_full_workspace_bytes": (i32, [vp, vp, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
+    "vf_png_decode_full": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp]),
     "vf_png_workspace_bytes": (i32, [i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_png_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_jpeg_encode_workspace_bytes": (i32, [i32, i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),

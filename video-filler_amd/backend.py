@@ -289,6 +289,8 @@ def jpeg_prog_coefficients(data, info=None, subseq_bytes=0):
 
 PNG_STATUS = {0: "ok", 1: "bad code", 2: "short data", 3: "bad distance", 4: "bad length", 5: "bad filter", 6: "bad Adler-32",
               7: "bad palette index"}
+_PNG_INFO_KEYS = ("width", "height", "bit_depth", "color_type", "interlace", "channels", "idat_bytes", "idat_chunks", "palette_entries",
+                  "trns_entries", "supported", "inflated_bytes")
 
 
 def png_inspect(data):
@@ -301,11 +303,31 @@ def png_inspect(data):
     why = C.create_string_buffer(160)
     if lib.vf_png_inspect(data, len(data), info, why, 160) != 0:
         raise ValueError(lib.vf_last_error().decode())
-    keys = ("width", "height", "bit_depth", "color_type", "interlace", "channels", "idat_bytes", "idat_chunks", "palette_entries",
-            "trns_entries", "supported", "inflated_bytes")
-    d = {k: int(v) for k, v in zip(keys, info)}
+    d = {k: int(v) for k, v in zip(_PNG_INFO_KEYS, info)}
     d["supported"] = bool(d["supported"])
     d["reason"] = why.value.decode()
+    return d
+
+
+def png_inspect_full(data, passes=True):
+    """png_inspect under the full rule (vf_png_inspect_full; no GPU needed), which also takes Adam7-interlaced and 16-bit
+    files: the same dict with the full rule's supported, reason and inflated_bytes (the sum of h * (1 + rowbytes) over the
+    passes), and passes: seven (width, height, rowbytes), zeros for an absent pass; a file without interlace is one pass,
+    the first.  passes=False leaves that key out (the batch decoder does not read it).  Raises ValueError for a malformed
+    file."""
+    lib = _lib.load()
+    data = bytes(data)
+    info = (C.c_int64 * 12)()
+    geo = (C.c_int64 * 21)() if passes else None
+    why = C.create_string_buffer(160)
+    if lib.vf_png_inspect_full(data, len(data), info, geo, why, 160) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    d = {k: int(v) for k, v in zip(_PNG_INFO_KEYS, info)}
+    d["supported"] = bool(d["supported"])
+    d["reason"] = why.value.decode()
+    if passes:
+        p = geo[:]
+        d["passes"] = list(zip(p[0::3], p[1::3], p[2::3]))
     return d
 
 
@@ -357,6 +379,18 @@ def png_decode_workspace_bytes(files, channels=None):
     ws_b, st_b = C.c_size_t(), C.c_size_t()
     if lib.vf_png_decode_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), len(files), int(channels or 0), C.byref(ws_b),
                                          C.byref(st_b)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return ws_b.value, st_b.value
+
+
+def png_decode_full_workspace_bytes(files, channels=None, out_kind=0):
+    """png_decode_workspace_bytes under the full rule (vf_png_decode_full_workspace_bytes; host only).  out_kind 0: uint8
+    output, 1: float32."""
+    lib = _lib.load()
+    data, offs = _joined(files)
+    ws_b, st_b = C.c_size_t(), C.c_size_t()
+    if lib.vf_png_decode_full_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), len(files), int(channels or 0), int(out_kind),
+                                              C.byref(ws_b), C.byref(st_b)) != 0:
         raise ValueError(lib.vf_last_error().decode())
     return ws_b.value, st_b.value
 
@@ -1058,16 +1092,17 @@ class HipBackend:
             setattr(self, attr, ws)
         return ws
 
-    def _decode(self, name, query, entry, files, sizes, query_args, call_args, *results, into=None):
+    def _decode(self, name, query, entry, files, sizes, query_args, call_args, *results, into=None, dtype=torch.uint8):
         """One batch-decoder call: the files back to back, image i's place in `out` from sizes[i], the bounds from `query`,
         the stage's scratch and its staging buffer of this turn, then `entry`.  -> (out, out_offs, status).  into: (out,
-        starts) of a buffer the caller owns, image i going to out[starts[i]:] (sizes is then unused); out_offs is starts."""
+        starts) of a buffer the caller owns, image i going to out[starts[i]:] (sizes is then unused); out_offs is starts.
+        dtype: the elements of `out`, which sizes and the offsets count."""
         n = len(files)
         data, offs = _joined(files)
         offs_p = offs.ctypes.data_as(C.c_void_p)
         if into is not None:
             out, out_offs = into[0], np.ascontiguousarray(into[1], np.int64)
-            assert out.dtype == torch.uint8 and out.device == self.device and len(out_offs) >= n
+            assert out.dtype == dtype and out.device == self.device and len(out_offs) >= n
         else:
             out_offs = np.zeros(n + 1, np.int64)
             out_offs[1:] = np.cumsum(sizes)
@@ -1080,7 +1115,7 @@ class HipBackend:
         stager = getattr(self, attr)
         stage = stager.take(st_b.value)
         if into is None:
-            out = torch.empty(max(int(out_offs[-1]), 1), dtype=torch.uint8, device=self.device)
+            out = torch.empty(max(int(out_offs[-1]), 1), dtype=dtype, device=self.device)
         status = torch.empty(n, dtype=torch.int32, device=self.device)
         self._c(entry, data, offs_p, n, *call_args, out_offs.ctypes.data_as(C.c_void_p), _ptr(out), C.c_void_p(stage.data_ptr()),
                 stage.numel(), _ptr(ws), ws.numel(), _ptr(status), *(r if isinstance(r, C.c_void_p) else _ptr(r) for r in results))
@@ -1126,6 +1161,17 @@ class HipBackend:
         return self._decode("pngd", "vf_png_decode_workspace_bytes", "vf_png_decode", files,
                             [s["height"] * s["width"] * (channels or s["channels"]) for s in shapes], (int(channels or 0),),
                             (int(channels or 0),))
+
+    def png_decode_full(self, files, channels=None, infos=None, out_kind=0):
+        """png_decode under the full rule (vf_png_decode_full): Adam7-interlaced and 16-bit files too.  out_kind 0: one
+        uint8 buffer, a 16-bit sample giving its high byte; 1: one float32 buffer written by the expansion kernel, byte / 255
+        for files of up to 8 bits and sample / 65535 for 16-bit files.  -> (out, offsets, status), the offsets counting
+        elements.  infos: the files' png_inspect_full results, if the caller has them."""
+        shapes = infos if infos is not None else [png_inspect_full(f) for f in files]
+        return self._decode("pngd", "vf_png_decode_full_workspace_bytes", "vf_png_decode_full", files,
+                            [s["height"] * s["width"] * (channels or s["channels"]) for s in shapes],
+                            (int(channels or 0), int(out_kind)), (int(channels or 0), int(out_kind)),
+                            dtype=torch.float32 if out_kind else torch.uint8)
 
     def png_bytes_to_float(self, t):
         """image.load(path, nc, 'float') on top of decoded bytes: a device uint8 tensor -> float32 of the same shape,

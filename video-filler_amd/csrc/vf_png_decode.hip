@@ -1,7 +1,9 @@
 // vf_png_decode.hip — batched PNG decode on the device: inflate, unfilter, expand.
 //   * vf_png_inspect (host only): chunks, IHDR, PLTE / tRNS, the zlib header, supported or why not;
 //   * vf_png_decode_workspace_bytes: device workspace and host staging sizes of one batch;
-//   * vf_png_decode: N files -> N uint8 H x W x C images at caller-given offsets of one buffer.
+//   * vf_png_decode: N files -> N uint8 H x W x C images at caller-given offsets of one buffer;
+//   * vf_png_inspect_full, vf_png_decode_full_workspace_bytes, vf_png_decode_full: the same for the full rule, which also
+//     takes Adam7-interlaced and 16-bit files and writes uint8 or float32 (the last section of this comment).
 // Pipeline (three launches, whatever N): the host walks the chunks, checks the CRCs, concatenates every file's IDAT
 // payloads behind one another (minus the two zlib header bytes) and packs them with PLTE / tRNS and one descriptor per
 // image into one staging buffer -> one upload.  Then
@@ -13,6 +15,12 @@
 //   k_pngd_expand    one thread per output pixel: sub-byte samples, palette and tRNS, alpha drop, grey replication.
 // Everything is integer arithmetic.  A corrupt stream ends in the image's status word: every read of the compressed
 // bytes is bounded by the stream's length, every store by the expected inflated size.
+// The full rule runs the same k_pngd_inflate over its own descriptor (PngdFull: the image's seven passes' sizes and places;
+// a plain file is the one-pass case) with the expected size sum h_p * (1 + rb_p), then
+//   k_pngd_unfilter_full  one wave per (image, pass): the same 64-row wavefront over the pass's h_p x rb_p, a filter unit of
+//                         up to 8 bytes (16-bit RGBA) in a 64-bit register when it is above 4;
+//   k_pngd_expand_full    one thread per output pixel: its pass from (x & 7, y & 7), its place inside the pass, 16-bit
+//                         samples big-endian; uint8 (a 16-bit sample's high byte) or float32 (byte / 255, sample / 65535).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -93,14 +101,28 @@ struct InflateLds {
 };
 static_assert(2 * sizeof(InflateLds) <= 160 * 1024, "k_pngd_inflate: two blocks per CU (160 KiB of LDS)");
 
-struct PngdBatch {
-  const PngdImage* img;
+// the full rule's descriptor: vf_png_decode's, then the passes.  A plain file has one pass, the first; an absent pass has
+// ph 0.  pinf / praw: the pass's first byte behind im.inf_off / im.raw_off (or im.out_off when direct)
+struct PngdFull {
+  PngdImage im;                // out_off counts ELEMENTS of the output (bytes or floats)
+  int32_t lace, out_kind;      // Adam7; 0: uint8, 1: float32
+  int32_t ph[7], prb[7], pinf[7], praw[7];   // rows and bytes per row of each pass, its first byte in either buffer
+};
+static_assert(sizeof(PngdImage) == 1112 && sizeof(PngdFull) == 1232, "DESIGN.md 5.6 states the descriptors' sizes");
+VF_HD const PngdImage& pngd_base(const PngdImage& d) { return d; }
+VF_HD const PngdImage& pngd_base(const PngdFull& d) { return d.im; }
+
+template <class Img>
+struct PngdBatchT {
+  const Img* img;
   const uint8_t* streams;
   uint8_t* inf;
   uint8_t* raw;
   uint8_t* out;
   int32_t* status;
 };
+using PngdBatch = PngdBatchT<PngdImage>;
+using PngdFullBatch = PngdBatchT<PngdFull>;
 
 __constant__ uint16_t c_lbase[29] = {3,  4,  5,  6,  7,  8,  9,  10, 11,  13,  15,  17,  19,  23, 27,
                                                       31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
@@ -517,10 +539,11 @@ VF_HD void pngd_ctl_init(PngdCtl& c, int slen) {
 }
 
 // one block per image
-__global__ __launch_bounds__(kInfThreads) void k_pngd_inflate(const PngdBatch B) {
+template <class Img>
+__global__ __launch_bounds__(kInfThreads) void k_pngd_inflate(const PngdBatchT<Img> B) {
   __shared__ InflateLds L;
   const int t = threadIdx.x;
-  const PngdImage& im = B.img[blockIdx.x];
+  const PngdImage& im = pngd_base(B.img[blockIdx.x]);
   const uint8_t* stream = B.streams + im.src;
   const uint32_t* src32 = (const uint32_t*)stream;
   const uint32_t ndw = ((uint32_t)im.slen + 3) >> 2;
@@ -680,6 +703,140 @@ __global__ void k_pngd_expand(const PngdBatch B) {
       o[2] = (uint8_t)b;
     }
     if (oc == 4) o[3] = (uint8_t)al;
+  }
+}
+
+// ------------------------------------------------------------------------------------- the full rule: Adam7 and 16 bits
+__constant__ uint8_t c_a7_pass[64] = {0, 5, 3, 5, 1, 5, 3, 5, 6, 6, 6, 6, 6, 6, 6, 6, 4, 5, 4, 5, 4, 5, 4, 5, 6, 6, 6, 6, 6, 6, 6, 6,
+                                      2, 5, 3, 5, 2, 5, 3, 5, 6, 6, 6, 6, 6, 6, 6, 6, 4, 5, 4, 5, 4, 5, 4, 5, 6, 6, 6, 6, 6, 6, 6, 6};
+__constant__ uint8_t c_a7_x0[7] = {0, 4, 0, 2, 0, 1, 0}, c_a7_y0[7] = {0, 0, 4, 0, 2, 0, 1};
+__constant__ uint8_t c_a7_dxs[7] = {3, 3, 2, 2, 1, 1, 0}, c_a7_dys[7] = {3, 3, 3, 2, 2, 1, 1};   // log2 of dx, dy
+
+// k_pngd_unfilter's wavefront over one pass of h rows of rb bytes; U holds one filter unit (bpp bytes).  A filter byte above
+// 4 is the image's BAD_FILTER, through atomicMax: the passes' waves share the status word
+template <class U>
+VF_HD void pngd_unfilter_pass(const uint8_t* in, uint8_t* dst, int H, int rb, int bpp, int32_t* status, int lane) {
+  const int nx = rb / bpp;
+  const int64_t stride = (int64_t)rb + 1;
+  for (int band = 0; band < H; band += 64) {
+    const int r = band + lane;
+    const bool active = r < H;
+    const int ft = active ? in[r * stride] : 0;
+    if (__any(ft > 4)) {
+      if (lane == 0) atomicMax(status, (int)VF_PNG_BAD_FILTER);
+      return;
+    }
+    const uint8_t* src = in + r * stride + 1;
+    uint8_t* row = dst + (int64_t)r * rb;
+    const uint8_t* above = dst + (int64_t)(band - 1) * rb;    // read by lane 0 when band > 0
+    const int rows = min(64, H - band);
+    U cur = 0, a = 0, c = 0;
+    for (int step = 0; step < nx + rows - 1; ++step) {
+      U up = __shfl_up(cur, 1);                               // two shuffles for a 64-bit unit
+      const int x = step - lane;
+      const bool on = active && x >= 0 && x < nx;
+      if (lane == 0) {
+        up = 0;
+        if (band > 0 && on)
+          for (int k = 0; k < bpp; ++k) up |= (U)above[(int64_t)x * bpp + k] << (8 * k);
+      }
+      if (on) {
+        U o = 0;
+        for (int k = 0; k < bpp; ++k) {
+          const int f = src[(int64_t)x * bpp + k];
+          const int av = (int)(a >> (8 * k)) & 255, bv = (int)(up >> (8 * k)) & 255, cv = (int)(c >> (8 * k)) & 255;
+          const int pred = ft == 0 ? 0 : ft == 1 ? av : ft == 2 ? bv : ft == 3 ? (av + bv) >> 1 : pngd_paeth(av, bv, cv);
+          const int v = (f + pred) & 255;
+          row[(int64_t)x * bpp + k] = (uint8_t)v;
+          o |= (U)v << (8 * k);
+        }
+        cur = o;
+        a = o;
+        c = up;
+      }
+    }
+    __syncthreads();   // the band's last row is in memory before lane 0 of the next band reads it
+  }
+}
+
+// one wave per (image, pass): block 7 * i + p.  An absent pass returns at once
+__global__ __launch_bounds__(64) void k_pngd_unfilter_full(const PngdFullBatch B) {
+  const int i = blockIdx.x / 7, p = blockIdx.x % 7;
+  const PngdFull& d = B.img[i];
+  const int h = d.ph[p];
+  if (h == 0 || B.status[i] != 0) return;
+  const uint8_t* in = B.inf + d.im.inf_off + d.pinf[p];
+  uint8_t* dst = (d.im.direct ? B.out + d.im.out_off : B.raw + d.im.raw_off) + d.praw[p];
+  if (d.im.bpp <= 4) pngd_unfilter_pass<uint32_t>(in, dst, h, d.prb[p], d.im.bpp, B.status + i, threadIdx.x);
+  else pngd_unfilter_pass<unsigned long long>(in, dst, h, d.prb[p], d.im.bpp, B.status + i, threadIdx.x);
+}
+
+// one thread per output pixel
+__global__ void k_pngd_expand_full(const PngdFullBatch B) {
+  const PngdFull& d = B.img[blockIdx.y];
+  const PngdImage& im = d.im;
+  if (im.direct || B.status[blockIdx.y] != 0) return;
+  const uint8_t* raw = B.raw + im.raw_off;
+  const int64_t npix = (int64_t)im.W * im.H;
+  const int depth = im.depth, oc = im.oc;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(i / im.W), x = (int)(i % im.W);
+    int px = x;                                               // the pixel's place in its pass, the pass's rows
+    const uint8_t* row;
+    if (d.lace) {
+      const int p = c_a7_pass[(y & 7) * 8 + (x & 7)];
+      px = (x - c_a7_x0[p]) >> c_a7_dxs[p];
+      row = raw + d.praw[p] + (int64_t)((y - c_a7_y0[p]) >> c_a7_dys[p]) * d.prb[p];
+    } else {
+      row = raw + (int64_t)y * im.rb;
+    }
+    int s[4] = {0, 0, 0, 255};
+    if (depth < 8) {                                          // colour types 0 and 3 only: one sample per pixel, MSB first
+      const int bit = px * depth;
+      const int v = (row[bit >> 3] >> (8 - depth - (bit & 7))) & ((1 << depth) - 1);
+      s[0] = im.ctype == 3 ? v : v * (255 / ((1 << depth) - 1));
+    } else if (depth == 8) {
+      for (int k = 0; k < im.rc; ++k) s[k] = row[(int64_t)px * im.rc + k];
+    } else {                                                  // 16 bits, big-endian
+      for (int k = 0; k < im.rc; ++k) {
+        const uint8_t* q = row + ((int64_t)px * im.rc + k) * 2;
+        s[k] = (q[0] << 8) | q[1];
+      }
+    }
+    int v[4];                                                 // the output's channels
+    if (im.ctype == 3) {
+      const int ix = s[0];
+      if (ix >= im.nplte) {
+        atomicMax(B.status + blockIdx.y, (int)VF_PNG_BAD_INDEX);
+        continue;
+      }
+      v[0] = im.plte[3 * ix];
+      v[1] = im.plte[3 * ix + 1];
+      v[2] = im.plte[3 * ix + 2];
+      v[3] = ix < im.ntrns ? im.trns[ix] : 255;
+    } else if (im.ctype == 0 || im.ctype == 4) {
+      v[0] = s[0];
+      if (oc == 2) {
+        v[1] = s[1];
+      } else {
+        v[1] = v[2] = s[0];
+        v[3] = s[1];
+      }
+    } else {
+      v[0] = s[0];
+      v[1] = s[1];
+      v[2] = s[2];
+      v[3] = s[3];
+    }
+    if (d.out_kind == 0) {
+      uint8_t* o = B.out + im.out_off + i * oc;
+      const int sh = depth == 16 ? 8 : 0;                     // a 16-bit sample's high byte
+      for (int k = 0; k < oc; ++k) o[k] = (uint8_t)(v[k] >> sh);
+    } else {
+      float* o = (float*)B.out + im.out_off + i * oc;
+      const float top = depth == 16 ? 65535.f : 255.f;
+      for (int k = 0; k < oc; ++k) o[k] = __fdiv_rn((float)v[k], top);
+    }
   }
 }
 
@@ -941,47 +1098,154 @@ int pngd_plan(const uint8_t* data, const int64_t* offs, int n, int channels, Png
   return 0;
 }
 
+// the descriptor's part that both rules share, and the image's stream into the upload: every IDAT payload behind the one
+// before, minus the stream's first two bytes (the zlib header), zero-padded.  -> the room the stream takes
+int64_t pngd_fill(PngdImage& im, const PngParsed& P, const uint8_t* d, int oc, bool direct, int64_t expect, uint8_t* streams,
+                  int64_t sc, int64_t inf, int64_t raw, int64_t out_off) {
+  im.W = (int32_t)P.W;
+  im.H = (int32_t)P.H;
+  im.depth = P.depth;
+  im.ctype = P.ctype;
+  im.rb = (int32_t)P.rb;
+  im.bpp = std::max(1, P.rc * P.depth / 8);
+  im.rc = P.rc;
+  im.oc = oc;
+  im.nplte = P.nplte;
+  im.ntrns = P.ctype == 3 ? P.ntrns : 0;
+  im.direct = direct ? 1 : 0;
+  memcpy(im.plte, P.plte, 768);
+  memcpy(im.trns, P.trns, 256);
+  im.expect = (int32_t)expect;
+  im.src = sc;
+  im.slen = (int32_t)(P.idat_bytes - 2);
+  im.inf_off = inf;
+  im.raw_off = raw;
+  im.out_off = out_off;
+  int64_t skip = 2, at = 0;
+  for (const auto& c : P.idat) {
+    const int64_t s = std::min(skip, c.second);
+    skip -= s;
+    memcpy(streams + sc + at, d + c.first + s, (size_t)(c.second - s));
+    at += c.second - s;
+  }
+  const int64_t room = (int64_t)vf_up256((size_t)im.slen + 8);
+  memset(streams + sc + at, 0, (size_t)(room - at));
+  return room;
+}
+
 void pngd_pack(const uint8_t* data, const int64_t* offs, int n, const int64_t* out_offs, const PngdPlan& L, uint8_t* st) {
   PngdImage* imgs = (PngdImage*)(st + L.o_img);
   uint8_t* streams = st + L.o_streams;
   int64_t sc = 0, inf = 0, raw = 0;
   for (int i = 0; i < n; ++i) {
     const PngParsed& P = L.P[i];
-    const uint8_t* d = data + offs[i];
     PngdImage& im = imgs[i];
     memset(&im, 0, sizeof(im));
-    im.W = (int32_t)P.W;
-    im.H = (int32_t)P.H;
-    im.depth = P.depth;
-    im.ctype = P.ctype;
-    im.rb = (int32_t)P.rb;
-    im.bpp = std::max(1, P.rc * P.depth / 8);
-    im.rc = P.rc;
-    im.oc = L.oc[i];
-    im.nplte = P.nplte;
-    im.ntrns = P.ctype == 3 ? P.ntrns : 0;
-    im.direct = pngd_direct(P, im.oc) ? 1 : 0;
-    memcpy(im.plte, P.plte, 768);
-    memcpy(im.trns, P.trns, 256);
-    im.expect = (int32_t)P.inflated;
-    im.src = sc;
-    im.slen = (int32_t)(P.idat_bytes - 2);
-    im.inf_off = inf;
-    im.raw_off = raw;
-    im.out_off = out_offs[i];
-    // every IDAT payload behind the one before, minus the stream's first two bytes (the zlib header)
-    int64_t skip = 2, at = 0;
-    for (const auto& c : P.idat) {
-      const int64_t s = std::min(skip, c.second);
-      skip -= s;
-      memcpy(streams + sc + at, d + c.first + s, (size_t)(c.second - s));
-      at += c.second - s;
-    }
-    const int64_t room = (int64_t)vf_up256((size_t)im.slen + 8);
-    memset(streams + sc + at, 0, (size_t)(room - at));
-    sc += room;
+    sc += pngd_fill(im, P, data + offs[i], L.oc[i], pngd_direct(P, L.oc[i]), P.inflated, streams, sc, inf, raw, out_offs[i]);
     inf += (int64_t)vf_up256((size_t)P.inflated);
     if (!im.direct) raw += (int64_t)vf_up256((size_t)(P.H * P.rb));
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ host side: full rule
+struct PngFull {
+  int64_t w[7] = {}, h[7] = {}, rb[7] = {};   // zeros for an absent pass; a plain file is one pass, the first
+  int64_t inflated = 0, raw = 0;              // sum h_p * (1 + rb_p), sum h_p * rb_p
+  bool supported = false;
+  std::string why;
+};
+
+// the full rule over a parsed file: the passes, the inflated size they promise, supported or why not
+void png_full_rule(const PngParsed& P, PngFull& F) {
+  static const int x0[7] = {0, 4, 0, 2, 0, 1, 0}, y0[7] = {0, 0, 4, 0, 2, 0, 1}, dx[7] = {8, 8, 4, 4, 2, 2, 1}, dy[7] = {8, 8, 8, 4, 4, 2, 2};
+  for (int p = 0; p < (P.lace ? 7 : 1); ++p) {
+    const int64_t w = P.lace ? std::max<int64_t>(0, (P.W - x0[p] + dx[p] - 1) / dx[p]) : P.W;
+    const int64_t h = P.lace ? std::max<int64_t>(0, (P.H - y0[p] + dy[p] - 1) / dy[p]) : P.H;
+    if (w == 0 || h == 0) continue;
+    F.w[p] = w;
+    F.h[p] = h;
+    F.rb[p] = (w * P.rc * P.depth + 7) / 8;
+    F.inflated += h * (1 + F.rb[p]);
+    F.raw += h * F.rb[p];
+  }
+  if (P.W > kPngdMaxSide || P.H > kPngdMaxSide) F.why = "larger than 16384 per side";
+  else if (P.idat_bytes > kPngdMaxIdat) F.why = "IDAT data above 256 MiB";
+  else if (F.inflated >= ((int64_t)1 << 31)) F.why = "inflated size of 2^31 bytes or more (the decoder's sizes are int32)";
+  F.supported = F.why.empty();
+}
+
+struct PngdFullPlan : PngdPlan {
+  std::vector<PngFull> F;
+};
+
+inline bool pngd_full_direct(const PngParsed& P, int oc, int out_kind) { return !P.lace && out_kind == 0 && pngd_direct(P, oc); }
+
+int pngd_plan_full(const uint8_t* data, const int64_t* offs, int n, int channels, int out_kind, PngdFullPlan& L, bool crc) {
+  VF_REQUIRE(n > 0 && data && offs, "vf_png_decode_full: empty batch");
+  VF_REQUIRE(n <= 65535, "vf_png_decode_full: %d files in one batch (65535 at most)", n);
+  VF_REQUIRE(channels == 0 || channels == 1 || channels == 3, "vf_png_decode_full: channels %d is not 0 (the file's), 1 or 3", channels);
+  VF_REQUIRE(out_kind == 0 || out_kind == 1, "vf_png_decode_full: out_kind %d is not 0 (uint8) or 1 (float32)", out_kind);
+  L.P.resize(n);
+  L.F.resize(n);
+  L.oc.resize(n);
+  for (int i = 0; i < n; ++i) {
+    std::string msg;
+    VF_REQUIRE(offs[i + 1] >= offs[i], "vf_png_decode_full: offsets decrease at image %d", i);
+    PngParsed& P = L.P[i];
+    PngFull& F = L.F[i];
+    if (png_parse(data + offs[i], offs[i + 1] - offs[i], P, msg, crc)) {
+      vf_set_error("vf_png_decode_full: image %d: %s", i, msg.c_str());
+      return 2;
+    }
+    png_full_rule(P, F);
+    std::string why = F.why;
+    if (F.supported) L.oc[i] = png_out_channels(P, channels, why);
+    if (!F.supported || !L.oc[i]) {
+      vf_set_error("vf_png_decode_full: image %d: unsupported: %s", i, why.c_str());
+      return 3;
+    }
+    L.stream_bytes += (int64_t)vf_up256((size_t)(P.idat_bytes - 2) + 8);
+    L.inf_bytes += (int64_t)vf_up256((size_t)F.inflated);
+    if (!pngd_full_direct(P, L.oc[i], out_kind)) L.raw_bytes += (int64_t)vf_up256((size_t)F.raw);
+    L.max_pix = std::max(L.max_pix, P.W * P.H);
+  }
+  VfCarve ws;
+  L.o_img = ws.take(sizeof(PngdFull) * n);
+  L.o_streams = ws.take((size_t)L.stream_bytes);
+  L.stage = ws.at;
+  L.o_inf = ws.take((size_t)L.inf_bytes);
+  L.o_raw = ws.take((size_t)L.raw_bytes);
+  L.ws = ws.at;
+  return 0;
+}
+
+void pngd_pack_full(const uint8_t* data, const int64_t* offs, int n, int out_kind, const int64_t* out_offs, const PngdFullPlan& L,
+                    uint8_t* st) {
+  PngdFull* imgs = (PngdFull*)(st + L.o_img);
+  uint8_t* streams = st + L.o_streams;
+  int64_t sc = 0, inf = 0, raw = 0;
+  for (int i = 0; i < n; ++i) {
+    const PngParsed& P = L.P[i];
+    const PngFull& F = L.F[i];
+    const uint8_t* d = data + offs[i];
+    PngdFull& f = imgs[i];
+    memset(&f, 0, sizeof(f));
+    PngdImage& im = f.im;
+    const int64_t room = pngd_fill(im, P, d, L.oc[i], pngd_full_direct(P, L.oc[i], out_kind), F.inflated, streams, sc, inf, raw, out_offs[i]);
+    f.lace = P.lace;
+    f.out_kind = out_kind;
+    int64_t pi = 0, pr = 0;
+    for (int p = 0; p < 7; ++p) {
+      f.ph[p] = (int32_t)F.h[p];
+      f.prb[p] = (int32_t)F.rb[p];
+      f.pinf[p] = (int32_t)pi;
+      f.praw[p] = (int32_t)pr;
+      pi += F.h[p] * (1 + F.rb[p]);
+      pr += F.h[p] * F.rb[p];
+    }
+    sc += room;
+    inf += (int64_t)vf_up256((size_t)F.inflated);
+    if (!im.direct) raw += (int64_t)vf_up256((size_t)F.raw);
   }
 }
 
@@ -1044,12 +1308,78 @@ VF_API int vf_png_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* 
     VF_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t) * n, st));
   }
   const double inf = (double)L.inf_bytes;
-  VF_LAUNCH_TIMED(ctx, "pngd_inflate", 0.0, (double)L.stream_bytes + inf, k_pngd_inflate, dim3((unsigned)n), dim3(kInfThreads), B);
+  VF_LAUNCH_TIMED(ctx, "pngd_inflate", 0.0, (double)L.stream_bytes + inf, k_pngd_inflate<PngdImage>, dim3((unsigned)n), dim3(kInfThreads), B);
   VF_LAUNCH_CHECK();
   VF_LAUNCH_TIMED(ctx, "pngd_unfilter", 0.0, 2.0 * inf, k_pngd_unfilter, dim3((unsigned)n), dim3(64), B);
   VF_LAUNCH_CHECK();
   const unsigned gp = (unsigned)std::min<int64_t>(std::max<int64_t>(1, vf_cdiv(L.max_pix, 256)), 4096);
   VF_LAUNCH_TIMED(ctx, "pngd_expand", 0.0, 2.0 * (double)L.raw_bytes, k_pngd_expand, dim3(gp, n), dim3(256), B);
+  VF_LAUNCH_CHECK();
+  return 0;
+}
+
+VF_API int vf_png_inspect_full(const unsigned char* data, size_t len, int64_t* info, int64_t* passes, char* reason, int reason_cap) {
+  VF_REQUIRE(data && info, "vf_png_inspect_full: NULL argument");
+  PngParsed P;
+  std::string msg;
+  const int rc = png_parse(data, (int64_t)len, P, msg, true);
+  if (rc) {
+    vf_set_error("vf_png_inspect_full: %s", msg.c_str());
+    return rc;
+  }
+  PngFull F;
+  png_full_rule(P, F);
+  const int64_t v[12] = {P.W, P.H, P.depth, P.ctype, P.lace, P.fc, P.idat_bytes, P.idat_chunks, P.nplte, P.ntrns, F.supported ? 1 : 0,
+                         F.inflated};
+  memcpy(info, v, sizeof v);
+  for (int p = 0; passes && p < 7; ++p) {
+    passes[3 * p] = F.w[p];
+    passes[3 * p + 1] = F.h[p];
+    passes[3 * p + 2] = F.rb[p];
+  }
+  if (reason && reason_cap > 0) snprintf(reason, (size_t)reason_cap, "%s", F.why.c_str());
+  return 0;
+}
+
+VF_API int vf_png_decode_full_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int channels, int out_kind,
+                                              size_t* ws_bytes, size_t* stage_bytes) {
+  PngdFullPlan L;
+  if (int e = pngd_plan_full(data, offs, n, channels, out_kind, L, false)) return e;   // vf_png_decode_full checks the CRCs
+  if (ws_bytes) *ws_bytes = L.ws;
+  if (stage_bytes) *stage_bytes = L.stage;
+  return 0;
+}
+
+VF_API int vf_png_decode_full(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int out_kind,
+                              const int64_t* out_offs, void* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
+                              int32_t* status) {
+  VF_REQUIRE(out && out_offs && stage && ws && status, "vf_png_decode_full: NULL argument");
+  PngdFullPlan L;
+  if (int e = pngd_plan_full(data, offs, n, channels, out_kind, L, true)) return e;
+  VF_REQUIRE(stage_bytes >= L.stage && ws_bytes >= L.ws, "vf_png_decode_full: staging %zu / workspace %zu bytes, need %zu / %zu",
+             stage_bytes, ws_bytes, L.stage, L.ws);
+  pngd_pack_full(data, offs, n, out_kind, out_offs, L, (uint8_t*)stage);
+  uint8_t* w = (uint8_t*)ws;
+  PngdFullBatch B;
+  B.img = (const PngdFull*)(w + L.o_img);
+  B.streams = w + L.o_streams;
+  B.inf = w + L.o_inf;
+  B.raw = w + L.o_raw;
+  B.out = (uint8_t*)out;
+  B.status = status;
+  hipStream_t st = ctx->stream;
+  {
+    VfRange r("pngd_upload");
+    VF_CHECK_HIP(hipMemcpyAsync(w, stage, L.stage, hipMemcpyHostToDevice, st));
+    VF_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t) * n, st));
+  }
+  const double inf = (double)L.inf_bytes;
+  VF_LAUNCH_TIMED(ctx, "pngd_inflate", 0.0, (double)L.stream_bytes + inf, k_pngd_inflate<PngdFull>, dim3((unsigned)n), dim3(kInfThreads), B);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "pngd_unfilter_full", 0.0, 2.0 * inf, k_pngd_unfilter_full, dim3(7u * (unsigned)n), dim3(64), B);
+  VF_LAUNCH_CHECK();
+  const unsigned gp = (unsigned)std::min<int64_t>(std::max<int64_t>(1, vf_cdiv(L.max_pix, 256)), 4096);
+  VF_LAUNCH_TIMED(ctx, "pngd_expand_full", 0.0, 2.0 * (double)L.raw_bytes, k_pngd_expand_full, dim3(gp, n), dim3(256), B);
   VF_LAUNCH_CHECK();
   return 0;
 }

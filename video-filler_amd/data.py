@@ -22,7 +22,7 @@ import torch
 
 from ._lib import VfError
 from .backend import (GIF_STATUS, JPEG_STATUS, METRIC_COLUMNS, PNG_STATUS, get_backend, gif_inspect, jpeg_inspect,
-                      jpeg_scans_inspect, nhwc_empty, png_inspect)
+                      jpeg_scans_inspect, nhwc_empty, png_inspect, png_inspect_full)
 
 CENTER_FILL = (117.0, 104.0, 123.0)      # train.lua:287-289
 
@@ -180,14 +180,16 @@ def decode_jpeg(items, channels=3, stack=False, fallback=None, subseq_bytes=256,
 
 
 # ------------------------------------------------------------------------------------------ PNG decode
-def png_info(item):
+def png_info(item, full=False):
     """The host-side inspection of one PNG file (no GPU): dict(width, height, bit_depth, color_type, interlace, channels,
     idat_bytes, idat_chunks, palette_entries, trns_entries, supported, inflated_bytes, reason).  ValueError if the file
-    is malformed (signature, chunk order, CRC, zlib header)."""
-    return png_inspect(_file_bytes(item))
+    is malformed (signature, chunk order, CRC, zlib header).  full=True: supported, reason and inflated_bytes are those of
+    the full rule (decode_png's full=True), and passes holds seven (width, height, rowbytes): the Adam7 passes, zeros for
+    an absent one; a file without interlace is one pass, the first."""
+    return (png_inspect_full if full else png_inspect)(_file_bytes(item))
 
 
-def decode_png(items, channels=None, stack=False, fallback=None, dtype="uint8"):
+def decode_png(items, channels=None, stack=False, fallback=None, dtype="uint8", full=False):
     """image.load(path[, channels]) of a batch of PNG files, decoded on the device in one pass (vf_png_decode): uint8
     H x W x C device tensors holding the bytes libpng gives with grey below 8 bits and palettes expanded (Torch7's
     image.load followed by :mul(255)).  channels None keeps the file's own (1 grey, 2 grey+alpha, 3 RGB or palette, 4 RGBA
@@ -199,7 +201,16 @@ def decode_png(items, channels=None, stack=False, fallback=None, dtype="uint8"):
     interlace, a colour file with channels=1, tRNS on a grey or RGB file with channels=None) go to fallback(bytes), which
     returns the decoded uint8 H x W x C image; without it they raise ValueError naming the item and why.  A malformed
     file raises ValueError naming the item before anything is launched; a corrupt stream raises it, with the status,
-    once the stream has synchronised."""
+    once the stream has synchronised.
+
+    full=True also decodes Adam7-interlaced files and 16-bit samples on the device (vf_png_decode_full):
+    an interlaced file gives the pixels of the same image stored plain; the uint8 result of a 16-bit sample is its high
+    byte (libpng's png_set_strip_16, Pillow's result), and dtype "float" of a 16-bit file is sample / 65535 on the whole
+    sample, written with every other file's byte / 255 by the expansion kernel itself.  Plain and interlaced, 8-bit and
+    16-bit items may be mixed; the results come back in item order as views of one buffer.  What still goes to the
+    fallback or raises with its reason: a colour file with channels=1, tRNS on a grey or RGB file with channels=None, a
+    side above 16384, IDAT data above 256 MiB, an inflated size of 2^31 bytes or more.  The default leaves every result
+    and every error as it was."""
     assert channels in (None, 1, 3), "channels is None (the file's own), 1 or 3"
     assert dtype in ("uint8", "float"), "dtype is 'uint8' or 'float'"
     B = get_backend()
@@ -210,9 +221,20 @@ def decode_png(items, channels=None, stack=False, fallback=None, dtype="uint8"):
         if ch is None and info["trns_entries"] and info["color_type"] != 3:
             return "tRNS on colour type %d with the file's channels" % info["color_type"]
 
+    shape_of = lambda info: (info["height"], info["width"], channels or info["channels"])
+    if full:
+        kind = 1 if dtype == "float" else 0
+        out = _decode_files("decode_png", [_file_bytes(it) for it in items], channels, fallback,
+                            lambda f: png_inspect_full(f, passes=False), refuse,
+                            lambda files, infos: B.png_decode_full(files, channels, infos, kind), PNG_STATUS,
+                            "corrupt image data", shape_of, stack and not kind)
+        if kind:   # what the fallback gave is bytes
+            out = [B.png_bytes_to_float(t) if t.dtype == torch.uint8 else t for t in out]
+            out = _stacked(out, None, []) if stack else out
+        return out
     out = _decode_files("decode_png", [_file_bytes(it) for it in items], channels, fallback, png_inspect, refuse,
                         lambda files, infos: B.png_decode(files, channels, infos), PNG_STATUS, "corrupt image data",
-                        lambda info: (info["height"], info["width"], channels or info["channels"]), stack)
+                        shape_of, stack)
     return _as_float(B, out) if dtype == "float" else out
 
 
@@ -221,11 +243,13 @@ def _as_float(B, out):
     return B.png_bytes_to_float(out) if torch.is_tensor(out) else [B.png_bytes_to_float(t) for t in out]
 
 
-def decode_image(items, channels=3, stack=False, fallback=None, dtype="uint8", progressive=False):
+def decode_image(items, channels=3, stack=False, fallback=None, dtype="uint8", progressive=False, full=False):
     """image.load(path, channels) for a mixed folder: every item's signature says whether it is a JPEG or a PNG file; the
     JPEGs go to decode_jpeg and the PNGs to decode_png, one call each, and the results come back in the caller's order.
-    progressive is decode_jpeg's: True decodes progressive JPEG files on the device as well.  ValueError naming the item
-    for a file that is neither."""
+    progressive is decode_jpeg's: True decodes progressive JPEG files on the device as well.  full is decode_png's: True
+    decodes Adam7-interlaced and 16-bit PNG files on the device as well (a 16-bit sample gives its high byte; dtype
+    "float" divides those bytes by 255 here, as it does for the JPEGs).  ValueError naming the item for a file that is
+    neither."""
     B = get_backend()
     files = [_file_bytes(it) for it in items]
     jpg, png = [], []
@@ -238,7 +262,7 @@ def decode_image(items, channels=3, stack=False, fallback=None, dtype="uint8", p
             raise ValueError("decode_image: item %d is neither a JPEG nor a PNG file" % i)
     out = [None] * len(files)
     for idx, dec, name, more in ((jpg, decode_jpeg, "decode_jpeg", {"progressive": True} if progressive else {}),
-                                 (png, decode_png, "decode_png", {})):
+                                 (png, decode_png, "decode_png", {"full": True} if full else {})):
         if not idx:
             continue
         try:
@@ -255,11 +279,12 @@ def decode_image(items, channels=3, stack=False, fallback=None, dtype="uint8", p
     return _as_float(B, out) if dtype == "float" else out
 
 
-def load_mask(item):
+def load_mask(item, full=False):
     """`image.load(maskName):byte()` of datavid/donkey_folder.lua for a PNG mask: the file's own channels decoded on the
     device, then byte_mask (only 255 becomes 1).  uint8 H x W (a grey file) or H x W x C on the device, ready for
-    ClipBatcher.set_mask, PatchArrayBatcher.set_mask and inference.load_whole_frames."""
-    (m,) = decode_png([item])
+    ClipBatcher.set_mask, PatchArrayBatcher.set_mask and inference.load_whole_frames.  full=True takes an
+    Adam7-interlaced or 16-bit mask too (decode_png's full=True; of a 16-bit sample the high byte is compared with 255)."""
+    (m,) = decode_png([item], full=full)
     m = byte_mask(m)
     return m[..., 0].contiguous() if m.shape[2] == 1 else m
 
