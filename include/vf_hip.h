@@ -487,6 +487,36 @@ int vf_jpeg_prog_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* o
 int vf_jpeg_prog_coefficients_host(const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef, size_t coef_blocks,
                                    int32_t* status);
 
+/* ---- other samplings, RGB and several scans (vf_jpeg.hip; DESIGN.md 5.2, "layouts") ----------------------------------
+ * Every 8-bit Huffman-coded SOF0 / SOF1 / SOF2 file of 1 or 3 components that libjpeg decodes without comment, byte for
+ * byte its output.  Sampling: factors 1..4 per component whose ratios to the frame's largest are whole numbers, at most
+ * 10 blocks in the MCU of all components (a one-component file ignores its factors); every component is upsampled by
+ * jdsample.c's choice for it (copy, h2v1 / h2v2 fancy above 2 samples of width, h1v2 fancy, else replication).  Colour:
+ * jdapimin.c's default_decompress_parms (JFIF or Adobe transform 1: YCbCr; Adobe transform 0, or no marker and ids
+ * 'R','G','B': RGB, copied; anything else YCbCr).  A sequential file may have any number of scans with Ss = 0, Se = 63,
+ * Ah = Al = 0, each of 1..3 components with the DHT / DRI state at its SOS (table slots 0..3 for SOF1), every component
+ * in exactly one scan: a component in two scans is malformed, one in no scan unsupported.  Progressive files follow
+ * vf_jpeg_scans_inspect's rules.  Unsupported, with vf_jpeg_inspect's reasons: 4 components, arithmetic coding, 12-bit
+ * samples, lossless and hierarchical files, sides above 16384.  The four entries above behave as before.
+ * vf_jpeg_inspect_layouts (host only, no GPU): walk the whole file.  info (int64[20]) = {width, height, components, h
+ * and v of component 0, of 1, of 2, colour (0 grey, 1 YCbCr, 2 RGB), scans, supported (0 / 1), SOF marker, sample
+ * precision, scan levels, coefficient blocks, blocks per MCU, 0, 0, 0}; reason as vf_jpeg_inspect. */
+int vf_jpeg_inspect_layouts(const unsigned char* data, size_t len, int64_t* info, char* reason, int reason_cap);
+/* Exact sizes for one batch, as vf_jpeg_prog_workspace_bytes; fails, naming the image, on a file the inspector refuses. */
+int vf_jpeg_layouts_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
+                                    size_t* stage_bytes);
+/* Decode the batch, sequential and progressive files mixed, on the context's stream; arguments, rules and launches as
+ * vf_jpeg_prog_decode.  Every scan of every sequential file is a first scan: its restart segments join level 0's one
+ * launch, a block each, and its DC differences are summed per (image, scan, restart segment, component).  Nothing is
+ * allocated, nothing synchronises, and the launch count is never a function of n. */
+int vf_jpeg_decode_layouts(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes,
+                           const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
+                           int32_t* status, int32_t* rounds, int32_t* levels);
+/* Host only, no GPU: as vf_jpeg_prog_coefficients_host for ONE file vf_jpeg_inspect_layouts supports, of either kind
+ * (coef_blocks >= its info[15]); blocks no scan codes (the dummy blocks of single-component scans) are zero. */
+int vf_jpeg_layouts_coefficients_host(const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef, size_t coef_blocks,
+                                      int32_t* status);
+
 /* ---- PNG decode (vf_png_decode.hip) ------------------------------------------------------------------
  * image.load of a PNG file (the masks of datavid/donkey_folder.lua, test_vid_wholeim.lua:112 and
  * test_more_complex.lua:102, demo.lua:51, and the frames vf_png_encode writes) on the device: the BYTES libpng gives

@@ -92,6 +92,10 @@ SIGNATURES = {
     "vf_jpeg_prog_workspace_bytes": (i32, [vp, vp, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_jpeg_prog_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp, vp]),
     "vf_jpeg_prog_coefficients_host": (i32, [vp, sz, i32, vp, sz, vp]),
+    "vf_jpeg_inspect_layouts": (i32, [vp, sz, vp, C.c_char_p, i32]),
+    "vf_jpeg_layouts_workspace_bytes": (i32, [vp, vp, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
+    "vf_jpeg_decode_layouts": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp, vp]),
+    "vf_jpeg_layouts_coefficients_host": (i32, [vp, sz, i32, vp, sz, vp]),
     "vf_png_inspect": (i32, [vp, sz, vp, C.c_char_p, i32]),
     "vf_png_decode_workspace_bytes": (i32, [vp, vp, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_png_decode": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, sz, vp, sz, vp]),

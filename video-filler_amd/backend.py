@@ -287,6 +287,53 @@ def jpeg_prog_coefficients(data, info=None, subseq_bytes=0):
     return coef, status.value
 
 
+JPEG_COLOUR = {0: "grey", 1: "YCbCr", 2: "RGB"}
+
+
+def jpeg_inspect_layouts(data):
+    """The host-only walk of one JPEG file under the layouts rule (vf_jpeg_inspect_layouts; no GPU needed) -> dict(width,
+    height, components, sampling (an (h, v) per component), colour ("grey", "YCbCr" or "RGB"), scans, supported, sof,
+    precision, levels, blocks, blocks_per_mcu, reason).  supported: vf_jpeg_decode_layouts takes the file (DESIGN.md
+    5.2), else reason says why not.  Raises ValueError for a malformed file (a component coded in two scans among them)."""
+    lib = _lib.load()
+    data = bytes(data)
+    info = (C.c_int64 * 20)()
+    why = C.create_string_buffer(160)
+    if lib.vf_jpeg_inspect_layouts(data, len(data), info, why, 160) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    v = [int(x) for x in info]
+    return dict(width=v[0], height=v[1], components=v[2], sampling=[(v[3 + 2 * c], v[4 + 2 * c]) for c in range(min(v[2], 3))],
+                colour=JPEG_COLOUR[v[9]], scans=v[10], supported=bool(v[11]), sof=v[12], precision=v[13], levels=v[14], blocks=v[15],
+                blocks_per_mcu=v[16], reason=why.value.decode())
+
+
+def jpeg_layouts_workspace_bytes(files, subseq_bytes=256):
+    """(device workspace bytes, host staging bytes) of one batch under the layouts rule (vf_jpeg_layouts_workspace_bytes;
+    host only, no GPU needed).  ValueError, naming the image, for a malformed or unsupported file."""
+    lib = _lib.load()
+    data, offs = _joined(files)
+    ws_b, st_b = C.c_size_t(), C.c_size_t()
+    if lib.vf_jpeg_layouts_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), len(files), subseq_bytes, C.byref(ws_b), C.byref(st_b)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return ws_b.value, st_b.value
+
+
+def jpeg_layouts_coefficients(data, info=None, subseq_bytes=0):
+    """jpeg_prog_coefficients for one file the layouts rule supports, sequential or progressive
+    (vf_jpeg_layouts_coefficients_host; no GPU needed) -> (coef, status).  The blocks no scan codes are zero."""
+    lib = _lib.load()
+    data = bytes(data)
+    info = info or jpeg_inspect_layouts(data)
+    if not info["supported"]:
+        raise ValueError("jpeg_layouts_coefficients: unsupported: %s" % info["reason"])
+    coef = np.zeros((info["blocks"], 64), np.int16)
+    status = C.c_int32(0)
+    if lib.vf_jpeg_layouts_coefficients_host(data, len(data), subseq_bytes, coef.ctypes.data_as(C.c_void_p), info["blocks"],
+                                             C.byref(status)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return coef, status.value
+
+
 PNG_STATUS = {0: "ok", 1: "bad code", 2: "short data", 3: "bad distance", 4: "bad length", 5: "bad filter", 6: "bad Adler-32",
               7: "bad palette index"}
 _PNG_INFO_KEYS = ("width", "height", "bit_depth", "color_type", "interlace", "channels", "idat_bytes", "idat_chunks", "palette_entries",
@@ -1147,6 +1194,18 @@ class HipBackend:
         rounds = torch.empty(1, dtype=torch.int32, device=self.device)
         levels = C.c_int32(0)
         out, out_offs, status = self._decode("jpegp", "vf_jpeg_prog_workspace_bytes", "vf_jpeg_prog_decode", files,
+                                             [s["height"] * s["width"] * channels for s in shapes], (subseq_bytes,),
+                                             (channels, subseq_bytes), rounds, C.cast(C.pointer(levels), C.c_void_p), into=into)
+        return out, out_offs, status, rounds, levels.value
+
+    def jpeg_decode_layouts(self, files, channels=3, subseq_bytes=256, infos=None, into=None):
+        """Decode a batch of files the layouts rule supports, sequential and progressive mixed, on the device
+        (vf_jpeg_decode_layouts).  -> (out, offsets, status, rounds, levels) as jpeg_prog_decode.  infos: the files'
+        jpeg_inspect_layouts results, if the caller has them; into: as jpeg_decode."""
+        shapes = infos if infos is not None else [jpeg_inspect(f, walk=False) for f in files]
+        rounds = torch.empty(1, dtype=torch.int32, device=self.device)
+        levels = C.c_int32(0)
+        out, out_offs, status = self._decode("jpegl", "vf_jpeg_layouts_workspace_bytes", "vf_jpeg_decode_layouts", files,
                                              [s["height"] * s["width"] * channels for s in shapes], (subseq_bytes,),
                                              (channels, subseq_bytes), rounds, C.cast(C.pointer(levels), C.c_void_p), into=into)
         return out, out_offs, status, rounds, levels.value

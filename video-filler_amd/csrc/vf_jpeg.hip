@@ -16,6 +16,10 @@
 // Progressive (SOF2) files share all of it but k_jpeg_huffman: vf_jpeg_scans_inspect walks their scans,
 // vf_jpeg_prog_decode assembles the coefficients scan level by scan level and runs the same IDCT and colour launches,
 // vf_jpeg_prog_coefficients_host assembles them on the host with the same functions.
+// Other samplings, RGB and sequential files of several scans ("layouts"): vf_jpeg_decode_layouts is the
+// progressive entry with a wider plan.  A sequential scan is a first scan whose lanes read a DC symbol and then AC symbols
+// per block (prog_first_lane), so its restart segments join k_jpeg_prog_first's launch; k_jpeg_idct places blocks by each
+// component's own factors and k_jpeg_color_layouts samples every component by its own upsampler.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -48,9 +52,12 @@ struct JpgImage {
   int32_t mcux, mcuy, bpm, nblocks;
   int32_t pw[3], ph[3];        // padded plane sizes (whole MCUs)
   int32_t cw[3], ch[3];        // real component sizes: ceil(W * h / hmax), ceil(H * v / vmax)
-  int32_t hs, vs;              // luma sampling (1, 1 for grayscale)
+  int32_t hs, vs;              // the frame's largest sampling factors (1, 1 for grayscale)
+  int32_t hc[3], vc[3];        // per component: its sampling factors (1, 1 for grayscale)
+  int32_t up[3];               // per component: its upsampler, UP_* (layouts)
+  int32_t rgb;                 // 1: the three planes are R, G, B and are copied (layouts)
   int32_t tab0;                // first of the image's 4 tables: DC0, DC1, AC0, AC1
-  int32_t bcomp[6], bx[6], by[6], dct[6], act[6];   // per block of the MCU: component, block offset in it, tables
+  int32_t bcomp[10], bx[10], by[10], dct[10], act[10];   // per block of the MCU: component, block offset in it, tables
   int32_t q[3][64];            // natural-order quantisation values per component
 };
 
@@ -462,8 +469,7 @@ __global__ void k_jpeg_idct(const JpgBatch B) {
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < im.nblocks; j += (int64_t)gridDim.x * blockDim.x) {
     const int m = (int)(j / im.bpm), b = (int)(j % im.bpm);
     const int ci = im.bcomp[b];
-    const int hc = ci == 0 ? im.hs : 1, vc = ci == 0 ? im.vs : 1;
-    const int bx = (m % im.mcux) * hc + im.bx[b], by = (m / im.mcux) * vc + im.by[b];
+    const int bx = (m % im.mcux) * im.hc[ci] + im.bx[b], by = (m / im.mcux) * im.vc[ci] + im.by[b];
     idct_islow(B.coef + (im.coef_base + j) * 64, im.q[ci], B.planes + im.plane_base[ci] + (int64_t)by * 8 * im.pw[ci] + bx * 8,
                im.pw[ci]);
   }
@@ -494,6 +500,69 @@ VF_HD int chroma_at(const JpgBatch& B, const JpgImage& im, int ci, int x, int y)
   const int c0 = cs(i);
   if (x & 1) return i == cw - 1 ? (4 * c0 + 7) >> 4 : (3 * c0 + cs(i + 1) + 7) >> 4;
   return i == 0 ? (4 * c0 + 8) >> 4 : (3 * c0 + cs(i - 1) + 8) >> 4;
+}
+
+// ---- layouts: jdsample.c jinit_upsampler's choice per component, made on the host
+enum { UP_COPY = 0, UP_H2V1 = 1, UP_H2V2 = 2, UP_H1V2 = 3, UP_INT = 4 };
+
+// sample of component ci at full-resolution (x, y), by the component's own upsampler
+__device__ __forceinline__ int sample_at(const JpgBatch& B, const JpgImage& im, int ci, int x, int y) {
+  const uint8_t* pl = B.planes + im.plane_base[ci];
+  const int pw = im.pw[ci], cw = im.cw[ci], ch = im.ch[ci];
+  switch (im.up[ci]) {
+    case UP_COPY: return pl[(int64_t)y * pw + x];
+    case UP_H2V1: {                                                     // h2v1_fancy_upsample (cw > 2)
+      const uint8_t* in = pl + (int64_t)y * pw;
+      const int i = x >> 1, v3 = 3 * in[i];
+      if (x & 1) return i == cw - 1 ? in[i] : (v3 + in[i + 1] + 2) >> 2;
+      return i == 0 ? in[0] : (v3 + in[i - 1] + 1) >> 2;
+    }
+    case UP_H2V2: {                                                     // h2v2_fancy_upsample (cw > 2)
+      const int i = x >> 1, r0 = y >> 1;
+      const int r1 = (y & 1) ? min(r0 + 1, ch - 1) : max(r0 - 1, 0);
+      const uint8_t* in0 = pl + (int64_t)r0 * pw;
+      const uint8_t* in1 = pl + (int64_t)r1 * pw;
+      const int c0 = 3 * in0[i] + in1[i];
+      if (x & 1) return i == cw - 1 ? (4 * c0 + 7) >> 4 : (3 * c0 + 3 * in0[i + 1] + in1[i + 1] + 7) >> 4;
+      return i == 0 ? (4 * c0 + 8) >> 4 : (3 * c0 + 3 * in0[i - 1] + in1[i - 1] + 8) >> 4;
+    }
+    case UP_H1V2: {                                                     // h1v2_fancy_upsample: per column, any width
+      const int r0 = y >> 1;
+      const int r1 = (y & 1) ? min(r0 + 1, ch - 1) : max(r0 - 1, 0);
+      return (3 * pl[(int64_t)r0 * pw + x] + pl[(int64_t)r1 * pw + x] + ((y & 1) ? 2 : 1)) >> 2;
+    }
+    default:                                                            // int_upsample: replicate
+      return pl[(int64_t)(y / (im.vs / im.vc[ci])) * pw + x / (im.hs / im.hc[ci])];
+  }
+}
+
+// k_jpeg_color for the layouts entry: every component through its own upsampler (luma may be the subsampled one), then
+// ycc_rgb_convert, a copy (RGB) or the grey plane replicated.  A kernel of its own, so that the old entries' kernel is
+// the one it was; `up` and `rgb` are the image's, so the branches are uniform per block.
+__global__ void k_jpeg_color_layouts(const JpgBatch B) {
+  const JpgImage& im = B.img[blockIdx.y];
+  const int64_t npix = (int64_t)im.W * im.H;
+  uint8_t* out = B.out + im.out_off;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(i / im.W), x = (int)(i % im.W);
+    const int Y = sample_at(B, im, 0, x, y);
+    if (im.ncomp == 1) {
+      for (int c = 0; c < im.channels; ++c) out[i * im.channels + c] = (uint8_t)Y;
+      continue;
+    }
+    const int c1 = sample_at(B, im, 1, x, y), c2 = sample_at(B, im, 2, x, y);
+    if (im.rgb) {
+      out[i * 3 + 0] = (uint8_t)Y;
+      out[i * 3 + 1] = (uint8_t)c1;
+      out[i * 3 + 2] = (uint8_t)c2;
+      continue;
+    }
+    const int cb = c1 - 128, cr = c2 - 128;
+    constexpr int SCALEBITS = 16, ONE_HALF = 1 << 15;
+    out[i * 3 + 0] = clamp255(Y + ((91881 * cr + ONE_HALF) >> SCALEBITS));
+    out[i * 3 + 1] = clamp255(Y + ((-22554 * cb + ONE_HALF + -46802 * cr) >> SCALEBITS));
+    out[i * 3 + 2] = clamp255(Y + ((116130 * cb + ONE_HALF) >> SCALEBITS));
+  }
 }
 
 __global__ void k_jpeg_color(const JpgBatch B) {
@@ -546,6 +615,8 @@ struct JpgParsed {
   int ss = 0, se = 63, ahal = 0;
   bool jfif = false, adobe = false;
   bool take_sof2 = false;   // set by the progressive path: SOF2 is no reason, and the scan checks are left to it
+  bool layouts = false;     // set by the layouts path: SOF0 / SOF1 / SOF2, any whole-number sampling, RGB; the scans are its own
+  bool rgb = false;         // layouts: the components are R, G, B (jdapimin.c default_decompress_parms)
   int adobe_transform = -1;
   int64_t scan_begin = 0, scan_end = 0;
   bool supported = false;
@@ -760,7 +831,7 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
         P.hmax = std::max(P.hmax, P.hf[c]);
         P.vmax = std::max(P.vmax, P.vf[c]);
       }
-      if (m == 0xC2 && P.take_sof2) {
+      if ((m == 0xC2 && P.take_sof2) || (P.layouts && (m == 0xC0 || m == 0xC1))) {
       } else if (m == 0xC2 || m == 0xC6 || m == 0xCA || m == 0xCE) unsupported("progressive");
       else if (m == 0xC3 || m == 0xC7 || m == 0xCB || m == 0xCF) unsupported("lossless");
       else if (m >= 0xC9) unsupported("arithmetic coding");
@@ -770,7 +841,22 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
       else if (P.ncomp != 1 && P.ncomp != 3) unsupported(std::to_string(P.ncomp) + " components");
       if (P.W <= 0 || P.H <= 0) unsupported("height or width 0 (DNL)");
       if (P.W > kJpgMaxSide || P.H > kJpgMaxSide) unsupported("larger than 16384 per side");
-      if (P.ncomp == 3) {
+      if (P.ncomp == 3 && P.layouts) {
+        // jdinput.c initial_setup / jdmaster.c: factors 1..4, whole-number ratios to the largest (libjpeg:
+        // JERR_FRACT_SAMPLE_NOTIMPL), at most 10 blocks in an MCU (D_MAX_BLOCKS_IN_MCU, JERR_BAD_MCU_SIZE)
+        const std::string f = std::to_string(P.hf[0]) + "x" + std::to_string(P.vf[0]) + "," + std::to_string(P.hf[1]) + "x" +
+                              std::to_string(P.vf[1]) + "," + std::to_string(P.hf[2]) + "x" + std::to_string(P.vf[2]);
+        int nb = 0;
+        bool range = true, whole = true;
+        for (int c = 0; c < 3; ++c) {
+          range &= P.hf[c] >= 1 && P.hf[c] <= 4 && P.vf[c] >= 1 && P.vf[c] <= 4;
+          nb += P.hf[c] * P.vf[c];
+        }
+        for (int c = 0; c < 3 && range; ++c) whole &= P.hmax % P.hf[c] == 0 && P.vmax % P.vf[c] == 0;
+        if (!range) unsupported("sampling " + f + " (factors are 1 to 4)");
+        else if (!whole) unsupported("sampling " + f + " (fractional ratio between components)");
+        else if (nb > 10) unsupported("sampling " + f + " (" + std::to_string(nb) + " blocks in an MCU, 10 at most)");
+      } else if (P.ncomp == 3) {
         const bool ok = P.hf[1] == 1 && P.vf[1] == 1 && P.hf[2] == 1 && P.vf[2] == 1 &&
                         ((P.hf[0] == 1 && P.vf[0] == 1) || (P.hf[0] == 2 && P.vf[0] == 1) || (P.hf[0] == 2 && P.vf[0] == 2));
         if (!ok)
@@ -811,13 +897,15 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
   if (P.ncomp == 3) {
     if (P.jfif) {
     } else if (P.adobe) {
-      if (P.adobe_transform == 0) unsupported("RGB colour transform (Adobe transform 0)");
+      if (P.adobe_transform == 0 && P.layouts) P.rgb = true;
+      else if (P.adobe_transform == 0) unsupported("RGB colour transform (Adobe transform 0)");
       else if (P.adobe_transform != 1) unsupported("Adobe transform " + std::to_string(P.adobe_transform));
     } else if (P.cid[0] == 82 && P.cid[1] == 71 && P.cid[2] == 66) {
-      unsupported("RGB components");
+      if (P.layouts) P.rgb = true;
+      else unsupported("RGB components");
     }
   }
-  if (P.take_sof2 && P.sof == 0xC2) {   // the scans are jpg_prog_parse's
+  if ((P.take_sof2 && P.sof == 0xC2) || P.layouts) {   // the scans are jpg_prog_parse's
     P.scan_end = -1;
     P.supported = P.why.empty();
     return 0;
@@ -1019,6 +1107,8 @@ void jpg_pack(const uint8_t* data, const int64_t* offs, int n, int channels, int
     coef += im.nblocks;
     for (int c = 0; c < P.ncomp; ++c) {
       const int h = gray ? 1 : P.hf[c], v = gray ? 1 : P.vf[c];
+      im.hc[c] = h;
+      im.vc[c] = v;
       im.pw[c] = im.mcux * 8 * h;
       im.ph[c] = im.mcuy * 8 * v;
       im.cw[c] = (int)vf_cdiv((int64_t)P.W * h, gray ? 1 : P.hmax);
@@ -1091,6 +1181,10 @@ struct ProgScan {
   int32_t boff[kProgMaxMcuBlocks];    // interleaved: each unit block's place in the frame's MCU ...
   int32_t bslot[kProgMaxMcuBlocks];   // ... and its component's place in the scan (DC predictor, table)
   int32_t tab[4];              // per scan component: its table in force at the SOS (DC for Ss = 0, else AC); -1: none
+  // a scan of a sequential file (layouts: Ss = 0, Se = 63): every block is its DC symbol and then its AC symbols
+  int32_t seq;
+  int32_t ntab;                // its distinct tables: tab[0 .. ntab) when <= 4, else the ntab tables from tab[0] on
+  int32_t dct[kProgMaxMcuBlocks], act[kProgMaxMcuBlocks];   // per unit block: its DC and AC table among those
 };
 
 struct ProgSeg {
@@ -1234,6 +1328,28 @@ VF_HD int prog_ac_refine(ProgReader& R, const JpgHuff& t, int ss, int se, int al
   return ST_OK;
 }
 
+// jdhuff.c decode_mcu for one block: the DC difference, then the AC symbols up to EOB or the 64th coefficient
+VF_HD int seq_block(ProgReader& R, const JpgHuff& dct, const JpgHuff& act, int& pred, int16_t* blk) {
+  if (int e = prog_dc_first(R, dct, 0, pred, blk)) return e;
+  for (int k = 1; k < 64;) {
+    const int rs = R.symbol(act);
+    if (rs < 0) return -rs;
+    const int r = rs >> 4, s = rs & 15;
+    uint32_t v = 0;
+    if (s) {
+      k += r;
+      if (int e = R.bits(s, v)) return e;
+      blk[natural(k)] = (int16_t)huff_extend(v, s);
+      ++k;
+    } else if (r == 15) {
+      k += 16;
+    } else {
+      break;
+    }
+  }
+  return ST_OK;
+}
+
 // One restart segment of one scan, its units u0 .. u0 + nu in order; coef: the image's first coefficient.  The
 // predictors and the EOB run start at 0 (process_restart); a run that outlasts the segment's blocks is bad data.
 __host__ __device__ inline int prog_decode_segment(const JpgImage& im, const ProgScan& sc, const JpgHuff* huff, const uint32_t* bits,
@@ -1247,7 +1363,8 @@ __host__ __device__ inline int prog_decode_segment(const JpgImage& im, const Pro
       int16_t* blk = coef + 64 * prog_block(im, sc, u, j);
       const int slot = sc.interleaved ? sc.bslot[j] : 0;
       int e;
-      if (sc.ss == 0) e = sc.ah == 0 ? prog_dc_first(R, huff[sc.tab[slot]], sc.al, pred[slot], blk) : prog_dc_refine(R, sc.al, blk);
+      if (sc.seq) e = seq_block(R, huff[sc.tab[0] + sc.dct[j]], huff[sc.tab[0] + sc.act[j]], pred[slot], blk);
+      else if (sc.ss == 0) e = sc.ah == 0 ? prog_dc_first(R, huff[sc.tab[slot]], sc.al, pred[slot], blk) : prog_dc_refine(R, sc.al, blk);
       else if (sc.ah == 0) e = prog_ac_first(R, huff[sc.tab[0]], sc.ss, sc.se, sc.al, eobrun, blk);
       else e = prog_ac_refine(R, huff[sc.tab[0]], sc.ss, sc.se, sc.al, eobrun, blk);
       if (e != ST_OK) return e;
@@ -1263,17 +1380,43 @@ __host__ __device__ inline int prog_decode_segment(const JpgImage& im, const Pro
 // of the block the lane is in (the exclusive scan of the counts; 0 when counting).  WRITE: store the coefficients (a DC
 // value as its difference) and stop once `total` blocks are done; else count: g comes back as the blocks advanced,
 // capped at total + 1.  Returns LANE_*.
-template <bool WRITE>
+// SEQ: the scan is a sequential file's (layouts), else a progressive first scan; the block picks the instance per scan.
+template <bool WRITE, bool SEQ>
 __host__ __device__ int prog_first_lane(const JpgImage& im, const ProgScan& sc, const JpgHuff* tabs, BitWin& bw, uint32_t nbits, uint32_t& p,
                                         int& j, int& k, uint32_t pend, int64_t& g, int64_t total, int u0, int16_t* coef) {
   const bool dc = sc.ss == 0;
   bw.seek(p);
   for (;;) {
     if (!WRITE && g > total) g = total + 1;
+    // bits behind a sequential scan's last block are not the scan's (libjpeg skips them); an EOB run past it is bad data
+    if (WRITE && SEQ && g >= total) return LANE_DONE;
     if (WRITE && (dc || k == sc.ss) && g >= total) return g > total ? LANE_BAD : LANE_DONE;
     if (p >= pend) return LANE_END;
     const uint32_t w = bw.peek(p);
     int sym;
+    if constexpr (SEQ) {
+      // a sequential scan: k = 0 is the block's DC symbol, j the block of the unit (its tables), g the block
+      const int l = huff_decode(tabs[k == 0 ? sc.dct[j] : sc.act[j]], w, sym);
+      if (!l || (k == 0 && sym > 15)) return LANE_BAD;
+      const int r = k == 0 ? 0 : sym >> 4, s = k == 0 ? sym : sym & 15;
+      if (p + (uint32_t)(l + s) > nbits) return LANE_SHORT;
+      if (k > 0 && s == 0) {
+        k = r == 15 ? k + 16 : 64;   // ZRL / EOB
+      } else {
+        k += r;
+        if (WRITE)
+          coef[64 * prog_block(im, sc, u0 + (int)(g / sc.nb), (int)(g % sc.nb)) + natural(k)] =
+              (int16_t)(s ? huff_extend((w << l) >> (32 - s), s) : 0);
+        ++k;
+      }
+      p += l + s;
+      if (k >= 64) {
+        k = 0;
+        ++g;
+        if (++j == sc.nb) j = 0;
+      }
+      continue;
+    }
     if (dc) {
       const int l = huff_decode(tabs[sc.bslot[j]], w, sym);
       if (!l || sym > 15) return LANE_BAD;
@@ -1326,21 +1469,14 @@ VF_HD void prog_dc_unit(const JpgImage& im, const ProgScan& sc, int u, unsigned*
   }
 }
 
-// one block per (image, first scan, restart segment)
-__global__ __launch_bounds__(kHuffThreads) void k_jpeg_prog_first(const JpgBatch B, const ProgScan* scans, const ProgSeg* segs) {
-  __shared__ JpgHuff tabs[4];
-  __shared__ unsigned long long s_w[kHuffThreads / 64];
-  __shared__ int changed;
+// one (image, first scan, restart segment) by its block.  SEQ as prog_first_lane; GT: the scan's tables are read from
+// global memory (a sequential scan of three components may name six; the block has four slots), else from `tabs`.
+// Both are template arguments so that each instance's table reads keep their address space.
+template <bool SEQ, bool GT>
+__device__ __forceinline__ void prog_first_block(const JpgBatch& B, const ProgSeg& sg, const ProgScan& sc, const JpgImage& im,
+                                                 const JpgHuff* tabs, unsigned long long* s_w, int* changed) {
   const int t = threadIdx.x;
-  const ProgSeg sg = segs[blockIdx.x];
-  const ProgScan& sc = scans[sg.scan];
-  const JpgImage& im = B.img[sc.img];
-  for (int c = 0; c < sc.ns; ++c) {
-    const uint32_t* src = (const uint32_t*)(B.huff + sc.tab[c]);
-    uint32_t* dst = (uint32_t*)(tabs + c);
-    for (int i = t; i < (int)(sizeof(JpgHuff) / 4); i += kHuffThreads) dst[i] = src[i];
-  }
-  __syncthreads();
+  const JpgHuff* T = GT ? B.huff + sc.tab[0] : tabs;
   const uint32_t nbits = 8u * (uint32_t)sg.len;
   const uint32_t sb = (uint32_t)B.sub_bits;
   const int nsub = sg.nsub;
@@ -1357,7 +1493,7 @@ __global__ __launch_bounds__(kHuffThreads) void k_jpeg_prog_first(const JpgBatch
     int j = (int)((e >> 8) & 0xff), k = (int)(e & 0xff);
     int64_t g = 0;
     const uint32_t pend = min(nbits, (uint32_t)(i + 1) * sb);
-    const int r = prog_first_lane<false>(im, sc, tabs, bw, nbits, p, j, k, pend, g, total, sg.u0, nullptr);
+    const int r = prog_first_lane<false, SEQ>(im, sc, T, bw, nbits, p, j, k, pend, g, total, sg.u0, nullptr);
     X[i] = r == LANE_END ? st_pack(p, j, k) : kDead;
     Nb[i] = (int32_t)g;
   };
@@ -1369,7 +1505,7 @@ __global__ __launch_bounds__(kHuffThreads) void k_jpeg_prog_first(const JpgBatch
   // synchronise, as k_jpeg_huffman does
   int nround = 0;
   for (;;) {
-    if (t == 0) changed = 0;
+    if (t == 0) *changed = 0;
     __syncthreads();
     for (int i = t; i < nsub; i += kHuffThreads) {
       D[i] = 0;
@@ -1378,11 +1514,11 @@ __global__ __launch_bounds__(kHuffThreads) void k_jpeg_prog_first(const JpgBatch
       if (x != E[i] && x != kDead) {
         E[i] = x;
         D[i] = 1;
-        changed = 1;
+        *changed = 1;
       }
     }
     __syncthreads();
-    if (!changed) break;
+    if (!*changed) break;
     ++nround;
     for (int i = t; i < nsub; i += kHuffThreads)
       if (D[i]) run(i, E[i]);
@@ -1413,7 +1549,7 @@ __global__ __launch_bounds__(kHuffThreads) void k_jpeg_prog_first(const JpgBatch
     uint32_t p = (uint32_t)(e >> 16);
     int j = (int)((e >> 8) & 0xff), k = (int)(e & 0xff);
     const uint32_t pend = min(nbits, (uint32_t)(i + 1) * sb);
-    const int r = prog_first_lane<true>(im, sc, tabs, bw, nbits, p, j, k, pend, g, total, sg.u0, coef);
+    const int r = prog_first_lane<true, SEQ>(im, sc, T, bw, nbits, p, j, k, pend, g, total, sg.u0, coef);
     if (r == LANE_BAD) err = ST_BAD;
     else if (r == LANE_SHORT || (r == LANE_END && i == nsub - 1)) err = max(err, (int)ST_SHORT);
   }
@@ -1438,11 +1574,31 @@ __global__ __launch_bounds__(kHuffThreads) void k_jpeg_prog_first(const JpgBatch
   }
 }
 
+
+__global__ __launch_bounds__(kHuffThreads) void k_jpeg_prog_first(const JpgBatch B, const ProgScan* scans, const ProgSeg* segs) {
+  __shared__ JpgHuff tabs[4];
+  __shared__ unsigned long long s_w[kHuffThreads / 64];
+  __shared__ int changed;
+  const int t = threadIdx.x;
+  const ProgSeg sg = segs[blockIdx.x];
+  const ProgScan& sc = scans[sg.scan];
+  const JpgImage& im = B.img[sc.img];
+  for (int c = 0; c < sc.ntab && sc.ntab <= 4; ++c) {
+    const uint32_t* src = (const uint32_t*)(B.huff + sc.tab[c]);
+    uint32_t* dst = (uint32_t*)(tabs + c);
+    for (int i = t; i < (int)(sizeof(JpgHuff) / 4); i += kHuffThreads) dst[i] = src[i];
+  }
+  __syncthreads();
+  if (!sc.seq) prog_first_block<false, false>(B, sg, sc, im, tabs, s_w, &changed);
+  else if (sc.ntab <= 4) prog_first_block<true, false>(B, sg, sc, im, tabs, s_w, &changed);
+  else prog_first_block<true, true>(B, sg, sc, im, tabs, s_w, &changed);
+}
+
 // the same on the host, lane after lane: what vf_jpeg_prog_coefficients_host runs the first scans through
 inline int prog_first_segment_host(const JpgImage& im, const ProgScan& sc, const JpgHuff* huff, const uint32_t* bits, int len, int sub_bytes,
                                    int u0, int nu, int16_t* coef) {
-  JpgHuff tabs[4];
-  for (int c = 0; c < sc.ns; ++c) tabs[c] = huff[sc.tab[c]];
+  JpgHuff tabs[6];
+  for (int c = 0; c < sc.ntab; ++c) tabs[c] = huff[sc.ntab > 4 ? sc.tab[0] + c : sc.tab[c]];
   const uint32_t nbits = 8u * (uint32_t)len, sb = 8u * (uint32_t)sub_bytes;
   const int nsub = (int)std::max<int64_t>(1, vf_cdiv(len, sub_bytes));
   const int64_t total = (int64_t)nu * sc.nb;
@@ -1454,7 +1610,9 @@ inline int prog_first_segment_host(const JpgImage& im, const ProgScan& sc, const
     uint32_t p = (uint32_t)(E[i] >> 16);
     int j = (int)((E[i] >> 8) & 0xff), k = (int)(E[i] & 0xff);
     int64_t g = 0;
-    const int r = prog_first_lane<false>(im, sc, tabs, bw, nbits, p, j, k, std::min(nbits, (uint32_t)(i + 1) * sb), g, total, u0, nullptr);
+    const uint32_t pend = std::min(nbits, (uint32_t)(i + 1) * sb);
+    const int r = sc.seq ? prog_first_lane<false, true>(im, sc, tabs, bw, nbits, p, j, k, pend, g, total, u0, nullptr)
+                         : prog_first_lane<false, false>(im, sc, tabs, bw, nbits, p, j, k, pend, g, total, u0, nullptr);
     X[i] = r == LANE_END ? state(p, j, k) : kDead;
     Nb[i] = g;
   };
@@ -1488,7 +1646,9 @@ inline int prog_first_segment_host(const JpgImage& im, const ProgScan& sc, const
     }
     uint32_t p = (uint32_t)(E[i] >> 16);
     int j = (int)((E[i] >> 8) & 0xff), k = (int)(E[i] & 0xff);
-    const int r = prog_first_lane<true>(im, sc, tabs, bw, nbits, p, j, k, std::min(nbits, (uint32_t)(i + 1) * sb), g, total, u0, coef);
+    const uint32_t pend = std::min(nbits, (uint32_t)(i + 1) * sb);
+    const int r = sc.seq ? prog_first_lane<true, true>(im, sc, tabs, bw, nbits, p, j, k, pend, g, total, u0, coef)
+                         : prog_first_lane<true, false>(im, sc, tabs, bw, nbits, p, j, k, pend, g, total, u0, coef);
     if (r == LANE_BAD) err = ST_BAD;
     else if (r == LANE_SHORT || (r == LANE_END && i == nsub - 1)) err = std::max(err, (int)ST_SHORT);
   }
@@ -1515,6 +1675,8 @@ __global__ void k_jpeg_prog_scan(const JpgBatch B, const ProgScan* scans, const 
 struct ProgScanHost {
   int ns = 0, scomp[4] = {}, ss = 0, se = 0, ah = 0, al = 0, ri = 0, level = 0;
   int tab[4] = {-1, -1, -1, -1};   // per scan component: its table among ProgParsed::tabs
+  bool seq = false;                // a scan of a sequential file (layouts): tab[0] is the first of its ntab tables,
+  int ntab = 0, dtab[4] = {}, atab[4] = {};   // dtab / atab each component's DC / AC table among them
   int64_t begin = 0, end = 0, nunit = 0;
   std::vector<JpgParsed::Seg> segs;
   std::vector<int64_t> drops;
@@ -1533,18 +1695,21 @@ struct ProgParsed {
   int vmax() const { return gray() ? 1 : P.vmax; }
   int64_t mcux() const { return vf_cdiv(P.W, 8 * hmax()); }
   int64_t mcuy() const { return vf_cdiv(P.H, 8 * vmax()); }
-  int bpm() const { return gray() ? 1 : P.hf[0] * P.vf[0] + 2; }
+  int bpm() const { return gray() ? 1 : P.hf[0] * P.vf[0] + P.hf[1] * P.vf[1] + P.hf[2] * P.vf[2]; }
   int64_t nblocks() const { return mcux() * mcuy() * bpm(); }
 };
 
-// 0: parsed (P.supported / P.why as jpg_parse); else malformed (msg).  Walks every scan.
-int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg) {
+// 0: parsed (P.supported / P.why as jpg_parse); else malformed (msg).  Walks every scan.  layouts: sequential files
+// too (SOF0 / SOF1, any number of scans), and jpg_parse's wider samplings and RGB.
+int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg, bool layouts = false) {
   JpgParsed& P = G.P;
   P.take_sof2 = true;
+  P.layouts = layouts;
   if (int e = jpg_parse(d, n, P, msg, false)) return e;
   P.supported = false;
-  if (P.sof != 0xC2 && P.why.empty()) P.why = "not progressive";
+  if (P.sof != 0xC2 && !layouts && P.why.empty()) P.why = "not progressive";
   if (!P.why.empty()) return 0;
+  const bool seq = P.sof != 0xC2;
   int cov[3][64];              // the Al each coefficient was last coded at; -1: not yet
   for (auto& c : cov)
     for (int& k : c) k = -1;
@@ -1565,14 +1730,47 @@ int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg)
     sc.al = P.ahal & 15;
     sc.ri = P.ri;
     sc.begin = P.scan_begin;
-    bool bad = sc.ss > sc.se || sc.se > 63 || (sc.ss == 0 && sc.se != 0) || (sc.ss > 0 && sc.ns != 1) || sc.al > 13 ||
+    sc.seq = seq;
+    if (seq && (sc.ss != 0 || sc.se != 63 || P.ahal != 0)) {
+      P.why = "non-baseline scan parameters";
+      return 0;
+    }
+    bool bad = seq ? false : sc.ss > sc.se || sc.se > 63 || (sc.ss == 0 && sc.se != 0) || (sc.ss > 0 && sc.ns != 1) || sc.al > 13 ||
                (sc.ah != 0 && sc.al != sc.ah - 1) || sc.ns > P.ncomp;
     if (bad) {   // jdphuff.c start_pass_phuff_decoder: JERR_BAD_PROGRESSION
       msg = at + "bad progression parameters Ss=" + std::to_string(sc.ss) + " Se=" + std::to_string(sc.se) +
             " Ah=" + std::to_string(sc.ah) + " Al=" + std::to_string(sc.al) + " with " + std::to_string(sc.ns) + " components";
       return 2;
     }
-    for (int i = 0; i < sc.ns; ++i) {
+    for (int i = 0; i < sc.ns && seq; ++i) {
+      // the scan's tables as they stand at this SOS, side by side: DC and AC of each component, equal slots shared
+      sc.scomp[i] = P.scomp[i];
+      const int top = P.sof == 0xC0 ? 1 : 3;   // baseline has two slots of each class, extended sequential four
+      for (int ac = 0; ac < 2; ++ac) {
+        const int slot = ac ? P.ta[i] : P.td[i];
+        const RawHuff* h = slot <= top ? (ac ? &P.hac[slot] : &P.hdc[slot]) : nullptr;
+        if (!h || !h->present) {
+          P.why = "missing Huffman table (or one beyond baseline's two)";
+          return 0;
+        }
+        if (!h->fits) {
+          msg = at + "bad Huffman table: its code counts overflow the code lengths";
+          return 2;
+        }
+        for (int v = 0; v < h->nval && !ac; ++v)
+          if (h->val[v] > 15 && P.why.empty()) P.why = "DC Huffman symbol above 15";
+        int found = -1;
+        for (int j = 0; j < i; ++j)
+          if ((ac ? P.ta[j] : P.td[j]) == slot) found = ac ? sc.atab[j] : sc.dtab[j];
+        if (found < 0) {
+          found = sc.ntab++;
+          if (found == 0) sc.tab[0] = (int)G.tabs.size();
+          G.tabs.push_back(*h);
+        }
+        (ac ? sc.atab[i] : sc.dtab[i]) = found;
+      }
+    }
+    for (int i = 0; i < sc.ns && !seq; ++i) {
       sc.scomp[i] = P.scomp[i];
       if (sc.ss == 0 && sc.ah != 0) continue;   // DC refinement reads raw bits
       const bool dc = sc.ss == 0;
@@ -1597,6 +1795,11 @@ int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg)
       sc.tab[i] = where;
     }
     // orderly: a first scan covers new ground, a refinement follows the Al before it, AC comes after the DC
+    for (int i = 0; i < sc.ns && seq; ++i)
+      if (cov[sc.scomp[i]][0] >= 0) {
+        msg = at + "component " + std::to_string(sc.scomp[i]) + " is coded in two scans";
+        return 2;
+      }
     for (int i = 0; i < sc.ns && P.why.empty(); ++i) {
       const int c = sc.scomp[i];
       if (sc.ss > 0 && cov[c][0] < 0) P.why = "progression out of order";
@@ -1687,7 +1890,7 @@ int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg)
   }
   for (int c = 0; c < P.ncomp; ++c)
     for (int k = 0; k < 64; ++k)
-      if (cov[c][k] != 0) P.why = "incomplete progression";
+      if (cov[c][k] != 0) P.why = seq ? "incomplete: component " + std::to_string(c) + " is in no scan" : "incomplete progression";
   P.supported = P.why.empty();
   return 0;
 }
@@ -1702,20 +1905,21 @@ struct ProgPlan {
 };
 
 // sub_bytes: the subsequence size of the first scans' decode (0: none of them is decoded that way)
-int jpg_prog_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes, ProgPlan& L) {
-  VF_REQUIRE(n > 0 && data && offs, "vf_jpeg_prog: empty batch");
-  VF_REQUIRE(sub_bytes == 0 || (sub_bytes >= 8 && sub_bytes <= (1 << 20)), "vf_jpeg_prog: subsequence size %d outside [8, 1 MiB]", sub_bytes);
+int jpg_prog_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes, ProgPlan& L, bool layouts = false) {
+  const char* who = layouts ? "vf_jpeg_layouts" : "vf_jpeg_prog";
+  VF_REQUIRE(n > 0 && data && offs, "%s: empty batch", who);
+  VF_REQUIRE(sub_bytes == 0 || (sub_bytes >= 8 && sub_bytes <= (1 << 20)), "%s: subsequence size %d outside [8, 1 MiB]", who, sub_bytes);
   L.G.resize(n);
   for (int i = 0; i < n; ++i) {
     std::string msg;
-    VF_REQUIRE(offs[i + 1] >= offs[i], "vf_jpeg_prog: offsets decrease at image %d", i);
+    VF_REQUIRE(offs[i + 1] >= offs[i], "%s: offsets decrease at image %d", who, i);
     ProgParsed& G = L.G[i];
-    if (jpg_prog_parse(data + offs[i], offs[i + 1] - offs[i], G, msg)) {
-      vf_set_error("vf_jpeg_prog: image %d: %s", i, msg.c_str());
+    if (jpg_prog_parse(data + offs[i], offs[i + 1] - offs[i], G, msg, layouts)) {
+      vf_set_error("%s: image %d: %s", who, i, msg.c_str());
       return 2;
     }
     if (!G.P.supported) {
-      vf_set_error("vf_jpeg_prog: image %d: unsupported: %s", i, G.P.why.c_str());
+      vf_set_error("%s: image %d: unsupported: %s", who, i, G.P.why.c_str());
       return 3;
     }
     L.nblk += G.nblocks();
@@ -1736,7 +1940,7 @@ int jpg_prog_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes
       L.scan_bytes += (int64_t)vf_up256((size_t)(sc.end - sc.begin) + 8);
     }
   }
-  VF_REQUIRE(L.nseg < ((int64_t)1 << 31) && L.nchunk < ((int64_t)1 << 31), "vf_jpeg_prog: more than 2^31 restart segments or chunks");
+  VF_REQUIRE(L.nseg < ((int64_t)1 << 31) && L.nchunk < ((int64_t)1 << 31), "%s: more than 2^31 restart segments or chunks", who);
   VfCarve ws;
   L.o_img = ws.take(sizeof(JpgImage) * n);
   L.o_scans = ws.take(sizeof(ProgScan) * L.nscan);
@@ -1757,6 +1961,15 @@ int jpg_prog_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes
 }
 
 // fill the staging buffer; the segments lie level by level
+// jdsample.c jinit_upsampler for a component that is 1 / rh by 1 / rv of the image and cw samples wide
+int jpg_upsampler(int rh, int rv, int cw) {
+  if (rh == 1 && rv == 1) return UP_COPY;
+  if (rh == 2 && rv == 1 && cw > 2) return UP_H2V1;
+  if (rh == 2 && rv == 2 && cw > 2) return UP_H2V2;
+  if (rh == 1 && rv == 2) return UP_H1V2;
+  return UP_INT;
+}
+
 void jpg_prog_pack(const uint8_t* data, const int64_t* offs, int n, int channels, int sub_bytes, const int64_t* out_offs, const ProgPlan& L,
                    uint8_t* st) {
   JpgImage* imgs = (JpgImage*)(st + L.o_img);
@@ -1781,6 +1994,7 @@ void jpg_prog_pack(const uint8_t* data, const int64_t* offs, int n, int channels
     im.channels = channels;
     im.hs = G.hmax();
     im.vs = G.vmax();
+    im.rgb = P.rgb;
     im.mcux = (int)G.mcux();
     im.mcuy = (int)G.mcuy();
     int cb0[3] = {0, 0, 0};   // each component's first block in the MCU (frame order)
@@ -1799,10 +2013,13 @@ void jpg_prog_pack(const uint8_t* data, const int64_t* offs, int n, int channels
     im.coef_base = coef;
     coef += im.nblocks;
     for (int c = 0; c < P.ncomp; ++c) {
+      im.hc[c] = G.h(c);
+      im.vc[c] = G.v(c);
       im.pw[c] = im.mcux * 8 * G.h(c);
       im.ph[c] = im.mcuy * 8 * G.v(c);
       im.cw[c] = (int)vf_cdiv((int64_t)P.W * G.h(c), G.hmax());
       im.ch[c] = (int)vf_cdiv((int64_t)P.H * G.v(c), G.vmax());
+      im.up[c] = jpg_upsampler(G.hmax() / G.h(c), G.vmax() / G.v(c), im.cw[c]);
       im.plane_base[c] = plane;
       plane += (int64_t)im.pw[c] * im.ph[c];
       for (int k = 0; k < 64; ++k) im.q[c][k] = G.q[c][k];
@@ -1822,6 +2039,8 @@ void jpg_prog_pack(const uint8_t* data, const int64_t* offs, int n, int channels
       s.nunit = (int32_t)h.nunit;
       s.interleaved = h.ns > 1;
       s.nb = 0;
+      s.seq = h.seq;
+      s.ntab = h.seq ? h.ntab : h.ns;
       for (int j = 0; j < h.ns; ++j) {
         const int c = h.scomp[j];
         s.tab[j] = h.tab[j] < 0 ? -1 : ti + h.tab[j];
@@ -1829,8 +2048,11 @@ void jpg_prog_pack(const uint8_t* data, const int64_t* offs, int n, int channels
           for (int x = 0; x < G.h(c); ++x, ++s.nb) {
             s.boff[s.nb] = cb0[c] + y * G.h(c) + x;
             s.bslot[s.nb] = j;
+            s.dct[s.nb] = h.dtab[j];
+            s.act[s.nb] = h.atab[j];
           }
       }
+      for (int t = 0; t < 4 && h.seq; ++t) s.tab[t] = t < h.ntab ? ti + h.tab[0] + t : -1;
       if (!s.interleaved) {
         const int c = h.scomp[0];
         s.nb = 1;
@@ -1944,14 +2166,14 @@ VF_API int vf_jpeg_prog_workspace_bytes(const unsigned char* data, const int64_t
   return 0;
 }
 
-VF_API int vf_jpeg_prog_coefficients_host(const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef, size_t coef_blocks,
-                                          int32_t* status) {
-  VF_REQUIRE(data && coef && status, "vf_jpeg_prog_coefficients_host: NULL argument");
+// the assembled coefficients of one file on the host: the progressive entry's, and with layouts the layouts entry's
+static int jpg_coefficients_host(const char* who, bool layouts, const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef,
+                                 size_t coef_blocks, int32_t* status) {
+  VF_REQUIRE(data && coef && status, "%s: NULL argument", who);
   const int64_t offs[2] = {0, (int64_t)len}, out_offs[2] = {0, 0};
   ProgPlan L;
-  if (int e = jpg_prog_plan(data, offs, 1, subseq_bytes, L)) return e;
-  VF_REQUIRE((int64_t)coef_blocks >= L.nblk, "vf_jpeg_prog_coefficients_host: room for %zu blocks, the file has %lld", coef_blocks,
-             (long long)L.nblk);
+  if (int e = jpg_prog_plan(data, offs, 1, subseq_bytes, L, layouts)) return e;
+  VF_REQUIRE((int64_t)coef_blocks >= L.nblk, "%s: room for %zu blocks, the file has %lld", who, coef_blocks, (long long)L.nblk);
   std::vector<uint64_t> stage(L.stage / 8 + 1), bits((size_t)L.bits_bytes / 8 + 1, 0);
   uint8_t* st = (uint8_t*)stage.data();
   jpg_prog_pack(data, offs, 1, 3, subseq_bytes, out_offs, L, st);
@@ -1974,18 +2196,30 @@ VF_API int vf_jpeg_prog_coefficients_host(const unsigned char* data, size_t len,
   return 0;
 }
 
-VF_API int vf_jpeg_prog_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes,
-                               const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
-                               int32_t* status, int32_t* rounds, int32_t* levels) {
-  VF_REQUIRE(channels == 1 || channels == 3, "vf_jpeg_prog_decode: channels %d is not 1 or 3", channels);
-  VF_REQUIRE(out && out_offs && stage && ws && status && rounds, "vf_jpeg_prog_decode: NULL argument");
-  VF_REQUIRE(subseq_bytes != 0, "vf_jpeg_prog: subsequence size 0 outside [8, 1 MiB]");
+VF_API int vf_jpeg_prog_coefficients_host(const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef, size_t coef_blocks,
+                                          int32_t* status) {
+  return jpg_coefficients_host("vf_jpeg_prog_coefficients_host", false, data, len, subseq_bytes, coef, coef_blocks, status);
+}
+
+VF_API int vf_jpeg_layouts_coefficients_host(const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef, size_t coef_blocks,
+                                             int32_t* status) {
+  return jpg_coefficients_host("vf_jpeg_layouts_coefficients_host", true, data, len, subseq_bytes, coef, coef_blocks, status);
+}
+
+// the progressive entry's decode, and with layouts the layouts entry's: sequential scans join the first scans' launch
+static int jpg_scans_decode(const char* who, bool layouts, vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels,
+                            int subseq_bytes, const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws,
+                            size_t ws_bytes, int32_t* status, int32_t* rounds, int32_t* levels) {
+  VF_REQUIRE(channels == 1 || channels == 3, "%s: channels %d is not 1 or 3", who, channels);
+  VF_REQUIRE(out && out_offs && stage && ws && status && rounds, "%s: NULL argument", who);
+  VF_REQUIRE(subseq_bytes != 0, "%s: subsequence size 0 outside [8, 1 MiB]", layouts ? "vf_jpeg_layouts" : "vf_jpeg_prog");
   ProgPlan L;
-  if (int e = jpg_prog_plan(data, offs, n, subseq_bytes, L)) return e;
-  VF_REQUIRE(stage_bytes >= L.stage && ws_bytes >= L.ws, "vf_jpeg_prog_decode: staging %zu / workspace %zu bytes, need %zu / %zu",
-             stage_bytes, ws_bytes, L.stage, L.ws);
+  if (int e = jpg_prog_plan(data, offs, n, subseq_bytes, L, layouts)) return e;
+  VF_REQUIRE(stage_bytes >= L.stage && ws_bytes >= L.ws, "%s: staging %zu / workspace %zu bytes, need %zu / %zu", who, stage_bytes, ws_bytes,
+             L.stage, L.ws);
   for (int i = 0; i < n; ++i)
-    VF_REQUIRE(!(L.G[i].P.ncomp == 3 && channels == 1), "vf_jpeg_prog_decode: image %d is YCbCr; channels=1 takes grayscale files only", i);
+    VF_REQUIRE(!(L.G[i].P.ncomp == 3 && channels == 1), "%s: image %d is %s; channels=1 takes grayscale files only", who, i,
+               L.G[i].P.rgb ? "RGB" : "YCbCr");
   jpg_prog_pack(data, offs, n, channels, subseq_bytes, out_offs, L, (uint8_t*)stage);
   uint8_t* w = (uint8_t*)ws;
   JpgBatch B = {};
@@ -2042,9 +2276,66 @@ VF_API int vf_jpeg_prog_decode(vf_ctx* ctx, const unsigned char* data, const int
   VF_LAUNCH_TIMED(ctx, "jpeg_idct", 0.0, 192.0 * L.nblk, k_jpeg_idct, dim3(gb, n), dim3(256), B);
   VF_LAUNCH_CHECK();
   const unsigned gp = (unsigned)std::min<int64_t>(vf_cdiv(L.max_pix, 256), 4096);
-  VF_LAUNCH_TIMED(ctx, "jpeg_color", 0.0, 2.0 * L.plane_bytes, k_jpeg_color, dim3(gp, n), dim3(256), B);
+  if (layouts) VF_LAUNCH_TIMED(ctx, "jpeg_color", 0.0, 2.0 * L.plane_bytes, k_jpeg_color_layouts, dim3(gp, n), dim3(256), B);
+  else VF_LAUNCH_TIMED(ctx, "jpeg_color", 0.0, 2.0 * L.plane_bytes, k_jpeg_color, dim3(gp, n), dim3(256), B);
   VF_LAUNCH_CHECK();
   if (levels) *levels = (int32_t)L.level_segs.size();
+  return 0;
+}
+
+VF_API int vf_jpeg_prog_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes,
+                               const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
+                               int32_t* status, int32_t* rounds, int32_t* levels) {
+  return jpg_scans_decode("vf_jpeg_prog_decode", false, ctx, data, offs, n, channels, subseq_bytes, out_offs, out, stage, stage_bytes, ws,
+                          ws_bytes, status, rounds, levels);
+}
+
+VF_API int vf_jpeg_decode_layouts(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes,
+                                  const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
+                                  int32_t* status, int32_t* rounds, int32_t* levels) {
+  return jpg_scans_decode("vf_jpeg_decode_layouts", true, ctx, data, offs, n, channels, subseq_bytes, out_offs, out, stage, stage_bytes, ws,
+                          ws_bytes, status, rounds, levels);
+}
+
+VF_API int vf_jpeg_layouts_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
+                                           size_t* stage_bytes) {
+  VF_REQUIRE(subseq_bytes != 0, "vf_jpeg_layouts: subsequence size 0 outside [8, 1 MiB]");
+  ProgPlan L;
+  if (int e = jpg_prog_plan(data, offs, n, subseq_bytes, L, true)) return e;
+  if (ws_bytes) *ws_bytes = L.ws;
+  if (stage_bytes) *stage_bytes = L.stage;
+  return 0;
+}
+
+// info (int64[20]) = {width, height, components, h0, v0, h1, v1, h2, v2, colour (0 grey, 1 YCbCr, 2 RGB), scans, supported,
+// sof, precision, levels, blocks, blocks per MCU, 0, 0, 0}
+VF_API int vf_jpeg_inspect_layouts(const unsigned char* data, size_t len, int64_t* info, char* reason, int reason_cap) {
+  VF_REQUIRE(data && info, "vf_jpeg_inspect_layouts: NULL argument");
+  ProgParsed G;
+  std::string msg;
+  if (int rc = jpg_prog_parse(data, (int64_t)len, G, msg, true)) {
+    vf_set_error("vf_jpeg_inspect_layouts: %s", msg.c_str());
+    return rc;
+  }
+  const JpgParsed& P = G.P;
+  const bool geo = (P.ncomp == 1 || P.ncomp == 3) && P.W > 0 && P.H > 0 && P.supported;
+  for (int i = 0; i < 20; ++i) info[i] = 0;
+  info[0] = P.W;
+  info[1] = P.H;
+  info[2] = P.ncomp;
+  for (int c = 0; c < 3 && c < P.ncomp; ++c) {
+    info[3 + 2 * c] = P.hf[c];
+    info[4 + 2 * c] = P.vf[c];
+  }
+  info[9] = P.ncomp == 1 ? 0 : P.rgb ? 2 : 1;
+  info[10] = (int64_t)G.scans.size();
+  info[11] = P.supported ? 1 : 0;
+  info[12] = P.sof;
+  info[13] = P.prec;
+  info[14] = G.nlevel;
+  info[15] = geo ? G.nblocks() : 0;
+  info[16] = geo ? G.bpm() : 0;
+  if (reason && reason_cap > 0) snprintf(reason, (size_t)reason_cap, "%s", P.why.c_str());
   return 0;
 }
 

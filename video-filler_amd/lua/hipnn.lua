@@ -157,6 +157,10 @@ int vf_jpeg_encode_opts_workspace_bytes(int n, int H, int W, int C, int subsampl
 int vf_jpeg_encode_opts(vf_ctx*, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling, int restart_rows, int restart_blocks, int optimize, void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
 int vf_jpeg_encode_prog_workspace_bytes(int n, int H, int W, int C, int subsampling, size_t* ws_bytes, size_t* out_bytes);
 int vf_jpeg_encode_prog(vf_ctx*, const void* src, int kind, int n, int H, int W, int C, int quality, int subsampling, void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
+int vf_jpeg_inspect_layouts(const unsigned char* data, size_t len, int64_t* info, char* reason, int reason_cap);
+int vf_jpeg_layouts_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes, size_t* stage_bytes);
+int vf_jpeg_decode_layouts(vf_ctx*, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes, const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes, int32_t* status, int32_t* rounds, int32_t* levels);
+int vf_jpeg_layouts_coefficients_host(const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef, size_t coef_blocks, int32_t* status);
 int vf_display_workspace_bytes(int N, int C, int h, int w, int padding, int nrow, int scaleeach, int has_min, int has_max, size_t* ws_bytes);
 int vf_display_tensor(vf_ctx*, const float* packed, int src_layout, float* grid, int N, int C, int h, int w, int padding, int nrow, int scaleeach, int has_min, double min, int has_max, double max, int symmetric, int saturate);
 int vf_center_finish(vf_ctx*, const float* ctx_nhwc, const float* pred_nhwc, float* pretty, float* pasted, float* pred_mapped, int B, int C, int fs, int overlapPred);
