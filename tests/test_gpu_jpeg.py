@@ -108,6 +108,38 @@ def test_corrupt_data_raises_after_sync():
         data.decode_jpeg([cut])
 
 
+def _truncated():
+    n = [x for x in NAMES if x.startswith("420_360x480")][0]
+    buf = _file(n)
+    return buf[:data.jpeg_info(buf)["scan_begin"] + 2000] + b"\xff\xd9"   # the file of test_corrupt_data_raises_after_sync
+
+
+def test_default_entry_is_the_layouts_entry_on_baseline_files():
+    # one scan of a baseline file is one sequential first scan of the shared pipeline: same bytes, statuses and rounds
+    files = [_file(n) for n in NAMES]
+    B = get_backend()
+    for sub in (16, 1024):
+        buf, offs, status, rounds = B.jpeg_decode(files, 3, sub)
+        lbuf, loffs, lstatus, lrounds, levels = B.jpeg_decode_layouts(files, 3, sub)
+        torch.cuda.synchronize()
+        assert levels == 1 and list(offs) == list(loffs)
+        assert torch.equal(buf, lbuf)
+        assert status.cpu().tolist() == lstatus.cpu().tolist() == [0] * len(files)
+        assert rounds.item() == lrounds.item() >= 1
+    cut = [_truncated()]
+    (_, _, status, _), (_, _, lstatus, _, _) = B.jpeg_decode(cut, 3, 256), B.jpeg_decode_layouts(cut, 3, 256)
+    torch.cuda.synchronize()
+    assert status.cpu().tolist() == lstatus.cpu().tolist() and status.item() != 0
+    # a run of zero bytes decodes as short blocks, so a restart segment's last block ends more than a 16-byte subsequence
+    # before its data does: the bits behind it are skipped, as libjpeg skips them (the lane this entry once had read on)
+    early = bytearray(_file("420_17x33_noise_q50_b4"))
+    early[651:672] = bytes(21)
+    for sub in (16, 256):
+        (_, _, status, _), (_, _, lstatus, _, _) = B.jpeg_decode([bytes(early)], 3, sub), B.jpeg_decode_layouts([bytes(early)], 3, sub)
+        torch.cuda.synchronize()
+        assert status.cpu().tolist() == lstatus.cpu().tolist() == [0]
+
+
 def test_malformed_files_raise_naming_the_item():
     good = _file(NAMES[0])
     b = bytearray(_file("420_360x480_noise_q90_none"))

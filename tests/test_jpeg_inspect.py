@@ -1,5 +1,6 @@
 """The host-only JPEG inspector (vf_jpeg_inspect): geometry, sampling, restart interval and scan range of
-baseline files; progressive, CMYK and 4:1:1 files reported as unsupported; malformed headers rejected with a message.
+baseline files; progressive, CMYK and 4:1:1 files reported as unsupported; malformed headers rejected with a message;
+the header-only sizes of vf_jpeg_workspace_bytes against the exact plan the decode makes.
 Encodes with Pillow when it is importable, otherwise reads the committed fixtures (tests/golden/jpeg_cases.npz)."""
 import ctypes as C
 import io
@@ -10,7 +11,7 @@ import pytest
 
 import video_filler_amd  # noqa: F401
 from video_filler_amd import _lib, data
-from video_filler_amd.backend import jpeg_inspect
+from video_filler_amd.backend import jpeg_inspect, jpeg_inspect_layouts
 
 try:
     from PIL import Image
@@ -177,6 +178,76 @@ def test_headers_only_mode_agrees(name):
     assert head["scan_end"] == head["segments"] == -1
     assert {k: v for k, v in full.items() if k not in ("scan_end", "segments")} == \
         {k: v for k, v in head.items() if k not in ("scan_end", "segments")}
+
+
+NAMES = sorted(k[4:] for k in GOLDEN.files if k.startswith("jpg/"))
+
+
+def _with_restart_interval(buf, ri):
+    """buf with its DRI marker (if any) dropped and one of `ri` MCUs put before the SOS."""
+    b = bytearray(buf)
+    sos = b.index(b"\xff\xda")
+    k = b.find(b"\xff\xdd\x00\x04", 0, sos)
+    if k >= 0:
+        del b[k:k + 6]
+        sos -= 6
+    b[sos:sos] = b"\xff\xdd\x00\x04" + ri.to_bytes(2, "big")
+    return bytes(b)
+
+
+def _bound_batches():
+    """name -> files: every fixture alone (the restart ones among them), all of them as one batch, and two hand-made files
+    that strain a header-only bound: the smallest scan with a segment's fixed costs on it (grey 8x8, restart interval 1),
+    and a scan of stuffed 0xFF00 pairs, whose compacted length is half its stuffed one and which spans several chunks."""
+    d = {n: [_fixture("jpg/" + n)] for n in NAMES}
+    d["all"] = [_fixture("jpg/" + n) for n in NAMES]
+    d["grey_8x8_ri1"] = [_with_restart_interval(_fixture("jpg/L_8x8_flat_q5_b1"), 1)]
+    big = _fixture("jpg/420_360x480_noise_q90_none")
+    d["stuffed"] = [big[:jpeg_inspect(big, walk=False)["scan_begin"]] + b"\xff\x00" * 5000 + b"\xff\xd9"]
+    return d
+
+
+BOUND_BATCHES = _bound_batches()
+
+
+def _sizes(entry, files, sub):
+    lib = _lib.load()
+    joined = b"".join(files)
+    offs = np.cumsum([0] + [len(f) for f in files]).astype(np.int64)
+    ws, st = C.c_size_t(), C.c_size_t()
+    assert getattr(lib, entry)(joined, offs.ctypes.data_as(C.c_void_p), len(files), sub, C.byref(ws), C.byref(st)) == 0, lib.vf_last_error()
+    return ws.value, st.value
+
+
+@pytest.mark.parametrize("sub", [8, 16, 256, 1024])
+@pytest.mark.parametrize("name", sorted(BOUND_BATCHES))
+def test_header_only_sizes_cover_the_exact_plan(name, sub):
+    # vf_jpeg_decode plans as the layouts entry does, from the walked scan; vf_jpeg_workspace_bytes reads the headers only
+    files = BOUND_BATCHES[name]
+    if name == "grey_8x8_ri1":
+        info = jpeg_inspect(files[0])
+        assert info["supported"] and (info["width"], info["height"], info["restart_interval"], info["segments"]) == (8, 8, 1, 1)
+    bound, exact = _sizes("vf_jpeg_workspace_bytes", files, sub), _sizes("vf_jpeg_layouts_workspace_bytes", files, sub)
+    assert bound[0] >= exact[0] and bound[1] >= exact[1], (bound, exact)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_walked_scan_equals_the_layouts_walk_and_the_bytes(name):
+    buf = _fixture("jpg/" + name)
+    info, lay = jpeg_inspect(buf), jpeg_inspect_layouts(buf)
+    assert info["supported"] and lay["supported"] and lay["scans"] == 1 and lay["levels"] == 1
+    assert (info["width"], info["height"], info["components"], info["sof"]) == (lay["width"], lay["height"], lay["components"], lay["sof"])
+    sos = buf.index(b"\xff\xda")
+    assert info["scan_begin"] == sos + 2 + int.from_bytes(buf[sos + 2:sos + 4], "big")
+    eoi = buf.rindex(b"\xff\xd9")
+    assert info["scan_end"] == eoi
+    # inside entropy-coded data a 0xFF is followed by 0x00 or by a restart marker, so the pairs can be counted as bytes
+    scan = buf[info["scan_begin"]:eoi]
+    assert info["segments"] == 1 + sum(scan.count(bytes([0xFF, 0xD0 + r])) for r in range(8))
+    dri = buf.find(b"\xff\xdd\x00\x04", 0, sos)
+    assert info["restart_interval"] == (int.from_bytes(buf[dri + 4:dri + 6], "big") if dri >= 0 else 0)
+    mcus = lay["blocks"] // lay["blocks_per_mcu"]
+    assert info["segments"] == (-(-mcus // info["restart_interval"]) if info["restart_interval"] else 1)
 
 
 def test_path_items(tmp_path):

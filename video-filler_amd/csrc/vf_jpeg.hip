@@ -1,25 +1,28 @@
-// vf_jpeg.hip — batched baseline-JPEG decode on the device, byte for byte libjpeg's default decompression.
-//   * vf_jpeg_inspect (host only): markers, geometry, sampling, restart interval, scan range, supported or why not;
-//   * vf_jpeg_workspace_bytes: device workspace and host staging sizes of one batch;
-//   * vf_jpeg_decode: N files -> N uint8 H x W x C images at caller-given offsets of one buffer.
-// Pipeline (the launch count does not depend on N): the host parses the headers, builds the Huffman decode tables
-// (9-bit lookahead + max-code fallback), the natural-order dequantisation tables and the restart segments, and packs
+// vf_jpeg.hip — batched JPEG decode on the device, byte for byte libjpeg's default decompression.
+// One pipeline, three rules (JpgRule) for which files it takes and how its errors are worded:
+//   baseline     vf_jpeg_inspect, vf_jpeg_workspace_bytes, vf_jpeg_decode: SOF0 / SOF1 files of ONE scan, 4:4:4 / 4:2:2 /
+//                4:2:0 or grey.  The workspace query reads the headers only (upper bounds), so the scan data is walked once;
+//   progressive  vf_jpeg_scans_inspect, vf_jpeg_prog_*: SOF2 files;
+//   layouts      vf_jpeg_inspect_layouts, vf_jpeg_layouts_*, vf_jpeg_decode_layouts: both kinds, any whole-number sampling,
+//                RGB, sequential files of several scans ("layouts").
+// Each decode entry turns N files into N uint8 H x W x C images at caller-given offsets of one buffer.  The launch count
+// does not depend on N: the host parses the headers, walks every scan for its restart segments and stuffed bytes, builds
+// the Huffman decode tables (9-bit lookahead + max-code fallback) and the natural-order dequantisation tables, and packs
 // them with every scan's bytes into one staging buffer -> one upload.  Then
-//   k_jpeg_unstuff   one wave per 4 KiB chunk drops the stuffed 0x00 bytes; the host found every 0xFF
-//                    while it parsed, so each chunk's output offset is known and the chunks are independent;
-//   k_jpeg_huffman   one block per segment: parallel Huffman decoding by self-synchronisation (Weißenberger & Schmidt,
-//                    ICPP 2018) over fixed-size subsequences, then the write pass (de-zigzagged int16 coefficients) and
-//                    the DC prediction as a segmented scan per component;
-//   k_jpeg_idct      one thread per 8x8 block: dequantise, jpeg_idct_islow, range-limit into uint8 component planes;
-//   k_jpeg_color     one thread per output pixel: fancy upsampling, ycc_rgb_convert, crop into H x W x C.
-// Everything is integer arithmetic.
-// Progressive (SOF2) files share all of it but k_jpeg_huffman: vf_jpeg_scans_inspect walks their scans,
-// vf_jpeg_prog_decode assembles the coefficients scan level by scan level and runs the same IDCT and colour launches,
-// vf_jpeg_prog_coefficients_host assembles them on the host with the same functions.
-// Other samplings, RGB and sequential files of several scans ("layouts"): vf_jpeg_decode_layouts is the
-// progressive entry with a wider plan.  A sequential scan is a first scan whose lanes read a DC symbol and then AC symbols
-// per block (prog_first_lane), so its restart segments join k_jpeg_prog_first's launch; k_jpeg_idct places blocks by each
-// component's own factors and k_jpeg_color_layouts samples every component by its own upsampler.
+//   k_jpeg_unstuff     one wave per 4 KiB chunk drops the stuffed 0x00 bytes; the host found every 0xFF
+//                      while it parsed, so each chunk's output offset is known and the chunks are independent;
+//   k_jpeg_prog_first  one block per (image, first scan, restart segment): parallel Huffman decoding by
+//                      self-synchronisation (Weißenberger & Schmidt, ICPP 2018) over fixed-size subsequences, then the
+//                      write pass (de-zigzagged int16 coefficients) and the DC prediction as a segmented scan per
+//                      component.  A sequential scan is a first scan whose lanes read a DC symbol and then AC symbols per
+//                      block (prog_first_lane<WRITE, SEQ>); a baseline file is one such scan;
+//   k_jpeg_prog_scan   one launch per further scan level (progressive refinements): one lane per (image, scan, segment);
+//   k_jpeg_idct        one thread per 8x8 block: dequantise, jpeg_idct_islow, range-limit into uint8 component planes,
+//                      each block placed by its component's own factors;
+//   k_jpeg_color       one thread per output pixel: fancy upsampling, ycc_rgb_convert, crop into H x W x C
+//                      (k_jpeg_color_layouts under the layouts rule: every component by its own upsampler, RGB copied).
+// Everything is integer arithmetic.  vf_jpeg_prog_coefficients_host and vf_jpeg_layouts_coefficients_host assemble the
+// coefficients on the host with the same lane functions.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -56,17 +59,8 @@ struct JpgImage {
   int32_t hc[3], vc[3];        // per component: its sampling factors (1, 1 for grayscale)
   int32_t up[3];               // per component: its upsampler, UP_* (layouts)
   int32_t rgb;                 // 1: the three planes are R, G, B and are copied (layouts)
-  int32_t tab0;                // first of the image's 4 tables: DC0, DC1, AC0, AC1
-  int32_t bcomp[10], bx[10], by[10], dct[10], act[10];   // per block of the MCU: component, block offset in it, tables
+  int32_t bcomp[10], bx[10], by[10];   // per block of the MCU: component, block offset in it
   int32_t q[3][64];            // natural-order quantisation values per component
-};
-
-struct JpgSeg {
-  int64_t src;                 // first byte in the scan-byte section of the upload (stuffed)
-  int64_t dst;                 // first byte in `bits` (compacted; 16-byte aligned, 16 bytes of slack behind)
-  int64_t sub0;                // first subsequence
-  int32_t slen, len;           // stuffed / compacted bytes
-  int32_t img, mcu0, nmcu, nsub;
 };
 
 // a piece of one segment's stuffed bytes and where its kept bytes go
@@ -78,7 +72,6 @@ struct JpgChunk {
 
 struct JpgBatch {
   const JpgImage* img;
-  const JpgSeg* seg;
   const JpgChunk* chunk;
   const JpgHuff* huff;
   const uint8_t* scan;         // stuffed bytes (uploaded)
@@ -92,7 +85,7 @@ struct JpgBatch {
   uint8_t* out;
   int32_t* status;
   int32_t* rounds;
-  int nseg, nchunk, sub_bits;
+  int nchunk, sub_bits;
 };
 
 __host__ __device__ constexpr int zz_natural(int k) {
@@ -173,54 +166,6 @@ VF_HD int huff_extend(uint32_t r, int s) {  // HUFF_EXTEND
 
 enum { LANE_END = 0, LANE_DONE = 1, LANE_BAD = 2, LANE_SHORT = 3 };
 
-// Decode symbols from state (p, b, k) while the next symbol starts before pend.  WRITE: store the coefficients (DC as
-// the difference) of block nb - 1 / nb ... at coef (the segment's first block), stop once `total` blocks are complete.
-// Returns LANE_*; (p, b, k) is the state at the stop, ndc the number of DC symbols decoded.
-template <bool WRITE>
-__host__ __device__ int decode_lane(const JpgImage& im, const JpgHuff* tabs, BitWin& bw, uint32_t nbits, uint32_t& p, int& b, int& k,
-                           uint32_t pend, int& ndc, int64_t nb, int64_t total, int16_t* coef) {
-  ndc = 0;
-  bw.seek(p);
-  for (;;) {
-    if (WRITE && k == 0 && nb >= total) return LANE_DONE;
-    if (p >= pend) return LANE_END;
-    const uint32_t w = bw.peek(p);
-    int sym;
-    if (k == 0) {
-      const int l = huff_decode(tabs[im.dct[b]], w, sym);
-      if (!l) return LANE_BAD;
-      const int s = sym;       // DC tables hold categories <= 15 (checked on the host)
-      if (p + (uint32_t)(l + s) > nbits) return LANE_SHORT;
-      int diff = 0;
-      if (s) diff = huff_extend((w << l) >> (32 - s), s);
-      p += l + s;
-      if (WRITE) coef[nb * 64] = (int16_t)diff;
-      ++nb;
-      ++ndc;
-      k = 1;
-    } else {
-      const int l = huff_decode(tabs[im.act[b]], w, sym);
-      if (!l) return LANE_BAD;
-      const int r = sym >> 4, s = sym & 15;
-      if (p + (uint32_t)(l + s) > nbits) return LANE_SHORT;
-      if (s) {
-        k += r;
-        if (WRITE && nb > 0) coef[(nb - 1) * 64 + natural(k)] = (int16_t)huff_extend((w << l) >> (32 - s), s);
-        ++k;
-      } else if (r == 15) {
-        k += 16;
-      } else {
-        k = 64;   // EOB
-      }
-      p += l + s;
-    }
-    if (k >= 64) {
-      k = 0;
-      if (++b == im.bpm) b = 0;
-    }
-  }
-}
-
 // one wave per chunk: keep every byte but the 0x00 after a 0xFF (stuffing)
 __global__ void k_jpeg_unstuff(const JpgBatch B) {
   const int lane = threadIdx.x & 63;
@@ -242,128 +187,6 @@ __global__ void k_jpeg_unstuff(const JpgBatch B) {
     const int pos = base + (int)__popcll(m & ((1ull << lane) - 1));
     if (keep && pos < ck.keep) out[pos] = v;
     base += (int)__popcll(m);
-  }
-}
-
-// one block per restart segment
-__global__ __launch_bounds__(kHuffThreads) void k_jpeg_huffman(const JpgBatch B) {
-  __shared__ JpgHuff tabs[4];
-  __shared__ int s_w[kHuffThreads / 64];                  // wave totals of the block scans
-  __shared__ int changed;
-  const int t = threadIdx.x;
-  const int s = blockIdx.x;
-  const JpgSeg sg = B.seg[s];
-  const JpgImage& im = B.img[sg.img];
-  {
-    const uint32_t* src = (const uint32_t*)(B.huff + im.tab0);
-    uint32_t* dst = (uint32_t*)tabs;
-    for (int i = t; i < (int)(4 * sizeof(JpgHuff) / 4); i += kHuffThreads) dst[i] = src[i];
-  }
-  __syncthreads();
-  const uint32_t* bits = (const uint32_t*)(B.bits + sg.dst);
-  const uint32_t nbits = 8u * (uint32_t)sg.len;
-  const uint32_t sb = (uint32_t)B.sub_bits;
-  const int nsub = sg.nsub;
-  uint64_t* E = B.E + sg.sub0;
-  uint64_t* X = B.X + sg.sub0;
-  int32_t* Nb = B.Nb + sg.sub0;
-  uint8_t* D = B.D + sg.sub0;
-  const int64_t total = (int64_t)sg.nmcu * im.bpm;
-  int16_t* coef = B.coef + (im.coef_base + (int64_t)sg.mcu0 * im.bpm) * 64;
-  BitWin bw{bits, 0, 0, 0};
-
-  auto run = [&](int i, uint64_t e) {
-    uint32_t p = (uint32_t)(e >> 16);
-    int b = (int)((e >> 8) & 0xff), k = (int)(e & 0xff), ndc;
-    const uint32_t pend = min(nbits, (uint32_t)(i + 1) * sb);
-    const int r = decode_lane<false>(im, tabs, bw, nbits, p, b, k, pend, ndc, 0, 0, nullptr);
-    X[i] = r == LANE_END ? st_pack(p, b, k) : kDead;
-    Nb[i] = ndc;
-  };
-  // speculative start of every subsequence at its first bit, at the start of an MCU
-  for (int i = t; i < nsub; i += kHuffThreads) {
-    const uint64_t e = st_pack((uint32_t)i * sb, 0, 0);
-    E[i] = e;
-    run(i, e);
-  }
-  // synchronise: a lane whose entry state differs from its predecessor's exit state decodes again from it.  A dead exit
-  // (the predecessor stopped on an invalid code) is no information: the lane keeps its state, otherwise the dead state
-  // would travel one lane per round to the end of the segment with the corrections behind it
-  int nround = 0;
-  for (;;) {
-    if (t == 0) changed = 0;
-    __syncthreads();
-    for (int i = t; i < nsub; i += kHuffThreads) {
-      D[i] = 0;
-      if (i == 0) continue;
-      const uint64_t x = X[i - 1];
-      if (x != E[i] && x != kDead) {
-        E[i] = x;
-        D[i] = 1;
-        changed = 1;
-      }
-    }
-    __syncthreads();
-    if (!changed) break;
-    ++nround;
-    for (int i = t; i < nsub; i += kHuffThreads)
-      if (D[i]) run(i, E[i]);
-    __syncthreads();
-  }
-  if (t == 0) atomicMax(B.rounds, nround);
-  // exclusive scan of the DC symbols per subsequence -> index of the first block each lane starts
-  {
-    int carry = 0;
-    for (int c = 0; c < nsub; c += kHuffThreads) {
-      const int i = c + t;
-      const int v = i < nsub ? Nb[i] : 0;
-      int tot;
-      const int pre = vf_block_excl_scan<int, kHuffThreads>(v, s_w, tot);
-      if (i < nsub) Nb[i] = carry + pre;
-      carry += tot;
-    }
-  }
-  __syncthreads();
-  // write pass from the synchronised states.  Behind a dead exit the chain is broken: that predecessor meets the invalid
-  // code in its own write pass, and this lane writes nothing (an error only if it still owes blocks)
-  int err = ST_OK;
-  for (int i = t; i < nsub; i += kHuffThreads) {
-    const uint64_t e = E[i];
-    const int64_t nb = Nb[i];
-    if (i > 0 && X[i - 1] == kDead) {
-      if (nb < total) err = ST_BAD;
-      continue;
-    }
-    uint32_t p = (uint32_t)(e >> 16);
-    int b = (int)((e >> 8) & 0xff), k = (int)(e & 0xff), ndc;
-    const uint32_t pend = min(nbits, (uint32_t)(i + 1) * sb);
-    const int r = decode_lane<true>(im, tabs, bw, nbits, p, b, k, pend, ndc, nb, total, coef);
-    if (r == LANE_BAD) err = ST_BAD;
-    else if (r == LANE_SHORT || (r == LANE_END && i == nsub - 1)) err = max(err, (int)ST_SHORT);
-  }
-  if (err != ST_OK) atomicMax(B.status + sg.img, err);
-  __syncthreads();
-  // DC prediction: per component, a running sum over the segment's blocks in MCU order (reset at every segment)
-  int carry[3] = {0, 0, 0};
-  for (int c = 0; c < sg.nmcu; c += kHuffThreads) {
-    const int m = c + t;
-    int sum[3] = {0, 0, 0};
-    if (m < sg.nmcu)
-      for (int b = 0; b < im.bpm; ++b) sum[im.bcomp[b]] += coef[((int64_t)m * im.bpm + b) * 64];
-    int run[3];
-    for (int ci = 0; ci < 3; ++ci) {
-      int tot;
-      run[ci] = carry[ci] + vf_block_excl_scan<int, kHuffThreads>(sum[ci], s_w, tot);
-      carry[ci] += tot;
-    }
-    if (m < sg.nmcu) {
-      for (int b = 0; b < im.bpm; ++b) {
-        int16_t* dc = coef + ((int64_t)m * im.bpm + b) * 64;
-        const int ci = im.bcomp[b];
-        run[ci] += *dc;
-        *dc = (int16_t)run[ci];
-      }
-    }
   }
 }
 
@@ -608,27 +431,41 @@ inline bool huff_fits(const uint8_t* bits) {
   return true;
 }
 
+// What a file must be for an entry to take it, and how the entry words its errors.  On the device it decides nothing but
+// the colour kernel.
+//   BASELINE     SOF0 / SOF1 files of one scan, 4:4:4 / 4:2:2 / 4:2:0 or grey, two Huffman slots per class;
+//   PROGRESSIVE  SOF2 files of the same samplings; SOF2 is no reason, and the scan checks are jpg_prog_parse's;
+//   LAYOUTS      SOF0 / SOF1 / SOF2, any whole-number sampling, RGB, sequential files of several scans.
+enum JpgKind { BASELINE, PROGRESSIVE, LAYOUTS };
+struct JpgRule {
+  JpgKind kind;
+  const char* who;       // what the messages about the batch's files start with
+  const char* upload;    // profiling labels of the upload range and of the first scans' launch
+  const char* entropy;
+};
+constexpr JpgRule kBaselineRule = {BASELINE, "vf_jpeg", "jpeg_upload", "jpeg_huffman"};
+constexpr JpgRule kProgressiveRule = {PROGRESSIVE, "vf_jpeg_prog", "jpeg_prog_upload", "jpeg_prog_first"};
+constexpr JpgRule kLayoutsRule = {LAYOUTS, "vf_jpeg_layouts", "jpeg_prog_upload", "jpeg_prog_first"};
+
 struct JpgParsed {
   int W = 0, H = 0, ncomp = 0, prec = 0, sof = -1, ri = 0, hmax = 1, vmax = 1;
   int cid[4] = {}, hf[4] = {}, vf[4] = {}, tq[4] = {};
   int ns = 0, scomp[4] = {}, td[4] = {}, ta[4] = {};
   int ss = 0, se = 63, ahal = 0;
   bool jfif = false, adobe = false;
-  bool take_sof2 = false;   // set by the progressive path: SOF2 is no reason, and the scan checks are left to it
-  bool layouts = false;     // set by the layouts path: SOF0 / SOF1 / SOF2, any whole-number sampling, RGB; the scans are its own
   bool rgb = false;         // layouts: the components are R, G, B (jdapimin.c default_decompress_parms)
   int adobe_transform = -1;
-  int64_t scan_begin = 0, scan_end = 0;
+  int64_t scan_begin = 0;   // of the scan whose SOS was read last
   bool supported = false;
   std::string why;
   uint16_t qt[4][64] = {};   // natural order
   bool qt_ok[4] = {};
   RawHuff hdc[4] = {}, hac[4] = {};
-  struct Seg {
-    int64_t begin, end, len;
-  };
-  std::vector<Seg> segs;
-  std::vector<int64_t> drops;   // positions of the bytes unstuffing drops, ascending
+};
+
+// one restart segment of a scan: its stuffed bytes [begin, end) of the file and how many unstuffing keeps
+struct JpgRestartSeg {
+  int64_t begin, end, len;
 };
 
 inline int rd16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
@@ -712,11 +549,12 @@ int jpg_sos(const uint8_t* s, int sl, JpgParsed& P, std::string& msg) {
 // One scan's entropy-coded data from byte `begin`: every 0xFF is stuffing (0xFF00), a restart marker, or the end of the
 // scan.  -> its restart segments, the stuffed 0x00s' positions (appended to drops), its end and the marker there (-1:
 // the data ran out)
-int jpg_walk(const uint8_t* d, int64_t n, int64_t begin, std::vector<JpgParsed::Seg>& segs, std::vector<int64_t>& drops,
+int jpg_walk(const uint8_t* d, int64_t n, int64_t begin, std::vector<JpgRestartSeg>& segs, std::vector<int64_t>& drops,
              int64_t& scan_end, int& end_marker, std::string& msg) {
   int64_t q = begin, seg0 = q, drop = 0;
   int nrst = 0;
   end_marker = -1;
+  drops.reserve(drops.size() + (size_t)(n - begin) / 200 + 16);   // entropy-coded bytes are 0xFF about once in 256
   for (;;) {
     const uint8_t* f = q < n ? (const uint8_t*)memchr(d + q, 0xFF, (size_t)(n - q)) : nullptr;
     if (!f) {
@@ -761,8 +599,10 @@ int jpg_walk(const uint8_t* d, int64_t n, int64_t begin, std::vector<JpgParsed::
   return 0;
 }
 
-// 0: headers parsed (P.supported says whether the decoder takes the file, P.why why not); else malformed (msg)
-int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool walk) {
+// The headers up to the first SOS.  0: parsed (P.supported says whether they let the rule take the file, P.why why not);
+// else malformed (msg).  The entropy-coded data is jpg_prog_parse's.
+int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, JpgKind kind) {
+  const bool layouts = kind == LAYOUTS;
   auto unsupported = [&](const std::string& w) {
     if (P.why.empty()) P.why = w;
   };
@@ -831,7 +671,7 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
         P.hmax = std::max(P.hmax, P.hf[c]);
         P.vmax = std::max(P.vmax, P.vf[c]);
       }
-      if ((m == 0xC2 && P.take_sof2) || (P.layouts && (m == 0xC0 || m == 0xC1))) {
+      if ((m == 0xC2 && kind != BASELINE) || (layouts && (m == 0xC0 || m == 0xC1))) {
       } else if (m == 0xC2 || m == 0xC6 || m == 0xCA || m == 0xCE) unsupported("progressive");
       else if (m == 0xC3 || m == 0xC7 || m == 0xCB || m == 0xCF) unsupported("lossless");
       else if (m >= 0xC9) unsupported("arithmetic coding");
@@ -841,7 +681,7 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
       else if (P.ncomp != 1 && P.ncomp != 3) unsupported(std::to_string(P.ncomp) + " components");
       if (P.W <= 0 || P.H <= 0) unsupported("height or width 0 (DNL)");
       if (P.W > kJpgMaxSide || P.H > kJpgMaxSide) unsupported("larger than 16384 per side");
-      if (P.ncomp == 3 && P.layouts) {
+      if (P.ncomp == 3 && layouts) {
         // jdinput.c initial_setup / jdmaster.c: factors 1..4, whole-number ratios to the largest (libjpeg:
         // JERR_FRACT_SAMPLE_NOTIMPL), at most 10 blocks in an MCU (D_MAX_BLOCKS_IN_MCU, JERR_BAD_MCU_SIZE)
         const std::string f = std::to_string(P.hf[0]) + "x" + std::to_string(P.vf[0]) + "," + std::to_string(P.hf[1]) + "x" +
@@ -897,19 +737,19 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
   if (P.ncomp == 3) {
     if (P.jfif) {
     } else if (P.adobe) {
-      if (P.adobe_transform == 0 && P.layouts) P.rgb = true;
+      if (P.adobe_transform == 0 && layouts) P.rgb = true;
       else if (P.adobe_transform == 0) unsupported("RGB colour transform (Adobe transform 0)");
       else if (P.adobe_transform != 1) unsupported("Adobe transform " + std::to_string(P.adobe_transform));
     } else if (P.cid[0] == 82 && P.cid[1] == 71 && P.cid[2] == 66) {
-      if (P.layouts) P.rgb = true;
+      if (layouts) P.rgb = true;
       else unsupported("RGB components");
     }
   }
-  if ((P.take_sof2 && P.sof == 0xC2) || P.layouts) {   // the scans are jpg_prog_parse's
-    P.scan_end = -1;
+  if (layouts || (kind == PROGRESSIVE && P.sof == 0xC2)) {   // every check of the scans is jpg_prog_parse's
     P.supported = P.why.empty();
     return 0;
   }
+  // the one scan of a baseline file
   if (P.ns != P.ncomp && (P.ncomp == 1 || P.ncomp == 3)) unsupported("multi-scan sequential");
   if (P.ss != 0 || P.se != 63 || P.ahal != 0) unsupported("non-baseline scan parameters");
   for (int i = 0; i < P.ns && P.why.empty(); ++i) {
@@ -932,40 +772,6 @@ int jpg_parse(const uint8_t* d, int64_t n, JpgParsed& P, std::string& msg, bool 
         return 2;
       }
   }
-  if (!walk) {   // headers only: the scan's extent, restart segments and stuffing stay unknown
-    P.scan_end = -1;
-    P.supported = P.why.empty();
-    return 0;
-  }
-  // the entropy-coded data: every 0xFF is stuffing (0xFF00), a restart marker, or the end of the scan
-  const int64_t nmcu = P.ncomp == 1 ? vf_cdiv(P.W, 8) * vf_cdiv(P.H, 8)
-                                    : vf_cdiv(P.W, 8 * P.hmax) * vf_cdiv(P.H, 8 * P.vmax);
-  int end_marker = -1;
-  if (int e = jpg_walk(d, n, P.scan_begin, P.segs, P.drops, P.scan_end, end_marker, msg)) return e;
-  if (end_marker >= 0 && end_marker != 0xD9) {
-    // anything but EOI after the scan: a second scan makes it multi-scan; other markers are skipped
-    int64_t r = P.scan_end;
-    while (r + 1 < n) {
-      if (d[r] != 0xFF) break;
-      while (r < n && d[r] == 0xFF) ++r;
-      if (r >= n) break;
-      const int mm = d[r++];
-      if (mm == 0xD9) break;
-      if (mm == 0xDA) {
-        unsupported("multi-scan sequential");
-        break;
-      }
-      if (r + 2 > n) break;
-      r += rd16(d + r);
-    }
-  }
-  const int64_t want = P.ri > 0 ? vf_cdiv(nmcu, P.ri) : 1;
-  if (P.why.empty() && (int64_t)P.segs.size() != want) {
-    msg = "found " + std::to_string(P.segs.size()) + " restart segments, the restart interval gives " + std::to_string(want);
-    return 2;
-  }
-  for (const auto& sg : P.segs)
-    if (sg.end - sg.begin > (int64_t)1 << 28) unsupported("a restart segment above 256 MiB");
   P.supported = P.why.empty();
   return 0;
 }
@@ -989,176 +795,7 @@ void build_huff(const RawHuff& r, JpgHuff& t) {
   memcpy(t.val, r.val, 256);
 }
 
-// sizes and section offsets of one batch
-struct JpgPlan {
-  std::vector<JpgParsed> P;
-  int64_t nseg = 0, nsub = 0, nblk = 0, plane_bytes = 0, scan_bytes = 0, bits_bytes = 0, nchunk = 0;
-  int64_t max_blocks = 0, max_pix = 0;
-  size_t o_img = 0, o_seg = 0, o_chunk = 0, o_huff = 0, o_scan = 0, stage = 0;   // staging layout (also the front of the workspace)
-  size_t o_bits = 0, o_E = 0, o_X = 0, o_N = 0, o_D = 0, o_coef = 0, o_planes = 0, ws = 0;
-};
-
 inline int64_t seg_bits_bytes(int64_t len) { return ((len + 15) & ~(int64_t)15) + 16; }   // BitWin reads up to 11 bytes past the end
-
-// walk: the exact sizes of a full parse (vf_jpeg_decode); else upper bounds from the headers alone
-// (vf_jpeg_workspace_bytes): a segment's compacted length is at most its stuffed length, and the segments share the
-// bytes from the scan's start to the end of the file
-int jpg_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes, JpgPlan& L, bool walk) {
-  VF_REQUIRE(n > 0 && data && offs, "vf_jpeg: empty batch");
-  VF_REQUIRE(sub_bytes >= 8 && sub_bytes <= (1 << 20), "vf_jpeg: subsequence size %d outside [8, 1 MiB]", sub_bytes);
-  L.P.resize(n);
-  for (int i = 0; i < n; ++i) {
-    std::string msg;
-    VF_REQUIRE(offs[i + 1] >= offs[i], "vf_jpeg: offsets decrease at image %d", i);
-    JpgParsed& P = L.P[i];
-    if (jpg_parse(data + offs[i], offs[i + 1] - offs[i], P, msg, walk)) {
-      vf_set_error("vf_jpeg: image %d: %s", i, msg.c_str());
-      return 2;
-    }
-    if (!P.supported) {
-      vf_set_error("vf_jpeg: image %d: unsupported: %s", i, P.why.c_str());
-      return 3;
-    }
-    const bool gray = P.ncomp == 1;
-    const int64_t mcux = gray ? vf_cdiv(P.W, 8) : vf_cdiv(P.W, 8 * P.hmax), mcuy = gray ? vf_cdiv(P.H, 8) : vf_cdiv(P.H, 8 * P.vmax);
-    const int bpm = gray ? 1 : P.hmax * P.vmax + 2;
-    L.nblk += mcux * mcuy * bpm;
-    L.max_blocks = std::max(L.max_blocks, mcux * mcuy * bpm);
-    L.max_pix = std::max(L.max_pix, (int64_t)P.W * P.H);
-    L.plane_bytes += mcux * mcuy * 64 * bpm;
-    L.plane_bytes = (int64_t)vf_up256((size_t)L.plane_bytes);
-    if (walk) {
-      L.nseg += (int64_t)P.segs.size();
-      for (const auto& s : P.segs) {
-        L.nsub += std::max<int64_t>(1, vf_cdiv(s.len, sub_bytes));
-        L.bits_bytes += seg_bits_bytes(s.len);
-        L.nchunk += vf_cdiv(s.end - s.begin, kChunk);
-      }
-      L.scan_bytes += (int64_t)vf_up256((size_t)(P.scan_end - P.scan_begin) + 8);
-    } else {
-      const int64_t nseg = P.ri > 0 ? vf_cdiv(mcux * mcuy, P.ri) : 1, sb = offs[i + 1] - offs[i] - P.scan_begin;
-      L.nseg += nseg;
-      L.nsub += vf_cdiv(sb, sub_bytes) + nseg;
-      L.bits_bytes += sb + 32 * nseg;
-      L.nchunk += vf_cdiv(sb, kChunk) + nseg;
-      L.scan_bytes += (int64_t)vf_up256((size_t)sb + 8);
-    }
-  }
-  VfCarve ws;
-  L.o_img = ws.take(sizeof(JpgImage) * n);
-  L.o_seg = ws.take(sizeof(JpgSeg) * L.nseg);
-  L.o_chunk = ws.take(sizeof(JpgChunk) * L.nchunk);
-  L.o_huff = ws.take(sizeof(JpgHuff) * 4 * n);
-  L.o_scan = ws.take((size_t)L.scan_bytes);
-  L.stage = ws.at;
-  L.o_bits = ws.take((size_t)L.bits_bytes);
-  L.o_E = ws.take(8 * (size_t)L.nsub);
-  L.o_X = ws.take(8 * (size_t)L.nsub);
-  L.o_N = ws.take(4 * (size_t)L.nsub);
-  L.o_D = ws.take((size_t)L.nsub);
-  L.o_coef = ws.take(128 * (size_t)L.nblk);
-  L.o_planes = ws.take((size_t)L.plane_bytes);
-  L.ws = ws.at;
-  return 0;
-}
-
-// fill the staging buffer
-void jpg_pack(const uint8_t* data, const int64_t* offs, int n, int channels, int sub_bytes, const int64_t* out_offs, const JpgPlan& L,
-              uint8_t* st) {
-  JpgImage* imgs = (JpgImage*)(st + L.o_img);
-  JpgSeg* segs = (JpgSeg*)(st + L.o_seg);
-  JpgChunk* chunks = (JpgChunk*)(st + L.o_chunk);
-  JpgHuff* huffs = (JpgHuff*)(st + L.o_huff);
-  uint8_t* scan = st + L.o_scan;
-  int64_t coef = 0, plane = 0, sc = 0, sub = 0, dst = 0;
-  int si = 0, ci = 0;
-  for (int i = 0; i < n; ++i) {
-    const JpgParsed& P = L.P[i];
-    const uint8_t* d = data + offs[i];
-    JpgImage& im = imgs[i];
-    memset(&im, 0, sizeof(im));
-    const bool gray = P.ncomp == 1;
-    im.W = P.W;
-    im.H = P.H;
-    im.ncomp = P.ncomp;
-    im.channels = channels;
-    im.hs = gray ? 1 : P.hmax;
-    im.vs = gray ? 1 : P.vmax;
-    im.mcux = (int)(gray ? vf_cdiv(P.W, 8) : vf_cdiv(P.W, 8 * P.hmax));
-    im.mcuy = (int)(gray ? vf_cdiv(P.H, 8) : vf_cdiv(P.H, 8 * P.vmax));
-    im.tab0 = 4 * i;
-    // MCU composition in scan order
-    int b = 0;
-    for (int s = 0; s < P.ns; ++s) {
-      const int f = P.scomp[s];
-      const int h = gray ? 1 : P.hf[f], v = gray ? 1 : P.vf[f];
-      for (int y = 0; y < v; ++y)
-        for (int x = 0; x < h; ++x, ++b) {
-          im.bcomp[b] = f;
-          im.bx[b] = x;
-          im.by[b] = y;
-          im.dct[b] = P.td[s];
-          im.act[b] = 2 + P.ta[s];
-        }
-    }
-    im.bpm = b;
-    im.nblocks = im.mcux * im.mcuy * im.bpm;
-    im.coef_base = coef;
-    coef += im.nblocks;
-    for (int c = 0; c < P.ncomp; ++c) {
-      const int h = gray ? 1 : P.hf[c], v = gray ? 1 : P.vf[c];
-      im.hc[c] = h;
-      im.vc[c] = v;
-      im.pw[c] = im.mcux * 8 * h;
-      im.ph[c] = im.mcuy * 8 * v;
-      im.cw[c] = (int)vf_cdiv((int64_t)P.W * h, gray ? 1 : P.hmax);
-      im.ch[c] = (int)vf_cdiv((int64_t)P.H * v, gray ? 1 : P.vmax);
-      im.plane_base[c] = plane;
-      plane += (int64_t)im.pw[c] * im.ph[c];
-      for (int k = 0; k < 64; ++k) im.q[c][k] = P.qt[P.tq[c]][k];
-    }
-    plane = (int64_t)vf_up256((size_t)plane);
-    im.out_off = out_offs[i];
-    for (int t = 0; t < 2; ++t) {
-      build_huff(P.hdc[t], huffs[4 * i + t]);
-      build_huff(P.hac[t], huffs[4 * i + 2 + t]);
-    }
-    const int64_t nbytes = P.scan_end - P.scan_begin;
-    memcpy(scan + sc, d + P.scan_begin, (size_t)nbytes);
-    memset(scan + sc + nbytes, 0, vf_up256((size_t)nbytes + 8) - (size_t)nbytes);
-    const int64_t nmcu = (int64_t)im.mcux * im.mcuy;
-    for (size_t k = 0; k < P.segs.size(); ++k, ++si) {
-      const auto& s = P.segs[k];
-      JpgSeg& g = segs[si];
-      g.src = sc + (s.begin - P.scan_begin);
-      g.dst = dst;
-      size_t di = std::lower_bound(P.drops.begin(), P.drops.end(), s.begin) - P.drops.begin();
-      int64_t kept = 0;
-      for (int64_t c0 = s.begin; c0 < s.end; c0 += kChunk, ++ci) {
-        const int64_t c1 = std::min<int64_t>(c0 + kChunk, s.end);
-        int64_t nd = 0;
-        for (; di < P.drops.size() && P.drops[di] < c1; ++di) ++nd;
-        JpgChunk& k = chunks[ci];
-        k.src = sc + (c0 - P.scan_begin);
-        k.dst = dst + kept;
-        k.n = (int32_t)(c1 - c0);
-        k.keep = (int32_t)(c1 - c0 - nd);
-        k.lo = c0 > s.begin;
-        kept += k.keep;
-      }
-      dst += seg_bits_bytes(s.len);
-      g.slen = (int32_t)(s.end - s.begin);
-      g.len = (int32_t)s.len;
-      g.img = i;
-      g.mcu0 = (int32_t)(P.ri > 0 ? (int64_t)k * P.ri : 0);
-      g.nmcu = (int32_t)(P.ri > 0 ? std::min<int64_t>(P.ri, nmcu - g.mcu0) : nmcu);
-      g.nsub = (int32_t)std::max<int64_t>(1, vf_cdiv(s.len, sub_bytes));
-      g.sub0 = sub;
-      sub += g.nsub;
-    }
-    sc += (int64_t)vf_up256((size_t)nbytes + 8);
-  }
-}
 
 // ===================================================================== progressive (SOF2) files: DESIGN.md 5.9
 // The entropy rule of jdphuff.c as four per-block functions (decode_mcu_DC_first, decode_mcu_AC_first,
@@ -1181,7 +818,7 @@ struct ProgScan {
   int32_t boff[kProgMaxMcuBlocks];    // interleaved: each unit block's place in the frame's MCU ...
   int32_t bslot[kProgMaxMcuBlocks];   // ... and its component's place in the scan (DC predictor, table)
   int32_t tab[4];              // per scan component: its table in force at the SOS (DC for Ss = 0, else AC); -1: none
-  // a scan of a sequential file (layouts: Ss = 0, Se = 63): every block is its DC symbol and then its AC symbols
+  // a scan of a sequential file (Ss = 0, Se = 63): every block is its DC symbol and then its AC symbols
   int32_t seq;
   int32_t ntab;                // its distinct tables: tab[0 .. ntab) when <= 4, else the ntab tables from tab[0] on
   int32_t dct[kProgMaxMcuBlocks], act[kProgMaxMcuBlocks];   // per unit block: its DC and AC table among those
@@ -1372,15 +1009,17 @@ __host__ __device__ inline int prog_decode_segment(const JpgImage& im, const Pro
   return eobrun > 0 ? (int)ST_BAD : (int)ST_OK;
 }
 
-// ---- first scans (Ah = 0) by self-synchronisation: k_jpeg_huffman's scheme.  A lane's state is (p, j, k): the bit it is
-// at, the block of the unit it is in (interleaved DC scans) and the zig-zag index (AC scans; Ss at the start of a block).
+// ---- first scans (Ah = 0) by self-synchronisation (Weißenberger & Schmidt, ICPP 2018).  A lane's state is (p, j, k):
+// the bit it is at, the block of the unit it is in (interleaved DC scans, sequential scans) and the zig-zag index (AC and
+// sequential scans; Ss at the start of a block).
 // An EOB run consumes no bits beyond its symbol, so it is taken whole where the symbol is read: it advances the block
 // count by its length and never enters the state.
 // Decode from (p, j, k) while the next symbol starts before pend.  g: the ordinal, among the segment's `total` blocks,
 // of the block the lane is in (the exclusive scan of the counts; 0 when counting).  WRITE: store the coefficients (a DC
 // value as its difference) and stop once `total` blocks are done; else count: g comes back as the blocks advanced,
 // capped at total + 1.  Returns LANE_*.
-// SEQ: the scan is a sequential file's (layouts), else a progressive first scan; the block picks the instance per scan.
+// SEQ: the scan is a sequential file's (baseline, layouts), else a progressive first scan; the block picks the instance
+// per scan.
 template <bool WRITE, bool SEQ>
 __host__ __device__ int prog_first_lane(const JpgImage& im, const ProgScan& sc, const JpgHuff* tabs, BitWin& bw, uint32_t nbits, uint32_t& p,
                                         int& j, int& k, uint32_t pend, int64_t& g, int64_t total, int u0, int16_t* coef) {
@@ -1497,12 +1136,15 @@ __device__ __forceinline__ void prog_first_block(const JpgBatch& B, const ProgSe
     X[i] = r == LANE_END ? st_pack(p, j, k) : kDead;
     Nb[i] = (int32_t)g;
   };
+  // speculative start of every subsequence at its first bit, at the start of a unit
   for (int i = t; i < nsub; i += kHuffThreads) {
     const uint64_t e = st_pack((uint32_t)i * sb, 0, sc.ss);
     E[i] = e;
     run(i, e);
   }
-  // synchronise, as k_jpeg_huffman does
+  // synchronise: a lane whose entry state differs from its predecessor's exit state decodes again from it.  A dead exit
+  // (the predecessor stopped on an invalid code) is no information: the lane keeps its state, otherwise the dead state
+  // would travel one lane per round to the end of the segment with the corrections behind it
   int nround = 0;
   for (;;) {
     if (t == 0) *changed = 0;
@@ -1538,6 +1180,8 @@ __device__ __forceinline__ void prog_first_block(const JpgBatch& B, const ProgSe
     }
   }
   __syncthreads();
+  // write pass from the synchronised states.  Behind a dead exit the chain is broken: that predecessor meets the invalid
+  // code in its own write pass, and this lane writes nothing (an error only if it still owes blocks)
   int err = ST_OK;
   for (int i = t; i < nsub; i += kHuffThreads) {
     const uint64_t e = E[i];
@@ -1675,11 +1319,11 @@ __global__ void k_jpeg_prog_scan(const JpgBatch B, const ProgScan* scans, const 
 struct ProgScanHost {
   int ns = 0, scomp[4] = {}, ss = 0, se = 0, ah = 0, al = 0, ri = 0, level = 0;
   int tab[4] = {-1, -1, -1, -1};   // per scan component: its table among ProgParsed::tabs
-  bool seq = false;                // a scan of a sequential file (layouts): tab[0] is the first of its ntab tables,
+  bool seq = false;                // a scan of a sequential file: tab[0] is the first of its ntab tables,
   int ntab = 0, dtab[4] = {}, atab[4] = {};   // dtab / atab each component's DC / AC table among them
   int64_t begin = 0, end = 0, nunit = 0;
-  std::vector<JpgParsed::Seg> segs;
-  std::vector<int64_t> drops;
+  std::vector<JpgRestartSeg> segs;
+  std::vector<int64_t> drops;   // positions of the bytes unstuffing drops, ascending
 };
 
 struct ProgParsed {
@@ -1699,17 +1343,28 @@ struct ProgParsed {
   int64_t nblocks() const { return mcux() * mcuy() * bpm(); }
 };
 
-// 0: parsed (P.supported / P.why as jpg_parse); else malformed (msg).  Walks every scan.  layouts: sequential files
-// too (SOF0 / SOF1, any number of scans), and jpg_parse's wider samplings and RGB.
-int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg, bool layouts = false) {
+// 0: parsed (P.supported / P.why as jpg_parse); else malformed (msg).  Walks every scan the rule takes: the one scan of a
+// BASELINE file (a second SOS behind it is a reason, its data is not walked), the scans of a PROGRESSIVE file, and under
+// LAYOUTS those of sequential files too (SOF0 / SOF1, any number of scans), with jpg_parse's wider samplings and RGB.
+// walk false (BASELINE, whose headers say whether the file is taken): the headers only, no scan is recorded.
+int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg, JpgKind kind, bool walk = true) {
   JpgParsed& P = G.P;
-  P.take_sof2 = true;
-  P.layouts = layouts;
-  if (int e = jpg_parse(d, n, P, msg, false)) return e;
+  if (int e = jpg_parse(d, n, P, msg, kind)) return e;
+  if (!walk) return 0;
   P.supported = false;
-  if (P.sof != 0xC2 && !layouts && P.why.empty()) P.why = "not progressive";
-  if (!P.why.empty()) return 0;
+  if (kind == PROGRESSIVE && P.sof != 0xC2 && P.why.empty()) P.why = "not progressive";
+  if (!P.why.empty()) {
+    if (kind == BASELINE) {   // vf_jpeg_inspect reports the extent of the first scan of a file it refuses, too
+      ProgScanHost sc;
+      sc.begin = P.scan_begin;
+      int end_marker;
+      if (int e = jpg_walk(d, n, sc.begin, sc.segs, sc.drops, sc.end, end_marker, msg)) return e;
+      G.scans.push_back(std::move(sc));
+    }
+    return 0;
+  }
   const bool seq = P.sof != 0xC2;
+  G.tabs.reserve(6);           // what one scan of three components names at most
   int cov[3][64];              // the Al each coefficient was last coded at; -1: not yet
   for (auto& c : cov)
     for (int& k : c) k = -1;
@@ -1721,7 +1376,7 @@ int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg,
       P.why = "more than " + std::to_string(kProgMaxScans) + " scans";
       return 0;
     }
-    const std::string at = "scan " + std::to_string(G.scans.size()) + ": ";
+    const std::string at = kind == BASELINE ? "" : "scan " + std::to_string(G.scans.size()) + ": ";   // a baseline file has the one
     ProgScanHost sc;
     sc.ns = P.ns;
     sc.ss = P.ss;
@@ -1745,7 +1400,8 @@ int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg,
     for (int i = 0; i < sc.ns && seq; ++i) {
       // the scan's tables as they stand at this SOS, side by side: DC and AC of each component, equal slots shared
       sc.scomp[i] = P.scomp[i];
-      const int top = P.sof == 0xC0 ? 1 : 3;   // baseline has two slots of each class, extended sequential four
+      // baseline has two slots of each class; extended sequential four, which only the layouts rule takes
+      const int top = kind == LAYOUTS && P.sof != 0xC0 ? 3 : 1;
       for (int ac = 0; ac < 2; ++ac) {
         const int slot = ac ? P.ta[i] : P.td[i];
         const RawHuff* h = slot <= top ? (ac ? &P.hac[slot] : &P.hdc[slot]) : nullptr;
@@ -1834,11 +1490,12 @@ int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg,
     }
     G.nlevel = std::max(G.nlevel, sc.level + 1);
     int end_marker = -1;
+    const int64_t want = sc.ri > 0 ? vf_cdiv(sc.nunit, sc.ri) : 1;
+    sc.segs.reserve((size_t)std::min(want, n));
     if (int e = jpg_walk(d, n, sc.begin, sc.segs, sc.drops, sc.end, end_marker, msg)) {
       msg = at + msg;
       return e;
     }
-    const int64_t want = sc.ri > 0 ? vf_cdiv(sc.nunit, sc.ri) : 1;
     if ((int64_t)sc.segs.size() != want) {
       msg = at + "found " + std::to_string(sc.segs.size()) + " restart segments, the restart interval gives " + std::to_string(want);
       return 2;
@@ -1856,6 +1513,15 @@ int jpg_prog_parse(const uint8_t* d, int64_t n, ProgParsed& G, std::string& msg,
       if (p >= n) break;
       const int m = d[p++];
       if (m == 0xD9) break;
+      if (kind == BASELINE) {   // a second SOS makes the file multi-scan; any other marker is skipped unread
+        if (m == 0xDA) {
+          P.why = "multi-scan sequential";
+          return 0;
+        }
+        if (p + 2 > n) break;
+        p += rd16(d + p);
+        continue;
+      }
       if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
       if (p + 2 > n) break;
       const int L = rd16(d + p);
@@ -1904,9 +1570,12 @@ struct ProgPlan {
   size_t o_bits = 0, o_E = 0, o_X = 0, o_N = 0, o_D = 0, o_coef = 0, o_planes = 0, ws = 0;
 };
 
-// sub_bytes: the subsequence size of the first scans' decode (0: none of them is decoded that way)
-int jpg_prog_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes, ProgPlan& L, bool layouts = false) {
-  const char* who = layouts ? "vf_jpeg_layouts" : "vf_jpeg_prog";
+// sub_bytes: the subsequence size of the first scans' decode (0: none of them is decoded that way).  bounds (the BASELINE
+// rule's workspace query): upper bounds from the headers alone, so that a decode walks each file once.  A baseline file
+// is one scan of at most four tables and as many segments as its restart interval gives; a segment's compacted length
+// is at most its stuffed length, and the segments share the bytes from the scan's start to the end of the file.
+int jpg_prog_plan(const JpgRule& rule, const uint8_t* data, const int64_t* offs, int n, int sub_bytes, ProgPlan& L, bool bounds = false) {
+  const char* who = rule.who;
   VF_REQUIRE(n > 0 && data && offs, "%s: empty batch", who);
   VF_REQUIRE(sub_bytes == 0 || (sub_bytes >= 8 && sub_bytes <= (1 << 20)), "%s: subsequence size %d outside [8, 1 MiB]", who, sub_bytes);
   L.G.resize(n);
@@ -1914,7 +1583,7 @@ int jpg_prog_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes
     std::string msg;
     VF_REQUIRE(offs[i + 1] >= offs[i], "%s: offsets decrease at image %d", who, i);
     ProgParsed& G = L.G[i];
-    if (jpg_prog_parse(data + offs[i], offs[i + 1] - offs[i], G, msg, layouts)) {
+    if (jpg_prog_parse(data + offs[i], offs[i + 1] - offs[i], G, msg, rule.kind, !bounds)) {
       vf_set_error("%s: image %d: %s", who, i, msg.c_str());
       return 2;
     }
@@ -1926,6 +1595,17 @@ int jpg_prog_plan(const uint8_t* data, const int64_t* offs, int n, int sub_bytes
     L.max_blocks = std::max(L.max_blocks, G.nblocks());
     L.max_pix = std::max(L.max_pix, (int64_t)G.P.W * G.P.H);
     L.plane_bytes = (int64_t)vf_up256((size_t)(L.plane_bytes + G.nblocks() * 64));
+    if (bounds) {
+      const int64_t nseg = G.P.ri > 0 ? vf_cdiv(G.mcux() * G.mcuy(), G.P.ri) : 1, sb = offs[i + 1] - offs[i] - G.P.scan_begin;
+      L.nscan += 1;
+      L.ntab += 4;
+      L.nseg += nseg;
+      L.nsub += vf_cdiv(sb, sub_bytes) + nseg;
+      L.bits_bytes += sb + 32 * nseg;
+      L.nchunk += vf_cdiv(sb, kChunk) + nseg;
+      L.scan_bytes += (int64_t)vf_up256((size_t)sb + 8);
+      continue;
+    }
     L.nscan += (int64_t)G.scans.size();
     L.ntab += (int64_t)G.tabs.size();
     if ((int)L.level_segs.size() < G.nlevel) L.level_segs.resize(G.nlevel, 0);
@@ -2117,7 +1797,7 @@ VF_API int vf_jpeg_scans_inspect(const unsigned char* data, size_t len, int64_t*
   VF_REQUIRE(data && info, "vf_jpeg_scans_inspect: NULL argument");
   ProgParsed G;
   std::string msg;
-  if (int rc = jpg_prog_parse(data, (int64_t)len, G, msg)) {
+  if (int rc = jpg_prog_parse(data, (int64_t)len, G, msg, PROGRESSIVE)) {
     vf_set_error("vf_jpeg_scans_inspect: %s", msg.c_str());
     return rc;
   }
@@ -2156,23 +1836,39 @@ VF_API int vf_jpeg_scans_inspect(const unsigned char* data, size_t len, int64_t*
   return 0;
 }
 
-VF_API int vf_jpeg_prog_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
-                                        size_t* stage_bytes) {
-  VF_REQUIRE(subseq_bytes != 0, "vf_jpeg_prog: subsequence size 0 outside [8, 1 MiB]");
+// the sizes of one batch under a rule: exact (every file is walked), or with bounds the header-only upper bounds
+static int jpg_workspace_bytes(const JpgRule& rule, bool bounds, const unsigned char* data, const int64_t* offs, int n, int subseq_bytes,
+                               size_t* ws_bytes, size_t* stage_bytes) {
+  VF_REQUIRE(subseq_bytes != 0, "%s: subsequence size 0 outside [8, 1 MiB]", rule.who);
   ProgPlan L;
-  if (int e = jpg_prog_plan(data, offs, n, subseq_bytes, L)) return e;
+  if (int e = jpg_prog_plan(rule, data, offs, n, subseq_bytes, L, bounds)) return e;
   if (ws_bytes) *ws_bytes = L.ws;
   if (stage_bytes) *stage_bytes = L.stage;
   return 0;
 }
 
-// the assembled coefficients of one file on the host: the progressive entry's, and with layouts the layouts entry's
-static int jpg_coefficients_host(const char* who, bool layouts, const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef,
+VF_API int vf_jpeg_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
+                                   size_t* stage_bytes) {
+  return jpg_workspace_bytes(kBaselineRule, true, data, offs, n, subseq_bytes, ws_bytes, stage_bytes);
+}
+
+VF_API int vf_jpeg_prog_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
+                                        size_t* stage_bytes) {
+  return jpg_workspace_bytes(kProgressiveRule, false, data, offs, n, subseq_bytes, ws_bytes, stage_bytes);
+}
+
+VF_API int vf_jpeg_layouts_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
+                                           size_t* stage_bytes) {
+  return jpg_workspace_bytes(kLayoutsRule, false, data, offs, n, subseq_bytes, ws_bytes, stage_bytes);
+}
+
+// the assembled coefficients of one file on the host, under the progressive or the layouts rule
+static int jpg_coefficients_host(const char* who, const JpgRule& rule, const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef,
                                  size_t coef_blocks, int32_t* status) {
   VF_REQUIRE(data && coef && status, "%s: NULL argument", who);
   const int64_t offs[2] = {0, (int64_t)len}, out_offs[2] = {0, 0};
   ProgPlan L;
-  if (int e = jpg_prog_plan(data, offs, 1, subseq_bytes, L, layouts)) return e;
+  if (int e = jpg_prog_plan(rule, data, offs, 1, subseq_bytes, L)) return e;
   VF_REQUIRE((int64_t)coef_blocks >= L.nblk, "%s: room for %zu blocks, the file has %lld", who, coef_blocks, (long long)L.nblk);
   std::vector<uint64_t> stage(L.stage / 8 + 1), bits((size_t)L.bits_bytes / 8 + 1, 0);
   uint8_t* st = (uint8_t*)stage.data();
@@ -2198,23 +1894,24 @@ static int jpg_coefficients_host(const char* who, bool layouts, const unsigned c
 
 VF_API int vf_jpeg_prog_coefficients_host(const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef, size_t coef_blocks,
                                           int32_t* status) {
-  return jpg_coefficients_host("vf_jpeg_prog_coefficients_host", false, data, len, subseq_bytes, coef, coef_blocks, status);
+  return jpg_coefficients_host("vf_jpeg_prog_coefficients_host", kProgressiveRule, data, len, subseq_bytes, coef, coef_blocks, status);
 }
 
 VF_API int vf_jpeg_layouts_coefficients_host(const unsigned char* data, size_t len, int subseq_bytes, int16_t* coef, size_t coef_blocks,
                                              int32_t* status) {
-  return jpg_coefficients_host("vf_jpeg_layouts_coefficients_host", true, data, len, subseq_bytes, coef, coef_blocks, status);
+  return jpg_coefficients_host("vf_jpeg_layouts_coefficients_host", kLayoutsRule, data, len, subseq_bytes, coef, coef_blocks, status);
 }
 
-// the progressive entry's decode, and with layouts the layouts entry's: sequential scans join the first scans' launch
-static int jpg_scans_decode(const char* who, bool layouts, vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels,
+// every entry's decode.  All first scans share level 0's launch: the one scan of a baseline file, the scans of a
+// sequential file (layouts) and the first scans of a progressive one
+static int jpg_scans_decode(const char* who, const JpgRule& rule, vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels,
                             int subseq_bytes, const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws,
                             size_t ws_bytes, int32_t* status, int32_t* rounds, int32_t* levels) {
   VF_REQUIRE(channels == 1 || channels == 3, "%s: channels %d is not 1 or 3", who, channels);
   VF_REQUIRE(out && out_offs && stage && ws && status && rounds, "%s: NULL argument", who);
-  VF_REQUIRE(subseq_bytes != 0, "%s: subsequence size 0 outside [8, 1 MiB]", layouts ? "vf_jpeg_layouts" : "vf_jpeg_prog");
+  VF_REQUIRE(subseq_bytes != 0, "%s: subsequence size 0 outside [8, 1 MiB]", rule.who);
   ProgPlan L;
-  if (int e = jpg_prog_plan(data, offs, n, subseq_bytes, L, layouts)) return e;
+  if (int e = jpg_prog_plan(rule, data, offs, n, subseq_bytes, L)) return e;
   VF_REQUIRE(stage_bytes >= L.stage && ws_bytes >= L.ws, "%s: staging %zu / workspace %zu bytes, need %zu / %zu", who, stage_bytes, ws_bytes,
              L.stage, L.ws);
   for (int i = 0; i < n; ++i)
@@ -2237,12 +1934,11 @@ static int jpg_scans_decode(const char* who, bool layouts, vf_ctx* ctx, const un
   B.out = out;
   B.status = status;
   B.rounds = rounds;
-  B.nseg = (int)L.nseg;
   B.nchunk = (int)L.nchunk;
   B.sub_bits = 8 * subseq_bytes;
   hipStream_t st = ctx->stream;
   {
-    VfRange r("jpeg_prog_upload");
+    VfRange r(rule.upload);
     VF_CHECK_HIP(hipMemcpyAsync(w, stage, L.stage, hipMemcpyHostToDevice, st));
     VF_CHECK_HIP(hipMemsetAsync(w + L.o_coef, 0, (size_t)(128 * L.nblk), st));
     VF_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t) * n, st));
@@ -2259,7 +1955,7 @@ static int jpg_scans_decode(const char* who, bool layouts, vf_ctx* ctx, const un
   for (size_t l = 0; l < L.level_segs.size(); ++l) {
     const int64_t cnt = L.level_segs[l];
     if (cnt > 0 && l == 0) {
-      VF_LAUNCH_TIMED(ctx, "jpeg_prog_first", 0.0, 3.0 * sb / (double)L.level_segs.size(), k_jpeg_prog_first, dim3((unsigned)cnt), dim3(kHuffThreads),
+      VF_LAUNCH_TIMED(ctx, rule.entropy, 0.0, 3.0 * sb / (double)L.level_segs.size(), k_jpeg_prog_first, dim3((unsigned)cnt), dim3(kHuffThreads),
                       B, d_scans, d_segs);
       VF_LAUNCH_CHECK();
     } else if (cnt > 0) {
@@ -2276,7 +1972,7 @@ static int jpg_scans_decode(const char* who, bool layouts, vf_ctx* ctx, const un
   VF_LAUNCH_TIMED(ctx, "jpeg_idct", 0.0, 192.0 * L.nblk, k_jpeg_idct, dim3(gb, n), dim3(256), B);
   VF_LAUNCH_CHECK();
   const unsigned gp = (unsigned)std::min<int64_t>(vf_cdiv(L.max_pix, 256), 4096);
-  if (layouts) VF_LAUNCH_TIMED(ctx, "jpeg_color", 0.0, 2.0 * L.plane_bytes, k_jpeg_color_layouts, dim3(gp, n), dim3(256), B);
+  if (rule.kind == LAYOUTS) VF_LAUNCH_TIMED(ctx, "jpeg_color", 0.0, 2.0 * L.plane_bytes, k_jpeg_color_layouts, dim3(gp, n), dim3(256), B);
   else VF_LAUNCH_TIMED(ctx, "jpeg_color", 0.0, 2.0 * L.plane_bytes, k_jpeg_color, dim3(gp, n), dim3(256), B);
   VF_LAUNCH_CHECK();
   if (levels) *levels = (int32_t)L.level_segs.size();
@@ -2286,25 +1982,15 @@ static int jpg_scans_decode(const char* who, bool layouts, vf_ctx* ctx, const un
 VF_API int vf_jpeg_prog_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes,
                                const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
                                int32_t* status, int32_t* rounds, int32_t* levels) {
-  return jpg_scans_decode("vf_jpeg_prog_decode", false, ctx, data, offs, n, channels, subseq_bytes, out_offs, out, stage, stage_bytes, ws,
+  return jpg_scans_decode("vf_jpeg_prog_decode", kProgressiveRule, ctx, data, offs, n, channels, subseq_bytes, out_offs, out, stage, stage_bytes, ws,
                           ws_bytes, status, rounds, levels);
 }
 
 VF_API int vf_jpeg_decode_layouts(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes,
                                   const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
                                   int32_t* status, int32_t* rounds, int32_t* levels) {
-  return jpg_scans_decode("vf_jpeg_decode_layouts", true, ctx, data, offs, n, channels, subseq_bytes, out_offs, out, stage, stage_bytes, ws,
+  return jpg_scans_decode("vf_jpeg_decode_layouts", kLayoutsRule, ctx, data, offs, n, channels, subseq_bytes, out_offs, out, stage, stage_bytes, ws,
                           ws_bytes, status, rounds, levels);
-}
-
-VF_API int vf_jpeg_layouts_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
-                                           size_t* stage_bytes) {
-  VF_REQUIRE(subseq_bytes != 0, "vf_jpeg_layouts: subsequence size 0 outside [8, 1 MiB]");
-  ProgPlan L;
-  if (int e = jpg_prog_plan(data, offs, n, subseq_bytes, L, true)) return e;
-  if (ws_bytes) *ws_bytes = L.ws;
-  if (stage_bytes) *stage_bytes = L.stage;
-  return 0;
 }
 
 // info (int64[20]) = {width, height, components, h0, v0, h1, v1, h2, v2, colour (0 grey, 1 YCbCr, 2 RGB), scans, supported,
@@ -2313,7 +1999,7 @@ VF_API int vf_jpeg_inspect_layouts(const unsigned char* data, size_t len, int64_
   VF_REQUIRE(data && info, "vf_jpeg_inspect_layouts: NULL argument");
   ProgParsed G;
   std::string msg;
-  if (int rc = jpg_prog_parse(data, (int64_t)len, G, msg, true)) {
+  if (int rc = jpg_prog_parse(data, (int64_t)len, G, msg, LAYOUTS)) {
     vf_set_error("vf_jpeg_inspect_layouts: %s", msg.c_str());
     return rc;
   }
@@ -2341,13 +2027,14 @@ VF_API int vf_jpeg_inspect_layouts(const unsigned char* data, size_t len, int64_
 
 VF_API int vf_jpeg_inspect(const unsigned char* data, size_t len, int scan_walk, int64_t* info, char* reason, int reason_cap) {
   VF_REQUIRE(data && info, "vf_jpeg_inspect: NULL argument");
-  JpgParsed P;
+  ProgParsed G;
   std::string msg;
-  const int rc = jpg_parse(data, (int64_t)len, P, msg, scan_walk != 0);
-  if (rc) {
+  if (int rc = jpg_prog_parse(data, (int64_t)len, G, msg, BASELINE, scan_walk != 0)) {
     vf_set_error("vf_jpeg_inspect: %s", msg.c_str());
     return rc;
   }
+  const JpgParsed& P = G.P;
+  const ProgScanHost* sc = G.scans.empty() ? nullptr : &G.scans[0];   // the first scan, when it was walked
   info[0] = P.W;
   info[1] = P.H;
   info[2] = P.ncomp;
@@ -2355,74 +2042,19 @@ VF_API int vf_jpeg_inspect(const unsigned char* data, size_t len, int scan_walk,
   info[4] = P.ncomp == 1 ? 1 : P.vf[0];
   info[5] = P.ri;
   info[6] = P.scan_begin;
-  info[7] = P.scan_end;
+  info[7] = sc ? sc->end : -1;
   info[8] = P.supported ? 1 : 0;
   info[9] = P.sof;
-  info[10] = scan_walk ? (int64_t)P.segs.size() : -1;
+  info[10] = sc ? (int64_t)sc->segs.size() : -1;
   info[11] = P.prec;
   if (reason && reason_cap > 0) snprintf(reason, (size_t)reason_cap, "%s", P.why.c_str());
-  return 0;
-}
-
-VF_API int vf_jpeg_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int subseq_bytes, size_t* ws_bytes,
-                                   size_t* stage_bytes) {
-  JpgPlan L;
-  if (int e = jpg_plan(data, offs, n, subseq_bytes, L, false)) return e;
-  if (ws_bytes) *ws_bytes = L.ws;
-  if (stage_bytes) *stage_bytes = L.stage;
   return 0;
 }
 
 VF_API int vf_jpeg_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int subseq_bytes,
                           const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
                           int32_t* status, int32_t* rounds) {
-  VF_REQUIRE(channels == 1 || channels == 3, "vf_jpeg_decode: channels %d is not 1 or 3", channels);
-  VF_REQUIRE(out && out_offs && stage && ws && status && rounds, "vf_jpeg_decode: NULL argument");
-  JpgPlan L;
-  if (int e = jpg_plan(data, offs, n, subseq_bytes, L, true)) return e;
-  VF_REQUIRE(stage_bytes >= L.stage && ws_bytes >= L.ws, "vf_jpeg_decode: staging %zu / workspace %zu bytes, need %zu / %zu",
-             stage_bytes, ws_bytes, L.stage, L.ws);
-  for (int i = 0; i < n; ++i)
-    VF_REQUIRE(!(L.P[i].ncomp == 3 && channels == 1), "vf_jpeg_decode: image %d is YCbCr; channels=1 takes grayscale files only", i);
-  jpg_pack(data, offs, n, channels, subseq_bytes, out_offs, L, (uint8_t*)stage);
-  uint8_t* w = (uint8_t*)ws;
-  JpgBatch B;
-  B.img = (const JpgImage*)(w + L.o_img);
-  B.seg = (const JpgSeg*)(w + L.o_seg);
-  B.chunk = (const JpgChunk*)(w + L.o_chunk);
-  B.huff = (const JpgHuff*)(w + L.o_huff);
-  B.scan = w + L.o_scan;
-  B.bits = w + L.o_bits;
-  B.E = (uint64_t*)(w + L.o_E);
-  B.X = (uint64_t*)(w + L.o_X);
-  B.Nb = (int32_t*)(w + L.o_N);
-  B.D = w + L.o_D;
-  B.coef = (int16_t*)(w + L.o_coef);
-  B.planes = w + L.o_planes;
-  B.out = out;
-  B.status = status;
-  B.rounds = rounds;
-  B.nseg = (int)L.nseg;
-  B.nchunk = (int)L.nchunk;
-  B.sub_bits = 8 * subseq_bytes;
-  hipStream_t st = ctx->stream;
-  {
-    VfRange r("jpeg_upload");
-    VF_CHECK_HIP(hipMemcpyAsync(w, stage, L.stage, hipMemcpyHostToDevice, st));
-    VF_CHECK_HIP(hipMemsetAsync(w + L.o_coef, 0, (size_t)(128 * L.nblk), st));
-    VF_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t) * n, st));
-    VF_CHECK_HIP(hipMemsetAsync(rounds, 0, sizeof(int32_t), st));
-  }
-  const int64_t sb = L.scan_bytes;
-  VF_LAUNCH_TIMED(ctx, "jpeg_unstuff", 0.0, 2.0 * sb, k_jpeg_unstuff, dim3((unsigned)std::max<int64_t>(1, vf_cdiv(L.nchunk, 4))), dim3(256), B);
-  VF_LAUNCH_CHECK();
-  VF_LAUNCH_TIMED(ctx, "jpeg_huffman", 0.0, 3.0 * sb + 128.0 * L.nblk, k_jpeg_huffman, dim3((unsigned)L.nseg), dim3(kHuffThreads), B);
-  VF_LAUNCH_CHECK();
-  const unsigned gb = (unsigned)std::min<int64_t>(vf_cdiv(L.max_blocks, 256), 4096);
-  VF_LAUNCH_TIMED(ctx, "jpeg_idct", 0.0, 192.0 * L.nblk, k_jpeg_idct, dim3(gb, n), dim3(256), B);
-  VF_LAUNCH_CHECK();
-  const unsigned gp = (unsigned)std::min<int64_t>(vf_cdiv(L.max_pix, 256), 4096);
-  VF_LAUNCH_TIMED(ctx, "jpeg_color", 0.0, 2.0 * L.plane_bytes, k_jpeg_color, dim3(gp, n), dim3(256), B);
-  VF_LAUNCH_CHECK();
-  return 0;
+  return jpg_scans_decode("vf_jpeg_decode", kBaselineRule, ctx, data, offs, n, channels, subseq_bytes, out_offs, out, stage, stage_bytes, ws,
+                          ws_bytes, status, rounds, nullptr);
 }
+

@@ -177,7 +177,7 @@ def decode_jpeg(items, channels=3, stack=False, fallback=None, subseq_bytes=256,
     (64 files of 537 x 936 / 256 of 360 x 480 against Pillow on 16 threads): 4:4:0 files 5.1 ms against 25 ms
     / 7.7 ms against 71 ms, RGB 4:4:4 files 16 ms against 35 ms / 23 ms against 62 ms, both bound by the host call, which
     walks every file twice; ordinary 4:2:0 files 2.9 / 3.1 ms, where the default entry takes 3.0 / 2.9 ms.  The default
-    leaves every result, error and launch as it was."""
+    leaves every result and error as it was."""
     assert channels in (1, 3), "channels is 1 or 3"
     B = get_backend()
     refuse = lambda info, ch: "YCbCr file with channels=1" if ch == 1 and info["components"] != 1 else None
