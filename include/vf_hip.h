@@ -683,6 +683,63 @@ int vf_gif_workspace_bytes(int clips, int frames, int H, int W, size_t* ws_bytes
 int vf_gif_encode(vf_ctx* ctx, const void* src, int kind, int clips, int frames, int H, int W, int delay_cs, void* ws,
                   size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
 
+/* ---- animated PNG encode (vf_png.hip) -----------------------------------------------------------------
+ * A clip as ONE lossless file every browser plays: g clips of n frames of one H x W x C in, g whole APNG files out, back to
+ * back.  tests/apng_ref.py is the definition: the file is assembled from the n PNG files vf_png_encode writes for the
+ * clip's frames — signature, frame 0's IHDR, acTL (num_frames n, num_plays loop; 0 plays forever); per frame an fcTL
+ * (the whole canvas at (0,0), delay / 100 s, dispose NONE, blend SOURCE) and the frame's own zlib stream, frame 0's as
+ * its IDAT chunks unchanged, every later frame's as one fdAT (sequence number + the IDAT's payload) per IDAT; IEND.
+ * Sequence numbers run 0, 1, 2, ... over fcTL and fdAT together.  No frame differencing, no sub-rectangles.  A file's
+ * bytes depend on its own frames, delay and loop only, and are the same on every run; the file is also a valid PNG of
+ * frame 0.  C, sides and kind as vf_png_encode; n and g 1 to 65535 each, n * (chunks of a frame + 1) below 2^31 (a chunk
+ * is 8192 filtered bytes), delay (centiseconds) and loop 0 to 65535; anything else is an error naming the argument,
+ * before anything is launched.  kind 0: float (g*n) x C x H x W; kind 1: uint8 (g*n) x H x W x C.
+ * vf_apng_workspace_bytes (host only, no GPU): the DEVICE workspace and an upper bound on the output for the batch,
+ * g * (n * (H * (W * C + 1) + 21 * chunks + 6 + 38) + 65). */
+int vf_apng_workspace_bytes(int g, int n, int H, int W, int C, int delay, int loop, size_t* ws_bytes, size_t* out_bytes);
+/* Encode on the context's stream.  ws (>= ws_bytes) and out (out_cap >= the bound above) are caller-owned DEVICE memory;
+ * offsets (DEVICE int64[g + 1]) receives the files' places: file i is out[offsets[i] .. offsets[i + 1]).  Nothing is
+ * allocated and nothing synchronises. */
+int vf_apng_encode(vf_ctx* ctx, const void* src, int kind, int g, int n, int H, int W, int C, int delay, int loop, void* ws,
+                   size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
+
+/* ---- animated PNG decode (vf_png_decode.hip, vf_apng_parse.h) -----------------------------------------
+ * APNG files (the ones vf_apng_encode writes among them) and plain PNG files to the composited canvas of every frame, on
+ * the device and all-integer; tests/apng_decode_ref.py is the definition.  Frames: acTL.num_frames of them, one per fcTL;
+ * frame k's pixels are the zlib stream of its data chunks (the IDATs when its fcTL precedes them, else its fdATs without
+ * their sequence numbers) decoded under the full PNG rule (vf_png_decode_full) as an image of the fcTL's width x height
+ * with the IHDR's depth, colour type and interlace and the file's PLTE / tRNS.  A default image without an fcTL in front
+ * is not a frame; a PNG without acTL is a clip of one frame.  Canvas: the IHDR's size, transparent black; blend SOURCE
+ * replaces the rectangle, alpha included; dispose 0 leaves the canvas, 1 clears the rectangle to transparent black, 2
+ * restores what was there before the frame (on the first frame: clears).  Output frame k is the canvas after frame k was
+ * rendered: grey replicated, alpha 255 where the file has none, a pixel nothing painted (0,0,0,0); a 16-bit sample gives
+ * its high byte.  Not taken (supported = 0 with the reason): blend OVER in a file that carries alpha (colour type 4 or 6,
+ * or tRNS; without alpha OVER is SOURCE), tRNS on colour types 0 and 2, a side above 16384, more than 65535 frames,
+ * 2 GiB or more of RGBA frames, a frame the full rule refuses.  Malformed (an error): a wrong CRC on IHDR, PLTE, tRNS,
+ * IDAT, IEND, acTL, fcTL or fdAT; a second acTL or one after IDAT; num_frames 0 or not the number of fcTL chunks; a
+ * sequence number missing, repeated or out of order; an fdAT before the first fcTL, shorter than 4 bytes or in the frame
+ * the IDATs hold; a frame without data or with a bad zlib header; a zero-size frame or one that leaves the canvas; an
+ * fcTL in front of IDAT that is not the whole canvas at (0,0), or two of them; dispose above 2, blend above 1;
+ * truncation; and what vf_png_inspect calls malformed.
+ * vf_apng_inspect (host only, no GPU): walk one whole file.  info (int64[12]) = {width, height, bit depth, colour type,
+ * interlace, channels of the decoded frames (1, 2, 3, 4), frames, num_plays or -1 without acTL, supported, animated (an
+ * acTL), the IDAT image is frame 0, palette entries}.  frames (int64[frame_cap][9], may be NULL with frame_cap 0)
+ * receives per frame {x, y, w, h, delay_num, delay_den, dispose, blend, data_bytes} for the first frame_cap frames.
+ * reason: why not supported.  Returns non-zero for a malformed file. */
+int vf_apng_inspect(const unsigned char* data, size_t len, int64_t* info, int64_t* frames, int frame_cap, char* reason,
+                    int reason_cap);
+/* The calling convention of vf_gif_decode: n files back to back (file i is data[offs[i] .. offs[i + 1])), alpha 0: RGB,
+ * 1: RGBA.  ws_bytes: the DEVICE workspace; stage_bytes: the HOST staging buffer.  An error naming the image for a
+ * malformed (2) or unsupported (3) file.  All frames of a batch are images of one launch: 65535 frames at most. */
+int vf_apng_decode_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int alpha, size_t* ws_bytes,
+                                   size_t* stage_bytes);
+/* Decode on the context's stream: file i's frames x H x W x (3 or 4) canvases go to out[out_offs[i] ...]; status (DEVICE
+ * int32[n]) receives VF_PNG_* per file: the first of its frames' that is not 0, and then nothing of the file is written.
+ * ONE upload, then four launches whatever n and the frame counts (inflate, unfilter, expand as in vf_png_decode_full with
+ * a frame per image, k_apng_compose: a thread per canvas pixel).  Nothing is allocated and nothing synchronises. */
+int vf_apng_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int alpha, const int64_t* out_offs,
+                   unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes, int32_t* status);
+
 /* ---- animated GIF decode (vf_gif_decode.hip) --------------------------------------------------------
  * GIF87a and GIF89a files (the ones vf_gif_encode writes among them) to the composited canvas of every frame, on the
  * device and all-integer; tests/gif_decode_ref.py is the definition.  Container: logical screen, optional global table,

@@ -113,6 +113,11 @@ SIGNATURES = {
     "vf_jpeg_encode_prog": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_gif_workspace_bytes": (i32, [i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_gif_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
+    "vf_apng_workspace_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
+    "vf_apng_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
+    "vf_apng_inspect": (i32, [vp, sz, vp, vp, i32, C.c_char_p, i32]),
+    "vf_apng_decode_workspace_bytes": (i32, [vp, vp, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
+    "vf_apng_decode": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, sz, vp, sz, vp]),
     "vf_gif_inspect": (i32, [vp, sz, vp, vp, i32, C.c_char_p, i32]),
     "vf_gif_decode_workspace_bytes": (i32, [vp, vp, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_gif_decode": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, sz, vp, sz, vp]),

@@ -496,7 +496,55 @@ def gif_workspace_bytes(clips, frames, H, W):
     return _encoder_bytes("vf_gif_workspace_bytes", clips, frames, H, W)
 
 
-GIF_DECODE_TOKENS = 1984     # tokens per batch of k_gifd_lzw (kTok of csrc/vf_gif_decode.hip): where a frame's codes change batch
+def apng_workspace_bytes(clips, frames, H, W, channels, delay=10, loop=0):
+    """(device workspace bytes, upper bound on the output bytes) of an APNG batch of `clips` clips of `frames` frames of
+    H x W x channels (vf_apng_workspace_bytes; host only, no GPU needed).  ValueError, naming the argument, for what the
+    encoder does not take: channels other than 1 or 3, a side outside 1..16384, a clip outside 1..65535 frames, a batch
+    outside 1..65535 clips, frames * (chunks + 1) of 2^31 or more, a delay or a loop count outside 0..65535."""
+    return _encoder_bytes("vf_apng_workspace_bytes", clips, frames, H, W, channels, delay, loop)
+
+
+APNG_FRAME_KEYS = ("x", "y", "w", "h", "delay_num", "delay_den", "dispose", "blend", "data_bytes")
+APNG_MAX_BATCH_FRAMES = 65535     # frames of one vf_apng_decode call: every frame is an image of its launches
+
+
+def apng_inspect(data):
+    """The host-only walk of one APNG or PNG file (vf_apng_inspect; no GPU needed) -> dict(width, height, bit_depth,
+    color_type, interlace, channels (of the decoded frames: 1, 2, 3, 4), frames, num_plays (-1 without acTL), supported,
+    animated, default_is_frame, palette_entries, reason, frame_info), frame_info a list with one dict of APNG_FRAME_KEYS
+    per frame.  Raises ValueError for a malformed file."""
+    lib = _lib.load()
+    data = bytes(data)
+    info = (C.c_int64 * 12)()
+    why = C.create_string_buffer(160)
+    if lib.vf_apng_inspect(data, len(data), info, None, 0, why, 160) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    keys = ("width", "height", "bit_depth", "color_type", "interlace", "channels", "frames", "num_plays", "supported", "animated",
+            "default_is_frame", "palette_entries")
+    d = {k: int(v) for k, v in zip(keys, info)}
+    rows = np.zeros((d["frames"], 9), np.int64)
+    if lib.vf_apng_inspect(data, len(data), info, rows.ctypes.data_as(C.c_void_p), d["frames"], why, 160) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    for k in ("supported", "animated", "default_is_frame"):
+        d[k] = bool(d[k])
+    d["reason"] = why.value.decode()
+    d["frame_info"] = [dict(zip(APNG_FRAME_KEYS, map(int, r))) for r in rows]
+    return d
+
+
+def apng_decode_workspace_bytes(files, alpha=False):
+    """(device workspace bytes, host staging bytes) of one APNG batch (vf_apng_decode_workspace_bytes; host only, no GPU
+    needed).  ValueError, naming the image, for a malformed or unsupported file, or for more than 65535 frames in all."""
+    lib = _lib.load()
+    data, offs = _joined(files)
+    ws_b, st_b = C.c_size_t(), C.c_size_t()
+    if lib.vf_apng_decode_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), len(files), int(bool(alpha)), C.byref(ws_b),
+                                          C.byref(st_b)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return ws_b.value, st_b.value
+
+
+GIF_DECODE_TOKENS = 1984    # tokens per batch of k_gifd_lzw (kTok of csrc/vf_gif_decode.hip): where a frame's codes change batch
 GIF_STATUS = {0: "ok", 1: "bad code", 2: "short data", 3: "bad colour index"}     # VF_GIF_* of include/vf_hip.h
 GIF_FRAME_KEYS = ("delay", "disposal", "x", "y", "w", "h", "interlace", "transparency", "table_size", "local_table", "min_code_size",
                   "data_bytes")
@@ -1300,6 +1348,29 @@ class HipBackend:
         if Cc != 3:
             raise ValueError("gif_encode: %d channels (a GIF frame here is RGB, 3)" % Cc)
         return self._encode("vf_gif_encode", "gif", clips, g, gif_workspace_bytes(g, n, H, W), kind, g, n, H, W, int(delay))
+
+    # ---- APNG encode (vf_png.hip)
+    def apng_encode(self, clips, delay, loop=0):
+        """Encode a batch of clips of one geometry as animated PNG files on the device, lossless.  clips: device uint8
+        G x N x H x W x C (taken as they are) or float32 G x N x C x H x W (through image.savePNG's truncating byte rule
+        inside the filter kernel), C = 1 or 3, contiguous; delay in centiseconds, loop the number of plays (0: forever).
+        -> (buffer, offsets): file i is buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8 tensor of the upper
+        bound's size, offsets a device int64[G + 1]; both are valid once the stream gets there."""
+        assert clips.dim() == 5 and clips.is_contiguous() and clips.device == self.device
+        (g, n), (kind, _, H, W, Cc) = clips.shape[:2], _frame_kind(clips.flatten(0, 1))
+        return self._encode("vf_apng_encode", "png", clips, g, apng_workspace_bytes(g, n, H, W, Cc, delay, loop), kind, g, n, H, W, Cc,
+                            int(delay), int(loop))
+
+    # ---- APNG decode (vf_png_decode.hip, DESIGN.md 5.11)
+    def apng_decode(self, files, alpha=False, infos=None):
+        """Decode a batch of supported APNG / PNG files (bytes each; 65535 frames in all at most) into one device uint8
+        buffer.  -> (out, offsets, status): file i is out[offsets[i]:offsets[i+1]] as frames x H x W x (4 if alpha else 3),
+        the composited canvas of every frame; status (device int32[n]) holds VF_PNG_* per file, valid once the stream
+        gets there.  infos: the files' apng_inspect results, if the caller has them."""
+        shapes = infos if infos is not None else [apng_inspect(f) for f in files]
+        oc = 4 if alpha else 3
+        return self._decode("pngd", "vf_apng_decode_workspace_bytes", "vf_apng_decode", files,
+                            [s["frames"] * s["height"] * s["width"] * oc for s in shapes], (int(bool(alpha)),), (int(bool(alpha)),))
 
     # ---- GIF decode (vf_gif_decode.hip, DESIGN.md 5.10)
     def gif_decode(self, files, alpha=False, infos=None):

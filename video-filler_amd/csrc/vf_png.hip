@@ -586,15 +586,15 @@ __global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
 // --------------------------------------------------------------------------------------------------------------- pack
 constexpr int PNG_HEAD = 8 + 25, PNG_TAIL = 12;   // signature + IHDR; IEND
 
-// one block per frame: where each IDAT goes, the frame's Adler-32, the file's size (offsets[f + 1], summed by k_vf_file_offsets)
-__global__ __launch_bounds__(256) void k_png_frame_scan(PngArgs a) {
+// One frame, by its block: where each of its chunks goes behind the first (chunk_off; `framing` bytes of length, type, CRC and,
+// in an APNG's fdAT, sequence number around each), the frame's Adler-32.  -> the bytes of all its chunks, in every thread.
+__device__ __forceinline__ unsigned png_scan_frame(const PngArgs& a, long long f, unsigned framing) {
   __shared__ unsigned s_w[4];
-  const long long f = blockIdx.x;
   const unsigned* meta = a.meta + f * a.nchunks * 4;
   unsigned run = 0;
   for (int base = 0; base < a.nchunks; base += 256) {
     const int k = base + threadIdx.x;
-    const unsigned v = k < a.nchunks ? 12u + meta[4 * k] + (k == a.nchunks - 1 ? 4u : 0u) : 0u;
+    const unsigned v = k < a.nchunks ? framing + meta[4 * k] + (k == a.nchunks - 1 ? 4u : 0u) : 0u;
     unsigned total;
     const unsigned e = vf_block_excl_scan<unsigned, 256>(v, s_w, total);
     if (k < a.nchunks) a.chunk_off[f * a.nchunks + k] = run + e;
@@ -624,8 +624,15 @@ __global__ __launch_bounds__(256) void k_png_frame_scan(PngArgs a) {
       s1 = (s1 + s_a[t]) % ADLER_MOD;
     }
     a.adler[f] = (unsigned)((s2 << 16) | s1);
-    a.offsets[f + 1] = (int64_t)PNG_HEAD + run + PNG_TAIL;
   }
+  return run;
+}
+
+// one block per frame: where each IDAT goes, the frame's Adler-32, the file's size (offsets[f + 1], summed by k_vf_file_offsets)
+__global__ __launch_bounds__(256) void k_png_frame_scan(PngArgs a) {
+  const long long f = blockIdx.x;
+  const unsigned run = png_scan_frame(a, f, 12u);
+  if (threadIdx.x == 0) a.offsets[f + 1] = (int64_t)PNG_HEAD + run + PNG_TAIL;
 }
 
 __device__ __forceinline__ void put_be32(unsigned char* p, unsigned v) {
@@ -668,6 +675,141 @@ __global__ __launch_bounds__(256) void k_png_pack(PngArgs a) {
   }
 }
 
+// --------------------------------------------------------------------------------------------------------------- APNG
+// An animated PNG of a clip: signature, frame 0's IHDR, acTL; per frame an fcTL and the frame's own zlib stream,
+// frame 0's as its IDATs, every later frame's as one fdAT (sequence number + the IDAT's payload) per IDAT; IEND.  The filter and
+// deflate kernels above run over all frames of all clips; what follows places and frames their chunks.
+constexpr int APNG_HEAD = PNG_HEAD + 20, APNG_FCTL = 38;   // signature + IHDR + acTL; an fcTL chunk
+constexpr int APNG_SLICE = 65535;                          // frames per launch of the kernels with a frame per blockIdx.y
+
+struct ApngArgs {
+  PngArgs p;                      // offsets: [clips + 1]; the other arrays hold clips * frames frames, clip after clip
+  unsigned* frame_len;            // [clips * frames]: bytes of the frame's chunks with their framing, behind its fcTL
+  unsigned long long* frame_off;  // [clips * frames]: the frame's fcTL in its clip's file
+  long long f0;                   // the first frame of this launch
+  int frames;                     // per clip
+  int delay, loop;
+};
+
+// one block per frame: k_png_frame_scan with 16 bytes around an fdAT's data, and the frame's size to frame_len
+__global__ __launch_bounds__(256) void k_apng_frame_scan(ApngArgs g) {
+  const long long f = g.f0 + blockIdx.x;
+  const unsigned run = png_scan_frame(g.p, f, f % g.frames == 0 ? 12u : 16u);
+  if (threadIdx.x == 0) g.frame_len[f] = run;
+}
+
+// one block per clip: where each frame's fcTL goes, the file's size (offsets[clip + 1], summed by k_vf_file_offsets)
+__global__ __launch_bounds__(256) void k_apng_clip_scan(ApngArgs g) {
+  __shared__ unsigned long long s_w[4];
+  const long long clip = blockIdx.x, fb = clip * g.frames;
+  unsigned long long run = APNG_HEAD;
+  for (int base = 0; base < g.frames; base += 256) {
+    const int j = base + threadIdx.x;
+    const unsigned long long v = j < g.frames ? (unsigned long long)APNG_FCTL + g.frame_len[fb + j] : 0ull;
+    unsigned long long total;
+    const unsigned long long e = vf_block_excl_scan<unsigned long long, 256>(v, s_w, total);
+    if (j < g.frames) g.frame_off[fb + j] = run + e;
+    run += total;
+  }
+  if (threadIdx.x == 0) g.p.offsets[clip + 1] = (int64_t)(run + PNG_TAIL);
+}
+
+// length, type and dlen bytes of data are in place at h: the CRC-32 behind them, serially (the small chunks: acTL, fcTL)
+__device__ __forceinline__ void apng_seal(unsigned char* h, int dlen) {
+  unsigned c = 0xFFFFFFFFu;
+  for (int i = 4; i < 8 + dlen; ++i) c = crc_byte(c, h[i]);
+  put_be32(h + 8 + dlen, ~c);
+}
+
+// one block per chunk.  Frame 0 of a clip: k_png_pack's copy behind signature, IHDR, acTL and fcTL.  A later frame: the IDAT's
+// data behind an fdAT's length, type and sequence number.  Its CRC comes from the IDAT's register r = S(F, 'IDAT' || data) the
+// deflate kernel left (S: the raw register function, F: the all-ones preset): S is linear in its start value, so
+//   S(F, 'fdAT' || seq || data) = r ^ (S(F, 'IDAT') ^ S(F, 'fdAT' || seq)) * x^(8 * dlen)   mod the CRC polynomial,
+// the power by square and multiply; the frame's Adler-32 then goes through that register as in k_png_pack.
+__global__ __launch_bounds__(256) void k_apng_pack(ApngArgs g) {
+  const PngArgs& a = g.p;
+  const int k = blockIdx.x;
+  const long long f = g.f0 + blockIdx.y, clip = f / g.frames;
+  const int j = (int)(f - clip * g.frames);
+  const bool last = k == a.nchunks - 1;
+  const unsigned* mt = a.meta + (f * a.nchunks + k) * 4;
+  const unsigned dlen = mt[0];
+  const unsigned char* slot = a.slots + (f * a.nchunks + k) * (long long)PNG_SLOT;
+  unsigned char* file = a.out + a.offsets[clip];
+  unsigned char* fctl = file + g.frame_off[f];
+  unsigned char* dst = fctl + APNG_FCTL + a.chunk_off[f * a.nchunks + k];
+  // sequence numbers: frame 0's fcTL has 0; frame j >= 1 takes nchunks + 1 from 1 + (j - 1) * (nchunks + 1) on
+  const unsigned seq_fctl = j ? 1u + (unsigned)(j - 1) * (unsigned)(a.nchunks + 1) : 0u;
+  const unsigned hd = j ? 12u : 8u;                    // bytes in front of the chunk's data
+  if (j == 0) {
+    const unsigned ncopy = 8 + dlen + (last ? 0u : 4u);
+    for (unsigned i = threadIdx.x; i < ncopy; i += 256) dst[i] = slot[i];
+  } else {
+    for (unsigned i = threadIdx.x; i < dlen; i += 256) dst[12 + i] = slot[8 + i];
+  }
+  if (threadIdx.x == 0 && (j || last)) {
+    unsigned c = mt[3];
+    if (j) {
+      const unsigned seq = seq_fctl + 1u + (unsigned)k;
+      put_be32(dst, dlen + 4u + (last ? 4u : 0u));
+      dst[4] = 'f'; dst[5] = 'd'; dst[6] = 'A'; dst[7] = 'T';
+      put_be32(dst + 8, seq);
+      unsigned r1 = 0xFFFFFFFFu, r2 = 0xFFFFFFFFu;
+      for (int i = 4; i < 8; ++i) r1 = crc_byte(r1, slot[i]);
+      for (int i = 4; i < 12; ++i) r2 = crc_byte(r2, dst[i]);
+      unsigned xp = 0x80000000u, sq = 0x00800000u;     // 1 and x^8
+      for (unsigned e = dlen; e; e >>= 1) {
+        if (e & 1) xp = crc_mulmod(xp, sq);
+        sq = crc_mulmod(sq, sq);
+      }
+      c ^= crc_mulmod(r1 ^ r2, xp);
+    }
+    unsigned char* t = dst + hd + dlen;
+    if (last) {
+      const unsigned ad = a.adler[f];
+      for (int i = 0; i < 4; ++i) c = crc_byte(c, (ad >> (24 - 8 * i)) & 255);
+      put_be32(t, ad);
+      t += 4;
+    }
+    put_be32(t, ~c);
+    if (last && j == g.frames - 1) {
+      const unsigned char iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xAE, 0x42, 0x60, 0x82};
+      for (int i = 0; i < 12; ++i) t[4 + i] = iend[i];
+    }
+  }
+  if (threadIdx.x == 64 && k == 0) {
+    if (j == 0) {
+      const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+      for (int i = 0; i < 8; ++i) file[i] = sig[i];
+      unsigned char* h = file + 8;
+      put_be32(h, 13);
+      h[4] = 'I'; h[5] = 'H'; h[6] = 'D'; h[7] = 'R';
+      put_be32(h + 8, (unsigned)a.W);
+      put_be32(h + 12, (unsigned)a.H);
+      h[16] = 8; h[17] = a.C == 3 ? 2 : 0; h[18] = 0; h[19] = 0; h[20] = 0;
+      apng_seal(h, 13);
+      h = file + PNG_HEAD;
+      put_be32(h, 8);
+      h[4] = 'a'; h[5] = 'c'; h[6] = 'T'; h[7] = 'L';
+      put_be32(h + 8, (unsigned)g.frames);
+      put_be32(h + 12, (unsigned)g.loop);
+      apng_seal(h, 8);
+    }
+    unsigned char* h = fctl;
+    put_be32(h, 26);
+    h[4] = 'f'; h[5] = 'c'; h[6] = 'T'; h[7] = 'L';
+    put_be32(h + 8, seq_fctl);
+    put_be32(h + 12, (unsigned)a.W);
+    put_be32(h + 16, (unsigned)a.H);
+    put_be32(h + 20, 0);
+    put_be32(h + 24, 0);
+    h[28] = (unsigned char)(g.delay >> 8); h[29] = (unsigned char)g.delay;
+    h[30] = 0; h[31] = 100;                             // delay_den: centiseconds
+    h[32] = 0; h[33] = 0;                               // dispose NONE, blend SOURCE
+    apng_seal(h, 26);
+  }
+}
+
 struct PngPlan {
   long long rb, stream_len, nchunks;
   size_t o_stream, o_slots, o_meta, o_off, o_adler, ws_bytes, out_bytes;
@@ -693,7 +835,107 @@ int png_plan(const char* who, int n, int H, int W, int C, PngPlan* p) {
   return 0;
 }
 
+struct ApngPlan {
+  PngPlan png;               // the geometry of one frame; its offsets and bounds are not used
+  long long frames_all;
+  size_t o_stream, o_slots, o_meta, o_off, o_adler, o_flen, o_foff, ws_bytes, out_bytes;
+};
+
+int apng_plan(const char* who, int g, int n, int H, int W, int C, int delay, int loop, ApngPlan* p) {
+  if (int e = png_plan(who, 1, H, W, C, &p->png)) return e;
+  VF_REQUIRE(n >= 1 && n <= 65535, "%s: n: a clip of %d frames (1 to 65535)", who, n);
+  VF_REQUIRE(g >= 1 && g <= 65535, "%s: g: a batch of %d clips (1 to 65535)", who, g);
+  VF_REQUIRE(delay >= 0 && delay <= 65535, "%s: delay: %d centiseconds (0 to 65535)", who, delay);
+  VF_REQUIRE(loop >= 0 && loop <= 65535, "%s: loop: %d plays (0 to 65535; 0 plays forever)", who, loop);
+  VF_REQUIRE((long long)n * (p->png.nchunks + 1) < (1ll << 31),
+             "%s: n: %d frames of %lld chunks (sequence numbers, frames * (chunks + 1), stay below 2^31)", who, n, p->png.nchunks);
+  p->frames_all = (long long)g * n;
+  const size_t frames = (size_t)p->frames_all, chunks = frames * (size_t)p->png.nchunks;
+  VfCarve ws;
+  p->o_stream = ws.take(frames * (size_t)p->png.stream_len);
+  p->o_slots = ws.take(chunks * PNG_SLOT);
+  p->o_meta = ws.take(chunks * 16);
+  p->o_off = ws.take(chunks * 4);
+  p->o_adler = ws.take(frames * 4);
+  p->o_flen = ws.take(frames * 4);
+  p->o_foff = ws.take(frames * 8);
+  p->ws_bytes = ws.at;
+  // every chunk stored: 5 bytes of block header and 16 of fdAT framing each; zlib header and Adler-32; an fcTL per frame;
+  // signature, IHDR, acTL, IEND
+  p->out_bytes = (size_t)g * ((size_t)n * ((size_t)p->png.stream_len + (size_t)p->png.nchunks * 21 + 6 + APNG_FCTL) + APNG_HEAD + PNG_TAIL);
+  return 0;
+}
+
 }  // namespace
+
+VF_API int vf_apng_workspace_bytes(int g, int n, int H, int W, int C, int delay, int loop, size_t* ws_bytes, size_t* out_bytes) {
+  ApngPlan p;
+  if (int e = apng_plan("vf_apng_workspace_bytes", g, n, H, W, C, delay, loop, &p)) return e;
+  if (ws_bytes) *ws_bytes = p.ws_bytes;
+  if (out_bytes) *out_bytes = p.out_bytes;
+  return 0;
+}
+
+VF_API int vf_apng_encode(vf_ctx* ctx, const void* src, int kind, int g, int n, int H, int W, int C, int delay, int loop, void* ws,
+                          size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
+  ApngPlan p;
+  if (int e = apng_plan("vf_apng_encode", g, n, H, W, C, delay, loop, &p)) return e;
+  char batch[80];
+  snprintf(batch, sizeof(batch), "%d clips of %d frames of %dx%dx%d", g, n, H, W, C);
+  if (int e = vf_check_encode_entry("vf_apng_encode", kind, "C", batch, ws_bytes, p.ws_bytes, out_cap, p.out_bytes)) return e;
+  ApngArgs A;
+  PngArgs& a = A.p;
+  a.src = src;
+  a.stream = (unsigned char*)ws + p.o_stream;
+  a.slots = (unsigned char*)ws + p.o_slots;
+  a.meta = (unsigned*)((char*)ws + p.o_meta);
+  a.chunk_off = (unsigned*)((char*)ws + p.o_off);
+  a.adler = (unsigned*)((char*)ws + p.o_adler);
+  a.out = out;
+  a.offsets = offsets;
+  a.n = n; a.H = H; a.W = W; a.C = C; a.rb = (int)p.png.rb; a.nchunks = (int)p.png.nchunks;
+  a.stream_len = p.png.stream_len;
+  A.frame_len = (unsigned*)((char*)ws + p.o_flen);
+  A.frame_off = (unsigned long long*)((char*)ws + p.o_foff);
+  A.frames = n; A.delay = delay; A.loop = loop;
+  const long long nchunks = p.png.nchunks;
+  // the kernels of vf_png_encode as they are, a slice of at most APNG_SLICE frames (blockIdx.y) at a time: the slice's arrays
+  for (long long f0 = 0; f0 < p.frames_all; f0 += APNG_SLICE) {
+    const int m = (int)(p.frames_all - f0 < APNG_SLICE ? p.frames_all - f0 : APNG_SLICE);
+    PngArgs s = a;
+    s.src = (const char*)src + (size_t)f0 * H * W * C * (kind == 0 ? sizeof(float) : 1);
+    s.stream = a.stream + f0 * a.stream_len;
+    s.slots = a.slots + f0 * nchunks * PNG_SLOT;
+    s.meta = a.meta + f0 * nchunks * 4;
+    s.n = m;
+    const double px = (double)m * H * W * C, stream = (double)m * a.stream_len;
+    if (kind == 0) VF_LAUNCH_TIMED(ctx, "png_filter", 0.0, 8.0 * px + stream, k_png_filter<0>, dim3(H, m), dim3(256), s);
+    else VF_LAUNCH_TIMED(ctx, "png_filter", 0.0, 2.0 * px + stream, k_png_filter<1>, dim3(H, m), dim3(256), s);
+    VF_LAUNCH_CHECK();
+    VF_LAUNCH_TIMED(ctx, "png_deflate", 0.0, 2.0 * stream, k_png_deflate, dim3((unsigned)nchunks, m), dim3(256), s);
+    VF_LAUNCH_CHECK();
+  }
+  {
+    VfProf prof(ctx, "apng_pack", 0.0, 2.0 * (double)p.frames_all * a.stream_len);
+    for (long long f0 = 0; f0 < p.frames_all; f0 += APNG_SLICE) {
+      const int m = (int)(p.frames_all - f0 < APNG_SLICE ? p.frames_all - f0 : APNG_SLICE);
+      A.f0 = f0;
+      hipLaunchKernelGGL(k_apng_frame_scan, dim3(m), dim3(256), 0, ctx->stream, A);
+      VF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_apng_clip_scan, dim3(g), dim3(256), 0, ctx->stream, A);
+    VF_LAUNCH_CHECK();
+    vf_launch_file_offsets(ctx->stream, offsets, g);
+    VF_LAUNCH_CHECK();
+    for (long long f0 = 0; f0 < p.frames_all; f0 += APNG_SLICE) {
+      const int m = (int)(p.frames_all - f0 < APNG_SLICE ? p.frames_all - f0 : APNG_SLICE);
+      A.f0 = f0;
+      hipLaunchKernelGGL(k_apng_pack, dim3((unsigned)nchunks, m), dim3(256), 0, ctx->stream, A);
+      VF_LAUNCH_CHECK();
+    }
+  }
+  return 0;
+}
 
 VF_API int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, size_t* out_bytes) {
   PngPlan p;

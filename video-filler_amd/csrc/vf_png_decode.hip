@@ -21,10 +21,14 @@
 //                         up to 8 bytes (16-bit RGBA) in a 64-bit register when it is above 4;
 //   k_pngd_expand_full    one thread per output pixel: its pass from (x & 7, y & 7), its place inside the pass, 16-bit
 //                         samples big-endian; uint8 (a 16-bit sample's high byte) or float32 (byte / 255, sample / 65535).
+// Animated PNG (vf_apng_inspect, vf_apng_decode_workspace_bytes, vf_apng_decode): the host walk of
+// vf_apng_parse.h makes every frame an image of the full rule, the three launches decode them all, then
+//   k_apng_compose        one thread per canvas pixel of a file: the frames in order, blend SOURCE, the three disposals.
 #include <algorithm>
 #include <string>
 #include <vector>
 
+#include "vf_apng_parse.h"
 #include "vf_block.h"
 #include "vf_common.h"
 
@@ -1249,7 +1253,292 @@ void pngd_pack_full(const uint8_t* data, const int64_t* offs, int n, int out_kin
   }
 }
 
+// ------------------------------------------------------------------------------------------- animated PNG
+// Every frame of every file is an image of the full rule above — its fcTL's width x height under the file's IHDR, PLTE and
+// tRNS, its stream the frame's IDAT or fdAT payloads — decoded by the same three launches into the file's own channels in the
+// workspace; k_apng_compose then paints the canvases.
+struct ApngdFile {
+  int64_t out_off;             // first byte of the file's frames x H x W x oc output
+  int32_t W, H;
+  int32_t first, frames;       // its frames in the frame arrays
+  int32_t fc, oc;              // channels of the decoded frames (1, 2, 3, 4), of the output (3, 4)
+};
+struct ApngdFrame {
+  int64_t px;                  // first byte of the decoded h x w x fc frame in the pixel section of the workspace
+  int32_t x, y, w, h;
+  int32_t dispose, pad;
+};
+
+struct ApngdBatch {
+  const ApngdFile* files;
+  const ApngdFrame* frames;
+  const uint8_t* px;
+  const int32_t* frame_status; // VF_PNG_* per frame, as the three launches left them
+  uint8_t* out;
+  int32_t* status;             // per file: the first of its frames' that is not 0
+};
+
+// One thread per canvas pixel of a file (blockIdx.y): the frames in order, the pixel's RGBA value and the copy PREVIOUS restores in
+// registers.  Blend SOURCE (OVER is refused where it differs): inside the frame's rectangle the frame's pixel replaces the canvas,
+// alpha too; the value goes to output frame k; then the disposal: BACKGROUND clears the rectangle to transparent black, PREVIOUS
+// restores what was there before the frame (on frame 0 that is the empty canvas).  All integer.  A file with a corrupt frame gets
+// that frame's status and is left alone.
+__global__ __launch_bounds__(256) void k_apng_compose(const ApngdBatch B) {
+  const ApngdFile& f = B.files[blockIdx.y];
+  int st = 0;
+  for (int k = 0; k < f.frames && st == 0; ++k) st = B.frame_status[f.first + k];
+  if (blockIdx.x == 0 && threadIdx.x == 0) B.status[blockIdx.y] = st;
+  if (st != 0) return;
+  const int64_t npix = (int64_t)f.W * f.H;
+  const int fc = f.fc, oc = f.oc;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(i / f.W), x = (int)(i % f.W);
+    uint32_t cur = 0;                                          // R | G << 8 | B << 16 | A << 24
+    uint8_t* o = B.out + f.out_off + i * oc;
+    for (int k = 0; k < f.frames; ++k) {
+      const ApngdFrame& fr = B.frames[f.first + k];
+      const uint32_t prev = cur;
+      const bool inside = x >= fr.x && x < fr.x + fr.w && y >= fr.y && y < fr.y + fr.h;
+      if (inside) {
+        const uint8_t* p = B.px + fr.px + ((int64_t)(y - fr.y) * fr.w + (x - fr.x)) * fc;
+        if (fc == 1) cur = p[0] * 0x010101u | 0xFF000000u;
+        else if (fc == 2) cur = p[0] * 0x010101u | ((uint32_t)p[1] << 24);
+        else if (fc == 3) cur = p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | 0xFF000000u;
+        else cur = p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+      }
+      o[0] = (uint8_t)cur;
+      o[1] = (uint8_t)(cur >> 8);
+      o[2] = (uint8_t)(cur >> 16);
+      if (oc == 4) o[3] = (uint8_t)(cur >> 24);
+      o += npix * oc;
+      if (inside && fr.dispose == 1) cur = 0;
+      else if (inside && fr.dispose == 2) cur = prev;
+    }
+  }
+}
+
+struct ApngdPlan {
+  std::vector<apngd::Parsed> A;
+  std::vector<PngParsed> P;    // one per frame: the frame as an image of the full rule
+  std::vector<PngFull> F;
+  std::vector<int> file_of;
+  int64_t nframes = 0, stream_bytes = 0, inf_bytes = 0, raw_bytes = 0, px_bytes = 0, max_fpix = 0, max_cpix = 0;
+  size_t o_img = 0, o_files = 0, o_frames = 0, o_streams = 0, stage = 0, o_inf = 0, o_raw = 0, o_px = 0, o_fstatus = 0, ws = 0;
+};
+
+// frame k of a parsed file as the image the full rule decodes
+void apngd_frame_image(const apngd::Parsed& A, const apngd::Frame& f, PngParsed& P) {
+  P.W = f.w;
+  P.H = f.h;
+  P.depth = A.depth;
+  P.ctype = A.ctype;
+  P.lace = A.lace;
+  P.rc = A.rc;
+  P.fc = A.fc;
+  P.nplte = A.nplte;
+  P.ntrns = A.ntrns;
+  P.has_plte = A.has_plte;
+  P.has_trns = A.has_trns;
+  memcpy(P.plte, A.plte, 768);
+  memcpy(P.trns, A.trns, 256);
+  P.idat_bytes = f.data_bytes;
+  P.idat_chunks = (int64_t)f.seg.size();
+  P.idat = f.seg;
+  P.rb = (P.W * P.rc * P.depth + 7) / 8;
+  P.inflated = P.H * (1 + P.rb);
+  P.supported = true;
+}
+
+// 0; 2 with the error set for a malformed file; 3 for one the device decoder does not take
+int apngd_plan(const char* who, const uint8_t* data, const int64_t* offs, int n, int alpha, ApngdPlan& L) {
+  VF_REQUIRE(n > 0 && data && offs, "%s: empty batch", who);
+  VF_REQUIRE(n <= 65535, "%s: %d files in one batch (65535 at most)", who, n);
+  VF_REQUIRE(alpha == 0 || alpha == 1, "%s: alpha %d is not 0 (RGB) or 1 (RGBA)", who, alpha);
+  L.A.resize(n);
+  for (int i = 0; i < n; ++i) {
+    std::string msg;
+    VF_REQUIRE(offs[i + 1] >= offs[i], "%s: offsets decrease at image %d", who, i);
+    apngd::Parsed& A = L.A[i];
+    if (apngd::parse(data + offs[i], offs[i + 1] - offs[i], A, msg)) {
+      vf_set_error("%s: image %d: %s", who, i, msg.c_str());
+      return 2;
+    }
+    if (!A.supported) {
+      vf_set_error("%s: image %d: unsupported: %s", who, i, A.why.c_str());
+      return 3;
+    }
+    for (size_t k = 0; k < A.frames.size(); ++k) {
+      L.P.emplace_back();
+      L.F.emplace_back();
+      L.file_of.push_back(i);
+      PngParsed& P = L.P.back();
+      PngFull& F = L.F.back();
+      apngd_frame_image(A, A.frames[k], P);
+      png_full_rule(P, F);
+      if (!F.supported) {
+        vf_set_error("%s: image %d: unsupported: frame %zu: %s", who, i, k, F.why.c_str());
+        return 3;
+      }
+      L.stream_bytes += (int64_t)vf_up256((size_t)(P.idat_bytes - 2) + 8);
+      L.inf_bytes += (int64_t)vf_up256((size_t)F.inflated);
+      if (!pngd_full_direct(P, A.fc, 0)) L.raw_bytes += (int64_t)vf_up256((size_t)F.raw);
+      L.px_bytes += (int64_t)vf_up256((size_t)(P.W * P.H * A.fc));
+      L.max_fpix = std::max(L.max_fpix, P.W * P.H);
+    }
+    L.max_cpix = std::max(L.max_cpix, A.W * A.H);
+  }
+  L.nframes = (int64_t)L.P.size();
+  VF_REQUIRE(L.nframes <= 65535, "%s: %lld frames in one batch (65535 at most; split the batch)", who, (long long)L.nframes);
+  VfCarve ws;
+  L.o_img = ws.take(sizeof(PngdFull) * (size_t)L.nframes);
+  L.o_files = ws.take(sizeof(ApngdFile) * (size_t)n);
+  L.o_frames = ws.take(sizeof(ApngdFrame) * (size_t)L.nframes);
+  L.o_streams = ws.take((size_t)L.stream_bytes);
+  L.stage = ws.at;
+  L.o_inf = ws.take((size_t)L.inf_bytes);
+  L.o_raw = ws.take((size_t)L.raw_bytes);
+  L.o_px = ws.take((size_t)L.px_bytes);
+  L.o_fstatus = ws.take(sizeof(int32_t) * (size_t)L.nframes);
+  L.ws = ws.at;
+  return 0;
+}
+
+void apngd_pack(const uint8_t* data, const int64_t* offs, int n, int alpha, const int64_t* out_offs, const ApngdPlan& L, uint8_t* st) {
+  PngdFull* imgs = (PngdFull*)(st + L.o_img);
+  ApngdFile* files = (ApngdFile*)(st + L.o_files);
+  ApngdFrame* frames = (ApngdFrame*)(st + L.o_frames);
+  uint8_t* streams = st + L.o_streams;
+  int64_t sc = 0, inf = 0, raw = 0, px = 0, j = 0;
+  for (int i = 0; i < n; ++i) {
+    const apngd::Parsed& A = L.A[i];
+    ApngdFile& fl = files[i];
+    memset(&fl, 0, sizeof(fl));
+    fl.out_off = out_offs[i];
+    fl.W = (int32_t)A.W;
+    fl.H = (int32_t)A.H;
+    fl.first = (int32_t)j;
+    fl.frames = (int32_t)A.frames.size();
+    fl.fc = A.fc;
+    fl.oc = alpha ? 4 : 3;
+    for (size_t k = 0; k < A.frames.size(); ++k, ++j) {
+      const PngParsed& P = L.P[j];
+      const PngFull& F = L.F[j];
+      PngdFull& f = imgs[j];
+      memset(&f, 0, sizeof(f));
+      const int64_t room = pngd_fill(f.im, P, data + offs[i], A.fc, pngd_full_direct(P, A.fc, 0), F.inflated, streams, sc, inf, raw, px);
+      f.lace = P.lace;
+      f.out_kind = 0;
+      int64_t pi = 0, pr = 0;
+      for (int p = 0; p < 7; ++p) {
+        f.ph[p] = (int32_t)F.h[p];
+        f.prb[p] = (int32_t)F.rb[p];
+        f.pinf[p] = (int32_t)pi;
+        f.praw[p] = (int32_t)pr;
+        pi += F.h[p] * (1 + F.rb[p]);
+        pr += F.h[p] * F.rb[p];
+      }
+      ApngdFrame& fr = frames[j];
+      memset(&fr, 0, sizeof(fr));
+      fr.px = px;
+      fr.x = (int32_t)A.frames[k].x;
+      fr.y = (int32_t)A.frames[k].y;
+      fr.w = (int32_t)A.frames[k].w;
+      fr.h = (int32_t)A.frames[k].h;
+      fr.dispose = A.frames[k].dispose;
+      sc += room;
+      inf += (int64_t)vf_up256((size_t)F.inflated);
+      if (!f.im.direct) raw += (int64_t)vf_up256((size_t)F.raw);
+      px += (int64_t)vf_up256((size_t)(P.W * P.H * A.fc));
+    }
+  }
+}
+
 }  // namespace
+
+VF_API int vf_apng_inspect(const unsigned char* data, size_t len, int64_t* info, int64_t* frames, int frame_cap, char* reason,
+                           int reason_cap) {
+  VF_REQUIRE(data && info && frame_cap >= 0 && (frames || frame_cap == 0), "vf_apng_inspect: NULL argument");
+  apngd::Parsed A;
+  std::string msg;
+  const int rc = apngd::parse(data, (int64_t)len, A, msg);
+  if (rc) {
+    vf_set_error("vf_apng_inspect: %s", msg.c_str());
+    return rc;
+  }
+  std::string why = A.why;
+  for (size_t k = 0; k < A.frames.size() && why.empty(); ++k) {   // what the full rule refuses of a single frame
+    PngParsed P;
+    PngFull F;
+    apngd_frame_image(A, A.frames[k], P);
+    png_full_rule(P, F);
+    if (!F.supported) why = "frame " + std::to_string(k) + ": " + F.why;
+  }
+  const int64_t v[12] = {A.W, A.H, A.depth, A.ctype, A.lace, A.fc, (int64_t)A.frames.size(), A.num_plays, why.empty() ? 1 : 0,
+                         A.animated ? 1 : 0, A.default_is_frame ? 1 : 0, A.nplte};
+  memcpy(info, v, sizeof v);
+  for (size_t k = 0; k < A.frames.size() && (int64_t)k < frame_cap; ++k) {
+    const apngd::Frame& f = A.frames[k];
+    const int64_t r[9] = {f.x, f.y, f.w, f.h, f.delay_num, f.delay_den, f.dispose, f.blend, f.data_bytes};
+    memcpy(frames + 9 * k, r, sizeof r);
+  }
+  if (reason && reason_cap > 0) snprintf(reason, (size_t)reason_cap, "%s", why.c_str());
+  return 0;
+}
+
+VF_API int vf_apng_decode_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int alpha, size_t* ws_bytes,
+                                          size_t* stage_bytes) {
+  ApngdPlan L;
+  if (int e = apngd_plan("vf_apng_decode_workspace_bytes", data, offs, n, alpha, L)) return e;
+  if (ws_bytes) *ws_bytes = L.ws;
+  if (stage_bytes) *stage_bytes = L.stage;
+  return 0;
+}
+
+VF_API int vf_apng_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int alpha, const int64_t* out_offs,
+                          unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes, int32_t* status) {
+  VF_REQUIRE(out && out_offs && stage && ws && status, "vf_apng_decode: NULL argument");
+  ApngdPlan L;
+  if (int e = apngd_plan("vf_apng_decode", data, offs, n, alpha, L)) return e;
+  VF_REQUIRE(stage_bytes >= L.stage && ws_bytes >= L.ws, "vf_apng_decode: staging %zu / workspace %zu bytes, need %zu / %zu", stage_bytes,
+             ws_bytes, L.stage, L.ws);
+  apngd_pack(data, offs, n, alpha, out_offs, L, (uint8_t*)stage);
+  uint8_t* w = (uint8_t*)ws;
+  const unsigned nf = (unsigned)L.nframes;
+  PngdFullBatch B;
+  B.img = (const PngdFull*)(w + L.o_img);
+  B.streams = w + L.o_streams;
+  B.inf = w + L.o_inf;
+  B.raw = w + L.o_raw;
+  B.out = w + L.o_px;
+  B.status = (int32_t*)(w + L.o_fstatus);
+  ApngdBatch Cb;
+  Cb.files = (const ApngdFile*)(w + L.o_files);
+  Cb.frames = (const ApngdFrame*)(w + L.o_frames);
+  Cb.px = w + L.o_px;
+  Cb.frame_status = B.status;
+  Cb.out = out;
+  Cb.status = status;
+  hipStream_t st = ctx->stream;
+  {
+    VfRange r("apngd_upload");
+    VF_CHECK_HIP(hipMemcpyAsync(w, stage, L.stage, hipMemcpyHostToDevice, st));
+    VF_CHECK_HIP(hipMemsetAsync(B.status, 0, sizeof(int32_t) * nf, st));
+  }
+  const double inf = (double)L.inf_bytes;
+  VF_LAUNCH_TIMED(ctx, "pngd_inflate", 0.0, (double)L.stream_bytes + inf, k_pngd_inflate<PngdFull>, dim3(nf), dim3(kInfThreads), B);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, "pngd_unfilter_full", 0.0, 2.0 * inf, k_pngd_unfilter_full, dim3(7u * nf), dim3(64), B);
+  VF_LAUNCH_CHECK();
+  const unsigned gp = (unsigned)std::min<int64_t>(std::max<int64_t>(1, vf_cdiv(L.max_fpix, 256)), 4096);
+  VF_LAUNCH_TIMED(ctx, "pngd_expand_full", 0.0, 2.0 * (double)L.raw_bytes, k_pngd_expand_full, dim3(gp, nf), dim3(256), B);
+  VF_LAUNCH_CHECK();
+  const unsigned gc = (unsigned)std::min<int64_t>(std::max<int64_t>(1, vf_cdiv(L.max_cpix, 256)), 4096);
+  double out_bytes = 0;
+  for (int i = 0; i < n; ++i) out_bytes += (double)L.A[i].frames.size() * (double)(L.A[i].W * L.A[i].H) * (alpha ? 4 : 3);
+  VF_LAUNCH_TIMED(ctx, "apng_compose", 0.0, (double)L.px_bytes + out_bytes, k_apng_compose, dim3(gc, (unsigned)n), dim3(256), Cb);
+  VF_LAUNCH_CHECK();
+  return 0;
+}
 
 VF_API int vf_png_inspect(const unsigned char* data, size_t len, int64_t* info, char* reason, int reason_cap) {
   VF_REQUIRE(data && info, "vf_png_inspect: NULL argument");

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ._lib import VfError
-from .backend import (GIF_STATUS, JPEG_STATUS, METRIC_COLUMNS, PNG_STATUS, get_backend, gif_inspect, jpeg_inspect,
+from .backend import (GIF_STATUS, JPEG_STATUS, METRIC_COLUMNS, PNG_STATUS, apng_inspect, get_backend, gif_inspect, jpeg_inspect,
                       jpeg_inspect_layouts, jpeg_scans_inspect, nhwc_empty, png_inspect, png_inspect_full)
 
 CENTER_FILL = (117.0, 104.0, 123.0)      # train.lua:287-289
@@ -405,6 +405,97 @@ def encode_gif(clips, delay=10):
         raise ValueError("encode_gif: delay=%r is not a whole number of centiseconds from 0 to 65535" % (delay,))
     B = get_backend()
     return _files_from(*B.gif_encode(B.from_host(t).contiguous(), int(delay)))
+
+
+# ------------------------------------------------------------------------------------------------ APNG
+def encode_apng(clips, delay=10, loop=0):
+    """A batch of clips as animated PNG files, lossless, encoded on the device in one call (vf_apng_encode): a list of
+    `bytes`, one whole APNG file per clip, `delay` centiseconds a frame, played `loop` times (0: forever).  clips: uint8
+    G x N x H x W x C (taken as they are) or float G x N x C x H x W (image.savePNG's rule); C = 1 (grey) or 3 (RGB); a
+    4-D input is one clip; host or device.  The file is what tests/apng_ref.py assembles from the N files encode_png
+    writes for the clip's frames: every frame is its own zlib stream, frame 0 in IDAT chunks — the file is
+    also a PNG of frame 0 — and the others in fdAT chunks; no frame differencing.  Decoding gives exactly the frames'
+    bytes; a file's bytes depend on its frames, delay and loop alone and are the same on every run.  One device-to-host
+    copy brings the batch back."""
+    t = torch.as_tensor(clips)
+    t = _as_frames("encode_apng", t.unsqueeze(0) if t.dim() == 4 else t, 5)
+    if int(delay) != delay or not 0 <= delay <= 65535:
+        raise ValueError("encode_apng: delay=%r is not a whole number of centiseconds from 0 to 65535" % (delay,))
+    if int(loop) != loop or not 0 <= loop <= 65535:
+        raise ValueError("encode_apng: loop=%r is not a whole number of plays from 0 to 65535 (0: forever)" % (loop,))
+    B = get_backend()
+    return _files_from(*B.apng_encode(B.from_host(t).contiguous(), int(delay), int(loop)))
+
+
+def apng_info(item):
+    """The host-side walk of one APNG or PNG file (no GPU): dict(width, height, bit_depth, color_type, interlace, channels
+    (of the decoded frames), frames, num_plays (-1 without acTL; 0: forever), supported, animated, default_is_frame,
+    palette_entries, reason, frame_info), frame_info holding per frame dict(x, y, w, h, delay_num, delay_den, dispose,
+    blend, data_bytes).  A PNG without acTL is a clip of one frame.  ValueError if the file is malformed (DESIGN 5.11
+    lists what that is: CRCs, acTL, sequence numbers, frames without data or outside the canvas, truncation)."""
+    return apng_inspect(_file_bytes(item))
+
+
+def decode_apng(items, alpha=False, fallback=None):
+    """The frames of a batch of APNG files, decoded and composited on the device (vf_apng_decode): a list with one device
+    uint8 N x H x W x 3 tensor per file (N x H x W x 4 with alpha=True), views of one buffer.  Output frame k is the
+    canvas after frame k was rendered, by the APNG specification (tests/apng_decode_ref.py is the
+    definition): the canvas starts transparent black, blend SOURCE replaces the frame's rectangle, dispose 1 clears it, 2
+    restores what was there; grey is replicated, a file without alpha paints alpha 255, a pixel nothing has painted is
+    (0,0,0) with alpha 0; a 16-bit sample gives its high byte.  Every format decode_png(full=True) takes works, Adam7
+    too.  A PNG without acTL is a clip of one frame.  Files `encode_apng` wrote come back as their frames' exact bytes.
+
+    items: bytes, uint8 arrays or paths.  Files the device decoder does not take (blend OVER with alpha, tRNS on grey or
+    RGB, a side above 16384, more than 65535 frames, 2 GiB of frames) go to fallback(bytes), which returns the uint8
+    N x H x W x C frames; without it they raise ValueError naming the item and why.  A malformed file raises ValueError
+    naming the item before anything is launched; a corrupt frame stream raises it, with the status, once the stream has
+    synchronised.  A batch of more than 65535 frames is decoded in several calls."""
+    from .backend import APNG_MAX_BATCH_FRAMES
+    B = get_backend()
+    oc = 4 if alpha else 3
+    files = [_file_bytes(it) for it in items]
+    infos, dev, out = {}, [], [None] * len(files)
+    for i, f in enumerate(files):
+        try:
+            info = apng_inspect(f)
+        except ValueError as e:
+            raise ValueError("decode_apng: item %d: %s" % (i, e)) from None
+        if not info["supported"]:
+            if fallback is None:
+                raise ValueError("decode_apng: item %d is not supported by the device decoder: %s" % (i, info["reason"]))
+            fr = torch.as_tensor(np.ascontiguousarray(fallback(f)))
+            assert fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == oc, \
+                "fallback returns uint8 N x H x W x %d, got %s %s" % (oc, fr.dtype, tuple(fr.shape))
+            out[i] = B.from_host(fr).contiguous()
+            continue
+        infos[i] = info
+        dev.append(i)
+    calls, count = [[]], 0
+    for i in dev:                                        # a call holds 65535 frames at most
+        if calls[-1] and count + infos[i]["frames"] > APNG_MAX_BATCH_FRAMES:
+            calls.append([])
+            count = 0
+        calls[-1].append(i)
+        count += infos[i]["frames"]
+    results = []
+    for part in calls:
+        if not part:
+            continue
+        try:
+            results.append((part, B.apng_decode([files[i] for i in part], alpha, [infos[i] for i in part])))
+        except VfError as e:   # found on the host while the batch was planned: nothing was launched
+            m = re.search(r"image (\d+)", str(e))
+            if m is None:
+                raise
+            raise ValueError("decode_apng: item %d: %s" % (part[int(m.group(1))], e)) from None
+    for part, (buf, offs, status) in results:
+        st = status.cpu().tolist()
+        for j, i in enumerate(part):
+            if st[j] != 0:
+                raise ValueError("decode_apng: item %d: corrupt image data (%s)" % (i, PNG_STATUS.get(st[j], st[j])))
+            s = infos[i]
+            out[i] = buf[offs[j]:offs[j + 1]].view(s["frames"], s["height"], s["width"], oc)
+    return out
 
 
 # ------------------------------------------------------------------------------------------ GIF decode (DESIGN 5.10)

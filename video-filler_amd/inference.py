@@ -207,6 +207,42 @@ def save_gifs(name, outImages=None, inpaintImages=None, fullImages=None, delay=1
     return _write_files(["%s_%s.gif" % (name, key) for key in keys], files)
 
 
+def save_apngs(name, outImages=None, inpaintImages=None, fullImages=None, delay=10, **named):
+    """save_gifs without its loss: name_result.png, name_inpaint.png, name_orig.png and name_<key>.png as animated PNG
+    files, all clips encoded on the device in ONE call (data.encode_apng); the host only writes the files.
+    Tensors are predLen x C x H x W in [0,1] (image.savePNG's truncating byte rule applies) or uint8 predLen x H x W x C,
+    C = 1 or 3.  Every frame keeps its exact bytes, and unlike save_gifs the clip holds ALL predLen frames: the frame
+    save_gifs drops is a quirk of the reference's `convert` loop, and no reference command writes these files.  Each file
+    is also a plain PNG of its first frame, and loops forever.  The parent directory is created.  Returns the paths, in the order result,
+    inpaint, orig, then the keywords'."""
+    import os
+    groups = [(p, t) for p, t in (("result", outImages), ("inpaint", inpaintImages), ("orig", fullImages)) if t is not None]
+    groups += list(named.items())
+    if not groups:
+        raise ValueError("save_apngs: nothing to save")
+    keys = [p for p, _ in groups]
+    if len(set(keys)) != len(keys):
+        raise ValueError("save_apngs: clip given twice (%s); one would overwrite the other" % ", ".join(keys))
+    ts = [t if torch.is_tensor(t) else torch.as_tensor(t) for _, t in groups]
+    if not all(t.dim() == 4 for t in ts) or len({(t.dtype, tuple(t.shape)) for t in ts}) != 1:
+        raise ValueError("save_apngs: the clips of one call are 4-D and share one type, length and frame size")
+    from .data import encode_apng
+    B = get_backend()
+    files = encode_apng(torch.stack([B.from_host(t) for t in ts]), delay)
+    os.makedirs(os.path.dirname(os.path.abspath(name)), exist_ok=True)
+    return _write_files(["%s_%s.png" % (name, key) for key in keys], files)
+
+
+def load_apng_clip(item):
+    """An APNG file (bytes, a path, a uint8 array or tensor) as the clip the drivers hold: float N x 3 x H x W in [0,1] on the
+    device — every frame composited on the device (data.decode_apng), b / 255 as a correctly rounded
+    float32 division, then the layout change.  What save_apngs wrote comes back without loss:
+    evaluate_frames(load_apng_clip(name + "_result.png"), load_apng_clip(name + "_orig.png")) scores the frames' own bytes.
+    ValueError for a malformed, unsupported or corrupt file."""
+    (frames,) = data.decode_apng([item])
+    return get_backend().png_bytes_to_float(frames).permute(0, 3, 1, 2).contiguous()
+
+
 def load_gif_clip(item):
     """A GIF file (bytes, a path, a uint8 array or tensor) as the clip the drivers hold: float N x 3 x H x W in [0,1] on the
     device — every frame composited on the device (data.decode_gif), b / 255 as a correctly rounded
