@@ -1,5 +1,7 @@
 """Shared helpers for the parity tests: layout conversion between the oracle's NCHW numpy arrays and the
 backend's channels-last device tensors, and error metrics."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -254,3 +256,32 @@ def untouched(buf, lo, hi=None):
     if buf.dtype == torch.float32:
         return bool((seg.view(torch.int32) == TAIL32).all())
     return bool((seg.view(torch.int64) == FILL64).all())
+
+
+# ---- a context's workspace inside a guard band (tests/test_gpu_workspace.py, tests/test_gpu_bias_grad.py)
+WS_FILL = 0xA5                   # workspace guard bytes
+
+
+def set_workspace(b, ptr, nbytes):
+    import ctypes as C
+    from video_filler_amd import _lib
+    _lib.check(b.lib.vf_ctx_set_workspace(b.ctx, C.c_void_p(ptr), nbytes))
+
+
+@contextlib.contextmanager
+def workspace(b, nbytes, guard=1 << 20, front=0):
+    """point b's context at `nbytes` of a fresh buffer followed by `guard` bytes of a fixed pattern (and, front > 0, behind `front`
+    such bytes); on exit the guards must be byte-identical.  b.workspace follows (bias_grad_multi sizes its partials from it; its
+    plans and vf_net's follow the workspace by themselves).  Yields the whole buffer: the workspace is buf[front:front + nbytes]."""
+    buf = torch.full((front + nbytes + guard,), WS_FILL, dtype=torch.uint8, device=b.device)
+    old = b.workspace
+    set_workspace(b, buf.data_ptr() + front, nbytes)
+    b.workspace = buf[front:front + nbytes]
+    try:
+        yield buf
+    finally:
+        b.synchronize()
+        intact = bool((buf[front + nbytes:] == WS_FILL).all()) and bool((buf[:front] == WS_FILL).all())
+        b.workspace = old
+        set_workspace(b, old.data_ptr(), old.numel())
+    assert intact, "a kernel wrote outside a %d-byte workspace" % nbytes

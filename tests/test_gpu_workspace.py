@@ -13,14 +13,11 @@ Every run checks:
   - the split count the library reports through its profile (slab_reduce_* records 4 * out_elems * (ksplit + 1) bytes per
     launch) against the workspace it had: ksplit * slab <= workspace, never more splits for less room.
 The split counts and routes each case reached are printed (pytest -rP shows them)."""
-import contextlib
-import ctypes as C
-
 import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import FILL64, TAIL32, guarded, untouched  # noqa: F401
+from helpers import FILL64, TAIL32, WS_FILL, guarded, untouched, workspace  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +27,6 @@ TOL = 2e-5           # against fp64, relative to the max-norm
 # (measured on the 256 -> 512 forward and the 384-channel gather), so the bar is 4e-6: still five times inside the fp64 bar
 AGREE = 4e-6
 U = 2.0 ** -24       # unit roundoff of fp32
-WS_FILL = 0xA5                   # workspace guard bytes
 SLOPE = 0.2
 
 
@@ -56,32 +52,6 @@ def mode(request, wb):
 
 def hint(b):
     return int(b.lib.vf_workspace_bytes_hint())
-
-
-def _set_ws(b, ptr, nbytes):
-    from video_filler_amd import _lib
-    _lib.check(b.lib.vf_ctx_set_workspace(b.ctx, C.c_void_p(ptr), nbytes))
-
-
-@contextlib.contextmanager
-def workspace(b, nbytes, guard=1 << 20):
-    """point b's context at `nbytes` of a fresh buffer followed by `guard` bytes of a fixed pattern; on exit the guard must be
-    byte-identical.  b.workspace follows (bias_grad_multi sizes its partials from it) and the pointer-keyed bias-gradient
-    plans are dropped."""
-    buf = torch.full((nbytes + guard,), WS_FILL, dtype=torch.uint8, device=b.device)
-    old = b.workspace
-    _set_ws(b, buf.data_ptr(), nbytes)
-    b.workspace = buf[:nbytes]
-    b.__dict__.pop("_colsum_plans", None)
-    try:
-        yield buf
-    finally:
-        b.synchronize()
-        intact = bool((buf[nbytes:] == WS_FILL).all())
-        b.workspace = old
-        b.__dict__.pop("_colsum_plans", None)
-        _set_ws(b, old.data_ptr(), old.numel())
-    assert intact, "a kernel wrote past the end of a %d-byte workspace" % nbytes
 
 
 def g_act(b, B, Cc, H, W):

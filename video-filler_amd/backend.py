@@ -862,11 +862,13 @@ class HipBackend:
     # ---- all conv bias gradients of one backward walk in two launches (vf_bias_grad_multi)
     def bias_grad_multi(self, items):
         """items: [(gradOutput B x C x H x W channels-last, gradBias [C], beta)], C % 4 == 0.  The descriptor table is built
-        once per combination of buffers and betas and kept on the device (the same walk recurs every iteration)."""
+        once per combination of buffers, betas and workspace and kept on the device (the same walk recurs every iteration; the table
+        holds the address of its partial rows, so a plan follows the workspace: another base or size is another plan)."""
         import numpy as np
         if not items:
             return
-        key = tuple((g.data_ptr(), gb.data_ptr(), g.numel(), gb.numel(), float(beta)) for g, gb, beta in items)
+        key = (self.workspace.data_ptr(), self.workspace.numel()) + tuple(
+            (g.data_ptr(), gb.data_ptr(), g.numel(), gb.numel(), float(beta)) for g, gb, beta in items)
         cache = self.__dict__.setdefault("_colsum_plans", {})
         plan = cache.get(key)
         if plan is None:

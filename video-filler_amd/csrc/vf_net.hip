@@ -131,7 +131,13 @@ struct vf_net {
   vf_net_act_observer observer = nullptr;
   void* observer_user = nullptr;
   // device tables built once per combination and kept (the same walk recurs every iteration)
-  std::map<std::string, std::pair<void*, std::vector<int>>> colsum_plans;
+  struct ColsumPlan {
+    void* dev = nullptr;           // VfColsumDesc[n]
+    int n = 0, b1 = 0, b2 = 0;
+    const char* ws = nullptr;      // the workspace the table's partial rows lie in: a plan follows the workspace (bias_grad_flush)
+    size_t ws_avail = 0;
+  };
+  std::map<std::string, ColsumPlan> colsum_plans;
   void* wp_table = nullptr;
   int wp_n = 0, wp_blocks = 0;
   std::vector<int> wp_key;
@@ -459,14 +465,17 @@ int bn_backward(vf_net* n, Layer& l, const float* x, const float* gy, int Bn, bo
   return 0;
 }
 
-// every deferred gradBias of a walk: two launches; the descriptor table is built once per combination and kept on the device
+// every deferred gradBias of a walk: two launches; the descriptor table is built once per combination and kept on the device.
+// The table holds the address of its partial rows, so it is rebuilt when the context's workspace is no longer the one it was built
+// under (vf_ctx_set_workspace) — into a fresh table, as refresh_weight_planes does: a launch in flight may still read the old one.
 int bias_grad_flush(vf_net* n, const std::vector<Deferred>& items) {
   if (items.empty()) return 0;
   std::string key((const char*)items.data(), items.size() * sizeof(Deferred));
+  char* ws = vf_ws_ptr(n->ctx);
+  const size_t ws_avail = vf_ws_avail(n->ctx);
   auto it = n->colsum_plans.find(key);
-  if (it == n->colsum_plans.end()) {
+  if (it == n->colsum_plans.end() || it->second.ws != ws || it->second.ws_avail != ws_avail) {
     std::vector<VfColsumDesc> desc(items.size());
-    char* ws = vf_ws_ptr(n->ctx);
     size_t off = 0;
     int b1 = 0, b2 = 0;
     for (size_t i = 0; i < items.size(); ++i) {
@@ -478,14 +487,19 @@ int bias_grad_flush(vf_net* n, const std::vector<Deferred>& items) {
       b1 += gx * gy;
       b2 += (d.C + 3) / 4;
     }
-    VF_REQUIRE(off <= vf_ws_avail(n->ctx), "vf_net: workspace too small for the bias-gradient partials");
+    VF_REQUIRE(off <= ws_avail, "vf_net: workspace too small for the bias-gradient partials");
     void* dev = nullptr;
     if (int rc = net_alloc(n->owned, &dev, desc.size() * sizeof(VfColsumDesc))) return rc;
     VF_CHECK_HIP(hipMemcpy(dev, desc.data(), desc.size() * sizeof(VfColsumDesc), hipMemcpyHostToDevice));
-    it = n->colsum_plans.emplace(key, std::make_pair(dev, std::vector<int>{(int)items.size(), b1, b2})).first;
+    vf_net::ColsumPlan plan;
+    plan.dev = dev;
+    plan.n = (int)items.size(); plan.b1 = b1; plan.b2 = b2;
+    plan.ws = ws; plan.ws_avail = ws_avail;
+    n->colsum_plans[key] = plan;
+    it = n->colsum_plans.find(key);
   }
-  const std::vector<int>& g = it->second.second;
-  return vf_bias_grad_multi(n->ctx, it->second.first, g[0], g[1], g[2]);
+  const vf_net::ColsumPlan& p = it->second;
+  return vf_bias_grad_multi(n->ctx, p.dev, p.n, p.b1, p.b2);
 }
 
 // Backward over plan entries hi-1 .. lo.  gi >= 0: the pass covers batch group gi of the G the last forward ran
