@@ -1,4 +1,5 @@
-"""Same answers from two builds of the library, where the test suite cannot see a difference: every conv pass of the C-ABI on
+"""Same answers from two builds of the library, byte for byte (whether those answers are RIGHT on non-square maps is
+tests/test_gpu_nonsquare.py's business: exact and fp64 checks of every route): every conv pass of the C-ABI on
 NON-SQUARE maps with Cin != Cout, the bottleneck and head geometries, the generic path, the planes passes, pending BatchNorm
 requests, vf_net with the planes gate dropped, weight-gradient groups under small workspaces and with every route in one walk
 — raw output bytes, and the messages of the calls that are refused.
