@@ -107,7 +107,8 @@ class Run:
         names = sorted(prof)
         want = NS.pwgrad_route(self.mode, c) if pname.startswith("pwgrad") else c.routes[pname]
         assert any(n.startswith(p) for n in names for p in want), "%s mode %d %s: launches %s, none of %s" % (c.id, self.mode, pname, names, want)
-        if self.kind == "int":
+        self.routes.append((pname, names))
+        if self.tol is None:
             print("(%s, mode %d, %s, %s)" % (c.id, self.mode, pname, "+".join(names)))
         return True
 

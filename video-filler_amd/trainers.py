@@ -196,6 +196,21 @@ def _solver(opt):
 
 
 import contextlib
+import gc
+
+
+@contextlib.contextmanager
+def _no_gc():
+    """no cyclic collection while a stream is captured: a finalizer that frees device memory from the capturing thread (a net, a plan
+    table, a graph of an earlier trainer) invalidates the capture, and WHEN the collector runs depends on every allocation the process
+    has made.  torch.cuda.graph collects once, explicitly, as it begins"""
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 def _no_range(name):
@@ -731,7 +746,7 @@ class _TrainerBase:
             self.step()
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+        with _no_gc(), torch.cuda.graph(g, capture_error_mode="thread_local"):
             B.use_current_stream()
             self.step()
         B.use_current_stream()
@@ -760,7 +775,7 @@ class _TrainerBase:
         pool = None
         for phase in phases:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):   # RCCL's watchdog thread may poll events meanwhile
+            with _no_gc(), torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):   # RCCL's watchdog thread may poll events meanwhile
                 B.use_current_stream()
                 phase()
             B.use_current_stream()
@@ -788,7 +803,7 @@ class _TrainerBase:
             self.step_phased()
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+        with _no_gc(), torch.cuda.graph(g, capture_error_mode="thread_local"):
             B.use_current_stream()
             self.step_phased()
         B.use_current_stream()
