@@ -600,6 +600,14 @@ int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, size_t*
  * allocated and nothing synchronises. */
 int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, void* ws, size_t ws_bytes,
                   unsigned char* out, size_t out_cap, int64_t* offsets);
+/* vf_png_encode with a compression level.  0: vf_png_encode, byte for byte.  1 ("dense"): the same filter, chunks, IDATs,
+ * Huffman construction and workspace, with a denser matcher in the deflate stage (k_png_deflate_dense; tests/png_dense_ref.py
+ * is its rule): hash chains over the chunk and the 8 KiB of the same frame's stream before it, distance 1 and 64 chain
+ * entries per position, the same literal pricing, one lazy step, so a back-reference may reach into the preceding chunk
+ * (never into another frame).  About half the bytes of level 0 on smooth frames, several times its deflate time.  Any other
+ * level is an error naming `level`, before anything is launched.  vf_png_workspace_bytes holds for both levels. */
+int vf_png_encode_level(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int level, void* ws, size_t ws_bytes,
+                        unsigned char* out, size_t out_cap, int64_t* offsets);
 
 /* ---- JPEG encode (vf_jpeg_enc.hip) ---------------------------------------------------------------------
  * image.save('x.jpg') / image.compressJPG, the JPEG folders the loaders read and the payload of the training scripts'
@@ -702,6 +710,10 @@ int vf_apng_workspace_bytes(int g, int n, int H, int W, int C, int delay, int lo
  * allocated and nothing synchronises. */
 int vf_apng_encode(vf_ctx* ctx, const void* src, int kind, int g, int n, int H, int W, int C, int delay, int loop, void* ws,
                    size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
+/* vf_apng_encode with vf_png_encode_level's compression level: the file assembled from the PNG files of that level.  Level 0
+ * is vf_apng_encode; any level but 0 and 1 is an error naming `level`.  vf_apng_workspace_bytes holds for both levels. */
+int vf_apng_encode_level(vf_ctx* ctx, const void* src, int kind, int g, int n, int H, int W, int C, int delay, int loop, int level,
+                         void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
 
 /* ---- animated PNG decode (vf_png_decode.hip, vf_apng_parse.h) -----------------------------------------
  * APNG files (the ones vf_apng_encode writes among them) and plain PNG files to the composited canvas of every frame, on

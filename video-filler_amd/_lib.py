@@ -105,6 +105,7 @@ SIGNATURES = {
     "vf_png_decode_full": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp]),
     "vf_png_workspace_bytes": (i32, [i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_png_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
+    "vf_png_encode_level": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_jpeg_encode_workspace_bytes": (i32, [i32, i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_jpeg_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_jpeg_encode_opts_workspace_bytes": (i32, [i32] * 8 + [C.POINTER(sz), C.POINTER(sz)]),
@@ -115,6 +116,7 @@ SIGNATURES = {
     "vf_gif_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_apng_workspace_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_apng_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
+    "vf_apng_encode_level": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
     "vf_apng_inspect": (i32, [vp, sz, vp, vp, i32, C.c_char_p, i32]),
     "vf_apng_decode_workspace_bytes": (i32, [vp, vp, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
     "vf_apng_decode": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, sz, vp, sz, vp]),

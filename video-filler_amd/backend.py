@@ -452,6 +452,16 @@ def _encoder_bytes(entry, *geometry):
 
 
 PNG_CHUNK = 8192     # filtered bytes per deflate block and IDAT chunk (csrc/vf_png.hip)
+PNG_HIST = 8192      # bytes of a frame's stream before a chunk that level 1's matches may reach into (csrc/vf_png.hip)
+PNG_LEVELS = (0, 1)  # vf_png_encode_level / vf_apng_encode_level: 0 the fast matcher, 1 dense (chained matches over history)
+
+
+def png_level(who, level):
+    """The `level` argument of the PNG and APNG encoders as an int; ValueError naming it for anything but PNG_LEVELS."""
+    import numbers
+    if isinstance(level, bool) or not isinstance(level, numbers.Integral) or level not in PNG_LEVELS:
+        raise ValueError("%s: level=%r is not 0 (fast) or 1 (dense)" % (who, level))
+    return int(level)
 
 
 def png_workspace_bytes(n, H, W, channels):
@@ -1301,14 +1311,19 @@ class HipBackend:
         return out, offsets
 
     # ---- PNG encode (vf_png.hip)
-    def png_encode(self, frames):
+    def png_encode(self, frames, level=0):
         """Encode a batch of frames of one size as PNG files on the device.  frames: device uint8 N x H x W x C (taken as
         they are) or float32 N x C x H x W (through image.savePNG's truncating byte rule inside the filter kernel), C = 1
-        or 3, contiguous.  -> (buffer, offsets): file i is buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8
-        tensor of the upper bound's size, offsets a device int64[N + 1]; both are valid once the stream gets there."""
+        or 3, contiguous.  level 0: vf_png_encode; level 1: the dense matcher of vf_png_encode_level (smaller files, a
+        slower deflate stage; profiling scope png_deflate_dense).  -> (buffer, offsets): file i is
+        buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8 tensor of the upper bound's size, offsets a device
+        int64[N + 1]; both are valid once the stream gets there."""
+        level = png_level("png_encode", level)
         assert frames.dim() == 4 and frames.is_contiguous() and frames.device == self.device
         kind, n, H, W, Cc = _frame_kind(frames)
-        return self._encode("vf_png_encode", "png", frames, n, png_workspace_bytes(n, H, W, Cc), kind, n, H, W, Cc)
+        if level == 0:
+            return self._encode("vf_png_encode", "png", frames, n, png_workspace_bytes(n, H, W, Cc), kind, n, H, W, Cc)
+        return self._encode("vf_png_encode_level", "png", frames, n, png_workspace_bytes(n, H, W, Cc), kind, n, H, W, Cc, level)
 
     # ---- JPEG encode (vf_jpeg_enc.hip, DESIGN.md 5.8)
     def jpeg_encode(self, frames, quality=75, subsampling="420", restart_rows=0, restart_blocks=0, optimize=False, progressive=False):
@@ -1352,16 +1367,20 @@ class HipBackend:
         return self._encode("vf_gif_encode", "gif", clips, g, gif_workspace_bytes(g, n, H, W), kind, g, n, H, W, int(delay))
 
     # ---- APNG encode (vf_png.hip)
-    def apng_encode(self, clips, delay, loop=0):
+    def apng_encode(self, clips, delay, loop=0, level=0):
         """Encode a batch of clips of one geometry as animated PNG files on the device, lossless.  clips: device uint8
         G x N x H x W x C (taken as they are) or float32 G x N x C x H x W (through image.savePNG's truncating byte rule
-        inside the filter kernel), C = 1 or 3, contiguous; delay in centiseconds, loop the number of plays (0: forever).
-        -> (buffer, offsets): file i is buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8 tensor of the upper
+        inside the filter kernel), C = 1 or 3, contiguous; delay in centiseconds, loop the number of plays (0: forever);
+        level as png_encode's (1: vf_apng_encode_level).  -> (buffer, offsets): file i is buffer[offsets[i]:offsets[i+1]]; buffer is a device uint8 tensor of the upper
         bound's size, offsets a device int64[G + 1]; both are valid once the stream gets there."""
+        level = png_level("apng_encode", level)
         assert clips.dim() == 5 and clips.is_contiguous() and clips.device == self.device
         (g, n), (kind, _, H, W, Cc) = clips.shape[:2], _frame_kind(clips.flatten(0, 1))
-        return self._encode("vf_apng_encode", "png", clips, g, apng_workspace_bytes(g, n, H, W, Cc, delay, loop), kind, g, n, H, W, Cc,
-                            int(delay), int(loop))
+        if level == 0:
+            return self._encode("vf_apng_encode", "png", clips, g, apng_workspace_bytes(g, n, H, W, Cc, delay, loop), kind, g, n, H, W,
+                                Cc, int(delay), int(loop))
+        return self._encode("vf_apng_encode_level", "png", clips, g, apng_workspace_bytes(g, n, H, W, Cc, delay, loop), kind, g, n, H, W,
+                            Cc, int(delay), int(loop), level)
 
     # ---- APNG decode (vf_png_decode.hip, DESIGN.md 5.11)
     def apng_decode(self, files, alpha=False, infos=None):

@@ -6,7 +6,9 @@
 //                   codes, the bits, or a stored block if that is not smaller; the chunk's IDAT with its CRC-32, its Adler sums.
 //   k_png_frame_scan / k_vf_file_offsets (vf_block.h) / k_png_pack   chunk and file offsets, the Adler-32 of every frame, the
 //                   files back to back.
-// No window crosses a chunk, so chunks are independent and a file's bytes depend on its own frame only.
+//   k_png_deflate_dense   level 1's deflate stage in k_png_deflate's place: hash chains over the chunk and the 8 KiB of the same
+//                   frame's stream before it, a lazy step, the same parse and coder; level 0's tokens where those code smaller.
+// At level 0 no window crosses a chunk; at level 1 none crosses a frame.  A file's bytes depend on its own frame only.
 #include "vf_block.h"
 #include "vf_common.h"
 
@@ -266,9 +268,7 @@ __device__ unsigned png_block_header(const unsigned char* lens, bool last, unsig
   return bw.pos;
 }
 
-struct DeflateLds {                        // all of k_png_deflate's LDS, in one place so that its size is checked
-  unsigned match[PNG_CHUNK];               // length | distance << 16 | token start << 31
-  unsigned tab[PNG_CHUNK / 4 + 4];         // hash table (position + 1), then tree scratch, then the bit buffer
+struct DeflateTables {                     // the small tables both deflate kernels keep beside their data, match words and scratch
   unsigned freq[320];
   unsigned crc[256];
   unsigned red[8];
@@ -280,118 +280,48 @@ struct DeflateLds {                        // all of k_png_deflate's LDS, in one
   unsigned short cost[256];                // a literal's price, 1/16 bit
   unsigned short seq[320];                 // the two length tables in 16 / 17 / 18 form
   unsigned char len[320];
-  unsigned char data[PNG_CHUNK + 8];
 };
-// 54308 B: three blocks fit a CU's 160 KiB with 916 B to spare.  Anything added here must keep that.
-static_assert(3 * sizeof(DeflateLds) <= 160 * 1024, "k_png_deflate: three blocks per CU no longer fit the LDS");
 
-__global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
-  __shared__ DeflateLds lds;
-  auto& s_data = lds.data;
-  auto& s_match = lds.match;
-  auto& s_tab = lds.tab;
-  auto& s_freq = lds.freq;
-  auto& s_sorted = lds.sorted;
-  auto& s_len = lds.len;
-  auto& s_code = lds.code;
-  auto& s_red = lds.red;
-  auto& s_crc = lds.crc;
-  auto& s_x = lds.x;
-  auto& s_m = lds.m;
-  auto& s_bits = lds.bits;
-  auto& s_cost = lds.cost;
-  auto& s_seq = lds.seq;
-
+// The chunk's Adler sums, from every thread's partial sums over its bytes, to the chunk's meta words.  Ends without a barrier:
+// the next stage's first one orders s_red.
+__device__ __forceinline__ void png_chunk_adler(const PngArgs& a, DeflateTables& t, long long f, int k, unsigned ad_a, unsigned ad_b) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int k = blockIdx.x;
-  const long long f = blockIdx.y;
-  const long long begin = (long long)k * PNG_CHUNK;
-  const int n = (int)min((long long)PNG_CHUNK, a.stream_len - begin);
-  const bool last = k == a.nchunks - 1;
-  const unsigned char* in = a.stream + f * a.stream_len + begin;
-
-  // ---- load, Adler partial sums, clear
-  unsigned ad_a = 0, ad_b = 0;
-  for (int p = tid; p < PNG_CHUNK + 8; p += 256) {
-    const unsigned d = p < n ? in[p] : 0;
-    s_data[p] = (unsigned char)d;
-    ad_a += d;
-    if (p < n) ad_b = (ad_b + (unsigned)(n - p) * d) % ADLER_MOD;
-  }
-  for (int i = tid; i < PNG_CHUNK / 4 + 4; i += 256) s_tab[i] = 0;
-  for (int i = tid; i < 320; i += 256) { s_freq[i] = 0; s_len[i] = 0; s_code[i] = 0; }
   ad_a = wave_sum(ad_a);
   ad_b = wave_sum(ad_b);
-  if (lane == 0) { s_red[wave] = ad_a; s_red[4 + wave] = ad_b; }
+  if (lane == 0) { t.red[wave] = ad_a; t.red[4 + wave] = ad_b; }
   __syncthreads();
   if (tid == 0) {
     unsigned* mt = a.meta + (f * a.nchunks + k) * 4;
-    mt[1] = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) % ADLER_MOD;
-    mt[2] = (s_red[4] + s_red[5] + s_red[6] + s_red[7]) % ADLER_MOD;
+    mt[1] = (t.red[0] + t.red[1] + t.red[2] + t.red[3]) % ADLER_MOD;
+    mt[2] = (t.red[4] + t.red[5] + t.red[6] + t.red[7]) % ADLER_MOD;
   }
+}
 
-  // ---- what a byte costs as a literal, in 1/16 bit: log2(n / count) from the chunk's byte histogram (the leading bit and four
-  // mantissa bits of the ratio), at least one bit.  A match is worth taking only where it beats that: in photographic rows
-  // three-byte repeats at long distances abound and cost more than the literals they replace.
-  for (int p = tid; p < n; p += 256) atomicAdd(&s_freq[s_data[p]], 1u);
+// What a byte costs as a literal, in 1/16 bit: log2(n / count) from the chunk's byte histogram (the leading bit and four
+// mantissa bits of the ratio), at least one bit.  A match is worth taking only where it beats that: in photographic rows
+// three-byte repeats at long distances abound and cost more than the literals they replace.  freq[] is zero on entry and is
+// cleared again; the caller's next barrier orders that.
+__device__ __forceinline__ void png_literal_costs(DeflateTables& t, const unsigned char* s_data, int n) {
+  const int tid = threadIdx.x;
+  for (int p = tid; p < n; p += 256) atomicAdd(&t.freq[s_data[p]], 1u);
   __syncthreads();
   {
-    const unsigned fr = s_freq[tid];
+    const unsigned fr = t.freq[tid];
     unsigned c = 15 * 16;
     if (fr) {
       const unsigned r = ((unsigned)n << 8) / fr;
       const int e = 31 - __clz((int)r);
       c = min(max((unsigned)((e - 8) << 4) + ((r >> (e - 4)) & 15u), 16u), 15u * 16u);
     }
-    s_cost[tid] = (unsigned short)c;
+    t.cost[tid] = (unsigned short)c;
   }
   __syncthreads();
-  for (int i = tid; i < 320; i += 256) s_freq[i] = 0;
+  for (int i = tid; i < 320; i += 256) t.freq[i] = 0;
+}
 
-  // ---- matches.  Positions go through the table 256 at a time: a position sees the latest earlier-batch position with its hash
-  // (atomicMax: by position, not by arrival), and its predecessor (runs).  Each is priced at 8 bits for the length symbol, 5 for
-  // the distance symbol and their extra bits; the one that saves more against the literals it covers wins, the nearer on a tie,
-  // and one that saves less than MATCH_GAIN is dropped.
-  for (int base = 0; base < n; base += 256) {
-    const int p = base + tid;
-    const bool h3 = p + 2 < n;
-    unsigned h = 0, cand = 0;
-    if (h3) {
-      h = ((s_data[p] | (s_data[p + 1] << 8) | (s_data[p + 2] << 16)) * 0x9E3779B1u) >> (32 - HASH_BITS);
-      cand = s_tab[h];
-    }
-    __syncthreads();
-    if (h3) atomicMax(&s_tab[h], (unsigned)(p + 1));
-    if (p < n) {
-      const int maxl = min(MAX_MATCH, n - p);
-      int l1 = 0, l2 = 0;
-      if (cand) {
-        const int q = (int)cand - 1;
-        while (l1 < maxl && s_data[q + l1] == s_data[p + l1]) ++l1;
-      }
-      if (p >= 1)
-        while (l2 < maxl && s_data[p - 1 + l2] == s_data[p + l2]) ++l2;
-      int lit1 = 0, lit2 = 0, acc = 0;
-      for (int i = 0; i < max(l1, l2); ++i) {
-        acc += s_cost[s_data[p + i]];
-        if (i + 1 == l1) lit1 = acc;
-        if (i + 1 == l2) lit2 = acc;
-      }
-      int bl = 0, bd = 0, bg = 0;
-      if (l1 >= MIN_MATCH) {
-        const int g = lit1 - match_cost(l1, p + 1 - (int)cand);
-        if (g >= MATCH_GAIN) { bg = g; bl = l1; bd = p + 1 - (int)cand; }
-      }
-      if (l2 >= MIN_MATCH) {
-        const int g = lit2 - match_cost(l2, 1);
-        if (g >= MATCH_GAIN && (!bl || g >= bg)) { bl = l2; bd = 1; }
-      }
-      s_match[p] = bl ? (unsigned)bl | ((unsigned)bd << 16) : 0u;
-    }
-    __syncthreads();
-  }
-
-  // ---- greedy parse by one wave: 64 positions at a time, up to and including the first match
+// Greedy parse by one wave: 64 positions at a time, up to and including the first match
+__device__ __forceinline__ void png_greedy_parse(unsigned* s_match, int n) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (wave == 0) {
     int pos = 0;
     while (pos < n) {
@@ -405,6 +335,22 @@ __global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
     }
   }
   __syncthreads();
+}
+
+// Everything behind the tokens, for both kernels, in three steps.  png_code_tables: the histograms of the parsed tokens
+// (s_match: length | distance << 16 | token start << 31 per chunk position; s_data: the chunk's n bytes), the two Huffman
+// codes, the block header at the front of the zeroed bit buffer.  s_tab: PNG_CHUNK / 4 + 4 words of scratch (tree scratch,
+// then the bit buffer).  freq[], len[] and code[] are zero on entry.
+__device__ __forceinline__ void png_code_tables(DeflateTables& t, const unsigned char* s_data, const unsigned* s_match, unsigned* s_tab,
+                                                int n, bool last) {
+  auto& s_freq = t.freq;
+  auto& s_sorted = t.sorted;
+  auto& s_len = t.len;
+  auto& s_code = t.code;
+  auto& s_m = t.m;
+  auto& s_bits = t.bits;
+  auto& s_seq = t.seq;
+  const int tid = threadIdx.x;
 
   // ---- histograms
   for (int p = tid; p < n; p += 256) {
@@ -438,9 +384,9 @@ __global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
     const unsigned fr = s_freq[lo + me];
     if (fr) {
       int r = 0;
-      for (int t = 0; t < cnt; ++t) {
-        const unsigned ft = s_freq[lo + t];
-        r += ft && (ft < fr || (ft == fr && t < me));
+      for (int u = 0; u < cnt; ++u) {
+        const unsigned ft = s_freq[lo + u];
+        r += ft && (ft < fr || (ft == fr && u < me));
       }
       s_sorted[lo + r] = (unsigned short)me;
     }
@@ -448,7 +394,7 @@ __global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
   if (tid == 64 || tid == 128) {
     const int lo = tid == 64 ? 0 : DIST0, cnt = tid == 64 ? 286 : 30;
     int m = 0;
-    for (int t = 0; t < cnt; ++t) m += s_freq[lo + t] != 0;
+    for (int u = 0; u < cnt; ++u) m += s_freq[lo + u] != 0;
     s_m[tid == 64 ? 0 : 1] = m;
   }
   __syncthreads();
@@ -469,8 +415,13 @@ __global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
   // ---- the block header
   if (tid == 0) s_bits[0] = png_block_header(s_len, last, s_tab, s_seq);
   __syncthreads();
+}
 
-  // ---- token bits: each thread owns 32 consecutive positions
+// png_token_bits: each thread owns 32 consecutive positions -> the bits of all tokens; tok_at: those before this thread's.
+__device__ __forceinline__ unsigned png_token_bits(DeflateTables& t, const unsigned char* s_data, const unsigned* s_match, int n,
+                                                   unsigned& tok_at) {
+  auto& s_len = t.len;
+  const int tid = threadIdx.x;
   const int p0 = tid * (PNG_CHUNK / 256);
   unsigned mybits = 0;
   for (int p = p0; p < p0 + PNG_CHUNK / 256 && p < n; ++p) {
@@ -488,11 +439,30 @@ __global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
     }
   }
   unsigned tok_bits;
-  const unsigned tok_at = vf_block_excl_scan<unsigned, 256>(mybits, s_red, tok_bits);
-  const unsigned hdr_bits = s_bits[0];
-  const unsigned body_bits = hdr_bits + tok_bits + s_len[256] + (last ? 0u : 3u);   // + the empty stored block's header
-  const unsigned body_bytes = (body_bits + 7) >> 3;
-  const unsigned coded_bytes = body_bytes + (last ? 0u : 4u);
+  tok_at = vf_block_excl_scan<unsigned, 256>(mybits, t.red, tok_bits);
+  return tok_bits;
+}
+
+// the bytes of the chunk's block(s) as coded (header, tokens, end of block, the empty stored block that byte-aligns all but the
+// last chunk); the chunk is coded if that is smaller than its n raw bytes, else stored in 5 + n
+__device__ __forceinline__ unsigned png_coded_bytes(unsigned hdr_bits, unsigned tok_bits, unsigned eob_bits, bool last) {
+  const unsigned body_bits = hdr_bits + tok_bits + eob_bits + (last ? 0u : 3u);   // + the empty stored block's header
+  return ((body_bits + 7) >> 3) + (last ? 0u : 4u);
+}
+
+// png_write_chunk: the bits, or a stored block if that is not smaller; the chunk's IDAT with its CRC-32 in its slot, its size and
+// CRC register in its meta words.
+__device__ __forceinline__ void png_write_chunk(const PngArgs& a, DeflateTables& t, const unsigned char* s_data, const unsigned* s_match,
+                                                unsigned* s_tab, long long f, int k, int n, bool last, unsigned tok_at, unsigned tok_bits) {
+  auto& s_len = t.len;
+  auto& s_code = t.code;
+  auto& s_crc = t.crc;
+  auto& s_x = t.x;
+  const int tid = threadIdx.x;
+  const int p0 = tid * (PNG_CHUNK / 256);
+  const unsigned hdr_bits = t.bits[0];
+  const unsigned coded_bytes = png_coded_bytes(hdr_bits, tok_bits, s_len[256], last);
+  const unsigned body_bytes = coded_bytes - (last ? 0u : 4u);
   const bool coded = coded_bytes < (unsigned)n;        // not smaller than the raw bytes: stored
   const unsigned zh = k == 0 ? 2u : 0u;
   unsigned char* slot = a.slots + (f * a.nchunks + k) * (long long)PNG_SLOT;
@@ -576,11 +546,300 @@ __global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
       mt[3] = s_crc[0];
       if (!last) {
         const unsigned crc = ~s_crc[0];
-        unsigned char* t = slot + 8 + dlen;
-        t[0] = (unsigned char)(crc >> 24); t[1] = (unsigned char)(crc >> 16); t[2] = (unsigned char)(crc >> 8); t[3] = (unsigned char)crc;
+        unsigned char* e = slot + 8 + dlen;
+        e[0] = (unsigned char)(crc >> 24); e[1] = (unsigned char)(crc >> 16); e[2] = (unsigned char)(crc >> 8); e[3] = (unsigned char)crc;
       }
     }
   }
+}
+
+__device__ __forceinline__ void png_code_chunk(const PngArgs& a, DeflateTables& t, const unsigned char* s_data, unsigned* s_match,
+                                               unsigned* s_tab, long long f, int k, int n, bool last) {
+  png_code_tables(t, s_data, s_match, s_tab, n, last);
+  unsigned tok_at;
+  const unsigned tok_bits = png_token_bits(t, s_data, s_match, n, tok_at);
+  png_write_chunk(a, t, s_data, s_match, s_tab, f, k, n, last, tok_at, tok_bits);
+}
+
+// Level 0's matches.  Positions go through the table 256 at a time: a position sees the latest earlier-batch position with its hash
+// (atomicMax: by position, not by arrival), and its predecessor (runs).  Each is priced at 8 bits for the length symbol, 5 for
+// the distance symbol and their extra bits; the one that saves more against the literals it covers wins, the nearer on a tie,
+// and one that saves less than MATCH_GAIN is dropped.  s_tab: the hash table, 1 << HASH_BITS zeroed words; s_data: the chunk's
+// bytes and two readable ones behind them.
+__device__ __forceinline__ void png_match_fast(DeflateTables& t, const unsigned char* s_data, unsigned* s_match, unsigned* s_tab, int n) {
+  auto& s_cost = t.cost;
+  const int tid = threadIdx.x;
+  for (int base = 0; base < n; base += 256) {
+    const int p = base + tid;
+    const bool h3 = p + 2 < n;
+    unsigned h = 0, cand = 0;
+    if (h3) {
+      h = ((s_data[p] | (s_data[p + 1] << 8) | (s_data[p + 2] << 16)) * 0x9E3779B1u) >> (32 - HASH_BITS);
+      cand = s_tab[h];
+    }
+    __syncthreads();
+    if (h3) atomicMax(&s_tab[h], (unsigned)(p + 1));
+    if (p < n) {
+      const int maxl = min(MAX_MATCH, n - p);
+      int l1 = 0, l2 = 0;
+      if (cand) {
+        const int q = (int)cand - 1;
+        while (l1 < maxl && s_data[q + l1] == s_data[p + l1]) ++l1;
+      }
+      if (p >= 1)
+        while (l2 < maxl && s_data[p - 1 + l2] == s_data[p + l2]) ++l2;
+      int lit1 = 0, lit2 = 0, acc = 0;
+      for (int i = 0; i < max(l1, l2); ++i) {
+        acc += s_cost[s_data[p + i]];
+        if (i + 1 == l1) lit1 = acc;
+        if (i + 1 == l2) lit2 = acc;
+      }
+      int bl = 0, bd = 0, bg = 0;
+      if (l1 >= MIN_MATCH) {
+        const int g = lit1 - match_cost(l1, p + 1 - (int)cand);
+        if (g >= MATCH_GAIN) { bg = g; bl = l1; bd = p + 1 - (int)cand; }
+      }
+      if (l2 >= MIN_MATCH) {
+        const int g = lit2 - match_cost(l2, 1);
+        if (g >= MATCH_GAIN && (!bl || g >= bg)) { bl = l2; bd = 1; }
+      }
+      s_match[p] = bl ? (unsigned)bl | ((unsigned)bd << 16) : 0u;
+    }
+    __syncthreads();
+  }
+}
+
+struct DeflateLds {                        // all of k_png_deflate's LDS, in one place so that its size is checked
+  unsigned match[PNG_CHUNK];               // length | distance << 16 | token start << 31
+  unsigned tab[PNG_CHUNK / 4 + 4];         // hash table (position + 1), then tree scratch, then the bit buffer
+  DeflateTables t;
+  unsigned char data[PNG_CHUNK + 8];
+};
+// 54308 B: three blocks fit a CU's 160 KiB with 916 B to spare.  Anything added here must keep that.
+static_assert(3 * sizeof(DeflateLds) <= 160 * 1024, "k_png_deflate: three blocks per CU no longer fit the LDS");
+
+__global__ __launch_bounds__(256) void k_png_deflate(PngArgs a) {
+  __shared__ DeflateLds lds;
+  auto& s_data = lds.data;
+  auto& s_match = lds.match;
+  auto& s_tab = lds.tab;
+
+  const int tid = threadIdx.x;
+  const int k = blockIdx.x;
+  const long long f = blockIdx.y;
+  const long long begin = (long long)k * PNG_CHUNK;
+  const int n = (int)min((long long)PNG_CHUNK, a.stream_len - begin);
+  const bool last = k == a.nchunks - 1;
+  const unsigned char* in = a.stream + f * a.stream_len + begin;
+
+  // ---- load, Adler partial sums, clear
+  unsigned ad_a = 0, ad_b = 0;
+  for (int p = tid; p < PNG_CHUNK + 8; p += 256) {
+    const unsigned d = p < n ? in[p] : 0;
+    s_data[p] = (unsigned char)d;
+    ad_a += d;
+    if (p < n) ad_b = (ad_b + (unsigned)(n - p) * d) % ADLER_MOD;
+  }
+  for (int i = tid; i < PNG_CHUNK / 4 + 4; i += 256) s_tab[i] = 0;
+  for (int i = tid; i < 320; i += 256) { lds.t.freq[i] = 0; lds.t.len[i] = 0; lds.t.code[i] = 0; }
+  png_chunk_adler(a, lds.t, f, k, ad_a, ad_b);
+  png_literal_costs(lds.t, s_data, n);
+
+  png_match_fast(lds.t, s_data, s_match, s_tab, n);
+  png_greedy_parse(s_match, n);
+  png_code_chunk(a, lds.t, s_data, s_match, s_tab, f, k, n, last);
+}
+
+// ------------------------------------------------------------------------------------------------------ deflate, level 1
+// k_png_deflate_dense: k_png_deflate's grid, slots and meta words, with a denser matcher and a lazy step in front of the same
+// parse and coder (tests/png_dense_ref.py is its rule).  The block loads the chunk behind up to PNG_HIST bytes of the same
+// frame's stream before it, the window; chunk 0 has none, and no window reaches into another frame.  Window positions are
+// linked into hash chains: prev of a position is the nearest earlier window position with its hash.  The table goes 256
+// positions at a time: a position takes the table's entry from the batches before (atomicMax: by position, not by arrival) or
+// the nearest lower lane of its own batch with its hash, so the chains are a function of the bytes alone.  A chunk position
+// then tries distance 1 and DENSE_CANDIDATES chain entries, nearest first; only a candidate longer than all before it is
+// priced (k_png_deflate's prices), the best gain of at least MATCH_GAIN wins, and the walk ends at the longest possible length.
+// Lazy step: a match is dropped if the next position holds a longer one.  The Adler sums and the CRC cover the chunk only.
+// Prices are estimates, so these tokens can code larger than level 0's (photographic rows, by a fraction of a percent): the
+// block first codes the chunk with level 0's matcher (png_match_fast), keeps that code's tables, header and size aside, and
+// falls back to it where it is strictly smaller, so no chunk is larger than level 0's.
+constexpr int PNG_HIST = 8192;             // window bytes in front of the chunk (tests/png_dense_ref.py HIST)
+constexpr int DENSE_HASH_BITS = 12;
+constexpr int DENSE_CANDIDATES = 64;
+static_assert(PNG_HIST + PNG_CHUNK <= 32768 && PNG_HIST + PNG_CHUNK < 65535, "distances fit deflate's window, positions + 1 a chain link");
+
+// The LDS plan.  One region of 48 KiB holds, in turn: level 0's hash table and scratch (at its front) and match words (its last
+// 32 KiB); then the chain links (2 B a window position, the first 32 KiB) and the hash heads (the last 16 KiB); then the match
+// words again (4 B a chunk position, the last 32 KiB), which grow over links that are done with: the match words of chunk
+// position p lie on the links of chunk positions 2p and 2p + 1, chains only run backwards, and the chunk's positions are
+// matched from its end, 256 at a time with a barrier between a batch's walks and its stores, so a store only covers links of
+// positions at or behind its own batch.  Last, the front of the region is scratch and bit buffer again.
+struct DenseLds {                          // all of k_png_deflate_dense's LDS
+  unsigned region[(PNG_HIST + PNG_CHUNK) / 2 + PNG_CHUNK / 2];
+  DeflateTables t;
+  unsigned alt_hdr[144];                   // level 0's code of the chunk, kept for the fallback: the header's bits (4498 at most),
+  unsigned alt_bits;                       // their number,
+  unsigned short alt_code[320];            // the codes
+  unsigned char alt_len[320];              // and their lengths
+  unsigned short hb[256];                  // the hashes of the batch being linked
+  unsigned char data[PNG_HIST + PNG_CHUNK + 8];
+};
+// 72 728 B: two blocks per CU (160 KiB).  With the match words beside the links (32 + 32 KiB, 89 112 B, one block per CU) the
+// kernel took 118.1 ms for 120 frames of 384 x 512 x 3 on an MI355X; see DESIGN.md 5.3 for this layout's time.
+static_assert(2 * sizeof(DenseLds) <= 160 * 1024, "k_png_deflate_dense: two blocks per CU no longer fit the LDS");
+static_assert(PNG_HIST == PNG_CHUNK, "the overlay of match words and links assumes a history of 0 or PNG_CHUNK bytes");
+static_assert((1 << DENSE_HASH_BITS) * 4 <= PNG_CHUNK * 2, "the hash heads live behind the links");
+
+__global__ __launch_bounds__(256) void k_png_deflate_dense(PngArgs a) {
+  __shared__ DenseLds lds;
+  auto& s_cost = lds.t.cost;
+  unsigned short* s_prev = (unsigned short*)lds.region;      // [PNG_HIST + PNG_CHUNK]
+  unsigned* s_head = lds.region + (PNG_HIST + PNG_CHUNK) / 2;   // [1 << DENSE_HASH_BITS]
+  unsigned* s_match = lds.region + PNG_CHUNK / 2;            // [PNG_CHUNK]
+  unsigned* s_tab = lds.region;                              // [PNG_CHUNK / 4 + 4]
+
+  const int tid = threadIdx.x;
+  const int k = blockIdx.x;
+  const long long f = blockIdx.y;
+  const long long begin = (long long)k * PNG_CHUNK;
+  const int n = (int)min((long long)PNG_CHUNK, a.stream_len - begin);
+  const int h0 = (int)min((long long)PNG_HIST, begin);       // history bytes: the same frame's only
+  const int m = h0 + n;                                      // window bytes
+  const bool last = k == a.nchunks - 1;
+  const unsigned char* in = a.stream + f * a.stream_len + begin - h0;
+  unsigned char* s_win = lds.data;                           // the window
+  unsigned char* s_data = lds.data + h0;                     // the chunk
+
+  // ---- load, Adler partial sums over the chunk, clear
+  unsigned ad_a = 0, ad_b = 0;
+  for (int i = tid; i < PNG_HIST + PNG_CHUNK + 8; i += 256) {
+    const unsigned d = i < m ? in[i] : 0;
+    s_win[i] = (unsigned char)d;
+    if (i >= h0 && i < m) {
+      ad_a += d;
+      ad_b = (ad_b + (unsigned)(m - i) * d) % ADLER_MOD;
+    }
+  }
+  for (int i = tid; i < PNG_CHUNK / 4 + 4; i += 256) s_tab[i] = 0;
+  for (int i = tid; i < 320; i += 256) { lds.t.freq[i] = 0; lds.t.len[i] = 0; lds.t.code[i] = 0; }
+  png_chunk_adler(a, lds.t, f, k, ad_a, ad_b);
+  png_literal_costs(lds.t, s_data, n);
+
+  // ---- level 0's tokens and their code, kept aside
+  png_match_fast(lds.t, s_data, s_match, s_tab, n);
+  png_greedy_parse(s_match, n);
+  png_code_tables(lds.t, s_data, s_match, s_tab, n, last);
+  unsigned tok_at0;
+  const unsigned tok_bits0 = png_token_bits(lds.t, s_data, s_match, n, tok_at0);
+  const unsigned coded0 = png_coded_bytes(lds.t.bits[0], tok_bits0, lds.t.len[256], last);
+  const unsigned bytes0 = coded0 < (unsigned)n ? coded0 : 5u + (unsigned)n;
+  for (int i = tid; i < 144; i += 256) lds.alt_hdr[i] = s_tab[i];
+  for (int i = tid; i < 320; i += 256) { lds.alt_code[i] = lds.t.code[i]; lds.alt_len[i] = lds.t.len[i]; }
+  if (tid == 0) lds.alt_bits = lds.t.bits[0];
+  __syncthreads();
+  for (int i = tid; i < (int)(sizeof(lds.region) / 4); i += 256) lds.region[i] = 0;      // links: none; heads: none
+  for (int i = tid; i < 320; i += 256) { lds.t.freq[i] = 0; lds.t.len[i] = 0; lds.t.code[i] = 0; }
+  __syncthreads();
+
+  // ---- chains over the window's hashed positions (those with two bytes behind them in the window)
+  const int nh = m - 2;
+  for (int base = 0; base < nh; base += 256) {
+    const int i = base + tid;
+    const bool on = i < nh;
+    unsigned h = 0xFFFFu, link = 0;
+    if (on) {
+      h = ((s_win[i] | (s_win[i + 1] << 8) | (s_win[i + 2] << 16)) * 0x9E3779B1u) >> (32 - DENSE_HASH_BITS);
+      link = s_head[h];
+    }
+    lds.hb[tid] = (unsigned short)h;
+    __syncthreads();
+    if (on) {
+      atomicMax(&s_head[h], (unsigned)(i + 1));
+      for (int j = tid - 1; j >= 0; j -= 8) {                // the nearest lower lane with this hash, eight lanes at a time
+        unsigned hit = 0;
+#pragma unroll
+        for (int u = 7; u >= 0; --u)
+          if (j - u >= 0 && lds.hb[j - u] == h) hit = (unsigned)(j - u + 1);
+        if (hit) { link = (unsigned)base + hit; break; }
+      }
+      s_prev[i] = (unsigned short)link;
+    }
+    __syncthreads();
+  }
+
+  // ---- matches of the chunk's positions, 256 at a time from the chunk's end (see DenseLds)
+  for (int base = (n - 1) & ~255; base >= 0; base -= 256) {
+    const int p = base + tid;
+    unsigned mw = 0;
+    if (p < n) {
+      const int i = h0 + p, maxl = min(MAX_MATCH, n - p);
+      int bl = 0, bd = 0, bg = 0, longest = 0, acc = 0;      // acc: the price of the first `longest` bytes as literals
+      unsigned link = s_prev[i];
+      for (int c = 0; c <= DENSE_CANDIDATES; ++c) {
+        int q;
+        if (c == 0) {
+          if (i < 1) continue;
+          q = i - 1;
+        } else {
+          if (!link) break;
+          q = (int)link - 1;
+          link = s_prev[q];
+        }
+        if (s_win[q + longest] != s_win[i + longest]) continue;   // cannot be longer
+        int l = 0;
+        while (l < maxl && s_win[q + l] == s_win[i + l]) ++l;
+        if (l <= longest) continue;
+        for (int u = longest; u < l; ++u) acc += s_cost[s_win[i + u]];
+        longest = l;
+        if (l >= MIN_MATCH) {
+          const int g = acc - match_cost(l, i - q);
+          if (g >= MATCH_GAIN && g > bg) { bg = g; bl = l; bd = i - q; }
+        }
+        if (l >= maxl) break;
+      }
+      mw = bl ? (unsigned)bl | ((unsigned)bd << 16) : 0u;
+    }
+    __syncthreads();
+    if (p < n) s_match[p] = mw;
+  }
+  __syncthreads();
+
+  // ---- lazy step: thread t owns positions t, t + 256, ...; all are read before any is dropped
+  unsigned drop = 0;
+  for (int r = 0; r < PNG_CHUNK / 256; ++r) {
+    const int p = r * 256 + tid;
+    if (p + 1 < n) {
+      const unsigned l0 = s_match[p] & 0x1FFu, l1 = s_match[p + 1] & 0x1FFu;
+      if (l0 && l1 > l0) drop |= 1u << r;
+    }
+  }
+  __syncthreads();
+  for (int r = 0; r < PNG_CHUNK / 256; ++r)
+    if (drop & (1u << r)) s_match[r * 256 + tid] = 0;
+  __syncthreads();
+
+  png_greedy_parse(s_match, n);
+  png_code_tables(lds.t, s_data, s_match, s_tab, n, last);
+  unsigned tok_at;
+  unsigned tok_bits = png_token_bits(lds.t, s_data, s_match, n, tok_at);
+  const unsigned coded1 = png_coded_bytes(lds.t.bits[0], tok_bits, lds.t.len[256], last);
+  const unsigned bytes1 = coded1 < (unsigned)n ? coded1 : 5u + (unsigned)n;
+
+  // ---- fallback (the same for the whole block): level 0's tokens again, behind the code kept aside
+  if (bytes0 < bytes1) {
+    __syncthreads();
+    for (int i = tid; i < PNG_CHUNK / 4 + 4; i += 256) s_tab[i] = 0;
+    __syncthreads();
+    png_match_fast(lds.t, s_data, s_match, s_tab, n);
+    png_greedy_parse(s_match, n);
+    for (int i = tid; i < PNG_CHUNK / 4 + 4; i += 256) s_tab[i] = i < 144 ? lds.alt_hdr[i] : 0u;
+    for (int i = tid; i < 320; i += 256) { lds.t.code[i] = lds.alt_code[i]; lds.t.len[i] = lds.alt_len[i]; }
+    if (tid == 0) lds.t.bits[0] = lds.alt_bits;
+    __syncthreads();
+    tok_at = tok_at0;
+    tok_bits = tok_bits0;
+  }
+  png_write_chunk(a, lds.t, s_data, s_match, s_tab, f, k, n, last, tok_at, tok_bits);
 }
 
 // --------------------------------------------------------------------------------------------------------------- pack
@@ -876,13 +1135,27 @@ VF_API int vf_apng_workspace_bytes(int g, int n, int H, int W, int C, int delay,
   return 0;
 }
 
-VF_API int vf_apng_encode(vf_ctx* ctx, const void* src, int kind, int g, int n, int H, int W, int C, int delay, int loop, void* ws,
-                          size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
+namespace {
+
+// level 0: k_png_deflate; level 1: k_png_deflate_dense.  Every other stage is the same for both.
+int png_check_level(const char* who, int level) {
+  VF_REQUIRE(level == 0 || level == 1, "%s: level: %d (0: the fast matcher; 1: dense, chained matches over history)", who, level);
+  return 0;
+}
+
+void png_launch_deflate(vf_ctx* ctx, int level, double stream, dim3 grid, const PngArgs& a) {
+  if (level == 0) VF_LAUNCH_TIMED(ctx, "png_deflate", 0.0, 2.0 * stream, k_png_deflate, grid, dim3(256), a);
+  else VF_LAUNCH_TIMED(ctx, "png_deflate_dense", 0.0, 3.0 * stream, k_png_deflate_dense, grid, dim3(256), a);
+}
+
+int apng_encode(const char* who, vf_ctx* ctx, const void* src, int kind, int g, int n, int H, int W, int C, int delay, int loop, int level,
+                void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
   ApngPlan p;
-  if (int e = apng_plan("vf_apng_encode", g, n, H, W, C, delay, loop, &p)) return e;
+  if (int e = png_check_level(who, level)) return e;
+  if (int e = apng_plan(who, g, n, H, W, C, delay, loop, &p)) return e;
   char batch[80];
   snprintf(batch, sizeof(batch), "%d clips of %d frames of %dx%dx%d", g, n, H, W, C);
-  if (int e = vf_check_encode_entry("vf_apng_encode", kind, "C", batch, ws_bytes, p.ws_bytes, out_cap, p.out_bytes)) return e;
+  if (int e = vf_check_encode_entry(who, kind, "C", batch, ws_bytes, p.ws_bytes, out_cap, p.out_bytes)) return e;
   ApngArgs A;
   PngArgs& a = A.p;
   a.src = src;
@@ -912,7 +1185,7 @@ VF_API int vf_apng_encode(vf_ctx* ctx, const void* src, int kind, int g, int n, 
     if (kind == 0) VF_LAUNCH_TIMED(ctx, "png_filter", 0.0, 8.0 * px + stream, k_png_filter<0>, dim3(H, m), dim3(256), s);
     else VF_LAUNCH_TIMED(ctx, "png_filter", 0.0, 2.0 * px + stream, k_png_filter<1>, dim3(H, m), dim3(256), s);
     VF_LAUNCH_CHECK();
-    VF_LAUNCH_TIMED(ctx, "png_deflate", 0.0, 2.0 * stream, k_png_deflate, dim3((unsigned)nchunks, m), dim3(256), s);
+    png_launch_deflate(ctx, level, stream, dim3((unsigned)nchunks, m), s);
     VF_LAUNCH_CHECK();
   }
   {
@@ -937,6 +1210,18 @@ VF_API int vf_apng_encode(vf_ctx* ctx, const void* src, int kind, int g, int n, 
   return 0;
 }
 
+}  // namespace
+
+VF_API int vf_apng_encode(vf_ctx* ctx, const void* src, int kind, int g, int n, int H, int W, int C, int delay, int loop, void* ws,
+                          size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
+  return apng_encode("vf_apng_encode", ctx, src, kind, g, n, H, W, C, delay, loop, 0, ws, ws_bytes, out, out_cap, offsets);
+}
+
+VF_API int vf_apng_encode_level(vf_ctx* ctx, const void* src, int kind, int g, int n, int H, int W, int C, int delay, int loop, int level,
+                                void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets) {
+  return apng_encode("vf_apng_encode_level", ctx, src, kind, g, n, H, W, C, delay, loop, level, ws, ws_bytes, out, out_cap, offsets);
+}
+
 VF_API int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, size_t* out_bytes) {
   PngPlan p;
   if (int e = png_plan("vf_png_workspace_bytes", n, H, W, C, &p)) return e;
@@ -945,13 +1230,16 @@ VF_API int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, 
   return 0;
 }
 
-VF_API int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, void* ws, size_t ws_bytes,
-                         unsigned char* out, size_t out_cap, int64_t* offsets) {
+namespace {
+
+int png_encode(const char* who, vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int level, void* ws, size_t ws_bytes,
+               unsigned char* out, size_t out_cap, int64_t* offsets) {
   PngPlan p;
-  if (int e = png_plan("vf_png_encode", n, H, W, C, &p)) return e;
+  if (int e = png_check_level(who, level)) return e;
+  if (int e = png_plan(who, n, H, W, C, &p)) return e;
   char batch[64];
   snprintf(batch, sizeof(batch), "%d frames of %dx%dx%d", n, H, W, C);
-  if (int e = vf_check_encode_entry("vf_png_encode", kind, "C", batch, ws_bytes, p.ws_bytes, out_cap, p.out_bytes)) return e;
+  if (int e = vf_check_encode_entry(who, kind, "C", batch, ws_bytes, p.ws_bytes, out_cap, p.out_bytes)) return e;
   PngArgs a;
   a.src = src;
   a.stream = (unsigned char*)ws + p.o_stream;
@@ -967,7 +1255,7 @@ VF_API int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, i
   if (kind == 0) VF_LAUNCH_TIMED(ctx, "png_filter", 0.0, 8.0 * px + stream, k_png_filter<0>, dim3(H, n), dim3(256), a);
   else VF_LAUNCH_TIMED(ctx, "png_filter", 0.0, 2.0 * px + stream, k_png_filter<1>, dim3(H, n), dim3(256), a);
   VF_LAUNCH_CHECK();
-  VF_LAUNCH_TIMED(ctx, "png_deflate", 0.0, 2.0 * stream, k_png_deflate, dim3((unsigned)p.nchunks, n), dim3(256), a);
+  png_launch_deflate(ctx, level, stream, dim3((unsigned)p.nchunks, n), a);
   VF_LAUNCH_CHECK();
   {
     VfProf prof(ctx, "png_pack", 0.0, 2.0 * stream);
@@ -979,4 +1267,16 @@ VF_API int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, i
     VF_LAUNCH_CHECK();
   }
   return 0;
+}
+
+}  // namespace
+
+VF_API int vf_png_encode(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, void* ws, size_t ws_bytes,
+                         unsigned char* out, size_t out_cap, int64_t* offsets) {
+  return png_encode("vf_png_encode", ctx, src, kind, n, H, W, C, 0, ws, ws_bytes, out, out_cap, offsets);
+}
+
+VF_API int vf_png_encode_level(vf_ctx* ctx, const void* src, int kind, int n, int H, int W, int C, int level, void* ws, size_t ws_bytes,
+                               unsigned char* out, size_t out_cap, int64_t* offsets) {
+  return png_encode("vf_png_encode_level", ctx, src, kind, n, H, W, C, level, ws, ws_bytes, out, out_cap, offsets);
 }

@@ -335,15 +335,19 @@ def _as_frames(who, frames, ndim):
 
 
 # ------------------------------------------------------------------------------------------------- PNG
-def encode_png(frames):
+def encode_png(frames, level=0):
     """image.save of a batch of frames as PNG, encoded on the device in one call (vf_png_encode): a list of `bytes`, one
     whole PNG file per frame.  frames: uint8 N x H x W x C (stored as they are) or float N x C x H x W (image.savePNG's
     rule: saturated to [0,1], times 255 in float32, truncated); C = 1 (grey) or 3 (RGB); host or device.  Decoding a
-    file gives exactly those bytes; the file bytes depend on the frame alone and are the same on every run.  One
-    device-to-host copy brings the batch back."""
+    file gives exactly those bytes; the file bytes depend on the frame alone and are the same on every run.  level: 0, the
+    fast encoder, or 1, "dense" (vf_png_encode_level): chained matches over the chunk and the 8 KiB of the
+    frame's stream before it, about half the bytes on smooth frames for a slower deflate stage; anything else is a
+    ValueError naming `level`.  One device-to-host copy brings the batch back."""
+    from .backend import png_level
+    level = png_level("encode_png", level)
     t = _as_frames("encode_png", frames, 4)
     B = get_backend()
-    return _files_from(*B.png_encode(B.from_host(t).contiguous()))
+    return _files_from(*B.png_encode(B.from_host(t).contiguous(), level))
 
 
 # ------------------------------------------------------------------------------------------------ JPEG (DESIGN 5.8)
@@ -408,15 +412,18 @@ def encode_gif(clips, delay=10):
 
 
 # ------------------------------------------------------------------------------------------------ APNG
-def encode_apng(clips, delay=10, loop=0):
+def encode_apng(clips, delay=10, loop=0, level=0):
     """A batch of clips as animated PNG files, lossless, encoded on the device in one call (vf_apng_encode): a list of
     `bytes`, one whole APNG file per clip, `delay` centiseconds a frame, played `loop` times (0: forever).  clips: uint8
     G x N x H x W x C (taken as they are) or float G x N x C x H x W (image.savePNG's rule); C = 1 (grey) or 3 (RGB); a
     4-D input is one clip; host or device.  The file is what tests/apng_ref.py assembles from the N files encode_png
     writes for the clip's frames: every frame is its own zlib stream, frame 0 in IDAT chunks — the file is
     also a PNG of frame 0 — and the others in fdAT chunks; no frame differencing.  Decoding gives exactly the frames'
-    bytes; a file's bytes depend on its frames, delay and loop alone and are the same on every run.  One device-to-host
-    copy brings the batch back."""
+    bytes; a file's bytes depend on its frames, delay and loop alone and are the same on every run.  level is
+    encode_png's: the file is assembled from the frames' files of that level.  One device-to-host copy brings the batch
+    back."""
+    from .backend import png_level
+    level = png_level("encode_apng", level)
     t = torch.as_tensor(clips)
     t = _as_frames("encode_apng", t.unsqueeze(0) if t.dim() == 4 else t, 5)
     if int(delay) != delay or not 0 <= delay <= 65535:
@@ -424,7 +431,7 @@ def encode_apng(clips, delay=10, loop=0):
     if int(loop) != loop or not 0 <= loop <= 65535:
         raise ValueError("encode_apng: loop=%r is not a whole number of plays from 0 to 65535 (0: forever)" % (loop,))
     B = get_backend()
-    return _files_from(*B.apng_encode(B.from_host(t).contiguous(), int(delay), int(loop)))
+    return _files_from(*B.apng_encode(B.from_host(t).contiguous(), int(delay), int(loop), level))
 
 
 def apng_info(item):

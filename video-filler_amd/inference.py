@@ -152,15 +152,18 @@ def _save_frame_groups(who, ext, encode, dirname, outImages, inpaintImages, full
     return _write_files(paths, encode(torch.cat(ts, 0)))
 
 
-def save_frames(dirname, outImages=None, inpaintImages=None, fullImages=None, **named):
+def save_frames(dirname, outImages=None, inpaintImages=None, fullImages=None, level=0, **named):
     """test_vid_wholeim.lua:226-242 (and test_more_complex.lua:200-214): `image.save` of every frame of the three results
     of WholeImageInpainter as dirname/pred_%d.png, inpaint_%d.png and orig_%d.png, numbered from 1.  The directory is
     created; all 3 * predLen frames are encoded on the device in ONE call (data.encode_png) and the host only writes
     the files.  Tensors are predLen x nc x H x W in [0,1] (image.savePNG's truncating byte rule applies), or uint8
     predLen x H x W x nc.  Other prefixes go by keyword: save_frames(dirname, pred=out_pred) is test_vid.lua:138's
-    pred_i.png.  Returns the paths, in the order pred, inpaint, orig (then the keywords'), frames innermost."""
+    pred_i.png.  level is encode_png's (1: the dense encoder, smaller files).  Returns the paths, in the order pred, inpaint,
+    orig (then the keywords'), frames innermost."""
+    from .backend import png_level
     from .data import encode_png
-    return _save_frame_groups("save_frames", "png", encode_png, dirname, outImages, inpaintImages, fullImages, named)
+    level = png_level("save_frames", level)      # refused before the directory is made
+    return _save_frame_groups("save_frames", "png", lambda t: encode_png(t, level), dirname, outImages, inpaintImages, fullImages, named)
 
 
 def save_frames_jpg(dirname, outImages=None, inpaintImages=None, fullImages=None, quality=75, subsampling="420", restart_rows=0,
@@ -207,15 +210,17 @@ def save_gifs(name, outImages=None, inpaintImages=None, fullImages=None, delay=1
     return _write_files(["%s_%s.gif" % (name, key) for key in keys], files)
 
 
-def save_apngs(name, outImages=None, inpaintImages=None, fullImages=None, delay=10, **named):
+def save_apngs(name, outImages=None, inpaintImages=None, fullImages=None, delay=10, level=0, **named):
     """save_gifs without its loss: name_result.png, name_inpaint.png, name_orig.png and name_<key>.png as animated PNG
     files, all clips encoded on the device in ONE call (data.encode_apng); the host only writes the files.
     Tensors are predLen x C x H x W in [0,1] (image.savePNG's truncating byte rule applies) or uint8 predLen x H x W x C,
     C = 1 or 3.  Every frame keeps its exact bytes, and unlike save_gifs the clip holds ALL predLen frames: the frame
     save_gifs drops is a quirk of the reference's `convert` loop, and no reference command writes these files.  Each file
-    is also a plain PNG of its first frame, and loops forever.  The parent directory is created.  Returns the paths, in the order result,
-    inpaint, orig, then the keywords'."""
+    is also a plain PNG of its first frame, and loops forever.  level is encode_apng's.  The parent directory is created.
+    Returns the paths, in the order result, inpaint, orig, then the keywords'."""
     import os
+    from .backend import png_level
+    level = png_level("save_apngs", level)
     groups = [(p, t) for p, t in (("result", outImages), ("inpaint", inpaintImages), ("orig", fullImages)) if t is not None]
     groups += list(named.items())
     if not groups:
@@ -228,7 +233,7 @@ def save_apngs(name, outImages=None, inpaintImages=None, fullImages=None, delay=
         raise ValueError("save_apngs: the clips of one call are 4-D and share one type, length and frame size")
     from .data import encode_apng
     B = get_backend()
-    files = encode_apng(torch.stack([B.from_host(t) for t in ts]), delay)
+    files = encode_apng(torch.stack([B.from_host(t) for t in ts]), delay, level=level)
     os.makedirs(os.path.dirname(os.path.abspath(name)), exist_ok=True)
     return _write_files(["%s_%s.png" % (name, key) for key in keys], files)
 
@@ -368,12 +373,14 @@ def load_demo_images(images, inputSize=128):
     return out
 
 
-def save_sheet(path, x, **display_args):
+def save_sheet(path, x, level=0, **display_args):
     """image.save(path, image.toDisplayTensor(x, ...)) (test.lua:129, demo.lua:96): display_tensor, data.encode_png of the
     one grid (image.savePNG's byte rule is applied inside the encoder; no byte copy of the sheet is made), then the file
-    is written.  Returns path."""
+    is written; level is encode_png's.  Returns path."""
+    from .backend import png_level
+    level = png_level("save_sheet", level)
     grid = display_tensor(x, **display_args)
-    (png,) = data.encode_png(grid.unsqueeze(0))
+    (png,) = data.encode_png(grid.unsqueeze(0), level)
     with open(path, "wb") as fh:
         fh.write(png)
     return path
@@ -391,11 +398,13 @@ def display_jpeg(x, quality=75, restart_rows=0, restart_blocks=0, optimize=False
     return jpg
 
 
-def save_clip_sheet(path, input_image, pred_image):
+def save_clip_sheet(path, input_image, pred_image, level=0):
     """test_vid.lua:131-137,149: pretty_output[2i-1] = input_image[i], pretty_output[2i] = pred_image[i] (predict_clip's two
-    results, predLen x nc x fs x fs in [0,1]), saved as toDisplayTensor(pretty_output, 0, 10)."""
+    results, predLen x nc x fs x fs in [0,1]), saved as toDisplayTensor(pretty_output, 0, 10); level is save_sheet's."""
+    from .backend import png_level
+    level = png_level("save_clip_sheet", level)
     B = get_backend()
     a, b = B.from_host(torch.as_tensor(input_image)).float(), B.from_host(torch.as_tensor(pred_image)).float()
     assert a.dim() == 4 and a.shape == b.shape, "input_image and pred_image are predLen x nc x fs x fs"
     pretty = torch.stack([a, b], 1).reshape(2 * a.shape[0], *a.shape[1:])
-    return save_sheet(path, pretty, padding=0, nrow=10)
+    return save_sheet(path, pretty, level=level, padding=0, nrow=10)

@@ -151,8 +151,10 @@ int vf_png_decode_full_workspace_bytes(const unsigned char* data, const int64_t*
 int vf_png_decode_full(vf_ctx*, const unsigned char* data, const int64_t* offs, int n, int channels, int out_kind, const int64_t* out_offs, void* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes, int32_t* status);
 int vf_png_workspace_bytes(int n, int H, int W, int C, size_t* ws_bytes, size_t* out_bytes);
 int vf_png_encode(vf_ctx*, const void* src, int kind, int n, int H, int W, int C, void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
+int vf_png_encode_level(vf_ctx*, const void* src, int kind, int n, int H, int W, int C, int level, void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
 int vf_apng_workspace_bytes(int g, int n, int H, int W, int C, int delay, int loop, size_t* ws_bytes, size_t* out_bytes);
 int vf_apng_encode(vf_ctx*, const void* src, int kind, int g, int n, int H, int W, int C, int delay, int loop, void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
+int vf_apng_encode_level(vf_ctx*, const void* src, int kind, int g, int n, int H, int W, int C, int delay, int loop, int level, void* ws, size_t ws_bytes, unsigned char* out, size_t out_cap, int64_t* offsets);
 int vf_apng_inspect(const unsigned char* data, size_t len, int64_t* info, int64_t* frames, int frame_cap, char* reason, int reason_cap);
 int vf_apng_decode_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int alpha, size_t* ws_bytes, size_t* stage_bytes);
 int vf_apng_decode(vf_ctx*, const unsigned char* data, const int64_t* offs, int n, int alpha, const int64_t* out_offs, unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes, int32_t* status);
