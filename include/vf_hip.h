@@ -550,7 +550,9 @@ int vf_png_decode_workspace_bytes(const unsigned char* data, const int64_t* offs
  * VF_PNG_* per image.  The host checks the CRCs, concatenates each file's IDAT payloads (minus the two zlib header
  * bytes) and packs them with PLTE / tRNS and a descriptor per image into stage (caller-owned, >= stage_bytes), and
  * enqueues one upload into ws (caller-owned DEVICE memory, >= ws_bytes) and three launches; stage must stay untouched
- * until the stream reaches this call's work.  Nothing is allocated and nothing synchronises. */
+ * until the stream reaches this call's work.  Nothing is allocated and nothing synchronises.  This is the pipeline of
+ * vf_png_decode_full below under the default rule with out_kind 0: the same descriptor and kernels, a file being the
+ * one-pass case; the profiling labels are pngd_inflate, pngd_unfilter, pngd_expand. */
 int vf_png_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, const int64_t* out_offs,
                   unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes, int32_t* status);
 /* image.load(path, nc, 'float') on top of the decoded bytes: dst[i] = src[i] / 255 in float32, an IEEE division
@@ -574,9 +576,11 @@ int vf_png_inspect_full(const unsigned char* data, size_t len, int64_t* info, in
 /* vf_png_decode_workspace_bytes and vf_png_decode under the full rule, with one more parameter.  out_kind 0: image i
  * becomes uint8 H x W x C; 1: float32 H x W x C written by the expansion kernel, byte / 255 for files of up to 8 bits
  * (the bits of vf_png_bytes_to_float) and sample / 65535 for 16-bit files, both IEEE divisions.  out_offs counts
- * ELEMENTS of out (bytes or floats).  Files vf_png_decode takes may be in the batch and give its bytes.  The same
- * contract otherwise: host files, one upload, three launches (inflate; unfilter, one wave per image and pass; expand),
- * nothing allocated, nothing synchronised, VF_PNG_* per image in status. */
+ * ELEMENTS of out (bytes or floats).  Files vf_png_decode takes may be in the batch and give its bytes, and a batch of
+ * such files with out_kind 0 needs exactly the sizes vf_png_decode_workspace_bytes returns.  The same contract
+ * otherwise: host files, one upload, three launches (inflate; unfilter, one wave per image and pass; expand; the
+ * profiling labels are pngd_inflate, pngd_unfilter_full, pngd_expand_full), nothing allocated, nothing synchronised,
+ * VF_PNG_* per image in status. */
 int vf_png_decode_full_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int channels, int out_kind,
                                        size_t* ws_bytes, size_t* stage_bytes);
 int vf_png_decode_full(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int out_kind,

@@ -13,7 +13,7 @@ import video_filler_amd  # noqa: F401
 from video_filler_amd.backend import (png_decode_full_workspace_bytes, png_decode_workspace_bytes, png_inspect,
                                       png_inspect_full)
 
-DESCRIPTOR = 1232      # sizeof(PngdFull), as DESIGN.md 5.6 states it
+DESCRIPTOR = 1232      # sizeof(PngdImage), as DESIGN.md 5.6 states it
 up256 = lambda v: (v + 255) // 256 * 256
 
 
@@ -43,10 +43,22 @@ def test_workspace_arithmetic(channels, out_kind):
         assert png_decode_full_workspace_bytes([f], channels, out_kind) == _sizes([f], channels, out_kind)
 
 
-def test_plain_files_need_what_the_default_entry_needs_but_for_the_descriptor():
-    f = cases.write_png(cases.random_pixels(33, 70, 0, 4, 2), 0, 4, False)
-    (a, sa), (b, sb) = png_decode_full_workspace_bytes([f]), png_decode_workspace_bytes([f])
-    assert a - b == sa - sb == up256(DESCRIPTOR) - up256(1112)
+def test_plain_files_need_what_the_default_entry_needs():
+    """both entries count the one descriptor: equal sizes for plain 8-bit files, also where up256(1112 n) and
+    up256(1232 n), the two descriptors there once were, differ (n = 3, 7)"""
+    plain = [cases.write_png(cases.random_pixels(33, 70, 0, 4, 2), 0, 4, False),                   # expanded
+             cases.write_png(cases.random_pixels(9, 17, 2, 8, 1), 2, 8, False),                     # direct with the file's channels
+             cases.write_png(cases.random_pixels(5, 4, 3, 2, 3), 3, 2, False, plte=cases.palette(2)),
+             cases.write_png(cases.random_pixels(70, 3, 4, 8, 4), 4, 8, False),
+             cases.write_png(cases.random_pixels(1, 1, 0, 8, 5), 0, 8, False),
+             cases.write_png(cases.random_pixels(8, 8, 6, 8, 6), 6, 8, False),
+             cases.write_png(cases.random_pixels(17, 23, 0, 1, 7), 0, 1, False)]
+    assert up256(1112 * 3) != up256(1232 * 3) and up256(1112 * 7) != up256(1232 * 7)
+    for n in (1, 3, 7):
+        for channels in (None, 3):
+            files = plain[:n]
+            full, default = png_decode_full_workspace_bytes(files, channels, 0), png_decode_workspace_bytes(files, channels)
+            assert default == full == _sizes(files, channels, 0), (n, channels)
 
 
 def _header_only(W, H, depth, ct, lace):

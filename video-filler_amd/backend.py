@@ -340,20 +340,26 @@ _PNG_INFO_KEYS = ("width", "height", "bit_depth", "color_type", "interlace", "ch
                   "trns_entries", "supported", "inflated_bytes")
 
 
-def png_inspect(data):
-    """The host-only chunk walk of one PNG file (vf_png_inspect; no GPU needed) -> dict(width, height, bit_depth,
-    color_type, interlace, channels, idat_bytes, idat_chunks, palette_entries, trns_entries, supported, inflated_bytes,
-    reason).  channels: what image.load(path) gives after expansion (1 - 4).  Raises ValueError for a malformed file."""
+def _png_inspect(entry, data, *geo):
+    """One host-only inspect entry of the PNG decoder -> the dict of _PNG_INFO_KEYS and reason.  geo: what the entry takes
+    between info and reason.  Raises ValueError for a malformed file."""
     lib = _lib.load()
     data = bytes(data)
     info = (C.c_int64 * 12)()
     why = C.create_string_buffer(160)
-    if lib.vf_png_inspect(data, len(data), info, why, 160) != 0:
+    if getattr(lib, entry)(data, len(data), info, *geo, why, 160) != 0:
         raise ValueError(lib.vf_last_error().decode())
     d = {k: int(v) for k, v in zip(_PNG_INFO_KEYS, info)}
     d["supported"] = bool(d["supported"])
     d["reason"] = why.value.decode()
     return d
+
+
+def png_inspect(data):
+    """The host-only chunk walk of one PNG file (vf_png_inspect; no GPU needed) -> dict(width, height, bit_depth,
+    color_type, interlace, channels, idat_bytes, idat_chunks, palette_entries, trns_entries, supported, inflated_bytes,
+    reason).  channels: what image.load(path) gives after expansion (1 - 4).  Raises ValueError for a malformed file."""
+    return _png_inspect("vf_png_inspect", data)
 
 
 def png_inspect_full(data, passes=True):
@@ -362,16 +368,8 @@ def png_inspect_full(data, passes=True):
     passes), and passes: seven (width, height, rowbytes), zeros for an absent pass; a file without interlace is one pass,
     the first.  passes=False leaves that key out (the batch decoder does not read it).  Raises ValueError for a malformed
     file."""
-    lib = _lib.load()
-    data = bytes(data)
-    info = (C.c_int64 * 12)()
     geo = (C.c_int64 * 21)() if passes else None
-    why = C.create_string_buffer(160)
-    if lib.vf_png_inspect_full(data, len(data), info, geo, why, 160) != 0:
-        raise ValueError(lib.vf_last_error().decode())
-    d = {k: int(v) for k, v in zip(_PNG_INFO_KEYS, info)}
-    d["supported"] = bool(d["supported"])
-    d["reason"] = why.value.decode()
+    d = _png_inspect("vf_png_inspect_full", data, geo)
     if passes:
         p = geo[:]
         d["passes"] = list(zip(p[0::3], p[1::3], p[2::3]))
@@ -417,29 +415,28 @@ def _frame_kind(frames):
     return kind, n, H, W, Cc
 
 
+def _png_query(entry, files, *args):
+    """One size query of the PNG decoder -> (device workspace bytes, host staging bytes).  args: what the entry takes between
+    the batch and the two results.  ValueError, naming the image, for a malformed or unsupported file."""
+    lib = _lib.load()
+    data, offs = _joined(files)
+    ws_b, st_b = C.c_size_t(), C.c_size_t()
+    if getattr(lib, entry)(data, offs.ctypes.data_as(C.c_void_p), len(files), *args, C.byref(ws_b), C.byref(st_b)) != 0:
+        raise ValueError(lib.vf_last_error().decode())
+    return ws_b.value, st_b.value
+
+
 def png_decode_workspace_bytes(files, channels=None):
     """(device workspace bytes, host staging bytes) of one PNG batch (vf_png_decode_workspace_bytes; host only, no GPU
     needed).  channels: None (each file's own), 1 or 3.  ValueError, naming the image, for a malformed or unsupported
     file."""
-    lib = _lib.load()
-    data, offs = _joined(files)
-    ws_b, st_b = C.c_size_t(), C.c_size_t()
-    if lib.vf_png_decode_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), len(files), int(channels or 0), C.byref(ws_b),
-                                         C.byref(st_b)) != 0:
-        raise ValueError(lib.vf_last_error().decode())
-    return ws_b.value, st_b.value
+    return _png_query("vf_png_decode_workspace_bytes", files, int(channels or 0))
 
 
 def png_decode_full_workspace_bytes(files, channels=None, out_kind=0):
     """png_decode_workspace_bytes under the full rule (vf_png_decode_full_workspace_bytes; host only).  out_kind 0: uint8
-    output, 1: float32."""
-    lib = _lib.load()
-    data, offs = _joined(files)
-    ws_b, st_b = C.c_size_t(), C.c_size_t()
-    if lib.vf_png_decode_full_workspace_bytes(data, offs.ctypes.data_as(C.c_void_p), len(files), int(channels or 0), int(out_kind),
-                                              C.byref(ws_b), C.byref(st_b)) != 0:
-        raise ValueError(lib.vf_last_error().decode())
-    return ws_b.value, st_b.value
+    output, 1: float32.  For files the default rule takes, with out_kind 0, both give the same sizes."""
+    return _png_query("vf_png_decode_full_workspace_bytes", files, int(channels or 0), int(out_kind))
 
 
 def _encoder_bytes(entry, *geometry):

@@ -1,29 +1,30 @@
 // vf_png_decode.hip — batched PNG decode on the device: inflate, unfilter, expand.
-//   * vf_png_inspect (host only): chunks, IHDR, PLTE / tRNS, the zlib header, supported or why not;
-//   * vf_png_decode_workspace_bytes: device workspace and host staging sizes of one batch;
-//   * vf_png_decode: N files -> N uint8 H x W x C images at caller-given offsets of one buffer;
-//   * vf_png_inspect_full, vf_png_decode_full_workspace_bytes, vf_png_decode_full: the same for the full rule, which also
-//     takes Adam7-interlaced and 16-bit files and writes uint8 or float32 (the last section of this comment).
+// One pipeline, two rules (PngRule) for which files it takes, how its messages begin and what its launches are called:
+//   default  vf_png_inspect (host only: chunks, IHDR, PLTE / tRNS, the zlib header, supported or why not),
+//            vf_png_decode_workspace_bytes (device workspace and host staging sizes of one batch), vf_png_decode (N files ->
+//            N uint8 H x W x C images at caller-given offsets of one buffer): files of 8 bits or fewer without interlace;
+//   full     vf_png_inspect_full, vf_png_decode_full_workspace_bytes, vf_png_decode_full: Adam7-interlaced and 16-bit files
+//            too, written as uint8 or float32.
+// An image is up to seven passes, each a sub-image with its own rows; a file without interlace is the one-pass case (pass 1
+// = the image), and the default rule's files are that case at 8 bits or fewer, written as uint8.
 // Pipeline (three launches, whatever N): the host walks the chunks, checks the CRCs, concatenates every file's IDAT
 // payloads behind one another (minus the two zlib header bytes) and packs them with PLTE / tRNS and one descriptor per
-// image into one staging buffer -> one upload.  Then
+// image (PngdImage: the file, then its passes' sizes and places) into one staging buffer -> one upload.  Then
 //   k_pngd_inflate   one 256-thread block per image: deflate blocks in stream order.  Thread 0 reads the block header,
 //                    all threads fill the lookup tables, thread 0 decodes symbols into a token batch in LDS, all threads
-//                    resolve the batch (pointer doubling for sources inside it), store it and add it to the Adler-32;
-//   k_pngd_unfilter  one wave per image: a band of 64 rows at a time, row r one pixel behind row r - 1, so that every
-//                    filter sees its left, upper and upper-left neighbours reconstructed;
-//   k_pngd_expand    one thread per output pixel: sub-byte samples, palette and tRNS, alpha drop, grey replication.
-// Everything is integer arithmetic.  A corrupt stream ends in the image's status word: every read of the compressed
-// bytes is bounded by the stream's length, every store by the expected inflated size.
-// The full rule runs the same k_pngd_inflate over its own descriptor (PngdFull: the image's seven passes' sizes and places;
-// a plain file is the one-pass case) with the expected size sum h_p * (1 + rb_p), then
-//   k_pngd_unfilter_full  one wave per (image, pass): the same 64-row wavefront over the pass's h_p x rb_p, a filter unit of
-//                         up to 8 bytes (16-bit RGBA) in a 64-bit register when it is above 4;
-//   k_pngd_expand_full    one thread per output pixel: its pass from (x & 7, y & 7), its place inside the pass, 16-bit
-//                         samples big-endian; uint8 (a 16-bit sample's high byte) or float32 (byte / 255, sample / 65535).
+//                    resolve the batch (pointer doubling for sources inside it), store it and add it to the Adler-32; the
+//                    expected size is sum h_p * (1 + rb_p);
+//   k_pngd_unfilter  one wave per (image, pass): a band of 64 rows of the pass's h_p x rb_p at a time, row r one filter
+//                    unit behind row r - 1, so that every filter sees its left, upper and upper-left neighbours
+//                    reconstructed; a unit of up to 8 bytes (16-bit RGBA) in a 64-bit register when it is above 4;
+//   k_pngd_expand    one thread per output pixel: its pass from (x & 7, y & 7), its place inside the pass; sub-byte samples,
+//                    16-bit samples big-endian, palette and tRNS, alpha drop, grey replication; uint8 (a 16-bit sample's
+//                    high byte) or float32 (byte / 255, sample / 65535).
+// Everything but that division is integer arithmetic.  A corrupt stream ends in the image's status word: every read of the
+// compressed bytes is bounded by the stream's length, every store by the expected inflated size.
 // Animated PNG (vf_apng_inspect, vf_apng_decode_workspace_bytes, vf_apng_decode): the host walk of
 // vf_apng_parse.h makes every frame an image of the full rule, the three launches decode them all, then
-//   k_apng_compose        one thread per canvas pixel of a file: the frames in order, blend SOURCE, the three disposals.
+//   k_apng_compose   one thread per canvas pixel of a file: the frames in order, blend SOURCE, the three disposals.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -50,22 +51,27 @@ constexpr uint32_t kAdlerMod = 65521;
 
 enum { S_HEADER = 0, S_HUFF = 1, S_STORED = 2, S_TRAILER = 3, S_END = 4 };
 
+// one image of a batch, under either rule: the file, then its passes.  A plain file has one pass, the first; an absent pass
+// has ph 0.  pinf / praw: the pass's first byte behind inf_off / raw_off (or out_off when direct)
 struct PngdImage {
   int64_t src;                 // first byte of the deflate stream in the stream section of the upload (256-byte aligned)
   int64_t inf_off;             // first byte of the inflated (filtered) rows in the workspace
   int64_t raw_off;             // first byte of the unfiltered rows in the workspace (unused when direct)
-  int64_t out_off;             // first byte of the H x W x C output
+  int64_t out_off;             // first ELEMENT of the H x W x C output (bytes or floats)
   int32_t slen;                // bytes of the stream (deflate blocks + Adler-32; zero-padded to 256 behind)
-  int32_t expect;              // H * (1 + rb): the inflated size the header promises
+  int32_t expect;              // sum h_p * (1 + rb_p): the inflated size the header promises
   int32_t W, H, depth, ctype;
   int32_t rb, bpp;             // bytes per row (without the filter byte), bytes per filter unit
   int32_t rc, oc;              // samples per pixel in the rows, channels of the output
   int32_t nplte, ntrns;
-  int32_t direct;              // the unfiltered rows ARE the output (8-bit, rc == oc, no palette)
+  int32_t direct;              // the unfiltered rows ARE the output (one pass, uint8, 8-bit, rc == oc, no palette)
   int32_t pad;
   uint8_t plte[768];
   uint8_t trns[256];
+  int32_t lace, out_kind;      // Adam7; 0: uint8, 1: float32
+  int32_t ph[7], prb[7], pinf[7], praw[7];   // rows and bytes per row of each pass, its first byte in either buffer
 };
+static_assert(sizeof(PngdImage) == 1232, "DESIGN.md 5.6 states the descriptor's size");
 
 // canonical code in puff's decode form: codes of length l are first[l] .. first[l] + count[l] - 1, their symbols
 // sym[index[l] ...]
@@ -105,28 +111,14 @@ struct InflateLds {
 };
 static_assert(2 * sizeof(InflateLds) <= 160 * 1024, "k_pngd_inflate: two blocks per CU (160 KiB of LDS)");
 
-// the full rule's descriptor: vf_png_decode's, then the passes.  A plain file has one pass, the first; an absent pass has
-// ph 0.  pinf / praw: the pass's first byte behind im.inf_off / im.raw_off (or im.out_off when direct)
-struct PngdFull {
-  PngdImage im;                // out_off counts ELEMENTS of the output (bytes or floats)
-  int32_t lace, out_kind;      // Adam7; 0: uint8, 1: float32
-  int32_t ph[7], prb[7], pinf[7], praw[7];   // rows and bytes per row of each pass, its first byte in either buffer
-};
-static_assert(sizeof(PngdImage) == 1112 && sizeof(PngdFull) == 1232, "DESIGN.md 5.6 states the descriptors' sizes");
-VF_HD const PngdImage& pngd_base(const PngdImage& d) { return d; }
-VF_HD const PngdImage& pngd_base(const PngdFull& d) { return d.im; }
-
-template <class Img>
-struct PngdBatchT {
-  const Img* img;
+struct PngdBatch {
+  const PngdImage* img;
   const uint8_t* streams;
   uint8_t* inf;
   uint8_t* raw;
   uint8_t* out;
   int32_t* status;
 };
-using PngdBatch = PngdBatchT<PngdImage>;
-using PngdFullBatch = PngdBatchT<PngdFull>;
 
 __constant__ uint16_t c_lbase[29] = {3,  4,  5,  6,  7,  8,  9,  10, 11,  13,  15,  17,  19,  23, 27,
                                                       31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
@@ -543,11 +535,16 @@ VF_HD void pngd_ctl_init(PngdCtl& c, int slen) {
 }
 
 // one block per image
-template <class Img>
-__global__ __launch_bounds__(kInfThreads) void k_pngd_inflate(const PngdBatchT<Img> B) {
-  __shared__ InflateLds L;
+__global__ __launch_bounds__(kInfThreads) void k_pngd_inflate(const PngdBatch B) {
+  // L is Ls: the compiler folds + z - z away and no instruction is left of it, but only after its interprocedural constant
+  // propagation, which would otherwise write the one LDS object's address into every helper below before they are simplified
+  // on their own.  The code that gives is the same size and up to 3.4 % slower on streams of literals (the token loop of
+  // pngd_tokens); this form keeps the helpers general until they are inlined (profiles/png_one_path_kernel_resources.txt)
+  __shared__ InflateLds Ls;
+  const int z = blockIdx.x;
+  InflateLds& L = *(InflateLds*)((char*)&Ls + z - z);
   const int t = threadIdx.x;
-  const PngdImage& im = pngd_base(B.img[blockIdx.x]);
+  const PngdImage& im = B.img[blockIdx.x];
   const uint8_t* stream = B.streams + im.src;
   const uint32_t* src32 = (const uint32_t*)stream;
   const uint32_t ndw = ((uint32_t)im.slen + 3) >> 2;
@@ -607,117 +604,16 @@ VF_HD int pngd_paeth(int a, int b, int c) {
   return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
 }
 
-// one wave per image.  Lane r of a band of 64 rows is at filter unit x = step - r (a unit: bpp bytes, packed in a dword), so
-// lane r - 1 finished unit x one step earlier: its value comes by shuffle, and the one before that is the upper-left
-// neighbour.  Lane 0 reads the row above the band from memory (zeros above the first row).
-__global__ __launch_bounds__(64) void k_pngd_unfilter(const PngdBatch B) {
-  const int lane = threadIdx.x;
-  const PngdImage& im = B.img[blockIdx.x];
-  if (B.status[blockIdx.x] != 0) return;
-  const uint8_t* in = B.inf + im.inf_off;
-  uint8_t* dst = im.direct ? B.out + im.out_off : B.raw + im.raw_off;
-  const int rb = im.rb, bpp = im.bpp, H = im.H;
-  const int nx = rb / bpp;
-  const int64_t stride = (int64_t)rb + 1;
-  for (int band = 0; band < H; band += 64) {
-    const int r = band + lane;
-    const bool active = r < H;
-    const int ft = active ? in[r * stride] : 0;
-    if (__any(ft > 4)) {
-      if (lane == 0) B.status[blockIdx.x] = VF_PNG_BAD_FILTER;
-      return;
-    }
-    const uint8_t* src = in + r * stride + 1;
-    uint8_t* row = dst + (int64_t)r * rb;
-    const uint8_t* above = dst + (int64_t)(band - 1) * rb;    // read by lane 0 when band > 0
-    const int rows = min(64, H - band);
-    uint32_t cur = 0, a = 0, c = 0;
-    for (int step = 0; step < nx + rows - 1; ++step) {
-      uint32_t up = __shfl_up(cur, 1);
-      const int x = step - lane;
-      const bool on = active && x >= 0 && x < nx;
-      if (lane == 0) {
-        up = 0;
-        if (band > 0 && on)
-          for (int k = 0; k < bpp; ++k) up |= (uint32_t)above[(int64_t)x * bpp + k] << (8 * k);
-      }
-      if (on) {
-        uint32_t o = 0;
-        for (int k = 0; k < bpp; ++k) {
-          const int f = src[(int64_t)x * bpp + k];
-          const int av = (a >> (8 * k)) & 255, bv = (up >> (8 * k)) & 255, cv = (c >> (8 * k)) & 255;
-          const int pred = ft == 0 ? 0 : ft == 1 ? av : ft == 2 ? bv : ft == 3 ? (av + bv) >> 1 : pngd_paeth(av, bv, cv);
-          const int v = (f + pred) & 255;
-          row[(int64_t)x * bpp + k] = (uint8_t)v;
-          o |= (uint32_t)v << (8 * k);
-        }
-        cur = o;
-        a = o;
-        c = up;
-      }
-    }
-    __syncthreads();   // the band's last row is in memory before lane 0 of the next band reads it
-  }
-}
-
-// one thread per output pixel
-__global__ void k_pngd_expand(const PngdBatch B) {
-  const PngdImage& im = B.img[blockIdx.y];
-  if (im.direct || B.status[blockIdx.y] != 0) return;
-  const uint8_t* raw = B.raw + im.raw_off;
-  uint8_t* out = B.out + im.out_off;
-  const int64_t npix = (int64_t)im.W * im.H;
-  const int depth = im.depth, oc = im.oc;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
-    const int y = (int)(i / im.W), x = (int)(i % im.W);
-    const uint8_t* row = raw + (int64_t)y * im.rb;
-    int s[4] = {0, 0, 0, 255};
-    if (depth < 8) {                                          // colour types 0 and 3 only: one sample per pixel, MSB first
-      const int bit = x * depth;
-      const int v = (row[bit >> 3] >> (8 - depth - (bit & 7))) & ((1 << depth) - 1);
-      s[0] = im.ctype == 3 ? v : v * (255 / ((1 << depth) - 1));
-    } else {
-      for (int k = 0; k < im.rc; ++k) s[k] = row[(int64_t)x * im.rc + k];
-    }
-    int r, g, b, al = 255;
-    if (im.ctype == 3) {
-      const int ix = s[0];
-      if (ix >= im.nplte) {
-        atomicMax(B.status + blockIdx.y, (int)VF_PNG_BAD_INDEX);
-        continue;
-      }
-      r = im.plte[3 * ix];
-      g = im.plte[3 * ix + 1];
-      b = im.plte[3 * ix + 2];
-      if (ix < im.ntrns) al = im.trns[ix];
-    } else if (im.ctype == 0 || im.ctype == 4) {
-      r = g = b = s[0];
-      if (im.ctype == 4) al = s[1];
-    } else {
-      r = s[0];
-      g = s[1];
-      b = s[2];
-      if (im.ctype == 6) al = s[3];
-    }
-    uint8_t* o = out + i * oc;
-    o[0] = (uint8_t)r;
-    if (oc == 2) o[1] = (uint8_t)al;
-    if (oc >= 3) {
-      o[1] = (uint8_t)g;
-      o[2] = (uint8_t)b;
-    }
-    if (oc == 4) o[3] = (uint8_t)al;
-  }
-}
-
-// ------------------------------------------------------------------------------------- the full rule: Adam7 and 16 bits
+// Adam7: the pass of pixel (x & 7, y & 7), each pass's first pixel and steps
 __constant__ uint8_t c_a7_pass[64] = {0, 5, 3, 5, 1, 5, 3, 5, 6, 6, 6, 6, 6, 6, 6, 6, 4, 5, 4, 5, 4, 5, 4, 5, 6, 6, 6, 6, 6, 6, 6, 6,
                                       2, 5, 3, 5, 2, 5, 3, 5, 6, 6, 6, 6, 6, 6, 6, 6, 4, 5, 4, 5, 4, 5, 4, 5, 6, 6, 6, 6, 6, 6, 6, 6};
 __constant__ uint8_t c_a7_x0[7] = {0, 4, 0, 2, 0, 1, 0}, c_a7_y0[7] = {0, 0, 4, 0, 2, 0, 1};
 __constant__ uint8_t c_a7_dxs[7] = {3, 3, 2, 2, 1, 1, 0}, c_a7_dys[7] = {3, 3, 3, 2, 2, 1, 1};   // log2 of dx, dy
 
-// k_pngd_unfilter's wavefront over one pass of h rows of rb bytes; U holds one filter unit (bpp bytes).  A filter byte above
-// 4 is the image's BAD_FILTER, through atomicMax: the passes' waves share the status word
+// One wave over one pass of H rows of rb bytes; U holds one filter unit (bpp bytes).  Lane r of a band of 64 rows is at filter
+// unit x = step - r, so lane r - 1 finished unit x one step earlier: its value comes by shuffle, and the one before that is
+// the upper-left neighbour.  Lane 0 reads the row above the band from memory (zeros above the first row).  A filter byte
+// above 4 is the image's BAD_FILTER, through atomicMax: the passes' waves share the status word
 template <class U>
 VF_HD void pngd_unfilter_pass(const uint8_t* in, uint8_t* dst, int H, int rb, int bpp, int32_t* status, int lane) {
   const int nx = rb / bpp;
@@ -764,21 +660,20 @@ VF_HD void pngd_unfilter_pass(const uint8_t* in, uint8_t* dst, int H, int rb, in
 }
 
 // one wave per (image, pass): block 7 * i + p.  An absent pass returns at once
-__global__ __launch_bounds__(64) void k_pngd_unfilter_full(const PngdFullBatch B) {
+__global__ __launch_bounds__(64) void k_pngd_unfilter(const PngdBatch B) {
   const int i = blockIdx.x / 7, p = blockIdx.x % 7;
-  const PngdFull& d = B.img[i];
+  const PngdImage& d = B.img[i];
   const int h = d.ph[p];
   if (h == 0 || B.status[i] != 0) return;
-  const uint8_t* in = B.inf + d.im.inf_off + d.pinf[p];
-  uint8_t* dst = (d.im.direct ? B.out + d.im.out_off : B.raw + d.im.raw_off) + d.praw[p];
-  if (d.im.bpp <= 4) pngd_unfilter_pass<uint32_t>(in, dst, h, d.prb[p], d.im.bpp, B.status + i, threadIdx.x);
-  else pngd_unfilter_pass<unsigned long long>(in, dst, h, d.prb[p], d.im.bpp, B.status + i, threadIdx.x);
+  const uint8_t* in = B.inf + d.inf_off + d.pinf[p];
+  uint8_t* dst = (d.direct ? B.out + d.out_off : B.raw + d.raw_off) + d.praw[p];
+  if (d.bpp <= 4) pngd_unfilter_pass<uint32_t>(in, dst, h, d.prb[p], d.bpp, B.status + i, threadIdx.x);
+  else pngd_unfilter_pass<unsigned long long>(in, dst, h, d.prb[p], d.bpp, B.status + i, threadIdx.x);
 }
 
 // one thread per output pixel
-__global__ void k_pngd_expand_full(const PngdFullBatch B) {
-  const PngdFull& d = B.img[blockIdx.y];
-  const PngdImage& im = d.im;
+__global__ void k_pngd_expand(const PngdBatch B) {
+  const PngdImage& im = B.img[blockIdx.y];
   if (im.direct || B.status[blockIdx.y] != 0) return;
   const uint8_t* raw = B.raw + im.raw_off;
   const int64_t npix = (int64_t)im.W * im.H;
@@ -787,10 +682,10 @@ __global__ void k_pngd_expand_full(const PngdFullBatch B) {
     const int y = (int)(i / im.W), x = (int)(i % im.W);
     int px = x;                                               // the pixel's place in its pass, the pass's rows
     const uint8_t* row;
-    if (d.lace) {
+    if (im.lace) {
       const int p = c_a7_pass[(y & 7) * 8 + (x & 7)];
       px = (x - c_a7_x0[p]) >> c_a7_dxs[p];
-      row = raw + d.praw[p] + (int64_t)((y - c_a7_y0[p]) >> c_a7_dys[p]) * d.prb[p];
+      row = raw + im.praw[p] + (int64_t)((y - c_a7_y0[p]) >> c_a7_dys[p]) * im.prb[p];
     } else {
       row = raw + (int64_t)y * im.rb;
     }
@@ -832,7 +727,7 @@ __global__ void k_pngd_expand_full(const PngdFullBatch B) {
       v[2] = s[2];
       v[3] = s[3];
     }
-    if (d.out_kind == 0) {
+    if (im.out_kind == 0) {
       uint8_t* o = B.out + im.out_off + i * oc;
       const int sh = depth == 16 ? 8 : 0;                     // a 16-bit sample's high byte
       for (int k = 0; k < oc; ++k) o[k] = (uint8_t)(v[k] >> sh);
@@ -1058,38 +953,94 @@ int png_out_channels(const PngParsed& P, int channels, std::string& why) {
   return channels;
 }
 
-struct PngdPlan {
+// ---------------------------------------------------------------------------------- host side: the rules and the one path
+// One pipeline, two rules for which files it takes; an entry is the path below under its rule value.
+struct PngRule {
+  const char* who;             // what the messages about the batch's files start with
+  bool full;                   // Adam7-interlaced and 16-bit files are taken
+  const char* unfilter;        // profiling labels of the unfilter and the expand launch
+  const char* expand;
+};
+constexpr PngRule kDefaultRule = {"vf_png_decode", false, "pngd_unfilter", "pngd_expand"};
+constexpr PngRule kFullRule = {"vf_png_decode_full", true, "pngd_unfilter_full", "pngd_expand_full"};
+
+struct PngPasses {
+  int64_t w[7] = {}, h[7] = {}, rb[7] = {};   // zeros for an absent pass; a plain file is one pass, the first
+  int64_t inflated = 0, raw = 0;              // sum h_p * (1 + rb_p), sum h_p * rb_p
+  bool supported = false;
+  std::string why;
+};
+
+// a parsed file under a rule: the passes, the inflated size they promise, supported or why not.  The default rule refuses an
+// interlaced file, so what it sizes is always one pass, and its refusals are png_parse's, in that order
+void png_rule(const PngParsed& P, const PngRule& rule, PngPasses& F) {
+  static const int x0[7] = {0, 4, 0, 2, 0, 1, 0}, y0[7] = {0, 0, 4, 0, 2, 0, 1}, dx[7] = {8, 8, 4, 4, 2, 2, 1}, dy[7] = {8, 8, 8, 4, 4, 2, 2};
+  const bool lace = rule.full && P.lace;
+  for (int p = 0; p < (lace ? 7 : 1); ++p) {
+    const int64_t w = lace ? std::max<int64_t>(0, (P.W - x0[p] + dx[p] - 1) / dx[p]) : P.W;
+    const int64_t h = lace ? std::max<int64_t>(0, (P.H - y0[p] + dy[p] - 1) / dy[p]) : P.H;
+    if (w == 0 || h == 0) continue;
+    F.w[p] = w;
+    F.h[p] = h;
+    F.rb[p] = (w * P.rc * P.depth + 7) / 8;
+    F.inflated += h * (1 + F.rb[p]);
+    F.raw += h * F.rb[p];
+  }
+  if (!rule.full) F.why = P.why;
+  else if (P.W > kPngdMaxSide || P.H > kPngdMaxSide) F.why = "larger than 16384 per side";
+  else if (P.idat_bytes > kPngdMaxIdat) F.why = "IDAT data above 256 MiB";
+  else if (F.inflated >= ((int64_t)1 << 31)) F.why = "inflated size of 2^31 bytes or more (the decoder's sizes are int32)";
+  F.supported = F.why.empty();
+}
+
+inline bool pngd_direct(const PngParsed& P, int oc, int out_kind) {
+  return !P.lace && out_kind == 0 && P.depth == 8 && P.ctype != 3 && oc == P.rc;
+}
+
+// the bytes of a batch's streams, inflated rows and unfiltered rows, image by image
+struct PngdSizes {
+  int64_t stream_bytes = 0, inf_bytes = 0, raw_bytes = 0;
+  void add(const PngParsed& P, const PngPasses& F, bool direct) {
+    stream_bytes += (int64_t)vf_up256((size_t)(P.idat_bytes - 2) + 8);
+    inf_bytes += (int64_t)vf_up256((size_t)F.inflated);
+    if (!direct) raw_bytes += (int64_t)vf_up256((size_t)F.raw);
+  }
+};
+
+struct PngdPlan : PngdSizes {
   std::vector<PngParsed> P;
+  std::vector<PngPasses> F;
   std::vector<int> oc;
-  int64_t stream_bytes = 0, inf_bytes = 0, raw_bytes = 0, max_pix = 0;
+  int64_t max_pix = 0;
   size_t o_img = 0, o_streams = 0, stage = 0, o_inf = 0, o_raw = 0, ws = 0;
 };
 
-inline bool pngd_direct(const PngParsed& P, int oc) { return P.depth == 8 && P.ctype != 3 && oc == P.rc; }
-
-int pngd_plan(const uint8_t* data, const int64_t* offs, int n, int channels, PngdPlan& L, bool crc) {
-  VF_REQUIRE(n > 0 && data && offs, "vf_png_decode: empty batch");
-  VF_REQUIRE(n <= 65535, "vf_png_decode: %d files in one batch (65535 at most)", n);
-  VF_REQUIRE(channels == 0 || channels == 1 || channels == 3, "vf_png_decode: channels %d is not 0 (the file's), 1 or 3", channels);
+int pngd_plan(const PngRule& rule, const uint8_t* data, const int64_t* offs, int n, int channels, int out_kind, PngdPlan& L, bool crc) {
+  const char* who = rule.who;
+  VF_REQUIRE(n > 0 && data && offs, "%s: empty batch", who);
+  VF_REQUIRE(n <= 65535, "%s: %d files in one batch (65535 at most)", who, n);
+  VF_REQUIRE(channels == 0 || channels == 1 || channels == 3, "%s: channels %d is not 0 (the file's), 1 or 3", who, channels);
+  VF_REQUIRE(out_kind == 0 || out_kind == 1, "%s: out_kind %d is not 0 (uint8) or 1 (float32)", who, out_kind);
   L.P.resize(n);
+  L.F.resize(n);
   L.oc.resize(n);
   for (int i = 0; i < n; ++i) {
     std::string msg;
-    VF_REQUIRE(offs[i + 1] >= offs[i], "vf_png_decode: offsets decrease at image %d", i);
+    VF_REQUIRE(offs[i + 1] >= offs[i], "%s: offsets decrease at image %d", who, i);
     PngParsed& P = L.P[i];
+    PngPasses& F = L.F[i];
     if (png_parse(data + offs[i], offs[i + 1] - offs[i], P, msg, crc)) {
-      vf_set_error("vf_png_decode: image %d: %s", i, msg.c_str());
+      vf_set_error("%s: image %d: %s", who, i, msg.c_str());
       return 2;
     }
-    std::string why = P.why;
-    if (P.supported) L.oc[i] = png_out_channels(P, channels, why);
-    if (!P.supported || !L.oc[i]) {
-      vf_set_error("vf_png_decode: image %d: unsupported: %s", i, why.c_str());
+    png_rule(P, rule, F);
+    std::string why = F.why;
+    if (F.supported) L.oc[i] = png_out_channels(P, channels, why);
+    if (!F.supported || !L.oc[i]) {
+      vf_set_error("%s: image %d: unsupported: %s", who, i, why.c_str());
       return 3;
     }
-    L.stream_bytes += (int64_t)vf_up256((size_t)(P.idat_bytes - 2) + 8);
-    L.inf_bytes += (int64_t)vf_up256((size_t)P.inflated);
-    if (!pngd_direct(P, L.oc[i])) L.raw_bytes += (int64_t)vf_up256((size_t)(P.H * P.rb));
+    L.add(P, F, pngd_direct(P, L.oc[i], out_kind));
     L.max_pix = std::max(L.max_pix, P.W * P.H);
   }
   VfCarve ws;
@@ -1102,10 +1053,16 @@ int pngd_plan(const uint8_t* data, const int64_t* offs, int n, int channels, Png
   return 0;
 }
 
-// the descriptor's part that both rules share, and the image's stream into the upload: every IDAT payload behind the one
-// before, minus the stream's first two bytes (the zlib header), zero-padded.  -> the room the stream takes
-int64_t pngd_fill(PngdImage& im, const PngParsed& P, const uint8_t* d, int oc, bool direct, int64_t expect, uint8_t* streams,
-                  int64_t sc, int64_t inf, int64_t raw, int64_t out_off) {
+// where the next image's stream, inflated rows and unfiltered rows begin in their sections
+struct PngdAt {
+  int64_t sc = 0, inf = 0, raw = 0;
+};
+
+// one image's descriptor, and its stream into the upload: every IDAT payload behind the one before, minus the stream's first
+// two bytes (the zlib header), zero-padded.  `at` moves on to the next image
+void pngd_fill(PngdImage& im, const PngParsed& P, const PngPasses& F, const uint8_t* d, int oc, int out_kind, int64_t out_off,
+               uint8_t* streams, PngdAt& at) {
+  memset(&im, 0, sizeof(im));
   im.W = (int32_t)P.W;
   im.H = (int32_t)P.H;
   im.depth = P.depth;
@@ -1116,142 +1073,123 @@ int64_t pngd_fill(PngdImage& im, const PngParsed& P, const uint8_t* d, int oc, b
   im.oc = oc;
   im.nplte = P.nplte;
   im.ntrns = P.ctype == 3 ? P.ntrns : 0;
-  im.direct = direct ? 1 : 0;
+  im.direct = pngd_direct(P, oc, out_kind) ? 1 : 0;
   memcpy(im.plte, P.plte, 768);
   memcpy(im.trns, P.trns, 256);
-  im.expect = (int32_t)expect;
-  im.src = sc;
+  im.expect = (int32_t)F.inflated;
+  im.src = at.sc;
   im.slen = (int32_t)(P.idat_bytes - 2);
-  im.inf_off = inf;
-  im.raw_off = raw;
+  im.inf_off = at.inf;
+  im.raw_off = at.raw;
   im.out_off = out_off;
-  int64_t skip = 2, at = 0;
+  im.lace = P.lace;
+  im.out_kind = out_kind;
+  int64_t pi = 0, pr = 0;
+  for (int p = 0; p < 7; ++p) {
+    im.ph[p] = (int32_t)F.h[p];
+    im.prb[p] = (int32_t)F.rb[p];
+    im.pinf[p] = (int32_t)pi;
+    im.praw[p] = (int32_t)pr;
+    pi += F.h[p] * (1 + F.rb[p]);
+    pr += F.h[p] * F.rb[p];
+  }
+  int64_t skip = 2, n = 0;
   for (const auto& c : P.idat) {
     const int64_t s = std::min(skip, c.second);
     skip -= s;
-    memcpy(streams + sc + at, d + c.first + s, (size_t)(c.second - s));
-    at += c.second - s;
+    memcpy(streams + at.sc + n, d + c.first + s, (size_t)(c.second - s));
+    n += c.second - s;
   }
   const int64_t room = (int64_t)vf_up256((size_t)im.slen + 8);
-  memset(streams + sc + at, 0, (size_t)(room - at));
-  return room;
+  memset(streams + at.sc + n, 0, (size_t)(room - n));
+  at.sc += room;
+  at.inf += (int64_t)vf_up256((size_t)F.inflated);
+  if (!im.direct) at.raw += (int64_t)vf_up256((size_t)F.raw);
 }
 
-void pngd_pack(const uint8_t* data, const int64_t* offs, int n, const int64_t* out_offs, const PngdPlan& L, uint8_t* st) {
+void pngd_pack(const uint8_t* data, const int64_t* offs, int n, int out_kind, const int64_t* out_offs, const PngdPlan& L, uint8_t* st) {
   PngdImage* imgs = (PngdImage*)(st + L.o_img);
-  uint8_t* streams = st + L.o_streams;
-  int64_t sc = 0, inf = 0, raw = 0;
-  for (int i = 0; i < n; ++i) {
-    const PngParsed& P = L.P[i];
-    PngdImage& im = imgs[i];
-    memset(&im, 0, sizeof(im));
-    sc += pngd_fill(im, P, data + offs[i], L.oc[i], pngd_direct(P, L.oc[i]), P.inflated, streams, sc, inf, raw, out_offs[i]);
-    inf += (int64_t)vf_up256((size_t)P.inflated);
-    if (!im.direct) raw += (int64_t)vf_up256((size_t)(P.H * P.rb));
-  }
+  PngdAt at;
+  for (int i = 0; i < n; ++i) pngd_fill(imgs[i], L.P[i], L.F[i], data + offs[i], L.oc[i], out_kind, out_offs[i], st + L.o_streams, at);
 }
 
-// ------------------------------------------------------------------------------------------------ host side: full rule
-struct PngFull {
-  int64_t w[7] = {}, h[7] = {}, rb[7] = {};   // zeros for an absent pass; a plain file is one pass, the first
-  int64_t inflated = 0, raw = 0;              // sum h_p * (1 + rb_p), sum h_p * rb_p
-  bool supported = false;
-  std::string why;
-};
-
-// the full rule over a parsed file: the passes, the inflated size they promise, supported or why not
-void png_full_rule(const PngParsed& P, PngFull& F) {
-  static const int x0[7] = {0, 4, 0, 2, 0, 1, 0}, y0[7] = {0, 0, 4, 0, 2, 0, 1}, dx[7] = {8, 8, 4, 4, 2, 2, 1}, dy[7] = {8, 8, 8, 4, 4, 2, 2};
-  for (int p = 0; p < (P.lace ? 7 : 1); ++p) {
-    const int64_t w = P.lace ? std::max<int64_t>(0, (P.W - x0[p] + dx[p] - 1) / dx[p]) : P.W;
-    const int64_t h = P.lace ? std::max<int64_t>(0, (P.H - y0[p] + dy[p] - 1) / dy[p]) : P.H;
-    if (w == 0 || h == 0) continue;
-    F.w[p] = w;
-    F.h[p] = h;
-    F.rb[p] = (w * P.rc * P.depth + 7) / 8;
-    F.inflated += h * (1 + F.rb[p]);
-    F.raw += h * F.rb[p];
+// The device half, whatever the entry: the staged descriptors and streams go up to the workspace's head in one copy, the
+// status words are cleared, and the three launches decode the batch's n images.  S: the batch's section sizes, for the
+// profile's byte counts; max_pix: the largest image, which sizes the expansion's grid; upload: the label of the upload range
+int pngd_run(const PngRule& rule, const char* upload, vf_ctx* ctx, const PngdBatch& B, void* ws, const void* stage, size_t stage_bytes,
+             unsigned n, const PngdSizes& S, int64_t max_pix) {
+  hipStream_t st = ctx->stream;
+  {
+    VfRange r(upload);
+    VF_CHECK_HIP(hipMemcpyAsync(ws, stage, stage_bytes, hipMemcpyHostToDevice, st));
+    VF_CHECK_HIP(hipMemsetAsync(B.status, 0, sizeof(int32_t) * n, st));
   }
-  if (P.W > kPngdMaxSide || P.H > kPngdMaxSide) F.why = "larger than 16384 per side";
-  else if (P.idat_bytes > kPngdMaxIdat) F.why = "IDAT data above 256 MiB";
-  else if (F.inflated >= ((int64_t)1 << 31)) F.why = "inflated size of 2^31 bytes or more (the decoder's sizes are int32)";
-  F.supported = F.why.empty();
-}
-
-struct PngdFullPlan : PngdPlan {
-  std::vector<PngFull> F;
-};
-
-inline bool pngd_full_direct(const PngParsed& P, int oc, int out_kind) { return !P.lace && out_kind == 0 && pngd_direct(P, oc); }
-
-int pngd_plan_full(const uint8_t* data, const int64_t* offs, int n, int channels, int out_kind, PngdFullPlan& L, bool crc) {
-  VF_REQUIRE(n > 0 && data && offs, "vf_png_decode_full: empty batch");
-  VF_REQUIRE(n <= 65535, "vf_png_decode_full: %d files in one batch (65535 at most)", n);
-  VF_REQUIRE(channels == 0 || channels == 1 || channels == 3, "vf_png_decode_full: channels %d is not 0 (the file's), 1 or 3", channels);
-  VF_REQUIRE(out_kind == 0 || out_kind == 1, "vf_png_decode_full: out_kind %d is not 0 (uint8) or 1 (float32)", out_kind);
-  L.P.resize(n);
-  L.F.resize(n);
-  L.oc.resize(n);
-  for (int i = 0; i < n; ++i) {
-    std::string msg;
-    VF_REQUIRE(offs[i + 1] >= offs[i], "vf_png_decode_full: offsets decrease at image %d", i);
-    PngParsed& P = L.P[i];
-    PngFull& F = L.F[i];
-    if (png_parse(data + offs[i], offs[i + 1] - offs[i], P, msg, crc)) {
-      vf_set_error("vf_png_decode_full: image %d: %s", i, msg.c_str());
-      return 2;
-    }
-    png_full_rule(P, F);
-    std::string why = F.why;
-    if (F.supported) L.oc[i] = png_out_channels(P, channels, why);
-    if (!F.supported || !L.oc[i]) {
-      vf_set_error("vf_png_decode_full: image %d: unsupported: %s", i, why.c_str());
-      return 3;
-    }
-    L.stream_bytes += (int64_t)vf_up256((size_t)(P.idat_bytes - 2) + 8);
-    L.inf_bytes += (int64_t)vf_up256((size_t)F.inflated);
-    if (!pngd_full_direct(P, L.oc[i], out_kind)) L.raw_bytes += (int64_t)vf_up256((size_t)F.raw);
-    L.max_pix = std::max(L.max_pix, P.W * P.H);
-  }
-  VfCarve ws;
-  L.o_img = ws.take(sizeof(PngdFull) * n);
-  L.o_streams = ws.take((size_t)L.stream_bytes);
-  L.stage = ws.at;
-  L.o_inf = ws.take((size_t)L.inf_bytes);
-  L.o_raw = ws.take((size_t)L.raw_bytes);
-  L.ws = ws.at;
+  const double inf = (double)S.inf_bytes;
+  VF_LAUNCH_TIMED(ctx, "pngd_inflate", 0.0, (double)S.stream_bytes + inf, k_pngd_inflate, dim3(n), dim3(kInfThreads), B);
+  VF_LAUNCH_CHECK();
+  VF_LAUNCH_TIMED(ctx, rule.unfilter, 0.0, 2.0 * inf, k_pngd_unfilter, dim3(7u * n), dim3(64), B);
+  VF_LAUNCH_CHECK();
+  const unsigned gp = (unsigned)std::min<int64_t>(std::max<int64_t>(1, vf_cdiv(max_pix, 256)), 4096);
+  VF_LAUNCH_TIMED(ctx, rule.expand, 0.0, 2.0 * (double)S.raw_bytes, k_pngd_expand, dim3(gp, n), dim3(256), B);
+  VF_LAUNCH_CHECK();
   return 0;
 }
 
-void pngd_pack_full(const uint8_t* data, const int64_t* offs, int n, int out_kind, const int64_t* out_offs, const PngdFullPlan& L,
-                    uint8_t* st) {
-  PngdFull* imgs = (PngdFull*)(st + L.o_img);
-  uint8_t* streams = st + L.o_streams;
-  int64_t sc = 0, inf = 0, raw = 0;
-  for (int i = 0; i < n; ++i) {
-    const PngParsed& P = L.P[i];
-    const PngFull& F = L.F[i];
-    const uint8_t* d = data + offs[i];
-    PngdFull& f = imgs[i];
-    memset(&f, 0, sizeof(f));
-    PngdImage& im = f.im;
-    const int64_t room = pngd_fill(im, P, d, L.oc[i], pngd_full_direct(P, L.oc[i], out_kind), F.inflated, streams, sc, inf, raw, out_offs[i]);
-    f.lace = P.lace;
-    f.out_kind = out_kind;
-    int64_t pi = 0, pr = 0;
-    for (int p = 0; p < 7; ++p) {
-      f.ph[p] = (int32_t)F.h[p];
-      f.prb[p] = (int32_t)F.rb[p];
-      f.pinf[p] = (int32_t)pi;
-      f.praw[p] = (int32_t)pr;
-      pi += F.h[p] * (1 + F.rb[p]);
-      pr += F.h[p] * F.rb[p];
-    }
-    sc += room;
-    inf += (int64_t)vf_up256((size_t)F.inflated);
-    if (!im.direct) raw += (int64_t)vf_up256((size_t)F.raw);
+// the body of both inspect entries.  passes: seven (w, h, rb), only under the full rule and only when asked for
+int png_inspect(const char* who, const PngRule& rule, const unsigned char* data, size_t len, int64_t* info, int64_t* passes, char* reason,
+                int reason_cap) {
+  VF_REQUIRE(data && info, "%s: NULL argument", who);
+  PngParsed P;
+  std::string msg;
+  const int rc = png_parse(data, (int64_t)len, P, msg, true);
+  if (rc) {
+    vf_set_error("%s: %s", who, msg.c_str());
+    return rc;
   }
+  PngPasses F;
+  png_rule(P, rule, F);
+  const int64_t v[12] = {P.W, P.H, P.depth, P.ctype, P.lace, P.fc, P.idat_bytes, P.idat_chunks, P.nplte, P.ntrns, F.supported ? 1 : 0,
+                         F.inflated};
+  memcpy(info, v, sizeof v);
+  for (int p = 0; passes && p < 7; ++p) {
+    passes[3 * p] = F.w[p];
+    passes[3 * p + 1] = F.h[p];
+    passes[3 * p + 2] = F.rb[p];
+  }
+  if (reason && reason_cap > 0) snprintf(reason, (size_t)reason_cap, "%s", F.why.c_str());
+  return 0;
 }
+
+// the body of both size queries: the chunk walk alone, the decode entry checks the CRCs
+int pngd_query(const PngRule& rule, const unsigned char* data, const int64_t* offs, int n, int channels, int out_kind, size_t* ws_bytes,
+               size_t* stage_bytes) {
+  PngdPlan L;
+  if (int e = pngd_plan(rule, data, offs, n, channels, out_kind, L, false)) return e;
+  if (ws_bytes) *ws_bytes = L.ws;
+  if (stage_bytes) *stage_bytes = L.stage;
+  return 0;
+}
+
+// the body of both decode entries
+int pngd_decode(const PngRule& rule, vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int out_kind,
+                const int64_t* out_offs, void* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes, int32_t* status) {
+  VF_REQUIRE(out && out_offs && stage && ws && status, "%s: NULL argument", rule.who);
+  PngdPlan L;
+  if (int e = pngd_plan(rule, data, offs, n, channels, out_kind, L, true)) return e;
+  VF_REQUIRE(stage_bytes >= L.stage && ws_bytes >= L.ws, "%s: staging %zu / workspace %zu bytes, need %zu / %zu", rule.who, stage_bytes,
+             ws_bytes, L.stage, L.ws);
+  pngd_pack(data, offs, n, out_kind, out_offs, L, (uint8_t*)stage);
+  uint8_t* w = (uint8_t*)ws;
+  PngdBatch B;
+  B.img = (const PngdImage*)(w + L.o_img);
+  B.streams = w + L.o_streams;
+  B.inf = w + L.o_inf;
+  B.raw = w + L.o_raw;
+  B.out = (uint8_t*)out;
+  B.status = status;
+  return pngd_run(rule, "pngd_upload", ctx, B, ws, stage, L.stage, (unsigned)n, L, L.max_pix);
+}
+
 
 // ------------------------------------------------------------------------------------------- animated PNG
 // Every frame of every file is an image of the full rule above — its fcTL's width x height under the file's IHDR, PLTE and
@@ -1317,12 +1255,12 @@ __global__ __launch_bounds__(256) void k_apng_compose(const ApngdBatch B) {
   }
 }
 
-struct ApngdPlan {
+struct ApngdPlan : PngdSizes {
   std::vector<apngd::Parsed> A;
   std::vector<PngParsed> P;    // one per frame: the frame as an image of the full rule
-  std::vector<PngFull> F;
+  std::vector<PngPasses> F;
   std::vector<int> file_of;
-  int64_t nframes = 0, stream_bytes = 0, inf_bytes = 0, raw_bytes = 0, px_bytes = 0, max_fpix = 0, max_cpix = 0;
+  int64_t nframes = 0, px_bytes = 0, max_fpix = 0, max_cpix = 0;
   size_t o_img = 0, o_files = 0, o_frames = 0, o_streams = 0, stage = 0, o_inf = 0, o_raw = 0, o_px = 0, o_fstatus = 0, ws = 0;
 };
 
@@ -1372,16 +1310,14 @@ int apngd_plan(const char* who, const uint8_t* data, const int64_t* offs, int n,
       L.F.emplace_back();
       L.file_of.push_back(i);
       PngParsed& P = L.P.back();
-      PngFull& F = L.F.back();
+      PngPasses& F = L.F.back();
       apngd_frame_image(A, A.frames[k], P);
-      png_full_rule(P, F);
+      png_rule(P, kFullRule, F);
       if (!F.supported) {
         vf_set_error("%s: image %d: unsupported: frame %zu: %s", who, i, k, F.why.c_str());
         return 3;
       }
-      L.stream_bytes += (int64_t)vf_up256((size_t)(P.idat_bytes - 2) + 8);
-      L.inf_bytes += (int64_t)vf_up256((size_t)F.inflated);
-      if (!pngd_full_direct(P, A.fc, 0)) L.raw_bytes += (int64_t)vf_up256((size_t)F.raw);
+      L.add(P, F, pngd_direct(P, A.fc, 0));
       L.px_bytes += (int64_t)vf_up256((size_t)(P.W * P.H * A.fc));
       L.max_fpix = std::max(L.max_fpix, P.W * P.H);
     }
@@ -1390,7 +1326,7 @@ int apngd_plan(const char* who, const uint8_t* data, const int64_t* offs, int n,
   L.nframes = (int64_t)L.P.size();
   VF_REQUIRE(L.nframes <= 65535, "%s: %lld frames in one batch (65535 at most; split the batch)", who, (long long)L.nframes);
   VfCarve ws;
-  L.o_img = ws.take(sizeof(PngdFull) * (size_t)L.nframes);
+  L.o_img = ws.take(sizeof(PngdImage) * (size_t)L.nframes);
   L.o_files = ws.take(sizeof(ApngdFile) * (size_t)n);
   L.o_frames = ws.take(sizeof(ApngdFrame) * (size_t)L.nframes);
   L.o_streams = ws.take((size_t)L.stream_bytes);
@@ -1404,11 +1340,11 @@ int apngd_plan(const char* who, const uint8_t* data, const int64_t* offs, int n,
 }
 
 void apngd_pack(const uint8_t* data, const int64_t* offs, int n, int alpha, const int64_t* out_offs, const ApngdPlan& L, uint8_t* st) {
-  PngdFull* imgs = (PngdFull*)(st + L.o_img);
+  PngdImage* imgs = (PngdImage*)(st + L.o_img);
   ApngdFile* files = (ApngdFile*)(st + L.o_files);
   ApngdFrame* frames = (ApngdFrame*)(st + L.o_frames);
-  uint8_t* streams = st + L.o_streams;
-  int64_t sc = 0, inf = 0, raw = 0, px = 0, j = 0;
+  PngdAt at;
+  int64_t px = 0, j = 0;
   for (int i = 0; i < n; ++i) {
     const apngd::Parsed& A = L.A[i];
     ApngdFile& fl = files[i];
@@ -1422,21 +1358,7 @@ void apngd_pack(const uint8_t* data, const int64_t* offs, int n, int alpha, cons
     fl.oc = alpha ? 4 : 3;
     for (size_t k = 0; k < A.frames.size(); ++k, ++j) {
       const PngParsed& P = L.P[j];
-      const PngFull& F = L.F[j];
-      PngdFull& f = imgs[j];
-      memset(&f, 0, sizeof(f));
-      const int64_t room = pngd_fill(f.im, P, data + offs[i], A.fc, pngd_full_direct(P, A.fc, 0), F.inflated, streams, sc, inf, raw, px);
-      f.lace = P.lace;
-      f.out_kind = 0;
-      int64_t pi = 0, pr = 0;
-      for (int p = 0; p < 7; ++p) {
-        f.ph[p] = (int32_t)F.h[p];
-        f.prb[p] = (int32_t)F.rb[p];
-        f.pinf[p] = (int32_t)pi;
-        f.praw[p] = (int32_t)pr;
-        pi += F.h[p] * (1 + F.rb[p]);
-        pr += F.h[p] * F.rb[p];
-      }
+      pngd_fill(imgs[j], P, L.F[j], data + offs[i], A.fc, 0, px, st + L.o_streams, at);
       ApngdFrame& fr = frames[j];
       memset(&fr, 0, sizeof(fr));
       fr.px = px;
@@ -1445,9 +1367,6 @@ void apngd_pack(const uint8_t* data, const int64_t* offs, int n, int alpha, cons
       fr.w = (int32_t)A.frames[k].w;
       fr.h = (int32_t)A.frames[k].h;
       fr.dispose = A.frames[k].dispose;
-      sc += room;
-      inf += (int64_t)vf_up256((size_t)F.inflated);
-      if (!f.im.direct) raw += (int64_t)vf_up256((size_t)F.raw);
       px += (int64_t)vf_up256((size_t)(P.W * P.H * A.fc));
     }
   }
@@ -1468,9 +1387,9 @@ VF_API int vf_apng_inspect(const unsigned char* data, size_t len, int64_t* info,
   std::string why = A.why;
   for (size_t k = 0; k < A.frames.size() && why.empty(); ++k) {   // what the full rule refuses of a single frame
     PngParsed P;
-    PngFull F;
+    PngPasses F;
     apngd_frame_image(A, A.frames[k], P);
-    png_full_rule(P, F);
+    png_rule(P, kFullRule, F);
     if (!F.supported) why = "frame " + std::to_string(k) + ": " + F.why;
   }
   const int64_t v[12] = {A.W, A.H, A.depth, A.ctype, A.lace, A.fc, (int64_t)A.frames.size(), A.num_plays, why.empty() ? 1 : 0,
@@ -1503,9 +1422,8 @@ VF_API int vf_apng_decode(vf_ctx* ctx, const unsigned char* data, const int64_t*
              ws_bytes, L.stage, L.ws);
   apngd_pack(data, offs, n, alpha, out_offs, L, (uint8_t*)stage);
   uint8_t* w = (uint8_t*)ws;
-  const unsigned nf = (unsigned)L.nframes;
-  PngdFullBatch B;
-  B.img = (const PngdFull*)(w + L.o_img);
+  PngdBatch B;
+  B.img = (const PngdImage*)(w + L.o_img);
   B.streams = w + L.o_streams;
   B.inf = w + L.o_inf;
   B.raw = w + L.o_raw;
@@ -1518,20 +1436,7 @@ VF_API int vf_apng_decode(vf_ctx* ctx, const unsigned char* data, const int64_t*
   Cb.frame_status = B.status;
   Cb.out = out;
   Cb.status = status;
-  hipStream_t st = ctx->stream;
-  {
-    VfRange r("apngd_upload");
-    VF_CHECK_HIP(hipMemcpyAsync(w, stage, L.stage, hipMemcpyHostToDevice, st));
-    VF_CHECK_HIP(hipMemsetAsync(B.status, 0, sizeof(int32_t) * nf, st));
-  }
-  const double inf = (double)L.inf_bytes;
-  VF_LAUNCH_TIMED(ctx, "pngd_inflate", 0.0, (double)L.stream_bytes + inf, k_pngd_inflate<PngdFull>, dim3(nf), dim3(kInfThreads), B);
-  VF_LAUNCH_CHECK();
-  VF_LAUNCH_TIMED(ctx, "pngd_unfilter_full", 0.0, 2.0 * inf, k_pngd_unfilter_full, dim3(7u * nf), dim3(64), B);
-  VF_LAUNCH_CHECK();
-  const unsigned gp = (unsigned)std::min<int64_t>(std::max<int64_t>(1, vf_cdiv(L.max_fpix, 256)), 4096);
-  VF_LAUNCH_TIMED(ctx, "pngd_expand_full", 0.0, 2.0 * (double)L.raw_bytes, k_pngd_expand_full, dim3(gp, nf), dim3(256), B);
-  VF_LAUNCH_CHECK();
+  if (int e = pngd_run(kFullRule, "apngd_upload", ctx, B, ws, stage, L.stage, (unsigned)L.nframes, L, L.max_fpix)) return e;
   const unsigned gc = (unsigned)std::min<int64_t>(std::max<int64_t>(1, vf_cdiv(L.max_cpix, 256)), 4096);
   double out_bytes = 0;
   for (int i = 0; i < n; ++i) out_bytes += (double)L.A[i].frames.size() * (double)(L.A[i].W * L.A[i].H) * (alpha ? 4 : 3);
@@ -1541,136 +1446,32 @@ VF_API int vf_apng_decode(vf_ctx* ctx, const unsigned char* data, const int64_t*
 }
 
 VF_API int vf_png_inspect(const unsigned char* data, size_t len, int64_t* info, char* reason, int reason_cap) {
-  VF_REQUIRE(data && info, "vf_png_inspect: NULL argument");
-  PngParsed P;
-  std::string msg;
-  const int rc = png_parse(data, (int64_t)len, P, msg, true);
-  if (rc) {
-    vf_set_error("vf_png_inspect: %s", msg.c_str());
-    return rc;
-  }
-  info[0] = P.W;
-  info[1] = P.H;
-  info[2] = P.depth;
-  info[3] = P.ctype;
-  info[4] = P.lace;
-  info[5] = P.fc;
-  info[6] = P.idat_bytes;
-  info[7] = P.idat_chunks;
-  info[8] = P.nplte;
-  info[9] = P.ntrns;
-  info[10] = P.supported ? 1 : 0;
-  info[11] = P.inflated;
-  if (reason && reason_cap > 0) snprintf(reason, (size_t)reason_cap, "%s", P.why.c_str());
-  return 0;
+  return png_inspect("vf_png_inspect", kDefaultRule, data, len, info, nullptr, reason, reason_cap);
 }
 
 VF_API int vf_png_decode_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int channels, size_t* ws_bytes,
                                          size_t* stage_bytes) {
-  PngdPlan L;
-  if (int e = pngd_plan(data, offs, n, channels, L, false)) return e;   // the chunk walk alone: vf_png_decode checks the CRCs
-  if (ws_bytes) *ws_bytes = L.ws;
-  if (stage_bytes) *stage_bytes = L.stage;
-  return 0;
+  return pngd_query(kDefaultRule, data, offs, n, channels, 0, ws_bytes, stage_bytes);
 }
 
 VF_API int vf_png_decode(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, const int64_t* out_offs,
                          unsigned char* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes, int32_t* status) {
-  VF_REQUIRE(out && out_offs && stage && ws && status, "vf_png_decode: NULL argument");
-  PngdPlan L;
-  if (int e = pngd_plan(data, offs, n, channels, L, true)) return e;
-  VF_REQUIRE(stage_bytes >= L.stage && ws_bytes >= L.ws, "vf_png_decode: staging %zu / workspace %zu bytes, need %zu / %zu", stage_bytes,
-             ws_bytes, L.stage, L.ws);
-  pngd_pack(data, offs, n, out_offs, L, (uint8_t*)stage);
-  uint8_t* w = (uint8_t*)ws;
-  PngdBatch B;
-  B.img = (const PngdImage*)(w + L.o_img);
-  B.streams = w + L.o_streams;
-  B.inf = w + L.o_inf;
-  B.raw = w + L.o_raw;
-  B.out = out;
-  B.status = status;
-  hipStream_t st = ctx->stream;
-  {
-    VfRange r("pngd_upload");
-    VF_CHECK_HIP(hipMemcpyAsync(w, stage, L.stage, hipMemcpyHostToDevice, st));
-    VF_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t) * n, st));
-  }
-  const double inf = (double)L.inf_bytes;
-  VF_LAUNCH_TIMED(ctx, "pngd_inflate", 0.0, (double)L.stream_bytes + inf, k_pngd_inflate<PngdImage>, dim3((unsigned)n), dim3(kInfThreads), B);
-  VF_LAUNCH_CHECK();
-  VF_LAUNCH_TIMED(ctx, "pngd_unfilter", 0.0, 2.0 * inf, k_pngd_unfilter, dim3((unsigned)n), dim3(64), B);
-  VF_LAUNCH_CHECK();
-  const unsigned gp = (unsigned)std::min<int64_t>(std::max<int64_t>(1, vf_cdiv(L.max_pix, 256)), 4096);
-  VF_LAUNCH_TIMED(ctx, "pngd_expand", 0.0, 2.0 * (double)L.raw_bytes, k_pngd_expand, dim3(gp, n), dim3(256), B);
-  VF_LAUNCH_CHECK();
-  return 0;
+  return pngd_decode(kDefaultRule, ctx, data, offs, n, channels, 0, out_offs, out, stage, stage_bytes, ws, ws_bytes, status);
 }
 
 VF_API int vf_png_inspect_full(const unsigned char* data, size_t len, int64_t* info, int64_t* passes, char* reason, int reason_cap) {
-  VF_REQUIRE(data && info, "vf_png_inspect_full: NULL argument");
-  PngParsed P;
-  std::string msg;
-  const int rc = png_parse(data, (int64_t)len, P, msg, true);
-  if (rc) {
-    vf_set_error("vf_png_inspect_full: %s", msg.c_str());
-    return rc;
-  }
-  PngFull F;
-  png_full_rule(P, F);
-  const int64_t v[12] = {P.W, P.H, P.depth, P.ctype, P.lace, P.fc, P.idat_bytes, P.idat_chunks, P.nplte, P.ntrns, F.supported ? 1 : 0,
-                         F.inflated};
-  memcpy(info, v, sizeof v);
-  for (int p = 0; passes && p < 7; ++p) {
-    passes[3 * p] = F.w[p];
-    passes[3 * p + 1] = F.h[p];
-    passes[3 * p + 2] = F.rb[p];
-  }
-  if (reason && reason_cap > 0) snprintf(reason, (size_t)reason_cap, "%s", F.why.c_str());
-  return 0;
+  return png_inspect("vf_png_inspect_full", kFullRule, data, len, info, passes, reason, reason_cap);
 }
 
 VF_API int vf_png_decode_full_workspace_bytes(const unsigned char* data, const int64_t* offs, int n, int channels, int out_kind,
                                               size_t* ws_bytes, size_t* stage_bytes) {
-  PngdFullPlan L;
-  if (int e = pngd_plan_full(data, offs, n, channels, out_kind, L, false)) return e;   // vf_png_decode_full checks the CRCs
-  if (ws_bytes) *ws_bytes = L.ws;
-  if (stage_bytes) *stage_bytes = L.stage;
-  return 0;
+  return pngd_query(kFullRule, data, offs, n, channels, out_kind, ws_bytes, stage_bytes);
 }
 
 VF_API int vf_png_decode_full(vf_ctx* ctx, const unsigned char* data, const int64_t* offs, int n, int channels, int out_kind,
                               const int64_t* out_offs, void* out, void* stage, size_t stage_bytes, void* ws, size_t ws_bytes,
                               int32_t* status) {
-  VF_REQUIRE(out && out_offs && stage && ws && status, "vf_png_decode_full: NULL argument");
-  PngdFullPlan L;
-  if (int e = pngd_plan_full(data, offs, n, channels, out_kind, L, true)) return e;
-  VF_REQUIRE(stage_bytes >= L.stage && ws_bytes >= L.ws, "vf_png_decode_full: staging %zu / workspace %zu bytes, need %zu / %zu",
-             stage_bytes, ws_bytes, L.stage, L.ws);
-  pngd_pack_full(data, offs, n, out_kind, out_offs, L, (uint8_t*)stage);
-  uint8_t* w = (uint8_t*)ws;
-  PngdFullBatch B;
-  B.img = (const PngdFull*)(w + L.o_img);
-  B.streams = w + L.o_streams;
-  B.inf = w + L.o_inf;
-  B.raw = w + L.o_raw;
-  B.out = (uint8_t*)out;
-  B.status = status;
-  hipStream_t st = ctx->stream;
-  {
-    VfRange r("pngd_upload");
-    VF_CHECK_HIP(hipMemcpyAsync(w, stage, L.stage, hipMemcpyHostToDevice, st));
-    VF_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t) * n, st));
-  }
-  const double inf = (double)L.inf_bytes;
-  VF_LAUNCH_TIMED(ctx, "pngd_inflate", 0.0, (double)L.stream_bytes + inf, k_pngd_inflate<PngdFull>, dim3((unsigned)n), dim3(kInfThreads), B);
-  VF_LAUNCH_CHECK();
-  VF_LAUNCH_TIMED(ctx, "pngd_unfilter_full", 0.0, 2.0 * inf, k_pngd_unfilter_full, dim3(7u * (unsigned)n), dim3(64), B);
-  VF_LAUNCH_CHECK();
-  const unsigned gp = (unsigned)std::min<int64_t>(std::max<int64_t>(1, vf_cdiv(L.max_pix, 256)), 4096);
-  VF_LAUNCH_TIMED(ctx, "pngd_expand_full", 0.0, 2.0 * (double)L.raw_bytes, k_pngd_expand_full, dim3(gp, n), dim3(256), B);
-  VF_LAUNCH_CHECK();
-  return 0;
+  return pngd_decode(kFullRule, ctx, data, offs, n, channels, out_kind, out_offs, out, stage, stage_bytes, ws, ws_bytes, status);
 }
 
 VF_API int vf_png_bytes_to_float(vf_ctx* ctx, const unsigned char* src, float* dst, int64_t n) {
