@@ -2,11 +2,14 @@
 tests/test_gpu_nonsquare.py's business: exact and fp64 checks of every route): every conv pass of the C-ABI on
 NON-SQUARE maps with Cin != Cout, the bottleneck and head geometries, the generic path, the planes passes, pending BatchNorm
 requests, vf_net with the planes gate dropped, weight-gradient groups under small workspaces and with every route in one walk
-— raw output bytes, and the messages of the calls that are refused.
+— raw output bytes, and the messages of the calls that are refused; and, per case of tests/route_cases.py (`pass_routes`), the
+profiler's launch list beside the output: the patch-fed planes kernels are bit-identical to k_pconv_dma by design, so equal bytes
+alone do not show that the same kernel ran.
 
     VF_HIP_LIB=/path/to/other/libvf_hip.so python scripts/ab_conv_outputs.py dump a.npz      # one fresh process per build
     python scripts/ab_conv_outputs.py dump b.npz                                             # the in-tree build
     python scripts/ab_conv_outputs.py compare a.npz b.npz [result.json]                      # byte for byte; exit 1 on a mismatch
+    VF_HIP_LIB=/path/to/parent/libvf_hip.so python scripts/ab_conv_outputs.py record-routes  # tests/golden/conv_routes.json
 
 The criterion is equality between the builds, not correctness: a shape one build refuses or gets wrong must be refused or wrong
 identically by the other (the tool of a refactoring of the host code: profiles/README.md, "One conv geometry type")."""
@@ -21,6 +24,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 MAPS = [(2, 8, 16), (3, 16, 4)]                                        # (B, H, W): both orders of a non-square map, two batches
 CHANNELS = [(3, 64), (32, 33), (64, 128), (128, 4), (64, 1), (128, 64)]     # Cin != Cout
@@ -54,7 +58,7 @@ class Dump:
     def keep(self, name, *tensors):
         assert name not in self.out, name
         torch.cuda.synchronize()
-        self.out[name] = np.concatenate([t.detach().contiguous().view(torch.uint8).reshape(-1).cpu().numpy() if torch.is_tensor(t)
+        self.out[name] = np.concatenate([t.detach().contiguous().reshape(-1).view(torch.uint8).cpu().numpy() if torch.is_tensor(t)
                                          else np.frombuffer(np.asarray(t).tobytes(), np.uint8) for t in tensors] or [np.zeros(0, np.uint8)])
 
     def run(self, name, fn, *tensors):
@@ -387,6 +391,42 @@ def wgrad_groups(d):
     hb.set_mfma_mode("f32_3xbf16")
 
 
+def pass_routes(d):
+    """every case of tests/route_cases.py: what the pass wrote, and its launch list (name, launches, flops, bytes) as JSON text"""
+    import route_cases as RC
+    for c in RC.CASES:
+        res = {}
+
+        def go():
+            res["rec"], res["written"] = RC.run_case(d.B, c)
+        if d.run("pass_routes/" + c["id"], go):
+            d.keep("pass_routes/%s/tensors" % c["id"], *res["written"])
+            d.out["pass_routes/%s/launches" % c["id"]] = np.frombuffer(json.dumps(res["rec"], sort_keys=True).encode(), np.uint8)
+
+
+def record_routes():
+    """tests/golden/conv_routes.json: per case the enumerators it stands for and the launch list of THIS process's library — the
+    parent commit's, through VF_HIP_LIB, when the table is recorded for a change of the plan functions"""
+    import route_cases as RC
+    from video_filler_amd import _lib
+    from video_filler_amd.backend import HipBackend
+    hb = HipBackend(workspace_bytes=1 << 20)
+    cases, wrong = {}, []
+    for c in RC.CASES:
+        rec, _ = RC.run_case(hb, c)
+        try:
+            RC.check_routes(c, rec)
+        except AssertionError as e:      # the case list is wrong about this library: say so for every case, then fail
+            wrong.append(str(e))
+        cases[c["id"]] = {"routes": c["routes"], "launches": rec}
+    with open(RC.GOLDEN, "w") as fh:
+        json.dump({"cases": cases}, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("%s: %d cases, library %s" % (RC.GOLDEN, len(cases), _lib.lib_path()))
+    if wrong:
+        sys.exit("\n".join(wrong))
+
+
 def dump(path):
     from video_filler_amd import _lib, nn
     from video_filler_amd.backend import get_backend
@@ -421,6 +461,7 @@ def dump(path):
             net_passes(d, "%s/%s/net_head_B3" % (mode, gname), head, (3, 3, 16, 16))
             net_passes(d, "%s/%s/net_bottleneck_B3" % (mode, gname), bottleneck, (3, 32, 8, 8))
     wgrad_groups(d)
+    pass_routes(d)
     np.savez(path, **d.out)
     n = sum(1 for k in d.out if k.startswith("refused:"))
     print("%s: %d records (%d refused), %d bytes, library %s" % (path, len(d.out), n, sum(v.size for v in d.out.values()), _lib.lib_path()))
@@ -452,6 +493,8 @@ def compare(pa, pb, out_json=None):
 if __name__ == "__main__":
     if len(sys.argv) >= 3 and sys.argv[1] == "dump":
         dump(sys.argv[2])
+    elif len(sys.argv) >= 2 and sys.argv[1] == "record-routes":
+        record_routes()
     elif len(sys.argv) >= 4 and sys.argv[1] == "compare":
         sys.exit(compare(sys.argv[2], sys.argv[3], sys.argv[4] if len(sys.argv) > 4 else None))
     else:

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -240,33 +241,78 @@ struct VfWpDesc {
 };
 static_assert(sizeof(VfWpDesc) == 48, "descriptor layout is shared with the host mirror");
 
-// The statistics plan of a GEMM launch (launch_igemm's IGemm, launch_pconv's PGemm; g.ksplit is set, bm x . tiles in gm rows,
-// zpar parity classes).  With one K range per tile the epilogue leaves a partial row per row tile and parity class, where the
-// batch groups are whole tiles; under split-K the slab reduce leaves them (returns true: the combine gets &g.st).  A shape that
-// fits neither, or no request (ex NULL: an inner launch), leaves g.st.mode 0.  Mode 2 stores the output masked by the
-// activation derivative: what BatchNorm's backward sums.
+// The split-K count of a GEMM launch, written once for ig_plan, wg_plan (vf_conv.hip) and pg_plan (vf_pgemm.hip): a grid below
+// three quarters of `target` blocks, with at least min_nk K steps, is split into up to nk / k_per_split ranges — as many as bring
+// it to the target and whose slabs (slab_bytes each) fit the workspace — and the ranges are then shaped by the caller's rule.
+enum VfKRanges {
+  VF_K_EVEN_OUT,      // ceil(nk / ksplit) steps per range, no empty trailing range
+  VF_K_WHOLE_EQUAL    // ksplit divides nk: every tile runs the same number of steps
+};
+static inline int vf_split_k(int64_t blocks, int target, int nk, int min_nk, int k_per_split, size_t slab_bytes, size_t ws_avail,
+                             VfKRanges rule) {
+  if (!(blocks < target * 3 / 4 && nk >= min_nk)) return 1;
+  int ksplit = (int)std::min<int64_t>(nk / k_per_split, vf_cdiv(target, blocks));
+  while (ksplit > 1 && (size_t)ksplit * slab_bytes > ws_avail) --ksplit;
+  if (rule == VF_K_WHOLE_EQUAL) {
+    while (ksplit > 1 && nk % ksplit != 0) --ksplit;
+    return ksplit;
+  }
+  if (ksplit < 1) ksplit = 1;
+  const int steps = (int)vf_cdiv(nk, ksplit);
+  return (int)vf_cdiv(nk, steps);
+}
+
+// The statistics plan of a GEMM launch (ig_plan's IGemm, pg_plan's PGemm; bm x . tiles in gm rows, zpar parity classes, ksplit K
+// ranges), as data: st.mode 0 is "none".  With one K range per tile the epilogue leaves a partial row per row tile and parity
+// class, where the batch groups are whole tiles; under split-K the slab reduce leaves them (`slab`: the combine gets &st).  A
+// shape that fits neither, or no request (r NULL: an inner launch), gives mode 0.  Mode 2 stores the output masked by the
+// activation derivative, what BatchNorm's backward sums: dmask / dact / dslope are the launch's mask either way.
+struct VfBnStPlan {
+  VfBnSt st = {};
+  bool slab = false;
+  const float* dmask = nullptr;
+  int dact = 0;
+  float dslope = 0.f;
+};
 template <class G>
-static inline bool vf_plan_bn_stats(VfConvExtras* ex, G& g, int bm, int gm, int zpar) {
-  g.st.mode = 0;
-  if (!ex || !ex->bn.st.mode) return false;
-  const VfBnRequest& r = ex->bn;
-  VfBnSt st = r.st;
-  st.zpar = g.ksplit == 1 ? zpar : 1;
-  if (g.ksplit == 1) {
-    if (g.M % r.groups != 0 || (g.M / r.groups) % bm != 0 || (int64_t)(gm / r.groups) * zpar > r.rows_cap) return false;
-    st.tiles_per_group = gm / r.groups;
-  } else if (!vf_internal_slab_st_ok(g.out_elems, g.N, r.groups, r.rows_cap, &st.tiles_per_group)) {
-    return false;
+static inline VfBnStPlan vf_plan_bn_stats(const VfBnRequest* r, const G& g, int ksplit, int bm, int gm, int zpar) {
+  VfBnStPlan p;
+  p.dmask = g.dmask; p.dact = g.dact; p.dslope = g.dslope;
+  if (!r || !r->st.mode) return p;
+  VfBnSt st = r->st;
+  st.zpar = ksplit == 1 ? zpar : 1;
+  if (ksplit == 1) {
+    if (g.M % r->groups != 0 || (g.M / r->groups) % bm != 0 || (int64_t)(gm / r->groups) * zpar > r->rows_cap) return p;
+    st.tiles_per_group = gm / r->groups;
+  } else if (!vf_internal_slab_st_ok(g.out_elems, g.N, r->groups, r->rows_cap, &st.tiles_per_group)) {
+    return p;
   }
   st.rows_per_group = st.tiles_per_group * st.zpar;
-  g.st = st;
-  ex->bn_result_rows = st.rows_per_group;
+  p.st = st;
   if (st.mode == 2) {
-    g.dmask = r.yact;
-    g.dact = r.act;
-    g.dslope = r.slope;
+    p.dmask = r->yact; p.dact = r->act; p.dslope = r->slope;
   }
-  return g.ksplit > 1;
+  p.slab = ksplit > 1;
+  return p;
+}
+// ... and its one writer: the launch step, once the pass is certain to launch, puts the plan into the kernel's arguments and tells
+// the caller's extras what it will find
+template <class G>
+static inline void vf_take_bn_stats(const VfBnStPlan& p, G& g, VfConvExtras* ex) {
+  g.st = p.st;
+  g.dmask = p.dmask; g.dact = p.dact; g.dslope = p.dslope;
+  if (p.st.mode) ex->bn_result_rows = p.st.rows_per_group;
+}
+// The tail of a split-K launch (kind: "igemm" or "pconv", the profiling label): the slabs are combined in a fixed order, with the
+// BatchNorm partials where the plan left them to this pass
+template <class G>
+static inline int vf_combine_slabs(vf_ctx* ctx, const char* kind, const G& g, bool slab_st, int groups) {
+  if (g.ksplit <= 1) return 0;
+  char label[48];
+  snprintf(label, sizeof(label), "slab_reduce_%s%s", kind, slab_st ? "_bnstats" : "");
+  VfProf prof(ctx, label, 0.0, 4.0 * (double)g.out_elems * (g.ksplit + 1));
+  return vf_internal_slab_reduce(ctx, g.slab, g.Y, g.bias, g.out_elems, g.N, g.ksplit, g.act, g.slope, g.dmask, g.dact, g.dslope,
+                                 slab_st ? &g.st : nullptr, slab_st ? groups : 1);
 }
 
 // optim/adam.lua's element update, fp32 in the reference's operation order (one definition for k_adam and for the weight-gradient

@@ -1299,67 +1299,42 @@ __global__ __launch_bounds__(256) void k_col2im4x4(const float* __restrict__ col
 }
 
 // ================================================================================================ host
-template <int BM, int BN, int WM, int WN, int BF>
-static void launch_igemm_tile_m(vf_ctx* ctx, const IGemm& g, dim3 grid, bool bkm, int v, const char* name, double flops,
-                                bool db = false) {
-  dim3 block(256);
-  // algorithmic bytes: both operands and the output once (small-batch passes over the bottleneck weights are bounded by these,
-  // not by the matrix pipe: bench.py prices a kernel against whichever of its two rooflines is the longer)
-  const double bytes = (double)g.a_bytes + (double)g.w_bytes + 4.0 * (double)g.out_elems;
-  if constexpr (BF == 3 && BM == 64 && BN == 64) {
-    if (db && v == 2) {
-      if (!bkm)
-        VF_LAUNCH_TIMED(ctx, name, flops, bytes, (k_igemm<BM, BN, WM, WN, false, 2, 3, false, true>), grid, block, g);
-      else
-        VF_LAUNCH_TIMED(ctx, name, flops, bytes, (k_igemm<BM, BN, WM, WN, true, 2, 3, false, true>), grid, block, g);
-      return;
-    }
-  }
-  if constexpr (BM == 64 && BN == 128) {
-    if (g.klin && !bkm && v == 2) {
-      VF_LAUNCH_TIMED(ctx, name, flops, bytes, (k_igemm<BM, BN, WM, WN, false, 2, BF, true>), grid, block, g);
-      return;
-    }
-  }
-  if (!bkm) {
-    if (v == 2)
-      VF_LAUNCH_TIMED(ctx, name, flops, bytes, (k_igemm<BM, BN, WM, WN, false, 2, BF>), grid, block, g);
-    else
-      VF_LAUNCH_TIMED(ctx, name, flops, bytes, (k_igemm<BM, BN, WM, WN, false, 0, BF>), grid, block, g);
-  } else {
-    if (v == 2)
-      VF_LAUNCH_TIMED(ctx, name, flops, bytes, (k_igemm<BM, BN, WM, WN, true, 2, BF>), grid, block, g);
-    else if (v == 1)
-      VF_LAUNCH_TIMED(ctx, name, flops, bytes, (k_igemm<BM, BN, WM, WN, true, 1, BF>), grid, block, g);
-    else
-      VF_LAUNCH_TIMED(ctx, name, flops, bytes, (k_igemm<BM, BN, WM, WN, true, 0, BF>), grid, block, g);
-  }
-}
-template <int BM, int BN, int WM, int WN>
-static void launch_igemm_tile(vf_ctx* ctx, const IGemm& g, dim3 grid, bool bkm, int v, const char* name, double flops,
-                              bool db = false) {
-  if (ctx->mfma_bf16 == 3)
-    launch_igemm_tile_m<BM, BN, WM, WN, 3>(ctx, g, grid, bkm, v, name, flops, db);
-  else if (ctx->mfma_bf16 == 1)
-    launch_igemm_tile_m<BM, BN, WM, WN, 1>(ctx, g, grid, bkm, v, name, flops);
-  else
-    launch_igemm_tile_m<BM, BN, WM, WN, 0>(ctx, g, grid, bkm, v, name, flops);
-}
-
-// vecA / vecB: 16-byte loads legal for the A / B operand.  ex: the extras of the pass whose output tensor this launch writes
-// (BatchNorm statistics: vf_plan_bn_stats); NULL for an inner GEMM into a column buffer.
-static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, VfConvExtras* ex) {
+// ---- the plan of one k_igemm pass: vector form, tile, split over K, the kernel form that serves it, what the profiler is told.
+// One enumerator per kernel form; DESIGN.md 4.1 is read from ig_plan() below.
+enum IgRoute {
+  IG_TILE,              // k_igemm on the planned tile
+  IG_TILE_KLIN,         //   ... K walked in memory order: the 64 x 128 tile of the 1x1-output bottleneck layers
+  IG_TILE_DB,           //   ... the double-buffered schedule: mode 3's 64 x 64 tile on grids of at most two blocks per CU
+  IG_SMALLM_ROWS,       // the bottleneck GEMMs at a small batch: vf_smallm.hip's weight-streaming kernel, weight rows of K floats
+  IG_SMALLM_KMAJOR      //   ... weights [C][N], N contiguous
+};
+struct IgPlan {
+  bool bkm;                    // B operand k-major (the transposed passes)
+  int64_t a_elems, w_elems;
+  int v, nq, nk, Ktot;         // vector form (k_igemm's V), 16-wide chunks, K steps, K
+  int bm, bn;                  // block tile
+  int ksplit, gm, gn, gz;
+  bool klin, db;
+  IgRoute route;
+  VfBnStPlan stats;             // BatchNorm statistics as a by-product: from the epilogue, or from the slab reduce under split-K
+  dim3 grid;
+  char name[64];               // one name per kernel symbol (what rocprofv3 lists): k_igemm<bm, bn, ., ., kmajorB, v, mode>
+  double flops, bytes;
+  bool in_range() const { return a_elems < ((int64_t)1 << 29) && w_elems < ((int64_t)1 << 29); }      // a buffer descriptor spans 2 GiB
+  bool smallm() const { return route == IG_SMALLM_ROWS || route == IG_SMALLM_KMAJOR; }
+};
+// g: the geometry; vecA / vecB: 16-byte loads legal for the A / B operand; mode: the product mode; req: the pending BatchNorm
+// request, or NULL.  Launches nothing and writes nothing: launch_igemm takes the plan into `g` and the caller's extras.
+static IgPlan ig_plan(const IGemm& g, bool vecA, bool vecB, int mode, size_t ws_avail, const VfBnRequest* req) {
+  IgPlan p;
   const int zpar = g.parity ? 4 : 1;
-  const bool bkm = g.wsN == 1 && g.wsC != 1;
-  const int64_t a_elems = (int64_t)(g.M >> (g.lgMh + g.lgMw)) * g.Hi * g.Wi * g.C;
-  const int64_t w_elems = bkm ? (int64_t)g.C * g.wsC : (int64_t)g.N * g.wsN;
-  VF_REQUIRE(a_elems < ((int64_t)1 << 29) && w_elems < ((int64_t)1 << 29), "operand exceeds the 2 GiB buffer-descriptor range");
-  g.a_bytes = (unsigned)(a_elems * 4);
-  g.w_bytes = (unsigned)(w_elems * 4);
-  int v = (vecA && vecB) ? 2 : ((vecA && bkm) ? 1 : 0);
-  const int Ktot = g.TH * g.TW * g.C;
-  g.nq = g.TH * g.TW * (g.C / 16);
-  g.nk = v >= 1 ? (g.nq + 1) / 2 : (int)vf_cdiv(Ktot, 32);
+  p.bkm = g.wsN == 1 && g.wsC != 1;
+  p.a_elems = (int64_t)(g.M >> (g.lgMh + g.lgMw)) * g.Hi * g.Wi * g.C;
+  p.w_elems = p.bkm ? (int64_t)g.C * g.wsC : (int64_t)g.N * g.wsN;
+  p.v = (vecA && vecB) ? 2 : ((vecA && p.bkm) ? 1 : 0);
+  p.Ktot = g.TH * g.TW * g.C;
+  p.nq = g.TH * g.TW * (g.C / 16);
+  p.nk = p.v >= 1 ? (p.nq + 1) / 2 : (int)vf_cdiv(p.Ktot, 32);
   // ---- tile selection: the largest tile that still gives >= 2 blocks per CU, else the smallest + split-K
   struct Tile { int bm, bn; };
   Tile t;
@@ -1371,13 +1346,13 @@ static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, VfConvExtra
     const Tile cand[3] = {{128, 128}, {128, 64}, {64, 64}};
     // mode 3's single-buffered three-plane tiles hide their two barriers per K step with co-resident blocks: they want
     // twice the blocks (measured: +2 % per step at 1024 and above)
-    const int min_blocks = ctx->mfma_bf16 == 3 ? 1024 : 512;
+    const int min_blocks = mode == 3 ? 1024 : 512;
     int pick = 2;
     for (int i = 0; i < 3; ++i) {
       if (cand[i].bn > 64 && g.N <= 64) continue;
       // a short K loop (<= 8 steps: the 64-channel transposed passes) leaves a 128-row block mostly prologue and
       // epilogue; four 64x64 blocks per CU cover each other's ends better (E2 data-gradient: 122 -> 112 us)
-      if (g.parity && g.nk <= 8 && cand[i].bm > 64) continue;
+      if (g.parity && p.nk <= 8 && cand[i].bm > 64) continue;
       const int64_t blocks = vf_cdiv(g.M, cand[i].bm) * vf_cdiv(g.N, cand[i].bn) * zpar;
       if (blocks >= min_blocks) {
         pick = i;
@@ -1388,68 +1363,101 @@ static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, VfConvExtra
     // (tried: 256 x 64 tiles — four 64x64 wave tiles stacked in M, one block per CU — for the N = 64 layers: 153 us
     //  against 125 us for E2's data-gradient; one wave per SIMD does not cover its own LDS/global latency)
   }
+  p.bm = t.bm; p.bn = t.bn;
   constexpr int split_blocks = 512;     // (768 for the M <= 64 GEMMs: a wash)
-  const int gm = (int)vf_cdiv(g.M, t.bm), gn = (int)vf_cdiv(g.N, t.bn);
-  const int64_t blocks = (int64_t)gm * gn * zpar;
-  int ksplit = 1;
-  if (blocks < split_blocks * 3 / 4 && g.nk >= 8) {
-    ksplit = (int)std::min<int64_t>(g.nk / 4, vf_cdiv(split_blocks, blocks));
-    const size_t slab_bytes = (size_t)g.out_elems * sizeof(float);
-    while (ksplit > 1 && (size_t)ksplit * slab_bytes > vf_ws_avail(ctx)) --ksplit;
-    if (ksplit < 1) ksplit = 1;
-    const int steps = (int)vf_cdiv(g.nk, ksplit);  // avoid empty trailing splits
-    ksplit = (int)vf_cdiv(g.nk, steps);
-  }
+  p.gm = (int)vf_cdiv(g.M, t.bm);
+  p.gn = (int)vf_cdiv(g.N, t.bn);
+  const int64_t blocks = (int64_t)p.gm * p.gn * zpar;
+  p.ksplit = vf_split_k(blocks, split_blocks, p.nk, 8, 4, (size_t)g.out_elems * sizeof(float), ws_avail, VF_K_EVEN_OUT);
   // ---- the bottleneck GEMMs at a small batch (M <= 8 rows against hundreds of MB of weights): a weight-streaming kernel instead
-  // of a tile (vf_smallm.hip); it leaves split-K slabs, which the combine below takes like the tiled kernel's
+  // of a tile (vf_smallm.hip); it leaves split-K slabs, which the combine takes like the tiled kernel's
   int sm_form = -1;
-  if (!g.parity && g.lgMh == 0 && g.lgMw == 0 && g.M <= 8 && v == 2) {
-    if (!bkm && g.Hi == g.TH && g.Wi == g.TW && g.oy0 == 0 && g.ox0 == 0 && g.sy == 1 && g.sx == 1 && g.ty == 1 && g.tx == 1 && g.wsC == 1 &&
-        g.wsTap == g.C && g.wsN == Ktot && g.kh0 == 0 && g.kw0 == 0 && g.khs == 1 && g.kws == 1)
+  if (!g.parity && g.lgMh == 0 && g.lgMw == 0 && g.M <= 8 && p.v == 2) {
+    if (!p.bkm && g.Hi == g.TH && g.Wi == g.TW && g.oy0 == 0 && g.ox0 == 0 && g.sy == 1 && g.sx == 1 && g.ty == 1 && g.tx == 1 && g.wsC == 1 &&
+        g.wsTap == g.C && g.wsN == p.Ktot && g.kh0 == 0 && g.kw0 == 0 && g.khs == 1 && g.kws == 1)
       sm_form = 0;        // A rows and weight rows are K = taps * C contiguous floats
-    else if (bkm && g.TH * g.TW == 1 && g.Hi == 1 && g.Wi == 1 && g.wsC == g.N)
+    else if (p.bkm && g.TH * g.TW == 1 && g.Hi == 1 && g.Wi == 1 && g.wsC == g.N)
       sm_form = 1;        // weights [C][N], N contiguous
     if (sm_form >= 0) {
-      const int s = vf_internal_smallm_plan(sm_form, g.M, g.N, Ktot, vf_ws_avail(ctx));
-      if (s >= 2) ksplit = s;
+      const int s = vf_internal_smallm_plan(sm_form, g.M, g.N, p.Ktot, ws_avail);
+      if (s >= 2) p.ksplit = s;
       else sm_form = -1;
     }
   }
-  g.ksplit = ksplit;
-  g.slab = ksplit > 1 ? (float*)vf_ws_ptr(ctx) : nullptr;
-  // ---- BatchNorm statistics as a by-product: from the epilogue, or from the slab reduce under split-K
-  const bool slab_st = vf_plan_bn_stats(ex, g, t.bm, gm, zpar);
-  g.klin = !g.parity && g.lgMh == 0 && g.lgMw == 0 && g.TH * g.TW > 1 && t.bm == 64 && t.bn == 128 && !bkm && v == 2;
-  g.gm = gm; g.gn = gn; g.gz = zpar * ksplit;
-  dim3 grid((unsigned)gm * gn * zpar * ksplit);
-  char pname[64];
-  // one name per kernel symbol (what rocprofv3 lists): k_igemm<bm, bn, ., ., kmajorB, v, mode>
+  p.stats = vf_plan_bn_stats(req, g, p.ksplit, t.bm, p.gm, zpar);
+  p.klin = !g.parity && g.lgMh == 0 && g.lgMw == 0 && g.TH * g.TW > 1 && t.bm == 64 && t.bn == 128 && !p.bkm && p.v == 2;
+  p.gz = zpar * p.ksplit;
+  p.grid = dim3((unsigned)p.gm * p.gn * zpar * p.ksplit);
   // double-buffered schedule: where the grid leaves at most two blocks per CU anyway (its 66 KB tiles cost nothing then)
-  const bool db = ctx->mfma_bf16 == 3 && v == 2 && t.bm == 64 && t.bn == 64 && (int64_t)grid.x <= 2 * 256;
-  snprintf(pname, sizeof(pname), "igemm_%dx%d_%s_v%d%s%s", t.bm, t.bn, bkm ? "kmajorB" : "rowB", v,
-           ctx->mfma_bf16 == 3 ? "_bf16x3" : (ctx->mfma_bf16 ? "_bf16" : ""), db ? "_db" : "");
-  if (sm_form >= 0) {
-    if (int rc = vf_internal_smallm_launch(ctx, sm_form, g.A, g.Wt, g.slab, g.M, g.N, Ktot, ksplit)) return rc;
+  p.db = mode == 3 && p.v == 2 && t.bm == 64 && t.bn == 64 && (int64_t)p.grid.x <= 2 * 256;
+  p.route = sm_form == 0 ? IG_SMALLM_ROWS : sm_form == 1 ? IG_SMALLM_KMAJOR : p.db ? IG_TILE_DB : p.klin ? IG_TILE_KLIN : IG_TILE;
+  snprintf(p.name, sizeof(p.name), "igemm_%dx%d_%s_v%d%s%s", t.bm, t.bn, p.bkm ? "kmajorB" : "rowB", p.v,
+           mode == 3 ? "_bf16x3" : (mode ? "_bf16" : ""), p.db ? "_db" : "");
+  p.flops = 2.0 * (double)g.M * g.N * p.Ktot * zpar;
+  // algorithmic bytes: both operands and the output once (small-batch passes over the bottleneck weights are bounded by these,
+  // not by the matrix pipe: bench.py prices a kernel against whichever of its two rooflines is the longer)
+  p.bytes = 4.0 * (double)p.a_elems + 4.0 * (double)p.w_elems + 4.0 * (double)g.out_elems;
+  return p;
+}
+
+// route -> kernel: every k_igemm instantiation the library holds, keyed by what ig_plan decides.  Per tile and product mode:
+// row-major B at V = 2 / 0 and k-major B at V = 2 / 1 / 0; besides them the K-in-memory-order form of the 64 x 128 tile and the
+// double-buffered form of mode 3's 64 x 64 tile.  (Wave tiles: four waves of 32 x 32 MFMA tiles per block.)
+typedef void (*IgKernel)(IGemm);
+struct IgEntry {
+  int bm, bn, mode;
+  IgRoute route;
+  bool bkm;
+  int v;
+  IgKernel kernel;
+};
+#define IG_TILE_ROWS(BM, BN, WM, WN, BF)                                    \
+  {BM, BN, BF, IG_TILE, false, 2, k_igemm<BM, BN, WM, WN, false, 2, BF>},   \
+  {BM, BN, BF, IG_TILE, false, 0, k_igemm<BM, BN, WM, WN, false, 0, BF>},   \
+  {BM, BN, BF, IG_TILE, true, 2, k_igemm<BM, BN, WM, WN, true, 2, BF>},     \
+  {BM, BN, BF, IG_TILE, true, 1, k_igemm<BM, BN, WM, WN, true, 1, BF>},     \
+  {BM, BN, BF, IG_TILE, true, 0, k_igemm<BM, BN, WM, WN, true, 0, BF>}
+#define IG_KLIN_ROW(BF) {64, 128, BF, IG_TILE_KLIN, false, 2, k_igemm<64, 128, 64, 32, false, 2, BF, true>}
+static const IgEntry ig_table[] = {
+    IG_TILE_ROWS(256, 32, 64, 32, 3), IG_TILE_ROWS(256, 32, 64, 32, 1), IG_TILE_ROWS(256, 32, 64, 32, 0),
+    IG_TILE_ROWS(128, 128, 64, 64, 3), IG_TILE_ROWS(128, 128, 64, 64, 1), IG_TILE_ROWS(128, 128, 64, 64, 0),
+    IG_TILE_ROWS(128, 64, 64, 32, 3), IG_TILE_ROWS(128, 64, 64, 32, 1), IG_TILE_ROWS(128, 64, 64, 32, 0),
+    IG_KLIN_ROW(3), IG_TILE_ROWS(64, 128, 64, 32, 3), IG_KLIN_ROW(1), IG_TILE_ROWS(64, 128, 64, 32, 1),
+    IG_KLIN_ROW(0), IG_TILE_ROWS(64, 128, 64, 32, 0),
+    {64, 64, 3, IG_TILE_DB, false, 2, k_igemm<64, 64, 32, 32, false, 2, 3, false, true>},
+    {64, 64, 3, IG_TILE_DB, true, 2, k_igemm<64, 64, 32, 32, true, 2, 3, false, true>},
+    IG_TILE_ROWS(64, 64, 32, 32, 3), IG_TILE_ROWS(64, 64, 32, 32, 1), IG_TILE_ROWS(64, 64, 32, 32, 0),
+};
+#undef IG_TILE_ROWS
+#undef IG_KLIN_ROW
+// NULL where the table holds no such row (a plan that ig_plan does not make): the launch then fails its check
+static IgKernel ig_kernel(const IgPlan& p, int mode) {
+  for (const IgEntry& e : ig_table)
+    if (e.bm == p.bm && e.bn == p.bn && e.mode == (mode == 3 ? 3 : mode ? 1 : 0) && e.route == p.route && e.bkm == p.bkm && e.v == p.v)
+      return e.kernel;
+  return nullptr;
+}
+
+// ex: the extras of the pass whose output tensor this launch writes (BatchNorm statistics: vf_plan_bn_stats); NULL for an inner
+// GEMM into a column buffer.
+static int launch_igemm(vf_ctx* ctx, IGemm& g, bool vecA, bool vecB, VfConvExtras* ex) {
+  const IgPlan p = ig_plan(g, vecA, vecB, ctx->mfma_bf16, vf_ws_avail(ctx), ex ? &ex->bn : nullptr);
+  VF_REQUIRE(p.in_range(), "operand exceeds the 2 GiB buffer-descriptor range");
+  g.a_bytes = (unsigned)(p.a_elems * 4);
+  g.w_bytes = (unsigned)(p.w_elems * 4);
+  g.nq = p.nq; g.nk = p.nk;
+  g.ksplit = p.ksplit;
+  g.slab = p.ksplit > 1 ? (float*)vf_ws_ptr(ctx) : nullptr;
+  g.klin = p.klin;
+  g.gm = p.gm; g.gn = p.gn; g.gz = p.gz;
+  vf_take_bn_stats(p.stats, g, ex);
+  if (p.smallm()) {
+    if (int rc = vf_internal_smallm_launch(ctx, p.route == IG_SMALLM_ROWS ? 0 : 1, g.A, g.Wt, g.slab, g.M, g.N, p.Ktot, p.ksplit)) return rc;
   } else {
-    const double fl = 2.0 * (double)g.M * g.N * Ktot * zpar;
-    if (t.bm == 256)
-      launch_igemm_tile<256, 32, 64, 32>(ctx, g, grid, bkm, v, pname, fl);
-    else if (t.bm == 128 && t.bn == 128)
-      launch_igemm_tile<128, 128, 64, 64>(ctx, g, grid, bkm, v, pname, fl);
-    else if (t.bm == 128)
-      launch_igemm_tile<128, 64, 64, 32>(ctx, g, grid, bkm, v, pname, fl);
-    else if (t.bn == 128)
-      launch_igemm_tile<64, 128, 64, 32>(ctx, g, grid, bkm, v, pname, fl);
-    else
-      launch_igemm_tile<64, 64, 32, 32>(ctx, g, grid, bkm, v, pname, fl, db);
+    VF_LAUNCH_TIMED(ctx, p.name, p.flops, p.bytes, ig_kernel(p, ctx->mfma_bf16), p.grid, dim3(256), g);
   }
   VF_LAUNCH_CHECK();
-  if (ksplit > 1) {
-    VfProf prof(ctx, slab_st ? "slab_reduce_igemm_bnstats" : "slab_reduce_igemm", 0.0, 4.0 * (double)g.out_elems * (ksplit + 1));
-    return vf_internal_slab_reduce(ctx, g.slab, g.Y, g.bias, g.out_elems, g.N, ksplit, g.act, g.slope, g.dmask, g.dact, g.dslope,
-                                   slab_st ? &g.st : nullptr, slab_st ? ex->bn.groups : 1);
-  }
-  return 0;
+  return vf_combine_slabs(ctx, "igemm", g, p.stats.slab, p.stats.slab ? ex->bn.groups : 1);
 }
 
 // the split-K combine for vf_pgemm.hip's launches (plain, or leaving BatchNorm statistics partials)
@@ -1536,44 +1544,140 @@ static int check_full_conv_args(const VfConvShape& s) {
   return 0;
 }
 
+// ---- which pass serves a layer in front of (or instead of) the GEMM.  The thin kernels (vf_conv_thin.hip) decline by return
+// value (< 0): where `route` is one of them, `fallback` is what serves the pass if it declines (else fallback == route).
+enum GaRoute {          // gather passes: conv forward, full-conv data-gradient
+  GA_DOT_HEAD,          // the 512 -> 1 head on its 4 x 4 map: k_dot_fwd
+  GA_THIN_IN,           // the 3-channel image side: vf_internal_conv_thin_fwd
+  GA_GEMM               // k_igemm over the 16 taps
+};
+struct GaPlan {
+  GaRoute route, fallback;
+};
+// s: the pass as a conv (k = 4); conv_entry: the conv forward entry (the only one the thin-input kernel serves); stats: a BatchNorm
+// request is pending
+static GaPlan ga_plan(const VfConvShape& s, bool conv_entry, bool stats) {
+  GaPlan p;
+  p.fallback = s.Cout == 1 && s.stride == 1 && s.H == 4 && s.W == 4 ? GA_DOT_HEAD : GA_GEMM;
+  p.route = conv_entry && s.stride == 2 && s.Cin == 3 && !stats ? GA_THIN_IN : p.fallback;
+  return p;
+}
+enum TrRoute {          // transposed passes: conv data-gradient, full-conv forward
+  TR_DOT_HEAD,          // the data-gradient of the 512 -> 1 head: k_dot_bwd_data
+  TR_THIN_OUT,          // the image side (at most 4 output channels): vf_internal_deconv_thin_out
+  TR_COL2IM,            // thin output: a column-buffer GEMM in the workspace, then k_col2im4x4
+  TR_PARITY_GEMM,       // k_igemm, four output-parity classes of 2 x 2 taps each
+  TR_GEMM_1X1           // 1 x 1 -> 4 x 4: a plain GEMM, with a pointwise bias pass behind it where there is a bias
+};
+struct TrPlan {
+  TrRoute route, fallback;
+  size_t col_bytes;     // TR_COL2IM: the column buffer
+};
+// s: the pass as a full-conv (k = 4), A on its H x W map; vecA / alignedW: 16-byte loads of A are legal, w is 16-byte aligned;
+// mask / stats: a derivative mask, a pending BatchNorm request; ws_front / ws_bytes: the workspace's held front and size;
+// conv_grad: the pass is a conv's data-gradient (the head's among them: one gradOutput channel on a 1 x 1 map)
+static TrPlan tr_plan(const VfConvShape& s, bool vecA, bool alignedW, bool mask, bool stats, size_t ws_front, size_t ws_bytes,
+                      bool conv_grad) {
+  TrPlan p;
+  p.col_bytes = 0;
+  if (conv_grad && s.stride == 1 && s.Cin == 1) {
+    p.route = p.fallback = TR_DOT_HEAD;
+    return p;
+  }
+  p.col_bytes = (size_t)s.B * s.H * s.W * 16 * s.Cout * sizeof(float);
+  const bool cols = s.stride == 2 && s.Cout < 32 && vecA && alignedW && ws_front == 0 && p.col_bytes + ((size_t)32 << 20) <= ws_bytes;
+  p.fallback = cols ? TR_COL2IM : s.stride == 2 ? TR_PARITY_GEMM : TR_GEMM_1X1;
+  p.route = s.stride == 2 && s.pad == 1 && s.Cout <= 4 && !mask && !stats ? TR_THIN_OUT : p.fallback;
+  return p;
+}
+
 // Generic "conv-like" pass: Y[b,oy,ox,n] = sum_{kh,kw,c} A[b, oy*s-pad+kh, ox*s-pad+kw, c] * Wt(n,kh,kw,c)
 // (conv forward: A = x, n = Cout, weights [n][kh][kw][c];  full-conv data-grad: A = gy, n = Cin_full,
 //  weights [n][kh][kw][c] as well — same physical layout by construction.)  s: the pass as a conv (k = 4), A on its H x W map.
 static int conv_like_fwd(vf_ctx* ctx, const float* A, const float* w, const float* bias, float* Y, const VfConvShape& s, int act,
-                         float slope, VfConvExtras* ex) {
+                         float slope, VfConvExtras* ex, bool conv_entry = false) {
   const int B = s.B, Hi = s.H, Wi = s.W, C = s.Cin, N = s.Cout, stride = s.stride, pad = s.pad, Ho = s.out_h(), Wo = s.out_w();
-  VF_REQUIRE(vf_is_pow2(Ho) && vf_is_pow2(Wo), "output spatial sizes must be powers of two");
-  if (N == 1 && stride == 1 && Hi == 4 && Wi == 4) {
-    hipLaunchKernelGGL(k_dot_fwd, dim3(B), dim3(256), 0, ctx->stream, A, w, bias, Y, 16 * C, act, slope);
-    VF_LAUNCH_CHECK();
-    return 0;
+  const GaPlan r = ga_plan(s, conv_entry, ex->bn.st.mode != 0);
+  if (r.route == GA_THIN_IN) {      // the image-side layers: direct convolution (vf_conv_thin.hip)
+    const int rc = vf_internal_conv_thin_fwd(ctx, A, w, bias, Y, nullptr, s, act, slope, ex);
+    if (rc >= 0) return rc;
   }
-  IGemm g;
-  memset(&g, 0, sizeof(g));
-  g.A = A; g.Wt = w; g.bias = bias; g.Y = Y;
-  g.lgMh = vf_ilog2(Ho); g.lgMw = vf_ilog2(Wo);
-  g.M = B * Ho * Wo;
-  g.Hi = Hi; g.Wi = Wi; g.C = C; g.N = N;
-  g.TH = 4; g.TW = 4;
-  g.sy = stride; g.ty = 1; g.oy0 = -pad; g.sx = stride; g.tx = 1; g.ox0 = -pad;
-  g.kh0 = 0; g.khs = 1; g.kw0 = 0; g.kws = 1;
-  g.wsN = 16 * C; g.wsC = 1; g.wsTap = C;
-  g.outH = Ho; g.outW = Wo; g.osy = 1; g.osx = 1;
-  g.out_elems = (int64_t)g.M * N;
-  g.act = act; g.slope = slope;
-  return launch_igemm(ctx, g, (C % 16 == 0) && vf_aligned16(A), (C % 16 == 0) && vf_aligned16(w), ex);
+  VF_REQUIRE(vf_is_pow2(Ho) && vf_is_pow2(Wo), "output spatial sizes must be powers of two");
+  switch (r.fallback) {
+    case GA_DOT_HEAD:
+      hipLaunchKernelGGL(k_dot_fwd, dim3(B), dim3(256), 0, ctx->stream, A, w, bias, Y, 16 * C, act, slope);
+      VF_LAUNCH_CHECK();
+      return 0;
+    default: {
+      IGemm g;
+      memset(&g, 0, sizeof(g));
+      g.A = A; g.Wt = w; g.bias = bias; g.Y = Y;
+      g.lgMh = vf_ilog2(Ho); g.lgMw = vf_ilog2(Wo);
+      g.M = B * Ho * Wo;
+      g.Hi = Hi; g.Wi = Wi; g.C = C; g.N = N;
+      g.TH = 4; g.TW = 4;
+      g.sy = stride; g.ty = 1; g.oy0 = -pad; g.sx = stride; g.tx = 1; g.ox0 = -pad;
+      g.kh0 = 0; g.khs = 1; g.kw0 = 0; g.kws = 1;
+      g.wsN = 16 * C; g.wsC = 1; g.wsTap = C;
+      g.outH = Ho; g.outW = Wo; g.osy = 1; g.osx = 1;
+      g.out_elems = (int64_t)g.M * N;
+      g.act = act; g.slope = slope;
+      return launch_igemm(ctx, g, (C % 16 == 0) && vf_aligned16(A), (C % 16 == 0) && vf_aligned16(w), ex);
+    }
+  }
+}
+
+// TR_COL2IM: cols[pixel][(kh,kw,n)] = A[pixel][:] . W[:][(kh,kw,n)]  (columns contiguous in [c][kh][kw][n]), then every output
+// pixel gathers its 4 taps.  The column buffer holds the front of the workspace around the inner GEMM only, whatever that returns.
+static int tr_col2im(vf_ctx* ctx, const TrPlan& r, const float* A, const float* w, const float* bias, float* Y, const VfConvShape& s,
+                     int act, float slope, const float* dmask, int dact, float dslope) {
+  const int B = s.B, Hi = s.H, Wi = s.W, C = s.Cin, N = s.Cout;
+  const int64_t Mi = (int64_t)B * Hi * Wi;
+  float* cols = (float*)ctx->ws;
+  IGemm q;
+  memset(&q, 0, sizeof(q));
+  q.A = A; q.Wt = w; q.bias = nullptr; q.Y = cols;
+  q.M = (int)Mi; q.lgMh = 0; q.lgMw = 0;
+  q.Hi = 1; q.Wi = 1; q.C = C; q.N = 16 * N;
+  q.TH = 1; q.TW = 1; q.sy = 1; q.ty = 1; q.sx = 1; q.tx = 1; q.khs = 1; q.kws = 1;
+  q.wsN = 1; q.wsC = 16 * N; q.wsTap = 0;
+  q.outH = 1; q.outW = 1; q.osy = 1; q.osx = 1;
+  q.out_elems = Mi * 16 * N;
+  q.act = VF_ACT_NONE;
+  ctx->ws_front = (r.col_bytes + 255) & ~(size_t)255;
+  const int rc = launch_igemm(ctx, q, true, true, nullptr);
+  ctx->ws_front = 0;
+  if (rc) return rc;
+  const int64_t total = Mi * 4 * N;
+  VfProf prof(ctx, "col2im4x4", 0.0, 4.0 * ((double)Mi * 16 * N + (double)total));
+  hipLaunchKernelGGL(k_col2im4x4, dim3((unsigned)vf_cdiv(total, 256)), dim3(256), 0, ctx->stream, (const float*)cols, bias, Y,
+                     B, vf_ilog2(Hi), vf_ilog2(Wi), N, act, slope);
+  VF_LAUNCH_CHECK();
+  if (dmask) return vf_act_bwd(ctx, dmask, Y, Y, total, dact, dslope);      // thin path: one more pass
+  return 0;
 }
 
 // Generic "transposed" pass: Y[b,oh,ow,n] = sum_{kh,kw,c : oh = 2i-1+kh ...} A[b,i,j,c] * Wt[c][kh][kw][n]
 // (conv data-grad: A = gy, c = Cout, n = Cin;  full-conv forward: A = x, c = Cin_full, n = Cout_full.)  s: the pass as a
 // full-conv (k = 4), A on its H x W map.
 static int conv_like_bwd(vf_ctx* ctx, const float* A, const float* w, const float* bias, float* Y, const VfConvShape& s, int act,
-                         float slope, VfConvExtras* ex, const float* dmask = nullptr, int dact = 0, float dslope = 0.f) {
-  const int B = s.B, Hi = s.H, Wi = s.W, C = s.Cin, N = s.Cout, stride = s.stride, pad = s.pad;
-  if (stride == 2 && pad == 1 && N <= 4 && !dmask && !ex->bn.st.mode) {      // the image side: direct kernel, no column matrix
+                         float slope, VfConvExtras* ex, const float* dmask = nullptr, int dact = 0, float dslope = 0.f,
+                         bool conv_grad = false) {
+  const int B = s.B, Hi = s.H, Wi = s.W, C = s.Cin, N = s.Cout;
+  const bool vecA = (C % 16 == 0) && vf_aligned16(A);
+  const TrPlan r = tr_plan(s, vecA, vf_aligned16(w), dmask != nullptr, ex->bn.st.mode != 0, ctx->ws_front, ctx->ws_bytes, conv_grad);
+  if (r.route == TR_DOT_HEAD) {      // with the derivative of the activation fused into that conv (VfConvExtras::dot_act_y)
+    const int64_t n = (int64_t)B * 16 * N;
+    hipLaunchKernelGGL(k_dot_bwd_data, dim3((int)vf_cdiv(n, 256)), dim3(256), 0, ctx->stream, A, w, Y, B, 16 * N, ex->dot_act_y,
+                       ex->dot_act, ex->dot_act_slope);
+    VF_LAUNCH_CHECK();
+    return 0;
+  }
+  if (r.route == TR_THIN_OUT) {      // the image side: direct kernel, no column matrix
     const int rc = vf_internal_deconv_thin_out(ctx, A, w, bias, Y, s, act, slope);
     if (rc >= 0) return rc;
   }
+  if (r.fallback == TR_COL2IM) return tr_col2im(ctx, r, A, w, bias, Y, s, act, slope, dmask, dact, dslope);
   IGemm g;
   memset(&g, 0, sizeof(g));
   g.A = A; g.Wt = w; g.bias = bias; g.Y = Y;
@@ -1581,75 +1685,46 @@ static int conv_like_bwd(vf_ctx* ctx, const float* A, const float* w, const floa
   g.Hi = Hi; g.Wi = Wi; g.C = C; g.N = N;
   g.wsN = 1; g.wsC = 16 * N; g.wsTap = N;
   g.act = act; g.slope = slope;
-  const bool vecA = (C % 16 == 0) && vf_aligned16(A);
-  bool vecB = (N % 4 == 0) && vf_aligned16(w);
-  if (stride == 2 && N < 32 && vecA && vf_aligned16(w) && ctx->ws_front == 0) {
-    const int64_t Mi = (int64_t)B * Hi * Wi;
-    const size_t col_bytes = (size_t)Mi * 16 * N * sizeof(float);
-    if (col_bytes + ((size_t)32 << 20) <= ctx->ws_bytes) {
-      // thin output: cols[pixel][(kh,kw,n)] = A[pixel][:] . W[:][(kh,kw,n)]  (columns contiguous in [c][kh][kw][n]), then
-      // every output pixel gathers its 4 taps
-      float* cols = (float*)ctx->ws;
-      ctx->ws_front = (col_bytes + 255) & ~(size_t)255;
-      IGemm q;
-      memset(&q, 0, sizeof(q));
-      q.A = A; q.Wt = w; q.bias = nullptr; q.Y = cols;
-      q.M = (int)Mi; q.lgMh = 0; q.lgMw = 0;
-      q.Hi = 1; q.Wi = 1; q.C = C; q.N = 16 * N;
-      q.TH = 1; q.TW = 1; q.sy = 1; q.ty = 1; q.sx = 1; q.tx = 1; q.khs = 1; q.kws = 1;
-      q.wsN = 1; q.wsC = 16 * N; q.wsTap = 0;
-      q.outH = 1; q.outW = 1; q.osy = 1; q.osx = 1;
-      q.out_elems = Mi * 16 * N;
-      q.act = VF_ACT_NONE;
-      const int rc = launch_igemm(ctx, q, true, true, nullptr);
-      ctx->ws_front = 0;
-      if (rc) return rc;
-      const int64_t total = Mi * 4 * N;
-      VfProf prof(ctx, "col2im4x4", 0.0, 4.0 * ((double)Mi * 16 * N + (double)total));
-      hipLaunchKernelGGL(k_col2im4x4, dim3((unsigned)vf_cdiv(total, 256)), dim3(256), 0, ctx->stream, (const float*)cols, bias, Y,
-                         B, vf_ilog2(Hi), vf_ilog2(Wi), N, act, slope);
-      VF_LAUNCH_CHECK();
-      if (dmask) return vf_act_bwd(ctx, dmask, Y, Y, total, dact, dslope);      // thin path: one more pass
+  switch (r.fallback) {
+    case TR_PARITY_GEMM:
+      // output (2*Hi) x (2*Wi); per parity class a 2x2-tap GEMM over the low-res grid
+      g.lgMh = vf_ilog2(Hi); g.lgMw = vf_ilog2(Wi);
+      g.M = B * Hi * Wi;
+      g.TH = 2; g.TW = 2;
+      g.sy = 1; g.ty = -1; g.oy0 = 0; g.sx = 1; g.tx = -1; g.ox0 = 0;  // iy = my + ph - th
+      g.khs = 2; g.kws = 2;                                            // kh = (1-ph) + 2*th
+      g.outH = 2 * Hi; g.outW = 2 * Wi; g.osy = 2; g.osx = 2;
+      g.parity = 1;
+      g.out_elems = (int64_t)B * g.outH * g.outW * N;
+      VF_REQUIRE(!(dmask && bias), "activation-backward epilogue is for data-gradient passes (no bias)");
+      return launch_igemm(ctx, g, vecA, (N % 4 == 0) && vf_aligned16(w), ex);
+    default: {
+      // stride 1, pad 0, low-res 1x1 -> 4x4: plain GEMM whose N' = (kh,kw,n) columns are contiguous in [c][kh][kw][n]
+      VF_REQUIRE(Hi == 1 && Wi == 1, "stride-1 transposed pass is built for the 1x1 bottleneck only (got %dx%d)", Hi, Wi);
+      g.lgMh = 0; g.lgMw = 0;
+      g.M = B;
+      g.TH = 1; g.TW = 1;
+      g.sy = 1; g.ty = 1; g.sx = 1; g.tx = 1;
+      g.N = 16 * N;
+      g.wsC = 16 * N; g.wsTap = 0;
+      g.outH = 1; g.outW = 1; g.osy = 1; g.osx = 1;
+      g.out_elems = (int64_t)B * 16 * N;
+      VF_REQUIRE(!(dmask && bias), "activation-backward epilogue is for data-gradient passes (no bias)");
+      if (bias) {  // bias index = column % N: apply bias + activation in a pointwise pass
+        g.bias = nullptr;
+        g.act = VF_ACT_NONE;
+      }
+      // (the GEMM columns are (kh, kw, n): not one channel per column, so no statistics by-product here)
+      if (int rc = launch_igemm(ctx, g, vecA, ((16 * N) % 4 == 0) && vf_aligned16(w), nullptr)) return rc;
+      if (bias) {
+        const int64_t total = (int64_t)B * 16 * N;
+        const int nb = (int)std::min<int64_t>(vf_cdiv(total, 256), 4096);
+        hipLaunchKernelGGL(k_slab_reduce, dim3(nb), dim3(256), 0, ctx->stream, (const float*)Y, Y, bias, total, N, 0, act, slope, 1.f);
+        VF_LAUNCH_CHECK();
+      }
       return 0;
     }
   }
-  if (stride == 2) {
-    // output (2*Hi) x (2*Wi); per parity class a 2x2-tap GEMM over the low-res grid
-    g.lgMh = vf_ilog2(Hi); g.lgMw = vf_ilog2(Wi);
-    g.M = B * Hi * Wi;
-    g.TH = 2; g.TW = 2;
-    g.sy = 1; g.ty = -1; g.oy0 = 0; g.sx = 1; g.tx = -1; g.ox0 = 0;  // iy = my + ph - th
-    g.khs = 2; g.kws = 2;                                            // kh = (1-ph) + 2*th
-    g.outH = 2 * Hi; g.outW = 2 * Wi; g.osy = 2; g.osx = 2;
-    g.parity = 1;
-    g.out_elems = (int64_t)B * g.outH * g.outW * N;
-  } else {
-    // stride 1, pad 0, low-res 1x1 -> 4x4: plain GEMM whose N' = (kh,kw,n) columns are contiguous in [c][kh][kw][n]
-    VF_REQUIRE(Hi == 1 && Wi == 1, "stride-1 transposed pass is built for the 1x1 bottleneck only (got %dx%d)", Hi, Wi);
-    g.lgMh = 0; g.lgMw = 0;
-    g.M = B;
-    g.TH = 1; g.TW = 1;
-    g.sy = 1; g.ty = 1; g.sx = 1; g.tx = 1;
-    g.N = 16 * N;
-    g.wsC = 16 * N; g.wsTap = 0;
-    g.outH = 1; g.outW = 1; g.osy = 1; g.osx = 1;
-    g.out_elems = (int64_t)B * 16 * N;
-    vecB = ((16 * N) % 4 == 0) && vf_aligned16(w);
-  }
-  VF_REQUIRE(!(dmask && bias), "activation-backward epilogue is for data-gradient passes (no bias)");
-  if (stride == 1 && bias) {  // bias index = column % N: apply bias + activation in a pointwise pass
-    g.bias = nullptr;
-    g.act = VF_ACT_NONE;
-  }
-  // (the 1x1 -> 4x4 form's GEMM columns are (kh, kw, n): not one channel per column, so no statistics by-product there)
-  if (int rc = launch_igemm(ctx, g, vecA, vecB, stride == 2 ? ex : nullptr)) return rc;
-  if (stride == 1 && bias) {
-    const int64_t total = (int64_t)B * 16 * N;
-    const int nb = (int)std::min<int64_t>(vf_cdiv(total, 256), 4096);
-    hipLaunchKernelGGL(k_slab_reduce, dim3(nb), dim3(256), 0, ctx->stream, (const float*)Y, Y, bias, total, N, 0, act, slope, 1.f);
-    VF_LAUNCH_CHECK();
-  }
-  return 0;
 }
 
 // dW[n][kh][kw][c] = beta*dW + sum_p U[p][n] * V[b, my*s-pad+kh, mx*s-pad+kw, c]
@@ -1717,14 +1792,7 @@ static WgPlan wg_plan(vf_ctx* ctx, const VfConvShape& s, bool full, const float*
   // iteration 2.851 ms at 256, 2.813 at 512, 2.842 before the form existed) — and the split is then the fp32-fed kernel's own: same bits
   p.target = use_pw && !pw64 ? 256 : 512;
   const int64_t tiles = (int64_t)p.gx * p.gy;
-  p.ksplit = 1;
-  if (tiles < p.target * 3 / 4 && p.nk >= 16) {
-    p.ksplit = (int)std::min<int64_t>(p.nk / 8, vf_cdiv(p.target, tiles));
-    while (p.ksplit > 1 && (size_t)p.ksplit * p.total * sizeof(float) > vf_ws_avail(ctx)) --p.ksplit;
-    if (p.ksplit < 1) p.ksplit = 1;
-    const int steps = (int)vf_cdiv(p.nk, p.ksplit);
-    p.ksplit = (int)vf_cdiv(p.nk, steps);
-  }
+  p.ksplit = vf_split_k(tiles, p.target, p.nk, 16, 8, (size_t)p.total * sizeof(float), vf_ws_avail(ctx), VF_K_EVEN_OUT);
   p.route = p.is_bottleneck() ? WG_SMALLK : use_pw ? (pw64 ? WG_PLANES_64 : WG_PLANES_128) : p.fp32_route();
   p.rider = p.is_bottleneck() && (mode == 3 || mode == 1) && p.bm == 128 && p.ksplit == 1 && (16 * p.Cv) % 128 == 0 && p.vecU && p.vecV;
   return p;
@@ -2027,11 +2095,7 @@ int vf_internal_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const fl
                            float slope, VfConvExtras* ex) {
   if (!s.matrix_core_conv()) return vf_internal_gconv_fwd(ctx, x, w, bias, y, s, act, slope);
   if (int rc = check_conv_args(s)) return rc;
-  if (s.stride == 2 && s.Cin == 3 && !ex->bn.st.mode) {      // the image-side layers: direct convolution (vf_conv_thin.hip)
-    const int rc = vf_internal_conv_thin_fwd(ctx, x, w, bias, y, nullptr, s, act, slope, ex);
-    if (rc >= 0) return rc;
-  }
-  return conv_like_fwd(ctx, x, w, bias, y, s, act, slope, ex);
+  return conv_like_fwd(ctx, x, w, bias, y, s, act, slope, ex, true);
 }
 VF_API int vf_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
                          int Cin, int Cout, int k, int stride, int pad, int act, float slope) {
@@ -2042,17 +2106,8 @@ VF_API int vf_conv2d_fwd(vf_ctx* ctx, const float* x, const float* w, const floa
 int vf_internal_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, const VfConvShape& s, VfConvExtras* ex) {
   if (!s.matrix_core_conv()) return vf_internal_gconv_bwd_data(ctx, gy, w, gx, s);
   if (int rc = check_conv_args(s)) return rc;
-  if (s.stride == 1) {
-    VF_REQUIRE(s.H == 4 && s.W == 4, "stride-1 conv data-grad is built for the 4x4 bottleneck input only");
-    if (s.Cout == 1) {      // the 512 -> 1 head, with the derivative of the activation fused into this conv (VfConvExtras::dot_act_y)
-      const int64_t n = (int64_t)s.B * 16 * s.Cin;
-      hipLaunchKernelGGL(k_dot_bwd_data, dim3((int)vf_cdiv(n, 256)), dim3(256), 0, ctx->stream, gy, w, gx, s.B, 16 * s.Cin, ex->dot_act_y,
-                         ex->dot_act, ex->dot_act_slope);
-      VF_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  return conv_like_bwd(ctx, gy, w, nullptr, gx, s.gradient_of_conv(), VF_ACT_NONE, 0.f, ex);
+  if (s.stride == 1) VF_REQUIRE(s.H == 4 && s.W == 4, "stride-1 conv data-grad is built for the 4x4 bottleneck input only");
+  return conv_like_bwd(ctx, gy, w, nullptr, gx, s.gradient_of_conv(), VF_ACT_NONE, 0.f, ex, nullptr, 0, 0.f, true);
 }
 VF_API int vf_conv2d_bwd_data(vf_ctx* ctx, const float* gy, const float* w, float* gx, int B, int H, int W, int Cin,
                               int Cout, int k, int stride, int pad) {

@@ -1608,116 +1608,178 @@ VF_API int vf_pconv_set_routing(int gather_patch, int scatter_patch) {
 
 typedef void (*PgKernel)(PGemm);
 
-template <int BM, int NTAPS>
-static PgKernel pg_dma_kernel(bool one_plane, bool one_stage) {
-  if (one_plane) return k_pconv_dma<BM, 64, NTAPS, 2, 1>;
-  return one_stage ? k_pconv_dma<BM, 64, NTAPS, 1> : k_pconv_dma<BM, 64, NTAPS, 2>;
+// ---- the plan of one planes GEMM: channel step, tile, split over K, the kernel form that serves it, what the profiler is told.
+// One enumerator per kernel form; DESIGN.md 4.1 is read from pg_route() below.
+enum PgRoute {
+  PG_DMA_2STAGE,       // k_pconv_dma, two LDS stages
+  PG_DMA_1STAGE,       //   ... one stage, two blocks per CU
+  PG_DMA_1PLANE,       //   ... one rounded plane per operand (product mode 1)
+  PG_PATCH_TR_C2,      // k_pconv_patch_tr: transposed passes on grids of at least 8 x 16, two parity classes per block
+  PG_PATCH_TR_C4,      //   ... four
+  PG_PATCH_G_M0,       // k_pconv_patch_g: gather passes on whole 128-row tiles, 8 x 16 regions
+  PG_PATCH_G_M1,       //   ... whole 8 x 8 maps
+  PG_PATCH_G_M2,       //   ... whole 4 x 4 maps
+  PG_PATCH_G_TR_M1,    // k_pconv_patch_g's TR form: transposed passes whose low-resolution grid is a whole 8 x 8 map
+  PG_PATCH_G_TR_M2,    //   ... a whole 4 x 4 map
+  PG_REG               // the register-staged k_pconv: ragged tiles, 32-channel steps
+};
+struct PgPlan {
+  int ntaps;             // taps of the window: 16, or the 4 of one output-parity class
+  int ch, nchunks;       // channels per K step, C / ch
+  int bm;                // tile rows (columns: 64)
+  bool use_dma;          // whole tiles of 64-channel stages: what the LDS-DMA and the patch-fed kernels take
+  int ksplit, gm, gn, gz;
+  PgRoute route;
+  VfBnStPlan stats;       // BatchNorm statistics as a by-product: from the epilogue, or from the slab reduce under split-K
+  dim3 grid, block;
+  char name[64];
+  double flops, bytes;
+};
+
+// which kernel form serves the GEMM `g` on p's tiles (p: everything above `route`); nt: tiles of the grid.  gather_patch /
+// scatter_patch: the process-wide switches of vf_pconv_set_routing
+static PgRoute pg_route(const PGemm& g, const PgPlan& p, int ntaps, unsigned nt, bool one_plane, bool gather_patch, bool scatter_patch) {
+  if (!p.use_dma) return PG_REG;
+  // one rounded plane per operand: 128x64 stages of 24 KB (two stages: 48 KB, three blocks per CU), 64x64 of 16 KB
+  if (one_plane) return PG_DMA_1PLANE;
+  const bool tr = ntaps == 4 && g.parity, tile128 = p.bm == 128;
+  // transposed passes on grids of at least 8 x 16: the patch kernel (k_pconv_patch_tr), 4 parity classes per block where that still
+  // gives two rounds of blocks, else 2      (its epilogue addresses the output through 32-bit buffer offsets)
+  if (scatter_patch && tr && p.ksplit == 1 && tile128 && g.Wi % 16 == 0 && g.Hi % 8 == 0 &&
+      (g.act == VF_ACT_NONE || g.act == VF_ACT_LRELU || g.act == VF_ACT_RELU) && g.out_elems * 4 < ((int64_t)1 << 31))
+    return (unsigned)(g.M / 128) * (unsigned)(g.N / 64) >= 512 ? PG_PATCH_TR_C4 : PG_PATCH_TR_C2;
+  // gather passes (conv forward, full-conv data-gradient) on whole 128-row tiles: the patch kernel (k_pconv_patch_g)
+  const int Ho = 1 << g.lgMh, Wo = 1 << g.lgMw;
+  const int gmode = (Wo % 16 == 0 && Ho % 8 == 0) ? 0 : (Ho == 8 && Wo == 8) ? 1 : (Ho == 4 && Wo == 4) ? 2 : -1;
+  if (gather_patch && ntaps == 16 && !g.parity && tile128 && g.sy == 2 && g.sx == 2 && gmode >= 0)
+    return gmode == 0 ? PG_PATCH_G_M0 : gmode == 1 ? PG_PATCH_G_M1 : PG_PATCH_G_M2;
+  // transposed passes whose low-resolution grid is a whole 8 x 8 / 4 x 4 map (what k_pconv_patch_tr's 8 x 16 regions do not cover): the
+  // patch kernel's TR form, one output-parity class per block as k_pconv_dma
+  // (grids of one tile per CU only: from two rounds of blocks the single-stage k_pconv_dma, two blocks per CU, is faster —
+  //  netD's third conv at 2B, 512 blocks: 45.6 us against 46.5, with its derivative mask 51.9 against 59.7)
+  if (scatter_patch && tr && tile128 && nt < 512 && ((g.Hi == 8 && g.Wi == 8) || (g.Hi == 4 && g.Wi == 4)))
+    return g.Hi == 8 ? PG_PATCH_G_TR_M1 : PG_PATCH_G_TR_M2;
+  // a grid of at least two tiles per CU runs the single-stage variant, two blocks per CU (measured, scripts/bench_pconv.py:
+  // E2 transposed pass 79 -> 67 us, E2 gather 68 -> 62, E3 transposed 31.2 -> 28.8, netD's first layer at 2B 58 -> 53;
+  // with one tile per CU the second stage is what is needed instead: E3 gather 29.7 vs 39.8 single-stage)
+  return tile128 && nt >= 512 ? PG_DMA_1STAGE : PG_DMA_2STAGE;
 }
 
-template <int BM, int WM, int NTAPS>
-static PgKernel pg_reg_kernel(int ch) {
-  return ch == 64 ? k_pconv<BM, 64, WM, 32, NTAPS, 64> : k_pconv<BM, 64, WM, 32, NTAPS, 32>;
-}
-
-static int launch_pconv(vf_ctx* ctx, PGemm& g, int ntaps, VfConvExtras* ex) {
+// g: the geometry (pg_fill_common and the caller's fields); mode: the product mode; req: the pending BatchNorm request or NULL.
+// Launches nothing and writes nothing: launch_pconv takes the plan into `g` and the caller's extras.
+static PgPlan pg_plan(const PGemm& g, int ntaps, int mode, size_t ws_avail, const VfBnRequest* req, bool gather_patch, bool scatter_patch) {
+  PgPlan p;
+  p.ntaps = ntaps;
   // ---- channel step, tile, split-K
   const int zpar = g.parity ? 4 : 1;
-  const int ch = g.C % 64 == 0 ? 64 : 32;      // channels per K step: whole 128-byte lines where possible
-  g.nchunks = g.C / ch;
+  p.ch = g.C % 64 == 0 ? 64 : 32;      // channels per K step: whole 128-byte lines where possible
+  p.nchunks = g.C / p.ch;
   // the LDS-DMA kernels take 64-channel stages and whole tiles (their row decode has no ragged edge): 128 x 64 tiles where the rows
   // divide, else 64 x 64; the register-staged k_pconv takes 128 x 64 when that still fills the chip twice over, else 64 x 64
   constexpr int bn = 64;
-  const bool dma_shape = ch == 64 && g.N % bn == 0;
-  const int bm = dma_shape ? (g.M % 128 == 0 ? 128 : 64) : (vf_cdiv(g.M, 128) * vf_cdiv(g.N, bn) * zpar >= 1024 ? 128 : 64);
-  const bool use_dma = dma_shape && g.M % bm == 0;
-  const int gm = (int)vf_cdiv(g.M, bm), gn = (int)vf_cdiv(g.N, bn);
-  const int64_t blocks = (int64_t)gm * gn * zpar;
+  const bool dma_shape = p.ch == 64 && g.N % bn == 0;
+  p.bm = dma_shape ? (g.M % 128 == 0 ? 128 : 64) : (vf_cdiv(g.M, 128) * vf_cdiv(g.N, bn) * zpar >= 1024 ? 128 : 64);
+  p.use_dma = dma_shape && g.M % p.bm == 0;
+  p.gm = (int)vf_cdiv(g.M, p.bm);
+  p.gn = (int)vf_cdiv(g.N, bn);
+  const int64_t blocks = (int64_t)p.gm * p.gn * zpar;
   // split-K over channel chunks for the small grids.  A grid of 256 tiles (one per CU) is left whole: measured 27.6 vs 39.2 us
   // (E4 data-gradient) against splitting it in two
   constexpr int SPLIT_BLOCKS = 340;
-  int ksplit = 1;
-  if (blocks < SPLIT_BLOCKS * 3 / 4 && g.nchunks >= 2) {
-    ksplit = (int)std::min<int64_t>(g.nchunks, vf_cdiv(SPLIT_BLOCKS, blocks));
-    const size_t slab_bytes = (size_t)g.out_elems * sizeof(float);
-    while (ksplit > 1 && (size_t)ksplit * slab_bytes > vf_ws_avail(ctx)) --ksplit;
-    while (ksplit > 1 && g.nchunks % ksplit != 0) --ksplit;      // equal K ranges: every tile runs the same number of steps
-  }
-  g.ksplit = ksplit;
-  g.slab = ksplit > 1 ? (float*)vf_ws_ptr(ctx) : nullptr;
-  g.gm = gm; g.gn = gn; g.gz = zpar * ksplit;
-  const unsigned nt = (unsigned)(blocks * ksplit);
-  // ---- BatchNorm statistics as a by-product: from the epilogue, or from the slab reduce under split-K
-  const bool slab_st = vf_plan_bn_stats(ex, g, bm, gm, zpar);
-  const bool one_plane = ctx->mfma_bf16 == 1;
-  VF_REQUIRE(!one_plane || use_dma, "vf_pconv: in the bf16-operand mode the planes path serves whole 64-channel / 64-row tiles only "
-             "(vf_pconv_supported_in_mode)");
+  p.ksplit = vf_split_k(blocks, SPLIT_BLOCKS, p.nchunks, 2, 1, (size_t)g.out_elems * sizeof(float), ws_avail, VF_K_WHOLE_EQUAL);
+  p.gz = zpar * p.ksplit;
+  const unsigned nt = (unsigned)(blocks * p.ksplit);
+  p.stats = vf_plan_bn_stats(req, g, p.ksplit, p.bm, p.gm, zpar);
+  p.route = pg_route(g, p, ntaps, nt, mode == 1, gather_patch, scatter_patch);
 
-  // ---- kernel
+  // ---- grid, name, what the profiler is told
   const char* taps = ntaps == 16 ? "t16" : "t4";
-  const double fl = 2.0 * (double)g.M * g.N * (double)ntaps * g.C * zpar;
+  p.flops = 2.0 * (double)g.M * g.N * (double)ntaps * g.C * zpar;
   // algorithmic bytes of the DMA-fed kernels: operand planes and weight planes once, the output (or its split-K slabs), and what the
   // epilogue reads (derivative mask, BatchNorm input) — bench.py prices a kernel against the LONGER of its two floors
-  const double dby = (double)g.a_bytes + (double)g.w_bytes + 4.0 * (double)g.out_elems * ksplit +
-                     (g.dmask ? (g.dbits ? 0.125 : 4.0) * (double)g.out_elems : 0.0) + (g.st.mode == 2 ? 4.0 * (double)g.out_elems : 0.0);
-  char name[64];
-  PgKernel kern;
-  dim3 grid(nt), block(bm == 128 ? 512 : 256);
-  double by = dby;
-  const int Ho = 1 << g.lgMh, Wo = 1 << g.lgMw;
-  const int gmode = (Wo % 16 == 0 && Ho % 8 == 0) ? 0 : (Ho == 8 && Wo == 8) ? 1 : (Ho == 4 && Wo == 4) ? 2 : -1;
-  if (use_dma && one_plane) {
-    // one rounded plane per operand: 128x64 stages of 24 KB (two stages: 48 KB, three blocks per CU), 64x64 of 16 KB
-    snprintf(name, sizeof(name), "pconv_dma_%dx%dx64_%s_bf16", bm, bn, taps);
-    kern = bm == 128 ? (ntaps == 16 ? pg_dma_kernel<128, 16>(true, false) : pg_dma_kernel<128, 4>(true, false))
-                     : (ntaps == 16 ? pg_dma_kernel<64, 16>(true, false) : pg_dma_kernel<64, 4>(true, false));
-  } else if (use_dma && g_scatter_patch && ntaps == 4 && g.parity && ksplit == 1 && bm == 128 && g.Wi % 16 == 0 && g.Hi % 8 == 0 &&
-             (g.act == VF_ACT_NONE || g.act == VF_ACT_LRELU || g.act == VF_ACT_RELU) &&
-             g.out_elems * 4 < ((int64_t)1 << 31)) {       // (its epilogue addresses the output through 32-bit buffer offsets)
-    // transposed passes on grids of at least 8 x 16: the patch kernel (k_pconv_patch_tr), 4 parity classes per block where that still
-    // gives two rounds of blocks, else 2
-    const unsigned tiles = (unsigned)(g.M / 128), slices = (unsigned)(g.N / 64);
-    const int cpb = tiles * slices >= 512 ? 4 : 2;
-    snprintf(name, sizeof(name), "pconv_patch_128x64_t4_c%d", cpb);
-    grid = dim3(tiles * slices * (cpb == 2 ? 2u : 1u));
-    kern = cpb == 4 ? k_pconv_patch_tr<4> : k_pconv_patch_tr<2>;
-  } else if (use_dma && g_gather_patch && ntaps == 16 && !g.parity && bm == 128 && g.sy == 2 && g.sx == 2 && gmode >= 0) {
-    // gather passes (conv forward, full-conv data-gradient) on whole 128-row tiles: the patch kernel (k_pconv_patch_g)
-    snprintf(name, sizeof(name), "pconv_patchg_128x64_t16_m%d", gmode);
-    kern = gmode == 0 ? k_pconv_patch_g<0> : gmode == 1 ? k_pconv_patch_g<1> : k_pconv_patch_g<2>;
-  } else if (use_dma && g_scatter_patch && ntaps == 4 && g.parity && bm == 128 && nt < 512 &&
-             ((g.Hi == 8 && g.Wi == 8) || (g.Hi == 4 && g.Wi == 4))) {
-    // transposed passes whose low-resolution grid is a whole 8 x 8 / 4 x 4 map (what k_pconv_patch_tr's 8 x 16 regions do not cover): the
-    // patch kernel's TR form, one output-parity class per block as k_pconv_dma
-    // (grids of one tile per CU only: from two rounds of blocks the single-stage k_pconv_dma, two blocks per CU, is faster —
-    //  netD's third conv at 2B, 512 blocks: 45.6 us against 46.5, with its derivative mask 51.9 against 59.7)
-    const int mode = g.Hi == 8 ? 1 : 2;
-    snprintf(name, sizeof(name), "pconv_patchg_128x64_t4_m%d", mode);
-    kern = mode == 1 ? k_pconv_patch_g<1, true> : k_pconv_patch_g<2, true>;
-  } else if (use_dma) {
-    // a grid of at least two tiles per CU runs the single-stage variant, two blocks per CU (measured, scripts/bench_pconv.py:
-    // E2 transposed pass 79 -> 67 us, E2 gather 68 -> 62, E3 transposed 31.2 -> 28.8, netD's first layer at 2B 58 -> 53;
-    // with one tile per CU the second stage is what is needed instead: E3 gather 29.7 vs 39.8 single-stage)
-    const bool one_stage = bm == 128 && nt >= 512;
-    snprintf(name, sizeof(name), "pconv_dma_%dx%dx64_%s%s", bm, bn, taps, one_stage ? "_1stage" : "");
-    kern = bm == 128 ? (ntaps == 16 ? pg_dma_kernel<128, 16>(false, one_stage) : pg_dma_kernel<128, 4>(false, one_stage))
-                     : (ntaps == 16 ? pg_dma_kernel<64, 16>(false, one_stage) : pg_dma_kernel<64, 4>(false, one_stage));
-  } else {
-    snprintf(name, sizeof(name), "pconv_%dx%dx%d_%s", bm, bn, ch, taps);
-    kern = bm == 128 ? (ntaps == 16 ? pg_reg_kernel<128, 64, 16>(ch) : pg_reg_kernel<128, 64, 4>(ch))
-                     : (ntaps == 16 ? pg_reg_kernel<64, 32, 16>(ch) : pg_reg_kernel<64, 32, 4>(ch));
-    block = dim3(256);
-    by = 0.0;
+  p.bytes = (double)g.a_bytes + (double)g.w_bytes + 4.0 * (double)g.out_elems * p.ksplit +
+            (p.stats.dmask ? (g.dbits ? 0.125 : 4.0) * (double)g.out_elems : 0.0) + (p.stats.st.mode == 2 ? 4.0 * (double)g.out_elems : 0.0);
+  p.grid = dim3(nt);
+  p.block = dim3(p.bm == 128 ? 512 : 256);
+  switch (p.route) {
+    case PG_DMA_1PLANE:
+      snprintf(p.name, sizeof(p.name), "pconv_dma_%dx%dx64_%s_bf16", p.bm, bn, taps);
+      break;
+    case PG_PATCH_TR_C2:
+    case PG_PATCH_TR_C4: {
+      const int cpb = p.route == PG_PATCH_TR_C4 ? 4 : 2;
+      snprintf(p.name, sizeof(p.name), "pconv_patch_128x64_t4_c%d", cpb);
+      p.grid = dim3((unsigned)(g.M / 128) * (unsigned)(g.N / 64) * (cpb == 2 ? 2u : 1u));
+      break;
+    }
+    case PG_PATCH_G_M0:
+    case PG_PATCH_G_M1:
+    case PG_PATCH_G_M2:
+      snprintf(p.name, sizeof(p.name), "pconv_patchg_128x64_t16_m%d", p.route - PG_PATCH_G_M0);
+      break;
+    case PG_PATCH_G_TR_M1:
+    case PG_PATCH_G_TR_M2:
+      snprintf(p.name, sizeof(p.name), "pconv_patchg_128x64_t4_m%d", p.route == PG_PATCH_G_TR_M1 ? 1 : 2);
+      break;
+    case PG_DMA_1STAGE:
+    case PG_DMA_2STAGE:
+      snprintf(p.name, sizeof(p.name), "pconv_dma_%dx%dx64_%s%s", p.bm, bn, taps, p.route == PG_DMA_1STAGE ? "_1stage" : "");
+      break;
+    case PG_REG:
+      snprintf(p.name, sizeof(p.name), "pconv_%dx%dx%d_%s", p.bm, bn, p.ch, taps);
+      p.block = dim3(256);
+      p.bytes = 0.0;
+      break;
   }
+  return p;
+}
 
-  // ---- launch, split-K combine
-  VF_LAUNCH_TIMED(ctx, name, fl, by, kern, grid, block, g);
-  VF_LAUNCH_CHECK();
-  if (ksplit > 1) {
-    VfProf prof(ctx, slab_st ? "slab_reduce_pconv_bnstats" : "slab_reduce_pconv", 0.0, 4.0 * (double)g.out_elems * (ksplit + 1));
-    return vf_internal_slab_reduce(ctx, g.slab, g.Y, g.bias, g.out_elems, g.N, ksplit, g.act, g.slope, g.dmask, g.dact, g.dslope,
-                                   slab_st ? &g.st : nullptr, slab_st ? ex->bn.groups : 1);
+// route -> kernel.  The tap-staged kernels are built per (tile rows, taps): the two helpers name the forms of one such pair
+template <int BM, int NTAPS>
+static PgKernel pg_dma_kernel(PgRoute r) {
+  if (r == PG_DMA_1PLANE) return k_pconv_dma<BM, 64, NTAPS, 2, 1>;
+  if (r == PG_DMA_1STAGE) return k_pconv_dma<BM, 64, NTAPS, 1>;
+  return k_pconv_dma<BM, 64, NTAPS, 2>;
+}
+template <int BM, int NTAPS>
+static PgKernel pg_reg_kernel(int ch) {
+  if (ch == 64) return k_pconv<BM, 64, BM / 2, 32, NTAPS, 64>;
+  return k_pconv<BM, 64, BM / 2, 32, NTAPS, 32>;
+}
+static PgKernel pg_kernel(const PgPlan& p) {
+  const bool t16 = p.ntaps == 16;
+  switch (p.route) {
+    case PG_DMA_1PLANE:
+    case PG_DMA_1STAGE:
+    case PG_DMA_2STAGE:
+      if (p.bm == 128) return t16 ? pg_dma_kernel<128, 16>(p.route) : pg_dma_kernel<128, 4>(p.route);
+      return t16 ? pg_dma_kernel<64, 16>(p.route) : pg_dma_kernel<64, 4>(p.route);
+    case PG_PATCH_TR_C4: return k_pconv_patch_tr<4>;
+    case PG_PATCH_TR_C2: return k_pconv_patch_tr<2>;
+    case PG_PATCH_G_M1: return k_pconv_patch_g<1>;
+    case PG_PATCH_G_M2: return k_pconv_patch_g<2>;
+    case PG_PATCH_G_M0: return k_pconv_patch_g<0>;
+    case PG_PATCH_G_TR_M1: return k_pconv_patch_g<1, true>;
+    case PG_PATCH_G_TR_M2: return k_pconv_patch_g<2, true>;
+    case PG_REG:
+      if (p.bm == 128) return t16 ? pg_reg_kernel<128, 16>(p.ch) : pg_reg_kernel<128, 4>(p.ch);
+      return t16 ? pg_reg_kernel<64, 16>(p.ch) : pg_reg_kernel<64, 4>(p.ch);
   }
-  return 0;
+  return nullptr;
+}
+
+static int launch_pconv(vf_ctx* ctx, PGemm& g, int ntaps, VfConvExtras* ex) {
+  const PgPlan p = pg_plan(g, ntaps, ctx->mfma_bf16, vf_ws_avail(ctx), ex ? &ex->bn : nullptr, g_gather_patch != 0, g_scatter_patch != 0);
+  VF_REQUIRE(ctx->mfma_bf16 != 1 || p.use_dma, "vf_pconv: in the bf16-operand mode the planes path serves whole 64-channel / 64-row tiles only "
+             "(vf_pconv_supported_in_mode)");
+  g.nchunks = p.nchunks;
+  g.ksplit = p.ksplit;
+  g.slab = p.ksplit > 1 ? (float*)vf_ws_ptr(ctx) : nullptr;
+  g.gm = p.gm; g.gn = p.gn; g.gz = p.gz;
+  vf_take_bn_stats(p.stats, g, ex);
+  VF_LAUNCH_TIMED(ctx, p.name, p.flops, p.bytes, pg_kernel(p), p.grid, p.block, g);
+  VF_LAUNCH_CHECK();
+  return vf_combine_slabs(ctx, "pconv", g, p.stats.slab, p.stats.slab ? ex->bn.groups : 1);
 }
 
 static int pg_fill_common(vf_ctx* ctx, PGemm& g, const void* a, const void* w, const float* bias, float* y, const VfConvShape& s) {
