@@ -362,6 +362,28 @@ int vf_tiles_gather(vf_ctx* ctx, const float* full, float* tiles, int groups, in
 int vf_tiles_scatter(vf_ctx* ctx, const float* tiles, float* out, int groups, int nc, int H, int W, int fs,
                      const unsigned char* vflip);
 
+/* Overlapped, blended inference windows (the rule is tests/window_blend_ref.py).  The clip is F frames of
+ * nc x H x W, planar (F*nc) x H x W; a window is inputLen frames x fs x fs.  Per axis the windows start at 0, stride,
+ * 2 stride, ... while they fit, and one more at n - size if the last ends before n (y, x: size fs, stride `stride`;
+ * t: size inputLen, stride `stride_t`); n >= size, 1 <= stride <= size and 2 stride >= size, nothing is padded.  Window
+ * (it, iy, ix) has number (it*NY + iy)*NX + ix and is batch row `number`; channel k of the row is frame origin + k / nc,
+ * colour k % nc.  All three check their arguments before any launch, allocate nothing and do not synchronise.
+ * vf_windows_gather: rows [w0, w0 + nw) of the window batch, NHWC nw x fs x fs x (inputLen*nc). */
+int vf_windows_gather(vf_ctx* ctx, const float* frames, float* tiles, int F, int nc, int H, int W, int inputLen, int fs,
+                      int stride, int stride_t, int w0, int nw);
+/* Adds the net's output rows [w0, w0 + nw) (NHWC, as gathered) into the fp32 accumulator acc ((F*nc) x H x W, zeroed by
+ * the caller before the first chunk): per sample, for every covering window of the chunk in ascending number,
+ * acc = fadd(acc, fmul(float(w), v)) with the integer weight w = wt wy wx, w.(i) = min(i + 1, size - i, size - stride + 1).
+ * No atomics; chunks issued in ascending order on one stream give the same bits whatever their size. */
+int vf_windows_accumulate(vf_ctx* ctx, const float* tiles, float* acc, int F, int nc, int H, int W, int inputLen, int fs,
+                          int stride, int stride_t, int w0, int nw);
+/* out = fdiv(acc, float(sum of the covering weights)), the sum an integer of the geometry.  With frames (planar, [-1,1]),
+ * mask (nc x H x W uint8, non-zero = hole), inpaint and full all given it also does test_vid_wholeim.lua:214-224: inpaint =
+ * out inside the mask, the frame outside, and out, inpaint, full = x * 0.5 + 0.5 of out, inpaint, frames (the bits of
+ * vf_masked_compose and vf_scale_shift); with all four NULL, out is the plain quotient. */
+int vf_windows_finish(vf_ctx* ctx, const float* acc, const float* frames, const unsigned char* mask, float* out, float* inpaint,
+                      float* full, int F, int nc, int H, int W, int inputLen, int fs, int stride, int stride_t);
+
 /* ---- Torch7 image.scale (bilinear) and the loaders built on it (vf_image.hip) --------------------
  * Bit-identical to the float32 restatement of image.c's scaleBilinear: rows first (W -> width), then columns
  * (H -> height), one rounding per operation.  src_layout 0: float planar N x C x H x W; src_layout 1: decoded uint8

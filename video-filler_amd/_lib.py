@@ -79,6 +79,9 @@ SIGNATURES = {
     "vf_clip_prepare": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp]),
     "vf_tiles_gather": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "vf_tiles_scatter": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "vf_windows_gather": (i32, [vp, vp, vp] + [i32] * 10),
+    "vf_windows_accumulate": (i32, [vp, vp, vp] + [i32] * 10),
+    "vf_windows_finish": (i32, [vp] * 7 + [i32] * 8),
     "vf_image_scale": (i32, [vp, vp, i32, vp] + [i32] * 6),
     "vf_image_scale_u8": (i32, [vp, vp, vp] + [i32] * 6),
     "vf_image_hook2d": (i32, [vp, vp, i32, vp] + [i32] * 9),

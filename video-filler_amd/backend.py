@@ -1123,6 +1123,34 @@ class HipBackend:
         self._c("vf_tiles_scatter", _ptr(tiles), _ptr(out), groups, Ct // groups, H, W, fs,
                 _ptr(vflip) if vflip is not None else None)
 
+    # ---- overlapped, blended windows.  geo = (inputLen, fs, stride, stride_t); frames / acc: F x nc x H x W planar
+    def windows_gather(self, frames, tiles, geo, w0):
+        """rows [w0, w0 + tiles.shape[0]) of the window batch: tiles n x (inputLen*nc) x fs x fs channels-last."""
+        F, nc, H, W = frames.shape
+        L, fs, stride, stride_t = geo
+        assert frames.is_contiguous() and frames.dtype == torch.float32 and is_nhwc(tiles) and tiles.dtype == torch.float32
+        assert tuple(tiles.shape[1:]) == (L * nc, fs, fs), "tiles are n x %d x %d x %d" % (L * nc, fs, fs)
+        self._c("vf_windows_gather", _ptr(frames), _ptr(tiles), F, nc, H, W, L, fs, stride, stride_t, w0, tiles.shape[0])
+
+    def windows_accumulate(self, tiles, acc, geo, w0):
+        """acc += the weighted rows [w0, w0 + tiles.shape[0]) (the net's output for the rows windows_gather made)."""
+        F, nc, H, W = acc.shape
+        L, fs, stride, stride_t = geo
+        assert acc.is_contiguous() and acc.dtype == torch.float32 and is_nhwc(tiles) and tiles.dtype == torch.float32
+        assert tuple(tiles.shape[1:]) == (L * nc, fs, fs), "tiles are n x %d x %d x %d" % (L * nc, fs, fs)
+        self._c("vf_windows_accumulate", _ptr(tiles), _ptr(acc), F, nc, H, W, L, fs, stride, stride_t, w0, tiles.shape[0])
+
+    def windows_finish(self, acc, geo, out, frames=None, mask=None, inpaint=None, full=None):
+        """out = acc / weight sum; with frames, mask (nc x H x W uint8), inpaint and full also the paste and the [0,1] mapping."""
+        F, nc, H, W = acc.shape
+        L, fs, stride, stride_t = geo
+        for t in (acc, out) + ((frames, inpaint, full) if frames is not None else ()):
+            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (F, nc, H, W)
+        if frames is not None:
+            assert mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (nc, H, W)
+        self._c("vf_windows_finish", _ptr(acc), _ptr(frames), _ptr(mask), _ptr(out), _ptr(inpaint), _ptr(full),
+                F, nc, H, W, L, fs, stride, stride_t)
+
     # ---- Torch7 image.scale and the loaders on it (vf_image.hip).  Frames: hwc -> uint8 N x H x W x C, else float N x C x H x W
     def image_scale(self, src, hwc, dst):
         """image.scale of N frames into dst (float N x C x h x w, contiguous)."""

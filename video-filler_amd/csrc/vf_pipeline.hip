@@ -3,7 +3,9 @@
 //     (train.lua:284-298 centre hole; datavid/donkey_folder.lua:135-189 crop / mask / fill / hflip / [0,1] -> [-1,1]),
 //     written straight into the NHWC buffers the kernels read;
 //   * the whole-image inference tile loop of test_vid_wholeim.lua:159-205 (gather fineSize tiles of the padded
-//     planar clip into ONE NHWC batch, scatter the net's output tiles back), incl. its per-tile vertical-flip rule.
+//     planar clip into ONE NHWC batch, scatter the net's output tiles back), incl. its per-tile vertical-flip rule;
+//   * the same loop for clips of any size and length: overlapped windows in y, x and t, gathered in chunks and blended
+//     with integer weights in a fixed order.
 // Every kernel is one pass: each output element is written once, each input element read at most once per output
 // that needs it.  Threads run along the NHWC channel axis (fastest) so the stores are fully coalesced; the planar
 // side is read in C strided streams that stay in L2 (the planes are a few MB).
@@ -119,6 +121,127 @@ __global__ void k_tiles_scatter(const float* __restrict__ tiles, float* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Overlapped, blended inference windows (tests/window_blend_ref.py is the rule).  One axis of the plan:
+// `count` windows of `size` samples over n samples, window i at min(i * stride, n - size) — regular origins and, where the
+// last regular window ends before n, one clamped to the end.  The origins are this closed form of three integers the
+// host has checked, so no table travels to the device and nothing unchecked is ever an address.  2 stride >= size: a sample
+// has at most two regular covers and the clamped one.
+struct WinAxis {
+  int n, size, stride, count;
+  __host__ __device__ int origin(int i) const { return i * stride < n - size ? i * stride : n - size; }
+  // integer taper at local coordinate l: 1, 2, ... up to r + 1 = size - stride + 1, and down again
+  __device__ int weight(int l) const { return min(min(l + 1, size - l), size - stride + 1); }
+  // the windows [lo, hi] that hold sample p
+  __device__ void cover(int p, int& lo, int& hi) const {
+    hi = min(p / stride, count - 1);
+    if (hi + 1 < count && origin(hi + 1) <= p) ++hi;      // the clamped last window starts inside its neighbour
+    lo = hi;
+    while (lo > 0 && origin(lo - 1) + size > p) --lo;
+  }
+  // sum of the weights of all covers of p: an integer of the geometry alone
+  __device__ int weight_sum(int p) const {
+    int lo, hi, s = 0;
+    cover(p, lo, hi);
+    for (int i = lo; i <= hi; ++i) s += weight(p - origin(i));
+    return s;
+  }
+};
+struct WinGeo {
+  WinAxis t, y, x;     // t: F frames in windows of L;  y, x: H, W in windows of fs
+  int nc;
+};
+
+// frames (F*nc) x H x W planar -> rows [w0, w0 + nw) of the window batch, NHWC nw x fs x fs x (L*nc): window
+// (it, iy, ix) has number (it*NY + iy)*NX + ix, channel k of its row is frame origin_t + k / nc, colour k % nc.
+__global__ void k_windows_gather(const float* __restrict__ frames, float* __restrict__ tiles, const WinGeo g, int w0, int nw) {
+  const int fs = g.y.size, Ck = g.t.size * g.nc, H = g.y.n, W = g.x.n;
+  const int64_t n = (int64_t)nw * fs * fs * Ck;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int k = (int)(i % Ck);
+    int64_t r = i / Ck;
+    const int x = (int)(r % fs);
+    r /= fs;
+    const int y = (int)(r % fs);
+    const int w = w0 + (int)(r / fs);
+    const int ix = w % g.x.count, iy = (w / g.x.count) % g.y.count, it = w / (g.x.count * g.y.count);
+    const int f = g.t.origin(it) + k / g.nc, c = k % g.nc;
+    tiles[i] = frames[((int64_t)(f * g.nc + c) * H + g.y.origin(iy) + y) * W + g.x.origin(ix) + x];
+  }
+}
+
+// Gather form of the blend: one thread owns one sample (frame f0 + .., colour, row y0 + .., column) of the accumulator
+// (F*nc) x H x W and adds the contributions of the windows [w0, w0 + nw) that hold it, in ascending window number:
+// acc = fadd(acc, fmul(float(w), v)), two roundings.  Chunks are launched in ascending order on one stream, so every sample
+// sees all its covers in ascending number whatever the chunk size.  No atomics.  The launch spans frames [f0, f0 + nf) and
+// rows [y0, y0 + ny): what the chunk's windows can touch.  Threads run along colour, then x: the NHWC rows are read in
+// whole runs of nc floats per pixel and each colour plane is touched in runs of blockDim / nc columns.
+__global__ void k_windows_accumulate(const float* __restrict__ tiles, float* __restrict__ acc, const WinGeo g, int w0, int nw,
+                                     int f0, int nf, int y0, int ny) {
+  const int fs = g.y.size, nc = g.nc, Ck = g.t.size * nc, H = g.y.n, W = g.x.n;
+  const int64_t n = (int64_t)nf * ny * W * nc;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % nc);
+    int64_t r = i / nc;
+    const int x = (int)(r % W);
+    r /= W;
+    const int y = y0 + (int)(r % ny);
+    const int f = f0 + (int)(r / ny);
+    int tl, th, yl, yh, xl, xh;
+    g.t.cover(f, tl, th);
+    g.y.cover(y, yl, yh);
+    g.x.cover(x, xl, xh);
+    float* dst = acc + ((int64_t)(f * nc + c) * H + y) * W + x;
+    float a = 0.f;
+    bool any = false;
+    for (int it = tl; it <= th; ++it) {
+      const int lt = f - g.t.origin(it), wt = g.t.weight(lt);
+      for (int iy = yl; iy <= yh; ++iy) {
+        const int ly = y - g.y.origin(iy), wy = wt * g.y.weight(ly);
+        for (int ix = xl; ix <= xh; ++ix) {
+          const int w = (it * g.y.count + iy) * g.x.count + ix - w0;
+          if (w < 0 || w >= nw) continue;
+          const int lx = x - g.x.origin(ix);
+          if (!any) {
+            a = *dst;
+            any = true;
+          }
+          const float v = tiles[(((int64_t)w * fs + ly) * fs + lx) * Ck + lt * nc + c];
+          a = __fadd_rn(a, __fmul_rn((float)(wy * g.x.weight(lx)), v));
+        }
+      }
+    }
+    if (any) *dst = a;
+  }
+}
+
+// out = fdiv(acc, float(sum of weights)); then, with frames given, the masked paste of test_vid_wholeim.lua:214-220 (mask:
+// nc x H x W Byte, non-zero = hole) and add(1):mul(0.5) (:222-224) on all three results, as vf_masked_compose and
+// vf_scale_shift(0.5, 0.5) compute them.  Planar throughout, x fastest.
+__global__ void k_windows_finish(const float* __restrict__ acc, const float* __restrict__ frames, const unsigned char* __restrict__ mask,
+                                 float* __restrict__ out, float* __restrict__ inpaint, float* __restrict__ full, const WinGeo g) {
+  const int nc = g.nc, H = g.y.n, W = g.x.n;
+  const int64_t n = (int64_t)g.t.n * nc * H * W;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % W);
+    int64_t r = i / W;
+    const int y = (int)(r % H);
+    r /= H;
+    const int c = (int)(r % nc), f = (int)(r / nc);
+    const int s = g.t.weight_sum(f) * g.y.weight_sum(y) * g.x.weight_sum(x);
+    const float o = __fdiv_rn(acc[i], (float)s);
+    if (!frames) {
+      out[i] = o;
+      continue;
+    }
+    const float fr = frames[i];
+    const float p = mask[((int64_t)c * H + y) * W + x] != 0 ? o : fr;
+    out[i] = __fadd_rn(__fmul_rn(o, 0.5f), 0.5f);
+    inpaint[i] = __fadd_rn(__fmul_rn(p, 0.5f), 0.5f);
+    full[i] = __fadd_rn(__fmul_rn(fr, 0.5f), 0.5f);
+  }
+}
+
 }  // namespace
 
 VF_API int vf_center_prepare(vf_ctx* ctx, const float* batch_nchw, float* ctx_nhwc, float* center_nhwc,
@@ -178,6 +301,86 @@ VF_API int vf_tiles_scatter(vf_ctx* ctx, const float* tiles, float* out, int gro
   const int64_t n = (int64_t)groups * nc * H * W;
   VfProf prof(ctx, "tiles_scatter", 0.0, 8.0 * (double)n);
   hipLaunchKernelGGL(k_tiles_scatter, dim3(pgrid(n)), dim3(256), 0, ctx->stream, tiles, out, groups, nc, H, W, fs, vflip);
+  VF_LAUNCH_CHECK();
+  return 0;
+}
+
+// One axis of a window plan, checked: n >= size, 1 <= stride <= size, 2 stride >= size.  nname, sname and stname are the caller's
+// names of n, size and stride, for the message.
+static int windows_axis(const char* who, const char* nname, const char* sname, const char* stname, int n, int size, int stride,
+                        WinAxis* a) {
+  VF_REQUIRE(size >= 1, "%s: %s=%d must be >= 1", who, sname, size);
+  VF_REQUIRE(n >= size, "%s: %s=%d is smaller than a window (%s=%d); nothing is padded", who, nname, n, sname, size);
+  VF_REQUIRE(stride >= 1 && stride <= size, "%s: %s=%d must lie in [1, %s=%d]", who, stname, stride, sname, size);
+  VF_REQUIRE(2 * (int64_t)stride >= size, "%s: %s=%d: 2 %s must be >= %s=%d (an overlap of at most half a window)", who, stname,
+             stride, stname, sname, size);
+  a->n = n; a->size = size; a->stride = stride;
+  a->count = (n - size) / stride + 1 + ((n - size) % stride != 0 ? 1 : 0);
+  return 0;
+}
+static int windows_geo(const char* who, int F, int nc, int H, int W, int L, int fs, int stride, int stride_t, WinGeo* g) {
+  VF_REQUIRE(nc >= 1, "%s: nc=%d must be >= 1", who, nc);
+  if (int e = windows_axis(who, "F", "inputLen", "stride_t", F, L, stride_t, &g->t)) return e;
+  if (int e = windows_axis(who, "H", "fineSize", "stride", H, fs, stride, &g->y)) return e;
+  if (int e = windows_axis(who, "W", "fineSize", "stride", W, fs, stride, &g->x)) return e;
+  g->nc = nc;
+  // a sample has at most 3 covers per axis, each of weight <= r + 1: weights and their sums stay exact in float
+  const int64_t bound = 27 * (int64_t)(fs - stride + 1) * (fs - stride + 1) * (L - stride_t + 1);
+  VF_REQUIRE(bound < (1 << 24), "%s: stride=%d, stride_t=%d: weight sums up to %lld are not exact in float", who, stride, stride_t,
+             (long long)bound);
+  VF_REQUIRE((int64_t)g->t.count * g->y.count * g->x.count < INT32_MAX && (int64_t)F * nc < INT32_MAX && (int64_t)L * nc < INT32_MAX,
+             "%s: the clip (F=%d, nc=%d, inputLen=%d) has too many windows or planes to number in 32 bits", who, F, nc, L);
+  return 0;
+}
+static int windows_chunk(const char* who, const WinGeo& g, int w0, int nw) {
+  const int64_t NW = (int64_t)g.t.count * g.y.count * g.x.count;
+  VF_REQUIRE(w0 >= 0 && nw >= 1 && (int64_t)w0 + nw <= NW, "%s: windows [w0=%d, +nw=%d) leave the plan's %lld", who, w0, nw, (long long)NW);
+  return 0;
+}
+VF_API int vf_windows_gather(vf_ctx* ctx, const float* frames, float* tiles, int F, int nc, int H, int W, int inputLen, int fs,
+                             int stride, int stride_t, int w0, int nw) {
+  WinGeo g;
+  if (int e = windows_geo("vf_windows_gather", F, nc, H, W, inputLen, fs, stride, stride_t, &g)) return e;
+  if (int e = windows_chunk("vf_windows_gather", g, w0, nw)) return e;
+  VF_REQUIRE(frames && tiles, "vf_windows_gather: frames and tiles are required");
+  const int64_t n = (int64_t)nw * inputLen * nc * fs * fs;
+  VfProf prof(ctx, "windows_gather", 0.0, 8.0 * (double)n);
+  hipLaunchKernelGGL(k_windows_gather, dim3(pgrid(n)), dim3(256), 0, ctx->stream, frames, tiles, g, w0, nw);
+  VF_LAUNCH_CHECK();
+  return 0;
+}
+VF_API int vf_windows_accumulate(vf_ctx* ctx, const float* tiles, float* acc, int F, int nc, int H, int W, int inputLen, int fs,
+                                 int stride, int stride_t, int w0, int nw) {
+  WinGeo g;
+  if (int e = windows_geo("vf_windows_accumulate", F, nc, H, W, inputLen, fs, stride, stride_t, &g)) return e;
+  if (int e = windows_chunk("vf_windows_accumulate", g, w0, nw)) return e;
+  VF_REQUIRE(tiles && acc, "vf_windows_accumulate: tiles and acc are required");
+  // the frames, and for a chunk inside one temporal window the rows, that the chunk's windows touch
+  const int per_t = g.y.count * g.x.count, w1 = w0 + nw - 1;
+  const int it0 = w0 / per_t, it1 = w1 / per_t;
+  const int f0 = g.t.origin(it0), nf = g.t.origin(it1) + inputLen - f0;
+  int y0 = 0, ny = H;
+  if (it0 == it1) {
+    y0 = g.y.origin((w0 % per_t) / g.x.count);
+    ny = g.y.origin((w1 % per_t) / g.x.count) + fs - y0;
+  }
+  const int64_t n = (int64_t)nf * nc * ny * W;
+  VfProf prof(ctx, "windows_accumulate", 0.0, 4.0 * (double)nw * inputLen * nc * fs * fs + 8.0 * (double)n);
+  hipLaunchKernelGGL(k_windows_accumulate, dim3(pgrid(n)), dim3(256), 0, ctx->stream, tiles, acc, g, w0, nw, f0, nf, y0, ny);
+  VF_LAUNCH_CHECK();
+  return 0;
+}
+VF_API int vf_windows_finish(vf_ctx* ctx, const float* acc, const float* frames, const unsigned char* mask, float* out,
+                             float* inpaint, float* full, int F, int nc, int H, int W, int inputLen, int fs, int stride,
+                             int stride_t) {
+  WinGeo g;
+  if (int e = windows_geo("vf_windows_finish", F, nc, H, W, inputLen, fs, stride, stride_t, &g)) return e;
+  VF_REQUIRE(acc && out, "vf_windows_finish: acc and out are required");
+  VF_REQUIRE(frames ? (mask && inpaint && full) : (!mask && !inpaint && !full),
+             "vf_windows_finish: frames, mask, inpaint and full go together (all for the paste and the [0,1] mapping, or none)");
+  const int64_t n = (int64_t)F * nc * H * W;
+  VfProf prof(ctx, "windows_finish", 0.0, (frames ? 21.0 : 8.0) * (double)n);
+  hipLaunchKernelGGL(k_windows_finish, dim3(pgrid(n)), dim3(256), 0, ctx->stream, acc, frames, mask, out, inpaint, full, g);
   VF_LAUNCH_CHECK();
   return 0;
 }

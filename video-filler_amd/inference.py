@@ -5,6 +5,8 @@ The generator runs in evaluate() mode (BatchNorm uses its running statistics), s
 whole-image loop — one net:forward per 128x128 tile in the reference (test_vid_wholeim.lua:159-205) — becomes ONE
 forward over all tiles: `vf_tiles_gather` builds the NHWC batch (incl. the script's vertical-flip rule for the first
 three tiles of the top row), `vf_tiles_scatter` writes the output tiles back into the planar frames.
+`WindowedInpainter` is that loop for clips of any size and length: windows that overlap in y, x and t, blended on the
+device.
 """
 import math
 
@@ -123,6 +125,97 @@ class WholeImageInpainter:
         for t in (outImages, inpaint, fullv):         # :222-224
             B.scale_shift(t, 0.5, 0.5)
         return outImages, inpaint, fullv.view(predLen, nc, H, W)
+
+
+# ------------------------------------------------------------------------- overlapped, blended windows
+def window_origins(n, size, stride):
+    """Where the windows of one axis start: 0, stride, 2 stride, ... while a window of `size` fits into n samples, and one
+    more at n - size if the last of them ends before n.  Nothing is padded.  ValueError, naming the argument, for n < size,
+    stride outside [1, size], or 2 stride < size (an overlap of more than half a window: more than three covers)."""
+    n, size, stride = int(n), int(size), int(stride)
+    if size < 1:
+        raise ValueError("window_origins: size=%d must be >= 1" % size)
+    if n < size:
+        raise ValueError("window_origins: n=%d is smaller than the window size=%d; nothing is padded" % (n, size))
+    if not 1 <= stride <= size:
+        raise ValueError("window_origins: stride=%d must lie in [1, size=%d]" % (stride, size))
+    if 2 * stride < size:
+        raise ValueError("window_origins: stride=%d: 2 stride must be >= size=%d (an overlap of at most half a window)" % (stride, size))
+    o = list(range(0, n - size + 1, stride))
+    if o[-1] + size < n:
+        o.append(n - size)
+    return o
+
+
+def window_weights(size, stride):
+    """The integer taper of a window along one axis: w(i) = min(i + 1, size - i, r + 1), r = size - stride.  Two regular
+    neighbours sum to r + 1 wherever they overlap; r = 0 gives 1 everywhere."""
+    window_origins(size, size, stride)           # the same refusals
+    r = int(size) - int(stride)
+    return [min(i + 1, size - i, r + 1) for i in range(int(size))]
+
+
+class WindowedInpainter:
+    """Whole clips of any size and length through a fineSize generator: windows of inputLen frames x fineSize x fineSize
+    that overlap in y, x (stride) and t (stride_t; default inputLen, no temporal overlap), every window one batch row, the
+    outputs blended with integer tapered weights in a fixed order (tests/window_blend_ref.py is the
+    rule).  No padding, no seams at tile borders, no vertical-flip rule.  Windows go through the net in chunks of at most
+    max_tiles, so device memory beyond the clip and its results is one accumulator and one chunk in and out, and the result
+    does not depend on max_tiles by a bit.  The initializer-net (netI) path of WholeImageInpainter is not offered here."""
+
+    def __init__(self, net, inputLen=1, fineSize=128, nc=3, stride=96, stride_t=None, max_tiles=64):
+        self.net, self.L, self.fs, self.nc = net, int(inputLen), int(fineSize), int(nc)
+        self.stride = int(stride)
+        self.stride_t = self.L if stride_t is None else int(stride_t)
+        self.max_tiles = int(max_tiles)
+        if self.max_tiles < 1:
+            raise ValueError("WindowedInpainter: max_tiles=%d must be >= 1" % self.max_tiles)
+        try:
+            window_weights(self.fs, self.stride)
+        except ValueError as e:
+            raise ValueError("WindowedInpainter: stride=%d does not fit fineSize=%d (%s)" % (self.stride, self.fs, e)) from None
+        try:
+            window_weights(self.L, self.stride_t)
+        except ValueError as e:
+            raise ValueError("WindowedInpainter: stride_t=%d does not fit inputLen=%d (%s)" % (self.stride_t, self.L, e)) from None
+        net.evaluate()
+
+    def plan(self, F, H, W):
+        """(ot, oy, ox): the origins of the windows of an F-frame H x W clip.  ValueError for a clip smaller than a window."""
+        for name, n, size in (("F", F, self.L), ("H", H, self.fs), ("W", W, self.fs)):
+            if n < size:
+                raise ValueError("WindowedInpainter: frames: %s=%d is smaller than a window (%d); nothing is padded" % (name, n, size))
+        return (window_origins(F, self.L, self.stride_t), window_origins(H, self.fs, self.stride),
+                window_origins(W, self.fs, self.stride))
+
+    def __call__(self, frames, mask):
+        """frames: F x nc x H x W in [-1,1], already mask-filled (load_whole_frames(...) cropped to [:inh, :inw]), F >=
+        inputLen and H, W >= fineSize; mask: nc x H x W Byte, non-zero = hole.  Returns (outImages, inpaintImages,
+        fullImages) in [0,1], each F x nc x H x W: what WholeImageInpainter returns, for save_frames, save_apngs, save_gifs
+        and evaluate_frames."""
+        B = get_backend()
+        x = B.from_host(torch.as_tensor(frames)).float().contiguous()
+        if x.dim() != 4 or x.shape[1] != self.nc:
+            raise ValueError("WindowedInpainter: frames are F x nc=%d x H x W, got %s" % (self.nc, tuple(x.shape)))
+        F, nc, H, W = x.shape
+        m = B.from_host(torch.as_tensor(mask)).contiguous()
+        if m.dtype != torch.uint8 or tuple(m.shape) != (nc, H, W):
+            raise ValueError("WindowedInpainter: mask is a Byte tensor nc x H x W = %s, got %s %s" % ((nc, H, W), m.dtype, tuple(m.shape)))
+        ot, oy, ox = self.plan(F, H, W)
+        NW = len(ot) * len(oy) * len(ox)
+        geo = (self.L, self.fs, self.stride, self.stride_t)
+        acc = B.zeros(F, nc, H, W)
+        tiles = nhwc_empty(min(self.max_tiles, NW), self.L * nc, self.fs, self.fs, x.device)
+        for w0 in range(0, NW, self.max_tiles):
+            chunk = tiles[:min(self.max_tiles, NW - w0)]
+            B.windows_gather(x, chunk, geo, w0)
+            out_tiles = to_nhwc(self.net.forward(chunk))
+            assert tuple(out_tiles.shape) == tuple(chunk.shape), \
+                "the net returns %s for a batch %s: it must give inputLen * nc channels of fineSize x fineSize" % (tuple(out_tiles.shape), tuple(chunk.shape))
+            B.windows_accumulate(out_tiles, acc, geo, w0)
+        outImages, inpaint, fullv = torch.empty_like(acc), torch.empty_like(acc), torch.empty_like(acc)
+        B.windows_finish(acc, geo, outImages, x, m, inpaint, fullv)
+        return outImages, inpaint, fullv
 
 
 def _write_files(paths, blobs):

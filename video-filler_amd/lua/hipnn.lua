@@ -136,6 +136,9 @@ int vf_center_prepare(vf_ctx*, const float* batch_nchw, float* ctx_nhwc, float* 
 int vf_clip_prepare(vf_ctx*, const float* clip, const float* mask, float* full, float* masked, float* maskout, int C, int iH, int iW, int fs, int w1, int h1, int flip, float mask_value, int nblocks, int block_size, const int* tlx, const int* tly);
 int vf_tiles_gather(vf_ctx*, const float* full, float* tiles, int groups, int nc, int H, int W, int fs, const unsigned char* vflip);
 int vf_tiles_scatter(vf_ctx*, const float* tiles, float* out, int groups, int nc, int H, int W, int fs, const unsigned char* vflip);
+int vf_windows_gather(vf_ctx*, const float* frames, float* tiles, int F, int nc, int H, int W, int inputLen, int fs, int stride, int stride_t, int w0, int nw);
+int vf_windows_accumulate(vf_ctx*, const float* tiles, float* acc, int F, int nc, int H, int W, int inputLen, int fs, int stride, int stride_t, int w0, int nw);
+int vf_windows_finish(vf_ctx*, const float* acc, const float* frames, const unsigned char* mask, float* out, float* inpaint, float* full, int F, int nc, int H, int W, int inputLen, int fs, int stride, int stride_t);
 int vf_image_scale(vf_ctx*, const void* src, int src_layout, float* dst, int N, int C, int H, int W, int height, int width);
 int vf_image_scale_u8(vf_ctx*, const unsigned char* src, unsigned char* dst, int N, int C, int H, int W, int height, int width);
 int vf_image_hook2d(vf_ctx*, const void* src, int src_layout, float* out, int C, int H, int W, int height, int width, int fs, int w1, int h1, int flip);
